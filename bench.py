@@ -9,6 +9,12 @@ run()), inputs already resident in HBM.  Metric: result ciphertexts per second, 
   python bench.py --gpus 1 --steps K --warmup W            (N=1: config C3 of BASELINE.json)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (config C4)
 
+A plain run sets up, warms up, times exactly K steps (one block; --repeats R times R blocks of K steps and reports the median
+block) and prints the result line.  Everything else the benchmark measures runs with --full: the per-kernel HIP-event passes
+(`kernels`, `roofline`), one query at a time and three query slots in flight, the reference's timer placement with the query
+in host memory, the projected strong scaling, the end-to-end PSI, the CPU baseline, and at N > 1 the steps with the queries
+already resident on every rank.  --dump-outputs DIR writes the result ciphertexts of the last timed step (dump_outputs()).
+
 Multi-GPU (BASELINE config C4): bin layers are independent, so the b = 14 bin layers of the C3 database are
 split over the ranks (strong scaling, the default for N > 1; speed-up is capped at b / ceil(b / N)); the only collective
 is the RCCL gather of the result ciphertexts to rank 0.  --scaling weak gives every rank its own b layers instead.
@@ -251,7 +257,8 @@ def synthetic_operator(pie, cc, cfg, b_local, rng, device_inputs):
 
 
 WARM_SECONDS = 0.3   # warm-up of the timed region by TIME: clocks, caches, lazily created queues (whatever --warmup says)
-REPEATS = 15         # timed blocks of exactly --steps steps each; the median block is reported
+REPEATS = 15         # timed blocks of exactly --steps steps each of the --full comparison legs; the median block is reported
+DUMP_RESIDUES = 1 << 21   # --dump-outputs writes at most this many result residues (two float64 files of 16 MiB each)
 
 
 def median(v):
@@ -597,7 +604,23 @@ def reference_timer(torch, op, idx, minus, b, iters, device, more_ops=(), run_st
                     "ciphertexts (%.1f MiB) are back in host memory" % (idx_h.shape[0] * idx_h.shape[1] + 1, mib, b, b * minus_h.nbytes / 2**20)}
 
 
-def main():
+def dump_outputs(outdir, res, limit=DUMP_RESIDUES):
+    """--dump-outputs: the result ciphertexts a caller of the timed path receives from its last step, res = [b][queries][2][L][N]
+    residues (uint64, each below its 60-bit prime), written exactly as two float64 arrays: residue = hi * 2^30 + lo
+    (result_hi.npy, result_lo.npy, both [b][queries][2][L][n]).  When there are more than `limit` residues, every polynomial
+    keeps the same n coefficient positions, a fixed seeded sample (result_positions.npy; all N positions otherwise)."""
+    res = np.ascontiguousarray(res).view(np.uint64)
+    N = res.shape[-1]
+    keep = min(N, max(1, limit // (res.size // N)))
+    pos = np.arange(N) if keep == N else np.sort(np.random.default_rng(0).choice(N, keep, replace=False))
+    s = res[..., pos]
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "result_hi.npy"), (s >> np.uint64(30)).astype(np.float64))
+    np.save(os.path.join(outdir, "result_lo.npy"), (s & np.uint64((1 << 30) - 1)).astype(np.float64))
+    np.save(os.path.join(outdir, "result_positions.npy"), pos.astype(np.float64))
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -616,9 +639,17 @@ def main():
     ap.add_argument("--transform-slots", type=int, default=None,
                     help="cap on the persistent transform grids (workgroups); default: every slot on one GPU, 32 fewer (16 CUs left to RCCL) for N > 1")
     ap.add_argument("--no-ref-timer", action="store_true", help="skip the host-inputs (reference timer placement) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every further measurement: per-kernel passes, one query at a time, three query slots, "
+                         "the reference timer placement, projected strong scaling, end-to-end PSI, CPU baseline, and at N > 1 the "
+                         "steps with the queries resident on every rank.  The headline stays one block of --steps steps as in a "
+                         "plain run (--repeats 15: the median of 15 blocks, the method of rounds 3-5); the legs take %d blocks"
+                         % REPEATS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result ciphertexts of the last timed step to DIR/*.npy (float64, exact; see dump_outputs())")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only the timed region and the per-kernel passes: no further legs (for profiler runs, whose per-kernel "
-                         "averages should see one launch shape per kernel)")
+                    help="implies --full, without its further legs: the timed region and the per-kernel passes only (for profiler "
+                         "runs, whose per-kernel averages should see one launch shape per kernel)")
     ap.add_argument("--graph", action="store_true", help="run() as one captured hipGraph (piehip_set_graph)")
     ap.add_argument("--in-flight", type=int, default=0,
                     help="queries in flight: query slots (own stream + workspace, one shared database: piehip_attach_database) that "
@@ -636,15 +667,23 @@ def main():
                          "over gloo (host-staged).  The timing means nothing; the line is marked")
     ap.add_argument("--force-collective", action="store_true",
                     help="rehearsal: run the RCCL gather path even with one rank (launch under torch.distributed.run)")
-    ap.add_argument("--repeats", type=int, default=REPEATS, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps; the median block is reported (default: the headline one block, so that "
+                         "--steps is the number of timed steps; the --full comparison legs %d)" % REPEATS)
     ap.add_argument("--warm-seconds", type=float, default=WARM_SECONDS, help="minimum warm-up time before the timed blocks")
     ap.add_argument("--query-dist", default="auto", choices=["auto", "broadcast", "scatter_gather", "none"],
                     help="N > 1: how the per-query inputs travel from rank 0 to the ranks inside every step (auto: time both, keep "
                          "the faster); none: every rank already holds them")
     ap.add_argument("--query-source", default="hbm", choices=["hbm", "host"],
                     help="N > 1: rank 0's copy of the query is resident in HBM (as at N = 1) or in page-locked host memory")
-    args = ap.parse_args()
-    if args.timed_only:
+    args = ap.parse_args(argv)
+    args.full = args.full or args.timed_only
+    return args
+
+
+def main():
+    args = parse_args()
+    if args.timed_only or not args.full:
         args.no_cpu_baseline = args.no_e2e = args.no_projection = args.no_ref_timer = True
 
     # stdout carries exactly one JSON line: libraries that print banners to fd 1 (RCCL's version block) go to stderr
@@ -729,13 +768,19 @@ def main():
     cc.set_run_streams(run_streams)
     cc.set_graph(args.graph)
     slots = [(cc, op, stream, idx, minus)]
-    # (one GPU: two further slots exist in any case -- the legs after the timed region use them -- but only the first
+    # (one GPU with --full: two further slots exist in any case -- the legs after the timed region use them -- but only the first
     # `in_flight` take steps)
-    n_slots = max(in_flight, 3) if (batching and not use_dist and op is not None) else in_flight
+    n_slots_full = max(in_flight, 3) if (batching and not use_dist and op is not None) else in_flight
+    n_slots = n_slots_full if args.full else in_flight
     if n_slots > 1 and op is not None:
         slots += make_query_slots(torch, pie, cc, op, (N, L, t, K, E), n_slots, device, local_rank, gen, args.streams or 1)
     elif n_slots > 1:   # a rank without bin layers still takes part in every slot's collective
         slots += [(None, None, torch.cuda.Stream(device), None, None) for _ in range(1, n_slots)]
+    for _ in range(max(n_slots, 1), n_slots_full):
+        # a plain run does not make the slots only the --full legs use, but draws their queries all the same: the timed region's
+        # inputs (the batch's further queries come next from `gen`) are the same with and without --full
+        uniform_limbs(torch, (K, E, 2), cc.q, N, device, gen)
+        uniform_limbs(torch, (2,), cc.q, N, device, gen)
     extra_inputs = []
     if batch > 1:
         for c_, o_, st_, i_, m_ in slots[:in_flight]:
@@ -864,7 +909,8 @@ def main():
         return float(tt.item())
 
     # Warm-up: at least --warmup steps and at least WARM_SECONDS of them (a 20-step block is 6 ms of GPU time; clocks, caches and
-    # the lazily created queues of every slot need longer than that), then REPEATS timed blocks of exactly --steps steps.
+    # the lazily created queues of every slot need longer than that), then one timed block of exactly --steps steps (--repeats
+    # blocks if given).
     def run_blocks():
         t_w = time.perf_counter()
         while True:
@@ -874,7 +920,7 @@ def main():
             if agree(time.perf_counter() - t_w, dist.ReduceOp.MIN if dist else None) >= args.warm_seconds:
                 break
         out_ = []
-        for _ in range(max(1, args.repeats)):
+        for _ in range(max(1, args.repeats or 1)):
             finish()
             t0 = time.perf_counter()
             for _ in range(args.steps):
@@ -885,7 +931,7 @@ def main():
 
     # The timed region.  N = 1: the queries are resident in HBM when a step starts.  N > 1: they are resident in RANK 0's HBM (the
     # rank that holds the client's socket, BatchedFHEPSIServer.cpp:94-99) and every step distributes its queries to all ranks -- the
-    # line's `value`; the steps are first timed with the queries already on every rank (`queries_resident_on_every_rank`).
+    # line's `value`; with --full the steps are first timed with the queries already on every rank (`queries_resident_on_every_rank`).
     # (CPython's cyclic garbage collector stays off from here to the end of the measurements: a full collection of this process takes
     # ~40 ms -- 65 steps of the timed region -- and fires by allocation count wherever the Python harness happens to be;
     # profiles/r05/host_stream_slow_leg_is_python_gc.txt.  The product is the C library; --keep-gc leaves the collector alone.)
@@ -893,8 +939,7 @@ def main():
         import gc
         gc.collect()
         gc.disable()
-    blocks = run_blocks()
-    ms_per_step = median(blocks)
+    blocks = run_blocks() if (args.full or not (rgs and qdist_kind)) else None
     dist_blocks = None
     if rgs and qdist_kind:
         for i_, rg_ in enumerate(rgs):
@@ -905,13 +950,23 @@ def main():
                 qb.set_query_device(flat_q)
             rg_.query, rg_.query_split = qb, q_split
         dist_blocks = run_blocks()
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed step receives: its slot's result list (N > 1: the rows gathered to rank 0)
+        # in the layout [bin layer][query] of the gathered rows and of the library
+        last = (nstep[0] - 1) % in_flight
+        if rgs:
+            res = rgs[last].rows((rgs[last].i - 1) & 1).cpu().numpy().view(np.uint64).reshape(b_total, batch, 2, L, N)
+        else:
+            res = slots[last][1].getResultList()    # a query batch comes back as [query][bin layer]
+            res = res.transpose(1, 0, 2, 3, 4) if batch > 1 else res[:, None]
+        dump_outputs(args.dump_outputs, res)
 
     # per-kernel times of the same run(), HIP events on the launch stream (separate, untimed passes).  These passes are
     # serial (one stream): with the default two queues a kernel shares the chip with the other queue's kernels and its
     # duration says nothing about the kernel itself.  `bench.py --streams 1` runs the timed region the same way.
     roofline = None
     kernels = {}
-    if op is not None and rank == 0:
+    if op is not None and rank == 0 and args.full:
         cc.set_run_streams(1)
         # warm, then every recorded pass runs straight behind an unrecorded one (the device does not idle in between);
         # per kernel class the MEDIAN pass is reported
@@ -969,7 +1024,7 @@ def main():
         # the steps with the queries already resident on every rank are reported beside it (`queries_resident_on_every_rank`).
         # (r04 had the two the other way round: ADVICE r04.)
         resident_blocks, blocks = blocks, dist_blocks
-        ms_per_step = median(blocks)
+    ms_per_step = median(blocks)
     if rank == 0:
         value = batch * b_total / (ms_per_step * 1e-3)
         cname = "C4 (C3's bin layers over %d GPUs)" % world if (world > 1 and scaling == "strong" and args.config == "C3") else args.config
@@ -977,7 +1032,7 @@ def main():
             "metric": "server PIE ciphertexts/sec", "value": value, "unit": "ciphertexts/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": scaling if world > 1 else "n/a",
             "repeats": len(blocks), "ms_per_step_min": min(blocks), "ms_per_step_max": max(blocks),
-            "timing": "median of %d blocks of exactly %d steps, each bracketed by barrier + synchronize, after >= %d steps and >= %.2f s "
+            "timing": "median of %d block(s) of exactly %d steps, each bracketed by barrier + synchronize, after >= %d steps and >= %.2f s "
                       "of warm-up" % (len(blocks), args.steps, args.warmup, args.warm_seconds),
             "vs_baseline": None, "dtype": "u64", "data": "synthetic",
             "python_gc": "left on (--keep-gc)" if args.keep_gc else "off during the measurements (a harness pause, not the product's: see bench.py)",
@@ -991,8 +1046,8 @@ def main():
                                       "rank 0, one communicator per query slot and direction%s"
                                       % ("gloo (rehearsal)" if args.rehearse_on_one_gpu else "rccl", qdist_kind or "NO distribution",
                                          args.query_source, args.collective,
-                                         "; the same steps with the queries resident on every rank: queries_resident_on_every_rank" if dist_blocks else
-                                         " (queries resident on every rank)")) if use_dist else "none",
+                                         "; the same steps with the queries resident on every rank: queries_resident_on_every_rank" if resident_blocks
+                                         else "" if dist_blocks else " (queries resident on every rank)")) if use_dist else "none",
                        "rccl_ranks": (dist.get_world_size() if dist else 1), "backend": (dist.get_backend() if dist else "none"),
                        "transform_slots": {"cap": tcap, "device": tdev},
                        "query_distribution_s": qdist_times,
@@ -1008,7 +1063,7 @@ def main():
                              "ref_schedule_GBps_per_gpu": batch * alg_bytes_run(dict(cfg, b=b_local)) / (ms_per_step * 1e-3) / 1e9,
                              "ref_schedule_bytes_over_time_frac": batch * alg_bytes_run(dict(cfg, b=b_local)) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
                              "note": "bytes of the reference's unfused schedule / measured time / 8 TB/s; not measured HBM traffic"},
-            "roofline": roofline, "kernels": kernels,
+            **({"roofline": roofline, "kernels": kernels} if args.full else {}),
         }
         if resident_blocks:
             rms = median(resident_blocks)
@@ -1019,17 +1074,18 @@ def main():
                 "what": "the same steps WITHOUT the per-query distribution: every step's %d quer%s already resident in every rank's HBM "
                         "when the step starts.  No shipped server works like that (the C++ sharded server broadcasts inside its online "
                         "timer); `value` above has the distribution inside every step" % (batch, "y" if batch == 1 else "ies")}
-        if world == 1 and op is not None and (in_flight > 1 or batch > 1) and not args.bins_per_rank and not args.timed_only:
+        leg_repeats = args.repeats or REPEATS
+        if world == 1 and op is not None and (in_flight > 1 or batch > 1) and not args.bins_per_rank and args.full and not args.timed_only:
             # the same steps with one query at a time (one slot, one query per run(), the library's default of two queues)
             cc.set_run_streams(args.streams)
-            one_ms = time_runs(op, args.steps, args.warmup, lambda: torch.cuda.synchronize(device), repeats=args.repeats, warm_seconds=0.15)
+            one_ms = time_runs(op, args.steps, args.warmup, lambda: torch.cuda.synchronize(device), repeats=leg_repeats, warm_seconds=0.15)
             line["one_query_at_a_time"] = {"ms_per_step": one_ms, "value": b_total / (one_ms * 1e-3), "run_streams": args.streams or 2}
             if len(slots) >= 3 and not (in_flight == 3 and batch == 1):
                 # ... and with three query slots in flight, one query per run() each, one queue per run(): the default timed
                 # region of rounds 2 and 3 before query batches
                 cc.set_run_streams(1)
                 tri_ms = time_slots([s_[1] for s_ in slots[:3]], args.steps, args.warmup, lambda: torch.cuda.synchronize(device),
-                                    repeats=args.repeats, warm_seconds=0.15)
+                                    repeats=leg_repeats, warm_seconds=0.15)
                 line["three_query_slots_in_flight"] = {"ms_per_step": tri_ms, "value": b_total / (tri_ms * 1e-3), "run_streams": 1,
                                                        "queries_per_step": 1}
             cc.set_run_streams(run_streams)

@@ -7,6 +7,6 @@ mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 i=0
 for grp in "$@"; do
   i=$((i+1))
-  timeout -k 10 180 rocprofv3 --output-format csv --pmc $grp -d $OUT/g$i -o g$i -- python3 $ROOT/bench.py --timed-only --streams 1 --steps 5 --warmup 1 --profile-steps 1 > /dev/null 2> $OUT/g$i.log || { echo "group $i failed or timed out: $grp"; exit 1; }
+  timeout -k 10 180 rocprofv3 --output-format csv --pmc $grp -d $OUT/g$i -o g$i -- python3 $ROOT/bench.py --full --timed-only --repeats 15 --streams 1 --steps 5 --warmup 1 --profile-steps 1 > /dev/null 2> $OUT/g$i.log || { echo "group $i failed or timed out: $grp"; exit 1; }
   echo "group $i done: $grp"
 done

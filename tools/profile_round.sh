@@ -14,7 +14,7 @@ OUT=$ROOT/gpurun_out/prof_$ROUND
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="$ROOT/bench.py --timed-only"
+BENCH="$ROOT/bench.py --full --timed-only --repeats 15"
 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/serial -o serial -- python3 $BENCH --streams 1 > $OUT/bench_serial.json 2> $OUT/serial.log
 echo "serial trace done"
 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/serial1 -o serial1 -- python3 $BENCH --streams 1 --in-flight 1 > $OUT/bench_serial1.json 2> $OUT/serial1.log
