@@ -43,7 +43,8 @@ typedef struct piehip_ctx *piehip_handle;
 
 /* 100 = rounds 1-4; 101 (round 5) adds piehip_profile_read_n, piehip_set/get_transform_slots, piehip_upload_turn_wait,
  * piehip_set_host_path_timing / piehip_host_path_times, piehip_rccl_wait / _abort / _agree; nothing of 100 changed its signature or
- * its meaning (piehip_profile_read keeps writing the twelve kernel classes of version 100). */
+ * its meaning (piehip_profile_read keeps writing the twelve kernel classes of version 100).  102 adds the seeded ciphertexts
+ * ("Seeded ciphertexts" below); nothing of 101 changed. */
 int piehip_version(void);
 const char *piehip_last_error(void);
 
@@ -365,6 +366,62 @@ int piehip_client_encrypt(piehip_handle h, const uint64_t *sk, const int64_t *sl
                           const uint64_t *seeds, uint64_t *out);
 /* Decrypt + GetPackedValue (BatchedFHEPSIClient.cpp:249-265): ct[nct][2][L][N] -> slots[nct][B] (centred) */
 int piehip_client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots);
+
+/* ---- seeded ciphertexts: the client uploads c0, the device regenerates c1 ---------------------------------------------------
+ * A secret-key ciphertext (c0, c1) = (-a s + e + round(Q m / t), a) -- how the reference client encrypts every query ciphertext
+ * (BatchedFHEPSIClient.cpp:156,166) and builds its EvalMult key (:91) -- carries a uniform polynomial a that does not depend on the
+ * message.  Sent as a 32-byte seed instead, it halves the query: a C3 query is 14.5 MiB of c0 instead of 29 MiB.
+ * Format (a wire format; both sides must agree bit for bit).  A seed stands for a[L][N] in the EVALUATION word order of this ABI (the
+ * array piehip_client_encrypt puts into the c1 half; no transform, no permutation).  For limb l (index into the handle's chain
+ * q_0..q_{L-1}) and chunk c (0 <= c < ceil(N / 10)):
+ *     msg = "PIEHIP-A" || seed[32] || u32le(l) || u32le(c)                   48 bytes
+ *     out = SHAKE128(msg), first 160 bytes                                    FIPS 202: one Keccak-f[1600]
+ *     a[l][10 c + t] = (bytes 16 t .. 16 t + 15 of out, little-endian) mod q_l,   t = 0..9, 10 c + t < N
+ * (128 bits reduced modulo a prime < 2^61: statistical distance < 2^-67 per coefficient, no rejection.)
+ *   seeded ciphertext     c0[L][N] + seed[32]
+ *   seeded EvalMult key   evk0[L][L][N] (the first component of each of the L rows) + seeds[L][32], one per row
+ * SECURITY: seeds must be distinct and drawn from a CSPRNG (32 fresh random bytes per ciphertext / key row).  A repeated seed repeats
+ * a, and two ciphertexts with the same a and the same key give away the difference of their messages and noise.  Seeding is sound for
+ * SECRET-KEY encryption only (what the reference client does); a public-key ciphertext's c1 is not uniform and cannot be seeded.
+ *   piehip_expand_uniform          n seeds -> out[n][L][N] (host memory); synchronous
+ *   piehip_expand_uniform_device   the same into caller-owned HBM d_out[n][L][N]; complete on return
+ *   piehip_stage_*_seeded_q        the seeded forms of piehip_stage_minus_q / _index_row_q / _index_ct_q: c0 only ([L][N];
+ *                                  a row is c0[E][L][N] + seeds[E][32]) goes up into the c0 half of the piece's slot, and the seed is
+ *                                  kept.  Order, batches and piehip_stage_reset follow the unseeded calls; seeded and unseeded pieces
+ *                                  mix freely in one staging sequence, and staging a piece again in either form replaces it (an
+ *                                  unseeded restage is never overwritten by an expansion).  piehip_run_staged queues ONE expansion
+ *                                  launch for every seeded piece of the batch, behind the pieces' uploads, in front of the
+ *                                  evaluation: the next handle's upload runs while it expands.
+ *   piehip_run_host_seeded(_async) exactly: piehip_stage_minus_seeded_q and piehip_stage_index_row_seeded_q for every query and row,
+ *                                  then piehip_run_staged; piehip_run_host_wait waits for it.  c0idx[nq][K][E][L][N],
+ *                                  idx_seeds[nq][K][E][32], c0minus[nq][L][N], minus_seeds[nq][32], results as piehip_run_host.
+ *                                  The page-locked arrays of piehip_host_buffers_q hold the c0 layouts (half of their size):
+ *                                  c0idx in `idx`, c0minus in `minus`.
+ *   piehip_load_relin_key_seeded(_q)   piehip_load_relin_key(_q) from evk0[L][L][N] + seeds[L][32]
+ *   piehip_client_encrypt_seeded   piehip_client_encrypt with a = expand(a_seeds[c]) and the noise drawn from noise_seeds[c];
+ *                                  writes c0[nct][L][N]
+ *   piehip_client_relin_keygen_seeded  piehip_client_relin_keygen with a_i = expand(a_seeds[i]), the noise drawn from `seed`;
+ *                                  writes evk0[L][L][N]
+ * Null seeds and positions outside the index matrix or the batch are PIEHIP_EINVAL before anything reaches the device.
+ * A sharded server's piehip_rccl_broadcast_query refuses (PIEHIP_ESTATE) a staged query with seeded pieces. */
+int piehip_expand_uniform(piehip_handle h, const uint8_t *seeds /*[n][32]*/, uint32_t n, uint64_t *out /*[n][L][N]*/);
+int piehip_expand_uniform_device(piehip_handle h, const uint8_t *seeds /*[n][32]*/, uint32_t n, void *d_out /*[n][L][N]*/);
+int piehip_stage_minus_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0 /*[L][N]*/, const uint8_t *seed /*[32]*/);
+int piehip_stage_index_row_seeded_q(piehip_handle h, uint32_t q, uint32_t row, const uint64_t *c0 /*[E][L][N]*/,
+                                    const uint8_t *seeds /*[E][32]*/);
+int piehip_stage_index_ct_seeded_q(piehip_handle h, uint32_t q, uint32_t row, uint32_t j, const uint64_t *c0 /*[L][N]*/,
+                                   const uint8_t *seed /*[32]*/);
+int piehip_run_host_seeded_async(piehip_handle h, const uint64_t *c0idx, const uint8_t *idx_seeds, const uint64_t *c0minus,
+                                 const uint8_t *minus_seeds, uint64_t *results);
+int piehip_run_host_seeded(piehip_handle h, const uint64_t *c0idx, const uint8_t *idx_seeds, const uint64_t *c0minus,
+                           const uint8_t *minus_seeds, uint64_t *results);
+int piehip_load_relin_key_seeded(piehip_handle h, const uint64_t *evk0 /*[L][L][N]*/, const uint8_t *seeds /*[L][32]*/);
+int piehip_load_relin_key_seeded_q(piehip_handle h, uint32_t q, const uint64_t *evk0, const uint8_t *seeds);
+int piehip_client_encrypt_seeded(piehip_handle h, const uint64_t *sk, const int64_t *slots, uint32_t nct, uint32_t B,
+                                 const uint64_t *noise_seeds /*[nct]*/, const uint8_t *a_seeds /*[nct][32]*/,
+                                 uint64_t *c0 /*[nct][L][N]*/);
+int piehip_client_relin_keygen_seeded(piehip_handle h, const uint64_t *sk, uint64_t seed, const uint8_t *a_seeds /*[L][32]*/,
+                                      uint64_t *evk0 /*[L][L][N]*/);
 
 /* ---- measurement ------------------------------------------------------------------------------
  * With profiling on, run() brackets every kernel launch with HIP events on the handle's stream.

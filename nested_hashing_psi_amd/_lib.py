@@ -6,6 +6,7 @@ import os
 from .build import LIB_PATH
 
 u64p = C.POINTER(C.c_uint64)
+u8p = C.POINTER(C.c_uint8)
 i64p = C.POINTER(C.c_int64)
 u32p = C.POINTER(C.c_uint32)
 i32p = C.POINTER(C.c_int32)
@@ -108,6 +109,17 @@ SYMBOLS = {
     "piehip_rccl_wait": (C.c_int, [C.c_void_p, C.c_uint32]),
     "piehip_rccl_abort": (C.c_int, [C.c_void_p]),
     "piehip_rccl_agree": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_uint32]),
+    "piehip_expand_uniform": (C.c_int, [C.c_void_p, u8p, C.c_uint32, u64p]),
+    "piehip_expand_uniform_device": (C.c_int, [C.c_void_p, u8p, C.c_uint32, C.c_void_p]),
+    "piehip_stage_minus_seeded_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p, u8p]),
+    "piehip_stage_index_row_seeded_q": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, u64p, u8p]),
+    "piehip_stage_index_ct_seeded_q": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u8p]),
+    "piehip_run_host_seeded_async": (C.c_int, [C.c_void_p, u64p, u8p, u64p, u8p, u64p]),
+    "piehip_run_host_seeded": (C.c_int, [C.c_void_p, u64p, u8p, u64p, u8p, u64p]),
+    "piehip_load_relin_key_seeded": (C.c_int, [C.c_void_p, u64p, u8p]),
+    "piehip_load_relin_key_seeded_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p, u8p]),
+    "piehip_client_encrypt_seeded": (C.c_int, [C.c_void_p, u64p, i64p, C.c_uint32, C.c_uint32, u64p, u8p, u64p]),
+    "piehip_client_relin_keygen_seeded": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u8p, u64p]),
 }
 
 _lib = None

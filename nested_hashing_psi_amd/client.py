@@ -5,10 +5,12 @@ the product is the server path.  Hashing of the (small) client set runs on the h
 generation, encryption and decryption run on the device through the C ABI (piehip_client_*).
 """
 import ctypes as C
+import hashlib
+import secrets
 
 import numpy as np
 
-from ._lib import i64p, lib, u64p
+from ._lib import i64p, lib, u8p, u64p
 from .pie import _check, _u64, tabulation_hash
 
 
@@ -18,6 +20,18 @@ def _out(shape, dtype):
     a = np.empty(shape, dtype=dtype)
     a.fill(0)
     return a
+
+
+def harness_seeds(base, n, tag):
+    """n 32-byte seeds of seeded ciphertexts / key rows, as an [n][32] uint8 array.  base=None: from the OS CSPRNG, as real use
+    must (seeds distinct and unpredictable: include/piehip.h).  An integer base derives them reproducibly -- SHA-256 of
+    (tag, base, i) -- for tests and benchmarks only: a client whose seeds can be guessed or repeat gives its queries away."""
+    if base is None:
+        return np.frombuffer(secrets.token_bytes(32 * n), dtype=np.uint8).reshape(n, 32).copy()
+    out = np.empty((n, 32), dtype=np.uint8)
+    for i in range(n):
+        out[i] = np.frombuffer(hashlib.sha256(b"piehip-harness-seed|%s|%d|%d" % (tag.encode(), int(base), i)).digest(), dtype=np.uint8)
+    return out
 
 
 PLAINTEXT_MODULI = {16: 65537, 32: 4296540161, 40: 1099579260929, 48: 281474981953537}
@@ -56,6 +70,18 @@ class BatchedFHEPSIClient:
         _check(lib().piehip_client_relin_keygen(cc._h, self.sk.ctypes.data_as(u64p), evalKeySeed,
                                                 self.evalMultKey.ctypes.data_as(u64p)))
         return self.evalMultKey
+
+    # -- the same with a seeded EvalMult key: evk0[L][L][N] + one seed per row (include/piehip.h "Seeded ciphertexts").
+    #    aSeedBase: harness_seeds (None = CSPRNG)
+    def runSetUpPhaseSeeded(self, keySeed=11, evalKeySeed=12, aSeedBase=None):
+        cc = self.cc
+        self.sk = _out((cc.L, cc.N), np.uint64)
+        _check(lib().piehip_client_keygen(cc._h, keySeed, self.sk.ctypes.data_as(u64p)))
+        self.evalMultKeySeeds = harness_seeds(aSeedBase, cc.L, "evk")
+        self.evalMultKey0 = _out((cc.L, cc.L, cc.N), np.uint64)
+        _check(lib().piehip_client_relin_keygen_seeded(cc._h, self.sk.ctypes.data_as(u64p), evalKeySeed,
+                                                       self.evalMultKeySeeds.ctypes.data_as(u8p), self.evalMultKey0.ctypes.data_as(u64p)))
+        return self.evalMultKey0, self.evalMultKeySeeds
 
     # -- EvalSumKeyGen + EvalRotateKeyGen of the rotation-based sibling (SimpleFHEPSIClient.cpp:80-89): keys for the
     #    rotations 2^r (r < ceil(log2 b)) and -1 .. -(b-1) that FHEHIPPIE::run needs
@@ -101,6 +127,35 @@ class BatchedFHEPSIClient:
         self.encryptedMinusElements = cts[0]
         self.batchedEncryptedIndexMatrix = cts[1:].reshape(K, E, 2, self.cc.L, self.cc.N)
         return self.encryptedMinusElements, self.batchedEncryptedIndexMatrix
+
+    def _query_vectors(self, clientSet):
+        self.clientTable = self._hash_client_set(clientSet)
+        k, e, K, E, B = self.k, self.e, self.K, self.E, self.B
+        flat = self.clientTable.reshape(-1)
+        index = np.zeros((K, E, B), dtype=np.int64)
+        minus = np.ones(B, dtype=np.int64)
+        occ = np.nonzero(flat)[0]
+        if len(occ):
+            minus[occ] = -flat[occ].astype(np.int64)
+            for hf in range(K):
+                hi = tabulation_hash(self.hashSeed, k + K, k + hf, flat[occ]) % np.uint64(E)
+                index[hf, hi.astype(np.int64), occ] = 1
+        self.plainIndex, self.plainMinus = index, minus
+        return np.concatenate([minus.reshape(1, B), index.reshape(K * E, B)])
+
+    # -- the offline phase with seeded ciphertexts: c0 halves + one 32-byte seed per ciphertext; the server expands the c1 halves.
+    #    Returns (minus c0 [L][N], minus seed [32], index c0 [K][E][L][N], index seeds [K][E][32]).  encSeedBase draws the noise as in
+    #    runOfflinePhase; aSeedBase: harness_seeds (None = CSPRNG)
+    def runOfflinePhaseSeeded(self, clientSet, encSeedBase=100, aSeedBase=None):
+        K, E, cc = self.K, self.E, self.cc
+        vecs = np.ascontiguousarray(self._query_vectors(clientSet), dtype=np.int64)
+        n = vecs.shape[0]
+        noise = np.array([encSeedBase - 1] + [encSeedBase + i for i in range(K * E)], dtype=np.uint64)
+        aseeds = harness_seeds(aSeedBase, n, "query")
+        c0 = _out((n, cc.L, cc.N), np.uint64)
+        _check(lib().piehip_client_encrypt_seeded(cc._h, self.sk.ctypes.data_as(u64p), vecs.ctypes.data_as(i64p), n, vecs.shape[1],
+                                                  noise.ctypes.data_as(u64p), aseeds.ctypes.data_as(u8p), c0.ctypes.data_as(u64p)))
+        return c0[0], aseeds[0].copy(), c0[1:].reshape(K, E, cc.L, cc.N), aseeds[1:].reshape(K, E, 32).copy()
 
     def _encrypt(self, vecs, seeds):
         cc = self.cc

@@ -210,4 +210,14 @@ void launch_dec_round(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *xs, u
 void launch_decode_gather(const DevConsts *dc, u32 N, u32 M, const u64 *u, const u32 *slot_pos, u32 B, int64_t *slots, u32 nct,
                           hipStream_t st);
 
+// Seeded ciphertexts (kernels_seed.hip): job j regenerates the uniform polynomial of its 32-byte seed, a[L][N] in EVALUATION word
+// order, into dst[L][N] (e.g. the c1 half of a ciphertext inside an index matrix [K][E][2][L][N]).  jobs is a device array;
+// more than SEED_MAX_JOBS_PER_LAUNCH jobs take several launches.
+struct SeedJob {
+    u64 *dst;
+    u32 seed[8];   // the seed's 32 bytes as little-endian words
+};
+static const u32 SEED_MAX_JOBS_PER_LAUNCH = 65535;
+void launch_expand_uniform(const DevConsts *dc, u32 N, u32 L, const SeedJob *jobs, u32 njobs, hipStream_t st);
+
 }  // namespace piehip

@@ -206,7 +206,7 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
 // =================================================================================================
 extern "C" {
 
-int piehip_version(void) { return 101; }   // 101: piehip_profile_read_n, piehip_set_transform_slots, piehip_upload_turn_wait, piehip_rccl_abort
+int piehip_version(void) { return 102; }   // 101: piehip_profile_read_n, piehip_set_transform_slots, piehip_upload_turn_wait, piehip_rccl_abort; 102: seeded ciphertexts
 const char *piehip_last_error(void) { return g_err.c_str(); }
 const char *piehip_kernel_name(int k) { return (k >= 0 && k < PIEHIP_NKERNELS) ? KNAMES[k] : "?"; }
 
@@ -1105,6 +1105,51 @@ int piehip_load_relin_key_q(piehip_handle h, uint32_t q, const uint64_t *evk)
     HIPCHK(hipStreamSynchronize(h->stream));
     h->evkq_loaded |= 1u << q;
     return PIEHIP_OK;
+}
+
+// Seeded EvalMult keys: the L first components come from the host, the L second ones are expanded from their seeds on the device;
+// the assembled key then loads as an unseeded one (offline phase: the key crosses the link twice, half of it each way).
+static int assemble_seeded_key(piehip_ctx *h, const uint64_t *evk0, const uint8_t *seeds, std::vector<u64> &key)
+{
+    const u32 L = h->hp.L;
+    const size_t LN = h->LN();
+    key.resize((size_t)L * 2 * LN);
+    u64 *d = nullptr;
+    int rc = dev_alloc(&d, (size_t)L * LN);
+    if (rc) return rc;
+    std::vector<SeedJob> jobs(L);
+    for (u32 i = 0; i < L; i++) jobs[i] = seed_job(d + (size_t)i * LN, seeds + (size_t)i * 32);
+    rc = expand_seeded_sync(h, jobs);
+    for (u32 i = 0; i < L && !rc; i++) {
+        memcpy(&key[(size_t)i * 2 * LN], evk0 + (size_t)i * LN, LN * sizeof(u64));
+        if (hipMemcpy(&key[((size_t)i * 2 + 1) * LN], d + (size_t)i * LN, LN * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(PIEHIP_EHIP, "load_relin_key_seeded: copy-out failed");
+    }
+    dev_free(&d);
+    return rc;
+}
+
+int piehip_load_relin_key_seeded(piehip_handle h, const uint64_t *evk0, const uint8_t *seeds)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!evk0 || !seeds) return fail(PIEHIP_EINVAL, "null evk0 or seeds");
+    if (h->db_borrowed) return fail(PIEHIP_EINVAL, "this handle uses another handle's key and database (piehip_attach_database)");
+    if (h->db_borrowers) return fail(PIEHIP_ESTATE, "the key cannot be reloaded while other handles are attached to this one");
+    NEED(h);
+    std::vector<u64> key;
+    int rc = assemble_seeded_key(h, evk0, seeds, key);
+    return rc ? rc : piehip_load_relin_key(h, key.data());
+}
+
+int piehip_load_relin_key_seeded_q(piehip_handle h, uint32_t q, const uint64_t *evk0, const uint8_t *seeds)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!evk0 || !seeds) return fail(PIEHIP_EINVAL, "null evk0 or seeds");
+    if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
+    NEED(h);
+    std::vector<u64> key;
+    int rc = assemble_seeded_key(h, evk0, seeds, key);
+    return rc ? rc : piehip_load_relin_key_q(h, q, key.data());
 }
 
 // Queues of a run().  The default is two when the handle evaluates enough bin layers to fill the chip twice over; below that

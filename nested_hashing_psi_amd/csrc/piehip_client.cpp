@@ -86,7 +86,9 @@ int piehip_client_keygen(piehip_handle h, uint64_t seed, uint64_t *sk)
 
 // BV key-switching key from s_from to sk (oracle: ks_keygen): row i = (e_i - a_i s + [j == i] s_from, a_i).
 // g == 0: s_from = s^2 (EvalMultKeyGen); otherwise s_from = s(X^g) (EvalAtIndexKeyGen / EvalSumKeyGen).
-static int client_ks_keygen(piehip_ctx *h, const uint64_t *sk, uint32_t g, uint64_t seed, uint64_t *out)
+// a_seeds == null: every a_i is sampled on the host from `seed` (before its e_i) and out is the key [L][2][L][N]; otherwise a_i is
+// the expansion of a_seeds[i] (kernels_seed.hip), `seed` draws the e_i only, and out is the first components [L][L][N].
+static int client_ks_keygen(piehip_ctx *h, const uint64_t *sk, uint32_t g, uint64_t seed, const uint8_t *a_seeds, uint64_t *out)
 {
     HIPCHK(hipSetDevice(h->device));
     const u32 N = h->hp.N, L = h->hp.L;
@@ -95,7 +97,7 @@ static int client_ks_keygen(piehip_ctx *h, const uint64_t *sk, uint32_t g, uint6
     std::vector<u64> ks((size_t)L * 2 * LN), e((size_t)L * LN);
     std::vector<int32_t> ev(N);
     for (u32 i = 0; i < L; i++) {
-        sample_uniform(r, h->hp, &ks[((size_t)i * 2 + 1) * LN]);
+        if (!a_seeds) sample_uniform(r, h->hp, &ks[((size_t)i * 2 + 1) * LN]);
         sample_error(r, N, ev.data());
         for (u32 l = 0; l < L; l++)
             for (u32 j = 0; j < N; j++) e[(size_t)i * LN + (size_t)l * N + j] = ev[j] >= 0 ? (u64)ev[j] : h->hp.moduli[l] - (u64)(-ev[j]);
@@ -106,7 +108,14 @@ static int client_ks_keygen(piehip_ctx *h, const uint64_t *sk, uint32_t g, uint6
     TMPGET(d_sk, LN);
     TMPGET(d_s2, LN);
     TMPGET(d_mapw, (N + 1) / 2 + 1);
-    HIPCHK(hipMemcpy(d_ks, ks.data(), ks.size() * sizeof(u64), hipMemcpyHostToDevice));
+    if (a_seeds) {
+        std::vector<SeedJob> jobs(L);
+        for (u32 i = 0; i < L; i++) jobs[i] = seed_job(d_ks + ((size_t)i * 2 + 1) * LN, a_seeds + (size_t)i * 32);
+        int rc = expand_seeded_sync(h, jobs);
+        if (rc) return rc;
+    } else {
+        HIPCHK(hipMemcpy(d_ks, ks.data(), ks.size() * sizeof(u64), hipMemcpyHostToDevice));
+    }
     HIPCHK(hipMemcpy(d_e, e.data(), e.size() * sizeof(u64), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_sk, sk, LN * sizeof(u64), hipMemcpyHostToDevice));
     launch_ntt(h->plan, d_e, L * L, 0, L, false, h->stream);
@@ -120,7 +129,11 @@ static int client_ks_keygen(piehip_ctx *h, const uint64_t *sk, uint32_t g, uint6
     launch_ks_finish(h->d_dc, N, L, d_e, d_sk, d_s2, d_ks, h->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, d_ks, ks.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    if (!a_seeds) {
+        HIPCHK(hipMemcpy(out, d_ks, ks.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    } else {
+        for (u32 i = 0; i < L; i++) HIPCHK(hipMemcpy(out + (size_t)i * LN, d_ks + (size_t)i * 2 * LN, LN * sizeof(u64), hipMemcpyDeviceToHost));
+    }
     return PIEHIP_OK;
 }
 
@@ -128,7 +141,15 @@ int piehip_client_relin_keygen(piehip_handle h, const uint64_t *sk, uint64_t see
 {
     NEED(h);
     if (!sk || !evk) return fail(PIEHIP_EINVAL, "null operand");
-    return client_ks_keygen(h, sk, 0, seed, evk);
+    return client_ks_keygen(h, sk, 0, seed, nullptr, evk);
+}
+
+int piehip_client_relin_keygen_seeded(piehip_handle h, const uint64_t *sk, uint64_t seed, const uint8_t *a_seeds, uint64_t *evk0)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!sk || !a_seeds || !evk0) return fail(PIEHIP_EINVAL, "null operand");
+    NEED(h);
+    return client_ks_keygen(h, sk, 0, seed, a_seeds, evk0);
 }
 
 int piehip_rotation_galois(piehip_handle h, int32_t index, uint32_t *g)
@@ -152,14 +173,14 @@ int piehip_client_rot_keygen(piehip_handle h, const uint64_t *sk, int32_t index,
     int rc = piehip_rotation_galois(h, index, &g);
     if (rc) return rc;
     if (g == 1) return fail(PIEHIP_EINVAL, "rotation index is a multiple of the row length");
-    return client_ks_keygen(h, sk, g, seed, rk);
+    return client_ks_keygen(h, sk, g, seed, nullptr, rk);
 }
 
-int piehip_client_encrypt(piehip_handle h, const uint64_t *sk, const int64_t *slots, uint32_t nct, uint32_t B,
-                          const uint64_t *seeds, uint64_t *out)
+// a_seeds == null: every ciphertext draws a (uniform), then e, from seeds[c] on the host and out is [nct][2][L][N]; otherwise a is
+// the expansion of a_seeds[c] (kernels_seed.hip), seeds[c] draws e only, and out is the c0 halves [nct][L][N]
+static int client_encrypt(piehip_ctx *h, const uint64_t *sk, const int64_t *slots, uint32_t nct, uint32_t B, const uint64_t *seeds,
+                          const uint8_t *a_seeds, uint64_t *out)
 {
-    NEED(h);
-    if (!sk || !slots || !seeds || !out || !nct) return fail(PIEHIP_EINVAL, "null operand");
     if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size exceeds the ring dimension");
     HIPCHK(hipSetDevice(h->device));
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M;
@@ -168,7 +189,7 @@ int piehip_client_encrypt(piehip_handle h, const uint64_t *sk, const int64_t *sl
     for (size_t i = 0; i < (size_t)nct * B; i++)
         if ((u64)(slots[i] < 0 ? -slots[i] : slots[i]) >= t) return fail(PIEHIP_EINVAL, "slot value out of range for the plaintext modulus");
     // host staging, not zero-filled (the sampling threads touch their own parts): a[nct][L][N] and e[nct][N]
-    std::unique_ptr<u64[]> a_host(new u64[(size_t)nct * LN]);
+    std::unique_ptr<u64[]> a_host(a_seeds ? nullptr : new u64[(size_t)nct * LN]);
     std::unique_ptr<int32_t[]> ev(new int32_t[(size_t)nct * N]);
     {
         // every ciphertext has its own seed and draws a (uniform), then e, as a sequential client would: the ciphertexts are
@@ -176,7 +197,7 @@ int piehip_client_encrypt(piehip_handle h, const uint64_t *sk, const int64_t *sl
         auto sample = [&](u32 c0, u32 c1) {
             for (u32 c = c0; c < c1; c++) {
                 HostRng r(seeds[c]);
-                sample_uniform(r, h->hp, &a_host[(size_t)c * LN]);
+                if (!a_seeds) sample_uniform(r, h->hp, &a_host[(size_t)c * LN]);
                 sample_error(r, N, &ev[(size_t)c * N]);
             }
         };
@@ -196,7 +217,14 @@ int piehip_client_encrypt(piehip_handle h, const uint64_t *sk, const int64_t *sl
     TMPGET(d_em, (size_t)nct * LN);
     TMPGET(d_evw, ((size_t)nct * N + 1) / 2 + 1);
     TMPGET(d_a, (size_t)nct * LN);
-    HIPCHK(hipMemcpy(d_a, a_host.get(), (size_t)nct * LN * sizeof(u64), hipMemcpyHostToDevice));  // enc_finish puts it into the c1 halves
+    if (a_seeds) {
+        std::vector<SeedJob> jobs(nct);
+        for (u32 c = 0; c < nct; c++) jobs[c] = seed_job(d_a + (size_t)c * LN, a_seeds + (size_t)c * 32);
+        int rc = expand_seeded_sync(h, jobs);
+        if (rc) return rc;
+    } else {
+        HIPCHK(hipMemcpy(d_a, a_host.get(), (size_t)nct * LN * sizeof(u64), hipMemcpyHostToDevice));  // enc_finish puts it into the c1 halves
+    }
     HIPCHK(hipMemcpy(d_sk, sk, LN * sizeof(u64), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_slotsw, slots, sizeof(int64_t) * (size_t)nct * B, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_evw, ev.get(), sizeof(int32_t) * (size_t)nct * N, hipMemcpyHostToDevice));
@@ -207,8 +235,29 @@ int piehip_client_encrypt(piehip_handle h, const uint64_t *sk, const int64_t *sl
     launch_enc_finish(h->d_dc, N, L, d_em, d_sk, d_a, d_out, nct, h->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, d_out, ct_words * sizeof(u64), hipMemcpyDeviceToHost));
+    if (!a_seeds) {
+        HIPCHK(hipMemcpy(out, d_out, ct_words * sizeof(u64), hipMemcpyDeviceToHost));
+    } else {
+        for (u32 c = 0; c < nct; c++) HIPCHK(hipMemcpy(out + (size_t)c * LN, d_out + (size_t)c * 2 * LN, LN * sizeof(u64), hipMemcpyDeviceToHost));
+    }
     return PIEHIP_OK;
+}
+
+int piehip_client_encrypt(piehip_handle h, const uint64_t *sk, const int64_t *slots, uint32_t nct, uint32_t B,
+                          const uint64_t *seeds, uint64_t *out)
+{
+    NEED(h);
+    if (!sk || !slots || !seeds || !out || !nct) return fail(PIEHIP_EINVAL, "null operand");
+    return client_encrypt(h, sk, slots, nct, B, seeds, nullptr, out);
+}
+
+int piehip_client_encrypt_seeded(piehip_handle h, const uint64_t *sk, const int64_t *slots, uint32_t nct, uint32_t B,
+                                 const uint64_t *noise_seeds, const uint8_t *a_seeds, uint64_t *c0)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!sk || !slots || !noise_seeds || !a_seeds || !c0 || !nct) return fail(PIEHIP_EINVAL, "null operand");
+    NEED(h);
+    return client_encrypt(h, sk, slots, nct, B, noise_seeds, a_seeds, c0);
 }
 
 int piehip_client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots)

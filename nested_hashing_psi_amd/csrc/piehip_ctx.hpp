@@ -74,6 +74,10 @@ struct QueryStage {
     std::vector<bool> rows;                        // pieces on their way since the staging sequence began
     std::vector<bool> cts;                         // ... ciphertext by ciphertext (piehip_stage_index_ct_q), [K][E]
     bool minus = false;
+    // seeded pieces (piehip_stage_*_seeded_q): c0 is on its way, c1 is expanded from the seed at piehip_run_staged.
+    // Index p < K E: index ciphertext p = row E + j; index K E: the minus element.  Staging a piece unseeded clears its entry.
+    std::vector<bool> seeded;                      // [K E + 1]
+    std::vector<u32> seeds;                        // [K E + 1][8]: the 32-byte seeds as little-endian words
 };
 
 }  // namespace piehip
@@ -114,6 +118,11 @@ struct piehip_ctx {
     hipEvent_t hp_ev[3] = {nullptr, nullptr, nullptr};
     int hp_ev_state = 0;                          // 0 nothing recorded, 1 first piece, 2 handed over, 3 complete sequence recorded
     u64 *host_results = nullptr;                  // set while piehip_run_staged enqueues: every queue group downloads its slice there
+    // the one expansion launch of a staging sequence with seeded pieces: its job table goes up from a page-locked table with two
+    // halves (sequence s writes half s & 1 once sequence s - 2's copy has left it: piehip_host.cpp) into d_seed_jobs
+    piehip::SeedJob *pin_seed_jobs = nullptr;     // [2][seed_jobs_cap]
+    piehip::SeedJob *d_seed_jobs = nullptr;       // [seed_jobs_cap]
+    size_t seed_jobs_cap = 0;
     u64 *pin_res = nullptr;                       // [b][nq][2][L][N]
     size_t pin_idx_words = 0, pin_res_words = 0;
     piehip::DevConsts *d_dc = nullptr;
@@ -278,6 +287,11 @@ int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 
 // device input buffers of query q of the batch (owned copies: the host setters and the staged uploads write them)
 int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus);
 void free_host_path(piehip_ctx *h);   // piehip_host.cpp: page-locked staging
+// piehip_host.cpp: expand the seeded polynomials of `jobs` on the handle's stream and wait for them (client, keys, tests; the
+// staged path queues its expansion without waiting)
+int expand_seeded_sync(piehip_ctx *h, const std::vector<SeedJob> &jobs);
+SeedJob seed_job(u64 *dst, const uint8_t *seed);
+bool stage_has_seeded(const piehip_ctx *h);
 // queues of a run() and the bin layers each takes
 u32 run_queue_count(const piehip_ctx *h);
 int ensure_run_queues(piehip_ctx *h, u32 ng);

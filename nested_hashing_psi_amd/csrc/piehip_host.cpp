@@ -26,6 +26,14 @@
 //     when the stream's whole backlog is done (measured: the wait covered the other slot's evaluation and download too);
 //   * from a word in page-locked memory that a one-thread kernel, queued between the uploads and the evaluation, sets to the
 //     query's sequence number.  The staging host thread polls it.
+//
+// Seeded pieces (piehip_stage_*_seeded_q, piehip_run_host_seeded*).  A seeded piece uploads its c0 half only, into the c0 half of
+// its slot in the input buffers, and leaves its 32-byte seed with the handle.  piehip_run_staged queues ONE expansion launch for all
+// seeded pieces of the batch (kernels_seed.hip), behind the "uploads handed over" word and in front of the evaluation, on the same
+// in-order chain: the next handle's uploads may start while this one expands, and the expansion runs under them.  Its job table
+// (destination + seed per piece) goes up from a page-locked table with two halves; the staging sequence with sequence number s
+// fills half s & 1, after the word of this handle says that sequence s - 2 -- whose copy read that half -- has left host memory.
+// In a stream of queries that is long true; nothing waits for the device otherwise.
 #include "piehip_ctx.hpp"
 
 #include <chrono>
@@ -155,6 +163,10 @@ void free_host_path(piehip_ctx *h)
     }
     if (h->pin_res) (void)hipHostFree(h->pin_res);
     h->pin_res = nullptr;
+    if (h->pin_seed_jobs) (void)hipHostFree(h->pin_seed_jobs);
+    if (h->d_seed_jobs) (void)hipFree(h->d_seed_jobs);
+    h->pin_seed_jobs = h->d_seed_jobs = nullptr;
+    h->seed_jobs_cap = 0;
     for (hipEvent_t &e : h->hp_ev) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
@@ -194,8 +206,29 @@ static int stage_begin(piehip_ctx *h, u32 q)
         h->qstage[i].minus = false;
         h->qstage[i].rows.assign(h->K, false);
         h->qstage[i].cts.clear();
+        h->qstage[i].seeded.assign((size_t)h->K * h->E + 1, false);
+        h->qstage[i].seeds.resize(((size_t)h->K * h->E + 1) * 8);
     }
     return PIEHIP_OK;
+}
+
+// piece p of query q (p < K E: index ciphertext p; p = K E: the minus element) was staged seeded (seed != null) or in full
+static void mark_seeded(piehip_ctx *h, u32 q, size_t p, const uint8_t *seed)
+{
+    QueryStage &s = h->qstage[q];
+    s.seeded[p] = seed != nullptr;
+    if (seed) memcpy(&s.seeds[p * 8], seed, 32);
+}
+
+// ciphertext (row, j) of query q has been staged: row `row` is complete once all E of its ciphertexts are
+static void ct_staged(piehip_ctx *h, u32 q, u32 row, u32 j)
+{
+    QueryStage &s = h->qstage[q];
+    if (s.cts.size() != (size_t)h->K * h->E) s.cts.assign((size_t)h->K * h->E, false);
+    s.cts[(size_t)row * h->E + j] = true;
+    bool all = true;
+    for (u32 i = 0; i < h->E && all; i++) all = s.cts[(size_t)row * h->E + i];
+    if (all) s.rows[row] = true;
 }
 
 extern "C" {
@@ -253,6 +286,7 @@ int piehip_stage_minus_q(piehip_handle h, uint32_t q, const uint64_t *minus)
     if ((rc = query_input_buffers(h, q, &di, &dm))) return rc;
     HIPCHK(hipMemcpyAsync(dm, minus, 2 * h->LN() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     h->qstage[q].minus = true;
+    mark_seeded(h, q, (size_t)h->K * h->E, nullptr);
     return PIEHIP_OK;
 }
 
@@ -268,6 +302,7 @@ int piehip_stage_index_row_q(piehip_handle h, uint32_t q, uint32_t row, const ui
     const size_t words = (size_t)h->E * 2 * h->LN();
     HIPCHK(hipMemcpyAsync(di + (size_t)row * words, row_data, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     h->qstage[q].rows[row] = true;
+    for (u32 j = 0; j < h->E; j++) mark_seeded(h, q, (size_t)row * h->E + j, nullptr);
     return PIEHIP_OK;
 }
 
@@ -282,12 +317,62 @@ int piehip_stage_index_ct_q(piehip_handle h, uint32_t q, uint32_t row, uint32_t 
     if ((rc = query_input_buffers(h, q, &di, &dm))) return rc;
     const size_t words = 2 * h->LN();
     HIPCHK(hipMemcpyAsync(di + ((size_t)row * h->E + j) * words, ct, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    QueryStage &s = h->qstage[q];
-    if (s.cts.size() != (size_t)h->K * h->E) s.cts.assign((size_t)h->K * h->E, false);
-    s.cts[(size_t)row * h->E + j] = true;
-    bool all = true;
-    for (u32 i = 0; i < h->E && all; i++) all = s.cts[(size_t)row * h->E + i];
-    if (all) s.rows[row] = true;
+    mark_seeded(h, q, (size_t)row * h->E + j, nullptr);
+    ct_staged(h, q, row, j);
+    return PIEHIP_OK;
+}
+
+// Seeded pieces: the c0 half goes up into the c0 half of the piece's slot; the seed waits for piehip_run_staged.  Arguments are
+// checked before anything touches the device.
+static int seeded_args(piehip_ctx *h, u32 q, const void *c0, const void *seeds)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!c0 || !seeds) return fail(PIEHIP_EINVAL, "null input (c0 or seed)");
+    if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
+    return PIEHIP_OK;
+}
+
+int piehip_stage_minus_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0, const uint8_t *seed)
+{
+    int rc = seeded_args(h, q, c0, seed);
+    if (rc || (rc = stage_begin(h, q))) return rc;
+    u64 *di = nullptr, *dm = nullptr;
+    if ((rc = query_input_buffers(h, q, &di, &dm))) return rc;
+    HIPCHK(hipMemcpyAsync(dm, c0, h->LN() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    h->qstage[q].minus = true;
+    mark_seeded(h, q, (size_t)h->K * h->E, seed);
+    return PIEHIP_OK;
+}
+
+int piehip_stage_index_ct_seeded_q(piehip_handle h, uint32_t q, uint32_t row, uint32_t j, const uint64_t *c0, const uint8_t *seed)
+{
+    int rc = seeded_args(h, q, c0, seed);
+    if (rc) return rc;
+    if (row >= h->K || j >= h->E) return fail(PIEHIP_EINVAL, "stage_index_ct_seeded: position outside the [K][E] index matrix");
+    if ((rc = stage_begin(h, q))) return rc;
+    u64 *di = nullptr, *dm = nullptr;
+    if ((rc = query_input_buffers(h, q, &di, &dm))) return rc;
+    HIPCHK(hipMemcpyAsync(di + ((size_t)row * h->E + j) * 2 * h->LN(), c0, h->LN() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    mark_seeded(h, q, (size_t)row * h->E + j, seed);
+    ct_staged(h, q, row, j);
+    return PIEHIP_OK;
+}
+
+int piehip_stage_index_row_seeded_q(piehip_handle h, uint32_t q, uint32_t row, const uint64_t *c0, const uint8_t *seeds)
+{
+    int rc = seeded_args(h, q, c0, seeds);
+    if (rc) return rc;
+    if (row >= h->K) return fail(PIEHIP_EINVAL, "stage_index_row_seeded: the index matrix has one row per inner hash function");
+    if ((rc = stage_begin(h, q))) return rc;
+    u64 *di = nullptr, *dm = nullptr;
+    if ((rc = query_input_buffers(h, q, &di, &dm))) return rc;
+    // the E c0 halves in ONE strided copy (their slots are [2][L][N] apart): a copy command costs ~20 us of its own, and E of them
+    // per row made a seeded C3 batch upload as slowly as a full one (87 copies of 0.5 MiB vs 9 of 7 MiB)
+    const size_t LN = h->LN();
+    HIPCHK(hipMemcpy2DAsync(di + (size_t)row * h->E * 2 * LN, 2 * LN * sizeof(u64), c0, LN * sizeof(u64), LN * sizeof(u64), h->E,
+                            hipMemcpyHostToDevice, h->stream));
+    for (u32 j = 0; j < h->E; j++) mark_seeded(h, q, (size_t)row * h->E + j, seeds + (size_t)j * 32);
+    h->qstage[q].rows[row] = true;
     return PIEHIP_OK;
 }
 
@@ -302,9 +387,68 @@ int piehip_stage_reset(piehip_handle h)
         s.minus = false;
         s.rows.assign(s.rows.size(), false);
         s.cts.clear();
+        s.seeded.assign(s.seeded.size(), false);
     }
     return PIEHIP_OK;
 }
+
+}  // extern "C"
+
+bool piehip::stage_has_seeded(const piehip_ctx *h)
+{
+    for (u32 q = 0; q < h->nq; q++)
+        for (bool b : h->qstage[q].seeded)
+            if (b) return true;
+    return false;
+}
+
+// The job table of the staged seeded pieces goes up (on the handle's stream, behind their c0 halves) into d_seed_jobs; *njobs = 0
+// when nothing is seeded.  Half (up_seq + 1) & 1 of the page-locked table is written only once this handle's staging sequence
+// up_seq - 1, the last one that read it, has left host memory (its copy is in front of its hand-over word).
+static int queue_seed_jobs(piehip_ctx *h, size_t *njobs)
+{
+    *njobs = 0;
+    const size_t LN = h->LN(), per_q = (size_t)h->K * h->E + 1;
+    size_t n = 0;
+    for (u32 q = 0; q < h->nq; q++)
+        for (bool b : h->qstage[q].seeded) n += b;
+    if (!n) return PIEHIP_OK;
+    if (n > h->seed_jobs_cap) {
+        // (re)allocated at the first seeded query of a shape; hipFree / hipHostFree wait for whatever still reads the old tables
+        if (h->pin_seed_jobs) (void)hipHostFree(h->pin_seed_jobs);
+        if (h->d_seed_jobs) (void)hipFree(h->d_seed_jobs);
+        h->pin_seed_jobs = h->d_seed_jobs = nullptr;
+        h->seed_jobs_cap = 0;
+        const size_t cap = (size_t)h->nq * per_q;   // every piece of the batch
+        HIPCHK(hipHostMalloc((void **)&h->pin_seed_jobs, 2 * cap * sizeof(SeedJob), hipHostMallocPortable));
+        HIPCHK(hipMalloc((void **)&h->d_seed_jobs, cap * sizeof(SeedJob)));
+        h->seed_jobs_cap = cap;
+    }
+    const u64 seq = h->up_seq + 1;
+    if (seq >= 3) {
+        const auto t0 = std::chrono::steady_clock::now();
+        while (__atomic_load_n((const volatile u64 *)h->pin_up_flag, __ATOMIC_ACQUIRE) < seq - 2) {
+            std::this_thread::yield();
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5))
+                return fail(PIEHIP_EHIP, "run_staged: this handle's query before last has not left host memory after 5 s");
+        }
+    }
+    SeedJob *tab = h->pin_seed_jobs + (seq & 1) * h->seed_jobs_cap;
+    for (u32 q = 0; q < h->nq; q++) {
+        const QueryStage &s = h->qstage[q];
+        u64 *di = q ? h->bq_idx_own[q] : h->d_idx_own, *dm = q ? h->bq_minus_own[q] : h->d_minus_own;
+        for (size_t p = 0; p < per_q; p++) {
+            if (!s.seeded[p]) continue;
+            SeedJob &j = tab[(*njobs)++];
+            j.dst = (p + 1 < per_q ? di + p * 2 * LN : dm) + LN;   // the c1 half of the piece's slot
+            memcpy(j.seed, &s.seeds[p * 8], 32);
+        }
+    }
+    HIPCHK(hipMemcpyAsync(h->d_seed_jobs, tab, *njobs * sizeof(SeedJob), hipMemcpyHostToDevice, h->stream));
+    return PIEHIP_OK;
+}
+
+extern "C" {
 
 int piehip_run_staged(piehip_handle h, uint64_t *results)
 {
@@ -326,9 +470,15 @@ int piehip_run_staged(piehip_handle h, uint64_t *results)
     // the uploads are on the handle's stream and the run's queues start behind it (the inputs changed); every queue group's slice
     // of the result list leaves on that group's queue as soon as the group is done
     mark_dirty(h);
-    int rc = upload_handed_over(h);
+    size_t njobs = 0;
+    int rc = queue_seed_jobs(h, &njobs);   // the seeds' way up: one more upload, in front of the hand-over
     if (rc) return rc;
+    if ((rc = upload_handed_over(h))) return rc;
     if (h->hp_timing && h->hp_ev_state == 1 && hipEventRecord(h->hp_ev[1], h->stream) == hipSuccess) h->hp_ev_state = 2;
+    if (njobs) {
+        launch_expand_uniform(h->d_dc, h->hp.N, h->hp.L, h->d_seed_jobs, (u32)njobs, h->stream);
+        HIPCHK(hipGetLastError());
+    }
     h->host_results = results;
     rc = piehip_run_into(h, h->d_out);
     h->host_results = nullptr;
@@ -357,6 +507,35 @@ int piehip_run_host_async(piehip_handle h, const uint64_t *idx, const uint64_t *
         return rc;
     }
     return piehip_run_staged(h, results);
+}
+
+int piehip_run_host_seeded_async(piehip_handle h, const uint64_t *c0idx, const uint8_t *idx_seeds, const uint64_t *c0minus,
+                                 const uint8_t *minus_seeds, uint64_t *results)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!c0idx || !idx_seeds || !c0minus || !minus_seeds) return fail(PIEHIP_EINVAL, "null input");
+    if (h->K && !run_keys_loaded(h)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
+    h->stage_open = false;  // queries of its own: pieces staged earlier and never run are dropped
+    const size_t LN = h->LN(), row = (size_t)h->E * LN;
+    int rc = PIEHIP_OK;
+    for (u32 q = 0; q < h->nq && !rc; q++) rc = piehip_stage_minus_seeded_q(h, q, c0minus + (size_t)q * LN, minus_seeds + (size_t)q * 32);
+    for (u32 q = 0; q < h->nq && !rc; q++)
+        for (u32 hf = 0; hf < h->K && !rc; hf++) {
+            const size_t r = (size_t)q * h->K + hf;
+            rc = piehip_stage_index_row_seeded_q(h, q, hf, c0idx + r * row, idx_seeds + r * h->E * 32);
+        }
+    if (rc) {
+        h->stage_open = false;
+        return rc;
+    }
+    return piehip_run_staged(h, results);
+}
+
+int piehip_run_host_seeded(piehip_handle h, const uint64_t *c0idx, const uint8_t *idx_seeds, const uint64_t *c0minus,
+                           const uint8_t *minus_seeds, uint64_t *results)
+{
+    const int rc = piehip_run_host_seeded_async(h, c0idx, idx_seeds, c0minus, minus_seeds, results);
+    return rc ? rc : piehip_run_host_wait(h);
 }
 
 int piehip_run_host_wait(piehip_handle h)
@@ -399,6 +578,59 @@ int piehip_run_host(piehip_handle h, const uint64_t *idx, const uint64_t *minus,
 {
     const int rc = piehip_run_host_async(h, idx, minus, results);
     return rc ? rc : piehip_run_host_wait(h);
+}
+
+}  // extern "C"
+
+// ---- seeded polynomials outside the query path: clients, keys, tests --------------------------------------------------------------
+SeedJob piehip::seed_job(u64 *dst, const uint8_t *seed)
+{
+    SeedJob j;
+    j.dst = dst;
+    memcpy(j.seed, seed, 32);
+    return j;
+}
+
+int piehip::expand_seeded_sync(piehip_ctx *h, const std::vector<SeedJob> &jobs)
+{
+    if (jobs.empty()) return PIEHIP_OK;
+    HIPCHK(hipSetDevice(h->device));
+    Tmp tmp;
+    TMPGET(d_jobs, (jobs.size() * sizeof(SeedJob) + 7) / 8);
+    HIPCHK(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(SeedJob), hipMemcpyHostToDevice, h->stream));
+    launch_expand_uniform(h->d_dc, h->hp.N, h->hp.L, (const SeedJob *)d_jobs, (u32)jobs.size(), h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));   // before the job table is freed
+    return PIEHIP_OK;
+}
+
+extern "C" {
+
+int piehip_expand_uniform_device(piehip_handle h, const uint8_t *seeds, uint32_t n, void *d_out)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!seeds || !d_out) return fail(PIEHIP_EINVAL, "null seeds or output");
+    NEED(h);
+    std::vector<SeedJob> jobs(n);
+    for (u32 i = 0; i < n; i++) jobs[i] = seed_job((u64 *)d_out + (size_t)i * h->LN(), seeds + (size_t)i * 32);
+    return expand_seeded_sync(h, jobs);
+}
+
+int piehip_expand_uniform(piehip_handle h, const uint8_t *seeds, uint32_t n, uint64_t *out)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!seeds || !out) return fail(PIEHIP_EINVAL, "null seeds or output");
+    NEED(h);
+    if (!n) return PIEHIP_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t words = (size_t)n * h->LN();
+    u64 *d = nullptr;
+    int rc = dev_alloc(&d, words);
+    if (rc) return rc;
+    rc = piehip_expand_uniform_device(h, seeds, n, d);
+    if (!rc && hipMemcpy(out, d, words * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PIEHIP_EHIP, "expand_uniform: copy-out failed");
+    dev_free(&d);
+    return rc;
 }
 
 }  // extern "C"

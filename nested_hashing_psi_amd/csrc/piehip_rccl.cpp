@@ -378,6 +378,8 @@ int piehip_rccl_broadcast_query(piehip_handle h, int root)
     // so it is checked before anything is queued.
     if (h->comm_rank == root) {
         if (!h->stage_open) return fail(PIEHIP_ESTATE, "rccl_broadcast_query: the root has no staged query");
+        if (stage_has_seeded(h))   // the expansion is queued by piehip_run_staged, which a broadcast query never reaches
+            return fail(PIEHIP_ESTATE, "rccl_broadcast_query: seeded pieces are not distributed (stage full ciphertexts)");
         for (u32 q = 0; q < h->nq; q++) {
             if (!h->qstage[q].minus) return fail(PIEHIP_ESTATE, "rccl_broadcast_query: minus element not staged");
             for (u32 hf = 0; hf < h->K; hf++)

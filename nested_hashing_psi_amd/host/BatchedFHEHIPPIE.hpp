@@ -69,6 +69,8 @@ public:
 
     // InsertEvalMultKey / DeserializeEvalMultKey (BatchedFHEPSIServer.cpp:49): evk[L][2][L][N]
     void setEvalMultKey(const uint64_t *evk) { check(piehip_load_relin_key(h_, evk)); }
+    // the same from a seeded key (include/piehip.h "Seeded ciphertexts"): evk0[L][L][N] + seeds[L][32]
+    void setEvalMultKeySeeded(const uint64_t *evk0, const uint8_t *seeds) { check(piehip_load_relin_key_seeded(h_, evk0, seeds)); }
     uint64_t GetPlaintextModulus() const { return t_; }
     uint32_t ringDimension() const { return N_; }
     uint32_t towers() const { return L_; }
@@ -238,6 +240,20 @@ public:
         PieContext::check(piehip_stage_minus(cc.handle(), pinMinus));
         minusStaged = true;
     }
+    // Seeded ciphertexts (include/piehip.h "Seeded ciphertexts"): the deserialiser writes only c0 -- [L][N], the first half of
+    // indexStaging(h, j) / minusStaging() -- and hands over the ciphertext's 32-byte seed; run() expands the c1 halves on the device
+    void stageIndexCiphertextSeeded(uint32_t h, uint32_t j, const uint8_t *seed)
+    {
+        if (h >= K || j >= E) throw std::invalid_argument("index matrix position out of range");
+        PieContext::check(piehip_stage_index_ct_seeded_q(cc.handle(), 0, h, j, indexStaging(h, j), seed));
+        arrived++;
+        if (++rowCount[h] == E) rowsStaged++;
+    }
+    void stageMinusSeeded(const uint8_t *seed)
+    {
+        PieContext::check(piehip_stage_minus_seeded_q(cc.handle(), 0, pinMinus, seed));
+        minusStaged = true;
+    }
 
     friend class BatchedFHEHIPPIEQueryBatch;
 
@@ -290,6 +306,11 @@ public:
     // the EvalMult key of query q's client, evk[L][2][L][N] (BatchedFHEPSIServer.cpp:45-49); queries without one use the key
     // of the context the database lives on
     void setEvalMultKey(uint32_t q, const uint64_t *evk) { PieContext::check(piehip_load_relin_key_q(cc.handle(), q, evk)); }
+    // ... from a seeded key: evk0[L][L][N] + seeds[L][32]
+    void setEvalMultKeySeeded(uint32_t q, const uint64_t *evk0, const uint8_t *seeds)
+    {
+        PieContext::check(piehip_load_relin_key_seeded_q(cc.handle(), q, evk0, seeds));
+    }
 
     void setIndex(uint32_t q, std::vector<std::vector<LimbCt>> &&indexMatrix)  // [K][E] ciphertexts of query q
     {
@@ -339,6 +360,21 @@ public:
     {
         checkQuery(q);
         PieContext::check(piehip_stage_minus_q(cc.handle(), q, st[q].pinMinus));
+        st[q].minusStaged = true;
+    }
+    // seeded pieces: c0 [L][N] at the start of indexStaging(q, h, j) / minusStaging(q), plus the 32-byte seed (see BatchedFHEHIPPIE)
+    void stageIndexCiphertextSeeded(uint32_t q, uint32_t h, uint32_t j, const uint8_t *seed)
+    {
+        checkQuery(q);
+        if (h >= K || j >= E) throw std::invalid_argument("index matrix position out of range");
+        PieContext::check(piehip_stage_index_ct_seeded_q(cc.handle(), q, h, j, indexStaging(q, h, j), seed));
+        st[q].arrived++;
+        if (++st[q].rowCount[h] == E) st[q].rowsStaged++;
+    }
+    void stageMinusSeeded(uint32_t q, const uint8_t *seed)
+    {
+        checkQuery(q);
+        PieContext::check(piehip_stage_minus_seeded_q(cc.handle(), q, st[q].pinMinus, seed));
         st[q].minusStaged = true;
     }
 

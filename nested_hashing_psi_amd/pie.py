@@ -15,7 +15,7 @@ import secrets
 
 import numpy as np
 
-from ._lib import NKERNELS, f64p, i32p, i64p, lib, u32p, u64p
+from ._lib import NKERNELS, f64p, i32p, i64p, lib, u8p, u32p, u64p
 
 EINVAL, ESTATE, EHIP, ENOMEM, EHASH = -1, -2, -3, -4, -5
 
@@ -36,6 +36,20 @@ def _check(rc):
 def _u64(a):
     a = np.ascontiguousarray(a, dtype=np.uint64)
     return a, a.ctypes.data_as(u64p)
+
+
+def _seeds(seeds, shape):
+    """32-byte seeds as a contiguous uint8 array of shape shape + (32,) (bytes, a list of bytes or an array)"""
+    if isinstance(seeds, (bytes, bytearray)):
+        a = np.frombuffer(bytes(seeds), dtype=np.uint8)
+    elif isinstance(seeds, (list, tuple)) and seeds and isinstance(seeds[0], (bytes, bytearray)):
+        a = np.frombuffer(b"".join(bytes(x) for x in seeds), dtype=np.uint8)
+    else:
+        a = np.asarray(seeds, dtype=np.uint8)
+    a = np.ascontiguousarray(a)
+    if a.size != int(np.prod(shape, dtype=np.int64)) * 32:
+        raise ValueError("expected %s seeds of 32 bytes" % (shape,))
+    return a.reshape(tuple(shape) + (32,))
 
 
 def tabulation_hash(hash_seed, nfun, hf, x):
@@ -178,6 +192,30 @@ class PieContext:
             _check(lib().piehip_load_relin_key(self._h, ap))
         else:
             _check(lib().piehip_load_relin_key_q(self._h, int(query), ap))
+
+    # -- seeded ciphertexts (include/piehip.h "Seeded ciphertexts"): c1 = expand(seed)
+    def expand_uniform(self, seeds):
+        """the uniform polynomials a[n][L][N] (EVALUATION word order) of n 32-byte seeds, expanded on the device"""
+        sd = _seeds(seeds, (len(seeds) // 32 if isinstance(seeds, (bytes, bytearray)) else len(seeds),))
+        out = np.empty((sd.shape[0], self.L, self.N), dtype=np.uint64)
+        _check(lib().piehip_expand_uniform(self._h, sd.ctypes.data_as(u8p), sd.shape[0], out.ctypes.data_as(u64p)))
+        return out
+
+    def expand_uniform_device(self, seeds, d_out):
+        """the same into caller-owned HBM d_out[n][L][N] (a device address); complete on return"""
+        sd = _seeds(seeds, (len(seeds) // 32 if isinstance(seeds, (bytes, bytearray)) else len(seeds),))
+        _check(lib().piehip_expand_uniform_device(self._h, sd.ctypes.data_as(u8p), sd.shape[0], C.c_void_p(d_out)))
+
+    def load_relin_key_seeded(self, evk0, seeds, query=None):
+        """InsertEvalMultKey from a seeded key: evk0[L][L][N] (first components) + seeds[L][32] (second components)"""
+        a, ap = _u64(evk0)
+        if a.shape != (self.L, self.L, self.N):
+            raise ValueError("a seeded EvalMult key is evk0[L][L][N] + L seeds")
+        sd = _seeds(seeds, (self.L,))
+        if query is None:
+            _check(lib().piehip_load_relin_key_seeded(self._h, ap, sd.ctypes.data_as(u8p)))
+        else:
+            _check(lib().piehip_load_relin_key_seeded_q(self._h, int(query), ap, sd.ctypes.data_as(u8p)))
 
     # -- sharded server over RCCL behind the C ABI (piehip_rccl.cpp): what a C++ server calls; shard.py is the torch.distributed way
     def rccl_init(self, unique_id, nranks, rank):
@@ -463,6 +501,58 @@ class BatchedFHEHIPPIE:
         if ciphertext.dtype != np.uint64 or not ciphertext.flags.c_contiguous or ciphertext.shape != (2, self.cc.L, self.cc.N):
             raise ValueError("an index matrix entry is one contiguous uint64 ciphertext")
         _check(lib().piehip_stage_index_ct_q(self.cc._h, int(query), int(row), int(j), ciphertext.ctypes.data_as(u64p)))
+
+    # -- seeded pieces: c0 [L][N] + a 32-byte seed per ciphertext (include/piehip.h "Seeded ciphertexts")
+    def _c0(self, a, lead, what):
+        if a.dtype != np.uint64 or not a.flags.c_contiguous or a.shape != tuple(lead) + (self.cc.L, self.cc.N):
+            raise ValueError("%s must be contiguous uint64 c0 halves %s[L][N]" % (what, "".join("[%d]" % x for x in lead)))
+        return a.ctypes.data_as(u64p)
+
+    def stageMinusSeeded(self, c0, seed, query=0):
+        """start the upload of query `query`'s seeded minus element, c0 [L][N] (piehip_stage_minus_seeded_q)"""
+        sd = _seeds(seed, ())
+        _check(lib().piehip_stage_minus_seeded_q(self.cc._h, int(query), self._c0(c0, (), "the minus element"), sd.ctypes.data_as(u8p)))
+
+    def stageIndexRowSeeded(self, row, c0, seeds, query=0):
+        """start the upload of seeded row `row` of query `query`'s index matrix, c0 [E][L][N] + seeds [E][32]"""
+        sd = _seeds(seeds, (self.E,))
+        _check(lib().piehip_stage_index_row_seeded_q(self.cc._h, int(query), int(row), self._c0(c0, (self.E,), "an index matrix row"),
+                                                     sd.ctypes.data_as(u8p)))
+
+    def stageIndexCiphertextSeeded(self, row, j, c0, seed, query=0):
+        """start the upload of seeded ciphertext (row, j) of query `query`'s index matrix, c0 [L][N] + seed"""
+        sd = _seeds(seed, ())
+        _check(lib().piehip_stage_index_ct_seeded_q(self.cc._h, int(query), int(row), int(j), self._c0(c0, (), "an index matrix entry"),
+                                                    sd.ctypes.data_as(u8p)))
+
+    def _seeded_args(self, c0Index, indexSeeds, c0Minus, minusSeeds):
+        nq = self.nq
+        pre = () if nq == 1 else (nq,)
+        ip = self._c0(c0Index, pre + (self.K, self.E), "the index matrix")
+        mp = self._c0(c0Minus, pre, "the minus element")
+        return ip, _seeds(indexSeeds, pre + (self.K, self.E)), mp, _seeds(minusSeeds, pre)
+
+    def runHostSeeded(self, c0Index, indexSeeds, c0Minus, minusSeeds, results=None):
+        """runHost with seeded queries (piehip_run_host_seeded): c0Index [K][E][L][N] + indexSeeds [K][E][32], c0Minus [L][N] +
+        minusSeeds [32] ([nq] in front of each for a batch); the device expands the c1 halves"""
+        ip, isd, mp, msd = self._seeded_args(c0Index, indexSeeds, c0Minus, minusSeeds)
+        if results is None:
+            if getattr(self, "_results", None) is None or self._results.shape != self._res_shape():
+                self._results = np.zeros(self._res_shape(), dtype=np.uint64)
+            results = self._results
+        if results.dtype != np.uint64 or not results.flags.c_contiguous or results.shape != self._res_shape():
+            raise ValueError("results must be [b] ([b][nq] for a batch) contiguous uint64 ciphertexts")
+        _check(lib().piehip_run_host_seeded(self.cc._h, ip, isd.ctypes.data_as(u8p), mp, msd.ctypes.data_as(u8p), results.ctypes.data_as(u64p)))
+        return results
+
+    def runHostSeededAsync(self, c0Index, indexSeeds, c0Minus, minusSeeds, results):
+        """queue runHostSeeded and return (piehip_run_host_seeded_async); c0Index, c0Minus and results must stay untouched until
+        waitHost() (the seeds are taken at once)"""
+        ip, isd, mp, msd = self._seeded_args(c0Index, indexSeeds, c0Minus, minusSeeds)
+        if results.dtype != np.uint64 or not results.flags.c_contiguous or results.shape != self._res_shape():
+            raise ValueError("results must be [b] ([b][nq] for a batch) contiguous uint64 ciphertexts")
+        _check(lib().piehip_run_host_seeded_async(self.cc._h, ip, isd.ctypes.data_as(u8p), mp, msd.ctypes.data_as(u8p),
+                                                  results.ctypes.data_as(u64p)))
 
     def stageReset(self):
         """drop a partial staging sequence (piehip_stage_reset)"""
