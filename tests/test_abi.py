@@ -238,3 +238,17 @@ def test_sharded_database_needs_explicit_seeds():
             pie.BatchedFHEHIPPIE(cc, serverSet=items, hashParams=hp, binSlice=(0, 2))
     with pytest.raises(ValueError, match="identical on every shard"):
         pie.BatchedFHEHIPPIE(cc, hashTable=np.zeros((2, 4, 2, 4, 4), dtype=np.uint64), shuffle_seed=5, binSlice=(0, 2))
+
+
+def test_depth_ten_tier_is_refused_by_name(built):
+    """the reference's deepest tier (depth 10 for inner tables of 5000 or more) asks for L = 11, beyond MAX_L = 7: creating a
+    context from it fails on the parameters, before any device is opened"""
+    from nested_hashing_psi_amd import pie
+    from nested_hashing_psi_amd.client import select_parameters
+    prm = select_parameters(32, 5000)
+    assert prm["L"] == 11
+    with pytest.raises(ValueError, match=r"\bL\b"):
+        pie.PieContext(prm["N"], prm["L"], prm["t"])
+    q, p = pie.default_moduli(prm["N"], 7)
+    with pytest.raises(ValueError, match=r"\bL\b"):
+        pie.PieContext(prm["N"], 0, prm["t"], q[:0], p[:1])

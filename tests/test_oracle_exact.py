@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import exact as ex
+from tests import param_chains as pc
 
 T16 = 65537
 T32 = 4296540161  # 2^32 + 2^20 + 2^19 + 1, reference BatchedFHEPSIClient.cpp:29
@@ -70,9 +71,34 @@ def test_twiddle_tables(ob):
         assert int(fwd[k]) == w and int(inv[k]) == pow(w, -1, q)
 
 
-@pytest.mark.parametrize("N,L,t", [(64, 1, T16), (64, 2, T16), (256, 3, T32), (128, 4, T32), (64, 6, T32)])
-def test_base_conversions_exact(ob, N, L, t):
-    o = ob.Oracle(N, L, t)
+def _chain(N, L, chain):
+    """None: the default chain; an int: the uniform chain below it; a str: a named chain of tests/param_chains.py"""
+    if chain is None:
+        return None, None
+    if isinstance(chain, int):
+        return pc.uniform_chain(N, L, chain)
+    return pc.named_chain(N, L, chain)
+
+
+def _cases(rows):
+    """parameter rows (N, L, t, chain); the ids of the default-chain rows stay N-L-t"""
+    def cid(N, L, t, chain):
+        tail = "" if chain is None else "-" + (chain if isinstance(chain, str) else "below2^%d" % (chain.bit_length() - 1))
+        return "%d-%d-%d%s" % (N, L, t, tail)
+    return [pytest.param(*r, id=cid(*r)) for r in rows]
+
+
+@pytest.mark.parametrize("N,L,t,chain", _cases([(64, 1, T16, None), (64, 2, T16, None), (256, 3, T32, None), (128, 4, T32, None),
+                                                (64, 6, T32, None),
+                                                (64, 7, T32, None), (128, 7, T16, None), (64, 7, T32, 1 << 61), (64, 7, T32, 1 << 50)]
+                                               + [(64, L, T32, name) for name in pc.NAMED for L in (2, 4, 7)]
+                                               + [(128, 3, T16, name) for name in pc.NAMED]))
+def test_base_conversions_exact(ob, N, L, t, chain):
+    """the oracle's three base conversions against big-integer arithmetic; up to L = 7 (MAX_L) and on the mixed-width chains"""
+    q, p = _chain(N, L, chain)
+    o = ob.Oracle(N, L, t, q, p)
+    if q is not None:
+        assert (o.q == q).all() and (o.p == p).all()
     qs = [int(x) for x in o.q]
     ps = [int(x) for x in o.p]
     rng = np.random.default_rng(1000 * N + L)
@@ -138,9 +164,13 @@ def test_tensor_product_exact(ob, N, L, t):
     assert (dec == x * y).all() and budget > 0
 
 
-@pytest.mark.parametrize("N,L,t", [(64, 2, T16), (1024, 3, T32)])
-def test_decrypt_and_relin_against_exact(ob, N, L, t):
-    o = ob.Oracle(N, L, t)
+@pytest.mark.parametrize("N,L,t,chain", _cases([(64, 2, T16, None), (1024, 3, T32, None), (64, 7, T16, None), (256, 7, T32, None),
+                                                (64, 3, T16, "q0_wide"), (256, 7, T16, "q0_wide"), (64, 3, T16, "q_narrow_p_wide")]))
+def test_decrypt_and_relin_against_exact(ob, N, L, t, chain):
+    """decryption and relinearisation against exact arithmetic; q0_wide lifts the digit of its 60-bit q_0 into 45-bit
+    moduli (q_i >= 2 q_j: the Barrett branch of the digit lift)"""
+    q, p = _chain(N, L, chain)
+    o = ob.Oracle(N, L, t, q, p)
     qs = [int(x) for x in o.q]
     rng = np.random.default_rng(3)
     sk = o.keygen(5)
@@ -157,9 +187,11 @@ def test_decrypt_and_relin_against_exact(ob, N, L, t):
         m_oracle, budget = o.decrypt(sk, ct)
         assert [int(v) for v in m_oracle] == m_exact
         assert worst < 0.5
-        # the fixed-point budget estimate agrees with the exact noise to within a bit
+        # the fixed-point budget estimate agrees with the exact noise to within a bit -- or, for a ciphertext quieter than
+        # the L ulps (of 2^-60) the per-limb fractions may lose, reads the best budget an L-limb sum can show
         import math
         exact_budget = min(58, int(math.floor(-math.log2(2 * worst)))) if worst > 0 else 58
-        assert abs(budget - exact_budget) <= 1
+        floor_L = 59 - L.bit_length()
+        assert abs(budget - exact_budget) <= 1 or (budget == floor_L and exact_budget > floor_L)
     dec, _ = o.decrypt_slots(sk, o.mul(cx, cy, evk), N)
     assert (dec == x * y).all()
