@@ -391,8 +391,9 @@ void launch_stage_a(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, cons
 }
 
 // Stage A of a query batch: acc[b][nq][K][2][L][N].  Column-accumulator kernel (every modulus < 2^60): groups of two to four
-// queries per launch (plus one launch for the layers left over by the per-thread layer count), each reading the database once;
-// otherwise one launch series per query.
+// queries per launch, ONE launch per group whatever the layer count (a layer count that is no multiple of the per-thread layer
+// count leaves a ragged last group, see launch_stage_a_batch_q), each reading the database once; otherwise one launch_stage_a
+// series per query.
 template <int Q, int BPT>
 static void launch_stage_a_batch_qb(const DevConsts *dc, u32 N, u32 L, u32 K, u32 nb, u32 E, const StageAQueries &qs, const u64 *db,
                                     u64 *acc, hipStream_t st, u32 bstride, u32 h0, u32 hn, u32 nq, u32 q0, StageAXOut xo)

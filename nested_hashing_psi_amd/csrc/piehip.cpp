@@ -859,6 +859,7 @@ int piehip_build_db_bins(piehip_handle h, const uint64_t *items, size_t n, uint3
         HIPCHK(launch_hash_build(d_tab, d_items, (u32)n, k, e, K, b, E, evict_seed, shuffle_seed, h->d_hash_tbl, (u32 *)d_keys,
                                  (u32 *)d_vals, (u32 *)d_start, d_temp, temp_bytes, d_fail, h->stream));
         launch_gather_slots(h->d_hash_tbl, (u32)B, K, b, E, h->hp.t, d_slots, d_fail, h->stream);
+        HIPCHK(hipGetLastError());  // a launch that failed would leave d_slots uninitialised for the encoder
     }
     u32 failed = 0;
     HIPCHK(hipMemcpyAsync(&failed, d_fail, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
@@ -901,6 +902,7 @@ int piehip_load_db_table_bins(piehip_handle h, const uint64_t *tbl, uint32_t k, 
     HIPCHK(hipMemsetAsync(d_fail, 0, sizeof(u32), h->stream));
     launch_shuffle_rows(h->d_hash_tbl, (u32)(B * K), b, E, shuffle_seed, h->stream);
     launch_gather_slots(h->d_hash_tbl, (u32)B, K, b, E, h->hp.t, d_slots, d_fail, h->stream);
+    HIPCHK(hipGetLastError());  // (as in piehip_build_db_bins)
     u32 failed = 0;
     HIPCHK(hipMemcpyAsync(&failed, d_fail, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -968,8 +968,10 @@ def test_batch_layer_groups_over_many_shapes(ob, pie):
 
 @pytest.mark.parametrize("E,b", [(1, 1), (1, 3), (15, 2), (16, 3), (40, 5)])
 def test_run_shape_extremes(ob, pie, E, b):
-    """one inner position, the last E of the carry-free accumulator (15), the first E of the 128-bit accumulator (16), a long
-    reduction (40), odd bin-layer counts across the two queues -- random limbs, ciphertext bits vs the oracle"""
+    """one inner position; on the default chain every E runs the carry-free column accumulators (stage_a_mad_kernel): E = 15
+    hands the epilogue 15 unreduced top-column terms, E = 16 is the first E with a mid-sum reduction (after term 15), E = 40
+    takes two of them; odd bin-layer counts -- random limbs, ciphertext bits vs the oracle (long sums and worst-case residues:
+    tests/test_gpu_long_sums.py)"""
     N, L, t, K = 2048, 3, T32, 2
     o = ob.Oracle(N, L, t)
     cc = pie.PieContext(N, L, t)

@@ -195,3 +195,40 @@ def test_decrypt_and_relin_against_exact(ob, N, L, t, chain):
         assert abs(budget - exact_budget) <= 1 or (budget == floor_L and exact_budget > floor_L)
     dec, _ = o.decrypt_slots(sk, o.mul(cx, cy, evk), N)
     assert (dec == x * y).all()
+
+
+@pytest.mark.parametrize("chain", [None, 1 << 61], ids=["60-bit", "61-bit"])
+@pytest.mark.parametrize("pattern", ["all_q_minus_1", "near_max"])
+def test_pie_run_long_sum_against_exact(ob, chain, pattern):
+    """run() with K = 1 is stage A plus the mask multiply, every step element-wise mod q in evaluation form: the oracle's
+    E = 581 inner products (one mulmod + addmod per term) against Python integers, with every index and database word q - 1
+    or in [q - 2^24, q) -- the reference side of tests/test_gpu_long_sums.py at its longest sum"""
+    N, L, K, E, b = 16, 2, 1, 581, 2
+    q, p = _chain(N, L, chain)
+    o = ob.Oracle(N, L, T16, q, p)
+    qs = [int(x) for x in o.q]
+    rng = np.random.default_rng(581 + len(pattern))
+
+    def words(shape):
+        a = np.zeros(tuple(shape) + (L, N), dtype=np.uint64)
+        for i, qi in enumerate(qs):
+            off = 0 if pattern == "all_q_minus_1" else rng.integers(0, 1 << 24, tuple(shape) + (N,), dtype=np.uint64)
+            a[..., i, :] = np.uint64(qi - 1) - off
+        return a
+
+    def rand(shape):
+        a = np.zeros(tuple(shape) + (L, N), dtype=np.uint64)
+        for i, qi in enumerate(qs):
+            a[..., i, :] = rng.integers(0, qi, tuple(shape) + (N,), dtype=np.uint64)
+        return a
+
+    idx, db = words((K, E, 2)), words((K, b, E))
+    minus, masks, evk = rand((2,)), rand((b,)), rand((L, 2))
+    got = o.pie_run(idx, minus, db, masks, evk)
+    io, do, mo, ko = idx.astype(object), db.astype(object), minus.astype(object), masks.astype(object)
+    for bn in range(b):
+        for c in range(2):
+            for i, qi in enumerate(qs):
+                acc = sum(io[0, j, c, i] * do[0, bn, j, i] for j in range(E))     # exact, ~2^131 before the one reduction
+                want = [int(v) for v in (acc + mo[c, i]) * ko[bn, i] % qi]
+                assert [int(v) for v in got[bn, c, i]] == want, "bin %d, component %d, limb %d" % (bn, c, i)
