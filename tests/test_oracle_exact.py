@@ -232,3 +232,68 @@ def test_pie_run_long_sum_against_exact(ob, chain, pattern):
                 acc = sum(io[0, j, c, i] * do[0, bn, j, i] for j in range(E))     # exact, ~2^131 before the one reduction
                 want = [int(v) for v in (acc + mo[c, i]) * ko[bn, i] % qi]
                 assert [int(v) for v in got[bn, c, i]] == want, "bin %d, component %d, limb %d" % (bn, c, i)
+
+
+# ---- the rotation path: Galois elements, the automorphism and its key switch ---------------------------------------------
+@pytest.mark.parametrize("N", [8, 16, 64, 4096, 65536])
+def test_rot_index_is_a_power_of_five(ob, N):
+    """po_rot_index(r) = 5^r mod 2N for r > 0 and 5^-|r| for r < 0 (EvalAtIndex: r > 0 rotates the rows left); every multiple
+    of the row length N/2 (5 has order N/2 mod 2N) is the identity"""
+    o = ob.Oracle(N, 1, T32)
+    m2, h = 2 * N, N // 2
+    inv5 = pow(5, -1, m2)
+    for r in sorted({1, 2, h - 1}):
+        assert o.rot_index(r) == pow(5, r, m2)
+        assert o.rot_index(-r) == pow(inv5, r, m2)
+        assert o.rot_index(r) * o.rot_index(-r) % m2 == 1
+    for r in (h, -h, 2 * h, -3 * h):
+        assert o.rot_index(r) == 1
+    assert len({pow(5, r, m2) for r in range(h)}) == h
+
+
+def sigma(a, g, M):
+    """sigma_g: a(X) -> a(X^g) mod (X^N + 1, M), coefficient lists"""
+    N = len(a)
+    out = [0] * N
+    for i, v in enumerate(a):
+        k = i * g % (2 * N)
+        if k < N:
+            out[k] = (out[k] + v) % M
+        else:
+            out[k - N] = (out[k - N] - v) % M
+    return out
+
+
+@pytest.mark.parametrize("chain", [None, "q0_wide", "q_narrow_p_wide"], ids=["60-bit", "q0_wide", "q_narrow_p_wide"])
+@pytest.mark.parametrize("N,L", [(64, 2), (64, 7), (256, 7), (1024, 3)])
+def test_automorph_against_exact(ob, N, L, chain):
+    """po_automorph(c, g, po_rot_keygen(s, g)) decrypts exactly to sigma_g of the message polynomial, and its phase c0 + c1 s is
+    sigma_g of c's phase plus the BV key-switch noise sum_i d_i e_i: |d_i| <= q_i / 2 (centred digits), |e_i| <= 20 (the centred
+    binomial of 2 x 20 bits), so every coefficient is at most N sum_i 10 q_i.  A key of the wrong secret or Galois element leaves
+    noise of size Q.  g: 5, 5^-1 (rotations by +-1), 25 (by 2) and 2N - 1 (the row swap)"""
+    t = T16
+    q, p = _chain(N, L, chain)
+    o = ob.Oracle(N, L, t, q, p)
+    qs = [int(x) for x in o.q]
+    Q = ex.prod(qs)
+    sk = o.keygen(5)
+    s = [int(v) if int(v) <= 1 else int(v) - qs[0] for v in o.intt(0, sk[0])]
+    assert set(s) <= {-1, 0, 1}
+    sQ = [v % Q for v in s]
+    rng = np.random.default_rng(N + L)
+    x = rng.integers(-(t // 2), t // 2 + 1, N)
+    m = [int(v) for v in o.encode(x)[0]]
+    c = o.encrypt(sk, m, 9)
+    c0, c1 = _coeff_ints(o, c, qs)
+    phase = [(u + v) % Q for u, v in zip(c0, ex.negacyclic_mul_mod(c1, sQ, Q))]
+    bound = N * sum(10 * qi for qi in qs)
+    for n, g in enumerate([5, pow(5, -1, 2 * N), 25, 2 * N - 1]):
+        rk = o.rot_keygen(sk, g, 40 + n)
+        out = o.automorph(c, g, rk)
+        d0, d1 = _coeff_ints(o, out, qs)
+        got, worst = ex.decrypt_exact([d0, d1], s, qs, t)
+        assert got == sigma(m, g, t), "g = %d" % g
+        assert worst < 0.5
+        ph = [(u + v) % Q for u, v in zip(d0, ex.negacyclic_mul_mod(d1, sQ, Q))]
+        noise = max(abs(ex.centered(u - v, Q)) for u, v in zip(ph, sigma(phase, g, Q)))
+        assert noise <= bound, "g = %d: key-switch noise 2^%.1f above the bound 2^%.1f" % (g, np.log2(noise), np.log2(bound))
