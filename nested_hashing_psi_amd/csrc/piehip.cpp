@@ -1,6 +1,6 @@
-// piehip.cpp -- C ABI (include/piehip.h) over the gfx950 kernels: the context, keys and database of a handle, its query inputs,
-// and the launch schedule of BatchedFHEHIPPIE::run() (reference BatchedFHEHIPPIE.cpp:88-129) on the handle's queues.
-// The other entry points live in piehip_host.cpp / _ops.cpp / _fhepie.cpp / _client.cpp / _rccl.cpp (piehip_ctx.hpp lists them).
+// piehip.cpp -- C ABI (include/piehip.h) over the gfx950 kernels: the context, keys and database of a handle and its query inputs.
+// The other entry points live in piehip_run.cpp / _host.cpp / _ops.cpp / _fhepie.cpp / _client.cpp / _rccl.cpp (piehip_ctx.hpp
+// lists them).
 #include "piehip_ctx.hpp"
 
 #include <random>
@@ -8,16 +8,19 @@
 using namespace piehip;
 
 static thread_local std::string g_err;
+static const char *KNAMES[PIEHIP_NKERNELS] = {"stage_a_mac", "ntt_fwd", "ntt_inv",  "expand",   "tensor",    "scale_round",
+                                              "digits",      "relin",   "mask_mul", "encode",   "automorph", "other",
+                                              "event_pair"};
+static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
+static void free_workspace(piehip_ctx *h);
+
 namespace piehip {
+
 int fail(int code, const std::string &msg)
 {
     g_err = msg;
     return code;
 }
-}  // namespace piehip
-static void free_workspace(piehip_ctx *h);
-
-namespace piehip {
 
 void join_pending(piehip_ctx *h)
 {
@@ -33,12 +36,6 @@ void drop_graph(piehip_ctx *h)
     if (h->gexec) (void)hipGraphExecDestroy(h->gexec);
     h->gexec = nullptr;
 }
-
-}  // namespace piehip
-static const char *KNAMES[PIEHIP_NKERNELS] = {"stage_a_mac", "ntt_fwd", "ntt_inv",  "expand",   "tensor",    "scale_round",
-                                              "digits",      "relin",   "mask_mul", "encode",   "automorph", "other",
-                                              "event_pair"};
-namespace piehip {
 
 // ---- profiling helpers -------------------------------------------------------------------------
 hipEvent_t prof_event(piehip_ctx *h)
@@ -87,118 +84,43 @@ void ws_free(MulWs &w)
     w.nb = 0;
 }
 
-// ---- schedule pieces ----------------------------------------------------------------------------
-// sigma: lane order on the EVALUATION side; fold: outer stage applied by the neighbouring kernels (both only
-// take effect when the context supports them; callers pass the same flags to those neighbours)
-void ntt(piehip_ctx *h, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inv, bool sigma, bool fold, const NttExtra *ex)
-{
-    ProfScope ps(h, inv ? PIEHIP_K_NTT_INV : PIEHIP_K_NTT_FWD, 16.0 * h->hp.N * nlimbs);
-    launch_ntt(h->plan, data, nlimbs, mod_base, mod_count, inv, h->stream, sigma && h->sigma_on, fold && h->fold_on, ex);
-}
-// The X operand of a ciphertext multiplication is available in EVALUATION format before its inverse transform; when
-// the register-blocked kernel runs that transform it also drops a lane-ordered copy into the Q limbs of the QP operand
-// array, and the forward transform over QP skips those limbs (8 of 36 per bin layer at L = 4).  (For the first product of a
-// query batch stage A has written X there already: enqueue_run_bins, x_direct.)
-bool xq_reuse(const piehip_ctx *h) { return h->sigma_on && ntt_supports_extra(h->plan, h->fold_on); }
-
-// BV key switch of the COEFFICIENT-format polynomials at w.d2c with `key`, added to the EVALUATION
-// ciphertexts at w.d01, optionally multiplied by mask plaintexts: out[nb][2][L][N]
-// sigma: w.d01 and the digits are in lane order, key/mask are lane-ordered copies, out is written in standard order
-void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u64 *mask, u64 *out, bool sigma, bool fold,
-                       size_t key_stride, u32 key_group, bool out_is_result, bool digits_ready)
-{
-    const u32 N = h->hp.N, L = h->hp.L;
-    const size_t LN = h->LN();
-    const double W = 8.0 * N;
-    set_small_moduli(h->small_moduli);
-    bool fused = digits_ready;  // the caller's transform launch of d01 also lifted and transformed the digits
-    // digit lift inside the transform's load phase (the 32-coefficient kernel; contexts whose lane order is the 16-coefficient
-    // kernel's take the digits kernel + transform below)
-    if (!fused && h->sigma_on && h->d_twc && h->hp.logN <= 14 && !(sigma && ntt16_applies(h->plan, fold && h->fold_on))) {
-        ProfScope ps(h, PIEHIP_K_NTT_FWD, 16.0 * N * nb * L * L);
-        fused = launch_ntt_digits(h->plan, w.d2c, w.dig, nb, L, sigma && h->sigma_on, fold && h->fold_on, h->stream);
-    }
-    if (!fused) {
-        {
-            ProfScope ps(h, PIEHIP_K_DIGITS, W * nb * (L + (double)L * L));
-            launch_digits(h->d_dc, N, L, w.d2c, LN, nb, w.dig, h->stream, fold && h->fold_on);
-        }
-        ntt(h, w.dig, nb * L * L, 0, L, false, sigma, fold);
-    }
-    {
-        // the result buffer may still be read by work the caller queued on the handle's stream before this run
-        if (h->wait_before_results && out_is_result) (void)hipStreamWaitEvent(h->stream, h->wait_before_results, 0);
-        if (h->chain_armed && out_is_result) {  // the next queue group of a host-results run may start (piehip_run_into)
-            h->chain_armed = false;
-            (void)hipEventRecord(h->ev_chain, h->stream);
-        }
-        ProfScope ps(h, PIEHIP_K_RELIN, W * (nb * ((double)L * L + 2 * L + 2 * L + (mask ? L : 0)) + 2.0 * L * L));
-        launch_relin_mac(h->d_dc, N, L, w.d01, 2 * LN, w.dig, key, mask, out, nb, h->stream,
-                         (sigma && h->sigma_on) ? h->d_sigma_inv : nullptr, key_stride, key_group,
-                         (sigma && h->sigma_on) ? h->sigma_T : 0, h->sigma_kp, mask ? h->mask_div : 1);
-    }
-}
-
-// One batched EvalMult(ct,ct) (BatchedFHEHIPPIE.cpp:123): operands in COEFFICIENT format (produced by
-// ntt(.., inverse, sigma = false, fold = true): with folding on, their outermost inverse stage is applied here),
-// X polynomial (o,c) at x + o*sx + c*LN, Y likewise.  relin: out[nb][2][L][N] (times mask if given);
-// otherwise out[nb][3][L][N] holds the EVALUATION-format tensor result.
-void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
-                 const u64 *mask, u64 *out, bool xq_ready, bool out_is_result)
+// device-side MakePackedPlaintext of npt slot vectors (already on the device) into out[npt][L][N]
+int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out)
 {
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M;
-    const size_t LN = h->LN();
-    const double W = 8.0 * N;
-    set_small_moduli(h->small_moduli);
-    {
-        ProfScope ps(h, PIEHIP_K_EXPAND, W * nb * (4.0 * L + 4.0 * M));
-        launch_expand_both(h->d_dc, N, L, x, sx, y, sy, LN, nb, w.eqp, h->stream, h->fold_on, xq_ready);
+    // chunk so the mod-t scratch stays small
+    const u32 chunk = ENCODE_CHUNK;
+    Tmp tmp(h);
+    TMPGET(d_u, (size_t)(npt < chunk ? npt : chunk) * N);
+    for (u32 s = 0; s < npt; s += chunk) {
+        const u32 c = npt - s < chunk ? npt - s : chunk;
+        ProfScope ps(h, PIEHIP_K_ENCODE, 8.0 * c * ((double)B + 2.0 * N + (double)L * N));
+        launch_encode_scatter(h->d_dc, N, M, d_slots + (size_t)s * B, B, h->d_inv_pos, d_u, c, h->stream);
+        launch_ntt(h->plan, d_u, c, M, 1, true, h->stream);
+        launch_encode_lift(h->d_dc, N, L, M, d_u, d_out + (size_t)s * L * N, c, h->stream);
+        launch_ntt(h->plan, d_out + (size_t)s * L * N, c * L, 0, L, false, h->stream);
     }
-    // the QP operands and the tensor result never leave the library: lane order, no LDS transposes
-    {
-        NttExtra ex;
-        ex.lazy_out = true;  // the tensor product's Barrett reduction takes any operands < 2^63
-        if (xq_ready) {
-            ex.skip_L = L;
-            ex.skip_M = M;
-        }
-        ntt(h, w.eqp, nb * (xq_ready ? 4 * M - 2 * L : 4 * M), 0, M, false, true, true, &ex);
-    }
-    {
-        ProfScope ps(h, PIEHIP_K_TENSOR, W * nb * 7.0 * M);
-        launch_tensor(h->d_dc, N, M, w.eqp, w.dqp, nb, h->stream);
-    }
-    ntt(h, w.dqp, nb * 3 * M, 0, M, true, true, true);
-    if (relin) {
-        {
-            ProfScope ps(h, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, h->stream, h->fold_on, false);
-        }
-        bool digits_ready = false;
-        {
-            NttExtra ex;
-            ex.lazy_out = true;  // the key-switch MAC adds d01 into its accumulator before reducing
-            if (h->sigma_on && h->small_moduli && ntt16_applies(h->plan, h->fold_on)) {
-                // one launch for both forward transforms in front of the key-switch MAC: d0, d1 and the L * L digits of d2
-                // (equal-width primes only: the kernel's lift is a conditional subtraction)
-                ProfScope ps(h, PIEHIP_K_NTT_FWD, 16.0 * N * nb * (2.0 * L + (double)L * L));
-                Ntt16Digits dg = {w.d2c, LN, w.dig, nb, L};
-                digits_ready = launch_ntt16(h->plan, h->fold_on, w.d01, nb * 2 * L, 0, L, false, true, h->stream, &ex, &dg);
-            }
-            if (!digits_ready) ntt(h, w.d01, nb * 2 * L, 0, L, false, true, true, &ex);
-        }
-        if (h->key_group > 1)  // a batch whose queries bring their own keys (piehip_load_relin_key_q)
-            enqueue_keyswitch(h, w, nb, h->sigma_on ? h->d_evkq_sigma : h->d_evkq, mask, out, true, true, (size_t)L * 2 * LN, h->key_group,
-                              out_is_result, digits_ready);
-        else
-            enqueue_keyswitch(h, w, nb, h->sigma_on ? h->d_evk_sigma : h->d_evk, mask, out, true, true, 0, 1, out_is_result, digits_ready);
-    } else {
-        {
-            ProfScope ps(h, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, out, 3 * LN, out + 2 * LN, 3 * LN, h->stream, h->fold_on, true);
-        }
-        ntt(h, out, nb * 3 * L, 0, L, false, false, true);
-    }
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(PIEHIP_EHIP, std::string("encode: ") + hipGetErrorString(e));
+    return PIEHIP_OK;
+}
+
+int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus)
+{
+    if (!h->K) return fail(PIEHIP_ESTATE, "load the database before the index matrix");
+    if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
+    Query &s = h->query[q];
+    int rc;
+    if (!s.idx_own && (rc = dev_alloc(&s.idx_own, (size_t)h->K * h->E * 2 * h->LN()))) return rc;
+    if (!s.minus_own && (rc = dev_alloc(&s.minus_own, 2 * h->LN()))) return rc;
+    *d_idx = s.idx_own;
+    *d_minus = s.minus_own;
+    return PIEHIP_OK;
+}
+
+void use_owned_inputs(piehip_ctx *h)
+{
+    for (u32 q = 0; q < h->nq; q++) h->query[q].idx = h->query[q].idx_own, h->query[q].minus = h->query[q].minus_own;
 }
 
 }  // namespace piehip
@@ -390,11 +312,9 @@ int piehip_destroy(piehip_handle h)
     dev_free(&h->d_evk);
     dev_free(&h->d_db);
     dev_free(&h->d_masks);
-    dev_free(&h->d_idx_own);
-    dev_free(&h->d_minus_own);
-    for (u32 q = 0; q < STAGE_A_MAX_QUERIES; q++) {
-        dev_free(&h->bq_idx_own[q]);
-        dev_free(&h->bq_minus_own[q]);
+    for (Query &s : h->query) {
+        dev_free(&s.idx_own);
+        dev_free(&s.minus_own);
     }
     free_workspace(h);
     if (h->d_dc) (void)hipFree(h->d_dc);
@@ -462,6 +382,20 @@ int piehip_get_slot_positions(piehip_handle h, uint32_t *pos)
     return PIEHIP_OK;
 }
 
+// Per-query key slots (piehip_load_relin_key_q) that no query loaded hold a COPY of the handle's key and of its lane-ordered
+// twin, if the handle has one: they follow it.  Queued on the handle's stream; the caller waits.
+static int fill_unloaded_key_slots(piehip_ctx *h)
+{
+    const size_t words = (size_t)h->hp.L * 2 * h->LN();
+    for (u32 i = 0; i < h->evkq_n && h->d_evkq && h->d_evk; i++) {
+        if (h->evkq_loaded >> i & 1) continue;
+        HIPCHK(hipMemcpyAsync(h->d_evkq + i * words, h->d_evk, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+        if (h->sigma_on && h->d_evkq_sigma)
+            HIPCHK(hipMemcpyAsync(h->d_evkq_sigma + i * words, h->d_evk_sigma, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+    }
+    return PIEHIP_OK;
+}
+
 int piehip_load_relin_key(piehip_handle h, const uint64_t *evk)
 {
     NEED(h);
@@ -485,13 +419,8 @@ int piehip_load_relin_key(piehip_handle h, const uint64_t *evk)
         launch_permute(h->hp.N, h->d_evk, h->d_sigma_inv, h->d_evk_sigma, h->hp.L * 2 * h->hp.L, h->stream);
         HIPCHK(hipStreamSynchronize(h->stream));
     }
-    // per-query key slots (piehip_load_relin_key_q) that no query loaded hold a COPY of the handle's key: they follow it
-    for (u32 i = 0; i < h->evkq_n && h->d_evkq; i++) {
-        if (h->evkq_loaded >> i & 1) continue;
-        HIPCHK(hipMemcpyAsync(h->d_evkq + i * words, h->d_evk, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
-        if (h->sigma_on && h->d_evkq_sigma)
-            HIPCHK(hipMemcpyAsync(h->d_evkq_sigma + i * words, h->d_evk_sigma, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
-    }
+    int rc = fill_unloaded_key_slots(h);
+    if (rc) return rc;
     if (h->d_evkq) HIPCHK(hipStreamSynchronize(h->stream));
     return PIEHIP_OK;
 }
@@ -558,8 +487,7 @@ static int alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db = 
     if (with_db && h->K == K && h->b == b && h->E == E && h->d_db && h->d_masks && h->d_acc && h->d_out && h->ws.nb == b * h->nq) {
         // same shape as the database being replaced (or reserved): keep the 0.5 GiB of buffers (hipFree + hipMalloc cost
         // ~10 ms); the inputs of the previous database are stale
-        h->d_idx = nullptr;
-        for (u32 q = 1; q < STAGE_A_MAX_QUERIES; q++) h->bq_idx[q] = nullptr;
+        for (Query &s : h->query) s.idx = nullptr;
         return PIEHIP_OK;
     }
     dev_free(&h->d_db);
@@ -576,11 +504,9 @@ static int alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db = 
     h->E = E;
     // inputs depend on K,E: drop stale copies
     h->stage_open = false;
-    dev_free(&h->d_idx_own);
-    h->d_idx = nullptr;
-    for (u32 q = 1; q < STAGE_A_MAX_QUERIES; q++) {
-        dev_free(&h->bq_idx_own[q]);
-        h->bq_idx[q] = nullptr;
+    for (Query &s : h->query) {
+        dev_free(&s.idx_own);
+        s.idx = nullptr;
     }
     return PIEHIP_OK;
 }
@@ -640,8 +566,6 @@ int piehip_attach_database(piehip_handle h, piehip_handle owner)
     return PIEHIP_OK;
 }
 
-static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
-
 // the persistent hash-table buffer [k][e][K][b][E]: reallocated only when the size changes
 static int hash_tbl_alloc(piehip_ctx *h, size_t words)
 {
@@ -662,31 +586,6 @@ static size_t build_db_scratch_words(const piehip_ctx *h, size_t n, u32 k, u32 e
     return g((size_t)(k + K) * 16 * 256) + g(n) + 2 * g(n + 1) + g((e + 2) / 2 + 1) + g(1) + g(hash_sort_temp_bytes((u32)n, e) / 8 + 1) +
            g((npt > b ? npt : b) * B) + g((size_t)ENCODE_CHUNK * h->hp.N);
 }
-
-// device-side MakePackedPlaintext of npt slot vectors (already on the device) into out[npt][L][N]
-}  // extern "C"
-namespace piehip {
-int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out)
-{
-    const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M;
-    // chunk so the mod-t scratch stays small
-    const u32 chunk = ENCODE_CHUNK;
-    Tmp tmp(h);
-    TMPGET(d_u, (size_t)(npt < chunk ? npt : chunk) * N);
-    for (u32 s = 0; s < npt; s += chunk) {
-        const u32 c = npt - s < chunk ? npt - s : chunk;
-        ProfScope ps(h, PIEHIP_K_ENCODE, 8.0 * c * ((double)B + 2.0 * N + (double)L * N));
-        launch_encode_scatter(h->d_dc, N, M, d_slots + (size_t)s * B, B, h->d_inv_pos, d_u, c, h->stream);
-        launch_ntt(h->plan, d_u, c, M, 1, true, h->stream);
-        launch_encode_lift(h->d_dc, N, L, M, d_u, d_out + (size_t)s * L * N, c, h->stream);
-        launch_ntt(h->plan, d_out + (size_t)s * L * N, c * L, 0, L, false, h->stream);
-    }
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(PIEHIP_EHIP, std::string("encode: ") + hipGetErrorString(e));
-    return PIEHIP_OK;
-}
-}  // namespace piehip
-extern "C" {
 
 int piehip_load_db_slots(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, uint32_t B, const int64_t *slots,
                          const int64_t *mask_slots)
@@ -810,10 +709,9 @@ int piehip_reserve(piehip_handle h, size_t n, uint32_t k, uint32_t e, uint32_t K
         if ((rc = dev_alloc(&h->arena, need))) return rc;
         h->arena_words = need;
     }
-    // the per-query input buffers too (setIndex / setMinusCompareElement from host memory)
-    if (!h->d_idx_own && (rc = dev_alloc(&h->d_idx_own, (size_t)K * E * 2 * h->LN()))) return rc;
-    if (!h->d_minus_own && (rc = dev_alloc(&h->d_minus_own, 2 * h->LN()))) return rc;
-    return PIEHIP_OK;
+    // the input buffers of query 0 too (setIndex / setMinusCompareElement from host memory)
+    u64 *di = nullptr, *dm = nullptr;
+    return query_input_buffers(h, 0, &di, &dm);
 }
 
 int piehip_build_db_bins(piehip_handle h, const uint64_t *items, size_t n, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
@@ -926,51 +824,63 @@ int piehip_get_hash_table(piehip_handle h, uint64_t *tbl)
     return PIEHIP_OK;
 }
 
-int piehip_set_index(piehip_handle h, const uint64_t *idx)
+// ---- query inputs ---------------------------------------------------------------------------------------------------------
+// Query q of the batch (piehip_set_query_batch; a handle without a batch has query 0 only, which the plain names set).
+static int batch_query_check(piehip_ctx *h, u32 q)
+{
+    if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
+    return PIEHIP_OK;
+}
+// a host array to the owned device copy of one input of a query, which the next run() then reads
+static int upload_input(piehip_ctx *h, const uint64_t *src, size_t words, u64 **own, const u64 **in)
+{
+    HIPCHK(hipSetDevice(h->device));
+    int rc;
+    if (!*own && (rc = dev_alloc(own, words))) return rc;
+    HIPCHK(hipMemcpyAsync(*own, src, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *in = *own;
+    return PIEHIP_OK;
+}
+int piehip_set_index_q(piehip_handle h, uint32_t q, const uint64_t *idx)
 {
     NEED(h);
     if (!idx) return fail(PIEHIP_EINVAL, "null index matrix");
     if (!h->K) return fail(PIEHIP_ESTATE, "load the database before the index matrix");
-    HIPCHK(hipSetDevice(h->device));
-    const size_t words = (size_t)h->K * h->E * 2 * h->LN();
-    if (!h->d_idx_own) {
-        int rc = dev_alloc(&h->d_idx_own, words);
-        if (rc) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(h->d_idx_own, idx, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->d_idx = h->d_idx_own;
-    return PIEHIP_OK;
+    int rc = batch_query_check(h, q);
+    if (rc) return rc;
+    return upload_input(h, idx, (size_t)h->K * h->E * 2 * h->LN(), &h->query[q].idx_own, &h->query[q].idx);
 }
-int piehip_set_minus(piehip_handle h, const uint64_t *minus)
+int piehip_set_minus_q(piehip_handle h, uint32_t q, const uint64_t *minus)
 {
     NEED(h);
     if (!minus) return fail(PIEHIP_EINVAL, "null minus element");
-    HIPCHK(hipSetDevice(h->device));
-    const size_t words = 2 * h->LN();
-    if (!h->d_minus_own) {
-        int rc = dev_alloc(&h->d_minus_own, words);
-        if (rc) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(h->d_minus_own, minus, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->d_minus = h->d_minus_own;
-    return PIEHIP_OK;
+    int rc = batch_query_check(h, q);
+    if (rc) return rc;
+    return upload_input(h, minus, 2 * h->LN(), &h->query[q].minus_own, &h->query[q].minus);
 }
-int piehip_set_index_device(piehip_handle h, const void *d_idx)
+int piehip_set_index_device_q(piehip_handle h, uint32_t q, const void *d_idx)
 {
     NEED(h);
     if (!d_idx) return fail(PIEHIP_EINVAL, "null index matrix");
-    h->d_idx = (const u64 *)d_idx;
+    int rc = batch_query_check(h, q);
+    if (rc) return rc;
+    h->query[q].idx = (const u64 *)d_idx;
     return PIEHIP_OK;
 }
-int piehip_set_minus_device(piehip_handle h, const void *d_minus)
+int piehip_set_minus_device_q(piehip_handle h, uint32_t q, const void *d_minus)
 {
     NEED(h);
     if (!d_minus) return fail(PIEHIP_EINVAL, "null minus element");
-    h->d_minus = (const u64 *)d_minus;
+    int rc = batch_query_check(h, q);
+    if (rc) return rc;
+    h->query[q].minus = (const u64 *)d_minus;
     return PIEHIP_OK;
 }
+int piehip_set_index(piehip_handle h, const uint64_t *idx) { return piehip_set_index_q(h, 0, idx); }
+int piehip_set_minus(piehip_handle h, const uint64_t *minus) { return piehip_set_minus_q(h, 0, minus); }
+int piehip_set_index_device(piehip_handle h, const void *d_idx) { return piehip_set_index_device_q(h, 0, d_idx); }
+int piehip_set_minus_device(piehip_handle h, const void *d_minus) { return piehip_set_minus_device_q(h, 0, d_minus); }
 
 // ---- query batches --------------------------------------------------------------------------------------------------------
 // run() over nq queries at once (each with its own index matrix and minus element) against the handle's database.  Stage A
@@ -987,7 +897,7 @@ int piehip_set_query_batch(piehip_handle h, uint32_t nq)
     h->stage_open = false;
     // caller-owned device pointers of queries outside the new batch are forgotten (they may be freed by now); a later, larger
     // batch must set them again.  Per-query keys are sized by the batch: load them again after a change.
-    for (u32 q = nq; q < STAGE_A_MAX_QUERIES; q++) h->bq_idx[q] = h->bq_minus[q] = nullptr;
+    for (u32 q = nq; q < STAGE_A_MAX_QUERIES; q++) h->query[q].idx = h->query[q].minus = nullptr;
     dev_free(&h->d_evkq);
     dev_free(&h->d_evkq_sigma);
     h->evkq_n = h->evkq_loaded = 0;
@@ -1002,79 +912,6 @@ int piehip_get_query_batch(piehip_handle h, uint32_t *nq)
     *nq = h->nq;
     return PIEHIP_OK;
 }
-static int batch_query_check(piehip_ctx *h, u32 q)
-{
-    if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
-    return PIEHIP_OK;
-}
-int piehip_set_index_device_q(piehip_handle h, uint32_t q, const void *d_idx)
-{
-    if (q == 0) return piehip_set_index_device(h, d_idx);
-    NEED(h);
-    if (!d_idx) return fail(PIEHIP_EINVAL, "null index matrix");
-    int rc = batch_query_check(h, q);
-    if (rc) return rc;
-    h->bq_idx[q] = (const u64 *)d_idx;
-    return PIEHIP_OK;
-}
-int piehip_set_minus_device_q(piehip_handle h, uint32_t q, const void *d_minus)
-{
-    if (q == 0) return piehip_set_minus_device(h, d_minus);
-    NEED(h);
-    if (!d_minus) return fail(PIEHIP_EINVAL, "null minus element");
-    int rc = batch_query_check(h, q);
-    if (rc) return rc;
-    h->bq_minus[q] = (const u64 *)d_minus;
-    return PIEHIP_OK;
-}
-int piehip_set_index_q(piehip_handle h, uint32_t q, const uint64_t *idx)
-{
-    if (q == 0) return piehip_set_index(h, idx);
-    NEED(h);
-    if (!idx) return fail(PIEHIP_EINVAL, "null index matrix");
-    if (!h->K) return fail(PIEHIP_ESTATE, "load the database before the index matrix");
-    int rc = batch_query_check(h, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t words = (size_t)h->K * h->E * 2 * h->LN();
-    if (!h->bq_idx_own[q] && (rc = dev_alloc(&h->bq_idx_own[q], words))) return rc;
-    HIPCHK(hipMemcpyAsync(h->bq_idx_own[q], idx, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->bq_idx[q] = h->bq_idx_own[q];
-    return PIEHIP_OK;
-}
-int piehip_set_minus_q(piehip_handle h, uint32_t q, const uint64_t *minus)
-{
-    if (q == 0) return piehip_set_minus(h, minus);
-    NEED(h);
-    if (!minus) return fail(PIEHIP_EINVAL, "null minus element");
-    int rc = batch_query_check(h, q);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t words = 2 * h->LN();
-    if (!h->bq_minus_own[q] && (rc = dev_alloc(&h->bq_minus_own[q], words))) return rc;
-    HIPCHK(hipMemcpyAsync(h->bq_minus_own[q], minus, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->bq_minus[q] = h->bq_minus_own[q];
-    return PIEHIP_OK;
-}
-
-}  // extern "C"
-namespace piehip {
-int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus)
-{
-    if (!h->K) return fail(PIEHIP_ESTATE, "load the database before the index matrix");
-    if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
-    u64 **pi = q ? &h->bq_idx_own[q] : &h->d_idx_own, **pm = q ? &h->bq_minus_own[q] : &h->d_minus_own;
-    int rc;
-    if (!*pi && (rc = dev_alloc(pi, (size_t)h->K * h->E * 2 * h->LN()))) return rc;
-    if (!*pm && (rc = dev_alloc(pm, 2 * h->LN()))) return rc;
-    *d_idx = *pi;
-    *d_minus = *pm;
-    return PIEHIP_OK;
-}
-}  // namespace piehip
-extern "C" {
 
 // The queries of a batch come from different clients (BatchedFHEPSIServer.cpp:94-95: one client per connection), and every client
 // has its own EvalMult key (.cpp:45-49): query q's key switch takes key q.  The key-switch kernel already selects its key per
@@ -1096,11 +933,7 @@ int piehip_load_relin_key_q(piehip_handle h, uint32_t q, const uint64_t *evk)
         if (h->sigma_on && (rc = dev_alloc(&h->d_evkq_sigma, words * h->nq))) return rc;
         h->evkq_n = h->nq;
         // queries without a key of their own use the handle's (piehip_load_relin_key), if it has one
-        for (u32 i = 0; i < h->nq && h->d_evk; i++) {
-            HIPCHK(hipMemcpyAsync(h->d_evkq + i * words, h->d_evk, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
-            if (h->sigma_on)
-                HIPCHK(hipMemcpyAsync(h->d_evkq_sigma + i * words, h->d_evk_sigma, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
-        }
+        if ((rc = fill_unloaded_key_slots(h))) return rc;
     }
     HIPCHK(hipMemcpyAsync(h->d_evkq + q * words, evk, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     if (h->sigma_on) launch_permute(h->hp.N, h->d_evkq + q * words, h->d_sigma_inv, h->d_evkq_sigma + q * words, h->hp.L * 2 * h->hp.L, h->stream);
@@ -1154,302 +987,6 @@ int piehip_load_relin_key_seeded_q(piehip_handle h, uint32_t q, const uint64_t *
     return rc ? rc : piehip_load_relin_key_q(h, q, key.data());
 }
 
-// Queues of a run().  The default is two when the handle evaluates enough bin layers to fill the chip twice over; below that
-// every launch is bound by its own latency, a second queue only interleaves two latency-bound chains on the same CUs, and one
-// queue is faster (measured at the C3 ring: 2 layers 115 vs 146 us, 5 layers of the E = 40 row 217 vs 239 us, 7 layers even).
-static const u32 MAX_RUN_QUEUES = 2;  // 3 is equal within noise, 4 and more collapse
-}  // extern "C"
-namespace piehip {
-u32 run_queue_count(const piehip_ctx *h)
-{
-    const u32 want = h->run_streams ? h->run_streams : (h->b >= 8 ? 2u : 1u);
-    return std::min(want, std::min(MAX_RUN_QUEUES, h->b));
-}
-}  // namespace piehip
-extern "C" {
-// The queues are created when a run first needs them: a handle that runs on one queue (a query slot, a rank's small share)
-// then owns one stream, not three -- the runtime multiplexes streams onto a few hardware queues, and streams that share one
-// serialise against each other.
-}  // extern "C"
-namespace piehip {
-int ensure_run_queues(piehip_ctx *h, u32 ng)
-{
-    while (h->side_streams.size() < ng) {
-        hipStream_t s = nullptr;
-        hipEvent_t e = nullptr;
-        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        h->side_streams.push_back(s);
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->ev_join.push_back(e);
-    }
-    return PIEHIP_OK;
-}
-}  // namespace piehip
-extern "C" {
-
-// bin layers of queue group g of ng.  Two groups take 4/7 and 3/7 of the layers: measured 3.5 % faster than equal halves at
-// b = 14 (8 + 6: the ragged transform launches of the two queues fit the workgroup slots better than 7 + 7).
-}  // extern "C"
-namespace piehip {
-u32 run_group_size(u32 b, u32 ng, u32 g)
-{
-    if (ng == 2) {
-        const u32 first = (4 * b + 3) / 7;
-        return g == 0 ? first : b - first;
-    }
-    return b / ng + (g < b % ng ? 1 : 0);
-}
-}  // namespace piehip
-extern "C" {
-
-// Bin layers [b0, b0 + nb) of run() on the handle's current stream: stage A, then the product chain.
-static void enqueue_run_bins(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
-{
-    const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M, K = h->K, b = h->b, E = h->E, nq = h->nq;
-    const size_t LN = h->LN();
-    const double W = 8.0 * N;
-    // rows of the workspace: (bin layer, query) pairs, nq per layer; the product chain sees nb * nq ciphertexts
-    const size_t r0 = (size_t)b0 * nq;
-    const u32 layers = nb;
-    nb *= nq;
-    MulWs w = h->ws;  // view of the workspace rows of these bin layers
-    w.nb = nb;
-    w.eqp += r0 * 4 * M * N;
-    w.dqp += r0 * 3 * M * N;
-    w.d01 += r0 * 2 * LN;
-    w.d2c += r0 * LN;
-    w.dig += r0 * L * LN;
-    u64 *acc = h->d_acc + r0 * K * 2 * LN;
-    u64 *prod = h->d_prod ? h->d_prod + r0 * 2 * LN : nullptr;
-    u64 *out = results + r0 * 2 * LN;
-    const u64 *masks = (h->sigma_on ? h->d_masks_sigma : h->d_masks) + (size_t)b0 * LN;
-    struct MaskDiv {
-        piehip_ctx *h;
-        ~MaskDiv() { h->mask_div = h->key_group = 1; }
-    } mask_div_scope{h};
-    h->mask_div = nq;
-    h->key_group = (nq > 1 && h->d_evkq && h->evkq_n == nq) ? nq : 1;  // per-query EvalMult keys: row r of a group is query r % nq
-    // Operand X of the first ciphertext product (the accumulators of inner hash function 0) is needed twice: in COEFFICIENT
-    // form by the base extension, and in EVALUATION form, lane-ordered, as the Q limbs of the QP operand (xq_reuse).  Until r04
-    // the inverse transform wrote that second copy; now stage A writes X there in the first place and the transform reads it
-    // from there (out of place, lane order in: its fast path) -- 44 MB less per step at the headline shape: the inverse launches
-    // 161 -> 150 us per step of three queries, stage A + 2.5 (its X rows leave in 64-byte runs) and the base extension + 2.5.
-    // Query batches only: one query's transform launches are single partial rounds that gain 1 us, and its stage A kernel, which
-    // runs at the HBM rate, loses 2.5 (profiles/r04/stage_a_writes_x_lane_ordered.txt).
-    const bool x_direct = K > 1 && nq > 1 && xq_reuse(h) && h->small_moduli && ntt16_applies(h->plan, h->fold_on);
-    if (h->profiling) {  // an empty bracket: what the event pair itself costs on this stream (reported beside the kernels' times)
-        ProfScope ps(h, PIEHIP_K_EVENT_PAIR, 0.0);
-    }
-    {   // stage A: all inner products of these bin layers in one launch (BatchedFHEHIPPIE.cpp:101-116)
-        ProfScope ps(h, PIEHIP_K_STAGE_A, W * ((double)layers * K * E * L + nq * ((double)K * E * 2 * L + 2.0 * L + (double)layers * K * 2 * L)));
-        StageAQueries qs = {};
-        qs.idx[0] = h->d_idx, qs.minus[0] = h->d_minus;
-        for (u32 q = 1; q < nq; q++) qs.idx[q] = h->bq_idx[q], qs.minus[q] = h->bq_minus[q];
-        const u64 *db = h->d_db + (size_t)b0 * E * LN;
-        StageAXOut xo;
-        if (x_direct) xo.out = w.eqp, xo.M = M, xo.logns = h->hp.logN - (h->fold_on ? 1 : 0);
-        if (nq > 1) {
-            launch_stage_a_batch(h->d_dc, N, L, K, layers, E, qs, nq, db, acc, h->stream, h->small_moduli, b, 0, 0, x_direct ? &xo : nullptr);
-        } else {
-            launch_stage_a(h->d_dc, N, L, K, nb, E, h->d_idx, h->d_minus, db, acc, h->stream, h->small_moduli, b, 0, 0, 1, 0,
-                           x_direct ? &xo : nullptr);
-        }
-    }
-    if (K == 1) {
-        // one inner hash function: multipliedResult is the inner product itself (BatchedFHEHIPPIE.cpp:117-120), so run() is
-        // stage A and the mask multiply (:126) -- no ciphertext product, no transform, no key
-        if (h->wait_before_results) (void)hipStreamWaitEvent(h->stream, h->wait_before_results, 0);
-        ProfScope ps(h, PIEHIP_K_MASK, W * nb * 5.0 * L);
-        launch_ct_mul_plain(h->d_dc, N, L, acc, h->d_masks + (size_t)b0 * LN, LN, out, nb, h->stream, nq);
-        return;
-    }
-    // every accumulator enters a ct x ct product exactly once: switch them all to COEFFICIENT format
-    const bool xq = xq_reuse(h);
-    NttExtra ex;
-    ex.copy_out = w.eqp;
-    ex.copy_K = K;
-    ex.copy_L = L;
-    ex.copy_M = M;
-    ex.x_lane_in = x_direct;
-    ntt(h, acc, nb * K * 2 * L, 0, L, true, false, true, xq ? &ex : nullptr);
-    ex.x_lane_in = false;
-    // product chain over the inner hash functions (BatchedFHEHIPPIE.cpp:117-124); the mask multiply
-    // (:126) is fused into the last key switch
-    const u64 *x = acc;
-    size_t sx = (size_t)K * 2 * LN;
-    for (u32 hf = 1; hf < K; hf++) {
-        const bool last = hf + 1 == K;
-        u64 *dst = last ? out : prod;
-        enqueue_mul(h, w, x, sx, acc + (size_t)hf * 2 * LN, (size_t)K * 2 * LN, nb, true, last ? masks : nullptr, dst, xq, last);
-        if (!last) {
-            ex.copy_K = 1;  // the product is the X operand of the next multiplication
-            ntt(h, prod, nb * 2 * L, 0, L, true, false, true, xq ? &ex : nullptr);
-            x = prod;
-            sx = 2 * LN;
-        }
-    }
-}
-
-// the result ciphertexts of bin layers [b0, b0 + nb) (rows [bin layer][query]) to the caller's host array, on the current queue
-static hipError_t download_rows(piehip_ctx *h, const u64 *d_results, u32 b0, u32 nb)
-{
-    const size_t row = (size_t)h->nq * 2 * h->LN();
-    return hipMemcpyAsync(h->host_results + (size_t)b0 * row, d_results + (size_t)b0 * row, (size_t)nb * row * sizeof(u64),
-                          hipMemcpyDeviceToHost, h->stream);
-}
-
-int piehip_run_into(piehip_handle h, void *d_results)
-{
-    if (!h) return fail(PIEHIP_EINVAL, "null handle");
-    if (!d_results) return fail(PIEHIP_EINVAL, "null result buffer");
-    if (!h->K || !h->d_db) return fail(PIEHIP_ESTATE, "run: database not loaded");
-    if (!h->d_acc || !h->ws.eqp) return fail(PIEHIP_ESTATE, "run: no workspace (an earlier allocation failed: piehip_set_query_batch / load)");
-    if (!run_keys_loaded(h)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
-    if (!h->d_idx || !h->d_minus) return fail(PIEHIP_ESTATE, "run: setIndex / setMinusCompareElement not called");
-    for (u32 q = 1; q < h->nq; q++)
-        if (!h->bq_idx[q] || !h->bq_minus[q]) return fail(PIEHIP_ESTATE, "run: a query of the batch has no index matrix or minus element");
-    HIPCHK(hipSetDevice(h->device));
-    const u32 b = h->b;
-    h->recs.clear();
-    h->pool_used = 0;
-    // Bin layers are independent: groups of them go to separate queues.  Most launches of one group leave part of the
-    // chip idle (a transform launch is 0.4 .. 2 rounds of workgroups); another group's kernels fill it.
-    // Ordering against the handle's stream:
-    //   * inputs changed since the last run (setIndex, keys, database): the queues wait for the handle's stream first;
-    //   * always: the kernel that writes the results waits for everything the caller queued on the handle's stream
-    //     before this call (it may still be reading the result buffer of an earlier run);
-    //   * the handle's stream joins the queues lazily, in the next entry point that is not a run (NEED / piehip_join),
-    //     so back-to-back runs of one query batch keep every queue busy across run boundaries.
-    const u32 ng = run_queue_count(h);
-    if (ng > 1) {
-        const int qrc = ensure_run_queues(h, ng);
-        if (qrc) return qrc;
-    }
-    if (h->use_graph && !h->profiling && !h->host_results && h->nq == 1) {
-        // One graph launch instead of ~13 kernel launches and 2 event operations per queue group: the same two chains, forked
-        // from and joined back to the handle's stream inside the graph (so consecutive runs do not overlap each other, which
-        // the eager path's lazy join allows).
-        if (!h->gexec || h->g_idx != h->d_idx || h->g_minus != h->d_minus || h->g_res != d_results || h->g_ng != ng) {
-            drop_graph(h);
-            join_pending(h);
-            struct Restore {
-                piehip_ctx *h;
-                hipStream_t s;
-                ~Restore() { h->stream = s; }
-            } restore{h, h->stream};
-            hipGraph_t graph = nullptr;
-            HIPCHK(hipStreamBeginCapture(restore.s, hipStreamCaptureModeThreadLocal));
-            hipError_t ce = hipSuccess;
-            if (ng > 1) {
-                ce = hipEventRecord(h->ev_fork, restore.s);
-                u32 b0 = 0;
-                for (u32 g = 0; g < ng && ce == hipSuccess; g++) {
-                    const u32 nb = run_group_size(b, ng, g);
-                    ce = hipStreamWaitEvent(h->side_streams[g], h->ev_fork, 0);
-                    h->stream = h->side_streams[g];
-                    enqueue_run_bins(h, b0, nb, (u64 *)d_results);
-                    if (ce == hipSuccess) ce = hipEventRecord(h->ev_join[g], h->side_streams[g]);
-                    if (ce == hipSuccess) ce = hipStreamWaitEvent(restore.s, h->ev_join[g], 0);
-                    b0 += nb;
-                }
-                h->stream = restore.s;
-            } else {
-                enqueue_run_bins(h, 0, b, (u64 *)d_results);
-            }
-            const hipError_t ee = hipStreamEndCapture(restore.s, &graph);
-            if (ce != hipSuccess || ee != hipSuccess || !graph) {
-                if (graph) (void)hipGraphDestroy(graph);
-                return fail(PIEHIP_EHIP, std::string("run: graph capture failed: ") + hipGetErrorString(ce != hipSuccess ? ce : ee));
-            }
-            const hipError_t ie = hipGraphInstantiate(&h->gexec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (ie != hipSuccess) {
-                h->gexec = nullptr;
-                return fail(PIEHIP_EHIP, std::string("run: hipGraphInstantiate: ") + hipGetErrorString(ie));
-            }
-            h->g_idx = h->d_idx, h->g_minus = h->d_minus, h->g_res = d_results, h->g_ng = ng;
-        }
-        join_pending(h);
-        HIPCHK(hipGraphLaunch(h->gexec, h->stream));
-        mark_dirty(h);  // the workspace is in use on the handle's stream
-        return PIEHIP_OK;
-    }
-    if (ng > 1) {
-        struct Restore {
-            piehip_ctx *h;
-            hipStream_t s;
-            ~Restore()
-            {
-                h->stream = s;
-                h->wait_before_results = nullptr;
-            }
-        } restore{h, h->stream};
-        HIPCHK(hipEventRecord(h->ev_fork, restore.s));
-        u32 b0 = 0;
-        for (u32 g = 0; g < ng; g++) {
-            const u32 nb = run_group_size(b, ng, g);
-            if (h->inputs_dirty) HIPCHK(hipStreamWaitEvent(h->side_streams[g], h->ev_fork, 0));
-            h->stream = h->side_streams[g];
-            h->wait_before_results = h->inputs_dirty ? nullptr : h->ev_fork;
-            // Results go down to host memory (piehip_run_staged / piehip_run_host*): the groups do not run side by side but one
-            // behind the other -- group g + 1 starts when group g has only its result-writing kernel left, and the download of
-            // group g (8 of 14 MiB at C3) travels under the evaluation of group g + 1.  Results in host memory after 0.53 ms
-            // instead of 0.60 at C3, 1.30 instead of 1.50 for a batch of three; a stream of queries over several handles is
-            // bound by the uploads either way (profiles/r04/online_phase_staggered_groups.txt).
-            if (h->host_results && g > 0) HIPCHK(hipStreamWaitEvent(h->side_streams[g], h->ev_chain, 0));
-            if (h->host_results && g + 1 < ng) {
-                if (!h->ev_chain) HIPCHK(hipEventCreateWithFlags(&h->ev_chain, hipEventDisableTiming));
-                h->chain_armed = true;
-            }
-            enqueue_run_bins(h, b0, nb, (u64 *)d_results);
-            if (h->chain_armed) {  // a chain without a key switch (K = 1): behind all of it
-                h->chain_armed = false;
-                HIPCHK(hipEventRecord(h->ev_chain, h->side_streams[g]));
-            }
-            if (h->host_results) HIPCHK(download_rows(h, (const u64 *)d_results, b0, nb));  // this group's slice, on this group's queue
-            HIPCHK(hipEventRecord(h->ev_join[g], h->side_streams[g]));
-            b0 += nb;
-        }
-        h->pending_join = true;
-        h->inputs_dirty = false;
-    } else {
-        join_pending(h);
-        enqueue_run_bins(h, 0, b, (u64 *)d_results);
-        if (h->host_results) HIPCHK(download_rows(h, (const u64 *)d_results, 0, b));
-        mark_dirty(h);  // the workspace is now in use on the handle's stream: the queues of a later multi-queue run wait for it
-    }
-    HIPCHK(hipGetLastError());
-    return PIEHIP_OK;
-}
-
-int piehip_run(piehip_handle h)
-{
-    if (!h) return fail(PIEHIP_EINVAL, "null handle");
-    if (!h->d_out) return fail(PIEHIP_ESTATE, "run: database not loaded");
-    return piehip_run_into(h, h->d_out);
-}
-
-int piehip_join(piehip_handle h)
-{
-    NEED_RO(h);
-    return PIEHIP_OK;
-}
-
-int piehip_set_graph(piehip_handle h, int on)
-{
-    NEED_RO(h);
-    h->use_graph = on != 0;
-    if (!on) drop_graph(h);
-    return PIEHIP_OK;
-}
-
-int piehip_set_run_streams(piehip_handle h, uint32_t n)
-{
-    NEED_RO(h);
-    h->run_streams = n;
-    return PIEHIP_OK;
-}
-
 int piehip_set_transform_slots(piehip_handle h, uint32_t n)
 {
     NEED_RO(h);
@@ -1501,4 +1038,4 @@ int piehip_copy_results_device(piehip_handle h, void *d_dst)
     return PIEHIP_OK;
 }
 
-}  // extern "C"
+}  // extern C

@@ -1,6 +1,7 @@
 // piehip_ctx.hpp -- what the translation units behind include/piehip.h share: the context behind a piehip_handle, error /
 // ordering macros, device scratch, event-bracketed launches, and the schedule pieces of a ciphertext multiplication.
-//   piehip.cpp         context, keys, database (offline phase), query inputs, run() and its queues
+//   piehip.cpp         context, keys, database (offline phase), query inputs
+//   piehip_run.cpp     the schedule pieces of a ciphertext multiplication, run() and its queues
 //   piehip_host.cpp    the host-memory path of a query: page-locked staging, piecewise uploads, run_staged / run_host
 //   piehip_ops.cpp     the OpenFHE primitives one by one (parity tests), NTT timing, per-kernel profiling
 //   piehip_fhepie.cpp  the rotation-based sibling operator (FHEHIPPIE)
@@ -68,12 +69,16 @@ struct MulWs {
     u64 *dig = nullptr;  // [nb][L][L][N]
 };
 
-// one query's way in from host memory (piehip_host_buffers_q, piehip_stage_*_q)
-struct QueryStage {
+// one query of the batch (piehip_set_query_batch; a handle without a batch has query 0 only): its device inputs, and its way
+// in from host memory (piehip_host_buffers_q, piehip_stage_*_q)
+struct Query {
+    const u64 *idx = nullptr, *minus = nullptr;    // what the next run() reads: [K][E][2][L][N], [2][L][N]; the caller's device
+                                                   // arrays (piehip_set_*_device_q) or the owned ones below
+    u64 *idx_own = nullptr, *minus_own = nullptr;  // owned copies: the host setters and the staged uploads write them
     u64 *pin_idx = nullptr, *pin_minus = nullptr;  // page-locked staging [K][E][2][L][N], [2][L][N]
     std::vector<bool> rows;                        // pieces on their way since the staging sequence began
     std::vector<bool> cts;                         // ... ciphertext by ciphertext (piehip_stage_index_ct_q), [K][E]
-    bool minus = false;
+    bool minus_staged = false;
     // seeded pieces (piehip_stage_*_seeded_q): c0 is on its way, c1 is expanded from the seed at piehip_run_staged.
     // Index p < K E: index ciphertext p = row E + j; index K E: the minus element.  Staging a piece unseeded clears its entry.
     std::vector<bool> seeded;                      // [K E + 1]
@@ -105,9 +110,8 @@ struct piehip_ctx {
     hipGraphExec_t gexec = nullptr;
     const void *g_idx = nullptr, *g_minus = nullptr, *g_res = nullptr;
     u32 g_ng = 0;
-    // the host-memory path (piehip_host.cpp): per query of the batch its page-locked staging and which pieces have been staged;
+    // the host-memory path (piehip_host.cpp): query[q] has every query's page-locked staging and which pieces have been staged;
     // all transfers travel on the handle's own queues (no copy stream: see piehip_host.cpp)
-    piehip::QueryStage qstage[piehip::STAGE_A_MAX_QUERIES];
     bool stage_open = false;                      // piehip_stage_*: the uploads of the next run()'s queries have begun
     u64 *pin_up_flag = nullptr;                   // page-locked word: sequence number of the last query of this handle whose uploads have
     u64 up_seq = 0;                               // left host memory (written by a one-thread kernel behind them); the next number
@@ -154,15 +158,12 @@ struct piehip_ctx {
     u64 *d_evk = nullptr;
     u32 K = 0, b = 0, E = 0;
     u64 *d_db = nullptr, *d_masks = nullptr;
-    u64 *d_idx_own = nullptr, *d_minus_own = nullptr;
-    const u64 *d_idx = nullptr, *d_minus = nullptr;
-    // query batch (piehip_set_query_batch): run() evaluates nq queries against the database at once; query 0 is d_idx / d_minus
-    // above, queries 1 .. nq - 1 are bq_*[q].  Workspace and results hold nq rows per bin layer: [b][nq][..].
+    // query batch (piehip_set_query_batch): run() evaluates queries 0 .. nq - 1 against the database at once.  Workspace and
+    // results hold nq rows per bin layer: [b][nq][..].
+    piehip::Query query[piehip::STAGE_A_MAX_QUERIES];
     u32 nq = 1;
     u32 mask_div = 1;  // set while run() enqueues a batch: ciphertext row r of the product chain takes mask r / mask_div
     u32 key_group = 1; // ... and, with per-query EvalMult keys, key r % key_group of d_evkq
-    const u64 *bq_idx[piehip::STAGE_A_MAX_QUERIES] = {}, *bq_minus[piehip::STAGE_A_MAX_QUERIES] = {};
-    u64 *bq_idx_own[piehip::STAGE_A_MAX_QUERIES] = {}, *bq_minus_own[piehip::STAGE_A_MAX_QUERIES] = {};
     // piehip_load_relin_key_q: the queries of a batch come from different clients, each with its own EvalMult key.  [evkq_n] keys
     // [L][2][L][N] one after the other (+ the lane-ordered copy); entries nobody loaded hold the handle's key
     u64 *d_evkq = nullptr, *d_evkq_sigma = nullptr;
@@ -272,7 +273,7 @@ struct Tmp {  // RAII device scratch: carved from the handle's arena while it ha
 int ws_alloc(piehip_ctx *h, MulWs &w, u32 nb);
 void ws_free(MulWs &w);
 
-// ---- schedule pieces (piehip.cpp) ------------------------------------------------------------------
+// ---- schedule pieces (piehip_run.cpp) --------------------------------------------------------------
 // sigma: lane order on the EVALUATION side; fold: outer stage applied by the neighbouring kernels (both only
 // take effect when the context supports them; callers pass the same flags to those neighbours)
 void ntt(piehip_ctx *h, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inv, bool sigma = false, bool fold = false,
@@ -286,6 +287,7 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
 int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out);
 // device input buffers of query q of the batch (owned copies: the host setters and the staged uploads write them)
 int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus);
+void use_owned_inputs(piehip_ctx *h);   // the next run() evaluates the owned copies of every query of the batch
 void free_host_path(piehip_ctx *h);   // piehip_host.cpp: page-locked staging
 // piehip_host.cpp: expand the seeded polynomials of `jobs` on the handle's stream and wait for them (client, keys, tests; the
 // staged path queues its expansion without waiting)

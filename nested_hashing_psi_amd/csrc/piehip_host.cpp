@@ -156,7 +156,7 @@ void free_host_path(piehip_ctx *h)
         g_words.of.erase(h);
         h->pin_up_flag = nullptr;
     }
-    for (QueryStage &s : h->qstage) {
+    for (Query &s : h->query) {
         if (s.pin_idx) (void)hipHostFree(s.pin_idx);
         if (s.pin_minus) (void)hipHostFree(s.pin_minus);
         s.pin_idx = s.pin_minus = nullptr;
@@ -203,11 +203,11 @@ static int stage_begin(piehip_ctx *h, u32 q)
         if (hipEventRecord(h->hp_ev[0], h->stream) == hipSuccess) h->hp_ev_state = 1;
     }
     for (u32 i = 0; i < h->nq; i++) {
-        h->qstage[i].minus = false;
-        h->qstage[i].rows.assign(h->K, false);
-        h->qstage[i].cts.clear();
-        h->qstage[i].seeded.assign((size_t)h->K * h->E + 1, false);
-        h->qstage[i].seeds.resize(((size_t)h->K * h->E + 1) * 8);
+        h->query[i].minus_staged = false;
+        h->query[i].rows.assign(h->K, false);
+        h->query[i].cts.clear();
+        h->query[i].seeded.assign((size_t)h->K * h->E + 1, false);
+        h->query[i].seeds.resize(((size_t)h->K * h->E + 1) * 8);
     }
     return PIEHIP_OK;
 }
@@ -215,7 +215,7 @@ static int stage_begin(piehip_ctx *h, u32 q)
 // piece p of query q (p < K E: index ciphertext p; p = K E: the minus element) was staged seeded (seed != null) or in full
 static void mark_seeded(piehip_ctx *h, u32 q, size_t p, const uint8_t *seed)
 {
-    QueryStage &s = h->qstage[q];
+    Query &s = h->query[q];
     s.seeded[p] = seed != nullptr;
     if (seed) memcpy(&s.seeds[p * 8], seed, 32);
 }
@@ -223,7 +223,7 @@ static void mark_seeded(piehip_ctx *h, u32 q, size_t p, const uint8_t *seed)
 // ciphertext (row, j) of query q has been staged: row `row` is complete once all E of its ciphertexts are
 static void ct_staged(piehip_ctx *h, u32 q, u32 row, u32 j)
 {
-    QueryStage &s = h->qstage[q];
+    Query &s = h->query[q];
     if (s.cts.size() != (size_t)h->K * h->E) s.cts.assign((size_t)h->K * h->E, false);
     s.cts[(size_t)row * h->E + j] = true;
     bool all = true;
@@ -241,7 +241,7 @@ int piehip_host_buffers_q(piehip_handle h, uint32_t q, uint64_t **idx, uint64_t 
     HIPCHK(hipSetDevice(h->device));
     const size_t iw = (size_t)h->K * h->E * 2 * h->LN(), rw = (size_t)h->b * h->nq * 2 * h->LN();
     if (h->pin_idx_words != iw)  // another database shape: every query's index staging goes
-        for (QueryStage &s : h->qstage)
+        for (Query &s : h->query)
             if (s.pin_idx) {
                 (void)hipHostFree(s.pin_idx);
                 s.pin_idx = nullptr;
@@ -252,7 +252,7 @@ int piehip_host_buffers_q(piehip_handle h, uint32_t q, uint64_t **idx, uint64_t 
     }
     // Portable: one process may drive several devices from the same staging arrays (host/ShardedBatchedFHEHIPPIE.hpp uploads
     // shard 0's arrays to every device).  Only what the caller asks for: such a shard needs a result array only.
-    QueryStage &s = h->qstage[q];
+    Query &s = h->query[q];
     if (idx && !s.pin_idx) HIPCHK(hipHostMalloc((void **)&s.pin_idx, iw * sizeof(u64), hipHostMallocPortable));
     if (minus && !s.pin_minus) HIPCHK(hipHostMalloc((void **)&s.pin_minus, 2 * h->LN() * sizeof(u64), hipHostMallocPortable));
     if (results && !h->pin_res) HIPCHK(hipHostMalloc((void **)&h->pin_res, rw * sizeof(u64), hipHostMallocPortable));
@@ -285,7 +285,7 @@ int piehip_stage_minus_q(piehip_handle h, uint32_t q, const uint64_t *minus)
     u64 *di = nullptr, *dm = nullptr;
     if ((rc = query_input_buffers(h, q, &di, &dm))) return rc;
     HIPCHK(hipMemcpyAsync(dm, minus, 2 * h->LN() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    h->qstage[q].minus = true;
+    h->query[q].minus_staged = true;
     mark_seeded(h, q, (size_t)h->K * h->E, nullptr);
     return PIEHIP_OK;
 }
@@ -301,7 +301,7 @@ int piehip_stage_index_row_q(piehip_handle h, uint32_t q, uint32_t row, const ui
     if ((rc = query_input_buffers(h, q, &di, &dm))) return rc;
     const size_t words = (size_t)h->E * 2 * h->LN();
     HIPCHK(hipMemcpyAsync(di + (size_t)row * words, row_data, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    h->qstage[q].rows[row] = true;
+    h->query[q].rows[row] = true;
     for (u32 j = 0; j < h->E; j++) mark_seeded(h, q, (size_t)row * h->E + j, nullptr);
     return PIEHIP_OK;
 }
@@ -339,7 +339,7 @@ int piehip_stage_minus_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0,
     u64 *di = nullptr, *dm = nullptr;
     if ((rc = query_input_buffers(h, q, &di, &dm))) return rc;
     HIPCHK(hipMemcpyAsync(dm, c0, h->LN() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    h->qstage[q].minus = true;
+    h->query[q].minus_staged = true;
     mark_seeded(h, q, (size_t)h->K * h->E, seed);
     return PIEHIP_OK;
 }
@@ -372,7 +372,7 @@ int piehip_stage_index_row_seeded_q(piehip_handle h, uint32_t q, uint32_t row, c
     HIPCHK(hipMemcpy2DAsync(di + (size_t)row * h->E * 2 * LN, 2 * LN * sizeof(u64), c0, LN * sizeof(u64), LN * sizeof(u64), h->E,
                             hipMemcpyHostToDevice, h->stream));
     for (u32 j = 0; j < h->E; j++) mark_seeded(h, q, (size_t)row * h->E + j, seeds + (size_t)j * 32);
-    h->qstage[q].rows[row] = true;
+    h->query[q].rows[row] = true;
     return PIEHIP_OK;
 }
 
@@ -383,8 +383,8 @@ int piehip_stage_reset(piehip_handle h)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
     h->stage_open = false;  // copies already queued still land (in buffers nothing reads until they are staged again)
-    for (QueryStage &s : h->qstage) {
-        s.minus = false;
+    for (Query &s : h->query) {
+        s.minus_staged = false;
         s.rows.assign(s.rows.size(), false);
         s.cts.clear();
         s.seeded.assign(s.seeded.size(), false);
@@ -397,7 +397,7 @@ int piehip_stage_reset(piehip_handle h)
 bool piehip::stage_has_seeded(const piehip_ctx *h)
 {
     for (u32 q = 0; q < h->nq; q++)
-        for (bool b : h->qstage[q].seeded)
+        for (bool b : h->query[q].seeded)
             if (b) return true;
     return false;
 }
@@ -411,7 +411,7 @@ static int queue_seed_jobs(piehip_ctx *h, size_t *njobs)
     const size_t LN = h->LN(), per_q = (size_t)h->K * h->E + 1;
     size_t n = 0;
     for (u32 q = 0; q < h->nq; q++)
-        for (bool b : h->qstage[q].seeded) n += b;
+        for (bool b : h->query[q].seeded) n += b;
     if (!n) return PIEHIP_OK;
     if (n > h->seed_jobs_cap) {
         // (re)allocated at the first seeded query of a shape; hipFree / hipHostFree wait for whatever still reads the old tables
@@ -435,8 +435,8 @@ static int queue_seed_jobs(piehip_ctx *h, size_t *njobs)
     }
     SeedJob *tab = h->pin_seed_jobs + (seq & 1) * h->seed_jobs_cap;
     for (u32 q = 0; q < h->nq; q++) {
-        const QueryStage &s = h->qstage[q];
-        u64 *di = q ? h->bq_idx_own[q] : h->d_idx_own, *dm = q ? h->bq_minus_own[q] : h->d_minus_own;
+        const Query &s = h->query[q];
+        u64 *di = s.idx_own, *dm = s.minus_own;
         for (size_t p = 0; p < per_q; p++) {
             if (!s.seeded[p]) continue;
             SeedJob &j = tab[(*njobs)++];
@@ -458,15 +458,13 @@ int piehip_run_staged(piehip_handle h, uint64_t *results)
     if (!h->stage_open) return fail(PIEHIP_ESTATE, "run_staged: query not staged");
     const u32 nq = h->nq;
     for (u32 q = 0; q < nq; q++) {
-        if (!h->qstage[q].minus) return fail(PIEHIP_ESTATE, "run_staged: minus element not staged");
+        if (!h->query[q].minus_staged) return fail(PIEHIP_ESTATE, "run_staged: minus element not staged");
         for (u32 hf = 0; hf < h->K; hf++)
-            if (!h->qstage[q].rows[hf]) return fail(PIEHIP_ESTATE, "run_staged: index matrix row not staged");
+            if (!h->query[q].rows[hf]) return fail(PIEHIP_ESTATE, "run_staged: index matrix row not staged");
     }
     HIPCHK(hipSetDevice(h->device));
     h->stage_open = false;
-    h->d_idx = h->d_idx_own;
-    h->d_minus = h->d_minus_own;
-    for (u32 q = 1; q < nq; q++) h->bq_idx[q] = h->bq_idx_own[q], h->bq_minus[q] = h->bq_minus_own[q];
+    use_owned_inputs(h);
     // the uploads are on the handle's stream and the run's queues start behind it (the inputs changed); every queue group's slice
     // of the result list leaves on that group's queue as soon as the group is done
     mark_dirty(h);

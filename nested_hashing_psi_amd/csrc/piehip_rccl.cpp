@@ -381,9 +381,9 @@ int piehip_rccl_broadcast_query(piehip_handle h, int root)
         if (stage_has_seeded(h))   // the expansion is queued by piehip_run_staged, which a broadcast query never reaches
             return fail(PIEHIP_ESTATE, "rccl_broadcast_query: seeded pieces are not distributed (stage full ciphertexts)");
         for (u32 q = 0; q < h->nq; q++) {
-            if (!h->qstage[q].minus) return fail(PIEHIP_ESTATE, "rccl_broadcast_query: minus element not staged");
+            if (!h->query[q].minus_staged) return fail(PIEHIP_ESTATE, "rccl_broadcast_query: minus element not staged");
             for (u32 hf = 0; hf < h->K; hf++)
-                if (!h->qstage[q].rows[hf]) return fail(PIEHIP_ESTATE, "rccl_broadcast_query: index matrix row not staged");
+                if (!h->query[q].rows[hf]) return fail(PIEHIP_ESTATE, "rccl_broadcast_query: index matrix row not staged");
         }
     }
     const size_t iw = (size_t)h->K * h->E * 2 * h->LN(), mw = 2 * h->LN();
@@ -405,9 +405,7 @@ int piehip_rccl_broadcast_query(piehip_handle h, int root)
         return fail(PIEHIP_EHIP, std::string("rccl_broadcast_query: ") + R->GetErrorString(gr != ncclSuccess ? gr : ge));
     // every rank now evaluates the received copy: as if the query had been staged here
     h->stage_open = false;
-    h->d_idx = h->d_idx_own;
-    h->d_minus = h->d_minus_own;
-    for (u32 q = 1; q < h->nq; q++) h->bq_idx[q] = h->bq_idx_own[q], h->bq_minus[q] = h->bq_minus_own[q];
+    use_owned_inputs(h);
     return PIEHIP_OK;
 }
 

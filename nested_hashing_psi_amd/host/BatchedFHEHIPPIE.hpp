@@ -90,6 +90,176 @@ private:
     uint64_t t_;
 };
 
+// The staging half of both operators below: the queries of one run() on one handle -- one for BatchedFHEHIPPIE, queriesPerRun
+// for BatchedFHEHIPPIEQueryBatch -- on their way from page-locked host memory (see "Host path" above), and the result rows
+// [bin layer][query] on their way back.  Internal: the two operators are its interface.
+class StagedQueries {
+public:
+    // once the handle has its database and batch size: the page-locked arrays of every query (owned by the library)
+    void init(PieContext &cryptoContext, uint32_t K_, uint32_t b_, uint32_t E_, uint32_t queriesPerRun)
+    {
+        cc = &cryptoContext, K = K_, b = b_, E = E_, nq = queriesPerRun;
+        st.resize(nq);
+        for (uint32_t q = 0; q < nq; q++) {
+            PieContext::check(piehip_host_buffers_q(cc->handle(), q, &st[q].pinIdx, &st[q].pinMinus, &pinRes));
+            st[q].rowCount.assign(K, 0u);
+        }
+        lists.assign(nq, std::vector<LimbCt>(b));
+        listStale.assign(nq, false);
+    }
+
+    void setIndex(uint32_t q, std::vector<std::vector<LimbCt>> &&indexMatrix)  // [K][E] ciphertexts of query q
+    {
+        const size_t ct = ctWords();
+        checkQuery(q);
+        if (indexMatrix.size() != K) throw std::invalid_argument("index matrix must have one row per inner hash function");
+        for (uint32_t h = 0; h < K; h++) {
+            if (indexMatrix[h].size() != E) throw std::invalid_argument("index matrix row length must be eachCuckooTableSize");
+            for (uint32_t j = 0; j < E; j++)
+                if (indexMatrix[h][j].limbs.size() != ct) throw std::invalid_argument("ciphertext does not match the context");
+        }
+        restartIndex(q);  // the reference's setter overwrites the matrix (.hpp:40-43): a second call before run() replaces the first
+        for (uint32_t h = 0; h < K; h++)
+            for (uint32_t j = 0; j < E; j++) {  // one copy, straight into the staging array; row h uploads while row h + 1 is copied
+                std::memcpy(indexStaging(q, h, j), indexMatrix[h][j].limbs.data(), ct * sizeof(uint64_t));
+                stageIndexCiphertext(q, h, j);
+            }
+    }
+    void setMinusCompareElement(uint32_t q, const LimbCt &minusCompareElement)
+    {
+        checkQuery(q);
+        if (minusCompareElement.limbs.size() != ctWords()) throw std::invalid_argument("ciphertext does not match the context");
+        if (st[q].minusStaged) drainUploads();  // the previous element may still be crossing PCIe from this very array
+        std::memcpy(minusStaging(q), minusCompareElement.limbs.data(), ctWords() * sizeof(uint64_t));
+        stageMinus(q);
+    }
+
+    uint64_t *indexStaging(uint32_t q, uint32_t h, uint32_t j) { return st[q].pinIdx + ((size_t)h * E + j) * ctWords(); }
+    uint64_t *minusStaging(uint32_t q) { return st[q].pinMinus; }
+    void restartIndex(uint32_t q)
+    {
+        checkQuery(q);
+        if (!st[q].arrived && !st[q].rowsStaged) return;
+        drainUploads();
+        std::fill(st[q].rowCount.begin(), st[q].rowCount.end(), 0u);
+        st[q].rowsStaged = st[q].arrived = 0;
+    }
+    // ciphertext (h, j) of query q has been written to indexStaging(q, h, j): its upload starts now
+    void stageIndexCiphertext(uint32_t q, uint32_t h, uint32_t j)
+    {
+        checkPosition(q, h, j);
+        PieContext::check(piehip_stage_index_ct_q(cc->handle(), q, h, j, indexStaging(q, h, j)));  // leaves at once
+        indexCiphertextStaged(q, h);
+    }
+    void stageMinus(uint32_t q)
+    {
+        checkQuery(q);
+        PieContext::check(piehip_stage_minus_q(cc->handle(), q, st[q].pinMinus));
+        st[q].minusStaged = true;
+    }
+    // seeded pieces: only c0, the first half of the staging slot, has been written
+    void stageIndexCiphertextSeeded(uint32_t q, uint32_t h, uint32_t j, const uint8_t *seed)
+    {
+        checkPosition(q, h, j);
+        PieContext::check(piehip_stage_index_ct_seeded_q(cc->handle(), q, h, j, indexStaging(q, h, j), seed));
+        indexCiphertextStaged(q, h);
+    }
+    void stageMinusSeeded(uint32_t q, const uint8_t *seed)
+    {
+        checkQuery(q);
+        PieContext::check(piehip_stage_minus_seeded_q(cc->handle(), q, st[q].pinMinus, seed));
+        st[q].minusStaged = true;
+    }
+
+    // run() in two halves: the evaluation and the download of the result rows are asynchronous; collect() waits for them.
+    // `incomplete`: what() of the std::runtime_error for a run() with some, but not all, pieces of its queries set.
+    void enqueue(const char *incomplete)
+    {
+        // whatever happens below, the next query starts from a clean slate: a refused or failed run() must not leave half a
+        // query counted (its pieces would never be staged again)
+        struct Reset {
+            StagedQueries &o;
+            bool ok = false;
+            ~Reset()
+            {
+                for (auto &s : o.st) {
+                    s.minusStaged = false;
+                    s.rowsStaged = s.arrived = 0;
+                    std::fill(s.rowCount.begin(), s.rowCount.end(), 0u);
+                }
+                if (!ok) piehip_stage_reset(o.cc->handle());
+            }
+        } reset{*this};
+        uint32_t complete = 0, touched = 0;
+        for (const auto &s : st) {
+            complete += (s.minusStaged && s.rowsStaged == K) ? 1u : 0u;
+            touched += (s.minusStaged || s.rowsStaged || s.arrived) ? 1u : 0u;
+        }
+        if (complete == nq) {
+            PieContext::check(piehip_run_staged(cc->handle(), pinRes));
+        } else if (touched) {
+            throw std::runtime_error(incomplete);
+        } else {
+            // the queries of the previous run() again (their inputs are still in HBM)
+            PieContext::check(piehip_run(cc->handle()));
+            rerun = true;
+        }
+        reset.ok = true;
+    }
+    void collect()
+    {
+        if (rerun) PieContext::check(piehip_get_results(cc->handle(), pinRes));
+        else PieContext::check(piehip_run_host_wait(cc->handle()));
+        rerun = false;
+        std::fill(listStale.begin(), listStale.end(), true);
+    }
+
+    // The b result ciphertexts of query q are materialised from the page-locked result array on the first call after a run() (the
+    // reference's timer has stopped by then: BatchedFHEPSIServer.cpp:105-108); resultTowers(q, i) reads them in place.
+    std::vector<LimbCt> &getResultList(uint32_t q)
+    {
+        checkQuery(q);
+        if (listStale[q]) {
+            const size_t ct = ctWords();
+            for (uint32_t i = 0; i < b; i++) lists[q][i].limbs.assign(resultTowers(q, i), resultTowers(q, i) + ct);
+            listStale[q] = false;
+        }
+        return lists[q];
+    }
+    const uint64_t *resultTowers(uint32_t q, uint32_t i) const { return pinRes + ((size_t)i * nq + q) * ctWords(); }  // rows [bin layer][query]
+
+private:
+    struct QueryState {
+        uint64_t *pinIdx = nullptr, *pinMinus = nullptr;  // page-locked, owned by the library
+        std::vector<uint32_t> rowCount;
+        uint32_t rowsStaged = 0, arrived = 0;
+        bool minusStaged = false;
+    };
+    size_t ctWords() const { return 2 * (size_t)cc->towers() * cc->ringDimension(); }
+    void checkQuery(uint32_t q) const
+    {
+        if (q >= nq) throw std::invalid_argument("query index outside the batch");
+    }
+    void checkPosition(uint32_t q, uint32_t h, uint32_t j) const
+    {
+        checkQuery(q);
+        if (h >= K || j >= E) throw std::invalid_argument("index matrix position out of range");
+    }
+    void indexCiphertextStaged(uint32_t q, uint32_t h)
+    {
+        st[q].arrived++;
+        if (++st[q].rowCount[h] == E) st[q].rowsStaged++;
+    }
+    void drainUploads() { PieContext::check(piehip_run_host_wait(cc->handle())); }  // the copy queue is idle afterwards
+    PieContext *cc = nullptr;
+    uint32_t K = 0, b = 0, E = 0, nq = 0;
+    std::vector<QueryState> st;
+    uint64_t *pinRes = nullptr;  // [b][nq][2][L][N], page-locked, owned by the library
+    std::vector<std::vector<LimbCt>> lists;
+    std::vector<bool> listStale;
+    bool rerun = false;
+};
+
 class BatchedFHEHIPPIE {
 public:
     // Seeds of the bin-layer shuffle (.cpp:23-35) and of the random masks (.cpp:72-82).  The masks are what hides
@@ -125,7 +295,7 @@ public:
         // bin-layer shuffle (.cpp:23-35), gather (.cpp:45-70), masks (.cpp:72-82) and MakePackedPlaintext (.cpp:68,81),
         // all on the device
         PieContext::check(piehip_load_db_table(cc.handle(), hct.table, k, e, K, b, E, shuffleSeed, maskSeed));
-        initStaging();
+        staged.init(cc, K, b, E, 1);
     }
 
     // A further query slot on `database`'s packed table and on its context's key (piehip_attach_database): `cryptoContext`
@@ -136,7 +306,7 @@ public:
     {
         K = database.K, b = database.b, E = database.E;
         PieContext::check(piehip_attach_database(cc.handle(), database.cc.handle()));
-        initStaging();
+        staged.init(cc, K, b, E, 1);
     }
 
     void run()  // BatchedFHEHIPPIE.cpp:88-129
@@ -145,140 +315,39 @@ public:
         collect();
     }
     // run() in two halves: the evaluation and the download of the result list are asynchronous; collect() waits for them
-    void enqueue()
-    {
-        // whatever happens below, the next query starts from a clean slate: a refused or failed run() must not leave half a
-        // query counted (its pieces would never be staged again)
-        struct Reset {
-            BatchedFHEHIPPIE &o;
-            bool ok = false;
-            ~Reset()
-            {
-                o.clearStaged();
-                if (!ok) piehip_stage_reset(o.cc.handle());
-            }
-        } reset{*this};
-        if (minusStaged && rowsStaged == K) {
-            PieContext::check(piehip_run_staged(cc.handle(), pinRes));
-        } else if (minusStaged || rowsStaged || arrived) {
-            throw std::runtime_error("run: setMinusCompareElement and setIndex must both precede run()");
-        } else {
-            // the query of the previous run() again (its inputs are still in HBM)
-            PieContext::check(piehip_run(cc.handle()));
-            rerun = true;
-        }
-        reset.ok = true;
-    }
-    void collect()
-    {
-        if (rerun) PieContext::check(piehip_get_results(cc.handle(), pinRes));
-        else PieContext::check(piehip_run_host_wait(cc.handle()));
-        rerun = false;
-        listStale = true;
-    }
+    void enqueue() { staged.enqueue("run: setMinusCompareElement and setIndex must both precede run()"); }
+    void collect() { staged.collect(); }
 
-    // .hpp:35-38.  The ciphertexts are materialised from the page-locked result array on the first call after a run() (the
-    // reference's timer has stopped by then: BatchedFHEPSIServer.cpp:105-108); resultTowers(i) reads them in place.
-    std::vector<LimbCt> &getResultList()
-    {
-        if (listStale) {
-            const size_t ct = ctWords();
-            for (uint32_t i = 0; i < b; i++) resultList[i].limbs.assign(pinRes + (size_t)i * ct, pinRes + (size_t)(i + 1) * ct);
-            listStale = false;
-        }
-        return resultList;
-    }
-    const uint64_t *resultTowers(uint32_t i) const { return pinRes + (size_t)i * ctWords(); }  // [2][L][N], valid until the next run()
+    // .hpp:35-38.  The ciphertexts are materialised from the page-locked result array on the first call after a run();
+    // resultTowers(i) reads them in place.
+    std::vector<LimbCt> &getResultList() { return staged.getResultList(0); }
+    const uint64_t *resultTowers(uint32_t i) const { return staged.resultTowers(0, i); }  // [2][L][N], valid until the next run()
 
-    void setIndex(std::vector<std::vector<LimbCt>> &&indexMatrix)  // .hpp:40-43, [K][E] ciphertexts
-    {
-        const size_t ct = ctWords();
-        if (indexMatrix.size() != K) throw std::invalid_argument("index matrix must have one row per inner hash function");
-        for (uint32_t h = 0; h < K; h++) {
-            if (indexMatrix[h].size() != E) throw std::invalid_argument("index matrix row length must be eachCuckooTableSize");
-            for (uint32_t j = 0; j < E; j++)
-                if (indexMatrix[h][j].limbs.size() != ct) throw std::invalid_argument("ciphertext does not match the context");
-        }
-        restartIndex();  // the reference's setter overwrites the matrix (.hpp:40-43): a second call before run() replaces the first
-        for (uint32_t h = 0; h < K; h++)
-            for (uint32_t j = 0; j < E; j++) {  // one copy, straight into the staging array; row h uploads while row h + 1 is copied
-                std::memcpy(indexStaging(h, j), indexMatrix[h][j].limbs.data(), ct * sizeof(uint64_t));
-                stageIndexCiphertext(h, j);
-            }
-    }
-
-    void setMinusCompareElement(LimbCt minusCompareElement)  // .hpp:45-48
-    {
-        if (minusCompareElement.limbs.size() != ctWords()) throw std::invalid_argument("ciphertext does not match the context");
-        if (minusStaged) drainUploads();  // the previous element may still be crossing PCIe from this very array
-        std::memcpy(minusStaging(), minusCompareElement.limbs.data(), ctWords() * sizeof(uint64_t));
-        stageMinus();
-    }
+    // .hpp:40-43, [K][E] ciphertexts
+    void setIndex(std::vector<std::vector<LimbCt>> &&indexMatrix) { staged.setIndex(0, std::move(indexMatrix)); }
+    // .hpp:45-48
+    void setMinusCompareElement(LimbCt minusCompareElement) { staged.setMinusCompareElement(0, minusCompareElement); }
 
     // ---- zero-copy variant of the two setters, for a deserialiser ------------------------------------------------------------
     // Call restartIndex() before writing a NEW index matrix over one whose pieces were already handed over and not yet run
     // (setIndex does): the uploads in flight are waited for and every row is staged afresh.
-    uint64_t *indexStaging(uint32_t h, uint32_t j) { return pinIdx + ((size_t)h * E + j) * ctWords(); }  // [2][L][N] of idx[h][j]
-    uint64_t *minusStaging() { return pinMinus; }
-    void restartIndex()
-    {
-        if (!arrived && !rowsStaged) return;
-        drainUploads();
-        std::fill(rowCount.begin(), rowCount.end(), 0u);
-        rowsStaged = arrived = 0;
-    }
+    uint64_t *indexStaging(uint32_t h, uint32_t j) { return staged.indexStaging(0, h, j); }  // [2][L][N] of idx[h][j]
+    uint64_t *minusStaging() { return staged.minusStaging(0); }
+    void restartIndex() { staged.restartIndex(0); }
     // ciphertext (h, j) has been written to indexStaging(h, j): its upload starts now
-    void stageIndexCiphertext(uint32_t h, uint32_t j)
-    {
-        if (h >= K || j >= E) throw std::invalid_argument("index matrix position out of range");
-        PieContext::check(piehip_stage_index_ct_q(cc.handle(), 0, h, j, indexStaging(h, j)));  // leaves at once
-        arrived++;
-        if (++rowCount[h] == E) rowsStaged++;
-    }
-    void stageMinus()
-    {
-        PieContext::check(piehip_stage_minus(cc.handle(), pinMinus));
-        minusStaged = true;
-    }
+    void stageIndexCiphertext(uint32_t h, uint32_t j) { staged.stageIndexCiphertext(0, h, j); }
+    void stageMinus() { staged.stageMinus(0); }
     // Seeded ciphertexts (include/piehip.h "Seeded ciphertexts"): the deserialiser writes only c0 -- [L][N], the first half of
     // indexStaging(h, j) / minusStaging() -- and hands over the ciphertext's 32-byte seed; run() expands the c1 halves on the device
-    void stageIndexCiphertextSeeded(uint32_t h, uint32_t j, const uint8_t *seed)
-    {
-        if (h >= K || j >= E) throw std::invalid_argument("index matrix position out of range");
-        PieContext::check(piehip_stage_index_ct_seeded_q(cc.handle(), 0, h, j, indexStaging(h, j), seed));
-        arrived++;
-        if (++rowCount[h] == E) rowsStaged++;
-    }
-    void stageMinusSeeded(const uint8_t *seed)
-    {
-        PieContext::check(piehip_stage_minus_seeded_q(cc.handle(), 0, pinMinus, seed));
-        minusStaged = true;
-    }
+    void stageIndexCiphertextSeeded(uint32_t h, uint32_t j, const uint8_t *seed) { staged.stageIndexCiphertextSeeded(0, h, j, seed); }
+    void stageMinusSeeded(const uint8_t *seed) { staged.stageMinusSeeded(0, seed); }
 
     friend class BatchedFHEHIPPIEQueryBatch;
 
 protected:
-    size_t ctWords() const { return 2 * (size_t)cc.towers() * cc.ringDimension(); }
-    void initStaging()
-    {
-        PieContext::check(piehip_host_buffers(cc.handle(), &pinIdx, &pinMinus, &pinRes));
-        resultList.resize(b);
-        rowCount.assign(K, 0u);
-    }
-    void clearStaged()
-    {
-        minusStaged = false;
-        rowsStaged = arrived = 0;
-        std::fill(rowCount.begin(), rowCount.end(), 0u);
-    }
-    void drainUploads() { PieContext::check(piehip_run_host_wait(cc.handle())); }  // the copy queue is idle afterwards
     PieContext &cc;
     uint32_t K = 0, b = 0, E = 0;
-    std::vector<LimbCt> resultList;
-    uint64_t *pinIdx = nullptr, *pinMinus = nullptr, *pinRes = nullptr;  // page-locked, owned by the library
-    std::vector<uint32_t> rowCount;
-    uint32_t rowsStaged = 0, arrived = 0;
-    bool minusStaged = false, rerun = false, listStale = false;
+    StagedQueries staged;  // its one query
 };
 
 // Several queries per run() (piehip_set_query_batch): a server with clients waiting evaluates their queries together -- stage A
@@ -296,10 +365,12 @@ protected:
 class BatchedFHEHIPPIEQueryBatch {
 public:
     BatchedFHEHIPPIEQueryBatch(PieContext &cryptoContext, const BatchedFHEHIPPIE &database, uint32_t queriesPerRun)
-        : cc(cryptoContext), K(database.K), b(database.b), E(database.E), nq(queriesPerRun)
+        : cc(cryptoContext), nq(queriesPerRun)
     {
         PieContext::check(piehip_attach_database(cc.handle(), database.cc.handle()));
-        init();
+        if (nq < 1) throw std::invalid_argument("at least one query per run()");
+        PieContext::check(piehip_set_query_batch(cc.handle(), nq));
+        staged.init(cc, database.K, database.b, database.E, nq);
     }
     uint32_t queriesPerRun() const { return nq; }
 
@@ -312,159 +383,34 @@ public:
         PieContext::check(piehip_load_relin_key_seeded_q(cc.handle(), q, evk0, seeds));
     }
 
-    void setIndex(uint32_t q, std::vector<std::vector<LimbCt>> &&indexMatrix)  // [K][E] ciphertexts of query q
-    {
-        const size_t ct = ctWords();
-        checkQuery(q);
-        if (indexMatrix.size() != K) throw std::invalid_argument("index matrix must have one row per inner hash function");
-        for (uint32_t h = 0; h < K; h++) {
-            if (indexMatrix[h].size() != E) throw std::invalid_argument("index matrix row length must be eachCuckooTableSize");
-            for (uint32_t j = 0; j < E; j++)
-                if (indexMatrix[h][j].limbs.size() != ct) throw std::invalid_argument("ciphertext does not match the context");
-        }
-        restartIndex(q);
-        for (uint32_t h = 0; h < K; h++)
-            for (uint32_t j = 0; j < E; j++) {
-                std::memcpy(indexStaging(q, h, j), indexMatrix[h][j].limbs.data(), ct * sizeof(uint64_t));
-                stageIndexCiphertext(q, h, j);
-            }
-    }
-    void setMinusCompareElement(uint32_t q, const LimbCt &minusCompareElement)
-    {
-        checkQuery(q);
-        if (minusCompareElement.limbs.size() != ctWords()) throw std::invalid_argument("ciphertext does not match the context");
-        if (st[q].minusStaged) drainUploads();
-        std::memcpy(minusStaging(q), minusCompareElement.limbs.data(), ctWords() * sizeof(uint64_t));
-        stageMinus(q);
-    }
+    // [K][E] ciphertexts of query q
+    void setIndex(uint32_t q, std::vector<std::vector<LimbCt>> &&indexMatrix) { staged.setIndex(q, std::move(indexMatrix)); }
+    void setMinusCompareElement(uint32_t q, const LimbCt &minusCompareElement) { staged.setMinusCompareElement(q, minusCompareElement); }
     // zero-copy variant for a deserialiser (see BatchedFHEHIPPIE)
-    uint64_t *indexStaging(uint32_t q, uint32_t h, uint32_t j) { return st[q].pinIdx + ((size_t)h * E + j) * ctWords(); }
-    uint64_t *minusStaging(uint32_t q) { return st[q].pinMinus; }
-    void restartIndex(uint32_t q)
-    {
-        checkQuery(q);
-        if (!st[q].arrived && !st[q].rowsStaged) return;
-        drainUploads();
-        std::fill(st[q].rowCount.begin(), st[q].rowCount.end(), 0u);
-        st[q].rowsStaged = st[q].arrived = 0;
-    }
-    void stageIndexCiphertext(uint32_t q, uint32_t h, uint32_t j)
-    {
-        checkQuery(q);
-        if (h >= K || j >= E) throw std::invalid_argument("index matrix position out of range");
-        PieContext::check(piehip_stage_index_ct_q(cc.handle(), q, h, j, indexStaging(q, h, j)));
-        st[q].arrived++;
-        if (++st[q].rowCount[h] == E) st[q].rowsStaged++;
-    }
-    void stageMinus(uint32_t q)
-    {
-        checkQuery(q);
-        PieContext::check(piehip_stage_minus_q(cc.handle(), q, st[q].pinMinus));
-        st[q].minusStaged = true;
-    }
+    uint64_t *indexStaging(uint32_t q, uint32_t h, uint32_t j) { return staged.indexStaging(q, h, j); }
+    uint64_t *minusStaging(uint32_t q) { return staged.minusStaging(q); }
+    void restartIndex(uint32_t q) { staged.restartIndex(q); }
+    void stageIndexCiphertext(uint32_t q, uint32_t h, uint32_t j) { staged.stageIndexCiphertext(q, h, j); }
+    void stageMinus(uint32_t q) { staged.stageMinus(q); }
     // seeded pieces: c0 [L][N] at the start of indexStaging(q, h, j) / minusStaging(q), plus the 32-byte seed (see BatchedFHEHIPPIE)
-    void stageIndexCiphertextSeeded(uint32_t q, uint32_t h, uint32_t j, const uint8_t *seed)
-    {
-        checkQuery(q);
-        if (h >= K || j >= E) throw std::invalid_argument("index matrix position out of range");
-        PieContext::check(piehip_stage_index_ct_seeded_q(cc.handle(), q, h, j, indexStaging(q, h, j), seed));
-        st[q].arrived++;
-        if (++st[q].rowCount[h] == E) st[q].rowsStaged++;
-    }
-    void stageMinusSeeded(uint32_t q, const uint8_t *seed)
-    {
-        checkQuery(q);
-        PieContext::check(piehip_stage_minus_seeded_q(cc.handle(), q, st[q].pinMinus, seed));
-        st[q].minusStaged = true;
-    }
+    void stageIndexCiphertextSeeded(uint32_t q, uint32_t h, uint32_t j, const uint8_t *seed) { staged.stageIndexCiphertextSeeded(q, h, j, seed); }
+    void stageMinusSeeded(uint32_t q, const uint8_t *seed) { staged.stageMinusSeeded(q, seed); }
 
     void run()  // BatchedFHEHIPPIE.cpp:88-129 for every query of the batch
     {
         enqueue();
         collect();
     }
-    void enqueue()
-    {
-        struct Reset {
-            BatchedFHEHIPPIEQueryBatch &o;
-            bool ok = false;
-            ~Reset()
-            {
-                for (auto &s : o.st) {
-                    s.minusStaged = false;
-                    s.rowsStaged = s.arrived = 0;
-                    std::fill(s.rowCount.begin(), s.rowCount.end(), 0u);
-                }
-                if (!ok) piehip_stage_reset(o.cc.handle());
-            }
-        } reset{*this};
-        uint32_t complete = 0, touched = 0;
-        for (const auto &s : st) {
-            complete += (s.minusStaged && s.rowsStaged == K) ? 1u : 0u;
-            touched += (s.minusStaged || s.rowsStaged || s.arrived) ? 1u : 0u;
-        }
-        if (complete == nq) {
-            PieContext::check(piehip_run_staged(cc.handle(), pinRes));
-        } else if (touched) {
-            throw std::runtime_error("run: setMinusCompareElement and setIndex of every query of the batch must precede run()");
-        } else {
-            PieContext::check(piehip_run(cc.handle()));  // the previous batch again
-            rerun = true;
-        }
-        reset.ok = true;
-    }
-    void collect()
-    {
-        if (rerun) PieContext::check(piehip_get_results(cc.handle(), pinRes));
-        else PieContext::check(piehip_run_host_wait(cc.handle()));
-        rerun = false;
-        std::fill(listStale.begin(), listStale.end(), true);
-    }
+    void enqueue() { staged.enqueue("run: setMinusCompareElement and setIndex of every query of the batch must precede run()"); }
+    void collect() { staged.collect(); }
     // the b result ciphertexts of query q (materialised on the first call after a run(); resultTowers reads them in place)
-    std::vector<LimbCt> &getResultList(uint32_t q)
-    {
-        checkQuery(q);
-        if (listStale[q]) {
-            const size_t ct = ctWords();
-            for (uint32_t i = 0; i < b; i++) lists[q][i].limbs.assign(resultTowers(q, i), resultTowers(q, i) + ct);
-            listStale[q] = false;
-        }
-        return lists[q];
-    }
-    const uint64_t *resultTowers(uint32_t q, uint32_t i) const { return pinRes + ((size_t)i * nq + q) * ctWords(); }  // rows [bin layer][query]
+    std::vector<LimbCt> &getResultList(uint32_t q) { return staged.getResultList(q); }
+    const uint64_t *resultTowers(uint32_t q, uint32_t i) const { return staged.resultTowers(q, i); }  // rows [bin layer][query]
 
 private:
-    struct QueryState {
-        uint64_t *pinIdx = nullptr, *pinMinus = nullptr;
-        std::vector<uint32_t> rowCount;
-        uint32_t rowsStaged = 0, arrived = 0;
-        bool minusStaged = false;
-    };
-    void init()
-    {
-        if (nq < 1) throw std::invalid_argument("at least one query per run()");
-        PieContext::check(piehip_set_query_batch(cc.handle(), nq));
-        st.resize(nq);
-        for (uint32_t q = 0; q < nq; q++) {
-            PieContext::check(piehip_host_buffers_q(cc.handle(), q, &st[q].pinIdx, &st[q].pinMinus, &pinRes));
-            st[q].rowCount.assign(K, 0u);
-        }
-        lists.assign(nq, std::vector<LimbCt>(b));
-        listStale.assign(nq, false);
-    }
-    void checkQuery(uint32_t q) const
-    {
-        if (q >= nq) throw std::invalid_argument("query index outside the batch");
-    }
-    void drainUploads() { PieContext::check(piehip_run_host_wait(cc.handle())); }
-    size_t ctWords() const { return 2 * (size_t)cc.towers() * cc.ringDimension(); }
     PieContext &cc;
-    uint32_t K, b, E, nq;
-    std::vector<QueryState> st;
-    uint64_t *pinRes = nullptr;  // [b][nq][2][L][N], page-locked, owned by the library
-    std::vector<std::vector<LimbCt>> lists;
-    std::vector<bool> listStale;
-    bool rerun = false;
+    uint32_t nq;
+    StagedQueries staged;
 };
 
 }  // namespace piehip
