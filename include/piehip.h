@@ -427,7 +427,7 @@ int piehip_client_relin_keygen_seeded(piehip_handle h, const uint64_t *sk, uint6
  * With profiling on, run() brackets every kernel launch with HIP events on the handle's stream.
  * piehip_profile_read returns, per kernel class, the launch count, total milliseconds, and the
  * algorithmic bytes (SURVEY.md 8d formulas) of the last run. */
-#define PIEHIP_NKERNELS 13
+#define PIEHIP_NKERNELS 14
 enum {
     PIEHIP_K_STAGE_A = 0,   /* fused ct x pt multiply-accumulate + minus add  (A3+A4)          */
     PIEHIP_K_NTT_FWD = 1,   /* forward negacyclic NTT                          (A1)             */
@@ -441,7 +441,10 @@ enum {
     PIEHIP_K_ENCODE = 9,    /* packed encoding                                 (A2)             */
     PIEHIP_K_AUTOMORPH = 10,/* automorphism permutation                        (A9)             */
     PIEHIP_K_OTHER = 11,
-    PIEHIP_K_EVENT_PAIR = 12 /* no launch: the two events of a bracket back to back -- what the bracket itself reads on this stream */
+    PIEHIP_K_EVENT_PAIR = 12,/* no launch: the two events of a bracket back to back -- what the bracket itself reads on this stream */
+    PIEHIP_K_TENSOR_NTT_INV = 13 /* tensor product formed in the load phase of the inverse NTT that follows it: one launch in place of
+                                  * a PIEHIP_K_TENSOR and a PIEHIP_K_NTT_INV launch (bytes: the tensor product's, 8N * 7M per row).
+                                  * A class of its own: it does a product's arithmetic, so it is not a transform for a roofline */
 };
 /* times `iters` back-to-back NTT launches over nlimbs random limbs (moduli cycle over mod_count from 0);
  * flags: bit 0 = inverse transform, bit 1 = EVALUATION side in the library's internal lane order.

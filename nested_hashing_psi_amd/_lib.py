@@ -12,7 +12,7 @@ u32p = C.POINTER(C.c_uint32)
 i32p = C.POINTER(C.c_int32)
 f64p = C.POINTER(C.c_double)
 
-NKERNELS = 13
+NKERNELS = 14
 
 # every symbol include/piehip.h declares: (restype, argtypes)
 SYMBOLS = {

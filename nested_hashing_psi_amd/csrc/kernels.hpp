@@ -80,6 +80,14 @@ struct Ntt16Digits {
 };
 bool launch_ntt16(const NttPlan &pl, bool folded, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, bool sigma,
                   hipStream_t st, const NttExtra *ex, const Ntt16Digits *dg = nullptr);
+// The tensor product fused into the load phase of the inverse transform that follows it (16-coefficient kernel, every modulus in
+// (2^59, 2^60), lane order): e[nb][4][M][N] (a0 a1 b0 b1, EVALUATION, [0, 8q) residues) -> d[nb][3][M][N] in COEFFICIENT format, as
+// launch_tensor + launch_ntt16(d, nb * 3 * M, 0, M, inverse, sigma) leave it.  Returns false when it does not apply or the
+// library was built with -DPIEHIP_FUSE_TENSOR=0 (the two-launch schedule, for A/B runs): callers then issue the two launches.
+#ifndef PIEHIP_FUSE_TENSOR
+#define PIEHIP_FUSE_TENSOR 1
+#endif
+bool launch_ntt16_tensor(const NttPlan &pl, bool folded, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st);
 inline bool ntt16_applies(const NttPlan &pl, bool folded)
 {
     return !pl.force_generic && pl.twp && (folded ? (pl.twk16_fold && (pl.logN == 14 || pl.logN == 15)) : (pl.twk16 && pl.logN == 13));

@@ -22,13 +22,15 @@ void ntt16_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map)
 }
 
 template <u32 LOGNS>
-static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 num_cus, hipStream_t st)
+static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 num_cus, hipStream_t st, bool tensor = false)
 {
     typedef ntt16::Geo<LOGNS> G;
     constexpr size_t lds = (size_t)G::LDS_WORDS * sizeof(u64);
-    static PerDeviceOnce attr[3];
-    if (attr[inverse ? 1 : (lift ? 2 : 0)].first_on_current_device()) {
-        if (inverse)
+    static PerDeviceOnce attr[4];
+    if (attr[tensor ? 3 : inverse ? 1 : (lift ? 2 : 0)].first_on_current_device()) {
+        if (tensor)
+            (void)hipFuncSetAttribute((const void *)ntt16::ntt16_kernel_t<LOGNS, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        else if (inverse)
             (void)hipFuncSetAttribute((const void *)ntt16::ntt16_kernel_t<LOGNS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         else if (lift)
             (void)hipFuncSetAttribute((const void *)ntt16::ntt16_kernel_t<LOGNS, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -38,7 +40,9 @@ static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 nu
     // resident workgroups per CU: two of 512 threads (68 KiB of LDS, 128 VGPRs each) or one of 1024 (136 KiB); persistent beyond
     const u32 slots = (LOGNS == 13 ? 2u : 1u) * num_cus;
     const u32 grid = a.nitems < slots ? a.nitems : slots;
-    if (inverse)
+    if (tensor)
+        hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, true, false, true>), dim3(grid), dim3(G::T), lds, st, a);
+    else if (inverse)
         hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, true>), dim3(grid), dim3(G::T), lds, st, a);
     else if (lift)
         hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, false, true>), dim3(grid), dim3(G::T), lds, st, a);
@@ -80,6 +84,7 @@ bool launch_ntt16(const NttPlan &pl, bool folded, u64 *data, u32 nlimbs, u32 mod
     a.lift_src = nullptr;
     a.lift_stride = 0;
     a.lift_L = 1;
+    a.tsrc = nullptr;
     if (dg && !inverse) {  // the key-switch digits ride in the same launch: nb * L * L more limbs, lifted in the load phase
         a.lift_first = a.nitems;
         a.nitems += (dg->nb * dg->L * dg->L) << s0;
@@ -94,6 +99,38 @@ bool launch_ntt16(const NttPlan &pl, bool folded, u64 *data, u32 nlimbs, u32 mod
     else
         launch_ntt16_t<13>(a, inverse, lift, pl.transform_cus(), st);
     return true;
+}
+
+bool launch_ntt16_tensor(const NttPlan &pl, bool folded, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st)
+{
+#if PIEHIP_FUSE_TENSOR
+    const u64 *twk = folded ? pl.twk16_fold : pl.twk16;
+    const u32 s0 = folded ? 1u : 0u;
+    const u32 slice_log = pl.logN - s0;
+    if (pl.force_generic || !twk || !pl.twp || (slice_log != 13 && slice_log != 14)) return false;
+    ntt16::Args a = {};
+    a.data = d;
+    a.twp = reinterpret_cast<const ntt16::u64x2 *>(pl.twp);
+    a.twk = reinterpret_cast<const ntt16::u64x2 *>(twk);
+    a.dc = pl.dc;
+    a.N = pl.N;
+    a.s0 = s0;
+    a.nitems = (nb * 3 * M) << s0;
+    a.mod_base = 0;
+    a.mod_count = M;
+    a.flags = folded ? ntt16::F_FOLDED : 0;
+    a.copy_K = a.copy_L = a.copy_M = 1;
+    a.lift_first = ~0u;
+    a.lift_L = 1;
+    a.tsrc = e;
+    if (slice_log == 14)
+        launch_ntt16_t<14>(a, true, false, pl.transform_cus(), st, true);
+    else
+        launch_ntt16_t<13>(a, true, false, pl.transform_cus(), st, true);
+    return true;
+#else
+    return false;
+#endif
 }
 
 }  // namespace piehip

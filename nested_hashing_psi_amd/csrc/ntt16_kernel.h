@@ -266,6 +266,9 @@ struct Args {
     const u64 *lift_src;
     size_t lift_stride;
     u32 lift_first, lift_L;
+    // inverse, TENSOR instantiation: the input of item (row, d, limb m, slice) is not read from data but formed in the load phase
+    // from the lane-ordered QP operands tsrc[row][4][mod_count][N] (a0 a1 b0 b1): d0 = a0 b0, d1 = a0 b1 + a1 b0, d2 = a1 b1
+    const u64 *tsrc;
 };
 enum : u32 {
     F_STD_IN = 1,    // inverse: EVALUATION input in standard (bit-reversed) order instead of lane order
@@ -348,9 +351,120 @@ inline u32 lane_to_std(u32 p) { return lane_to_std_t(p, T); }
 #ifndef NTT16_LIFT_XCD
 #define NTT16_LIFT_XCD 1
 #endif
+// ---- the tensor product in the inverse transform's load phase (TENSOR instantiation) ----------------------------------------
+// What tensor_kernel<true> (kernels_pie.hip) computes, for the one result polynomial d of the item, straight into x[16]: the
+// result never goes to memory.  The operands arrive in [0, 8q) from the lazy forward transform; sign-mask subtractions bring
+// them below 2q (the second factor of a single product: below 4q is enough), the products go through the carry-free 30-bit
+// column sums (madasm.h) and one Barrett block that leaves [0, 4q) -- what the inverse butterflies take.  Bounds, q < 2^60:
+//   one product   a < 2q, b < 4q:  30-bit low halves, high halves < 2^31 and < 2^32; columns < 2^60, < 2^63, < 2^63; z < 8 q^2 < 2^123
+//   two products  all < 2q:        high halves < 2^31; columns < 2^61, < 2^63, < 2^63;                           z < 8 q^2 < 2^123
+// The block is kernels_pie.hip's PIE_COLACC123_TO_4Q (one-word Barrett with mu = floor(2^123 / q): z >> 59 from the
+// carry-normalised columns, quotient estimate at most 3 short) on ten of the butterfly blocks' fixed registers.
+#ifndef NTT16_TENSOR_XCD
+#define NTT16_TENSOR_XCD 1
+#endif
+// x in [0, 8q) -> [0, 2q): csub_neg by 4q, then by 2q, as one statement
+__device__ __forceinline__ u64 csub2_neg(u64 x, u64 negm4, u64 negm2)
+{
+    u32 lo, hi;
+    asm("v_lshl_add_u64 v[126:127], %[x], 0, %[n4]\n\t"
+        "v_ashrrev_i32 v125, 31, v127\n\t"
+        "v_bfi_b32 v122, v125, %[xl], v126\n\t"
+        "v_bfi_b32 v123, v125, %[xh], v127\n\t"
+        "v_lshl_add_u64 v[126:127], v[122:123], 0, %[n2]\n\t"
+        "v_ashrrev_i32 v125, 31, v127\n\t"
+        "v_bfi_b32 %[lo], v125, v122, v126\n\t"
+        "v_bfi_b32 %[hi], v125, v123, v127"
+        : [lo] "=&v"(lo), [hi] "=&v"(hi)
+        : [x] "v"(x), [xl] "v"((u32)x), [xh] "v"((u32)(x >> 32)), [n4] "s"(negm4), [n2] "s"(negm2)
+        : "v122", "v123", "v125", "v126", "v127");
+    return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 colacc123_to_4q(u64 c0, u64 c1, u64 c2, u64 mu, u64 nq)
+{
+    u64 r;
+    asm("v_lshrrev_b64 v[118:119], 30, %[c0]\n\t"
+        "v_lshl_add_u64 v[118:119], v[118:119], 0, %[c1]\n\t"
+        "v_lshrrev_b64 v[120:121], 30, v[118:119]\n\t"
+        "v_lshl_add_u64 v[120:121], v[120:121], 0, %[c2]\n\t"
+        "v_lshlrev_b64 v[122:123], 1, v[120:121]\n\t"
+        "v_bfe_u32 v126, v118, 29, 1\n\t"
+        "v_and_b32 v124, 0x3fffffff, %[c0l]\n\t"
+        "v_bfe_u32 v125, v118, 2, 28\n\t"
+        "v_or_b32 v122, v122, v126\n\t"
+        "v_lshl_or_b32 v124, v118, 30, v124\n\t"
+        "v_lshl_or_b32 v125, v120, 28, v125\n\t"
+        "v_mul_hi_u32 v126, v122, %[mul]\n\t"
+        "v_mov_b32 v127, 0\n\t"
+        "v_mad_u64_u32 v[126:127], vcc, v122, %[muh], v[126:127]\n\t"
+        "v_mad_u64_u32 v[126:127], vcc, v123, %[mul], v[126:127]\n\t"
+        "v_mad_u64_u32 v[118:119], s[96:97], v123, %[muh], 0\n\t"
+        "v_lshrrev_b64 v[126:127], 32, v[126:127]\n\t"
+        "v_addc_co_u32 v127, vcc, 0, v127, vcc\n\t"
+        "v_lshl_add_u64 v[126:127], v[118:119], 0, v[126:127]\n\t"
+        "v_mad_u64_u32 v[118:119], vcc, v126, %[nqh], 0\n\t"
+        "v_mad_u64_u32 v[118:119], vcc, v127, %[nql], v[118:119]\n\t"
+        "v_add_u32 v125, v125, v118\n\t"
+        "v_mad_u64_u32 %[r], vcc, v126, %[nql], v[124:125]"
+        : [r] "=v"(r)
+        : [c0] "v"(c0), [c1] "v"(c1), [c2] "v"(c2), [c0l] "v"((u32)c0), [mul] "s"((u32)mu), [muh] "s"((u32)(mu >> 32)),
+          [nql] "s"((u32)nq), [nqh] "s"((u32)(nq >> 32))
+        : "vcc", "s96", "s97", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127");
+    return r;
+}
+// x[16] <- a b (TWO: a b + c d) of the lane-ordered slices at pa, pb (pc, pd).  Four operands of 16 coefficients do not fit
+// beside x[16]: the 16-byte lanes come in as a window of NTT16_TENSOR_DEPTH pairs per operand, the next one requested as a pair's
+// products are done (its registers are the ones just freed).
+#ifndef NTT16_TENSOR_DEPTH
+#define NTT16_TENSOR_DEPTH 3
+#endif
+template <u32 T, bool TWO>
+__device__ __forceinline__ void tensor_load(u64 (&x)[16], const u64 *pa, const u64 *pb, const u64 *pc, const u64 *pd, u32 voffb, u64 q,
+                                            u64 mu)
+{
+    constexpr int DEPTH = NTT16_TENSOR_DEPTH;
+    const u64 nq = 0 - q, nq2 = 0 - 2 * q, nq4 = 0 - 4 * q;
+    u64x2 va[8], vb[8], vc[8], vd[8];
+#define NTT16_TLOAD(j)                                                           \
+    do {                                                                         \
+        va[j] = pair_get_global(at_bytes(pa + 2 * T * (j), voffb));              \
+        vb[j] = pair_get_global(at_bytes(pb + 2 * T * (j), voffb));              \
+        if (TWO) {                                                               \
+            vc[j] = pair_get_global(at_bytes(pc + 2 * T * (j), voffb));          \
+            vd[j] = pair_get_global(at_bytes(pd + 2 * T * (j), voffb));          \
+        }                                                                        \
+    } while (0)
+#pragma unroll
+    for (int j = 0; j < DEPTH; j++) NTT16_TLOAD(j);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        NTT16_FENCE();
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const u64 fa = csub2_neg(k ? va[j].y : va[j].x, nq4, nq2);
+            const u64 fb = TWO ? csub2_neg(k ? vb[j].y : vb[j].x, nq4, nq2) : csub_neg(k ? vb[j].y : vb[j].x, nq4);
+            const Split30 sa = split30(fa), sb = split30(fb);
+            ColAcc c;
+            c.c0 = mul_u(sa.lo, sb.lo);
+            c.c1 = mad_u(sa.hi, sb.lo, mul_u(sa.lo, sb.hi));
+            c.c2 = mul_u(sa.hi, sb.hi);
+            if (TWO) {
+                const u64 fc = csub2_neg(k ? vc[j].y : vc[j].x, nq4, nq2);
+                const u64 fd = csub2_neg(k ? vd[j].y : vd[j].x, nq4, nq2);
+                colacc_mac(c, split30(fc), split30(fd));
+            }
+            x[2 * j + k] = colacc123_to_4q(c.c0, c.c1, c.c2, mu, nq);
+        }
+        NTT16_FENCE();
+        if (j + DEPTH < 8) NTT16_TLOAD(j + DEPTH);
+    }
+#undef NTT16_TLOAD
+}
+
 // LIFT (forward only): the launch may carry key-switch digit items (Args::lift_first); a separate instantiation, so that the
 // plain forward transform does not pay for the lift's registers
-template <u32 LOGNS, bool INV, bool LIFT = false>
+// TENSOR (inverse only, lane order in): every item forms its input from the QP operands (Args::tsrc); likewise its own instantiation
+template <u32 LOGNS, bool INV, bool LIFT = false, bool TENSOR = false>
 __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 {
     typedef Geo<LOGNS> G;
@@ -401,8 +515,29 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             if (item_l - within + blk8 <= a.nitems - a.lift_first) item_l = item_l - within + (within & 7) * G + (within >> 3);
 #endif
         }
-        const u32 blk = item_l & ((1u << a.s0) - 1);
-        const u32 limb = lift ? item_l >> a.s0 : limb_of(item);
+        // TENSOR: the three items d = 0, 1, 2 of one (row, limb, slice) read the same four operand slices (a0 b0 | a0 b1 a1 b0 | a1 b1).
+        // Enumerated with d innermost and dealt like the digit items above (blocks of 8 x 3), they run in workgroups 8 apart in the
+        // same round: one XCD, each operand slice fetched once.  (The persistent grid strides by gridDim.x = 16 mod 24 or 8 mod 24
+        // on 256 CUs: a workgroup's items cycle through d, none collects the twice as long d = 1 items.)
+        u32 t_d = 0, t_row = 0, t_blk = 0, t_limb = 0;
+        if (TENSOR) {
+            const u32 M_ = a.mod_count;
+#if NTT16_TENSOR_XCD
+            u32 il = item;
+            const u32 within = il % 24;
+            if (il - within + 24 <= a.nitems) il = il - within + (within & 7) * 3 + (within >> 3);
+            const u32 u = il / 3, lm = u >> a.s0;
+            t_d = il % 3, t_blk = u & ((1u << a.s0) - 1), t_row = lm / M_;
+            t_limb = (t_row * 3 + t_d) * M_ + lm % M_;
+#else
+            t_limb = item >> a.s0, t_blk = item & ((1u << a.s0) - 1);
+            t_row = t_limb / (3 * M_), t_d = (t_limb / M_) % 3;
+#endif
+            t_d = __builtin_amdgcn_readfirstlane(t_d), t_row = __builtin_amdgcn_readfirstlane(t_row);
+            t_blk = __builtin_amdgcn_readfirstlane(t_blk), t_limb = __builtin_amdgcn_readfirstlane(t_limb);
+        }
+        const u32 blk = TENSOR ? t_blk : item_l & ((1u << a.s0) - 1);
+        const u32 limb = TENSOR ? t_limb : lift ? item_l >> a.s0 : limb_of(item);
         // (uniform; laundered through a scalar register pair so that the slice's addresses stay "scalar base + lane offset": left to
         // itself the compiler hoists a.data + lane offset out of the item loop as a 64-bit vector base, which the inverse kernel
         // -- at its 128-register budget -- spilled to scratch, and a scratch reload is a vector-memory operation: the
@@ -605,7 +740,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             NTT16_LOAD4(t12, 4, 4);   // (the other four behind the data loads: the register budget is x 32 + twiddles)
             // operand-0 polynomials of a standard-order launch: their lane-ordered EVALUATION form lives in the Q limbs of the QP
             // operand array -- written there by this launch (copy) or already by stage A (F_X_LANE_IN: read from there)
-            const bool is_x = (a.flags & F_STD_IN) && a.copy_out && (limb / (2 * a.copy_L)) % a.copy_K == 0;
+            const bool is_x = !TENSOR && (a.flags & F_STD_IN) && a.copy_out && (limb / (2 * a.copy_L)) % a.copy_K == 0;
             u64 *co = nullptr;
             if (is_x) {
                 const u32 bin = limb / (2 * a.copy_L * a.copy_K), cc = (limb / a.copy_L) & 1, i = limb % a.copy_L;
@@ -613,7 +748,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                 asm("" : "+s"(co));
             }
             const bool x_in = is_x && (a.flags & F_X_LANE_IN);
-            if ((a.flags & F_STD_IN) && !x_in) {
+            if (!TENSOR && (a.flags & F_STD_IN) && !x_in) {
                 // Standard order in.  A wave's pass-4' elements are the 1024 contiguous coefficients of its own block: it loads
                 // exactly those (coalesced: pair 64 j + l of the block per lane and instruction), drops them into its own region of
                 // the image and picks up its 16 contiguous coefficients -- a hand-off inside the wave.  (Until r04 the slice
@@ -651,6 +786,17 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                         pair_put_global(v, at_bytes(co + 2 * T * j, voffb));
                     }
                 }
+            } else if (TENSOR) {
+                const u32 M_ = a.mod_count;
+                const size_t ss = ((size_t)M_ << a.s0) * NS;  // one operand polynomial
+                const u64 *e0 = a.tsrc + ((((size_t)t_row * 4 * M_ + limb % M_) << a.s0) + blk) * NS;
+                const u64 *pa = e0 + (t_d == 2 ? ss : 0), *pb = e0 + (t_d == 0 ? 2 : 3) * ss, *pc = e0 + ss, *pd = e0 + 2 * ss;
+                asm("" : "+s"(pa), "+s"(pb), "+s"(pc), "+s"(pd));
+                const u64 mu = (dcs->mod[mod].r1 << 59) | (dcs->mod[mod].r0 >> 5);  // floor(2^123 / q)
+                if (t_d == 1)
+                    tensor_load<T, true>(x, pa, pb, pc, pd, voffb, q, mu);
+                else
+                    tensor_load<T, false>(x, pa, pb, pc, pd, voffb, q, mu);
             } else {
                 const u64 *src = x_in ? co : g;
                 asm("" : "+s"(src));

@@ -10,7 +10,7 @@ using namespace piehip;
 static thread_local std::string g_err;
 static const char *KNAMES[PIEHIP_NKERNELS] = {"stage_a_mac", "ntt_fwd", "ntt_inv",  "expand",   "tensor",    "scale_round",
                                               "digits",      "relin",   "mask_mul", "encode",   "automorph", "other",
-                                              "event_pair"};
+                                              "event_pair",  "tensor_ntt_inv"};
 static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
 static void free_workspace(piehip_ctx *h);
 

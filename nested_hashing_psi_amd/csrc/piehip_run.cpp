@@ -96,11 +96,21 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
         }
         ntt(h, w.eqp, nb * (xq_ready ? 4 * M - 2 * L : 4 * M), 0, M, false, true, true, &ex);
     }
-    {
-        ProfScope ps(h, PIEHIP_K_TENSOR, W * nb * 7.0 * M);
-        launch_tensor(h->d_dc, N, M, w.eqp, w.dqp, nb, h->stream);
+    // Tensor product and inverse transform of its result.  One launch where the 16-coefficient kernel runs the transform in lane
+    // order and every modulus has 60 bits: each item forms its input from the four operands in its load phase, the tensor
+    // result is neither written nor read back (3 M limbs per row each way).  Otherwise two launches.
+    bool fused = false;
+    if (PIEHIP_FUSE_TENSOR && h->sigma_on && h->small_moduli && ntt16_applies(h->plan, h->fold_on)) {
+        ProfScope ps(h, PIEHIP_K_TENSOR_NTT_INV, W * nb * 7.0 * M);
+        fused = launch_ntt16_tensor(h->plan, h->fold_on, w.eqp, w.dqp, nb, M, h->stream);
     }
-    ntt(h, w.dqp, nb * 3 * M, 0, M, true, true, true);
+    if (!fused) {
+        {
+            ProfScope ps(h, PIEHIP_K_TENSOR, W * nb * 7.0 * M);
+            launch_tensor(h->d_dc, N, M, w.eqp, w.dqp, nb, h->stream);
+        }
+        ntt(h, w.dqp, nb * 3 * M, 0, M, true, true, true);
+    }
     if (relin) {
         {
             ProfScope ps(h, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
