@@ -44,7 +44,9 @@ typedef struct piehip_ctx *piehip_handle;
 /* 100 = rounds 1-4; 101 (round 5) adds piehip_profile_read_n, piehip_set/get_transform_slots, piehip_upload_turn_wait,
  * piehip_set_host_path_timing / piehip_host_path_times, piehip_rccl_wait / _abort / _agree; nothing of 100 changed its signature or
  * its meaning (piehip_profile_read keeps writing the twelve kernel classes of version 100).  102 adds the seeded ciphertexts
- * ("Seeded ciphertexts" below); nothing of 101 changed. */
+ * ("Seeded ciphertexts" below); nothing of 101 changed.  The result limbs ("Result limbs" below: piehip_mod_reduce, piehip_set / get_result_limbs,
+ * three more kernel classes, PIEHIP_NKERNELS 14 -> 17) were added without a new number: look the symbols up; nothing of 102 changed
+ * (piehip_profile_read_n writes min(n, PIEHIP_NKERNELS) entries, so a caller built with 14 keeps its 14). */
 int piehip_version(void);
 const char *piehip_last_error(void);
 
@@ -321,6 +323,39 @@ int piehip_encode(piehip_handle h, const int64_t *slots, uint32_t npt, uint32_t 
  * which = 2: scale by t/P from QP into Q      in[npoly][2L+1][N] -> out[npoly][L][N] */
 int piehip_base_convert(piehip_handle h, int which, const uint64_t *in, uint32_t npoly, uint64_t *out);
 
+/* ---- result limbs: result ciphertexts leave the device on a prefix of the prime chain ------------------------------------------
+ * After the last multiplication a result ciphertext is only ever decrypted, and it decrypts as well on fewer RNS limbs (what SEAL
+ * does before it serialises a result, and OpenFHE's Compress; the reference calls neither): a C3 result (4 x 60-bit primes, 33-bit t)
+ * is 3.5 MiB per query on one limb instead of 14 MiB on four.
+ * The operation, in exact integers.  A component is a polynomial with coefficients c in [0, Q), held as residues.  The limbs
+ * l = L - 1, L - 2, .., keep are dropped one after the other; each drop is
+ *     r = c mod q_l, centred (r = v if v <= (q_l - 1) / 2 else v - q_l);   c <- (c - r) / q_l   (exact),
+ * i.e. c_i <- (c_i - r) q_l^-1 mod q_i for i < l, coefficient by coefficient in COEFFICIENT format, both components alike.  Input and
+ * output cross the ABI in EVALUATION format; the output is [2][keep][N], canonical, under q_0 .. q_{keep-1}, and decrypts as a plain
+ * BFV ciphertext of the context (N, keep, t, q[:keep]) with the first `keep` limbs of the secret key.  A drop adds at most
+ * t (1 + N) / (2 q_0) to the invariant noise.  Integer arithmetic only: every schedule gives the same bits.
+ *   piehip_mod_reduce        the operation on nct ciphertexts in host memory; synchronous.  keep == L copies the input.
+ *   piehip_set_result_limbs  run() ends with the reduction of its result list to `keep` limbs (default L: nothing is added, no
+ *                            launch, buffer or byte differs).  With keep < L every queue group of a run() is followed, on its own
+ *                            queue, by an inverse transform of its result rows, the limb-drop kernel and a forward transform of the
+ *                            kept limbs, and everything that hands results out uses rows of 2 keep N words: piehip_run,
+ *                            piehip_run_into (d_results[b][nq][2][keep][N]), piehip_get_results, piehip_results_device,
+ *                            piehip_copy_results_device, piehip_run_staged, piehip_run_host(_async / _wait / _seeded*) and the
+ *                            page-locked result array of piehip_host_buffers(_q), which is sized by the setting at the time of the
+ *                            call (ask again after changing it).  Per handle: a query slot (piehip_attach_database) has its own
+ *                            setting.  Any K.  In a host-results run a queue group's download follows that group's reduction; the
+ *                            next group is released (see piehip_run_host) in front of the group's limb-drop kernel, when the group
+ *                            has that kernel and the forward transform of the kept limbs left.
+ *   piehip_get_result_limbs  the setting.
+ * PIEHIP_EINVAL: keep == 0 or keep > L.  PIEHIP_ESTATE: keep < L on a handle with piehip_set_graph(1), and piehip_set_graph(1) on a
+ * handle with keep < L (the captured graph stays one plain query per run()).  piehip_gather_results(_host) REFUSES (PIEHIP_ESTATE) a
+ * handle with keep < L: the ranks' row sizes would have to agree and nothing checks that across ranks.  piehip_fhepie_* ignores the
+ * setting. */
+int piehip_mod_reduce(piehip_handle h, const uint64_t *in /*[nct][2][L][N]*/, uint32_t nct, uint32_t keep,
+                      uint64_t *out /*[nct][2][keep][N]*/);
+int piehip_set_result_limbs(piehip_handle h, uint32_t keep);
+int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
+
 /* ---- FHEHIPPIE: the rotation-based sibling operator ---------------------------------
  * Reference: src/Common/Crypto/PrivateIndexedEqualityCheck/FHEHIPPIE.{hpp,cpp}; one operator per client slot
  * (FHEHIPPIECollection, PIECollection.hpp); `npie` operators are evaluated as one batch here.
@@ -427,7 +462,7 @@ int piehip_client_relin_keygen_seeded(piehip_handle h, const uint64_t *sk, uint6
  * With profiling on, run() brackets every kernel launch with HIP events on the handle's stream.
  * piehip_profile_read returns, per kernel class, the launch count, total milliseconds, and the
  * algorithmic bytes (SURVEY.md 8d formulas) of the last run. */
-#define PIEHIP_NKERNELS 14
+#define PIEHIP_NKERNELS 17
 enum {
     PIEHIP_K_STAGE_A = 0,   /* fused ct x pt multiply-accumulate + minus add  (A3+A4)          */
     PIEHIP_K_NTT_FWD = 1,   /* forward negacyclic NTT                          (A1)             */
@@ -442,9 +477,13 @@ enum {
     PIEHIP_K_AUTOMORPH = 10,/* automorphism permutation                        (A9)             */
     PIEHIP_K_OTHER = 11,
     PIEHIP_K_EVENT_PAIR = 12,/* no launch: the two events of a bracket back to back -- what the bracket itself reads on this stream */
-    PIEHIP_K_TENSOR_NTT_INV = 13 /* tensor product formed in the load phase of the inverse NTT that follows it: one launch in place of
+    PIEHIP_K_TENSOR_NTT_INV = 13,/* tensor product formed in the load phase of the inverse NTT that follows it: one launch in place of
                                   * a PIEHIP_K_TENSOR and a PIEHIP_K_NTT_INV launch (bytes: the tensor product's, 8N * 7M per row).
                                   * A class of its own: it does a product's arithmetic, so it is not a transform for a roofline */
+    PIEHIP_K_RESULT_NTT_INV = 14,/* result limbs: inverse transform of the result rows, standard order in and out (bytes 16 N per limb) */
+    PIEHIP_K_LIMB_DROP = 15,     /* result limbs: the coefficient-wise limb-drop kernel (bytes: 8 N (L + keep) per polynomial)       */
+    PIEHIP_K_RESULT_NTT_FWD = 16 /* result limbs: forward transform of the kept limbs.  Classes of their own: the reduction's cost is
+                                  * read off these three, and the transforms of the multiplication chain keep their roofline class   */
 };
 /* times `iters` back-to-back NTT launches over nlimbs random limbs (moduli cycle over mod_count from 0);
  * flags: bit 0 = inverse transform, bit 1 = EVALUATION side in the library's internal lane order.

@@ -12,7 +12,7 @@ u32p = C.POINTER(C.c_uint32)
 i32p = C.POINTER(C.c_int32)
 f64p = C.POINTER(C.c_double)
 
-NKERNELS = 14
+NKERNELS = 17
 
 # every symbol include/piehip.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -120,6 +120,9 @@ SYMBOLS = {
     "piehip_load_relin_key_seeded_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p, u8p]),
     "piehip_client_encrypt_seeded": (C.c_int, [C.c_void_p, u64p, i64p, C.c_uint32, C.c_uint32, u64p, u8p, u64p]),
     "piehip_client_relin_keygen_seeded": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u8p, u64p]),
+    "piehip_mod_reduce": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_uint32, u64p]),
+    "piehip_set_result_limbs": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "piehip_get_result_limbs": (C.c_int, [C.c_void_p, u32p]),
 }
 
 _lib = None

@@ -166,18 +166,39 @@ class BatchedFHEPSIClient:
                                            s.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
         return out
 
-    def decrypt(self, cts, nslots=None):
+    def _reduced_context(self, limbs):
+        """the context (N, limbs, t, q[:limbs]) that decrypts results the server reduced to `limbs` limbs (setResultLimbs), made
+        once per limb count and kept.  A context wants an auxiliary basis too: the next limbs + 1 primes of this context's chain
+        (decryption never touches them)."""
+        cache = self.__dict__.setdefault("_reduced", {})
+        if limbs not in cache:
+            cc = self.cc
+            chain = [int(v) for v in cc.moduli[:cc.M]]
+            cache[limbs] = type(cc)(cc.N, limbs, cc.t, chain[:limbs], chain[limbs:2 * limbs + 1])
+        return cache[limbs]
+
+    def decrypt(self, cts, nslots=None, limbs=None):
+        """cts [n][2][L][N] -> slots [n][nslots].  limbs = keep < L: cts [n][2][keep][N] as a server with setResultLimbs(keep)
+        returns them, decrypted in the reduced context with the first `keep` limbs of the secret key."""
         cc = self.cc
         a, ap = _u64(cts)
+        limbs = cc.L if limbs is None else int(limbs)
+        if not 1 <= limbs <= cc.L:
+            raise ValueError("limbs must be between 1 and L")
+        if a.ndim != 4 or a.shape[1:] != (2, limbs, cc.N):
+            raise ValueError("ciphertexts must be [n][2][%d][N]" % limbs)
         n = a.shape[0]
         nslots = nslots or self.B
         out = _out((n, nslots), np.int64)
-        _check(lib().piehip_client_decrypt(cc._h, self.sk.ctypes.data_as(u64p), ap, n, nslots, out.ctypes.data_as(i64p)))
+        h, sk = cc._h, self.sk
+        if limbs < cc.L:
+            h, sk = self._reduced_context(limbs)._h, np.ascontiguousarray(self.sk[:limbs])
+        _check(lib().piehip_client_decrypt(h, sk.ctypes.data_as(u64p), ap, n, nslots, out.ctypes.data_as(i64p)))
         return out
 
     # -- online (BatchedFHEPSIClient.cpp:176-192): zero slot in any of the b results <=> item in the intersection
-    def extractIntersection(self, resultList):
-        self.batchedDecryptedResult = self.decrypt(resultList)
+    def extractIntersection(self, resultList, limbs=None):
+        self.batchedDecryptedResult = self.decrypt(resultList, limbs=limbs)
         flat = self.clientTable.reshape(-1)
         hit = (self.batchedDecryptedResult == 0).any(axis=0)
         return flat[hit].copy()

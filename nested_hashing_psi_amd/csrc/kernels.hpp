@@ -190,6 +190,9 @@ void launch_ct_add(const DevConsts *dc, u32 N, u32 L, const u64 *x, const u64 *y
 // (pt_div > 1: ciphertext i takes plaintext i / pt_div)
 void launch_ct_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, const u64 *pt, size_t pt_stride, u64 *out,
                          u32 nct, hipStream_t st, u32 pt_div = 1);
+// limb drop of npoly polynomials in COEFFICIENT format: in[npoly][L][N] -> out[npoly][keep][N], the limbs L - 1 .. keep dropped one
+// after the other with centred rounding (include/piehip.h "Result limbs").  1 <= keep < L <= MAX_L; false (nothing launched) otherwise
+bool launch_limb_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, const u64 *in, u64 *out, u32 npoly, hipStream_t st);
 // out[r][p] = in[r][map[p]] for nrows limbs
 void launch_permute(u32 N, const u64 *in, const u32 *map, u64 *out, u32 nrows, hipStream_t st);
 // packed encoding: slots[npt][B] -> u[npt][N] residues mod t at their EVALUATION positions

@@ -1530,6 +1530,63 @@ void launch_ct_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, const 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Limb drop (include/piehip.h "Result limbs"): in[npoly][L][N] -> out[npoly][KEEP][N], COEFFICIENT format, canonical residues.
+// One thread holds the L residues of one coefficient and drops the limbs L - 1 .. KEEP one after the other:
+//     r = c mod q_l centred,  c_i <- (c_i - r) q_l^-1 mod q_i  for i < l.
+// With s = [c_l > (q_l - 1) / 2] as a 64-bit sign mask, c_i - r = c_i - c_l + (s ? q_l : off) where off is a multiple of q_i that
+// is >= (q_l - 1) / 2 (DevConsts::drop_off): one non-negative word below 2^63 for moduli of any widths, which the Shoup product
+// with q_l^-1 takes as it is.  (L - KEEP)(L + KEEP - 1) / 2 such products per coefficient; every constant is wave-uniform
+// (scalar loads, the indices are compile-time), the conditional subtraction is csub_u's sign-mask block.
+// ---------------------------------------------------------------------------------------------
+template <int L, int KEEP>
+__global__ void __launch_bounds__(TPB) limb_drop_kernel(const DevConsts *__restrict__ dc, u32 N, u32 blocks_per_poly,
+                                                        const u64 *__restrict__ in, u64 *__restrict__ out)
+{
+    const u32 poly = blockIdx.x / blocks_per_poly;
+    const u32 n = (blockIdx.x % blocks_per_poly) * TPB + threadIdx.x;
+    if (n >= N) return;
+    const u64 *pin = in + (size_t)poly * L * N + n;
+    u64 c[L];
+#pragma unroll
+    for (int i = 0; i < L; i++) c[i] = pin[(size_t)i * N];
+#pragma unroll
+    for (int l = L - 1; l >= KEEP; l--) {
+        const u64 ql = dc->mod[l].q;
+        const u64 v = c[l];
+        const u64 s = (u64)((int64_t)((ql >> 1) - v) >> 63);  // all ones when the centred residue is negative
+#pragma unroll
+        for (int i = 0; i < l; i++) {
+            const u64 off = dc->drop_off[l][i];
+            const u64 x = c[i] - v + off + (s & (ql - off));
+            c[i] = mul_shoup_u(x, dc->drop_inv[l][i], dc->drop_inv_sh[l][i], dc->mod[i].q, dc->drop_negq[i]);
+        }
+    }
+    u64 *pout = out + (size_t)poly * KEEP * N + n;
+#pragma unroll
+    for (int i = 0; i < KEEP; i++) pout[(size_t)i * N] = c[i];
+}
+bool launch_limb_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, const u64 *in, u64 *out, u32 npoly, hipStream_t st)
+{
+    if (keep < 1 || keep >= L || L > MAX_L || !npoly) return false;
+    const u32 bpp = (N + TPB - 1) / TPB;
+    const dim3 grid(bpp * npoly), block(TPB);
+#define DROP_(L_, K_)                                                                                          \
+    case (L_) * 8 + (K_):                                                                                      \
+        hipLaunchKernelGGL((limb_drop_kernel<L_, K_>), grid, block, 0, st, dc, N, bpp, in, out);               \
+        return true
+    switch (L * 8 + keep) {
+        DROP_(2, 1);
+        DROP_(3, 1); DROP_(3, 2);
+        DROP_(4, 1); DROP_(4, 2); DROP_(4, 3);
+        DROP_(5, 1); DROP_(5, 2); DROP_(5, 3); DROP_(5, 4);
+        DROP_(6, 1); DROP_(6, 2); DROP_(6, 3); DROP_(6, 4); DROP_(6, 5);
+        DROP_(7, 1); DROP_(7, 2); DROP_(7, 3); DROP_(7, 4); DROP_(7, 5); DROP_(7, 6);
+    }
+#undef DROP_
+    return false;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Automorphism permutation in EVALUATION format (row A9): out[r][p] = in[r][map[p]]
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TPB) permute_kernel(u32 N, const u64 *__restrict__ in, const u32 *__restrict__ map,

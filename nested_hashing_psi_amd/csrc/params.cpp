@@ -250,6 +250,16 @@ std::string HostParams::init(u32 N_, u32 L_, u64 t_, const u64 *q, const u64 *p)
         dc.fold_ibt[k] = mm(dc.fold_ib[k], dc.tPinv_modq[k], qk);
         dc.fold_ibt_sh[k] = shoup(dc.fold_ibt[k], qk);
     }
+    for (u32 l = 0; l < L; l++) {
+        const u64 half = (Q[l] - 1) / 2;
+        dc.drop_negq[l] = 0 - Q[l];
+        for (u32 i = 0; i < l; i++) {
+            const u64 qi = Q[i];
+            dc.drop_inv[l][i] = invmod(Q[l] % qi, qi);
+            dc.drop_inv_sh[l][i] = shoup(dc.drop_inv[l][i], qi);
+            dc.drop_off[l][i] = (half + qi - 1) / qi * qi;
+        }
+    }
     return "";
 }
 

@@ -54,6 +54,11 @@ struct DevConsts {
     u64 t_inv_modq[8];
     u64 t_modq_sh[8];
     u64 Q_modt;
+    // limb drop of a result ciphertext (kernels_pie.hip "Limb drop"): dropping q_l turns the residue mod q_i, i < l, into
+    // (c_i - r) q_l^-1 with r the centred residue mod q_l
+    u64 drop_inv[8][8], drop_inv_sh[8][8];  // [l][i]  [q_l^-1]_{q_i} and its Shoup companion
+    u64 drop_off[8][8];                     // [l][i]  the smallest multiple of q_i that is >= (q_l - 1) / 2
+    u64 drop_negq[8];                       // 2^64 - q_i
     u32 N, logN, L, M;
 };
 

@@ -10,7 +10,7 @@ using namespace piehip;
 static thread_local std::string g_err;
 static const char *KNAMES[PIEHIP_NKERNELS] = {"stage_a_mac", "ntt_fwd", "ntt_inv",  "expand",   "tensor",    "scale_round",
                                               "digits",      "relin",   "mask_mul", "encode",   "automorph", "other",
-                                              "event_pair",  "tensor_ntt_inv"};
+                                              "event_pair",  "tensor_ntt_inv", "result_ntt_inv", "limb_drop", "result_ntt_fwd"};
 static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
 static void free_workspace(piehip_ctx *h);
 
@@ -118,6 +118,12 @@ int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus)
     return PIEHIP_OK;
 }
 
+int ensure_full_rows(piehip_ctx *h)
+{
+    if (h->res_limbs >= h->hp.L || h->d_full || !h->ws_cap_rows) return PIEHIP_OK;
+    return dev_alloc(&h->d_full, h->ws_cap_rows * 2 * h->LN());
+}
+
 void use_owned_inputs(piehip_ctx *h)
 {
     for (u32 q = 0; q < h->nq; q++) h->query[q].idx = h->query[q].idx_own, h->query[q].minus = h->query[q].minus_own;
@@ -128,7 +134,7 @@ void use_owned_inputs(piehip_ctx *h)
 // =================================================================================================
 extern "C" {
 
-int piehip_version(void) { return 102; }   // 101: piehip_profile_read_n, piehip_set_transform_slots, piehip_upload_turn_wait, piehip_rccl_abort; 102: seeded ciphertexts
+int piehip_version(void) { return 102; }   // 101: piehip_profile_read_n, piehip_set_transform_slots, piehip_upload_turn_wait, piehip_rccl_abort; 102: seeded ciphertexts (the result limbs came without a new number)
 const char *piehip_last_error(void) { return g_err.c_str(); }
 const char *piehip_kernel_name(int k) { return (k >= 0 && k < PIEHIP_NKERNELS) ? KNAMES[k] : "?"; }
 
@@ -161,6 +167,7 @@ int piehip_create(piehip_handle *out, uint32_t N, uint32_t L, uint64_t t, const 
                                      std::to_string(ndev) + " devices): libpiehip has no CPU fallback");
     }
     h->device = device;
+    h->res_limbs = L;
 #define CHK_(expr)                                                                          \
     do {                                                                                    \
         hipError_t e_ = (expr);                                                             \
@@ -445,6 +452,7 @@ static void free_workspace(piehip_ctx *h)
     dev_free(&h->d_acc);
     dev_free(&h->d_prod);
     dev_free(&h->d_out);
+    dev_free(&h->d_full);
     ws_free(h->ws);
     h->ws_cap_rows = h->ws_cap_K = 0;
 }
@@ -457,7 +465,7 @@ static int alloc_workspace(piehip_ctx *h, u32 K, u32 b)
     const size_t LN = h->LN(), rows = (size_t)b * h->nq;
     if (h->d_acc && h->d_out && h->ws.eqp && h->ws_cap_K == K && rows <= h->ws_cap_rows && (K <= 2 || h->d_prod)) {
         h->ws.nb = (u32)rows;
-        return PIEHIP_OK;
+        return ensure_full_rows(h);
     }
     free_workspace(h);
     int rc;
@@ -467,7 +475,7 @@ static int alloc_workspace(piehip_ctx *h, u32 K, u32 b)
     if ((rc = ws_alloc(h, h->ws, (u32)rows))) return rc;
     h->ws_cap_rows = rows;
     h->ws_cap_K = K;
-    return PIEHIP_OK;
+    return ensure_full_rows(h);
 }
 
 static int alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db = true)
@@ -1011,13 +1019,36 @@ int piehip_sync(piehip_handle h)
     return PIEHIP_OK;
 }
 
+// Result limbs (include/piehip.h): the setting of a handle.  The full-width rows the reduction reads are allocated here, outside the
+// timed path, and stay with the workspace: going back and forth between settings allocates nothing.
+int piehip_set_result_limbs(piehip_handle h, uint32_t keep)
+{
+    NEED(h);
+    if (keep < 1 || keep > h->hp.L) return fail(PIEHIP_EINVAL, "set_result_limbs: keep must be between 1 and L");
+    if (keep < h->hp.L && h->use_graph)
+        return fail(PIEHIP_ESTATE, "set_result_limbs: a handle that replays a captured graph (piehip_set_graph) hands out full results");
+    HIPCHK(hipSetDevice(h->device));
+    const u32 before = h->res_limbs;
+    h->res_limbs = keep;
+    const int rc = ensure_full_rows(h);
+    if (rc) h->res_limbs = before;
+    return rc;
+}
+int piehip_get_result_limbs(piehip_handle h, uint32_t *keep)
+{
+    NEED_RO(h);
+    if (!keep) return fail(PIEHIP_EINVAL, "null out");
+    *keep = h->res_limbs;
+    return PIEHIP_OK;
+}
+
 int piehip_get_results(piehip_handle h, uint64_t *out)
 {
     NEED(h);
     if (!out) return fail(PIEHIP_EINVAL, "null out");
     if (!h->d_out) return fail(PIEHIP_ESTATE, "no results");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(out, h->d_out, sizeof(u64) * (size_t)h->b * h->nq * 2 * h->LN(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out, h->d_out, sizeof(u64) * (size_t)h->b * h->nq * h->res_ct_words(), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PIEHIP_OK;
 }
@@ -1034,7 +1065,7 @@ int piehip_copy_results_device(piehip_handle h, void *d_dst)
     NEED(h);
     if (!d_dst) return fail(PIEHIP_EINVAL, "null destination");
     if (!h->d_out) return fail(PIEHIP_ESTATE, "no results");
-    HIPCHK(hipMemcpyAsync(d_dst, h->d_out, sizeof(u64) * (size_t)h->b * h->nq * 2 * h->LN(), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_dst, h->d_out, sizeof(u64) * (size_t)h->b * h->nq * h->res_ct_words(), hipMemcpyDeviceToDevice, h->stream));
     return PIEHIP_OK;
 }
 

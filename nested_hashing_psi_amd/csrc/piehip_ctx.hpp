@@ -172,6 +172,10 @@ struct piehip_ctx {
     u64 *d_acc = nullptr;   // [b][K][2][L][N]
     u64 *d_prod = nullptr;  // [b][2][L][N]  (K > 2 only)
     u64 *d_out = nullptr;   // [b][2][L][N]
+    // piehip_set_result_limbs: run() hands its results out on the first res_limbs limbs of Q (L = as they are).  With fewer, the
+    // product chain writes full rows into d_full and the reduction writes [b][nq][2][res_limbs][N] into the result buffer
+    u32 res_limbs = 0;
+    u64 *d_full = nullptr;  // [b][nq][2][L][N], allocated with the first setting below L and kept with the workspace
     piehip::MulWs ws;
     size_t ws_cap_rows = 0;   // rows (bin layer x query) the workspace arrays were allocated for; ws.nb = rows in use
     u32 ws_cap_K = 0;
@@ -199,6 +203,7 @@ struct piehip_ctx {
     size_t pool_used = 0;
 
     size_t LN() const { return (size_t)hp.L * hp.N; }
+    size_t res_ct_words() const { return 2 * (size_t)res_limbs * hp.N; }   // one result ciphertext as it leaves the handle
 };
 
 namespace piehip {
@@ -285,6 +290,10 @@ void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u6
 void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
                  const u64 *mask, u64 *out, bool xq_ready = false, bool out_is_result = false);
 int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out);
+// result limbs (piehip_run.cpp): `rows` ciphertexts full[rows][2][L][N] (EVALUATION, standard order; overwritten) reduced to their
+// first `keep` limbs, out[rows][2][keep][N], on the handle's current stream.  out_is_result: out is a run()'s result buffer
+void enqueue_mod_reduce(piehip_ctx *h, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result = false);
+int ensure_full_rows(piehip_ctx *h);   // piehip.cpp: d_full for the workspace's rows when the handle reduces its results
 // device input buffers of query q of the batch (owned copies: the host setters and the staged uploads write them)
 int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus);
 void use_owned_inputs(piehip_ctx *h);   // the next run() evaluates the owned copies of every query of the batch

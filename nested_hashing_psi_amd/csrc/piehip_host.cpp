@@ -239,7 +239,7 @@ int piehip_host_buffers_q(piehip_handle h, uint32_t q, uint64_t **idx, uint64_t 
     if (!h->K) return fail(PIEHIP_ESTATE, "load the database first (the buffer sizes depend on K, E and b)");
     if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
     HIPCHK(hipSetDevice(h->device));
-    const size_t iw = (size_t)h->K * h->E * 2 * h->LN(), rw = (size_t)h->b * h->nq * 2 * h->LN();
+    const size_t iw = (size_t)h->K * h->E * 2 * h->LN(), rw = (size_t)h->b * h->nq * h->res_ct_words();
     if (h->pin_idx_words != iw)  // another database shape: every query's index staging goes
         for (Query &s : h->query)
             if (s.pin_idx) {

@@ -177,6 +177,30 @@ int piehip_base_convert(piehip_handle h, int which, const uint64_t *in, uint32_t
     return PIEHIP_OK;
 }
 
+int piehip_mod_reduce(piehip_handle h, const uint64_t *in, uint32_t nct, uint32_t keep, uint64_t *out)
+{
+    NEED(h);
+    if (!in || !out || !nct) return fail(PIEHIP_EINVAL, "null operand");
+    if (keep < 1 || keep > h->hp.L) return fail(PIEHIP_EINVAL, "mod_reduce: keep must be between 1 and L");
+    if (nct > (1u << 20)) return fail(PIEHIP_EINVAL, "mod_reduce: at most 2^20 ciphertexts per call");
+    const u32 N = h->hp.N, L = h->hp.L;
+    const size_t win = (size_t)nct * 2 * L * N, wout = (size_t)nct * 2 * keep * N;
+    if (keep == L) {
+        if (out != in) memcpy(out, in, win * sizeof(u64));
+        return PIEHIP_OK;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    Tmp tmp;
+    TMPGET(din, win);
+    TMPGET(dout, wout);
+    HIPCHK(hipMemcpy(din, in, win * sizeof(u64), hipMemcpyHostToDevice));
+    enqueue_mod_reduce(h, din, nct, keep, dout);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, dout, wout * sizeof(u64), hipMemcpyDeviceToHost));
+    return PIEHIP_OK;
+}
+
 int piehip_bench_ntt(piehip_handle h, uint32_t nlimbs, uint32_t mod_count, int flags, uint32_t iters, double *ms_per_launch)
 {
     NEED(h);

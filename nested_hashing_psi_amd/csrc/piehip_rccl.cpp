@@ -284,6 +284,8 @@ int piehip_rccl_bin_slice(uint32_t b_total, int nranks, int rank, uint32_t *bin_
 int piehip_gather_results(piehip_handle h, uint32_t b_total, int root, void *d_out)
 {
     NEED(h);   // the handle's stream is behind the run whose results travel
+    if (h->res_limbs != h->hp.L)   // the ranks' row sizes would have to agree, and nothing checks a setting across ranks
+        return fail(PIEHIP_ESTATE, "gather_results: results reduced to fewer limbs (piehip_set_result_limbs) are not gathered");
     if (!h->comm) return fail(PIEHIP_ESTATE, "gather_results: no communicator (piehip_rccl_init / piehip_rccl_attach)");
     const int G = h->comm_ranks, me = h->comm_rank;
     if (root < 0 || root >= G) return fail(PIEHIP_EINVAL, "gather_results: root outside the communicator");
@@ -322,6 +324,8 @@ int piehip_gather_results(piehip_handle h, uint32_t b_total, int root, void *d_o
 int piehip_gather_results_host(piehip_handle h, uint32_t b_total, int root, uint64_t **results)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (h->res_limbs != h->hp.L)
+        return fail(PIEHIP_ESTATE, "gather_results: results reduced to fewer limbs (piehip_set_result_limbs) are not gathered");
     if (!h->comm) return fail(PIEHIP_ESTATE, "gather_results: no communicator (piehip_rccl_init / piehip_rccl_attach)");
     const bool is_root = h->comm_rank == root;
     if (is_root && !results) return fail(PIEHIP_EINVAL, "gather_results: the root needs a destination");

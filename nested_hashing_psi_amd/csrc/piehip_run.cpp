@@ -140,6 +140,41 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
     }
 }
 
+// Result limbs (include/piehip.h): rows of full-width ciphertexts to their first `keep` limbs.  Three launches on the current queue: the
+// inverse transform of every limb (standard order in, where relin_mac and the K = 1 mask multiply write), the limb-drop kernel --
+// which holds a coefficient's L residues in registers -- and the forward transform of the kept limbs, in place in `out`.  All limbs
+// are transformed; the other schedule the definition allows (inverse-transform the dropped limbs only, forward-transform a
+// correction and combine in EVALUATION format) has not been built or measured.  No outer-stage folding either: the rows arrive in
+// standard order from kernels that do not fold.
+// In a run that brings its results down to host memory the next queue group is released here, in front of the limb-drop kernel:
+// this group then has that kernel and the forward transform of the kept limbs left, about what the key-switch MAC alone is when
+// nothing is reduced, and its (smaller) download still travels under the next group's evaluation.
+void enqueue_mod_reduce(piehip_ctx *h, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result)
+{
+    const u32 N = h->hp.N, L = h->hp.L;
+    const double W = 8.0 * N;
+    {
+        ProfScope ps(h, PIEHIP_K_RESULT_NTT_INV, 2 * W * rows * 2 * L);
+        launch_ntt(h->plan, full, rows * 2 * L, 0, L, true, h->stream);
+    }
+    if (out_is_result) {
+        // the result buffer may still be read by work the caller queued on the handle's stream before this run
+        if (h->wait_before_results) (void)hipStreamWaitEvent(h->stream, h->wait_before_results, 0);
+        if (h->chain_armed) {
+            h->chain_armed = false;
+            (void)hipEventRecord(h->ev_chain, h->stream);
+        }
+    }
+    {
+        ProfScope ps(h, PIEHIP_K_LIMB_DROP, W * rows * 2 * (L + keep));
+        launch_limb_drop(h->d_dc, N, L, keep, full, out, rows * 2, h->stream);
+    }
+    {
+        ProfScope ps(h, PIEHIP_K_RESULT_NTT_FWD, 2 * W * rows * 2 * keep);
+        launch_ntt(h->plan, out, rows * 2 * keep, 0, keep, false, h->stream);
+    }
+}
+
 // Queues of a run().  The default is two when the handle evaluates enough bin layers to fill the chip twice over; below that
 // every launch is bound by its own latency, a second queue only interleaves two latency-bound chains on the same CUs, and one
 // queue is faster (measured at the C3 ring: 2 layers 115 vs 146 us, 5 layers of the E = 40 row 217 vs 239 us, 7 layers even).
@@ -182,8 +217,29 @@ u32 run_group_size(u32 b, u32 ng, u32 g)
 // =================================================================================================
 extern "C" {
 
-// Bin layers [b0, b0 + nb) of run() on the handle's current stream: stage A, then the product chain.
+// Bin layers [b0, b0 + nb) of run() on the handle's current stream: stage A, then the product chain; results[b][nq][2][L][N].
+static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results);
+// ... and, on a handle that hands its results out on fewer limbs, their reduction: results[b][nq][2][res_limbs][N].  The chain then
+// writes the handle's full-width rows, which no caller reads: what orders a run against the result buffer's readers (and releases
+// the next queue group of a host-results run) moves from the chain's last kernel to the reduction.
 static void enqueue_run_bins(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
+{
+    const u32 keep = h->res_limbs, nq = h->nq;
+    if (keep >= h->hp.L) {
+        enqueue_run_bins_full(h, b0, nb, results);
+        return;
+    }
+    const hipEvent_t wait = h->wait_before_results;
+    const bool chain = h->chain_armed;
+    h->wait_before_results = nullptr;
+    h->chain_armed = false;
+    enqueue_run_bins_full(h, b0, nb, h->d_full);
+    h->wait_before_results = wait;
+    h->chain_armed = chain;
+    const size_t r0 = (size_t)b0 * nq;
+    enqueue_mod_reduce(h, h->d_full + r0 * 2 * h->LN(), nb * nq, keep, results + r0 * h->res_ct_words(), true);
+}
+static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
 {
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M, K = h->K, b = h->b, E = h->E, nq = h->nq;
     const size_t LN = h->LN();
@@ -272,7 +328,7 @@ static void enqueue_run_bins(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
 // the result ciphertexts of bin layers [b0, b0 + nb) (rows [bin layer][query]) to the caller's host array, on the current queue
 static hipError_t download_rows(piehip_ctx *h, const u64 *d_results, u32 b0, u32 nb)
 {
-    const size_t row = (size_t)h->nq * 2 * h->LN();
+    const size_t row = (size_t)h->nq * h->res_ct_words();
     return hipMemcpyAsync(h->host_results + (size_t)b0 * row, d_results + (size_t)b0 * row, (size_t)nb * row * sizeof(u64),
                           hipMemcpyDeviceToHost, h->stream);
 }
@@ -284,6 +340,7 @@ int piehip_run_into(piehip_handle h, void *d_results)
     if (!h->K || !h->d_db) return fail(PIEHIP_ESTATE, "run: database not loaded");
     if (!h->d_acc || !h->ws.eqp) return fail(PIEHIP_ESTATE, "run: no workspace (an earlier allocation failed: piehip_set_query_batch / load)");
     if (!run_keys_loaded(h)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
+    if (h->res_limbs < h->hp.L && !h->d_full) return fail(PIEHIP_ESTATE, "run: no rows for the result reduction (an earlier allocation failed: piehip_set_result_limbs)");
     for (u32 q = 0; q < h->nq; q++) {
         if (h->query[q].idx && h->query[q].minus) continue;
         if (q) return fail(PIEHIP_ESTATE, "run: a query of the batch has no index matrix or minus element");
@@ -419,6 +476,8 @@ int piehip_join(piehip_handle h)
 int piehip_set_graph(piehip_handle h, int on)
 {
     NEED_RO(h);
+    if (on && h->res_limbs < h->hp.L)
+        return fail(PIEHIP_ESTATE, "set_graph: the captured graph hands out full results (piehip_set_result_limbs is below L)");
     h->use_graph = on != 0;
     if (!on) drop_graph(h);
     return PIEHIP_OK;

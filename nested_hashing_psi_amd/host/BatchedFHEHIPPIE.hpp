@@ -106,7 +106,21 @@ public:
         }
         lists.assign(nq, std::vector<LimbCt>(b));
         listStale.assign(nq, false);
+        PieContext::check(piehip_get_result_limbs(cc->handle(), &resLimbs));
     }
+
+    // Result limbs (include/piehip.h "Result limbs"): from the next run() on the result ciphertexts are [2][keep][N], on the first
+    // `keep` primes of the chain.  The page-locked result array follows the setting; result lists of earlier runs are dropped.
+    void setResultLimbs(uint32_t keep)
+    {
+        PieContext::check(piehip_set_result_limbs(cc->handle(), keep));
+        PieContext::check(piehip_host_buffers_q(cc->handle(), 0, nullptr, nullptr, &pinRes));
+        resLimbs = keep;
+        std::fill(listStale.begin(), listStale.end(), false);
+        for (auto &l : lists)
+            for (auto &c : l) c.limbs.clear();
+    }
+    uint32_t resultLimbs() const { return resLimbs; }
 
     void setIndex(uint32_t q, std::vector<std::vector<LimbCt>> &&indexMatrix)  // [K][E] ciphertexts of query q
     {
@@ -220,13 +234,14 @@ public:
     {
         checkQuery(q);
         if (listStale[q]) {
-            const size_t ct = ctWords();
+            const size_t ct = resultWords();
             for (uint32_t i = 0; i < b; i++) lists[q][i].limbs.assign(resultTowers(q, i), resultTowers(q, i) + ct);
             listStale[q] = false;
         }
         return lists[q];
     }
-    const uint64_t *resultTowers(uint32_t q, uint32_t i) const { return pinRes + ((size_t)i * nq + q) * ctWords(); }  // rows [bin layer][query]
+    const uint64_t *resultTowers(uint32_t q, uint32_t i) const { return pinRes + ((size_t)i * nq + q) * resultWords(); }  // rows [bin layer][query]
+    size_t resultWords() const { return 2 * (size_t)resLimbs * cc->ringDimension(); }  // one result ciphertext, [2][resultLimbs][N]
 
 private:
     struct QueryState {
@@ -254,7 +269,8 @@ private:
     PieContext *cc = nullptr;
     uint32_t K = 0, b = 0, E = 0, nq = 0;
     std::vector<QueryState> st;
-    uint64_t *pinRes = nullptr;  // [b][nq][2][L][N], page-locked, owned by the library
+    uint64_t *pinRes = nullptr;  // [b][nq][2][resLimbs][N], page-locked, owned by the library
+    uint32_t resLimbs = 0;       // piehip_set_result_limbs: L unless setResultLimbs said otherwise
     std::vector<std::vector<LimbCt>> lists;
     std::vector<bool> listStale;
     bool rerun = false;
@@ -322,6 +338,11 @@ public:
     // resultTowers(i) reads them in place.
     std::vector<LimbCt> &getResultList() { return staged.getResultList(0); }
     const uint64_t *resultTowers(uint32_t i) const { return staged.resultTowers(0, i); }  // [2][L][N], valid until the next run()
+    // Result limbs (include/piehip.h "Result limbs"): run() hands its results out as [2][keep][N] on the first `keep` primes of the
+    // chain -- a quarter of the bytes at C3 with keep = 1 -- which decrypt in the context (N, keep, t, q[:keep]).  The reference
+    // operator has no counterpart (OpenFHE's Compress is the call a maintainer would make: INTEGRATION.md).  Default: L.
+    void setResultLimbs(uint32_t keep) { staged.setResultLimbs(keep); }
+    uint32_t resultLimbs() const { return staged.resultLimbs(); }
 
     // .hpp:40-43, [K][E] ciphertexts
     void setIndex(std::vector<std::vector<LimbCt>> &&indexMatrix) { staged.setIndex(0, std::move(indexMatrix)); }
@@ -406,6 +427,9 @@ public:
     // the b result ciphertexts of query q (materialised on the first call after a run(); resultTowers reads them in place)
     std::vector<LimbCt> &getResultList(uint32_t q) { return staged.getResultList(q); }
     const uint64_t *resultTowers(uint32_t q, uint32_t i) const { return staged.resultTowers(q, i); }  // rows [bin layer][query]
+    // result limbs of every query of the batch (see BatchedFHEHIPPIE::setResultLimbs): rows [bin layer][query] of [2][keep][N]
+    void setResultLimbs(uint32_t keep) { staged.setResultLimbs(keep); }
+    uint32_t resultLimbs() const { return staged.resultLimbs(); }
 
 private:
     PieContext &cc;

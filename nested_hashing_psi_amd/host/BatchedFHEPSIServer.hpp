@@ -75,6 +75,12 @@ public:
         maskSeed = mask;
     }
 
+    // Result limbs (include/piehip.h "Result limbs"): the result messages carry the first `keep` limbs of every result ciphertext
+    // (0 = all L, the reference's behaviour) -- reduced on the device before they come down, framed with `keep` limbs by sendResult.
+    // The clients decrypt in the context (N, keep, t, q[:keep]).  Call before run(); std::invalid_argument from the set-up phase when
+    // keep exceeds the clients' L.
+    void setResultLimbs(uint32_t keep) { resultLimbs = keep; }
+
     long long offlineComputation = 0, onlineComputation = 0;  // microseconds, PSIServer.hpp:89-103
 
     void runSetUpPhase()  // receiveAndSetContextAndKeys, BatchedFHEPSIServer.cpp:21-54, once per client
@@ -96,6 +102,7 @@ public:
                 // the table sizes are known since construction (htParams): allocate the database, workspace and scratch now, so
                 // the timed offline phase does not pay for hipMalloc
                 PieContext::check(piehip_set_query_batch(cc->handle(), nq));
+                if (resultLimbs) PieContext::check(piehip_set_result_limbs(cc->handle(), resultLimbs));
                 PieContext::check(piehip_reserve(cc->handle(), serverSet.size(), ht.numberOfSimpleHashFunctions, ht.eachSimpleTableSize,
                                                  ht.numberOfCuckooHashFunctions, ht.maxItemsPerPosition, ht.eachCuckooTableSize, 0,
                                                  ht.maxItemsPerPosition));
@@ -179,9 +186,11 @@ public:
         PieContext::check(piehip_run_staged(cc->handle(), pinRes));
         PieContext::check(piehip_run_host_wait(cc->handle()));
         onlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
+        const uint32_t keep = resultLimbs ? resultLimbs : L;   // limbs per result ciphertext as it leaves the device and the server
+        const size_t rct = 2 * (size_t)keep * N;
         for (uint32_t q = 0; q < nq; q++)
             for (uint32_t i = 0; i < b; i++) {  // sendResult, .cpp:143-152; rows of the result array are [bin layer][query]
-                const auto out = wire::packCiphertexts(pinRes + ((size_t)i * nq + q) * ct, 1, L, N);
+                const auto out = wire::packCiphertexts(pinRes + ((size_t)i * nq + q) * rct, 1, keep, N);
                 wire::writeWithSize(fds[q], out.data(), out.size());
             }
     }
@@ -192,6 +201,7 @@ private:
     HashTableParameter ht;
     uint64_t hashSeed;
     uint64_t evictSeed = 0, shuffleSeed = 0, maskSeed = 0;
+    uint32_t resultLimbs = 0;   // setResultLimbs: 0 = every limb
     std::vector<uint64_t> qMod;
     std::unique_ptr<PieContext> cc;
 };

@@ -183,6 +183,21 @@ class PieContext:
         _check(lib().piehip_base_convert(self._h, which, ap, npoly, out.ctypes.data_as(u64p)))
         return out
 
+    def mod_reduce(self, cts, keep):
+        """ciphertexts [..][2][L][N] switched down to the first `keep` limbs of the chain, [..][2][keep][N] (piehip_mod_reduce): they
+        decrypt in the context (N, keep, t, q[:keep]) with the first `keep` limbs of the secret key"""
+        a, ap = _u64(cts)
+        if a.ndim < 3 or a.shape[-3:] != (2, self.L, self.N):
+            raise ValueError("ciphertexts must be [..][2][L][N]")
+        keep = int(keep)
+        if not 1 <= keep <= self.L:
+            raise ValueError("keep must be between 1 and L")
+        out = np.empty(a.shape[:-2] + (keep, self.N), dtype=np.uint64)
+        out.fill(0)
+        nct = int(np.prod(a.shape[:-3], dtype=np.int64))
+        _check(lib().piehip_mod_reduce(self._h, ap, nct, keep, out.ctypes.data_as(u64p)))
+        return out
+
     def load_relin_key(self, evk, query=None):
         """InsertEvalMultKey.  query=q: the key of query q's client in a batch (piehip_load_relin_key_q; the queries of a batch are
         different clients', each with its own key -- BatchedFHEPSIServer.cpp:45-49); queries without one use the context's key."""
@@ -431,7 +446,8 @@ class BatchedFHEHIPPIE:
         _check(lib().piehip_set_minus_device_q(self.cc._h, query, ptr))
 
     def run(self, sync=True, into=None):
-        """into: device address of a caller-owned result buffer [b][2][L][N] (piehip_run_into; [b][nq][2][L][N] for a query batch)"""
+        """into: device address of a caller-owned result buffer [b][2][L][N] (piehip_run_into; [b][nq][2][L][N] for a query batch;
+        resultLimbs in place of L after setResultLimbs)"""
         if into is None:
             _check(lib().piehip_run(self.cc._h))
         else:
@@ -439,9 +455,22 @@ class BatchedFHEHIPPIE:
         if sync:
             _check(lib().piehip_sync(self.cc._h))
 
+    def setResultLimbs(self, keep):
+        """run() hands its result ciphertexts out on the first `keep` limbs of the chain (piehip_set_result_limbs; L = as they are):
+        every result array is then [..][2][keep][N] and decrypts in the context (N, keep, t, q[:keep]) -- client.decrypt(.., limbs=keep).
+        Page-locked result arrays follow the setting: ask hostBuffers() again after changing it."""
+        _check(lib().piehip_set_result_limbs(self.cc._h, int(keep)))
+        self._results = None
+
+    @property
+    def resultLimbs(self):
+        n = C.c_uint32()
+        _check(lib().piehip_get_result_limbs(self.cc._h, C.byref(n)))
+        return n.value
+
     def _res_shape(self):
-        nq = self.nq
-        return (self.b, 2, self.cc.L, self.cc.N) if nq == 1 else (self.b, nq, 2, self.cc.L, self.cc.N)
+        nq, keep = self.nq, self.resultLimbs
+        return (self.b, 2, keep, self.cc.N) if nq == 1 else (self.b, nq, 2, keep, self.cc.N)
 
     def hostBuffers(self, query=0):
         """page-locked numpy views (index matrix [K][E][2][L][N] and minus element [2][L][N] of query `query` of the batch, and the
@@ -581,11 +610,11 @@ class BatchedFHEHIPPIE:
         vector) the array belongs to the operator and is overwritten by the next call; copy it to keep it.  (A fresh
         14 MiB numpy array per query costs ~25 ms of first-touch page faults under the device-to-host copy.)"""
         nq = self.nq
-        want = (self.b, 2, self.cc.L, self.cc.N) if nq == 1 else (self.b, nq, 2, self.cc.L, self.cc.N)
+        want = self._res_shape()
         if getattr(self, "_results", None) is not None and self._results.shape != want:
             self._results = None
         if getattr(self, "_results", None) is None:
-            self._results = np.empty((self.b, 2, self.cc.L, self.cc.N) if nq == 1 else (self.b, nq, 2, self.cc.L, self.cc.N), dtype=np.uint64)
+            self._results = np.empty(want, dtype=np.uint64)
             self._results.fill(0)
         out = self._results
         _check(lib().piehip_get_results(self.cc._h, out.ctypes.data_as(u64p)))
