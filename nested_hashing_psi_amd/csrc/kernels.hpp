@@ -23,19 +23,44 @@ struct PerDeviceOnce {
     }
 };
 
-// Device-resident NTT tables: for modulus a, tables + a*4*N holds tw | tw_sh | itw | itw_sh (N each).
+// Which transform kernel a call takes: radix-2 stages in LDS (kernels_ntt.hip), 32 coefficients per thread (kernels_ntt_fast.hip),
+// 16 coefficients per thread (ntt16_kernel.h, kernels_ntt16.hip).  DESIGN.md section 5a is the table; ntt_route() implements it.
+enum class NttKernel { radix2, blocked32, blocked16 };
+struct NttRoute {
+    NttKernel kernel;
+    u32 s0;             // log2 of the slices per limb
+    u32 global_stages;  // outermost stages run in global memory around the slice kernel (a folded call has none: its neighbours apply it)
+    bool extra() const { return kernel != NttKernel::radix2 && !global_stages; }  // the call honours NttExtra
+};
+
+// Device-resident NTT tables (for modulus a, tables + a*4*N holds tw | tw_sh | itw | itw_sh, N each) and what the context does with
+// them: every field below max_slots is decided once, by ntt_plan_decide() in piehip_create, and only read afterwards.
 struct NttPlan {
     const u64 *tables;
     const u64 *twp;       // interleaved {w, w_shoup} pairs: per modulus [fwd N pairs][inv N pairs]
-    const u64 *twc;       // pass-C twiddles in kernel order: per modulus [fwd][inv], see build_twc_table
-    const u64 *twc_fold;  // the same for the folded configuration (two half-size slices per limb), or null
-    const u64 *twk16 = nullptr;       // ntt16_kernel.h: kernel-ordered pairs of passes 3, 4, one 2^13 slice per limb (ring 2^13), or null
-    const u64 *twk16_fold = nullptr;  // ... two folded slices per limb: of 2^13 (ring 2^14) or 2^14 coefficients (ring 2^15), or null
+    const u64 *twc = nullptr;       // 32-coefficient kernel, pass-C twiddles in kernel order: per modulus [fwd][inv], see build_twc_table
+    const u64 *twc_fold = nullptr;  // ... for two folded half-size slices per limb (fold)
+    const u64 *twk16 = nullptr;     // 16-coefficient kernel: kernel-ordered pairs of passes 3, 4 for the slices of its lane order
     const DevConsts *dc;  // device pointer
     u32 N, logN;
     u32 num_cus;
     u32 max_slots = 0;    // piehip_set_transform_slots: cap on the persistent transform grids (workgroups), 0 = every slot
-    bool force_generic;   // tests: route every size through the radix-2 LDS kernel
+    bool lane_order = false;     // the register-blocked kernels apply: arrays that stay inside the library keep their EVALUATION side as
+                                 // the threads of lane_kernel hold it (sigma), keys and masks have lane-ordered copies
+    bool fold = false;           // lane-ordered transforms run as two half-size slices per limb; the neighbouring coefficient-wise
+                                 // kernels apply the outermost stage (kernels_pie.hip "Outer-stage folding")
+    NttKernel lane_kernel = NttKernel::radix2;  // the kernel that defines the lane order
+    u32 lane_logn = 0;           // log2 of its slice length,
+    u32 lane_T = 0;              // its threads per slice
+    u32 lane_kp = 16;            // and coefficient pairs per thread (16: kernels_ntt_fast.hip, 8: ntt16_kernel.h)
+    bool small_moduli = false;   // every Q and P modulus lies in (2^59, 2^60): v_mad_u64_u32 column accumulators, one-word Barrett
+    // schedule switches derived from the above (piehip_run.cpp)
+    bool xq_reuse = false;         // the inverse transform of operand X drops a lane-ordered copy into the QP array, the forward skips it
+    bool x_direct = false;         // stage A of a query batch may write X there in the first place (StageAXOut)
+    bool fused_tensor = false;     // launch_ntt16_tensor instead of launch_tensor + inverse transform
+    bool digits_with_d01 = false;  // the key-switch digits join the forward launch of d0, d1 (Ntt16Digits)
+    bool digit_lift_lane = false;  // launch_ntt_digits instead of launch_digits + transform: lane-ordered key switches,
+    bool digit_lift_std = false;   // ... standard-order key switches (FHEHIPPIE, piehip_eval_automorph)
     // CUs the persistent transform grids may fill (two workgroup slots of 512 threads, or one of 1024, per CU)
     u32 transform_cus() const
     {
@@ -44,12 +69,19 @@ struct NttPlan {
         return c < num_cus ? (c ? c : 1u) : num_cus;
     }
 };
+// fills in everything from lane_order on, from N / logN and the two facts about the moduli: lazy_ok -- every modulus, t included, is
+// below 2^60 (lazy residues need 8q < 2^63) -- and small_moduli
+void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli);
+// sigma, folded: as for launch_ntt.  Requires sigma <= pl.lane_order and folded <= pl.fold (the callers' wrappers mask them)
+NttRoute ntt_route(const NttPlan &pl, bool inverse, bool sigma, bool folded);
 
-// In-place negacyclic NTT over `nlimbs` limbs [nlimbs][N]; limb i uses modulus mod_base + i % mod_count.
-// (replaces DCRTPoly::SetFormat under BatchedFHEHIPPIE.cpp:123; SURVEY 8a row A1)
+// host side of piehip_create: kernel-ordered twiddles of one (modulus, direction) from its natural-order {w, w_shoup} pairs, and the
+// map lane-order position -> standard position, for the 32-coefficient kernel (s0 = ~0u: no lane order, identity) and the 16-coefficient one
 void build_twc_table(const u64 *nat_pairs, u32 logN, u32 s0, std::vector<u64> &out);
-u32 ntt_fast_s0(u32 logN);  // log2 slices per limb the fast kernel would use, or ~0u if it does not apply
-// Optional extras of the register-blocked kernel (ciphertext multiplication, kernels_ntt_fast.hip):
+void build_twk16_table(const u64 *nat_pairs, u32 s0, u32 slice_log, std::vector<u64> &out);  // slices of 2^13 or 2^14
+void ntt_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map);
+void ntt16_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map);
+// Optional extras of the register-blocked kernels (ciphertext multiplication), honoured where NttRoute::extra():
 //   inverse, standard order in:  limbs [nb][copy_K][2][copy_L]; the lane-ordered EVALUATION input of operand 0 of every
 //                                bin is also written to the Q limbs of copy_out[nb][4][copy_M][N] (slots 0, 1)
 //   forward, lane order:         lazy_out -- no final normalisation
@@ -64,53 +96,37 @@ struct NttExtra {
     bool x_lane_in = false; // 16-coefficient kernel, inverse, standard order in: the operand-0 polynomials are READ, lane-ordered, from
                             // where copy_out would have put them (stage A wrote them there: StageAXOut) and nothing is copied
 };
-// The 16-coefficients-per-thread kernel (ntt16_kernel.h, kernels_ntt16.hip) for slices of 2^13 and 2^14 coefficients: every transform whose
-// EVALUATION side is in lane order, and every inverse transform.  Its lane order differs from the 32-coefficient kernel's:
-// a context uses one of the two for all lane-ordered arrays (ntt16_applies).  Returns false when it does not apply.
-void build_twk16_table(const u64 *nat_pairs, u32 s0, u32 slice_log, std::vector<u64> &out);  // slices of 2^13 or 2^14
-void ntt16_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map);
-// dg (forward, lane order, mod_base 0, mod_count L): the BV key-switch digits of nb polynomials join the launch -- limb (bin, i, j)
-// of dig[nb][L][L][N] = transform of the centred lift into q_j of residue limb i of the COEFFICIENT polynomial d2 + bin * stride2
-// (replaces launch_digits + a second transform launch)
+// In-place negacyclic NTT over `nlimbs` limbs [nlimbs][N]; limb i uses modulus mod_base + i % mod_count.
+// (replaces DCRTPoly::SetFormat under BatchedFHEHIPPIE.cpp:123; SURVEY 8a row A1)
+// sigma: the EVALUATION side is in the plan's lane order (internal arrays only); folded: the outermost stage is NOT done here, the
+// limb is transformed as two independent half-size slices.  The kernel follows from ntt_route().
+void launch_ntt(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, hipStream_t st,
+                bool sigma = false, bool folded = false, const NttExtra *ex = nullptr);
+// The launchers below are what launch_ntt dispatches to; the schedule calls them directly only for the fusions, and only where
+// the plan's switch says so (they assert it).
+void launch_ntt_fast(const NttPlan &pl, const u64 *twc, u32 s0, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse,
+                     bool sigma, hipStream_t st, const u64 *lift_src = nullptr, u32 lift_L = 0, const NttExtra *ex = nullptr);
+// dg (forward, lane order, mod_base 0, mod_count L; pl.digits_with_d01): the BV key-switch digits of nb polynomials join the launch --
+// limb (bin, i, j) of dig[nb][L][L][N] = transform of the centred lift into q_j of residue limb i of the COEFFICIENT polynomial
+// d2 + bin * stride2 (replaces launch_digits + a second transform launch)
 struct Ntt16Digits {
     const u64 *d2;
     size_t stride2;
     u64 *dig;
     u32 nb, L;
 };
-bool launch_ntt16(const NttPlan &pl, bool folded, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, bool sigma,
-                  hipStream_t st, const NttExtra *ex, const Ntt16Digits *dg = nullptr);
-// The tensor product fused into the load phase of the inverse transform that follows it (16-coefficient kernel, every modulus in
-// (2^59, 2^60), lane order): e[nb][4][M][N] (a0 a1 b0 b1, EVALUATION, [0, 8q) residues) -> d[nb][3][M][N] in COEFFICIENT format, as
-// launch_tensor + launch_ntt16(d, nb * 3 * M, 0, M, inverse, sigma) leave it.  Returns false when it does not apply or the
-// library was built with -DPIEHIP_FUSE_TENSOR=0 (the two-launch schedule, for A/B runs): callers then issue the two launches.
+void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, bool sigma, hipStream_t st,
+                  const NttExtra *ex, const Ntt16Digits *dg = nullptr);
+// pl.fused_tensor: the tensor product in the load phase of the inverse transform that follows it: e[nb][4][M][N] (a0 a1 b0 b1,
+// EVALUATION, lane order, [0, 8q) residues) -> d[nb][3][M][N] in COEFFICIENT format, as launch_tensor +
+// launch_ntt(d, nb * 3 * M, 0, M, inverse, sigma, fold) leave it.  -DPIEHIP_FUSE_TENSOR=0 clears the switch (two launches, for A/B runs)
 #ifndef PIEHIP_FUSE_TENSOR
 #define PIEHIP_FUSE_TENSOR 1
 #endif
-bool launch_ntt16_tensor(const NttPlan &pl, bool folded, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st);
-inline bool ntt16_applies(const NttPlan &pl, bool folded)
-{
-    return !pl.force_generic && pl.twp && (folded ? (pl.twk16_fold && (pl.logN == 14 || pl.logN == 15)) : (pl.twk16 && pl.logN == 13));
-}
-bool launch_ntt_fast(const u64 *twp, const u64 *twc, const DevConsts *dc, u32 N, u32 logN, u32 s0, u64 *data, u32 nlimbs, u32 mod_base,
-                     u32 mod_count, bool inverse, bool sigma, u32 num_cus, hipStream_t st, const u64 *lift_src = nullptr,
-                     u32 lift_L = 0, u32 sigma_split = 0, const NttExtra *ex = nullptr);
-// true when launch_ntt(.., folded) / launch_ntt(..) for this plan goes to the register-blocked kernel and honours NttExtra
-bool ntt_supports_extra(const NttPlan &pl, bool folded);
-// forward transform of the BV digits with the digit lift fused into the load (no digits kernel):
-// d2[nb][L][N] COEFFICIENT -> dig[nb][L(i)][L(j)][N] EVALUATION.  Returns false if the register-blocked
-// kernel does not cover this ring dimension as one slice (callers then use launch_digits + launch_ntt).
-// folded_layout: write the lane order of the folded configuration (two slices per limb), matching arrays
-// produced by launch_ntt(.., folded = true)
-bool launch_ntt_digits(const NttPlan &pl, const u64 *d2, u64 *dig, u32 nb, u32 L, bool sigma, bool folded_layout,
-                       hipStream_t st);
-void ntt_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map);  // s0 = ~0u: identity
-// sigma: keep the EVALUATION side in the register-blocked kernel's lane order (internal arrays only; ignored,
-// i.e. standard order, when that kernel does not apply -- ntt_sigma_inverse_map is then the identity)
-// folded: the outermost stage is NOT done here (the caller's neighbouring kernels apply it, kernels_pie.hip
-// "Outer-stage folding"); the limb is transformed as two independent half-size slices.  Requires pl.twc_fold.
-void launch_ntt(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, hipStream_t st,
-                bool sigma = false, bool folded = false, const NttExtra *ex = nullptr);
+void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st);
+// pl.digit_lift_lane / digit_lift_std: forward transform of the BV digits with the digit lift in the 32-coefficient kernel's load
+// phase (no digits kernel): d2[nb][L][N] COEFFICIENT -> dig[nb][L(i)][L(j)][N] EVALUATION
+void launch_ntt_digits(const NttPlan &pl, const u64 *d2, u64 *dig, u32 nb, u32 L, bool sigma, hipStream_t st);
 
 // Stage A: acc[b][K][2][L][N] = sum_j idx[h][j] (.) db[h][beta][j] + minus    (BatchedFHEHIPPIE.cpp:101-116)
 // small_moduli: every RNS modulus is < 2^60 (enables the v_mad_u64_u32 column-accumulator kernel)
@@ -139,31 +155,28 @@ void launch_stage_a_batch(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E
                           u64 *acc, hipStream_t st, bool small_moduli, u32 bstride = 0, u32 h0 = 0, u32 hn = 0,
                           const StageAXOut *xo = nullptr);
 
-// (per-host-thread switch, set from the context before its launches: all Q and P moduli lie in (2^59, 2^60), which lets
-// the base-conversion and key-switch kernels use the carry-free v_mad_u64_u32 column accumulators and one-word Barrett)
-void set_small_moduli(bool v);
-
 // Base conversions, COEFFICIENT format.  Polynomial (o, c), o < n_outer, c < 2,
 // is read at in + o*in_stride_outer + c*in_stride_inner ([L][N] limbs) and written to
 // out + ((o*out_polys + out_slot + c)*M)*N ([M][N] limbs).
 // skip_q: leave the Q limbs of the output alone (they already hold the operand's EVALUATION form, see NttExtra)
+// small_moduli (here and below): NttPlan::small_moduli of the context -- selects the v_mad_u64_u32 / one-word Barrett variants
 void launch_expand_q_to_qp(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t in_stride_outer,
                            size_t in_stride_inner, u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st,
-                           bool fold = false, bool skip_q = false);
+                           bool small_moduli, bool fold = false, bool skip_q = false);
 void launch_scale_pq_expand(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t in_stride_outer,
                             size_t in_stride_inner, u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st,
-                            bool fold = false);
+                            bool small_moduli, bool fold = false);
 // both conversions of a ciphertext multiplication in one launch: X (polynomials at x + o*sx + c*si) centred-lifted into slots 0, 1
 // of out[n_outer][4][M][N], Y (at y + o*sy + c*si) scaled by P/Q into slots 2, 3
 void launch_expand_both(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, const u64 *y, size_t sy, size_t si, u32 n_outer,
-                        u64 *out, hipStream_t st, bool fold = false, bool skip_q = false);
+                        u64 *out, hipStream_t st, bool small_moduli, bool fold = false, bool skip_q = false);
 // e[nb][4][M][N] (a0 a1 b0 b1, EVALUATION) -> d[nb][3][M][N]
-void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 nb, hipStream_t st);
+void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 nb, hipStream_t st, bool small_moduli);
 // d[nb][3][M][N] (COEFFICIENT) -> components 0,1 to out01 + bin*stride01 + c*L*N, component 2 to out2 + bin*stride2
 // fold: the outermost NTT stage of the neighbouring transforms is applied here (see kernels_pie.hip, "Outer-stage
 // folding"); fold_comp2: component 2 also feeds a forward transform directly (3-component output)
 void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb, u64 *out01, size_t stride01, u64 *out2,
-                        size_t stride2, hipStream_t st, bool fold = false, bool fold_comp2 = false);
+                        size_t stride2, hipStream_t st, bool small_moduli, bool fold = false, bool fold_comp2 = false);
 // BV digits: d2c at d2 + bin*stride2 ([L][N], COEFFICIENT) -> dig[nb][L(i)][L(j)][N] (centred lift of residue i into q_j)
 void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stride2, u32 nb, u64 *dig, hipStream_t st,
                    bool fold = false);
@@ -174,7 +187,7 @@ void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stri
 // sigma_T != 0: out_map is the lane order of a transform with sigma_T threads per slice and sigma_kp coefficient pairs per thread
 // (16: kernels_ntt_fast.hip, 8: ntt16_kernel.h); stores then go through an LDS tile
 void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t stride01, const u64 *dig, const u64 *key,
-                      const u64 *mask, u64 *out, u32 nb, hipStream_t st, const u32 *out_map = nullptr, size_t key_stride = 0,
+                      const u64 *mask, u64 *out, u32 nb, hipStream_t st, bool small_moduli, const u32 *out_map = nullptr, size_t key_stride = 0,
                       u32 key_group = 1, u32 sigma_T = 0, u32 sigma_kp = 16, u32 mask_div = 1);
 // rotation-based PIE (FHEHIPPIE.cpp:61-77), see kernels_pie.hip
 void launch_bcast_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t xs, u32 group, const u64 *pt, size_t ps_outer,

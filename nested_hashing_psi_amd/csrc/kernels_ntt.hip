@@ -12,6 +12,9 @@
 // streaming pass over global memory and the rest as two 16384-point LDS transforms.
 #include "kernels.hpp"
 
+#include <algorithm>
+#include <cassert>
+
 namespace piehip {
 
 static const u32 NTT_LDS_MAX_LOG = 14;  // 2^14 coefficients * 8 B = 128 KiB
@@ -134,39 +137,58 @@ __global__ void __launch_bounds__(256) ntt_global_stage(NttArgs a, u32 mstage, u
 
 static PerDeviceOnce g_attr_set[2];
 
-u32 ntt_fast_s0(u32 logN)
+// The one place that knows which kernel a call takes
+NttRoute ntt_route(const NttPlan &pl, bool inverse, bool sigma, bool folded)
 {
-    const u32 s0 = logN > NTT_LDS_MAX_LOG ? logN - NTT_LDS_MAX_LOG : 0;
-    return (logN - s0 >= 12 && logN - s0 <= 14) ? s0 : ~0u;
+    assert((!sigma || pl.lane_order) && (!folded || pl.fold));
+    const u32 s0 = pl.logN > NTT_LDS_MAX_LOG ? pl.logN - NTT_LDS_MAX_LOG : 0;  // slices that fit the LDS; the stages above run in global memory
+    if (!pl.lane_order) return {NttKernel::radix2, s0, s0};
+    // the 16-coefficient kernel: the calls of its own slicing whose EVALUATION side is in lane order, and every inverse among them
+    if (pl.lane_kernel == NttKernel::blocked16 && folded == pl.fold && (inverse || sigma)) return {NttKernel::blocked16, folded ? 1u : 0u, 0};
+    if (folded) return {NttKernel::blocked32, 1, 0};
+    return {NttKernel::blocked32, s0, s0};
 }
 
-bool launch_ntt_digits(const NttPlan &pl, const u64 *d2, u64 *dig, u32 nb, u32 L, bool sigma, bool folded_layout, hipStream_t st)
+void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli)
 {
-    if (pl.force_generic || !pl.twp || !pl.twc || ntt_fast_s0(pl.logN) != 0) return false;
-    if (sigma && ntt16_applies(pl, folded_layout)) return false;  // the lane order is the 16-coefficient kernel's: digits kernel + its transform
-    return launch_ntt_fast(pl.twp, pl.twc, pl.dc, pl.N, pl.logN, 0, dig, nb * L * L, 0, L, false, sigma, pl.transform_cus(), st, d2, L,
-                           (sigma && folded_layout) ? 1u : 0u);
+    pl.lane_order = lazy_ok && pl.logN >= 12;
+    pl.small_moduli = small_moduli;
+    if (!pl.lane_order) return;
+    const bool k16 = pl.logN >= 13 && pl.logN <= 15;
+    pl.lane_kernel = k16 ? NttKernel::blocked16 : NttKernel::blocked32;
+    pl.fold = pl.logN == 14 || pl.logN == 15;
+    pl.lane_logn = pl.logN - ntt_route(pl, true, true, pl.fold).s0;
+    pl.lane_T = (1u << pl.lane_logn) / (k16 ? 16 : 32);
+    pl.lane_kp = k16 ? 8 : 16;
+    pl.xq_reuse = ntt_route(pl, true, false, pl.fold).extra();
+    pl.fused_tensor = PIEHIP_FUSE_TENSOR && k16 && small_moduli;
+    pl.digits_with_d01 = k16 && small_moduli;  // equal-width primes only: the kernel's lift is a conditional subtraction
+    pl.x_direct = pl.xq_reuse && k16 && small_moduli;
+    const NttRoute std_fwd = ntt_route(pl, false, false, false);  // the digit lift is in the 32-coefficient kernel, one slice per limb
+    pl.digit_lift_std = std_fwd.kernel == NttKernel::blocked32 && std_fwd.s0 == 0;
+    pl.digit_lift_lane = pl.digit_lift_std && !k16;  // a 16-coefficient lane order: digits kernel + transform (or digits_with_d01)
 }
 
-bool ntt_supports_extra(const NttPlan &pl, bool folded)
+void launch_ntt_digits(const NttPlan &pl, const u64 *d2, u64 *dig, u32 nb, u32 L, bool sigma, hipStream_t st)
 {
-    if (pl.force_generic || !pl.twp) return false;
-    if (ntt16_applies(pl, folded)) return true;
-    if (folded) return pl.twc_fold != nullptr;
-    return pl.twc != nullptr && ntt_fast_s0(pl.logN) == 0;
+    assert(sigma ? pl.digit_lift_lane : pl.digit_lift_std);
+    launch_ntt_fast(pl, pl.twc, 0, dig, nb * L * L, 0, L, false, sigma, st, d2, L);
 }
 
 void launch_ntt(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, hipStream_t st, bool sigma,
                 bool folded, const NttExtra *ex)
 {
     if (!nlimbs) return;
-    if (ntt16_applies(pl, folded) && launch_ntt16(pl, folded, data, nlimbs, mod_base, mod_count, inverse, sigma, st, ex)) return;
+    const NttRoute r = ntt_route(pl, inverse, sigma, folded);
+    if (r.kernel == NttKernel::blocked16) {
+        launch_ntt16(pl, data, nlimbs, mod_base, mod_count, inverse, sigma, st, ex);
+        return;
+    }
     if (folded) {  // two half-size slices per limb, outer stage done by the neighbouring kernels
         NttExtra exf;
         if (ex) exf = *ex;
         exf.folded = true;
-        (void)launch_ntt_fast(pl.twp, pl.twc_fold, pl.dc, pl.N, pl.logN, 1, data, nlimbs, mod_base, mod_count, inverse, sigma,
-                              pl.transform_cus(), st, nullptr, 0, 0, &exf);
+        launch_ntt_fast(pl, pl.twc_fold, 1, data, nlimbs, mod_base, mod_count, inverse, sigma, st, nullptr, 0, &exf);
         return;
     }
     NttArgs a;
@@ -175,36 +197,29 @@ void launch_ntt(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_
     a.dc = pl.dc;
     a.N = pl.N;
     a.logN = pl.logN;
-    a.s0 = pl.logN > NTT_LDS_MAX_LOG ? pl.logN - NTT_LDS_MAX_LOG : 0;
+    a.s0 = r.s0;
     a.mod_base = mod_base;
     a.mod_count = mod_count;
     const u32 nl = pl.N >> a.s0;
     const size_t lds = (size_t)nl * sizeof(u64);
-    u32 threads = nl / 2;
-    if (threads > 1024) threads = 1024;
-    if (threads < 64) threads = 64;
-    if (g_attr_set[inverse ? 1 : 0].first_on_current_device()) {
-        // a workgroup may use up to 160 KiB of LDS on gfx950; raise the dynamic-LDS cap once
-        if (inverse)
-            (void)hipFuncSetAttribute((const void *)ntt_lds_generic<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (1 << NTT_LDS_MAX_LOG) * 8);
-        else
-            (void)hipFuncSetAttribute((const void *)ntt_lds_generic<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (1 << NTT_LDS_MAX_LOG) * 8);
-    }
+    const u32 threads = std::min(std::max(nl / 2, 64u), 1024u);
+    const bool radix2 = r.kernel == NttKernel::radix2;
+    // a workgroup may use up to 160 KiB of LDS on gfx950; raise the dynamic-LDS cap once
+    if (radix2 && g_attr_set[inverse ? 1 : 0].first_on_current_device())
+        (void)hipFuncSetAttribute(inverse ? (const void *)ntt_lds_generic<true> : (const void *)ntt_lds_generic<false>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (1 << NTT_LDS_MAX_LOG) * 8);
     const dim3 ggrid((pl.N / 2 + 255) / 256, nlimbs);
-    const bool fast_ok = !pl.force_generic && pl.twp && pl.twc && pl.logN - a.s0 >= 12;
     if (!inverse) {
-        for (u32 ms = 1; ms < (1u << a.s0); ms <<= 1)
+        for (u32 ms = 1; ms < (1u << r.global_stages); ms <<= 1)
             hipLaunchKernelGGL(ntt_global_stage<false>, ggrid, dim3(256), 0, st, a, ms, 0u);
-        if (!(fast_ok && launch_ntt_fast(pl.twp, pl.twc, pl.dc, pl.N, pl.logN, a.s0, data, nlimbs, mod_base, mod_count, false, sigma, pl.transform_cus(), st, nullptr, 0, 0, ex)))
-            hipLaunchKernelGGL(ntt_lds_generic<false>, dim3(nlimbs << a.s0), dim3(threads), lds, st, a);
-    } else {
-        if (!(fast_ok && launch_ntt_fast(pl.twp, pl.twc, pl.dc, pl.N, pl.logN, a.s0, data, nlimbs, mod_base, mod_count, true, sigma, pl.transform_cus(), st, nullptr, 0, 0, ex)))
-            hipLaunchKernelGGL(ntt_lds_generic<true>, dim3(nlimbs << a.s0), dim3(threads), lds, st, a);
-        for (u32 ms = (1u << a.s0) >> 1; ms >= 1; ms >>= 1)
-            hipLaunchKernelGGL(ntt_global_stage<true>, ggrid, dim3(256), 0, st, a, ms, ms == 1 ? 1u : 0u);
+        if (radix2) hipLaunchKernelGGL(ntt_lds_generic<false>, dim3(nlimbs << a.s0), dim3(threads), lds, st, a);
+    } else if (radix2) {
+        hipLaunchKernelGGL(ntt_lds_generic<true>, dim3(nlimbs << a.s0), dim3(threads), lds, st, a);
     }
+    if (!radix2) launch_ntt_fast(pl, pl.twc, r.s0, data, nlimbs, mod_base, mod_count, inverse, sigma, st, nullptr, 0, ex);
+    if (inverse)
+        for (u32 ms = (1u << r.global_stages) >> 1; ms >= 1; ms >>= 1)
+            hipLaunchKernelGGL(ntt_global_stage<true>, ggrid, dim3(256), 0, st, a, ms, ms == 1 ? 1u : 0u);
 }
 
 }  // namespace piehip

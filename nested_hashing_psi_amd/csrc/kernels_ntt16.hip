@@ -1,6 +1,8 @@
 // kernels_ntt16.hip -- launch side of the 16-coefficients-per-thread NTT (ntt16_kernel.h) for slices of 2^13 coefficients:
 // ring 2^13 as one slice per limb, ring 2^14 as two slices with the outermost stage folded into the neighbouring kernels.
 // Replaces DCRTPoly::SetFormat under EvalMult(ct, ct) (reference BatchedFHEHIPPIE.cpp:123).
+#include <cassert>
+
 #include "kernels.hpp"
 #include "ntt16_kernel.h"
 
@@ -50,18 +52,16 @@ static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 nu
         hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, false>), dim3(grid), dim3(G::T), lds, st, a);
 }
 
-bool launch_ntt16(const NttPlan &pl, bool folded, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, bool sigma,
-                  hipStream_t st, const NttExtra *ex, const Ntt16Digits *dg)
+void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, bool sigma, hipStream_t st,
+                  const NttExtra *ex, const Ntt16Digits *dg)
 {
-    const u64 *twk = folded ? pl.twk16_fold : pl.twk16;
+    const bool folded = pl.fold;
     const u32 s0 = folded ? 1u : 0u;
-    const u32 slice_log = pl.logN - s0;
-    if (pl.force_generic || !twk || !pl.twp || (slice_log != 13 && slice_log != 14)) return false;
-    if (!inverse && !sigma) return false;  // standard-order output is the 32-coefficient kernel's
+    assert(ntt_route(pl, inverse, sigma, folded).kernel == NttKernel::blocked16 && (!dg || pl.digits_with_d01));
     ntt16::Args a;
     a.data = data;
     a.twp = reinterpret_cast<const ntt16::u64x2 *>(pl.twp);
-    a.twk = reinterpret_cast<const ntt16::u64x2 *>(twk);
+    a.twk = reinterpret_cast<const ntt16::u64x2 *>(pl.twk16);
     a.dc = pl.dc;
     a.N = pl.N;
     a.s0 = s0;
@@ -94,24 +94,21 @@ bool launch_ntt16(const NttPlan &pl, bool folded, u64 *data, u32 nlimbs, u32 mod
         a.lift_L = dg->L;
     }
     const bool lift = a.lift_first != ~0u;
-    if (slice_log == 14)
+    if (pl.lane_logn == 14)
         launch_ntt16_t<14>(a, inverse, lift, pl.transform_cus(), st);
     else
         launch_ntt16_t<13>(a, inverse, lift, pl.transform_cus(), st);
-    return true;
 }
 
-bool launch_ntt16_tensor(const NttPlan &pl, bool folded, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st)
+void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st)
 {
-#if PIEHIP_FUSE_TENSOR
-    const u64 *twk = folded ? pl.twk16_fold : pl.twk16;
+    assert(pl.fused_tensor);
+    const bool folded = pl.fold;
     const u32 s0 = folded ? 1u : 0u;
-    const u32 slice_log = pl.logN - s0;
-    if (pl.force_generic || !twk || !pl.twp || (slice_log != 13 && slice_log != 14)) return false;
     ntt16::Args a = {};
     a.data = d;
     a.twp = reinterpret_cast<const ntt16::u64x2 *>(pl.twp);
-    a.twk = reinterpret_cast<const ntt16::u64x2 *>(twk);
+    a.twk = reinterpret_cast<const ntt16::u64x2 *>(pl.twk16);
     a.dc = pl.dc;
     a.N = pl.N;
     a.s0 = s0;
@@ -123,14 +120,10 @@ bool launch_ntt16_tensor(const NttPlan &pl, bool folded, const u64 *e, u64 *d, u
     a.lift_first = ~0u;
     a.lift_L = 1;
     a.tsrc = e;
-    if (slice_log == 14)
+    if (pl.lane_logn == 14)
         launch_ntt16_t<14>(a, true, false, pl.transform_cus(), st, true);
     else
         launch_ntt16_t<13>(a, true, false, pl.transform_cus(), st, true);
-    return true;
-#else
-    return false;
-#endif
 }
 
 }  // namespace piehip

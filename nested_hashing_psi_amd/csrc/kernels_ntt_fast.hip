@@ -26,6 +26,7 @@
 //
 // The ALU, not HBM, bounds this kernel: a 60-bit Shoup butterfly is ~10 v_mad_u64_u32 plus ~10 32-bit
 // adds/selects, 7 butterflies per 16 bytes moved (DESIGN.md "NTT roofline").
+#include <cassert>
 #include <vector>
 
 #include "kernels.hpp"
@@ -481,7 +482,6 @@ static void launch_one(const NttFastArgs &a, u32 max_groups, hipStream_t st)
     hipLaunchKernelGGL((ntt_fast_kernel<LOGN, INV, SIGMA, LAZY>), dim3(grid), dim3(n / 32), lds, st, a.data, reinterpret_cast<const u64x2 *>(a.twp), reinterpret_cast<const u64x2 *>(a.twc), a.dc, a);
 }
 
-// returns false if this slice size has no register-blocked kernel
 // Host side: pass-C twiddles of one (modulus, direction) in kernel order [blk][stage][j][tau].
 // nat[k] = {w, w_shoup} pairs in natural (bit-reversed exponent) order, N pairs.
 void build_twc_table(const u64 *nat, u32 logN, u32 s0, std::vector<u64> &out)
@@ -522,25 +522,24 @@ void ntt_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map)
     }
 }
 
-bool launch_ntt_fast(const u64 *twp, const u64 *twc, const DevConsts *dc, u32 N, u32 logN, u32 s0, u64 *data, u32 nlimbs, u32 mod_base,
-                     u32 mod_count, bool inverse, bool sigma, u32 num_cus, hipStream_t st, const u64 *lift_src, u32 lift_L,
-                     u32 sigma_split, const NttExtra *ex)
+void launch_ntt_fast(const NttPlan &pl, const u64 *twc, u32 s0, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse,
+                     bool sigma, hipStream_t st, const u64 *lift_src, u32 lift_L, const NttExtra *ex)
 {
-    const u32 logn = logN - s0;
-    if (logn < 12 || logn > 14) return false;
+    const u32 logn = pl.logN - s0;
+    assert(twc && logn >= 12 && logn <= 14);
     NttFastArgs a;
     a.data = data;
-    a.twp = twp;
+    a.twp = pl.twp;
     a.twc = twc;
-    a.dc = dc;
-    a.N = N;
-    a.logN = logN;
+    a.dc = pl.dc;
+    a.N = pl.N;
+    a.logN = pl.logN;
     a.s0 = s0;
     a.nitems = nlimbs << s0;
     a.sigma = sigma ? 1u : 0u;
     a.lift_src = lift_src;
     a.lift_L = (lift_src && !inverse && s0 == 0) ? lift_L : 0;
-    a.sigma_split = (!inverse && s0 == 0) ? sigma_split : 0;
+    a.sigma_split = 0;  // (the lifted digits in the lane order of two folded slices: those contexts' lane order is the other kernel's now)
     a.mod_base = mod_base;
     a.mod_count = mod_count;
     a.copy_out = (ex && inverse && !sigma) ? ex->copy_out : nullptr;
@@ -553,7 +552,7 @@ bool launch_ntt_fast(const u64 *twp, const u64 *twc, const DevConsts *dc, u32 N,
     const bool lazy = ex && ex->lazy_out && !inverse && sigma && !a.lift_L;
     // resident workgroups per CU by LDS: 136 KiB -> 1, 68 KiB -> 2, 34 KiB -> 4
     const u32 per_cu = logn == 14 ? 1 : (logn == 13 ? 2 : 4);
-    const u32 maxg = num_cus * per_cu;
+    const u32 maxg = pl.transform_cus() * per_cu;
 #define NTT_DISPATCH(LG)                                                          \
     do {                                                                          \
         if (inverse) {                                                            \
@@ -569,7 +568,6 @@ bool launch_ntt_fast(const u64 *twp, const u64 *twc, const DevConsts *dc, u32 N,
     else if (logn == 13) NTT_DISPATCH(13);
     else NTT_DISPATCH(12);
 #undef NTT_DISPATCH
-    return true;
 }
 
 }  // namespace piehip

@@ -15,11 +15,6 @@ namespace piehip {
 
 static const u32 TPB = 256;
 
-// set by the calling context right before its launches (all Q, P moduli in (2^59, 2^60)); per host thread, so
-// contexts with different moduli can be driven from different threads
-static thread_local bool g_small_moduli = false;
-void set_small_moduli(bool v) { g_small_moduli = v; }
-
 // ---------------------------------------------------------------------------------------------
 // Stage A (rows A3+A4): acc[beta][h][c][l][n] = sum_j idx[h][j][c][l][n] * db[h][beta][j][l][n] + minus[c][l][n]
 //
@@ -1015,15 +1010,15 @@ __global__ void __launch_bounds__(TPB) expand_both_kernel(const DevConsts *__res
         expand_body<false, FOLD, L, MAD, SKIPQ>(dc, N, x, sx, si, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
 void launch_expand_both(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, const u64 *y, size_t sy, size_t si, u32 n_outer,
-                        u64 *out, hipStream_t st, bool fold, bool skip_q)
+                        u64 *out, hipStream_t st, bool small_moduli, bool fold, bool skip_q)
 {
     dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, n_outer * 4);
 #define EB(F_, L_, M_, Q_) hipLaunchKernelGGL((expand_both_kernel<F_, L_, M_, Q_>), grid, dim3(TPB), 0, st, dc, N, x, sx, y, sy, si, out, n_outer)
 #define EBL(L_)                                                                          \
     case L_:                                                                             \
-        if (fold && g_small_moduli) { if (skip_q) EB(true, L_, true, true); else EB(true, L_, true, false); }      \
+        if (fold && small_moduli) { if (skip_q) EB(true, L_, true, true); else EB(true, L_, true, false); }      \
         else if (fold) { if (skip_q) EB(true, L_, false, true); else EB(true, L_, false, false); }                 \
-        else if (g_small_moduli) { if (skip_q) EB(false, L_, true, true); else EB(false, L_, true, false); }       \
+        else if (small_moduli) { if (skip_q) EB(false, L_, true, true); else EB(false, L_, true, false); }       \
         else { if (skip_q) EB(false, L_, false, true); else EB(false, L_, false, false); }                         \
         break;
     switch (L) { EBL(1) EBL(2) EBL(3) EBL(4) EBL(5) EBL(6) EBL(7) }
@@ -1032,12 +1027,12 @@ void launch_expand_both(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t 
 }
 
 static void launch_expand_common(bool scale, bool fold, const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t so, size_t si,
-                                 u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st, bool skip_q = false)
+                                 u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st, bool small_moduli, bool skip_q = false)
 {
     dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, n_outer * 2);
 #define EX(S_, F_, L_, Q_)                                                                                                    \
     do {                                                                                                                      \
-        if (g_small_moduli)                                                                                                   \
+        if (small_moduli)                                                                                                   \
             hipLaunchKernelGGL((expand_kernel<S_, F_, L_, true, Q_>), grid, dim3(TPB), 0, st, dc, N, in, so, si, out, out_polys, out_slot); \
         else                                                                                                                  \
             hipLaunchKernelGGL((expand_kernel<S_, F_, L_, false, Q_>), grid, dim3(TPB), 0, st, dc, N, in, so, si, out, out_polys, out_slot); \
@@ -1057,14 +1052,14 @@ static void launch_expand_common(bool scale, bool fold, const DevConsts *dc, u32
 #undef EX
 }
 void launch_expand_q_to_qp(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t so, size_t si, u32 n_outer, u64 *out,
-                           u32 out_polys, u32 out_slot, hipStream_t st, bool fold, bool skip_q)
+                           u32 out_polys, u32 out_slot, hipStream_t st, bool small_moduli, bool fold, bool skip_q)
 {
-    launch_expand_common(false, fold, dc, N, L, in, so, si, n_outer, out, out_polys, out_slot, st, skip_q);
+    launch_expand_common(false, fold, dc, N, L, in, so, si, n_outer, out, out_polys, out_slot, st, small_moduli, skip_q);
 }
 void launch_scale_pq_expand(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t so, size_t si, u32 n_outer, u64 *out,
-                            u32 out_polys, u32 out_slot, hipStream_t st, bool fold)
+                            u32 out_polys, u32 out_slot, hipStream_t st, bool small_moduli, bool fold)
 {
-    launch_expand_common(true, fold, dc, N, L, in, so, si, n_outer, out, out_polys, out_slot, st);
+    launch_expand_common(true, fold, dc, N, L, in, so, si, n_outer, out, out_polys, out_slot, st, small_moduli);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1124,10 +1119,10 @@ __global__ void __launch_bounds__(TPB) tensor_kernel(const DevConsts *dc, u32 N,
     *reinterpret_cast<u64x2 *>(pd + MN) = r1;
     *reinterpret_cast<u64x2 *>(pd + 2 * MN) = r2;
 }
-void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 nb, hipStream_t st)
+void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 nb, hipStream_t st, bool small_moduli)
 {
     dim3 grid((N / 2 + TPB - 1) / TPB, M, nb);   // (N is a power of two >= 8)
-    if (g_small_moduli)
+    if (small_moduli)
         hipLaunchKernelGGL(tensor_kernel<true>, grid, dim3(TPB), 0, st, dc, N, M, e, d);
     else
         hipLaunchKernelGGL(tensor_kernel<false>, grid, dim3(TPB), 0, st, dc, N, M, e, d);
@@ -1249,18 +1244,18 @@ __global__ void __launch_bounds__(TPB) scale_round_kernel(const DevConsts *__res
     }
 }
 void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb, u64 *out01, size_t stride01, u64 *out2,
-                        size_t stride2, hipStream_t st, bool fold, bool fold_comp2)
+                        size_t stride2, hipStream_t st, bool small_moduli, bool fold, bool fold_comp2)
 {
     dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, 3, nb);
 #define SRL(L_)                                                                                                              \
     case L_:                                                                                                                 \
-        if (fold && g_small_moduli)                                                                                          \
+        if (fold && small_moduli)                                                                                          \
             hipLaunchKernelGGL((scale_round_kernel<true, L_, true>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, \
                                fold_comp2 ? 1u : 0u);                                                                        \
         else if (fold)                                                                                                       \
             hipLaunchKernelGGL((scale_round_kernel<true, L_, false>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, \
                                fold_comp2 ? 1u : 0u);                                                                        \
-        else if (g_small_moduli)                                                                                             \
+        else if (small_moduli)                                                                                             \
             hipLaunchKernelGGL((scale_round_kernel<false, L_, true>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, 0u); \
         else                                                                                                                 \
             hipLaunchKernelGGL((scale_round_kernel<false, L_, false>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, 0u); \
@@ -1456,8 +1451,8 @@ __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restr
     }
 }
 void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t stride01, const u64 *dig, const u64 *key,
-                      const u64 *mask, u64 *out, u32 nb, hipStream_t st, const u32 *out_map, size_t key_stride, u32 key_group,
-                      u32 sigma_T, u32 sigma_kp, u32 mask_div)
+                      const u64 *mask, u64 *out, u32 nb, hipStream_t st, bool small_moduli, const u32 *out_map, size_t key_stride,
+                      u32 key_group, u32 sigma_T, u32 sigma_kp, u32 mask_div)
 {
     if (!key_group) key_group = 1;
     if (!mask_div) mask_div = 1;
@@ -1466,7 +1461,7 @@ void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t 
                       (N / 2) % TPB == 0;
     const int kp = tile ? (int)sigma_kp : 0;
     // two rows per thread where at least two rows share a key (the column-accumulator path)
-    const bool two = g_small_moduli && nb >= 2 * key_group;
+    const bool two = small_moduli && nb >= 2 * key_group;
     const u32 zrows = two ? ((nb + 2 * key_group - 1) / (2 * key_group)) * key_group : nb;
     dim3 grid((N / 2 + TPB - 1) / TPB, L, zrows);
 #define RM(M_, K_, R_)                                                                                                              \
@@ -1474,7 +1469,7 @@ void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t 
                        key_stride, key_group, sigma_T, mask_div, nb)
     if (two) {
         if (kp == 16) RM(true, 16, 2); else if (kp == 8) RM(true, 8, 2); else RM(true, 0, 2);
-    } else if (g_small_moduli) {
+    } else if (small_moduli) {
         if (kp == 16) RM(true, 16, 1); else if (kp == 8) RM(true, 8, 1); else RM(true, 0, 1);
     } else {
         if (kp == 16) RM(false, 16, 1); else if (kp == 8) RM(false, 8, 1); else RM(false, 0, 1);

@@ -129,6 +129,18 @@ void use_owned_inputs(piehip_ctx *h)
     for (u32 q = 0; q < h->nq; q++) h->query[q].idx = h->query[q].idx_own, h->query[q].minus = h->query[q].minus_own;
 }
 
+// device copy of a table made by piehip_create (src null: room for one); the handle owns it (piehip_destroy frees dev_tables)
+template <class T, class P>
+static hipError_t upload_table(piehip_ctx *h, const T *src, size_t n, P **dst)
+{
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, n * sizeof(T));
+    if (e != hipSuccess) return e;
+    h->dev_tables.push_back(p);
+    *dst = (P *)p;
+    return src ? hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+}
+
 }  // namespace piehip
 
 // =================================================================================================
@@ -185,114 +197,72 @@ int piehip_create(piehip_handle *out, uint32_t N, uint32_t L, uint64_t t, const 
         h->own_stream = true;
     }
     CHK_(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    const u32 M = h->hp.M;
-    CHK_(hipMalloc((void **)&h->d_dc, sizeof(DevConsts)));
-    CHK_(hipMemcpy(h->d_dc, &h->hp.dc, sizeof(DevConsts), hipMemcpyHostToDevice));
-    CHK_(hipMalloc((void **)&h->d_tables, sizeof(u64) * (size_t)(M + 1) * 4 * N));
-    for (u32 a = 0; a <= M; a++) {
-        u64 *base = h->d_tables + (size_t)a * 4 * N;
-        CHK_(hipMemcpy(base, h->hp.tw[a].data(), sizeof(u64) * N, hipMemcpyHostToDevice));
-        CHK_(hipMemcpy(base + N, h->hp.tw_sh[a].data(), sizeof(u64) * N, hipMemcpyHostToDevice));
-        CHK_(hipMemcpy(base + 2 * (size_t)N, h->hp.itw[a].data(), sizeof(u64) * N, hipMemcpyHostToDevice));
-        CHK_(hipMemcpy(base + 3 * (size_t)N, h->hp.itw_sh[a].data(), sizeof(u64) * N, hipMemcpyHostToDevice));
+    const u32 M = h->hp.M, logN = h->hp.logN;
+    NttPlan &pl = h->plan;
+    pl.N = N;
+    pl.logN = logN;
+    {
+        bool lazy_ok = true, small_moduli = true;
+        for (u32 a = 0; a <= M; a++) {
+            if (h->hp.moduli[a] >> 60) lazy_ok = false;                      // lazy residues need 8q < 2^63 (t included)
+            if (a < M && (h->hp.moduli[a] >> 59) != 1) small_moduli = false;  // the mad paths assume 2^59 < q < 2^60 (Q and P)
+        }
+        ntt_plan_decide(pl, lazy_ok, small_moduli);
+        hipDeviceProp_t prop;
+        pl.num_cus = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? (u32)prop.multiProcessorCount : 256u;
     }
+    CHK_(upload_table(h, &h->hp.dc, 1, &h->d_dc));
+    pl.dc = h->d_dc;
     {
         std::vector<u64> pairs((size_t)(M + 1) * 4 * N);
-        for (u32 a = 0; a <= M; a++)
+        u64 *tables = nullptr;  // [(M+1)][4][N]
+        CHK_(upload_table(h, (const u64 *)nullptr, pairs.size(), &tables));
+        pl.tables = tables;
+        for (u32 a = 0; a <= M; a++) {
+            for (const std::vector<u64> *t : {&h->hp.tw[a], &h->hp.tw_sh[a], &h->hp.itw[a], &h->hp.itw_sh[a]}) {
+                CHK_(hipMemcpy(tables, t->data(), sizeof(u64) * N, hipMemcpyHostToDevice));
+                tables += N;
+            }
             for (u32 k = 0; k < N; k++) {
                 u64 *f = &pairs[((size_t)a * 2 + 0) * 2 * N + 2 * (size_t)k];
                 u64 *i = &pairs[((size_t)a * 2 + 1) * 2 * N + 2 * (size_t)k];
-                // the register-blocked kernel uses 63-bit Shoup constants floor(w 2^63 / q) (kernels_ntt_fast.hip)
+                // the register-blocked kernels use 63-bit Shoup constants floor(w 2^63 / q) (kernels_ntt_fast.hip)
                 f[0] = h->hp.tw[a][k];
                 f[1] = h->hp.tw_sh[a][k] >> 1;
                 i[0] = h->hp.itw[a][k];
                 i[1] = h->hp.itw_sh[a][k] >> 1;
             }
-        CHK_(hipMalloc((void **)&h->d_twp, pairs.size() * sizeof(u64)));
-        CHK_(hipMemcpy(h->d_twp, pairs.data(), pairs.size() * sizeof(u64), hipMemcpyHostToDevice));
-        u32 s0 = ntt_fast_s0(h->hp.logN);
-        for (u32 a = 0; a <= M; a++)
-            if (h->hp.moduli[a] >> 60) s0 = ~0u;  // lazy residues need 8q < 2^63
-        if (s0 != ~0u) {
+        }
+        CHK_(upload_table(h, pairs.data(), pairs.size(), &pl.twp));
+        // the kernel-ordered twiddles of every (modulus, direction), one after the other
+        auto kernel_order = [&](bool k16, u32 s0, const u64 **dst) {
             std::vector<u64> all, one;
             for (u32 a = 0; a <= M; a++)
                 for (u32 dir = 0; dir < 2; dir++) {
-                    build_twc_table(&pairs[((size_t)a * 2 + dir) * 2 * N], h->hp.logN, s0, one);
+                    const u64 *nat = &pairs[((size_t)a * 2 + dir) * 2 * N];
+                    if (k16)
+                        build_twk16_table(nat, s0, logN - s0, one);
+                    else
+                        build_twc_table(nat, logN, s0, one);
                     all.insert(all.end(), one.begin(), one.end());
                 }
-            CHK_(hipMalloc((void **)&h->d_twc, all.size() * sizeof(u64)));
-            CHK_(hipMemcpy(h->d_twc, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice));
-            if (h->hp.logN >= 14 && h->hp.logN <= 15) {  // folded configuration: slices of N/2
-                all.clear();
-                for (u32 a = 0; a <= M; a++)
-                    for (u32 dir = 0; dir < 2; dir++) {
-                        build_twc_table(&pairs[((size_t)a * 2 + dir) * 2 * N], h->hp.logN, 1, one);
-                        all.insert(all.end(), one.begin(), one.end());
-                    }
-                CHK_(hipMalloc((void **)&h->d_twc_fold, all.size() * sizeof(u64)));
-                CHK_(hipMemcpy(h->d_twc_fold, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice));
-                h->fold_on = true;
-            }
-            if (h->hp.logN >= 13 && h->hp.logN <= 15) {  // the 16-coefficients-per-thread kernel: slices of 2^13 (rings 2^13, 2^14) or 2^14 (ring 2^15)
-                const u32 s16 = h->hp.logN == 13 ? 0u : 1u;
-                all.clear();
-                for (u32 a = 0; a <= M; a++)
-                    for (u32 dir = 0; dir < 2; dir++) {
-                        build_twk16_table(&pairs[((size_t)a * 2 + dir) * 2 * N], s16, h->hp.logN - s16, one);
-                        all.insert(all.end(), one.begin(), one.end());
-                    }
-                CHK_(hipMalloc((void **)&h->d_twk16, all.size() * sizeof(u64)));
-                CHK_(hipMemcpy(h->d_twk16, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice));
-            }
-        }
+            return upload_table(h, all.data(), all.size(), dst);
+        };
+        if (pl.lane_order) CHK_(kernel_order(false, ntt_route(pl, false, false, false).s0, &pl.twc));
+        if (pl.fold) CHK_(kernel_order(false, 1, &pl.twc_fold));
+        if (pl.lane_kernel == NttKernel::blocked16) CHK_(kernel_order(true, logN - pl.lane_logn, &pl.twk16));
     }
     {
-        std::vector<u32> inv(N, 0xFFFFFFFFu);
+        std::vector<u32> inv(N, 0xFFFFFFFFu), smap;
         for (u32 s = 0; s < N; s++) inv[h->hp.slot_pos[s]] = s;
-        CHK_(hipMalloc((void **)&h->d_inv_pos, sizeof(u32) * N));
-        CHK_(hipMemcpy(h->d_inv_pos, inv.data(), sizeof(u32) * N, hipMemcpyHostToDevice));
+        CHK_(upload_table(h, inv.data(), inv.size(), &h->d_inv_pos));
+        if (pl.lane_kernel == NttKernel::blocked16)
+            ntt16_sigma_inverse_map(logN, logN - pl.lane_logn, smap);
+        else
+            ntt_sigma_inverse_map(logN, pl.lane_order ? logN - pl.lane_logn : ~0u, smap);
+        CHK_(upload_table(h, smap.data(), smap.size(), &h->d_sigma_inv));
     }
 #undef CHK_
-    h->plan.tables = h->d_tables;
-    h->plan.twp = h->d_twp;
-    h->plan.logN = h->hp.logN;
-    h->plan.force_generic = false;
-    if (h->hp.logN == 13) h->plan.twk16 = h->d_twk16;
-    if (h->hp.logN == 14 || h->hp.logN == 15) h->plan.twk16_fold = h->d_twk16;
-    const bool use16 = ntt16_applies(h->plan, h->fold_on);  // which kernel defines this context's lane order
-    {
-        std::vector<u32> smap;
-        if (use16)
-            ntt16_sigma_inverse_map(h->hp.logN, h->fold_on ? 1u : 0u, smap);
-        else
-            ntt_sigma_inverse_map(h->hp.logN, h->d_twc ? (h->fold_on ? 1u : ntt_fast_s0(h->hp.logN)) : ~0u, smap);
-        if (hipMalloc((void **)&h->d_sigma_inv, sizeof(u32) * N) != hipSuccess ||
-            hipMemcpy(h->d_sigma_inv, smap.data(), sizeof(u32) * N, hipMemcpyHostToDevice) != hipSuccess) {
-            piehip_destroy(h);
-            return fail(PIEHIP_EHIP, "sigma map upload failed");
-        }
-        h->sigma_on = h->d_twc != nullptr;
-        if (h->sigma_on) {
-            const u32 s0 = h->fold_on ? 1u : ntt_fast_s0(h->hp.logN);
-            h->sigma_T = use16 ? (N >> s0) / 16 : (N >> s0) / 32;
-            h->sigma_kp = use16 ? 8 : 16;
-        }
-        h->small_moduli = true;
-        for (u32 a = 0; a < M; a++)
-            if ((h->hp.moduli[a] >> 59) != 1) h->small_moduli = false;  // the mad paths assume 2^59 < q < 2^60
-    }
-    h->plan.twp = h->d_twp;
-    h->plan.twc = h->d_twc;
-    h->plan.twc_fold = h->d_twc_fold;
-    h->plan.force_generic = false;
-    {
-        hipDeviceProp_t prop;
-        h->plan.num_cus = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-                              ? (u32)prop.multiProcessorCount : 256u;
-    }
-    h->plan.dc = h->d_dc;
-    h->plan.N = N;
-    h->plan.logN = h->hp.logN;
     *out = h;
     return PIEHIP_OK;
 }
@@ -324,14 +294,7 @@ int piehip_destroy(piehip_handle h)
         dev_free(&s.minus_own);
     }
     free_workspace(h);
-    if (h->d_dc) (void)hipFree(h->d_dc);
-    if (h->d_tables) (void)hipFree(h->d_tables);
-    if (h->d_twp) (void)hipFree(h->d_twp);
-    if (h->d_twc) (void)hipFree(h->d_twc);
-    if (h->d_twc_fold) (void)hipFree(h->d_twc_fold);
-    if (h->d_twk16) (void)hipFree(h->d_twk16);
-    if (h->d_inv_pos) (void)hipFree(h->d_inv_pos);
-    if (h->d_sigma_inv) (void)hipFree(h->d_sigma_inv);
+    for (void *p : h->dev_tables) (void)hipFree(p);
     dev_free(&h->d_evk_sigma);
     dev_free(&h->d_evkq);
     dev_free(&h->d_evkq_sigma);
@@ -397,7 +360,7 @@ static int fill_unloaded_key_slots(piehip_ctx *h)
     for (u32 i = 0; i < h->evkq_n && h->d_evkq && h->d_evk; i++) {
         if (h->evkq_loaded >> i & 1) continue;
         HIPCHK(hipMemcpyAsync(h->d_evkq + i * words, h->d_evk, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
-        if (h->sigma_on && h->d_evkq_sigma)
+        if (h->plan.lane_order && h->d_evkq_sigma)
             HIPCHK(hipMemcpyAsync(h->d_evkq_sigma + i * words, h->d_evk_sigma, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
     }
     return PIEHIP_OK;
@@ -418,7 +381,7 @@ int piehip_load_relin_key(piehip_handle h, const uint64_t *evk)
     // on the handle's stream: NEED() has ordered it behind every run still in flight (a null-stream copy would not be)
     HIPCHK(hipMemcpyAsync(h->d_evk, evk, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->sigma_on) {  // lane-ordered copy for the key-switch MAC
+    if (h->plan.lane_order) {  // lane-ordered copy for the key-switch MAC
         if (!h->d_evk_sigma) {
             int rc = dev_alloc(&h->d_evk_sigma, words);
             if (rc) return rc;
@@ -435,7 +398,7 @@ int piehip_load_relin_key(piehip_handle h, const uint64_t *evk)
 // lane-ordered copy of the mask plaintexts for the fused mask multiply of the last key switch
 static int make_masks_sigma(piehip_ctx *h)
 {
-    if (!h->sigma_on) return PIEHIP_OK;
+    if (!h->plan.lane_order) return PIEHIP_OK;
     if (!h->d_masks_sigma) {  // freed with the run buffers when the shape changes
         int rc = dev_alloc(&h->d_masks_sigma, (size_t)h->b * h->LN());
         if (rc) return rc;
@@ -938,13 +901,13 @@ int piehip_load_relin_key_q(piehip_handle h, uint32_t q, const uint64_t *evk)
         dev_free(&h->d_evkq_sigma);
         h->evkq_n = h->evkq_loaded = 0;
         if ((rc = dev_alloc(&h->d_evkq, words * h->nq))) return rc;
-        if (h->sigma_on && (rc = dev_alloc(&h->d_evkq_sigma, words * h->nq))) return rc;
+        if (h->plan.lane_order && (rc = dev_alloc(&h->d_evkq_sigma, words * h->nq))) return rc;
         h->evkq_n = h->nq;
         // queries without a key of their own use the handle's (piehip_load_relin_key), if it has one
         if ((rc = fill_unloaded_key_slots(h))) return rc;
     }
     HIPCHK(hipMemcpyAsync(h->d_evkq + q * words, evk, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    if (h->sigma_on) launch_permute(h->hp.N, h->d_evkq + q * words, h->d_sigma_inv, h->d_evkq_sigma + q * words, h->hp.L * 2 * h->hp.L, h->stream);
+    if (h->plan.lane_order) launch_permute(h->hp.N, h->d_evkq + q * words, h->d_sigma_inv, h->d_evkq_sigma + q * words, h->hp.L * 2 * h->hp.L, h->stream);
     HIPCHK(hipStreamSynchronize(h->stream));
     h->evkq_loaded |= 1u << q;
     return PIEHIP_OK;

@@ -130,18 +130,11 @@ struct piehip_ctx {
     u64 *pin_res = nullptr;                       // [b][nq][2][L][N]
     size_t pin_idx_words = 0, pin_res_words = 0;
     piehip::DevConsts *d_dc = nullptr;
-    u64 *d_tables = nullptr;  // [(M+1)][4][N]
-    u64 *d_twp = nullptr;     // [(M+1)][2][N][2] interleaved {w, w_shoup}
-    u64 *d_twc = nullptr;     // pass-C kernel-order copy of the same pairs
-    u64 *d_twc_fold = nullptr;  // ... for the folded configuration (two half-size slices per limb)
-    bool fold_on = false;     // outermost NTT stage folded into the coefficient-wise kernels (N >= 2^14)
-    u32 *d_inv_pos = nullptr; // EVALUATION position -> slot
-    u32 *d_sigma_inv = nullptr;  // lane-order position -> standard position (identity for small rings)
-    u32 sigma_T = 0;             // threads per slice of the transform that defines the lane order
-    u32 sigma_kp = 16;           // ... and coefficient pairs per thread (16: kernels_ntt_fast.hip, 8: ntt16_kernel.h)
-    u64 *d_twk16 = nullptr;      // ntt16_kernel.h tables (ring 2^13 as one slice per limb; rings 2^14, 2^15 as two folded slices)
-    bool small_moduli = false;   // all Q and P moduli in (2^59, 2^60): v_mad_u64_u32 column accumulators, one-word Barrett
-    bool sigma_on = false;       // the register-blocked NTT (and hence the lane order) applies to this context
+    // tables of piehip_create, freed through dev_tables: the transform tables live in `plan`, which also says what the context can
+    // do with them (lane order, folding, fusions: DESIGN.md section 5a)
+    std::vector<void *> dev_tables;
+    u32 *d_inv_pos = nullptr;    // EVALUATION position -> slot
+    u32 *d_sigma_inv = nullptr;  // lane-order position -> standard position (identity without a lane order)
     u64 *d_evk_sigma = nullptr, *d_masks_sigma = nullptr;  // lane-ordered copies of key and masks
     u64 *d_hash_tbl = nullptr;   // [k][e][K][b][E] of the last piehip_build_db
     size_t hash_tbl_words = 0;
@@ -279,14 +272,13 @@ int ws_alloc(piehip_ctx *h, MulWs &w, u32 nb);
 void ws_free(MulWs &w);
 
 // ---- schedule pieces (piehip_run.cpp) --------------------------------------------------------------
-// sigma: lane order on the EVALUATION side; fold: outer stage applied by the neighbouring kernels (both only
-// take effect when the context supports them; callers pass the same flags to those neighbours)
+// sigma: lane order on the EVALUATION side; fold: outer stage applied by the neighbouring kernels.  Callers say what they would
+// like; ntt() and enqueue_keyswitch() are where a context without lane order / folding (h->plan) turns that into standard order
 void ntt(piehip_ctx *h, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inv, bool sigma = false, bool fold = false,
          const NttExtra *ex = nullptr);
-bool xq_reuse(const piehip_ctx *h);
-void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u64 *mask, u64 *out, bool sigma = false,
-                       bool fold = false, size_t key_stride = 0, u32 key_group = 1, bool out_is_result = false,
-                       bool digits_ready = false);
+// lane: w.d01, the digits, key and mask are lane-ordered (and folded) where the context has a lane order; out is in standard order
+void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u64 *mask, u64 *out, bool lane = false,
+                       size_t key_stride = 0, u32 key_group = 1, bool out_is_result = false, bool digits_ready = false);
 void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
                  const u64 *mask, u64 *out, bool xq_ready = false, bool out_is_result = false);
 int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out);

@@ -191,7 +191,7 @@ int piehip_fhepie_run(piehip_handle h)
                 launch_rot_prepare(h->d_dc, N, L, prod, h->fp_negmaps, b, false, true, w.d01, w.d2c, nb, h->stream);
             }
             ntt(h, w.d2c, nb * L, 0, L, true);
-            enqueue_keyswitch(h, w, nb, h->fp_negkeys, nullptr, prod, false, false, keyw, b);
+            enqueue_keyswitch(h, w, nb, h->fp_negkeys, nullptr, prod, false, keyw, b);
         } else {
             ProfScope ps(h, PIEHIP_K_MASK, W * nb * 5.0 * L);
             launch_ct_mul_plain(h->d_dc, N, L, prod, h->fp_e0, 0, prod, nb, h->stream);

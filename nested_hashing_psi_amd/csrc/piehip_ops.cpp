@@ -70,7 +70,7 @@ int piehip_eval_mult(piehip_handle h, const uint64_t *x, const uint64_t *y, uint
         ws_free(w);
         return rc;
     }
-    const bool xq = xq_reuse(h);
+    const bool xq = h->plan.xq_reuse;
     NttExtra ex;  // operand layout [nct][x, y][2][L]: x is "operand 0" of every pair
     ex.copy_out = w.eqp;
     ex.copy_K = 2;
@@ -163,14 +163,13 @@ int piehip_base_convert(piehip_handle h, int which, const uint64_t *in, uint32_t
     const size_t win = (size_t)npoly * (which == 2 ? MN : LN), wout = (size_t)npoly * (which == 2 ? LN : MN);
     TMPGET(din, win);
     TMPGET(dout, wout);
-    set_small_moduli(h->small_moduli);
     HIPCHK(hipMemcpy(din, in, win * sizeof(u64), hipMemcpyHostToDevice));
     if (which == 0)
-        launch_expand_q_to_qp(h->d_dc, N, L, din, 2 * LN, LN, npoly / 2, dout, 2, 0, h->stream);
+        launch_expand_q_to_qp(h->d_dc, N, L, din, 2 * LN, LN, npoly / 2, dout, 2, 0, h->stream, h->plan.small_moduli);
     else if (which == 1)
-        launch_scale_pq_expand(h->d_dc, N, L, din, 2 * LN, LN, npoly / 2, dout, 2, 0, h->stream);
+        launch_scale_pq_expand(h->d_dc, N, L, din, 2 * LN, LN, npoly / 2, dout, 2, 0, h->stream, h->plan.small_moduli);
     else
-        launch_scale_round(h->d_dc, N, L, din, npoly / 3, dout, 3 * LN, dout + 2 * LN, 3 * LN, h->stream);
+        launch_scale_round(h->d_dc, N, L, din, npoly / 3, dout, 3 * LN, dout + 2 * LN, 3 * LN, h->stream, h->plan.small_moduli);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out, dout, wout * sizeof(u64), hipMemcpyDeviceToHost));
@@ -224,7 +223,7 @@ int piehip_bench_ntt(piehip_handle h, uint32_t nlimbs, uint32_t mod_count, int f
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
-    const bool inverse = (flags & 1) != 0, sigma = (flags & 2) != 0 && h->sigma_on;
+    const bool inverse = (flags & 1) != 0, sigma = (flags & 2) != 0 && h->plan.lane_order;
     launch_ntt(h->plan, d, nlimbs, 0, mod_count, inverse, h->stream, sigma);  // warm-up
     HIPCHK(hipEventRecord(e0, h->stream));
     for (u32 i = 0; i < iters; i++) launch_ntt(h->plan, d, nlimbs, 0, mod_count, inverse, h->stream, sigma);

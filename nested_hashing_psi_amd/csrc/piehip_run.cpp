@@ -7,42 +7,34 @@ using namespace piehip;
 namespace piehip {
 
 // ---- schedule pieces ----------------------------------------------------------------------------
-// sigma: lane order on the EVALUATION side; fold: outer stage applied by the neighbouring kernels (both only
-// take effect when the context supports them; callers pass the same flags to those neighbours)
+// What a context does where -- which transform kernel, which fusions -- is decided once, in h->plan
 void ntt(piehip_ctx *h, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inv, bool sigma, bool fold, const NttExtra *ex)
 {
     ProfScope ps(h, inv ? PIEHIP_K_NTT_INV : PIEHIP_K_NTT_FWD, 16.0 * h->hp.N * nlimbs);
-    launch_ntt(h->plan, data, nlimbs, mod_base, mod_count, inv, h->stream, sigma && h->sigma_on, fold && h->fold_on, ex);
+    launch_ntt(h->plan, data, nlimbs, mod_base, mod_count, inv, h->stream, sigma && h->plan.lane_order, fold && h->plan.fold, ex);
 }
-// The X operand of a ciphertext multiplication is available in EVALUATION format before its inverse transform; when
-// the register-blocked kernel runs that transform it also drops a lane-ordered copy into the Q limbs of the QP operand
-// array, and the forward transform over QP skips those limbs (8 of 36 per bin layer at L = 4).  (For the first product of a
-// query batch stage A has written X there already: enqueue_run_bins, x_direct.)
-bool xq_reuse(const piehip_ctx *h) { return h->sigma_on && ntt_supports_extra(h->plan, h->fold_on); }
 
 // BV key switch of the COEFFICIENT-format polynomials at w.d2c with `key`, added to the EVALUATION
 // ciphertexts at w.d01, optionally multiplied by mask plaintexts: out[nb][2][L][N]
-// sigma: w.d01 and the digits are in lane order, key/mask are lane-ordered copies, out is written in standard order
-void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u64 *mask, u64 *out, bool sigma, bool fold,
-                       size_t key_stride, u32 key_group, bool out_is_result, bool digits_ready)
+void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u64 *mask, u64 *out, bool lane, size_t key_stride,
+                       u32 key_group, bool out_is_result, bool digits_ready)
 {
+    const NttPlan &pl = h->plan;
     const u32 N = h->hp.N, L = h->hp.L;
     const size_t LN = h->LN();
     const double W = 8.0 * N;
-    set_small_moduli(h->small_moduli);
-    bool fused = digits_ready;  // the caller's transform launch of d01 also lifted and transformed the digits
-    // digit lift inside the transform's load phase (the 32-coefficient kernel; contexts whose lane order is the 16-coefficient
-    // kernel's take the digits kernel + transform below)
-    if (!fused && h->sigma_on && h->d_twc && h->hp.logN <= 14 && !(sigma && ntt16_applies(h->plan, fold && h->fold_on))) {
+    lane = lane && pl.lane_order;
+    if (digits_ready) {
+        // the caller's transform launch of d01 also lifted and transformed the digits
+    } else if (lane ? pl.digit_lift_lane : pl.digit_lift_std) {
         ProfScope ps(h, PIEHIP_K_NTT_FWD, 16.0 * N * nb * L * L);
-        fused = launch_ntt_digits(h->plan, w.d2c, w.dig, nb, L, sigma && h->sigma_on, fold && h->fold_on, h->stream);
-    }
-    if (!fused) {
+        launch_ntt_digits(pl, w.d2c, w.dig, nb, L, lane, h->stream);
+    } else {
         {
             ProfScope ps(h, PIEHIP_K_DIGITS, W * nb * (L + (double)L * L));
-            launch_digits(h->d_dc, N, L, w.d2c, LN, nb, w.dig, h->stream, fold && h->fold_on);
+            launch_digits(h->d_dc, N, L, w.d2c, LN, nb, w.dig, h->stream, lane && pl.fold);
         }
-        ntt(h, w.dig, nb * L * L, 0, L, false, sigma, fold);
+        ntt(h, w.dig, nb * L * L, 0, L, false, lane, lane);
     }
     {
         // the result buffer may still be read by work the caller queued on the handle's stream before this run
@@ -52,9 +44,8 @@ void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u6
             (void)hipEventRecord(h->ev_chain, h->stream);
         }
         ProfScope ps(h, PIEHIP_K_RELIN, W * (nb * ((double)L * L + 2 * L + 2 * L + (mask ? L : 0)) + 2.0 * L * L));
-        launch_relin_mac(h->d_dc, N, L, w.d01, 2 * LN, w.dig, key, mask, out, nb, h->stream,
-                         (sigma && h->sigma_on) ? h->d_sigma_inv : nullptr, key_stride, key_group,
-                         (sigma && h->sigma_on) ? h->sigma_T : 0, h->sigma_kp, mask ? h->mask_div : 1);
+        launch_relin_mac(h->d_dc, N, L, w.d01, 2 * LN, w.dig, key, mask, out, nb, h->stream, pl.small_moduli,
+                         lane ? h->d_sigma_inv : nullptr, key_stride, key_group, lane ? pl.lane_T : 0, pl.lane_kp, mask ? h->mask_div : 1);
     }
 }
 
@@ -67,8 +58,9 @@ struct RunKey {
 };
 static RunKey run_key(const piehip_ctx *h)
 {
-    if (h->key_group > 1) return {h->sigma_on ? h->d_evkq_sigma : h->d_evkq, (size_t)h->hp.L * 2 * h->LN(), h->key_group};
-    return {h->sigma_on ? h->d_evk_sigma : h->d_evk, 0, 1};
+    const bool lane = h->plan.lane_order;
+    if (h->key_group > 1) return {lane ? h->d_evkq_sigma : h->d_evkq, (size_t)h->hp.L * 2 * h->LN(), h->key_group};
+    return {lane ? h->d_evk_sigma : h->d_evk, 0, 1};
 }
 
 // One batched EvalMult(ct,ct) (BatchedFHEHIPPIE.cpp:123): operands in COEFFICIENT format (produced by
@@ -81,10 +73,10 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M;
     const size_t LN = h->LN();
     const double W = 8.0 * N;
-    set_small_moduli(h->small_moduli);
+    const NttPlan &pl = h->plan;
     {
         ProfScope ps(h, PIEHIP_K_EXPAND, W * nb * (4.0 * L + 4.0 * M));
-        launch_expand_both(h->d_dc, N, L, x, sx, y, sy, LN, nb, w.eqp, h->stream, h->fold_on, xq_ready);
+        launch_expand_both(h->d_dc, N, L, x, sx, y, sy, LN, nb, w.eqp, h->stream, pl.small_moduli, pl.fold, xq_ready);
     }
     // the QP operands and the tensor result never leave the library: lane order, no LDS transposes
     {
@@ -96,45 +88,39 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
         }
         ntt(h, w.eqp, nb * (xq_ready ? 4 * M - 2 * L : 4 * M), 0, M, false, true, true, &ex);
     }
-    // Tensor product and inverse transform of its result.  One launch where the 16-coefficient kernel runs the transform in lane
-    // order and every modulus has 60 bits: each item forms its input from the four operands in its load phase, the tensor
-    // result is neither written nor read back (3 M limbs per row each way).  Otherwise two launches.
-    bool fused = false;
-    if (PIEHIP_FUSE_TENSOR && h->sigma_on && h->small_moduli && ntt16_applies(h->plan, h->fold_on)) {
+    // Tensor product and inverse transform of its result.  One launch where the plan allows: each item forms its input from the four
+    // operands in its load phase, the tensor result is neither written nor read back (3 M limbs per row each way).
+    if (pl.fused_tensor) {
         ProfScope ps(h, PIEHIP_K_TENSOR_NTT_INV, W * nb * 7.0 * M);
-        fused = launch_ntt16_tensor(h->plan, h->fold_on, w.eqp, w.dqp, nb, M, h->stream);
-    }
-    if (!fused) {
+        launch_ntt16_tensor(pl, w.eqp, w.dqp, nb, M, h->stream);
+    } else {
         {
             ProfScope ps(h, PIEHIP_K_TENSOR, W * nb * 7.0 * M);
-            launch_tensor(h->d_dc, N, M, w.eqp, w.dqp, nb, h->stream);
+            launch_tensor(h->d_dc, N, M, w.eqp, w.dqp, nb, h->stream, pl.small_moduli);
         }
         ntt(h, w.dqp, nb * 3 * M, 0, M, true, true, true);
     }
     if (relin) {
         {
             ProfScope ps(h, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, h->stream, h->fold_on, false);
+            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, h->stream, pl.small_moduli, pl.fold, false);
         }
-        bool digits_ready = false;
-        {
-            NttExtra ex;
-            ex.lazy_out = true;  // the key-switch MAC adds d01 into its accumulator before reducing
-            if (h->sigma_on && h->small_moduli && ntt16_applies(h->plan, h->fold_on)) {
-                // one launch for both forward transforms in front of the key-switch MAC: d0, d1 and the L * L digits of d2
-                // (equal-width primes only: the kernel's lift is a conditional subtraction)
-                ProfScope ps(h, PIEHIP_K_NTT_FWD, 16.0 * N * nb * (2.0 * L + (double)L * L));
-                Ntt16Digits dg = {w.d2c, LN, w.dig, nb, L};
-                digits_ready = launch_ntt16(h->plan, h->fold_on, w.d01, nb * 2 * L, 0, L, false, true, h->stream, &ex, &dg);
-            }
-            if (!digits_ready) ntt(h, w.d01, nb * 2 * L, 0, L, false, true, true, &ex);
+        NttExtra ex;
+        ex.lazy_out = true;  // the key-switch MAC adds d01 into its accumulator before reducing
+        if (pl.digits_with_d01) {
+            // one launch for both forward transforms in front of the key-switch MAC: d0, d1 and the L * L digits of d2
+            ProfScope ps(h, PIEHIP_K_NTT_FWD, 16.0 * N * nb * (2.0 * L + (double)L * L));
+            Ntt16Digits dg = {w.d2c, LN, w.dig, nb, L};
+            launch_ntt16(pl, w.d01, nb * 2 * L, 0, L, false, true, h->stream, &ex, &dg);
+        } else {
+            ntt(h, w.d01, nb * 2 * L, 0, L, false, true, true, &ex);
         }
         const RunKey k = run_key(h);
-        enqueue_keyswitch(h, w, nb, k.key, mask, out, true, true, k.stride, k.group, out_is_result, digits_ready);
+        enqueue_keyswitch(h, w, nb, k.key, mask, out, true, k.stride, k.group, out_is_result, pl.digits_with_d01);
     } else {
         {
             ProfScope ps(h, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, out, 3 * LN, out + 2 * LN, 3 * LN, h->stream, h->fold_on, true);
+            launch_scale_round(h->d_dc, N, L, w.dqp, nb, out, 3 * LN, out + 2 * LN, 3 * LN, h->stream, pl.small_moduli, pl.fold, true);
         }
         ntt(h, out, nb * 3 * L, 0, L, false, false, true);
     }
@@ -258,7 +244,7 @@ static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
     u64 *acc = h->d_acc + r0 * K * 2 * LN;
     u64 *prod = h->d_prod ? h->d_prod + r0 * 2 * LN : nullptr;
     u64 *out = results + r0 * 2 * LN;
-    const u64 *masks = (h->sigma_on ? h->d_masks_sigma : h->d_masks) + (size_t)b0 * LN;
+    const u64 *masks = (h->plan.lane_order ? h->d_masks_sigma : h->d_masks) + (size_t)b0 * LN;
     struct MaskDiv {
         piehip_ctx *h;
         ~MaskDiv() { h->mask_div = h->key_group = 1; }
@@ -266,13 +252,13 @@ static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
     h->mask_div = nq;
     h->key_group = (nq > 1 && h->d_evkq && h->evkq_n == nq) ? nq : 1;  // per-query EvalMult keys: row r of a group is query r % nq
     // Operand X of the first ciphertext product (the accumulators of inner hash function 0) is needed twice: in COEFFICIENT
-    // form by the base extension, and in EVALUATION form, lane-ordered, as the Q limbs of the QP operand (xq_reuse).  Until r04
+    // form by the base extension, and in EVALUATION form, lane-ordered, as the Q limbs of the QP operand (plan.xq_reuse).  Until r04
     // the inverse transform wrote that second copy; now stage A writes X there in the first place and the transform reads it
     // from there (out of place, lane order in: its fast path) -- 44 MB less per step at the headline shape: the inverse launches
     // 161 -> 150 us per step of three queries, stage A + 2.5 (its X rows leave in 64-byte runs) and the base extension + 2.5.
     // Query batches only: one query's transform launches are single partial rounds that gain 1 us, and its stage A kernel, which
     // runs at the HBM rate, loses 2.5 (profiles/r04/stage_a_writes_x_lane_ordered.txt).
-    const bool x_direct = K > 1 && nq > 1 && xq_reuse(h) && h->small_moduli && ntt16_applies(h->plan, h->fold_on);
+    const bool x_direct = K > 1 && nq > 1 && h->plan.x_direct;
     if (h->profiling) {  // an empty bracket: what the event pair itself costs on this stream (reported beside the kernels' times)
         ProfScope ps(h, PIEHIP_K_EVENT_PAIR, 0.0);
     }
@@ -282,11 +268,11 @@ static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
         for (u32 q = 0; q < nq; q++) qs.idx[q] = h->query[q].idx, qs.minus[q] = h->query[q].minus;
         const u64 *db = h->d_db + (size_t)b0 * E * LN;
         StageAXOut xo;
-        if (x_direct) xo.out = w.eqp, xo.M = M, xo.logns = h->hp.logN - (h->fold_on ? 1 : 0);
+        if (x_direct) xo.out = w.eqp, xo.M = M, xo.logns = h->plan.lane_logn;
         if (nq > 1) {
-            launch_stage_a_batch(h->d_dc, N, L, K, layers, E, qs, nq, db, acc, h->stream, h->small_moduli, b, 0, 0, x_direct ? &xo : nullptr);
+            launch_stage_a_batch(h->d_dc, N, L, K, layers, E, qs, nq, db, acc, h->stream, h->plan.small_moduli, b, 0, 0, x_direct ? &xo : nullptr);
         } else {
-            launch_stage_a(h->d_dc, N, L, K, nb, E, qs.idx[0], qs.minus[0], db, acc, h->stream, h->small_moduli, b, 0, 0, 1, 0,
+            launch_stage_a(h->d_dc, N, L, K, nb, E, qs.idx[0], qs.minus[0], db, acc, h->stream, h->plan.small_moduli, b, 0, 0, 1, 0,
                            x_direct ? &xo : nullptr);
         }
     }
@@ -299,7 +285,7 @@ static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
         return;
     }
     // every accumulator enters a ct x ct product exactly once: switch them all to COEFFICIENT format
-    const bool xq = xq_reuse(h);
+    const bool xq = h->plan.xq_reuse;
     NttExtra ex;
     ex.copy_out = w.eqp;
     ex.copy_K = K;

@@ -182,7 +182,7 @@ def test_L7_sixteen_coefficient_rings(ob, pie, N, ops, run, extreme):
 # ---- ring sizes outside the benchmark's ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("L", [3, 7])
 def test_largest_ring(ob, pie, L):
-    """N = 65536: the only ring with ntt_fast_s0 = 2 (two ntt_global_stage passes before the fast kernel, in that order), no
+    """N = 65536: the only ring whose route (ntt_route) has s0 = 2 (two ntt_global_stage passes before the fast kernel, in that order), no
     folded or 16-coefficient transform: unfolded base conversions and digits_kernel"""
     o, cc = _contexts(ob, pie, 65536, L, T32, None)
     rng = np.random.default_rng(65536 + L)
