@@ -58,6 +58,8 @@ struct NttPlan {
     bool xq_reuse = false;         // the inverse transform of operand X drops a lane-ordered copy into the QP array, the forward skips it
     bool x_direct = false;         // stage A of a query batch may write X there in the first place (StageAXOut)
     bool fused_tensor = false;     // launch_ntt16_tensor instead of launch_tensor + inverse transform
+    bool d01_eval_q = false;       // relinearising product: the Q limbs of d0, d1 stay in EVALUATION form -- not inverse-
+                                   // transformed, not seen by scale-and-round; the key-switch MAC forms c_k (a (x) b)_k from the QP operands
     bool digits_with_d01 = false;  // the key-switch digits join the forward launch of d0, d1 (Ntt16Digits)
     bool digit_lift_lane = false;  // launch_ntt_digits instead of launch_digits + transform: lane-ordered key switches,
     bool digit_lift_std = false;   // ... standard-order key switches (FHEHIPPIE, piehip_eval_automorph)
@@ -123,7 +125,12 @@ void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mo
 #ifndef PIEHIP_FUSE_TENSOR
 #define PIEHIP_FUSE_TENSOR 1
 #endif
-void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st);
+// eval_q_L = L (pl.d01_eval_q, relinearising products): the Q limbs (< L) of d0 and d1 are not produced -- 3 M - 2 L limbs per row; their
+// places in d[nb][3][M][N] are not written.  -DPIEHIP_D01_EVAL_Q=0 clears that switch
+#ifndef PIEHIP_D01_EVAL_Q
+#define PIEHIP_D01_EVAL_Q 1
+#endif
+void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st, u32 eval_q_L = 0);
 // pl.digit_lift_lane / digit_lift_std: forward transform of the BV digits with the digit lift in the 32-coefficient kernel's load
 // phase (no digits kernel): d2[nb][L][N] COEFFICIENT -> dig[nb][L(i)][L(j)][N] EVALUATION
 void launch_ntt_digits(const NttPlan &pl, const u64 *d2, u64 *dig, u32 nb, u32 L, bool sigma, hipStream_t st);
@@ -175,8 +182,10 @@ void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 
 // d[nb][3][M][N] (COEFFICIENT) -> components 0,1 to out01 + bin*stride01 + c*L*N, component 2 to out2 + bin*stride2
 // fold: the outermost NTT stage of the neighbouring transforms is applied here (see kernels_pie.hip, "Outer-stage
 // folding"); fold_comp2: component 2 also feeds a forward transform directly (3-component output)
+// p_only01 (pl.d01_eval_q): components 0 and 1 are computed from their P limbs alone -- the Q limbs of d are not read and the own-limb
+// term d_k [t P^-1]_{q_k} is left out (the key-switch MAC adds its transform: launch_relin_mac, eqp)
 void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb, u64 *out01, size_t stride01, u64 *out2,
-                        size_t stride2, hipStream_t st, bool small_moduli, bool fold = false, bool fold_comp2 = false);
+                        size_t stride2, hipStream_t st, bool small_moduli, bool fold = false, bool fold_comp2 = false, bool p_only01 = false);
 // BV digits: d2c at d2 + bin*stride2 ([L][N], COEFFICIENT) -> dig[nb][L(i)][L(j)][N] (centred lift of residue i into q_j)
 void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stride2, u32 nb, u64 *dig, hipStream_t st,
                    bool fold = false);
@@ -186,9 +195,11 @@ void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stri
 // mask_div > 1: ciphertext `bin` takes mask[bin / mask_div] (a query batch: mask_div queries per bin layer)
 // sigma_T != 0: out_map is the lane order of a transform with sigma_T threads per slice and sigma_kp coefficient pairs per thread
 // (16: kernels_ntt_fast.hip, 8: ntt16_kernel.h); stores then go through an LDS tile
+// eqp (pl.d01_eval_q; null: off): the QP operands e[nb][4][eqp_M][N] (a0 a1 b0 b1, EVALUATION, ordered like d01, [0, 8q) residues) of the
+// product whose d0, d1 arrive without their own-limb term: [t P^-1]_{q_j} a0 b0 is added to component 0, ... (a0 b1 + a1 b0) to component 1
 void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t stride01, const u64 *dig, const u64 *key,
                       const u64 *mask, u64 *out, u32 nb, hipStream_t st, bool small_moduli, const u32 *out_map = nullptr, size_t key_stride = 0,
-                      u32 key_group = 1, u32 sigma_T = 0, u32 sigma_kp = 16, u32 mask_div = 1);
+                      u32 key_group = 1, u32 sigma_T = 0, u32 sigma_kp = 16, u32 mask_div = 1, const u64 *eqp = nullptr, u32 eqp_M = 0);
 // rotation-based PIE (FHEHIPPIE.cpp:61-77), see kernels_pie.hip
 void launch_bcast_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t xs, u32 group, const u64 *pt, size_t ps_outer,
                             size_t ps_inner, u64 *out, u32 nct, hipStream_t st);

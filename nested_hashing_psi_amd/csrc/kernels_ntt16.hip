@@ -85,6 +85,8 @@ void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mo
     a.lift_stride = 0;
     a.lift_L = 1;
     a.tsrc = nullptr;
+    a.tq_L = 0;
+    a.tq_first = 0;
     if (dg && !inverse) {  // the key-switch digits ride in the same launch: nb * L * L more limbs, lifted in the load phase
         a.lift_first = a.nitems;
         a.nitems += (dg->nb * dg->L * dg->L) << s0;
@@ -100,9 +102,9 @@ void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mo
         launch_ntt16_t<13>(a, inverse, lift, pl.transform_cus(), st);
 }
 
-void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st)
+void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st, u32 eval_q_L)
 {
-    assert(pl.fused_tensor);
+    assert(pl.fused_tensor && (!eval_q_L || (pl.d01_eval_q && eval_q_L < M)));
     const bool folded = pl.fold;
     const u32 s0 = folded ? 1u : 0u;
     ntt16::Args a = {};
@@ -112,7 +114,9 @@ void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M,
     a.dc = pl.dc;
     a.N = pl.N;
     a.s0 = s0;
-    a.nitems = (nb * 3 * M) << s0;
+    a.tq_L = eval_q_L;
+    a.tq_first = (nb * 3 * (M - eval_q_L)) << s0;
+    a.nitems = a.tq_first + ((nb * eval_q_L) << s0);  // 3 M - 2 eval_q_L limbs per row
     a.mod_base = 0;
     a.mod_count = M;
     a.flags = folded ? ntt16::F_FOLDED : 0;

@@ -6,6 +6,8 @@
 // from one DevConsts block.  Reference call sites: BatchedFHEHIPPIE.cpp:101-127.
 #include <stdlib.h>
 
+#include <cassert>
+
 #include <algorithm>
 
 #include "kernels.hpp"
@@ -1136,7 +1138,10 @@ void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 
 // transform of the 16-coefficient kernel
 // PRE: the inputs come from a folded load with the merged constants (DevConsts::fold_iap / fold_iat): the P limbs already hold
 // yp_j = [d_j (QP/p_j)^-1]_{p_j}, the Q limbs [d_k t P^-1]_{q_k} -- the products this routine would form first
-template <u32 L, bool MAD, int NP, bool PRE = false>
+// PONLY: the own-limb term d_k [t P^-1]_{q_k} is left out and d[.][k < L] is not read.  The term is the only place a Q limb enters, one
+// constant times the limb's own coefficients: it commutes with the transform of limb k, and the key-switch MAC adds it in EVALUATION
+// form (relin_mac_kernel, EQ) -- components 0 and 1 of a relinearising product.  Every column sum below only loses a term.
+template <u32 L, bool MAD, int NP, bool PRE = false, bool PONLY = false>
 __device__ __forceinline__ void scale_round_core(const DevConsts *dc, const u64 (&d)[NP][2 * L + 1], u64 (&out)[NP][L], bool lz = false)
 {
     constexpr u32 Lp = L + 1;
@@ -1177,14 +1182,18 @@ __device__ __forceinline__ void scale_round_core(const DevConsts *dc, const u64 
                 ColAcc a = {itot[p].lo, 0, 0};
 #pragma unroll
                 for (u32 j = 0; j < Lp; j++) colacc_mac(a, split30(yp[p][j]), split30(col[j]));
-                if (PRE)
+                if (PONLY)
+                    ;
+                else if (PRE)
                     a.c0 += d[p][k];  // (canonical, < 2^60: column 0 holds L + 2 products' low parts and the integer parts besides)
                 else
                     colacc_mac(a, split30(d[p][k]), split30(tp));
                 out[p][k] = (L <= 5 && lz) ? colacc_reduce123_lazy(a, qk, nq) : colacc_reduce<(L > 5)>(a, qk, nq);
             } else {
                 U128 acc = dot128<Lp, MAD>(yp[p], col);
-                if (PRE)
+                if (PONLY)
+                    ;
+                else if (PRE)
                     add128(acc, U128{d[p][k], 0});
                 else
                     mac128(acc, d[p][k], tp);
@@ -1197,22 +1206,17 @@ __device__ __forceinline__ void scale_round_core(const DevConsts *dc, const u64 
 
 // FOLD: inverse outer stage on load; forward outer stage on the store of components 0 and 1 (they go to a
 // forward transform); component 2 is stored as plain coefficients (the digit kernel folds it per target modulus)
-template <bool FOLD, u32 L, bool MAD>
-__global__ void __launch_bounds__(TPB) scale_round_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ d,
-                                                          u64 *__restrict__ out01, size_t stride01,
-                                                          u64 *__restrict__ out2, size_t stride2, u32 fold_comp2)
+// PONLY: this component takes its P limbs only (scale_round_core); the loads of the Q limbs and their folded-load products go with the term
+template <bool FOLD, u32 L, bool MAD, bool PONLY>
+__device__ __forceinline__ void scale_round_comp(const DevConsts *__restrict__ dc, u32 N, u32 n, const u64 *__restrict__ pin,
+                                                 u64 *__restrict__ pout, bool fold_out, bool lz)
 {
-    const u32 n = blockIdx.x * TPB + threadIdx.x;
     const u32 H = N / 2;
-    if (n >= (FOLD ? H : N)) return;
-    const u32 comp = blockIdx.y, bin = blockIdx.z;
     constexpr u32 M = 2 * L + 1;
-    const u64 *pin = d + ((size_t)(bin * 3 + comp) * M) * N + n;
-    u64 *pout = comp < 2 ? out01 + (size_t)bin * stride01 + (size_t)comp * L * N + n : out2 + (size_t)bin * stride2 + n;
     constexpr int NP = FOLD ? 2 : 1;
     u64 x[NP][M], y[NP][L];
 #pragma unroll
-    for (u32 a = 0; a < M; a++) {
+    for (u32 a = PONLY ? L : 0; a < M; a++) {
         if (FOLD) {
             // the folded load and the first product of scale-and-round in one Shoup multiplication (merged constants)
             PIE_ITER_FENCE();
@@ -1227,15 +1231,13 @@ __global__ void __launch_bounds__(TPB) scale_round_kernel(const DevConsts *__res
             x[0][a] = pin[(size_t)a * N];
         }
     }
-    // d0, d1 of the key-switch path go on through fold_store into the forward transform ([0, 8q) in): [0, 4q) will do.  d2 feeds the
-    // digit lift (canonical), and with fold_comp2 the three components leave the library's lane-ordered world
-    scale_round_core<L, MAD, NP, FOLD>(dc, x, y, FOLD && MAD && comp < 2 && !fold_comp2);
+    scale_round_core<L, MAD, NP, FOLD, PONLY>(dc, x, y, lz);
 #pragma unroll
     for (u32 k = 0; k < L; k++) {
         PIE_ITER_FENCE();
         if (FOLD) {
             u64 y0 = y[0][k], y1 = y[NP - 1][k];
-            if (comp < 2 || fold_comp2) fold_store(dc, k, y[0][k], y[NP - 1][k], y0, y1);
+            if (fold_out) fold_store(dc, k, y[0][k], y[NP - 1][k], y0, y1);
             pout[(size_t)k * N] = y0;
             pout[(size_t)k * N + H] = y1;
         } else {
@@ -1243,24 +1245,45 @@ __global__ void __launch_bounds__(TPB) scale_round_kernel(const DevConsts *__res
         }
     }
 }
-void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb, u64 *out01, size_t stride01, u64 *out2,
-                        size_t stride2, hipStream_t st, bool small_moduli, bool fold, bool fold_comp2)
+// P01: components 0 and 1 are the PONLY variant (a uniform branch on the component: blockIdx.y), component 2 the full one
+template <bool FOLD, u32 L, bool MAD, bool P01 = false>
+__global__ void __launch_bounds__(TPB) scale_round_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ d,
+                                                          u64 *__restrict__ out01, size_t stride01,
+                                                          u64 *__restrict__ out2, size_t stride2, u32 fold_comp2)
 {
+    const u32 n = blockIdx.x * TPB + threadIdx.x;
+    if (n >= (FOLD ? N / 2 : N)) return;
+    const u32 comp = blockIdx.y, bin = blockIdx.z;
+    constexpr u32 M = 2 * L + 1;
+    const u64 *pin = d + ((size_t)(bin * 3 + comp) * M) * N + n;
+    u64 *pout = comp < 2 ? out01 + (size_t)bin * stride01 + (size_t)comp * L * N + n : out2 + (size_t)bin * stride2 + n;
+    // d0, d1 of the key-switch path go on through fold_store into the forward transform ([0, 8q) in): [0, 4q) will do.  d2 feeds the
+    // digit lift (canonical), and with fold_comp2 the three components leave the library's lane-ordered world
+    const bool lz = FOLD && MAD && comp < 2 && !fold_comp2;
+    if (P01 && comp < 2)
+        scale_round_comp<FOLD, L, MAD, true>(dc, N, n, pin, pout, true, lz);
+    else
+        scale_round_comp<FOLD, L, MAD, false>(dc, N, n, pin, pout, comp < 2 || fold_comp2, lz);
+}
+void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb, u64 *out01, size_t stride01, u64 *out2,
+                        size_t stride2, hipStream_t st, bool small_moduli, bool fold, bool fold_comp2, bool p_only01)
+{
+    assert(!p_only01 || (small_moduli && !fold_comp2));
     dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, 3, nb);
-#define SRL(L_)                                                                                                              \
-    case L_:                                                                                                                 \
-        if (fold && small_moduli)                                                                                          \
-            hipLaunchKernelGGL((scale_round_kernel<true, L_, true>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, \
-                               fold_comp2 ? 1u : 0u);                                                                        \
-        else if (fold)                                                                                                       \
-            hipLaunchKernelGGL((scale_round_kernel<true, L_, false>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, \
-                               fold_comp2 ? 1u : 0u);                                                                        \
-        else if (small_moduli)                                                                                             \
-            hipLaunchKernelGGL((scale_round_kernel<false, L_, true>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, 0u); \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((scale_round_kernel<false, L_, false>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, 0u); \
+#define SRK(F_, L_, M_, P_) \
+    hipLaunchKernelGGL((scale_round_kernel<F_, L_, M_, P_>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, (fold_comp2 && F_) ? 1u : 0u)
+#define SRL(L_)                                                                        \
+    case L_:                                                                           \
+        if (p_only01) {                                                                \
+            if (fold) SRK(true, L_, true, true); else SRK(false, L_, true, true);      \
+        } else if (small_moduli) {                                                     \
+            if (fold) SRK(true, L_, true, false); else SRK(false, L_, true, false);    \
+        } else {                                                                       \
+            if (fold) SRK(true, L_, false, false); else SRK(false, L_, false, false);  \
+        }                                                                              \
         break;
     switch (L) { SRL(1) SRL(2) SRL(3) SRL(4) SRL(5) SRL(6) SRL(7) }
+#undef SRK
 #undef SRL
 }
 
@@ -1314,14 +1337,20 @@ void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stri
 // r and r + key_group -- and loads every key word once for both.  The kernel is bound by the traffic through the L1s (330 MB per step at
 // the headline shape, more than half of it key words that every row re-reads from the L2: profiles/r05/stage_a_batch_layer_groups.txt
 // has the model); a launch's last block of rows may have no second row (uniform branch).
-template <bool MAD, int KP, int RPT = 1>
+// EQ (column-accumulator path only; NttPlan::d01_eval_q): d01 arrives without the own-limb term of scale-and-round (scale_round_core, PONLY).
+// Its transform is [t P^-1]_{q_j} times limb j of the tensor product in EVALUATION form, which this kernel forms from the QP operands
+// eqp[row][4][eqp_M][N] (a0 a1 b0 b1 at limb j, ordered like d01, [0, 8q) residues) as tensor_kernel<true> does: t0 = a0 b0 for component
+// 0, t1 = a0 b1 + a1 b0 for component 1, each through one reduction block to [0, 4q) and one Shoup product with the constant.
+template <bool MAD, int KP, int RPT = 1, bool EQ = false>
 __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, const u64 *__restrict__ d01,
                                                         size_t stride01, const u64 *__restrict__ dig,
                                                         const u64 *__restrict__ key0, const u64 *__restrict__ mask,
                                                         u64 *__restrict__ out, const u32 *__restrict__ out_map,
-                                                        size_t key_stride, u32 key_group, u32 T, u32 mask_div, u32 nb)
+                                                        size_t key_stride, u32 key_group, u32 T, u32 mask_div, u32 nb,
+                                                        const u64 *__restrict__ eqp, u32 eqp_M)
 {
     static_assert(RPT == 1 || MAD, "two rows per thread: the column-accumulator path");
+    static_assert(!EQ || MAD, "the own-limb term: the column-accumulator path");
     constexpr bool TILE = KP > 0;
     constexpr u32 TT = TILE ? TPB / (KP ? KP : 1) : 1;  // threads of the transform per tile
     __shared__ u64x2 s_tile[TILE ? 2 * RPT : 1][TILE ? TPB : 1];
@@ -1354,7 +1383,11 @@ __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restr
     u64x2 res[RPT][2];
     if (MAD) {
         // column accumulators end to end: the L products, then d01 (it may arrive unnormalised, < 2^63, from the forward
-        // transform) into column 0 -- (L + 8) 2^60 < 2^64 -- and one reduction block; the mask product likewise
+        // transform) into column 0 -- (L + 8) 2^60 < 2^64 -- and one reduction block; the mask product likewise.
+        // EQ: the own-limb term v < 4q < 2^62 joins as its 30-bit halves, v mod 2^30 into column 0 and v >> 30 < 2^32 into column 1.
+        // Column 0 then holds less than (L + 8) 2^60 + 2^30 <= 15 2^60 + 2^30 < 2^64 at L = 7 (whole, the term would make it
+        // (L + 9) 2^60 = 2^64 there); column 1 less than 2 L 2^60 + 2^32; the value z grows by less than 2^62, far inside the reduction
+        // block's 2^123 (L products below 2^120 each).
         ColAcc a[RPT][2][2];
 #pragma unroll
         for (int r = 0; r < RPT; r++)
@@ -1376,6 +1409,33 @@ __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restr
             }
         }
         const u64 nq = 0 - m.q;
+        if (EQ) {
+            const u64 n2q = neg_u(2 * m.q), n4q = neg_u(4 * m.q);
+            const u64 tp = dc->tPinv_modq[j], tpsh = dc->tPinv_modq_sh[j];
+            const size_t MN = (size_t)eqp_M * N;
+#pragma unroll
+            for (int r = 0; r < RPT; r++) {
+                if (r && !has[r]) continue;
+                const u64 *pe = eqp + (size_t)rows[r] * 4 * MN + (size_t)j * N + n;
+                const u64x2 va0 = *reinterpret_cast<const u64x2 *>(pe), va1 = *reinterpret_cast<const u64x2 *>(pe + MN),
+                            vb0 = *reinterpret_cast<const u64x2 *>(pe + 2 * MN), vb1 = *reinterpret_cast<const u64x2 *>(pe + 3 * MN);
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    // operands below 2q (two sign-mask subtractions); d1's two products keep every column below 2^63, z < 8 q^2 < 2^123
+                    const Split30 sa0 = split30(csub_u(csub_u(k ? va0.y : va0.x, n4q), n2q)), sa1 = split30(csub_u(csub_u(k ? va1.y : va1.x, n4q), n2q));
+                    const Split30 sb0 = split30(csub_u(csub_u(k ? vb0.y : vb0.x, n4q), n2q)), sb1 = split30(csub_u(csub_u(k ? vb1.y : vb1.x, n4q), n2q));
+                    ColAcc t = {0, 0, 0};
+                    colacc_mac(t, sa0, sb0);
+                    const u64 v0 = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+                    t = ColAcc{0, 0, 0};
+                    colacc_mac(t, sa0, sb1);
+                    colacc_mac(t, sa1, sb0);
+                    const u64 v1 = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+                    a[r][0][k].c0 += v0 & 0x3FFFFFFFull, a[r][0][k].c1 += v0 >> 30;
+                    a[r][1][k].c0 += v1 & 0x3FFFFFFFull, a[r][1][k].c1 += v1 >> 30;
+                }
+            }
+        }
 #pragma unroll
         for (int r = 0; r < RPT; r++) {
             if (r && !has[r]) continue;
@@ -1452,8 +1512,9 @@ __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restr
 }
 void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t stride01, const u64 *dig, const u64 *key,
                       const u64 *mask, u64 *out, u32 nb, hipStream_t st, bool small_moduli, const u32 *out_map, size_t key_stride,
-                      u32 key_group, u32 sigma_T, u32 sigma_kp, u32 mask_div)
+                      u32 key_group, u32 sigma_T, u32 sigma_kp, u32 mask_div, const u64 *eqp, u32 eqp_M)
 {
+    assert(!eqp || (small_moduli && eqp_M >= L));
     if (!key_group) key_group = 1;
     if (!mask_div) mask_div = 1;
     // sigma_T: out_map is the lane order of a register-blocked transform with sigma_T threads per slice, sigma_kp pairs per thread
@@ -1464,17 +1525,25 @@ void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t 
     const bool two = small_moduli && nb >= 2 * key_group;
     const u32 zrows = two ? ((nb + 2 * key_group - 1) / (2 * key_group)) * key_group : nb;
     dim3 grid((N / 2 + TPB - 1) / TPB, L, zrows);
-#define RM(M_, K_, R_)                                                                                                              \
-    hipLaunchKernelGGL((relin_mac_kernel<M_, K_, R_>), grid, dim3(TPB), 0, st, dc, N, L, d01, stride01, dig, key, mask, out, out_map, \
-                       key_stride, key_group, sigma_T, mask_div, nb)
-    if (two) {
+#define RME(M_, K_, R_, E_)                                                                                                            \
+    hipLaunchKernelGGL((relin_mac_kernel<M_, K_, R_, E_>), grid, dim3(TPB), 0, st, dc, N, L, d01, stride01, dig, key, mask, out, out_map, \
+                       key_stride, key_group, sigma_T, mask_div, nb, eqp, eqp_M)
+#define RM(M_, K_, R_) RME(M_, K_, R_, false)
+#define RQ(K_, R_) RME(true, K_, R_, true)
+    if (eqp && two) {
+        if (kp == 16) RQ(16, 2); else if (kp == 8) RQ(8, 2); else RQ(0, 2);
+    } else if (eqp) {
+        if (kp == 16) RQ(16, 1); else if (kp == 8) RQ(8, 1); else RQ(0, 1);
+    } else if (two) {
         if (kp == 16) RM(true, 16, 2); else if (kp == 8) RM(true, 8, 2); else RM(true, 0, 2);
     } else if (small_moduli) {
         if (kp == 16) RM(true, 16, 1); else if (kp == 8) RM(true, 8, 1); else RM(true, 0, 1);
     } else {
         if (kp == 16) RM(false, 16, 1); else if (kp == 8) RM(false, 8, 1); else RM(false, 0, 1);
     }
+#undef RQ
 #undef RM
+#undef RME
 }
 
 // One word for the host: `value` lands in page-locked host memory when everything queued on the stream before it is done

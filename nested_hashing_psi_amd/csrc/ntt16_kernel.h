@@ -269,6 +269,9 @@ struct Args {
     // inverse, TENSOR instantiation: the input of item (row, d, limb m, slice) is not read from data but formed in the load phase
     // from the lane-ordered QP operands tsrc[row][4][mod_count][N] (a0 a1 b0 b1): d0 = a0 b0, d1 = a0 b1 + a1 b0, d2 = a1 b1
     const u64 *tsrc;
+    // ... tq_L != 0: d0 and d1 are wanted on their P limbs (>= tq_L) only.  Items [0, tq_first) are the (d0, d1, d2) triples of the P
+    // limbs, items [tq_first, nitems) the d2 items of the Q limbs: (row, limb < tq_L, slice).  tq_L = 0: tq_first = nitems, every limb a triple
+    u32 tq_L, tq_first;
 };
 enum : u32 {
     F_STD_IN = 1,    // inverse: EVALUATION input in standard (bit-reversed) order instead of lane order
@@ -519,20 +522,30 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
         // Enumerated with d innermost and dealt like the digit items above (blocks of 8 x 3), they run in workgroups 8 apart in the
         // same round: one XCD, each operand slice fetched once.  (The persistent grid strides by gridDim.x = 16 mod 24 or 8 mod 24
         // on 256 CUs: a workgroup's items cycle through d, none collects the twice as long d = 1 items.)
+        // With tq_L the triples are those of the P limbs only (their last, incomplete block of 24 in natural order, as before); the Q limbs'
+        // d2 items share their operands with nobody and follow in natural order -- the shortest items, at the launch's tail.
         u32 t_d = 0, t_row = 0, t_blk = 0, t_limb = 0;
         if (TENSOR) {
-            const u32 M_ = a.mod_count;
+            const u32 M_ = a.mod_count, TL = a.tq_L, TM = M_ - TL;  // TM: limbs with triples
+            if (item < a.tq_first) {
 #if NTT16_TENSOR_XCD
-            u32 il = item;
-            const u32 within = il % 24;
-            if (il - within + 24 <= a.nitems) il = il - within + (within & 7) * 3 + (within >> 3);
-            const u32 u = il / 3, lm = u >> a.s0;
-            t_d = il % 3, t_blk = u & ((1u << a.s0) - 1), t_row = lm / M_;
-            t_limb = (t_row * 3 + t_d) * M_ + lm % M_;
+                u32 il = item;
+                const u32 within = il % 24;
+                if (il - within + 24 <= a.tq_first) il = il - within + (within & 7) * 3 + (within >> 3);
+                const u32 u = il / 3, lm = u >> a.s0;
+                t_d = il % 3, t_blk = u & ((1u << a.s0) - 1), t_row = lm / TM;
+                t_limb = (t_row * 3 + t_d) * M_ + TL + lm % TM;
 #else
-            t_limb = item >> a.s0, t_blk = item & ((1u << a.s0) - 1);
-            t_row = t_limb / (3 * M_), t_d = (t_limb / M_) % 3;
+                const u32 lm = item >> a.s0;
+                t_blk = item & ((1u << a.s0) - 1);
+                t_row = lm / (3 * TM), t_d = (lm / TM) % 3;
+                t_limb = (t_row * 3 + t_d) * M_ + TL + lm % TM;
 #endif
+            } else {
+                const u32 v = item - a.tq_first, lm = v >> a.s0;
+                t_d = 2, t_blk = v & ((1u << a.s0) - 1), t_row = lm / TL;
+                t_limb = (t_row * 3 + 2) * M_ + lm % TL;
+            }
             t_d = __builtin_amdgcn_readfirstlane(t_d), t_row = __builtin_amdgcn_readfirstlane(t_row);
             t_blk = __builtin_amdgcn_readfirstlane(t_blk), t_limb = __builtin_amdgcn_readfirstlane(t_limb);
         }

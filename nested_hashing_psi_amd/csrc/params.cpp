@@ -201,6 +201,7 @@ std::string HostParams::init(u32 N_, u32 L_, u64 t_, const u64 *q, const u64 *p)
         dc.P_modq[i] = prod_mod(P, Lp, -1, qi);
         dc.P_modq_sh[i] = shoup(dc.P_modq[i], qi);
         dc.tPinv_modq[i] = mm(t % qi, invmod(dc.P_modq[i], qi), qi);
+        dc.tPinv_modq_sh[i] = shoup(dc.tPinv_modq[i], qi);
         for (u32 j = 0; j < Lp; j++) {
             const u64 pj = P[j];
             dc.qhat_modp[i][j] = prod_mod(Q, L, (int)i, pj);

@@ -36,6 +36,7 @@ struct DevConsts {
     u64 qp_hat_inv[16];       // [(QP/m)^-1]_m   (only the P entries are used)
     u64 qp_hat_inv_sh[16];
     u64 tPinv_modq[8];        // [t P^-1]_{q_k}
+    u64 tPinv_modq_sh[8];
     u64 tQ_modp[8];           // [tQ]_{p_j}
     u64 tQ_modp_sh[8];
     u64 tQF_modq[8][8];       // [j][k]  [floor(tQ/p_j)]_{q_k}

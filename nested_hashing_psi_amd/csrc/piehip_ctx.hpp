@@ -278,7 +278,8 @@ void ntt(piehip_ctx *h, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool
          const NttExtra *ex = nullptr);
 // lane: w.d01, the digits, key and mask are lane-ordered (and folded) where the context has a lane order; out is in standard order
 void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u64 *mask, u64 *out, bool lane = false,
-                       size_t key_stride = 0, u32 key_group = 1, bool out_is_result = false, bool digits_ready = false);
+                       size_t key_stride = 0, u32 key_group = 1, bool out_is_result = false, bool digits_ready = false,
+                       bool d01_eval_q = false);
 void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
                  const u64 *mask, u64 *out, bool xq_ready = false, bool out_is_result = false);
 int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out);

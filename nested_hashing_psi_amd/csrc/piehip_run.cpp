@@ -1,5 +1,7 @@
 // piehip_run.cpp -- the launch schedule of BatchedFHEHIPPIE::run() (reference BatchedFHEHIPPIE.cpp:88-129) on the handle's queues:
 // the schedule pieces of a ciphertext multiplication, the queues of a run and the bin layers each takes, piehip_run_into.
+#include <cassert>
+
 #include "piehip_ctx.hpp"
 
 using namespace piehip;
@@ -16,8 +18,9 @@ void ntt(piehip_ctx *h, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool
 
 // BV key switch of the COEFFICIENT-format polynomials at w.d2c with `key`, added to the EVALUATION
 // ciphertexts at w.d01, optionally multiplied by mask plaintexts: out[nb][2][L][N]
+// d01_eval_q (enqueue_mul only, plan.d01_eval_q): w.d01 lacks the own-limb term of scale-and-round; the MAC adds it from the QP operands at w.eqp
 void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u64 *mask, u64 *out, bool lane, size_t key_stride,
-                       u32 key_group, bool out_is_result, bool digits_ready)
+                       u32 key_group, bool out_is_result, bool digits_ready, bool d01_eval_q)
 {
     const NttPlan &pl = h->plan;
     const u32 N = h->hp.N, L = h->hp.L;
@@ -43,9 +46,12 @@ void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u6
             h->chain_armed = false;
             (void)hipEventRecord(h->ev_chain, h->stream);
         }
-        ProfScope ps(h, PIEHIP_K_RELIN, W * (nb * ((double)L * L + 2 * L + 2 * L + (mask ? L : 0)) + 2.0 * L * L));
+        assert(!d01_eval_q || (pl.d01_eval_q && lane));
+        ProfScope ps(h, PIEHIP_K_RELIN,
+                     W * (nb * ((double)L * L + 2 * L + 2 * L + (mask ? L : 0) + (d01_eval_q ? 4 * L : 0)) + 2.0 * L * L));
         launch_relin_mac(h->d_dc, N, L, w.d01, 2 * LN, w.dig, key, mask, out, nb, h->stream, pl.small_moduli,
-                         lane ? h->d_sigma_inv : nullptr, key_stride, key_group, lane ? pl.lane_T : 0, pl.lane_kp, mask ? h->mask_div : 1);
+                         lane ? h->d_sigma_inv : nullptr, key_stride, key_group, lane ? pl.lane_T : 0, pl.lane_kp, mask ? h->mask_div : 1,
+                         d01_eval_q ? w.eqp : nullptr, h->hp.M);
     }
 }
 
@@ -90,9 +96,13 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
     }
     // Tensor product and inverse transform of its result.  One launch where the plan allows: each item forms its input from the four
     // operands in its load phase, the tensor result is neither written nor read back (3 M limbs per row each way).
+    // A relinearising product needs d0 and d1 back in EVALUATION form, and their Q limbs enter scale-and-round only as the own-limb term
+    // c_k d_k: where the plan says so those 2 L limbs per row are neither inverse-transformed here nor read by scale-and-round, and the
+    // key-switch MAC adds c_k (a (x) b)_k from the QP operands.  d2 keeps every limb: the digit lift wants coefficients.
+    const bool eval_q = relin && pl.d01_eval_q;
     if (pl.fused_tensor) {
-        ProfScope ps(h, PIEHIP_K_TENSOR_NTT_INV, W * nb * 7.0 * M);
-        launch_ntt16_tensor(pl, w.eqp, w.dqp, nb, M, h->stream);
+        ProfScope ps(h, PIEHIP_K_TENSOR_NTT_INV, W * nb * 7.0 * M);  // (the tensor product's bytes, whichever limbs are transformed)
+        launch_ntt16_tensor(pl, w.eqp, w.dqp, nb, M, h->stream, eval_q ? L : 0);
     } else {
         {
             ProfScope ps(h, PIEHIP_K_TENSOR, W * nb * 7.0 * M);
@@ -103,7 +113,7 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
     if (relin) {
         {
             ProfScope ps(h, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, h->stream, pl.small_moduli, pl.fold, false);
+            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, h->stream, pl.small_moduli, pl.fold, false, eval_q);
         }
         NttExtra ex;
         ex.lazy_out = true;  // the key-switch MAC adds d01 into its accumulator before reducing
@@ -116,7 +126,7 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
             ntt(h, w.d01, nb * 2 * L, 0, L, false, true, true, &ex);
         }
         const RunKey k = run_key(h);
-        enqueue_keyswitch(h, w, nb, k.key, mask, out, true, k.stride, k.group, out_is_result, pl.digits_with_d01);
+        enqueue_keyswitch(h, w, nb, k.key, mask, out, true, k.stride, k.group, out_is_result, pl.digits_with_d01, eval_q);
     } else {
         {
             ProfScope ps(h, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
