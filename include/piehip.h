@@ -356,6 +356,79 @@ int piehip_mod_reduce(piehip_handle h, const uint64_t *in /*[nct][2][L][N]*/, ui
 int piehip_set_result_limbs(piehip_handle h, uint32_t keep);
 int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
 
+/* ---- query slices: stage A sharded by inner hash function and limb --------------------------------------
+ * The reference evaluates, per bin layer, K inner products over E index ciphertexts (BatchedFHEHIPPIE.cpp:96-116) and then multiplies
+ * the K accumulators together (.cpp:117-126).  Every RNS limb of an inner product depends on that limb of its operands only, so the
+ * first half shards by what the QUERY is made of.  A unit u = h L + l, 0 <= u < K L, is limb l = u % L (modulus q_l) of inner hash
+ * function h = u / L.  A query-sliced handle has two sides:
+ *   the slice side (.cpp:96-116)   a contiguous unit range [u_lo, u_hi), u_n = u_hi - u_lo: those limbs of the packed database for ALL
+ *                                  b bin layers ([u_n][b][E][N] words, 1 / (K L) of the database per unit), those limbs of every
+ *                                  query's index ciphertexts and minus element, and -- piehip_run_slice -- those limbs of every
+ *                                  accumulator, acc_slice[b][nq][u_n][2][N] (EVALUATION format, canonical residues)
+ *   the chain side (.cpp:117-126)  the bin layers [bin_lo, bin_hi) of b, as a piehip_load_db_table_bins handle has them: their masks, a
+ *                                  run() workspace, the EvalMult key(s).  piehip_put_accumulators(_from) places the limbs that arrive
+ *                                  from the slice sides; piehip_run_chain runs everything of run() behind stage A.
+ * G handles whose unit ranges tile [0, K L) and whose bin ranges tile [0, b) evaluate a query together; each is sent u_n / (K L) of it.
+ * The results are, word for word, those of piehip_run on unsliced handles.  Either range may be empty (a handle that only computes
+ * units, or only runs chains; G > K L and G > b are legal).
+ *   piehip_query_slice            (.cpp:96-116; host only) the units of rank `rank` of nranks: [K L rank / nranks, K L (rank + 1) / nranks),
+ *                                 the rule of piehip_rccl_bin_slice
+ *   piehip_load_db_table_sliced   (.cpp:45-82 for the slice side, the masks of :77-81 for the chain side) the table is shuffled whole with
+ *                                 shuffle_seed -- the database of piehip_load_db_table with the same seeds -- and the handle gathers and
+ *                                 encodes only its units' limbs (the forward transform runs for those limbs only); the masks of its bin
+ *                                 layers are the ones the unsharded call draws.  Refuses K = 1 as every hashing entry point does.
+ *                                 Synchronous, on the handle's stream.
+ *   piehip_load_db_sliced         the same from arrays: pts_slice[u_n][b][E][N] (unit u: limb u % L of pts[u / L][.][.] of piehip_load_db),
+ *                                 masks[bin_hi - bin_lo][L][N].  Any K >= 1.  Synchronous.
+ *   piehip_get_query_slice        the four bounds of a sliced handle
+ *   piehip_set_index_slice_q      (.hpp:40-43) query q's index slice, host memory: idx_slice[u_n][E][2][N]; synchronous
+ *   piehip_set_minus_slice_q      (.hpp:45-48) ... minus slice [u_n][2][N]: limb u % L of the minus element for every unit
+ *   piehip_set_*_slice_from_q     the same cut out of the WHOLE input in host memory (idx[K][E][2][L][N], minus[2][L][N]): one strided
+ *                                 copy per unit; only the handle's units cross the link
+ *   piehip_set_*_slice_device_q   arrays in HBM, no copy taken; ordered as piehip_set_index_device is (written on the handle's stream, or complete)
+ *                                 piehip_set_query_batch sizes everything for nq queries, as on any handle
+ *   piehip_run_slice              (.cpp:96-116) stage A of the handle's units, all b layers, all nq queries, into the handle's acc_slice: one
+ *                                 launch per group of one to four queries.  Asynchronous, on the handle's stream (not behind the queues of
+ *                                 an earlier piehip_run_chain: it touches none of their buffers)
+ *   piehip_slice_accumulators_device   device address of acc_slice (valid until the slice or the batch size changes)
+ *   piehip_get_slice_accumulators acc_slice to host memory (tests); synchronous
+ *   piehip_put_accumulators       (.cpp:117: the accumulators as the chain reads them) rows [bin_lo, bin_hi) of d_src[b][nq][u_hi - u_lo][2][N]
+ *                                 -- units [u_lo, u_hi) of ALL b layers, 16-byte aligned, readable by h's device -- into h's accumulators.
+ *                                 One launch on h's stream, behind the queues of h's last run_chain; the caller orders the writer of d_src
+ *                                 before it.  Where the context hands operand X of the first product to the chain in lane order (batches
+ *                                 on rings from 8192), the units of inner hash function 0 land where the unsliced stage A puts them.
+ *   piehip_put_accumulators_from  the same from a sliced handle `src` of this process (its acc_slice and unit range): h's stream waits for
+ *                                 what src's stream holds at the call (its piehip_run_slice), and src's stream waits for the placement
+ *                                 before anything queued on it later.  Same device, or another with peer access enabled
+ *   piehip_run_chain(_into)       (.cpp:117-126) everything of run() behind stage A for the handle's bin layers -- transforms, product chain,
+ *                                 key switch with the mask multiply (K = 1: the mask multiply), the result-limb reduction, both queues,
+ *                                 per-query keys -- with the result rows, result buffer and stream order of piehip_run(_into) on a
+ *                                 piehip_load_db_table_bins(bin_lo, bin_hi) handle.  No bin layers: nothing is launched
+ * PIEHIP_ESTATE: piehip_run_chain unless every unit 0 .. K L - 1 has been put since the last piehip_run_chain or batch-size change; a put
+ * whose range overlaps one already put in this round; piehip_run_slice without its slice inputs; piehip_run(_into / _staged / _host*) and
+ * piehip_set_graph(1) on a sliced handle; piehip_attach_database to or from one; the slice calls on an unsliced handle.  PIEHIP_EINVAL:
+ * ranges outside [0, K L] or [0, b], u_lo > u_hi, bin_lo > bin_hi.  A refused call changes nothing.  Loading a whole database
+ * (piehip_load_db*, piehip_build_db*) makes the handle an unsliced one again. */
+int piehip_query_slice(uint32_t K, uint32_t L, int nranks, int rank, uint32_t *u_lo, uint32_t *u_hi);
+int piehip_load_db_table_sliced(piehip_handle h, const uint64_t *tbl, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
+                                uint64_t shuffle_seed, uint64_t mask_seed, uint32_t u_lo, uint32_t u_hi, uint32_t bin_lo, uint32_t bin_hi);
+int piehip_load_db_sliced(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, uint32_t u_lo, uint32_t u_hi,
+                          const uint64_t *pts_slice /*[u_n][b][E][N]*/, uint32_t bin_lo, uint32_t bin_hi, const uint64_t *masks /*[bin_n][L][N]*/);
+int piehip_get_query_slice(piehip_handle h, uint32_t *u_lo, uint32_t *u_hi, uint32_t *bin_lo, uint32_t *bin_hi);
+int piehip_set_index_slice_q(piehip_handle h, uint32_t q, const uint64_t *idx_slice /*[u_n][E][2][N]*/);
+int piehip_set_minus_slice_q(piehip_handle h, uint32_t q, const uint64_t *minus_slice /*[u_n][2][N]*/);
+int piehip_set_index_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *idx /*[K][E][2][L][N]*/);
+int piehip_set_minus_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *minus /*[2][L][N]*/);
+int piehip_set_index_slice_device_q(piehip_handle h, uint32_t q, const void *d_idx_slice);
+int piehip_set_minus_slice_device_q(piehip_handle h, uint32_t q, const void *d_minus_slice);
+int piehip_run_slice(piehip_handle h);
+int piehip_slice_accumulators_device(piehip_handle h, void **d_acc_slice);
+int piehip_get_slice_accumulators(piehip_handle h, uint64_t *out /*[b][nq][u_n][2][N]*/);
+int piehip_put_accumulators(piehip_handle h, uint32_t u_lo, uint32_t u_hi, const void *d_src /*[b][nq][u_hi - u_lo][2][N]*/);
+int piehip_put_accumulators_from(piehip_handle h, piehip_handle src);
+int piehip_run_chain(piehip_handle h);
+int piehip_run_chain_into(piehip_handle h, void *d_results);
+
 /* ---- FHEHIPPIE: the rotation-based sibling operator ---------------------------------
  * Reference: src/Common/Crypto/PrivateIndexedEqualityCheck/FHEHIPPIE.{hpp,cpp}; one operator per client slot
  * (FHEHIPPIECollection, PIECollection.hpp); `npie` operators are evaluated as one batch here.

@@ -123,6 +123,23 @@ SYMBOLS = {
     "piehip_mod_reduce": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_uint32, u64p]),
     "piehip_set_result_limbs": (C.c_int, [C.c_void_p, C.c_uint32]),
     "piehip_get_result_limbs": (C.c_int, [C.c_void_p, u32p]),
+    "piehip_query_slice": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, u32p, u32p]),
+    "piehip_load_db_table_sliced": (C.c_int, [C.c_void_p, u64p] + [C.c_uint32] * 5 + [C.c_uint64] * 2 + [C.c_uint32] * 4),
+    "piehip_load_db_sliced": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [u64p, C.c_uint32, C.c_uint32, u64p]),
+    "piehip_get_query_slice": (C.c_int, [C.c_void_p, u32p, u32p, u32p, u32p]),
+    "piehip_set_index_slice_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p]),
+    "piehip_set_minus_slice_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p]),
+    "piehip_set_index_slice_from_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p]),
+    "piehip_set_minus_slice_from_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p]),
+    "piehip_set_index_slice_device_q": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "piehip_set_minus_slice_device_q": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "piehip_run_slice": (C.c_int, [C.c_void_p]),
+    "piehip_slice_accumulators_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "piehip_get_slice_accumulators": (C.c_int, [C.c_void_p, u64p]),
+    "piehip_put_accumulators": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "piehip_put_accumulators_from": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "piehip_run_chain": (C.c_int, [C.c_void_p]),
+    "piehip_run_chain_into": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -223,7 +223,23 @@ void launch_permute(u32 N, const u64 *in, const u32 *map, u64 *out, u32 nrows, h
 void launch_encode_scatter(const DevConsts *dc, u32 N, u32 M, const int64_t *slots, u32 B, const u32 *inv_pos, u64 *u,
                            u32 npt, hipStream_t st);
 // coefficients mod t [npt][N] -> centred lift into every q_i: out[npt][L][N]
-void launch_encode_lift(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *u, u64 *out, u32 npt, hipStream_t st);
+// l0 (the query-sliced database: one limb per plaintext): into the L moduli from q_l0 on
+void launch_encode_lift(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *u, u64 *out, u32 npt, hipStream_t st, u32 l0 = 0);
+
+// ---- query-sliced stage A (kernels_slice.hip; include/piehip.h "Query slices") ----------------------------------------------
+// Unit u = h L + l is limb l of inner hash function h; a handle holds the units [u_lo, u_lo + un) as one-limb arrays.
+//   db   [un][b][E][N]                       the database plaintexts' limbs
+//   idx  [un][E][2][N], minus [un][2][N]     per query: the index ciphertexts' and the minus element's limbs
+//   acc  [b][nq][un][2][N]                   = sum_j idx[u][j] (.) db[u][beta][j] + minus[u], canonical, EVALUATION format
+// The arithmetic of launch_stage_a / launch_stage_a_batch (column accumulators where small_moduli, 128-bit otherwise); one launch per
+// group of one to four queries whatever b.
+void launch_stage_a_slice(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, u32 b, u32 E, const StageAQueries &qs, u32 nq,
+                          const u64 *db, u64 *acc, hipStream_t st, bool small_moduli);
+// Placement: the rows of bin layers [bin_lo, bin_lo + bn) of src[b][nq][un][2][N] (units from u_lo) into the chain side's
+// acc[bn][nq][K][2][L][N]; with xo, the units of inner hash function 0 go, lane-ordered, into the Q limbs of the QP operand array
+// instead (where stage A of an unsliced batch puts them: StageAXOut)
+void launch_place_accumulators(u32 N, u32 L, u32 K, u32 u_lo, u32 un, u32 bin_lo, u32 bn, u32 nq, const u64 *src, u64 *acc,
+                               const StageAXOut *xo, hipStream_t st);
 
 // ---- offline phase: nested hashing and database gather on the device (kernels_hash.hip) -----------------------
 size_t hash_sort_temp_bytes(u32 n, u32 e);

@@ -12,6 +12,7 @@
 
 #include "kernels.hpp"
 #include "madasm.h"
+#include "stage_a_common.h"
 
 namespace piehip {
 
@@ -29,26 +30,6 @@ static const u32 TPB = 256;
 // ---------------------------------------------------------------------------------------------
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 
-// Block -> (coefficient block, limb, inner hash function, group of bin layers).  The `groups` blocks of one tile read the same
-// index-ciphertext words (and different database words): they should run on the same XCD, one after the other, so that all
-// but the first take the index words from that XCD's L2.  Workgroups go to the eight XCDs round-robin by their linear id, so
-// a one-dimensional grid is cut as id = 8 * slot + xcd, slot = tile_of_this_xcd * groups + group.  (With the layer group in
-// blockIdx.z the blocks of a tile were `tiles` apart in dispatch order: every group fetched the index matrix from HBM again.)
-struct StageATile {
-    u32 bx, l, hz, grp;
-};
-__device__ __forceinline__ bool stage_a_tile(u32 nx, u32 L, u32 tiles, u32 groups, StageATile &t)
-{
-    const u32 id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    t.grp = slot % groups;
-    const u32 tile = (slot / groups) * 8 + xcd;
-    if (tile >= tiles) return false;
-    t.bx = tile % nx;
-    t.l = (tile / nx) % L;
-    t.hz = tile / (nx * L);
-    return true;
-}
-static dim3 stage_a_grid(u32 nx, u32 L, u32 hn, u32 groups) { return dim3(8 * ((nx * L * hn + 7) / 8) * groups); }
 
 template <int BPT>
 __global__ void __launch_bounds__(TPB) stage_a_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 K, u32 b, u32 E,
@@ -120,36 +101,7 @@ __global__ void __launch_bounds__(TPB) stage_a_kernel(const DevConsts *__restric
 // runs this kernel over a rotation of databases (every launch from HBM): 49 us for the 196 MiB of the headline workload
 // with seven layers per thread (168 registers, three waves per SIMD), the same with 16-byte lanes and one term ahead, 63 us
 // when it is forced to four waves per SIMD (spills) -- and 35 us for a plain read of the same bytes.
-// Lane-ordered home of coefficient n of a limb (ntt16_kernel.h: slices of 2^logns coefficients, T = 2^logns / 16 threads, thread tau
-// holds elements 16 tau .. 16 tau + 15 and stores pair j at 2 (T j + tau)): the offset inside the limb
-__device__ __forceinline__ u32 lane_home(u32 n, u32 logns)
-{
-    const u32 ns = 1u << logns, e = n & (ns - 1);
-    return (n & ~(ns - 1)) + 2 * ((ns >> 4) * ((e >> 1) & 7) + (e >> 4)) + (e & 1);
-}
-
-// a + b mod q for canonical a, b and q < 2^62, without the compare / select pair hipcc makes of addmod(): v_cndmask_b32 on VCC
-// issues at a sixth of the rate of the other vector instructions here (profiles/r03/microbench_operands.txt: 23.7 cycles per
-// wave against 4.2), and the epilogue of stage A has 24 of these sums per thread
-__device__ __forceinline__ u64 addmod_nb(u64 a, u64 b, u64 q)
-{
-    // (as an instruction block: written in C the compiler turns the mask back into a compare and a select)
-    const u64 s = a + b;
-    u32 lo, hi;
-    asm("v_lshl_add_u64 v[60:61], %[x], 0, %[nm]\n\t"  // s - q: negative iff s < q
-        "v_ashrrev_i32 v62, 31, v61\n\t"
-        "v_bfi_b32 %[lo], v62, %[xl], v60\n\t"
-        "v_bfi_b32 %[hi], v62, %[xh], v61"
-        : [lo] "=&v"(lo), [hi] "=&v"(hi)
-        : [x] "v"(s), [xl] "v"((u32)s), [xh] "v"((u32)(s >> 32)), [nm] "s"(0 - q)
-        : "v62", "v60", "v61");
-    return ((u64)hi << 32) | lo;
-}
-
 static const int SA_DEPTH = 4;
-template <bool W124>
-__device__ __forceinline__ u64 colacc_reduce(const ColAcc &a, const Mod &m, u64 nq);  // (instruction block, defined below)
-__device__ __forceinline__ u64 colacc_reduce123_lazy(const ColAcc &a, const Mod &m, u64 nq);
 template <int BPT>
 __global__ void __launch_bounds__(TPB) stage_a_mad_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 K, u32 b, u32 E,
                                                           const u64 *__restrict__ idx, const u64 *__restrict__ minus,
@@ -533,7 +485,6 @@ __device__ __forceinline__ u64 reduce123_u(U128 z, const Mod &m, u64 negq, u64 n
 // canonical result.  Temporaries whose halves are needed live in fixed registers v60-v71 (low enough that scale_round stays at
 // 76 VGPRs = six waves per SIMD: its 5.25 waves per SIMD are then one round; an asm operand cannot name the
 // halves of a 64-bit pair); constants are SGPR operands, one per instruction (constant-bus limit of VOP3 on gfx9).
-#define PIE_ASM_CLOB "vcc", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71"
 // a < 2^63, w < q < 2^60: v[64:65] <- all but the last product of a w mod q + {0..3} q, v[62:63] <- the quotient estimate
 #define PIE_SHOUP63_HEAD                                        \
     "v_mad_u64_u32 v[60:61], vcc, %[al], %[sh], 0\n\t"          \
@@ -623,116 +574,6 @@ __device__ __forceinline__ u64 mulhi_sb(u64 a, u64 b)
         : [r] "=v"(r)
         : [al] "v"((u32)a), [ah] "v"((u32)(a >> 32)), [bl] "s"((u32)b), [bh] "s"((u32)(b >> 32))
         : PIE_ASM_CLOB, "s96", "s97");
-    return r;
-}
-// Column accumulator -> residue in one block (2^59 < q < 2^60).  The columns are carry-normalised (c1' = c1 + (c0 >> 30),
-// c2' = c2 + (c1' >> 30)), after which z >> 59 = (c2' << 1) | bit 29 of c1' and the low word of z is three disjoint bit fields;
-// one-word Barrett as reduce123 / reduce124 of modarith.h (same quotient estimate, same remainder), mulhi as mulhi_sb, the
-// remainder z + qhat (2^64 - q) on one v_mad_u64_u32 chain, sign-mask subtractions.  32 instructions (35 with W124) where the
-// compiler's colacc_value + reduce123 take ~65 (128-bit additions through v_cmp / v_cndmask carries, an 11-instruction mulhi).
-// W124: z < 2^124 (eight products), otherwise z < 2^123 (seven).
-// a three-column accumulator below 2^123 to v[66:67] in [0, 4q) (v60-v71, vcc, s[96:97] as scratch): the body of colacc_reduce<false>
-#define PIE_COLACC123_TO_4Q \
-    "v_lshrrev_b64 v[60:61], 30, %[c0]\n\t" \
-    "v_lshl_add_u64 v[60:61], v[60:61], 0, %[c1]\n\t" \
-    "v_lshrrev_b64 v[62:63], 30, v[60:61]\n\t" \
-    "v_lshl_add_u64 v[62:63], v[62:63], 0, %[c2]\n\t" \
-    "v_lshlrev_b64 v[64:65], 1, v[62:63]\n\t" \
-    "v_bfe_u32 v68, v60, 29, 1\n\t" \
-    "v_and_b32 v66, 0x3fffffff, %[c0l]\n\t" \
-    "v_bfe_u32 v67, v60, 2, 28\n\t" \
-    "v_or_b32 v64, v64, v68\n\t" \
-    "v_lshl_or_b32 v66, v60, 30, v66\n\t" \
-    "v_lshl_or_b32 v67, v62, 28, v67\n\t" \
-    "v_mul_hi_u32 v68, v64, %[mul]\n\t" \
-    "v_mov_b32 v69, 0\n\t" \
-    "v_mad_u64_u32 v[68:69], vcc, v64, %[muh], v[68:69]\n\t" \
-    "v_mad_u64_u32 v[68:69], vcc, v65, %[mul], v[68:69]\n\t" \
-    "v_mad_u64_u32 v[70:71], s[96:97], v65, %[muh], 0\n\t" \
-    "v_lshrrev_b64 v[68:69], 32, v[68:69]\n\t" \
-    "v_addc_co_u32 v69, vcc, 0, v69, vcc\n\t" \
-    "v_lshl_add_u64 v[68:69], v[70:71], 0, v[68:69]\n\t" \
-    "v_mad_u64_u32 v[70:71], vcc, v68, %[nqh], 0\n\t" \
-    "v_mad_u64_u32 v[70:71], vcc, v69, %[nql], v[70:71]\n\t" \
-    "v_add_u32 v67, v67, v70\n\t" \
-    "v_mad_u64_u32 v[66:67], vcc, v68, %[nql], v[66:67]\n\t"
-// ... left there: [0, 4q).  For values that go on into a folded forward transform (fold_store adds a [0, 4q) product to them and the
-// transform takes anything below 8q) or into a Shoup product (any operand below 2^63): eight instructions less than the canonical form
-__device__ __forceinline__ u64 colacc_reduce123_lazy(const ColAcc &a, const Mod &m, u64 nq)
-{
-    const u64 mu = (m.r1 << 59) | (m.r0 >> 5);   // floor(2^123 / q)
-    u64 r;
-    asm(PIE_COLACC123_TO_4Q
-        "v_lshl_add_u64 %[r], v[66:67], 0, 0"
-        : [r] "=v"(r)
-        : [c0] "v"(a.c0), [c1] "v"(a.c1), [c2] "v"(a.c2), [c0l] "v"((u32)a.c0), [mul] "s"((u32)mu), [muh] "s"((u32)(mu >> 32)),
-          [nql] "s"((u32)nq), [nqh] "s"((u32)(nq >> 32))
-        : PIE_ASM_CLOB, "s96", "s97");
-    return r;
-}
-template <bool W124>
-__device__ __forceinline__ u64 colacc_reduce(const ColAcc &a, const Mod &m, u64 nq)
-{
-    const u64 mu = (m.r1 << 59) | (m.r0 >> 5);   // floor(2^123 / q)
-    const u64 n2q = 2 * nq, n4q = 4 * nq;
-    u64 r;
-    if (!W124) {
-        asm(PIE_COLACC123_TO_4Q
-            "v_lshl_add_u64 v[60:61], v[66:67], 0, %[n2q]\n\t"
-            "v_ashrrev_i32 v62, 31, v61\n\t"
-            "v_bfi_b32 v66, v62, v66, v60\n\t"
-            "v_bfi_b32 v67, v62, v67, v61\n\t"
-            "v_lshl_add_u64 v[60:61], v[66:67], 0, %[n1q]\n\t"
-            "v_ashrrev_i32 v62, 31, v61\n\t"
-            "v_and_b32 v64, %[ql], v62\n\t"
-            "v_and_b32 v65, %[qh], v62\n\t"
-            "v_lshl_add_u64 %[r], v[60:61], 0, v[64:65]"
-            : [r] "=v"(r)
-            : [c0] "v"(a.c0), [c1] "v"(a.c1), [c2] "v"(a.c2), [c0l] "v"((u32)a.c0), [mul] "s"((u32)mu), [muh] "s"((u32)(mu >> 32)),
-              [nql] "s"((u32)nq), [nqh] "s"((u32)(nq >> 32)), [n2q] "s"(n2q), [n1q] "s"(nq), [ql] "s"((u32)m.q), [qh] "s"((u32)(m.q >> 32))
-            : PIE_ASM_CLOB, "s96", "s97");
-    } else {
-        // z >> 60 = c2' after the normalisation; qhat = 2 floor(zh mu / 2^64); remainder in [0, 7q): one more subtraction
-        asm("v_lshrrev_b64 v[60:61], 30, %[c0]\n\t"
-            "v_lshl_add_u64 v[60:61], v[60:61], 0, %[c1]\n\t"
-            "v_lshrrev_b64 v[64:65], 30, v[60:61]\n\t"
-            "v_lshl_add_u64 v[64:65], v[64:65], 0, %[c2]\n\t"
-            "v_and_b32 v66, 0x3fffffff, %[c0l]\n\t"
-            "v_bfe_u32 v67, v60, 2, 28\n\t"
-            "v_lshl_or_b32 v66, v60, 30, v66\n\t"
-            "v_lshl_or_b32 v67, v64, 28, v67\n\t"
-            "v_mul_hi_u32 v68, v64, %[mul]\n\t"
-            "v_mov_b32 v69, 0\n\t"
-            "v_mad_u64_u32 v[68:69], vcc, v64, %[muh], v[68:69]\n\t"
-            "v_mad_u64_u32 v[68:69], vcc, v65, %[mul], v[68:69]\n\t"
-            "v_mad_u64_u32 v[70:71], s[96:97], v65, %[muh], 0\n\t"
-            "v_lshrrev_b64 v[68:69], 32, v[68:69]\n\t"
-            "v_addc_co_u32 v69, vcc, 0, v69, vcc\n\t"
-            "v_lshl_add_u64 v[68:69], v[70:71], 0, v[68:69]\n\t"
-            "v_lshlrev_b64 v[68:69], 1, v[68:69]\n\t"
-            "v_mad_u64_u32 v[70:71], vcc, v68, %[nqh], 0\n\t"
-            "v_mad_u64_u32 v[70:71], vcc, v69, %[nql], v[70:71]\n\t"
-            "v_add_u32 v67, v67, v70\n\t"
-            "v_mad_u64_u32 v[66:67], vcc, v68, %[nql], v[66:67]\n\t"
-            "v_lshl_add_u64 v[60:61], v[66:67], 0, %[n4q]\n\t"
-            "v_ashrrev_i32 v62, 31, v61\n\t"
-            "v_bfi_b32 v66, v62, v66, v60\n\t"
-            "v_bfi_b32 v67, v62, v67, v61\n\t"
-            "v_lshl_add_u64 v[60:61], v[66:67], 0, %[n2q]\n\t"
-            "v_ashrrev_i32 v62, 31, v61\n\t"
-            "v_bfi_b32 v66, v62, v66, v60\n\t"
-            "v_bfi_b32 v67, v62, v67, v61\n\t"
-            "v_lshl_add_u64 v[60:61], v[66:67], 0, %[n1q]\n\t"
-            "v_ashrrev_i32 v62, 31, v61\n\t"
-            "v_and_b32 v64, %[ql], v62\n\t"
-            "v_and_b32 v65, %[qh], v62\n\t"
-            "v_lshl_add_u64 %[r], v[60:61], 0, v[64:65]"
-            : [r] "=v"(r)
-            : [c0] "v"(a.c0), [c1] "v"(a.c1), [c2] "v"(a.c2), [c0l] "v"((u32)a.c0), [mul] "s"((u32)mu), [muh] "s"((u32)(mu >> 32)),
-              [nql] "s"((u32)nq), [nqh] "s"((u32)(nq >> 32)), [n4q] "s"(n4q), [n2q] "s"(n2q), [n1q] "s"(nq), [ql] "s"((u32)m.q),
-              [qh] "s"((u32)(m.q >> 32))
-            : PIE_ASM_CLOB, "s96", "s97");
-    }
     return r;
 }
 // a small integer v (< 2^30) times a residue c, into the columns
@@ -1770,19 +1611,19 @@ void launch_encode_scatter(const DevConsts *dc, u32 N, u32 M, const int64_t *slo
     hipLaunchKernelGGL(encode_scatter_kernel, grid, dim3(TPB), 0, st, dc, N, M, slots, B, inv_pos, u);
 }
 __global__ void __launch_bounds__(TPB) encode_lift_kernel(const DevConsts *dc, u32 N, u32 L, u32 M,
-                                                          const u64 *__restrict__ u, u64 *__restrict__ out)
+                                                          const u64 *__restrict__ u, u64 *__restrict__ out, u32 l0)
 {
     const u32 n = blockIdx.x * TPB + threadIdx.x;
     if (n >= N) return;
     const u64 t = dc->mod[M].q;
     const u64 v = u[(size_t)blockIdx.z * N + n];
-    const u64 q = dc->mod[blockIdx.y].q;
+    const u64 q = dc->mod[l0 + blockIdx.y].q;
     out[((size_t)blockIdx.z * L + blockIdx.y) * N + n] = v > t / 2 ? q - (t - v) : v;  // centred lift
 }
-void launch_encode_lift(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *u, u64 *out, u32 npt, hipStream_t st)
+void launch_encode_lift(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *u, u64 *out, u32 npt, hipStream_t st, u32 l0)
 {
     dim3 grid((N + TPB - 1) / TPB, L, npt);
-    hipLaunchKernelGGL(encode_lift_kernel, grid, dim3(TPB), 0, st, dc, N, L, M, u, out);
+    hipLaunchKernelGGL(encode_lift_kernel, grid, dim3(TPB), 0, st, dc, N, L, M, u, out, l0);
 }
 
 }  // namespace piehip

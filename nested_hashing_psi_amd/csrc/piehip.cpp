@@ -11,7 +11,6 @@ static thread_local std::string g_err;
 static const char *KNAMES[PIEHIP_NKERNELS] = {"stage_a_mac", "ntt_fwd", "ntt_inv",  "expand",   "tensor",    "scale_round",
                                               "digits",      "relin",   "mask_mul", "encode",   "automorph", "other",
                                               "event_pair",  "tensor_ntt_inv", "result_ntt_inv", "limb_drop", "result_ntt_fwd"};
-static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
 static void free_workspace(piehip_ctx *h);
 
 namespace piehip {
@@ -286,6 +285,7 @@ int piehip_destroy(piehip_handle h)
     (void)piehip_rccl_destroy(h);
     for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
     detach_database(h);
+    slice_free(h);
     dev_free(&h->d_evk);
     dev_free(&h->d_db);
     dev_free(&h->d_masks);
@@ -396,7 +396,7 @@ int piehip_load_relin_key(piehip_handle h, const uint64_t *evk)
 }
 
 // lane-ordered copy of the mask plaintexts for the fused mask multiply of the last key switch
-static int make_masks_sigma(piehip_ctx *h)
+extern "C++" int piehip::make_masks_sigma(piehip_ctx *h)
 {
     if (!h->plan.lane_order) return PIEHIP_OK;
     if (!h->d_masks_sigma) {  // freed with the run buffers when the shape changes
@@ -441,15 +441,17 @@ static int alloc_workspace(piehip_ctx *h, u32 K, u32 b)
     return ensure_full_rows(h);
 }
 
-static int alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db = true)
+extern "C++" int piehip::alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db)
 {
     drop_graph(h);  // the captured launches hold the addresses and shapes of the buffers below
+    if (with_db) slice_free(h);  // a whole database from here on: no longer a query-sliced handle
     if (h->db_borrowed && with_db) {  // a database of its own from here on; the key goes back too (load it again)
         detach_database(h);
         h->K = h->b = h->E = 0;
     }
     if (K < 1) return fail(PIEHIP_EINVAL, "at least one inner hash function");
-    if (b < 1 || E < 1) return fail(PIEHIP_EINVAL, "Bin size needs to be at least of size one!");
+    // (a query-sliced handle without a chain side keeps no bin layer: piehip_slice.cpp, with_db false)
+    if ((b < 1 && with_db) || E < 1) return fail(PIEHIP_EINVAL, "Bin size needs to be at least of size one!");
     // the database and masks are shared with the attached query slots, whose streams are not ordered against this handle's:
     // rewriting them in place (same shape) would race with their runs, reallocating them would leave them dangling
     if (with_db && h->db_borrowers)
@@ -505,6 +507,7 @@ int piehip_attach_database(piehip_handle h, piehip_handle owner)
 {
     NEED(h);
     if (!owner || owner == h) return fail(PIEHIP_EINVAL, "attach_database: needs another handle");
+    if (h->slice.on || owner->slice.on) return fail(PIEHIP_ESTATE, "attach_database: a query-sliced handle neither lends nor borrows a database");
     if (h->db_borrowers)  // its key and database are in use by the handles attached to it: nothing of them may be freed
         return fail(PIEHIP_ESTATE, "attach_database: other handles are attached to this handle's database (detach or destroy them first)");
     join_pending(owner);
@@ -538,7 +541,7 @@ int piehip_attach_database(piehip_handle h, piehip_handle owner)
 }
 
 // the persistent hash-table buffer [k][e][K][b][E]: reallocated only when the size changes
-static int hash_tbl_alloc(piehip_ctx *h, size_t words)
+extern "C++" int piehip::hash_tbl_alloc(piehip_ctx *h, size_t words)
 {
     if (h->d_hash_tbl && h->hash_tbl_words == words) return PIEHIP_OK;
     dev_free(&h->d_hash_tbl);
@@ -874,7 +877,8 @@ int piehip_set_query_batch(piehip_handle h, uint32_t nq)
     h->evkq_n = h->evkq_loaded = 0;
     h->nq = nq;
     if (!h->K) return PIEHIP_OK;  // the database's arrival sizes the workspace
-    return alloc_workspace(h, h->K, h->b);
+    const int rc = alloc_workspace(h, h->K, h->b);
+    return rc ? rc : slice_batch_changed(h);
 }
 int piehip_get_query_batch(piehip_handle h, uint32_t *nq)
 {

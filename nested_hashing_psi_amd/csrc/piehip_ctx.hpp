@@ -7,6 +7,7 @@
 //   piehip_fhepie.cpp  the rotation-based sibling operator (FHEHIPPIE)
 //   piehip_client.cpp  client-side harness (key generation, encryption, decryption)
 //   piehip_rccl.cpp    the final gather of a sharded server over RCCL
+//   piehip_slice.cpp   query-sliced stage A: a handle's (inner hash function, limb) units, the accumulators' way to the chain side
 #pragma once
 #include "../../include/piehip.h"
 
@@ -83,6 +84,26 @@ struct Query {
     // Index p < K E: index ciphertext p = row E + j; index K E: the minus element.  Staging a piece unseeded clears its entry.
     std::vector<bool> seeded;                      // [K E + 1]
     std::vector<u32> seeds;                        // [K E + 1][8]: the 32-byte seeds as little-endian words
+};
+
+// Query slices (piehip_slice.cpp; include/piehip.h "Query slices").  Unit u = h L + l is limb l of inner hash function h.  The handle
+// holds the units [u_lo, u_hi) of the database for ALL b_total bin layers and computes those limbs of every accumulator (the slice
+// side); it runs the product chain of the bin layers [bin_lo, bin_hi) (the chain side: piehip_ctx::b = bin_hi - bin_lo, masks and
+// workspace as on any handle, no database) on the accumulators piehip_put_accumulators(_from) places there.
+struct SliceState {
+    bool on = false;
+    u32 u_lo = 0, u_hi = 0;
+    u32 bin_lo = 0, bin_hi = 0, b_total = 0;
+    u64 *db = nullptr;    // [u_n][b_total][E][N]: one limb per unit
+    u64 *acc = nullptr;   // [b_total][nq][u_n][2][N]: what piehip_run_slice writes
+    u32 acc_nq = 0;       // the batch size acc was allocated for
+    // slice inputs of every query of the batch: what the next piehip_run_slice reads (the caller's device arrays or the owned copies)
+    const u64 *idx[STAGE_A_MAX_QUERIES] = {}, *minus[STAGE_A_MAX_QUERIES] = {};   // [u_n][E][2][N], [u_n][2][N]
+    u64 *idx_own[STAGE_A_MAX_QUERIES] = {}, *minus_own[STAGE_A_MAX_QUERIES] = {};
+    std::vector<bool> put;             // [K L]: units placed since the last piehip_run_chain or batch-size change
+    hipEvent_t ev_ready = nullptr;     // recorded on this handle's stream for a reader of acc on another stream (piehip_put_accumulators_from),
+    hipEvent_t ev_read = nullptr;      // ... and on this handle's stream behind its own placement launch, for the source to wait on
+    u32 u_n() const { return u_hi - u_lo; }
 };
 
 }  // namespace piehip
@@ -178,6 +199,7 @@ struct piehip_ctx {
     int comm_ranks = 0, comm_rank = 0;
     u64 *d_gather = nullptr, *pin_gather = nullptr;   // the root's gathered result list [b_total][nq][2][L][N]: HBM, page-locked host
     size_t gather_words = 0;
+    piehip::SliceState slice;
     // rotation-based PIE (FHEHIPPIE): rotation keys by index, EVALUATION index maps, packed sub-tables
     std::map<int32_t, u64 *> rotkeys;   // [L][2][L][N] each
     std::map<int32_t, u32 *> rotmaps;   // [N] each
@@ -283,6 +305,18 @@ void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u6
 void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
                  const u64 *mask, u64 *out, bool xq_ready = false, bool out_is_result = false);
 int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out);
+static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
+// piehip.cpp: run() workspace (and, with_db, database and masks) of a handle for b bin layers; the lane-ordered copy of its masks; the
+// persistent hash-table buffer
+int alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db = true);
+int make_masks_sigma(piehip_ctx *h);
+int hash_tbl_alloc(piehip_ctx *h, size_t words);
+// piehip_run.cpp: the queues of piehip_run_into / piehip_run_chain_into; whether stage A hands operand X over in lane order
+int run_on_queues(piehip_ctx *h, void *d_results, bool chain_only);
+bool run_x_direct(const piehip_ctx *h);
+// piehip_slice.cpp
+void slice_free(piehip_ctx *h);          // back to an unsliced handle: the slice side's buffers and state
+int slice_batch_changed(piehip_ctx *h);  // piehip_set_query_batch on a sliced handle: acc for the new batch, nothing put
 // result limbs (piehip_run.cpp): `rows` ciphertexts full[rows][2][L][N] (EVALUATION, standard order; overwritten) reduced to their
 // first `keep` limbs, out[rows][2][keep][N], on the handle's current stream.  out_is_result: out is a run()'s result buffer
 void enqueue_mod_reduce(piehip_ctx *h, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result = false);

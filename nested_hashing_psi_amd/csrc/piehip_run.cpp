@@ -197,6 +197,9 @@ int ensure_run_queues(piehip_ctx *h, u32 ng)
     return PIEHIP_OK;
 }
 
+// stage A of the run being enqueued hands operand X of the first product over in lane order, inside the QP operand array
+bool run_x_direct(const piehip_ctx *h) { return h->K > 1 && h->nq > 1 && h->plan.x_direct; }
+
 // bin layers of queue group g of ng.  Two groups take 4/7 and 3/7 of the layers: measured 3.5 % faster than equal halves at
 // b = 14 (8 + 6: the ragged transform launches of the two queues fit the workgroup slots better than 7 + 7).
 u32 run_group_size(u32 b, u32 ng, u32 g)
@@ -214,28 +217,31 @@ u32 run_group_size(u32 b, u32 ng, u32 g)
 extern "C" {
 
 // Bin layers [b0, b0 + nb) of run() on the handle's current stream: stage A, then the product chain; results[b][nq][2][L][N].
-static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results);
+// chain_only (piehip_run_chain: the accumulators were put there, piehip_put_accumulators): the product chain alone
+static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results, bool chain_only);
+// everything of run() behind stage A for those layers (BatchedFHEHIPPIE.cpp:117-126): both callers above share it
+static void enqueue_chain_bins(piehip_ctx *h, u32 b0, u32 layers, u64 *results);
 // ... and, on a handle that hands its results out on fewer limbs, their reduction: results[b][nq][2][res_limbs][N].  The chain then
 // writes the handle's full-width rows, which no caller reads: what orders a run against the result buffer's readers (and releases
 // the next queue group of a host-results run) moves from the chain's last kernel to the reduction.
-static void enqueue_run_bins(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
+static void enqueue_run_bins(piehip_ctx *h, u32 b0, u32 nb, u64 *results, bool chain_only)
 {
     const u32 keep = h->res_limbs, nq = h->nq;
     if (keep >= h->hp.L) {
-        enqueue_run_bins_full(h, b0, nb, results);
+        enqueue_run_bins_full(h, b0, nb, results, chain_only);
         return;
     }
     const hipEvent_t wait = h->wait_before_results;
     const bool chain = h->chain_armed;
     h->wait_before_results = nullptr;
     h->chain_armed = false;
-    enqueue_run_bins_full(h, b0, nb, h->d_full);
+    enqueue_run_bins_full(h, b0, nb, h->d_full, chain_only);
     h->wait_before_results = wait;
     h->chain_armed = chain;
     const size_t r0 = (size_t)b0 * nq;
     enqueue_mod_reduce(h, h->d_full + r0 * 2 * h->LN(), nb * nq, keep, results + r0 * h->res_ct_words(), true);
 }
-static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
+static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results, bool chain_only)
 {
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M, K = h->K, b = h->b, E = h->E, nq = h->nq;
     const size_t LN = h->LN();
@@ -244,6 +250,41 @@ static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
     const size_t r0 = (size_t)b0 * nq;
     const u32 layers = nb;
     nb *= nq;
+    u64 *acc = h->d_acc + r0 * K * 2 * LN;
+    // Operand X of the first ciphertext product (the accumulators of inner hash function 0) is needed twice: in COEFFICIENT
+    // form by the base extension, and in EVALUATION form, lane-ordered, as the Q limbs of the QP operand (plan.xq_reuse).  Until r04
+    // the inverse transform wrote that second copy; now stage A writes X there in the first place and the transform reads it
+    // from there (out of place, lane order in: its fast path) -- 44 MB less per step at the headline shape: the inverse launches
+    // 161 -> 150 us per step of three queries, stage A + 2.5 (its X rows leave in 64-byte runs) and the base extension + 2.5.
+    // Query batches only: one query's transform launches are single partial rounds that gain 1 us, and its stage A kernel, which
+    // runs at the HBM rate, loses 2.5 (profiles/r04/stage_a_writes_x_lane_ordered.txt).
+    const bool x_direct = run_x_direct(h);
+    if (h->profiling) {  // an empty bracket: what the event pair itself costs on this stream (reported beside the kernels' times)
+        ProfScope ps(h, PIEHIP_K_EVENT_PAIR, 0.0);
+    }
+    if (!chain_only) {   // stage A: all inner products of these bin layers in one launch (BatchedFHEHIPPIE.cpp:101-116)
+        ProfScope ps(h, PIEHIP_K_STAGE_A, W * ((double)layers * K * E * L + nq * ((double)K * E * 2 * L + 2.0 * L + (double)layers * K * 2 * L)));
+        StageAQueries qs = {};
+        for (u32 q = 0; q < nq; q++) qs.idx[q] = h->query[q].idx, qs.minus[q] = h->query[q].minus;
+        const u64 *db = h->d_db + (size_t)b0 * E * LN;
+        StageAXOut xo;
+        if (x_direct) xo.out = h->ws.eqp + r0 * 4 * M * N, xo.M = M, xo.logns = h->plan.lane_logn;
+        if (nq > 1) {
+            launch_stage_a_batch(h->d_dc, N, L, K, layers, E, qs, nq, db, acc, h->stream, h->plan.small_moduli, b, 0, 0, x_direct ? &xo : nullptr);
+        } else {
+            launch_stage_a(h->d_dc, N, L, K, nb, E, qs.idx[0], qs.minus[0], db, acc, h->stream, h->plan.small_moduli, b, 0, 0, 1, 0,
+                           x_direct ? &xo : nullptr);
+        }
+    }
+    enqueue_chain_bins(h, b0, layers, results);
+}
+static void enqueue_chain_bins(piehip_ctx *h, u32 b0, u32 layers, u64 *results)
+{
+    const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M, K = h->K, nq = h->nq;
+    const size_t LN = h->LN();
+    const double W = 8.0 * N;
+    const size_t r0 = (size_t)b0 * nq;
+    const u32 nb = layers * nq;
     MulWs w = h->ws;  // view of the workspace rows of these bin layers
     w.nb = nb;
     w.eqp += r0 * 4 * M * N;
@@ -261,31 +302,7 @@ static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results)
     } mask_div_scope{h};
     h->mask_div = nq;
     h->key_group = (nq > 1 && h->d_evkq && h->evkq_n == nq) ? nq : 1;  // per-query EvalMult keys: row r of a group is query r % nq
-    // Operand X of the first ciphertext product (the accumulators of inner hash function 0) is needed twice: in COEFFICIENT
-    // form by the base extension, and in EVALUATION form, lane-ordered, as the Q limbs of the QP operand (plan.xq_reuse).  Until r04
-    // the inverse transform wrote that second copy; now stage A writes X there in the first place and the transform reads it
-    // from there (out of place, lane order in: its fast path) -- 44 MB less per step at the headline shape: the inverse launches
-    // 161 -> 150 us per step of three queries, stage A + 2.5 (its X rows leave in 64-byte runs) and the base extension + 2.5.
-    // Query batches only: one query's transform launches are single partial rounds that gain 1 us, and its stage A kernel, which
-    // runs at the HBM rate, loses 2.5 (profiles/r04/stage_a_writes_x_lane_ordered.txt).
-    const bool x_direct = K > 1 && nq > 1 && h->plan.x_direct;
-    if (h->profiling) {  // an empty bracket: what the event pair itself costs on this stream (reported beside the kernels' times)
-        ProfScope ps(h, PIEHIP_K_EVENT_PAIR, 0.0);
-    }
-    {   // stage A: all inner products of these bin layers in one launch (BatchedFHEHIPPIE.cpp:101-116)
-        ProfScope ps(h, PIEHIP_K_STAGE_A, W * ((double)layers * K * E * L + nq * ((double)K * E * 2 * L + 2.0 * L + (double)layers * K * 2 * L)));
-        StageAQueries qs = {};
-        for (u32 q = 0; q < nq; q++) qs.idx[q] = h->query[q].idx, qs.minus[q] = h->query[q].minus;
-        const u64 *db = h->d_db + (size_t)b0 * E * LN;
-        StageAXOut xo;
-        if (x_direct) xo.out = w.eqp, xo.M = M, xo.logns = h->plan.lane_logn;
-        if (nq > 1) {
-            launch_stage_a_batch(h->d_dc, N, L, K, layers, E, qs, nq, db, acc, h->stream, h->plan.small_moduli, b, 0, 0, x_direct ? &xo : nullptr);
-        } else {
-            launch_stage_a(h->d_dc, N, L, K, nb, E, qs.idx[0], qs.minus[0], db, acc, h->stream, h->plan.small_moduli, b, 0, 0, 1, 0,
-                           x_direct ? &xo : nullptr);
-        }
-    }
+    const bool x_direct = run_x_direct(h);
     if (K == 1) {
         // one inner hash function: multipliedResult is the inner product itself (BatchedFHEHIPPIE.cpp:117-120), so run() is
         // stage A and the mask multiply (:126) -- no ciphertext product, no transform, no key
@@ -329,15 +346,19 @@ static hipError_t download_rows(piehip_ctx *h, const u64 *d_results, u32 b0, u32
                           hipMemcpyDeviceToHost, h->stream);
 }
 
-int piehip_run_into(piehip_handle h, void *d_results)
+}  // extern C
+
+// piehip_run_into, and piehip_run_chain_into (chain_only: piehip_slice.cpp has checked what that call needs): the queues of a run
+int piehip::run_on_queues(piehip_ctx *h, void *d_results, bool chain_only)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
     if (!d_results) return fail(PIEHIP_EINVAL, "null result buffer");
-    if (!h->K || !h->d_db) return fail(PIEHIP_ESTATE, "run: database not loaded");
+    if (!chain_only && h->slice.on) return fail(PIEHIP_ESTATE, "run: a query-sliced handle holds no whole database (piehip_run_slice / piehip_run_chain)");
+    if (!h->K || (!chain_only && !h->d_db)) return fail(PIEHIP_ESTATE, "run: database not loaded");
     if (!h->d_acc || !h->ws.eqp) return fail(PIEHIP_ESTATE, "run: no workspace (an earlier allocation failed: piehip_set_query_batch / load)");
     if (!run_keys_loaded(h)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
     if (h->res_limbs < h->hp.L && !h->d_full) return fail(PIEHIP_ESTATE, "run: no rows for the result reduction (an earlier allocation failed: piehip_set_result_limbs)");
-    for (u32 q = 0; q < h->nq; q++) {
+    for (u32 q = 0; q < h->nq && !chain_only; q++) {
         if (h->query[q].idx && h->query[q].minus) continue;
         if (q) return fail(PIEHIP_ESTATE, "run: a query of the batch has no index matrix or minus element");
         return fail(PIEHIP_ESTATE, "run: setIndex / setMinusCompareElement not called");
@@ -381,14 +402,14 @@ int piehip_run_into(piehip_handle h, void *d_results)
                     const u32 nb = run_group_size(b, ng, g);
                     ce = hipStreamWaitEvent(h->side_streams[g], h->ev_fork, 0);
                     h->stream = h->side_streams[g];
-                    enqueue_run_bins(h, b0, nb, (u64 *)d_results);
+                    enqueue_run_bins(h, b0, nb, (u64 *)d_results, chain_only);
                     if (ce == hipSuccess) ce = hipEventRecord(h->ev_join[g], h->side_streams[g]);
                     if (ce == hipSuccess) ce = hipStreamWaitEvent(restore.s, h->ev_join[g], 0);
                     b0 += nb;
                 }
                 h->stream = restore.s;
             } else {
-                enqueue_run_bins(h, 0, b, (u64 *)d_results);
+                enqueue_run_bins(h, 0, b, (u64 *)d_results, chain_only);
             }
             const hipError_t ee = hipStreamEndCapture(restore.s, &graph);
             if (ce != hipSuccess || ee != hipSuccess || !graph) {
@@ -435,7 +456,7 @@ int piehip_run_into(piehip_handle h, void *d_results)
                 if (!h->ev_chain) HIPCHK(hipEventCreateWithFlags(&h->ev_chain, hipEventDisableTiming));
                 h->chain_armed = true;
             }
-            enqueue_run_bins(h, b0, nb, (u64 *)d_results);
+            enqueue_run_bins(h, b0, nb, (u64 *)d_results, chain_only);
             if (h->chain_armed) {  // a chain without a key switch (K = 1): behind all of it
                 h->chain_armed = false;
                 HIPCHK(hipEventRecord(h->ev_chain, h->side_streams[g]));
@@ -448,13 +469,17 @@ int piehip_run_into(piehip_handle h, void *d_results)
         h->inputs_dirty = false;
     } else {
         join_pending(h);
-        enqueue_run_bins(h, 0, b, (u64 *)d_results);
+        enqueue_run_bins(h, 0, b, (u64 *)d_results, chain_only);
         if (h->host_results) HIPCHK(download_rows(h, (const u64 *)d_results, 0, b));
         mark_dirty(h);  // the workspace is now in use on the handle's stream: the queues of a later multi-queue run wait for it
     }
     HIPCHK(hipGetLastError());
     return PIEHIP_OK;
 }
+
+extern "C" {
+
+int piehip_run_into(piehip_handle h, void *d_results) { return run_on_queues(h, d_results, false); }
 
 int piehip_run(piehip_handle h)
 {
@@ -474,6 +499,7 @@ int piehip_set_graph(piehip_handle h, int on)
     NEED_RO(h);
     if (on && h->res_limbs < h->hp.L)
         return fail(PIEHIP_ESTATE, "set_graph: the captured graph hands out full results (piehip_set_result_limbs is below L)");
+    if (on && h->slice.on) return fail(PIEHIP_ESTATE, "set_graph: a query-sliced handle runs in two halves (piehip_run_slice, piehip_run_chain): no captured graph");
     h->use_graph = on != 0;
     if (!on) drop_graph(h);
     return PIEHIP_OK;

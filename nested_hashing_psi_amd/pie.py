@@ -645,6 +645,140 @@ class BatchedFHEHIPPIE:
         return p.value
 
 
+def query_slice(K, L, nranks, rank):
+    """the units [u_lo, u_hi) of rank `rank` of `nranks` (piehip_query_slice)"""
+    lo, hi = C.c_uint32(), C.c_uint32()
+    _check(lib().piehip_query_slice(int(K), int(L), int(nranks), int(rank), C.byref(lo), C.byref(hi)))
+    return lo.value, hi.value
+
+
+class QuerySlicedBatchedFHEHIPPIE:
+    """The reference operator's shape (BatchedFHEHIPPIE.hpp:18-49) over G handles of ONE process -- one per device, or several on
+    one device -- with stage A sharded by what the query is made of (include/piehip.h "Query slices").  Handle g holds query slice g
+    (the units piehip_query_slice gives rank g of G) of the database for all bin layers, and bin slice g (shard.bin_slice) of the
+    product chain.  setIndex / setMinusCompareElement take the whole query in host memory and upload to every handle only its
+    units; run() is run_slice on every handle, the G x G placements, run_chain on every handle; getResultList is in bin order.
+
+    contexts: the G PieContexts (same parameters; each holds the EvalMult key(s) when it has bin layers).  The database comes as a
+    hash table [k][e][K][b][E] with explicit seeds (every handle shuffles the whole table), or as EVALUATION limbs (vectorizedHCT
+    [K][b][E][L][N], preCalcRandomMask [b][L][N]: the form that allows K = 1)."""
+
+    def __init__(self, contexts, hashTable=None, shuffle_seed=None, mask_seed=None, vectorizedHCT=None, preCalcRandomMask=None,
+                 serverStashSize=0, simpleMultiTables=True, cuckooMultiTables=True, unitSlices=None, binSlices=None):
+        from . import shard
+        if serverStashSize != 0:
+            raise ValueError("Error, batched FHE PIE does not support a stash (yet).")
+        if not simpleMultiTables or not cuckooMultiTables:
+            raise ValueError("Error, batched FHE PIE currently does not support combined tables.")
+        self.ccs = list(contexts)
+        if not self.ccs:
+            raise ValueError("at least one context")
+        c0 = self.ccs[0]
+        if any(c.N != c0.N or c.L != c0.L or c.t != c0.t or (c.moduli != c0.moduli).any() for c in self.ccs):
+            raise ValueError("contexts of a query-sliced operator must share their parameters")
+        G, L, N = len(self.ccs), c0.L, c0.N
+        if hashTable is not None:
+            if shuffle_seed is None or mask_seed is None:
+                raise ValueError("a query-sliced database needs explicit shuffle / mask seeds, identical on every handle")
+            tbl, tp = _u64(hashTable)
+            k, e, self.K, self.b, self.E = tbl.shape
+        else:
+            db, _ = _u64(vectorizedHCT)
+            mk, _ = _u64(preCalcRandomMask)
+            self.K, self.b, self.E = db.shape[:3]
+            if db.shape[3:] != (L, N) or mk.shape != (self.b, L, N):
+                raise ValueError("database shape does not match the crypto context")
+        K, b, E = self.K, self.b, self.E
+        self.unitSlices = list(unitSlices) if unitSlices is not None else [shard.query_slice(K, L, G, g) for g in range(G)]
+        self.binSlices = list(binSlices) if binSlices is not None else [shard.bin_slice(b, g, G) for g in range(G)]
+        for g, cc in enumerate(self.ccs):
+            (ul, uh), (bl, bh) = self.unitSlices[g], self.binSlices[g]
+            if hashTable is not None:
+                _check(lib().piehip_load_db_table_sliced(cc._h, tp, k, e, K, b, E, int(shuffle_seed), int(mask_seed), ul, uh, bl, bh))
+            else:
+                # unit u: limb u % L of the plaintexts of inner hash function u // L
+                sl = np.ascontiguousarray(np.stack([db[u // L, :, :, u % L] for u in range(ul, uh)]) if uh > ul
+                                          else np.zeros((0, b, E, N), dtype=np.uint64))
+                ms = np.ascontiguousarray(mk[bl:bh])
+                _check(lib().piehip_load_db_sliced(cc._h, K, b, E, ul, uh, sl.ctypes.data_as(u64p), bl, bh, ms.ctypes.data_as(u64p)))
+        self._nq = 1
+        self._bytes = [[0, 0] for _ in range(G)]   # per handle: index bytes, minus bytes of the last query set
+
+    def setQueryBatch(self, nq):
+        for cc in self.ccs:
+            _check(lib().piehip_set_query_batch(cc._h, int(nq)))
+        self._nq = int(nq)
+
+    @property
+    def nq(self):
+        return self._nq
+
+    def setResultLimbs(self, keep):
+        for cc in self.ccs:
+            _check(lib().piehip_set_result_limbs(cc._h, int(keep)))
+
+    def setIndex(self, indexMatrix, query=0):
+        a, ap = _u64(indexMatrix)
+        c0 = self.ccs[0]
+        if a.shape != (self.K, self.E, 2, c0.L, c0.N):
+            raise ValueError("index matrix must be [K][E] ciphertexts")
+        for g, cc in enumerate(self.ccs):
+            _check(lib().piehip_set_index_slice_from_q(cc._h, query, ap))
+            ul, uh = self.unitSlices[g]
+            self._bytes[g][0] = (uh - ul) * self.E * 2 * c0.N * 8
+
+    def setMinusCompareElement(self, minusCompareElement, query=0):
+        a, ap = _u64(minusCompareElement)
+        c0 = self.ccs[0]
+        if a.shape != (2, c0.L, c0.N):
+            raise ValueError("minus element must be one ciphertext")
+        for g, cc in enumerate(self.ccs):
+            _check(lib().piehip_set_minus_slice_from_q(cc._h, query, ap))
+            ul, uh = self.unitSlices[g]
+            self._bytes[g][1] = (uh - ul) * 2 * c0.N * 8
+
+    def uploadedBytes(self):
+        """per handle: the bytes of the last query set (index matrix + minus element) that went up to it: u_n / (K L) of the index matrix and, per unit, its limb of the minus element"""
+        return [i + m for i, m in self._bytes]
+
+    def run(self, sync=True, putOrder=None):
+        """BatchedFHEHIPPIE.cpp:88-129: :96-116 on the slice sides, the accumulators' way across, :117-126 on the chain sides.
+        putOrder (tests): the (destination, source) pairs in another order than destination-major"""
+        G = len(self.ccs)
+        for cc in self.ccs:
+            _check(lib().piehip_run_slice(cc._h))
+        pairs = putOrder if putOrder is not None else [(d, s) for d in range(G) for s in range(G)]
+        for d, s in pairs:
+            _check(lib().piehip_put_accumulators_from(self.ccs[d]._h, self.ccs[s]._h))
+        for cc in self.ccs:
+            _check(lib().piehip_run_chain(cc._h))
+        if sync:
+            for cc in self.ccs:
+                _check(lib().piehip_sync(cc._h))
+
+    def sliceAccumulators(self, g):
+        """handle g's acc_slice [b][nq][u_n][2][N] (tests)"""
+        ul, uh = self.unitSlices[g]
+        out = np.zeros((self.b, self._nq, uh - ul, 2, self.ccs[0].N), dtype=np.uint64)
+        _check(lib().piehip_get_slice_accumulators(self.ccs[g]._h, out.ctypes.data_as(u64p)))
+        return out
+
+    def getResultList(self):
+        """the b result ciphertexts in bin order: [b][2][keep][N], or [nq][b][2][keep][N] for a batch"""
+        c0 = self.ccs[0]
+        keep = C.c_uint32()
+        _check(lib().piehip_get_result_limbs(c0._h, C.byref(keep)))
+        nq = self._nq
+        out = np.zeros((self.b, nq, 2, keep.value, c0.N), dtype=np.uint64)
+        for g, cc in enumerate(self.ccs):
+            bl, bh = self.binSlices[g]
+            if bh > bl:
+                part = np.zeros((bh - bl, nq, 2, keep.value, c0.N), dtype=np.uint64)
+                _check(lib().piehip_get_results(cc._h, part.ctypes.data_as(u64p)))
+                out[bl:bh] = part
+        return out[:, 0] if nq == 1 else out.transpose(1, 0, 2, 3, 4)
+
+
 class QueryPipeline:
     """Several queries in flight on one database: `depth` query slots, each a context with its own stream and run() workspace,
     all reading slot 0's key and packed database (piehip_attach_database).  submit() hands the next query to the next slot

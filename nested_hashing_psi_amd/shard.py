@@ -23,6 +23,11 @@ def bin_slice(b, rank, world):
     return (b * rank) // world, (b * (rank + 1)) // world
 
 
+def query_slice(K, L, G, r):
+    """[u_lo, u_hi): the (inner hash function, limb) units u = h L + l of rank r of G (piehip_query_slice; empty when G > K L)"""
+    return (K * L * r) // G, (K * L * (r + 1)) // G
+
+
 def max_bins(b, world):
     return -(-b // world)
 
