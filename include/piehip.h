@@ -385,6 +385,18 @@ int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
  *   piehip_set_minus_slice_q      (.hpp:45-48) ... minus slice [u_n][2][N]: limb u % L of the minus element for every unit
  *   piehip_set_*_slice_from_q     the same cut out of the WHOLE input in host memory (idx[K][E][2][L][N], minus[2][L][N]): one strided
  *                                 copy per unit; only the handle's units cross the link
+ *   piehip_set_index_slice_seeded_q   seeded slice inputs ("Seeded ciphertexts"): only the c0 rows cross the link, c0_slice[u_n][E][N] (unit u:
+ *   piehip_set_minus_slice_seeded_q   limb u % L of the c0 halves of inner hash function u / L) and [u_n][N], into the c0 rows of the owned
+ *                                 slice copy.  `seeds` is always the WHOLE query's table, [K][E][32] for the index matrix and [32] for the
+ *                                 minus element: the handle picks the rows of its own units.  Synchronous, as their unseeded siblings;
+ *                                 the seeds are remembered.  The next piehip_run_slice queues ONE limb-selective expansion launch
+ *                                 (kernels_seed.hip), on the handle's stream in front of stage A, for every piece of the batch that was
+ *                                 set seeded since the last piehip_run_slice: row c1 of unit u is limb u % L of the seed's polynomial,
+ *                                 bit for bit.  A piece that is not set again is not expanded again (its c1 is still there).  Setting a
+ *                                 piece through any unseeded or device-pointer setter cancels its pending expansion: an expansion never
+ *                                 writes over an unseeded input (the contract of the host-memory path)
+ *   piehip_set_*_slice_seeded_from_q  the same cut out of the WHOLE c0 arrays in host memory (c0idx[K][E][L][N], c0minus[L][N]): one strided
+ *                                 copy per unit.  Per query a handle receives (E + 1) N 8 bytes per unit: half of the unseeded bytes
  *   piehip_set_*_slice_device_q   arrays in HBM, no copy taken; ordered as piehip_set_index_device is (written on the handle's stream, or complete)
  *                                 piehip_set_query_batch sizes everything for nq queries, as on any handle
  *   piehip_run_slice              (.cpp:96-116) stage A of the handle's units, all b layers, all nq queries, into the handle's acc_slice: one
@@ -407,7 +419,9 @@ int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
  * PIEHIP_ESTATE: piehip_run_chain unless every unit 0 .. K L - 1 has been put since the last piehip_run_chain or batch-size change; a put
  * whose range overlaps one already put in this round; piehip_run_slice without its slice inputs; piehip_run(_into / _staged / _host*) and
  * piehip_set_graph(1) on a sliced handle; piehip_attach_database to or from one; the slice calls on an unsliced handle.  PIEHIP_EINVAL:
- * ranges outside [0, K L] or [0, b], u_lo > u_hi, bin_lo > bin_hi.  A refused call changes nothing.  Loading a whole database
+ * ranges outside [0, K L] or [0, b], u_lo > u_hi, bin_lo > bin_hi.  The slice setters: null input or seeds and q >= nq are PIEHIP_EINVAL, an
+ * unsliced handle PIEHIP_ESTATE, all before anything reaches the device; on a handle without units they return PIEHIP_OK and do nothing.
+ * A refused call changes nothing.  Loading a whole database
  * (piehip_load_db*, piehip_build_db*) makes the handle an unsliced one again. */
 int piehip_query_slice(uint32_t K, uint32_t L, int nranks, int rank, uint32_t *u_lo, uint32_t *u_hi);
 int piehip_load_db_table_sliced(piehip_handle h, const uint64_t *tbl, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
@@ -419,6 +433,10 @@ int piehip_set_index_slice_q(piehip_handle h, uint32_t q, const uint64_t *idx_sl
 int piehip_set_minus_slice_q(piehip_handle h, uint32_t q, const uint64_t *minus_slice /*[u_n][2][N]*/);
 int piehip_set_index_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *idx /*[K][E][2][L][N]*/);
 int piehip_set_minus_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *minus /*[2][L][N]*/);
+int piehip_set_index_slice_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0_slice /*[u_n][E][N]*/, const uint8_t *seeds /*[K][E][32]*/);
+int piehip_set_minus_slice_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0_slice /*[u_n][N]*/, const uint8_t *seed /*[32]*/);
+int piehip_set_index_slice_seeded_from_q(piehip_handle h, uint32_t q, const uint64_t *c0idx /*[K][E][L][N]*/, const uint8_t *seeds /*[K][E][32]*/);
+int piehip_set_minus_slice_seeded_from_q(piehip_handle h, uint32_t q, const uint64_t *c0minus /*[L][N]*/, const uint8_t *seed /*[32]*/);
 int piehip_set_index_slice_device_q(piehip_handle h, uint32_t q, const void *d_idx_slice);
 int piehip_set_minus_slice_device_q(piehip_handle h, uint32_t q, const void *d_minus_slice);
 int piehip_run_slice(piehip_handle h);

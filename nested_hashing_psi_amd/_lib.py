@@ -131,6 +131,10 @@ SYMBOLS = {
     "piehip_set_minus_slice_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p]),
     "piehip_set_index_slice_from_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p]),
     "piehip_set_minus_slice_from_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p]),
+    "piehip_set_index_slice_seeded_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p, u8p]),
+    "piehip_set_minus_slice_seeded_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p, u8p]),
+    "piehip_set_index_slice_seeded_from_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p, u8p]),
+    "piehip_set_minus_slice_seeded_from_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p, u8p]),
     "piehip_set_index_slice_device_q": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "piehip_set_minus_slice_device_q": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "piehip_run_slice": (C.c_int, [C.c_void_p]),

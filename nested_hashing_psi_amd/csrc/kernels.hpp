@@ -270,5 +270,14 @@ struct SeedJob {
 };
 static const u32 SEED_MAX_JOBS_PER_LAUNCH = 65535;
 void launch_expand_uniform(const DevConsts *dc, u32 N, u32 L, const SeedJob *jobs, u32 njobs, hipStream_t st);
+// Limb-selective expansion: job j regenerates limb `limb` of its seed's polynomial -- row `limb` of what a SeedJob writes, bit for
+// bit -- into the one row dst[N] and writes nothing behind it (the c1 rows of a query slice, idx[u_n][E][2][N] and minus[u_n][2][N]:
+// the next row there is the c0 of the next ciphertext).  limb < L; the same job limit per launch.
+struct SeedLimbJob {
+    u64 *dst;      // one row of N words
+    u32 seed[8];
+    u32 limb;
+};
+void launch_expand_uniform_limb(const DevConsts *dc, u32 N, const SeedLimbJob *jobs, u32 njobs, hipStream_t st);
 
 }  // namespace piehip

@@ -107,15 +107,12 @@ __device__ __forceinline__ void keccak_f1600(Lane A[25])
 }
 #undef KECCAK_RHO_PI
 
-// one thread per (job, limb, chunk of ten coefficients); grid (chunks / SEED_TPB, L, jobs).  The job (seed and destination) is
-// uniform over the workgroup: scalar loads.
-__global__ void __launch_bounds__(SEED_TPB) expand_uniform_kernel(const DevConsts *__restrict__ dc, u32 N, const SeedJob *__restrict__ jobs)
+// One chunk: the permutation of the chunk's message and its ten words reduced mod q_l into dst[0 .. 9], as far as they lie below N
+// (the last chunk of a row is partial), dst = job.dst + row + n0.  Both kernels below are this function behind their own indexing
+// and job type; job and l are uniform over the workgroup.
+template <class Job>
+__device__ __forceinline__ void expand_chunk(const DevConsts *__restrict__ dc, const Job &job, u32 l, u32 c, size_t row, u32 n0, u32 N)
 {
-    const u32 c = blockIdx.x * SEED_TPB + threadIdx.x;
-    const u32 n0 = c * 10;
-    if (n0 >= N) return;
-    const u32 l = blockIdx.y;
-    const SeedJob &job = jobs[blockIdx.z];
     const Mod m = dc->mod[l];
     Lane A[25];
 #pragma unroll
@@ -127,12 +124,38 @@ __global__ void __launch_bounds__(SEED_TPB) expand_uniform_kernel(const DevConst
     A[6].lo = 0x1Fu;           // SHAKE domain bits + first pad bit, at byte 48
     A[20].hi = 0x80000000u;    // last pad bit, at byte 167 (end of the 168-byte rate)
     keccak_f1600(A);
-    u64 *dst = job.dst + (size_t)l * N + n0;
+    u64 *dst = job.dst + row + n0;
 #pragma unroll
     for (int t = 0; t < 10; t++) {
         const Lane lo = A[2 * t], hi = A[2 * t + 1];
         if (n0 + t < N) dst[t] = barrett128(((u64)hi.hi << 32) | hi.lo, ((u64)lo.hi << 32) | lo.lo, m);  // the last chunk is partial
     }
+}
+
+// one thread per (job, limb, chunk of ten coefficients); grid (chunks / SEED_TPB, L, jobs).  The job (seed and destination) is
+// uniform over the workgroup: scalar loads.
+__global__ void __launch_bounds__(SEED_TPB) expand_uniform_kernel(const DevConsts *__restrict__ dc, u32 N, const SeedJob *__restrict__ jobs)
+{
+    const u32 c = blockIdx.x * SEED_TPB + threadIdx.x;
+    const u32 n0 = c * 10;
+    if (n0 >= N) return;
+    const u32 l = blockIdx.y;
+    const SeedJob &job = jobs[blockIdx.z];
+    expand_chunk(dc, job, l, c, (size_t)l * N, n0, N);
+}
+
+// Limb-selective expansion (query slices: a slice holds one-limb rows): one thread per (job, chunk); grid (chunks / SEED_TPB, jobs).
+// Job j writes limb job.limb of its seed's polynomial -- the words expand_uniform_kernel writes into row job.limb -- into the ONE
+// row dst[N].  What follows the row is not this polynomial's next limb (in a slice: the c0 row of the next ciphertext), so the
+// partial last chunk's bound in expand_chunk is what keeps live data intact.  The job -- seed, destination, limb and with it the
+// limb's reduction constants -- is uniform over the workgroup: scalar loads.
+__global__ void __launch_bounds__(SEED_TPB) expand_uniform_limb_kernel(const DevConsts *__restrict__ dc, u32 N, const SeedLimbJob *__restrict__ jobs)
+{
+    const u32 c = blockIdx.x * SEED_TPB + threadIdx.x;
+    const u32 n0 = c * 10;
+    if (n0 >= N) return;
+    const SeedLimbJob &job = jobs[blockIdx.y];
+    expand_chunk(dc, job, job.limb, c, 0, n0, N);
 }
 
 void launch_expand_uniform(const DevConsts *dc, u32 N, u32 L, const SeedJob *jobs, u32 njobs, hipStream_t st)
@@ -141,6 +164,15 @@ void launch_expand_uniform(const DevConsts *dc, u32 N, u32 L, const SeedJob *job
     for (u32 j0 = 0; j0 < njobs; j0 += SEED_MAX_JOBS_PER_LAUNCH) {
         const u32 nj = std::min(njobs - j0, SEED_MAX_JOBS_PER_LAUNCH);
         hipLaunchKernelGGL(expand_uniform_kernel, dim3((chunks + SEED_TPB - 1) / SEED_TPB, L, nj), dim3(SEED_TPB), 0, st, dc, N, jobs + j0);
+    }
+}
+
+void launch_expand_uniform_limb(const DevConsts *dc, u32 N, const SeedLimbJob *jobs, u32 njobs, hipStream_t st)
+{
+    const u32 chunks = (N + 9) / 10;
+    for (u32 j0 = 0; j0 < njobs; j0 += SEED_MAX_JOBS_PER_LAUNCH) {
+        const u32 nj = std::min(njobs - j0, SEED_MAX_JOBS_PER_LAUNCH);
+        hipLaunchKernelGGL(expand_uniform_limb_kernel, dim3((chunks + SEED_TPB - 1) / SEED_TPB, nj), dim3(SEED_TPB), 0, st, dc, N, jobs + j0);
     }
 }
 

@@ -145,7 +145,7 @@ static hipError_t upload_table(piehip_ctx *h, const T *src, size_t n, P **dst)
 // =================================================================================================
 extern "C" {
 
-int piehip_version(void) { return 102; }   // 101: piehip_profile_read_n, piehip_set_transform_slots, piehip_upload_turn_wait, piehip_rccl_abort; 102: seeded ciphertexts (the result limbs came without a new number)
+int piehip_version(void) { return 102; }   // 101: piehip_profile_read_n, piehip_set_transform_slots, piehip_upload_turn_wait, piehip_rccl_abort; 102: seeded ciphertexts (the result limbs, the query slices and the seeded query slices came without a new number)
 const char *piehip_last_error(void) { return g_err.c_str(); }
 const char *piehip_kernel_name(int k) { return (k >= 0 && k < PIEHIP_NKERNELS) ? KNAMES[k] : "?"; }
 

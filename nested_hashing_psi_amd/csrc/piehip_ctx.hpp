@@ -100,6 +100,16 @@ struct SliceState {
     // slice inputs of every query of the batch: what the next piehip_run_slice reads (the caller's device arrays or the owned copies)
     const u64 *idx[STAGE_A_MAX_QUERIES] = {}, *minus[STAGE_A_MAX_QUERIES] = {};   // [u_n][E][2][N], [u_n][2][N]
     u64 *idx_own[STAGE_A_MAX_QUERIES] = {}, *minus_own[STAGE_A_MAX_QUERIES] = {};
+    // seeded slice inputs (piehip_set_*_slice_seeded*_q): the c0 rows are in the owned copy, the c1 rows are expanded from the seeds by
+    // the next piehip_run_slice, which clears the mark.  Every other setter of the piece clears it too: nothing is expanded over it.
+    bool idx_seeded[STAGE_A_MAX_QUERIES] = {}, minus_seeded[STAGE_A_MAX_QUERIES] = {};
+    std::vector<u32> seeds[STAGE_A_MAX_QUERIES];   // [K E + 1][8]: the query's seed tables as little-endian words, the minus seed last
+    // the job table of that one expansion launch: written in page-locked memory, copied up on the handle's stream.  ev_jobs is recorded
+    // behind the copy and waited for before the table is written again (piehip_slice.cpp, queue_slice_expansion)
+    SeedLimbJob *pin_jobs = nullptr, *d_jobs = nullptr;   // [jobs_cap] each
+    size_t jobs_cap = 0;
+    hipEvent_t ev_jobs = nullptr;
+    bool jobs_copied = false;          // ev_jobs has been recorded
     std::vector<bool> put;             // [K L]: units placed since the last piehip_run_chain or batch-size change
     hipEvent_t ev_ready = nullptr;     // recorded on this handle's stream for a reader of acc on another stream (piehip_put_accumulators_from),
     hipEvent_t ev_read = nullptr;      // ... and on this handle's stream behind its own placement launch, for the source to wait on

@@ -20,6 +20,9 @@ void slice_free(piehip_ctx *h)
     for (u32 q = 0; q < STAGE_A_MAX_QUERIES; q++) dev_free(&s.idx_own[q]), dev_free(&s.minus_own[q]);
     if (s.ev_ready) (void)hipEventDestroy(s.ev_ready);
     if (s.ev_read) (void)hipEventDestroy(s.ev_read);
+    if (s.ev_jobs) (void)hipEventDestroy(s.ev_jobs);
+    if (s.pin_jobs) (void)hipHostFree(s.pin_jobs);
+    if (s.d_jobs) (void)hipFree(s.d_jobs);
     s = SliceState();
 }
 
@@ -39,7 +42,7 @@ int slice_batch_changed(piehip_ctx *h)
     SliceState &s = h->slice;
     if (!s.on) return PIEHIP_OK;
     // caller-owned slice inputs of queries outside the new batch are forgotten, as piehip_set_query_batch forgets the whole ones
-    for (u32 q = h->nq; q < STAGE_A_MAX_QUERIES; q++) s.idx[q] = s.minus[q] = nullptr;
+    for (u32 q = h->nq; q < STAGE_A_MAX_QUERIES; q++) s.idx[q] = s.minus[q] = nullptr, s.idx_seeded[q] = s.minus_seeded[q] = false;
     std::fill(s.put.begin(), s.put.end(), false);
     return slice_alloc_acc(h);
 }
@@ -70,6 +73,7 @@ static int slice_setup(piehip_ctx *h, u32 K, u32 b, u32 E, u32 u_lo, u32 u_hi, u
     if ((rc = slice_alloc_acc(h))) return rc;
     HIPCHK(hipEventCreateWithFlags(&s.ev_ready, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&s.ev_read, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&s.ev_jobs, hipEventDisableTiming));
     s.on = true;
     return PIEHIP_OK;
 }
@@ -112,13 +116,81 @@ static int slice_query_check(piehip_ctx *h, u32 q, const void *p, const char *wh
     return PIEHIP_OK;
 }
 
-// `rows` rows of N words each, `pitch` words apart in host memory, to the owned device copy of a slice input at word offset dst_off
-static int upload_rows(piehip_ctx *h, u64 **own, size_t own_words, size_t dst_off, const u64 *src, size_t pitch, u32 rows)
+// `rows` rows of N words each, `pitch` words apart in host memory, to the owned device copy of a slice input at word offset dst_off,
+// dpitch words apart there (0: one behind the other; 2 N: the c0 rows of ciphertexts that follow each other)
+static int upload_rows(piehip_ctx *h, u64 **own, size_t own_words, size_t dst_off, const u64 *src, size_t pitch, u32 rows, size_t dpitch = 0)
 {
     int rc;
     if (!*own && (rc = dev_alloc(own, own_words))) return rc;
     const size_t w = (size_t)h->hp.N * sizeof(u64);
-    HIPCHK(hipMemcpy2DAsync(*own + dst_off, w, src, pitch * sizeof(u64), w, rows, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpy2DAsync(*own + dst_off, dpitch ? dpitch * sizeof(u64) : w, src, pitch * sizeof(u64), w, rows, hipMemcpyHostToDevice, h->stream));
+    return PIEHIP_OK;
+}
+
+// the refusals of a seeded setter, all in front of the device: null input, unsliced handle, query outside the batch
+static int slice_seeded_check(piehip_ctx *h, u32 q, const void *c0, const void *seeds, const char *what)
+{
+    if (!seeds) return fail(PIEHIP_EINVAL, std::string("null seeds of ") + what);
+    return slice_query_check(h, q, c0, what);
+}
+
+// query q's seed tables as the expansion reads them: n seeds from `seeds` to position `at` of [K E + 1][8]
+static void keep_seeds(piehip_ctx *h, u32 q, size_t at, const uint8_t *seeds, size_t n)
+{
+    std::vector<u32> &t = h->slice.seeds[q];
+    t.resize(((size_t)h->K * h->E + 1) * 8);
+    memcpy(&t[at * 8], seeds, n * 32);   // little-endian host: the bytes are the words
+}
+
+// One expansion launch for every piece of the batch that was set seeded since the last piehip_run_slice, on the handle's stream in
+// front of stage A: the c1 row of limb u % L behind each c0 row of the handle's units.
+// The job table.  The page-locked table is read by ONE copy, queued here; ev_jobs is recorded behind that copy, and the next call
+// that has jobs waits for ev_jobs before it writes the table -- so the table is never rewritten while an earlier run's copy of it
+// can still be in flight.  The device table is written by that copy alone, on the handle's stream, behind the earlier run's
+// expansion launch that read it (stream order).  Both tables hold every piece of the batch and are reallocated (a new batch size)
+// only once the stream has drained.
+static int queue_slice_expansion(piehip_ctx *h)
+{
+    SliceState &s = h->slice;
+    const u32 N = h->hp.N, L = h->hp.L, E = h->E, un = s.u_n();
+    size_t n = 0;
+    for (u32 q = 0; q < h->nq; q++) n += (size_t)un * ((s.idx_seeded[q] ? E : 0) + (s.minus_seeded[q] ? 1 : 0));
+    if (!n) return PIEHIP_OK;
+    if (n > s.jobs_cap) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (s.pin_jobs) (void)hipHostFree(s.pin_jobs);
+        if (s.d_jobs) (void)hipFree(s.d_jobs);
+        s.pin_jobs = s.d_jobs = nullptr;
+        s.jobs_cap = 0, s.jobs_copied = false;
+        const size_t cap = (size_t)h->nq * un * (E + 1);   // every piece of the batch
+        HIPCHK(hipHostMalloc((void **)&s.pin_jobs, cap * sizeof(SeedLimbJob), hipHostMallocPortable));
+        HIPCHK(hipMalloc((void **)&s.d_jobs, cap * sizeof(SeedLimbJob)));
+        s.jobs_cap = cap;
+    }
+    if (s.jobs_copied) HIPCHK(hipEventSynchronize(s.ev_jobs));
+    size_t at = 0;
+    for (u32 q = 0; q < h->nq; q++) {
+        const u32 *seeds = s.seeds[q].data();
+        for (u32 u = s.u_lo; u < s.u_hi && s.idx_seeded[q]; u++)
+            for (u32 j = 0; j < E; j++) {
+                SeedLimbJob &job = s.pin_jobs[at++];
+                job.dst = s.idx_own[q] + (((size_t)(u - s.u_lo) * E + j) * 2 + 1) * N;
+                memcpy(job.seed, seeds + ((size_t)(u / L) * E + j) * 8, 32);
+                job.limb = u % L;
+            }
+        for (u32 u = s.u_lo; u < s.u_hi && s.minus_seeded[q]; u++) {
+            SeedLimbJob &job = s.pin_jobs[at++];
+            job.dst = s.minus_own[q] + ((size_t)(u - s.u_lo) * 2 + 1) * N;
+            memcpy(job.seed, seeds + (size_t)h->K * E * 8, 32);
+            job.limb = u % L;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(s.d_jobs, s.pin_jobs, n * sizeof(SeedLimbJob), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(s.ev_jobs, h->stream));
+    s.jobs_copied = true;
+    launch_expand_uniform_limb(h->d_dc, N, s.d_jobs, (u32)n, h->stream);
+    HIPCHK(hipGetLastError());
+    for (u32 q = 0; q < h->nq; q++) s.idx_seeded[q] = s.minus_seeded[q] = false;
     return PIEHIP_OK;
 }
 
@@ -232,7 +304,7 @@ int piehip_set_index_slice_q(piehip_handle h, uint32_t q, const uint64_t *idx_sl
     const size_t words = (size_t)s.u_n() * h->E * 2 * h->hp.N;
     if ((rc = upload_rows(h, &s.idx_own[q], words, 0, idx_slice, h->hp.N, s.u_n() * h->E * 2))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    s.idx[q] = s.idx_own[q];
+    s.idx[q] = s.idx_own[q], s.idx_seeded[q] = false;
     return PIEHIP_OK;
 }
 int piehip_set_minus_slice_q(piehip_handle h, uint32_t q, const uint64_t *minus_slice)
@@ -245,7 +317,7 @@ int piehip_set_minus_slice_q(piehip_handle h, uint32_t q, const uint64_t *minus_
     HIPCHK(hipSetDevice(h->device));
     if ((rc = upload_rows(h, &s.minus_own[q], (size_t)s.u_n() * 2 * h->hp.N, 0, minus_slice, h->hp.N, s.u_n() * 2))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    s.minus[q] = s.minus_own[q];
+    s.minus[q] = s.minus_own[q], s.minus_seeded[q] = false;
     return PIEHIP_OK;
 }
 int piehip_set_index_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *idx)
@@ -264,7 +336,7 @@ int piehip_set_index_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *i
         if ((rc = upload_rows(h, &s.idx_own[q], words, (size_t)(u - s.u_lo) * E * 2 * N, src, (size_t)L * N, E * 2))) return rc;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    s.idx[q] = s.idx_own[q];
+    s.idx[q] = s.idx_own[q], s.idx_seeded[q] = false;
     return PIEHIP_OK;
 }
 int piehip_set_minus_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *minus)
@@ -280,7 +352,76 @@ int piehip_set_minus_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *m
         if ((rc = upload_rows(h, &s.minus_own[q], (size_t)s.u_n() * 2 * N, (size_t)(u - s.u_lo) * 2 * N, minus + (size_t)(u % L) * N, (size_t)L * N, 2)))
             return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    s.minus[q] = s.minus_own[q];
+    s.minus[q] = s.minus_own[q], s.minus_seeded[q] = false;
+    return PIEHIP_OK;
+}
+// ---- seeded slice inputs: the c0 rows go up, the c1 rows are expanded at piehip_run_slice (queue_slice_expansion) -----------------
+int piehip_set_index_slice_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0_slice, const uint8_t *seeds)
+{
+    NEED(h);
+    int rc = slice_seeded_check(h, q, c0_slice, seeds, "seeded index slice");
+    if (rc) return rc;
+    SliceState &s = h->slice;
+    if (!s.u_n()) return PIEHIP_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const u32 N = h->hp.N;
+    // c0_slice[u_n][E][N] into the c0 rows of idx_own[u_n][E][2][N]: one copy, rows 2 N apart on the device
+    if ((rc = upload_rows(h, &s.idx_own[q], (size_t)s.u_n() * h->E * 2 * N, 0, c0_slice, N, s.u_n() * h->E, 2 * (size_t)N))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    keep_seeds(h, q, 0, seeds, (size_t)h->K * h->E);
+    s.idx[q] = s.idx_own[q], s.idx_seeded[q] = true;
+    return PIEHIP_OK;
+}
+int piehip_set_minus_slice_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0_slice, const uint8_t *seed)
+{
+    NEED(h);
+    int rc = slice_seeded_check(h, q, c0_slice, seed, "seeded minus slice");
+    if (rc) return rc;
+    SliceState &s = h->slice;
+    if (!s.u_n()) return PIEHIP_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const u32 N = h->hp.N;
+    if ((rc = upload_rows(h, &s.minus_own[q], (size_t)s.u_n() * 2 * N, 0, c0_slice, N, s.u_n(), 2 * (size_t)N))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    keep_seeds(h, q, (size_t)h->K * h->E, seed, 1);
+    s.minus[q] = s.minus_own[q], s.minus_seeded[q] = true;
+    return PIEHIP_OK;
+}
+int piehip_set_index_slice_seeded_from_q(piehip_handle h, uint32_t q, const uint64_t *c0idx, const uint8_t *seeds)
+{
+    NEED(h);
+    int rc = slice_seeded_check(h, q, c0idx, seeds, "seeded index matrix");
+    if (rc) return rc;
+    SliceState &s = h->slice;
+    if (!s.u_n()) return PIEHIP_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const u32 N = h->hp.N, L = h->hp.L, E = h->E;
+    const size_t words = (size_t)s.u_n() * E * 2 * N;
+    // one strided copy per unit (not one per ciphertext: DESIGN.md section 4b): limb l of the c0 halves of the E ciphertexts of inner
+    // hash function hf, E rows of N words that lie L N apart in c0idx[K][E][L][N] and 2 N apart in the slice
+    for (u32 u = s.u_lo; u < s.u_hi; u++) {
+        const u64 *src = c0idx + ((size_t)(u / L) * E * L + u % L) * N;
+        if ((rc = upload_rows(h, &s.idx_own[q], words, (size_t)(u - s.u_lo) * E * 2 * N, src, (size_t)L * N, E, 2 * (size_t)N))) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    keep_seeds(h, q, 0, seeds, (size_t)h->K * E);
+    s.idx[q] = s.idx_own[q], s.idx_seeded[q] = true;
+    return PIEHIP_OK;
+}
+int piehip_set_minus_slice_seeded_from_q(piehip_handle h, uint32_t q, const uint64_t *c0minus, const uint8_t *seed)
+{
+    NEED(h);
+    int rc = slice_seeded_check(h, q, c0minus, seed, "seeded minus element");
+    if (rc) return rc;
+    SliceState &s = h->slice;
+    if (!s.u_n()) return PIEHIP_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const u32 N = h->hp.N, L = h->hp.L;
+    for (u32 u = s.u_lo; u < s.u_hi; u++)   // the unit's limb of c0minus[L][N]: one row
+        if ((rc = upload_rows(h, &s.minus_own[q], (size_t)s.u_n() * 2 * N, (size_t)(u - s.u_lo) * 2 * N, c0minus + (size_t)(u % L) * N, N, 1))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    keep_seeds(h, q, (size_t)h->K * h->E, seed, 1);
+    s.minus[q] = s.minus_own[q], s.minus_seeded[q] = true;
     return PIEHIP_OK;
 }
 int piehip_set_index_slice_device_q(piehip_handle h, uint32_t q, const void *d_idx_slice)
@@ -288,7 +429,7 @@ int piehip_set_index_slice_device_q(piehip_handle h, uint32_t q, const void *d_i
     NEED(h);
     int rc = slice_query_check(h, q, d_idx_slice, "index slice");
     if (rc) return rc;
-    h->slice.idx[q] = (const u64 *)d_idx_slice;
+    h->slice.idx[q] = (const u64 *)d_idx_slice, h->slice.idx_seeded[q] = false;
     return PIEHIP_OK;
 }
 int piehip_set_minus_slice_device_q(piehip_handle h, uint32_t q, const void *d_minus_slice)
@@ -296,7 +437,7 @@ int piehip_set_minus_slice_device_q(piehip_handle h, uint32_t q, const void *d_m
     NEED(h);
     int rc = slice_query_check(h, q, d_minus_slice, "minus slice");
     if (rc) return rc;
-    h->slice.minus[q] = (const u64 *)d_minus_slice;
+    h->slice.minus[q] = (const u64 *)d_minus_slice, h->slice.minus_seeded[q] = false;
     return PIEHIP_OK;
 }
 
@@ -315,6 +456,8 @@ int piehip_run_slice(piehip_handle h)
     }
     HIPCHK(hipSetDevice(h->device));
     const u32 N = h->hp.N;
+    const int rc = queue_slice_expansion(h);   // the c1 rows of the pieces set seeded since the last run
+    if (rc) return rc;
     {
         ProfScope ps(h, PIEHIP_K_STAGE_A, 8.0 * N * s.u_n() * ((double)s.b_total * h->E + h->nq * (2.0 * h->E + 2.0 + 2.0 * s.b_total)));
         launch_stage_a_slice(h->d_dc, N, h->hp.L, s.u_lo, s.u_n(), s.b_total, h->E, qs, h->nq, s.db, s.acc, h->stream, h->plan.small_moduli);

@@ -94,6 +94,28 @@ public:
             uploaded[g] = idxBytes[g] + minusBytes[g];
         }
     }
+    // seeded queries (include/piehip.h "Seeded ciphertexts"): c0Index[K][E][L][N] + seeds[K][E][32], c0[L][N] + seed[32] in host memory.
+    // Handle g is sent the c0 limbs of its units -- one strided copy per unit -- and expands the c1 limbs itself at run()
+    void setIndexSeeded(const uint64_t *c0Index, const uint8_t *seeds) { setIndexSeeded(0, c0Index, seeds); }
+    void setIndexSeeded(uint32_t q, const uint64_t *c0Index, const uint8_t *seeds)
+    {
+        for (size_t g = 0; g < ccs.size(); g++) {
+            PieContext::check(piehip_set_index_slice_seeded_from_q(ccs[g]->handle(), q, c0Index, seeds));
+            const size_t un = units[g].hi - units[g].lo;
+            idxBytes[g] = un * E * ccs[0]->ringDimension() * sizeof(uint64_t) + (un ? (size_t)K * E * 32 : 0);
+            uploaded[g] = idxBytes[g] + minusBytes[g];
+        }
+    }
+    void setMinusCompareElementSeeded(const uint64_t *c0, const uint8_t *seed) { setMinusCompareElementSeeded(0, c0, seed); }
+    void setMinusCompareElementSeeded(uint32_t q, const uint64_t *c0, const uint8_t *seed)
+    {
+        for (size_t g = 0; g < ccs.size(); g++) {
+            PieContext::check(piehip_set_minus_slice_seeded_from_q(ccs[g]->handle(), q, c0, seed));
+            const size_t un = units[g].hi - units[g].lo;
+            minusBytes[g] = un * ccs[0]->ringDimension() * sizeof(uint64_t) + (un ? 32 : 0);
+            uploaded[g] = idxBytes[g] + minusBytes[g];
+        }
+    }
     // the EvalMult key of query q's client on every handle that runs a chain
     void setEvalMultKey(uint32_t q, const uint64_t *evk)
     {
@@ -136,7 +158,8 @@ public:
 
     const std::vector<Slice> &unitSlices() const { return units; }
     const std::vector<Slice> &binSlices() const { return bins; }
-    // bytes that went up to handle g for the last query set (index matrix + minus element): u_n / (K L) of the matrix, and per unit its limb of the minus element
+    // bytes that went up to handle g for the last query set (index matrix + minus element): u_n / (K L) of the matrix, and per unit its limb of the minus element.
+    // Seeded inputs: the c0 rows only, u_n (E + 1) N 8 bytes, plus the seed tables a handle with units is handed whole (32 K E and 32 bytes)
     size_t uploadedBytes(size_t g) const { return uploaded.at(g); }
     uint32_t queriesPerRun() const { return nq; }
 

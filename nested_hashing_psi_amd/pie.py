@@ -737,8 +737,36 @@ class QuerySlicedBatchedFHEHIPPIE:
             ul, uh = self.unitSlices[g]
             self._bytes[g][1] = (uh - ul) * 2 * c0.N * 8
 
+    # -- seeded queries (include/piehip.h "Seeded ciphertexts"): c0 halves + 32-byte seeds; every handle is sent the c0 limbs of its
+    # units and expands the c1 limbs itself at run()
+    def setIndexSeeded(self, c0Index, seeds, query=0):
+        """c0Index [K][E][L][N] + seeds [K][E][32] (piehip_set_index_slice_seeded_from_q on every handle)"""
+        a, ap = _u64(c0Index)
+        c0 = self.ccs[0]
+        sd = np.ascontiguousarray(seeds, dtype=np.uint8)
+        if a.shape != (self.K, self.E, c0.L, c0.N) or sd.shape != (self.K, self.E, 32):
+            raise ValueError("a seeded index matrix is c0 [K][E][L][N] + seeds [K][E][32]")
+        for g, cc in enumerate(self.ccs):
+            _check(lib().piehip_set_index_slice_seeded_from_q(cc._h, query, ap, sd.ctypes.data_as(u8p)))
+            ul, uh = self.unitSlices[g]
+            self._bytes[g][0] = (uh - ul) * self.E * c0.N * 8 + (sd.size if uh > ul else 0)
+
+    def setMinusCompareElementSeeded(self, c0, seed, query=0):
+        """c0 [L][N] + seed [32] (piehip_set_minus_slice_seeded_from_q on every handle)"""
+        a, ap = _u64(c0)
+        c = self.ccs[0]
+        sd = np.ascontiguousarray(seed, dtype=np.uint8)
+        if a.shape != (c.L, c.N) or sd.shape != (32,):
+            raise ValueError("a seeded minus element is c0 [L][N] + a 32-byte seed")
+        for g, cc in enumerate(self.ccs):
+            _check(lib().piehip_set_minus_slice_seeded_from_q(cc._h, query, ap, sd.ctypes.data_as(u8p)))
+            ul, uh = self.unitSlices[g]
+            self._bytes[g][1] = (uh - ul) * c.N * 8 + (32 if uh > ul else 0)
+
     def uploadedBytes(self):
-        """per handle: the bytes of the last query set (index matrix + minus element) that went up to it: u_n / (K L) of the index matrix and, per unit, its limb of the minus element"""
+        """per handle: the bytes of the last query set (index matrix + minus element) that went up to it: u_n / (K L) of the index matrix
+        and, per unit, its limb of the minus element.  Seeded inputs: the c0 rows only -- u_n (E + 1) N 8, half of that -- plus the seed
+        tables, which every handle with units is handed whole: 32 K E bytes for the index matrix, 32 for the minus element"""
         return [i + m for i, m in self._bytes]
 
     def run(self, sync=True, putOrder=None):
