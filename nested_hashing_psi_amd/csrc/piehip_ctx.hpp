@@ -1,5 +1,5 @@
-// piehip_ctx.hpp -- what the translation units behind include/piehip.h share: the context behind a piehip_handle, error /
-// ordering macros, device scratch, event-bracketed launches, and the schedule pieces of a ciphertext multiplication.
+// piehip_ctx.hpp -- what the translation units behind include/piehip.h share: the context behind a piehip_handle, error / ordering
+// macros, device scratch, event-bracketed launches, the schedule pieces of a ciphertext multiplication and the Sched each is enqueued with.
 //   piehip.cpp         context, keys, database (offline phase), query inputs
 //   piehip_run.cpp     the schedule pieces of a ciphertext multiplication, run() and its queues
 //   piehip_host.cpp    the host-memory path of a query: page-locked staging, piecewise uploads, run_staged / run_host
@@ -130,11 +130,9 @@ struct piehip_ctx {
     hipEvent_t ev_fork = nullptr;
     // runs that bring their results down to host memory: queue group g + 1 starts when group g has reached the kernel that writes
     // its results, so that the download of group g runs under the evaluation of group g + 1 (piehip_run_into)
-    hipEvent_t ev_chain = nullptr;
-    bool chain_armed = false;                     // set while such a group is enqueued: recorded in front of its result-writing kernel
+    hipEvent_t ev_chain = nullptr;                // (the event; Sched::release says which group records it)
     u32 run_streams = 0;                          // piehip_set_run_streams: 0 = all queues
     bool inputs_dirty = true;                     // inputs / keys / database changed on the handle's stream since the last run()
-    hipEvent_t wait_before_results = nullptr;     // set while run() enqueues a group: its result-writing kernel waits for this
     bool pending_join = false;                    // run() left work on the bin-layer queues that the handle's stream has not waited for
     // piehip_set_graph: run() as one captured hipGraph per (inputs, result buffer, queue count), replayed on the handle's stream
     bool use_graph = false;
@@ -152,7 +150,6 @@ struct piehip_ctx {
     bool hp_timing = false;
     hipEvent_t hp_ev[3] = {nullptr, nullptr, nullptr};
     int hp_ev_state = 0;                          // 0 nothing recorded, 1 first piece, 2 handed over, 3 complete sequence recorded
-    u64 *host_results = nullptr;                  // set while piehip_run_staged enqueues: every queue group downloads its slice there
     // the one expansion launch of a staging sequence with seeded pieces: its job table goes up from a page-locked table with two
     // halves (sequence s writes half s & 1 once sequence s - 2's copy has left it: piehip_host.cpp) into d_seed_jobs
     piehip::SeedJob *pin_seed_jobs = nullptr;     // [2][seed_jobs_cap]
@@ -186,8 +183,6 @@ struct piehip_ctx {
     // results hold nq rows per bin layer: [b][nq][..].
     piehip::Query query[piehip::STAGE_A_MAX_QUERIES];
     u32 nq = 1;
-    u32 mask_div = 1;  // set while run() enqueues a batch: ciphertext row r of the product chain takes mask r / mask_div
-    u32 key_group = 1; // ... and, with per-query EvalMult keys, key r % key_group of d_evkq
     // piehip_load_relin_key_q: the queries of a batch come from different clients, each with its own EvalMult key.  [evkq_n] keys
     // [L][2][L][N] one after the other (+ the lane-ordered copy); entries nobody loaded hold the handle's key
     u64 *d_evkq = nullptr, *d_evkq_sigma = nullptr;
@@ -239,13 +234,36 @@ inline bool run_keys_loaded(const piehip_ctx *h)
     return h->K <= 1 || h->d_evk || (h->d_evkq && h->evkq_n == h->nq && h->evkq_loaded == (1u << h->nq) - 1);
 }
 
+// Where and how a schedule piece is enqueued.  A handle alone converts to "its stream, no gate, one mask and one key for every
+// row": what every entry point outside run() enqueues with.  run_on_queues makes one per queue group.
+struct Sched {
+    piehip_ctx *h;
+    hipStream_t stream;
+    hipEvent_t wait_before_results = nullptr;  // the result buffer may still be read by work queued on the handle's stream before
+                                               // this run: the kernel that writes the results waits for this (null: no need)
+    hipEvent_t release = nullptr;  // host-results runs: recorded, and cleared, when this group has only its result-writing kernel
+                                   // left; the next queue group starts behind it (null: nobody waits)
+    u32 mask_div = 1;   // a batch: ciphertext row r of the product chain takes mask r / mask_div
+    u32 key_group = 1;  // ... and, with per-query EvalMult keys, key r % key_group of d_evkq
+    Sched(piehip_ctx *h_) : h(h_), stream(h_->stream) {}
+    Sched(piehip_ctx *h_, hipStream_t s) : h(h_), stream(s) {}
+    void wait_for_readers() const { if (wait_before_results) (void)hipStreamWaitEvent(stream, wait_before_results, 0); }
+    void gate()  // in front of the kernel that writes a run's results
+    {
+        wait_for_readers();
+        if (release) (void)hipEventRecord(release, stream);
+        release = nullptr;
+    }
+};
+
 hipEvent_t prof_event(piehip_ctx *h);
-// brackets the launches queued in its scope with HIP events on the handle's current stream when profiling is on
+// brackets the launches queued in its scope with HIP events on the caller's stream (a handle: its own) when profiling is on
 struct ProfScope {
     piehip_ctx *h;
+    hipStream_t stream;
     ProfRec r;
     bool on;
-    ProfScope(piehip_ctx *h_, int k, double bytes) : h(h_), on(h_->profiling)
+    ProfScope(const Sched &s, int k, double bytes) : h(s.h), stream(s.stream), on(s.h->profiling)
     {
         if (!on) return;
         r.k = k;
@@ -256,12 +274,12 @@ struct ProfScope {
             on = false;
             return;
         }
-        (void)hipEventRecord(r.a, h->stream);
+        (void)hipEventRecord(r.a, stream);
     }
     ~ProfScope()
     {
         if (!on) return;
-        (void)hipEventRecord(r.b, h->stream);
+        (void)hipEventRecord(r.b, stream);
         h->recs.push_back(r);
     }
 };
@@ -304,15 +322,26 @@ int ws_alloc(piehip_ctx *h, MulWs &w, u32 nb);
 void ws_free(MulWs &w);
 
 // ---- schedule pieces (piehip_run.cpp) --------------------------------------------------------------
+// Each launches on s.stream; a piece told that it writes a run's results (out_is_result) passes s.gate() in front of that kernel
 // sigma: lane order on the EVALUATION side; fold: outer stage applied by the neighbouring kernels.  Callers say what they would
 // like; ntt() and enqueue_keyswitch() are where a context without lane order / folding (h->plan) turns that into standard order
-void ntt(piehip_ctx *h, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inv, bool sigma = false, bool fold = false,
+void ntt(const Sched &s, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inv, bool sigma = false, bool fold = false,
          const NttExtra *ex = nullptr);
-// lane: w.d01, the digits, key and mask are lane-ordered (and folded) where the context has a lane order; out is in standard order
-void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u64 *mask, u64 *out, bool lane = false,
-                       size_t key_stride = 0, u32 key_group = 1, bool out_is_result = false, bool digits_ready = false,
-                       bool d01_eval_q = false);
-void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
+// a key-switching key [L][2][L][N]; group > 1: ciphertext row r takes key r % group of an array of keys `stride` words apart
+struct RunKey {
+    const u64 *key;
+    size_t stride;
+    u32 group;
+    RunKey(const u64 *key_, size_t stride_ = 0, u32 group_ = 1) : key(key_), stride(stride_), group(group_) {}
+};
+struct KeyswitchOpts {
+    bool lane = false;           // w.d01, the digits, key and mask are lane-ordered (and folded) where the context has a lane order
+    bool out_is_result = false;  // out (always in standard order) is a run()'s result buffer
+    bool digits_ready = false;
+    bool d01_eval_q = false;     // (enqueue_mul only, plan.d01_eval_q) w.d01 lacks the own-limb term; the MAC adds it from w.eqp
+};
+void enqueue_keyswitch(Sched &s, MulWs &w, u32 nb, RunKey key, const u64 *mask, u64 *out, KeyswitchOpts o = {});
+void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
                  const u64 *mask, u64 *out, bool xq_ready = false, bool out_is_result = false);
 int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out);
 static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
@@ -321,15 +350,16 @@ static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device enco
 int alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db = true);
 int make_masks_sigma(piehip_ctx *h);
 int hash_tbl_alloc(piehip_ctx *h, size_t words);
-// piehip_run.cpp: the queues of piehip_run_into / piehip_run_chain_into; whether stage A hands operand X over in lane order
-int run_on_queues(piehip_ctx *h, void *d_results, bool chain_only);
+// piehip_run.cpp: the queues of piehip_run_into / piehip_run_chain_into (host_results, piehip_run_staged: every queue group also
+// downloads its slice of the results there); whether stage A hands operand X over in lane order
+int run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *host_results = nullptr);
 bool run_x_direct(const piehip_ctx *h);
 // piehip_slice.cpp
 void slice_free(piehip_ctx *h);          // back to an unsliced handle: the slice side's buffers and state
 int slice_batch_changed(piehip_ctx *h);  // piehip_set_query_batch on a sliced handle: acc for the new batch, nothing put
 // result limbs (piehip_run.cpp): `rows` ciphertexts full[rows][2][L][N] (EVALUATION, standard order; overwritten) reduced to their
-// first `keep` limbs, out[rows][2][keep][N], on the handle's current stream.  out_is_result: out is a run()'s result buffer
-void enqueue_mod_reduce(piehip_ctx *h, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result = false);
+// first `keep` limbs, out[rows][2][keep][N].  out_is_result: out is a run()'s result buffer
+void enqueue_mod_reduce(Sched &s, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result = false);
 int ensure_full_rows(piehip_ctx *h);   // piehip.cpp: d_full for the workspace's rows when the handle reduces its results
 // device input buffers of query q of the batch (owned copies: the host setters and the staged uploads write them)
 int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus);

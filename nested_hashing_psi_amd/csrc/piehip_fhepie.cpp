@@ -167,6 +167,7 @@ int piehip_fhepie_run(piehip_handle h)
     h->pool_used = 0;
     h->recs.clear();
     const double W = 8.0 * N;
+    Sched s(h);
     for (u32 hf = 0; hf < K; hf++) {
         {
             ProfScope ps(h, PIEHIP_K_MASK, W * nb * 5.0 * L);
@@ -178,8 +179,8 @@ int piehip_fhepie_run(piehip_handle h)
                 ProfScope ps(h, PIEHIP_K_AUTOMORPH, W * nb * 7.0 * L);
                 launch_rot_prepare(h->d_dc, N, L, prod, summaps[r], 1, true, false, w.d01, w.d2c, nb, h->stream);
             }
-            ntt(h, w.d2c, nb * L, 0, L, true);
-            enqueue_keyswitch(h, w, nb, sumkeys[r], nullptr, prod);
+            ntt(s, w.d2c, nb * L, 0, L, true);
+            enqueue_keyswitch(s, w, nb, sumkeys[r], nullptr, prod);
         }
         if (b > 1) {
             {
@@ -190,8 +191,8 @@ int piehip_fhepie_run(piehip_handle h)
                 ProfScope ps(h, PIEHIP_K_AUTOMORPH, W * nb * 5.0 * L);
                 launch_rot_prepare(h->d_dc, N, L, prod, h->fp_negmaps, b, false, true, w.d01, w.d2c, nb, h->stream);
             }
-            ntt(h, w.d2c, nb * L, 0, L, true);
-            enqueue_keyswitch(h, w, nb, h->fp_negkeys, nullptr, prod, false, keyw, b);
+            ntt(s, w.d2c, nb * L, 0, L, true);
+            enqueue_keyswitch(s, w, nb, {h->fp_negkeys, keyw, b}, nullptr, prod);
         } else {
             ProfScope ps(h, PIEHIP_K_MASK, W * nb * 5.0 * L);
             launch_ct_mul_plain(h->d_dc, N, L, prod, h->fp_e0, 0, prod, nb, h->stream);

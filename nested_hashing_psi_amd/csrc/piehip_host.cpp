@@ -477,9 +477,7 @@ int piehip_run_staged(piehip_handle h, uint64_t *results)
         launch_expand_uniform(h->d_dc, h->hp.N, h->hp.L, h->d_seed_jobs, (u32)njobs, h->stream);
         HIPCHK(hipGetLastError());
     }
-    h->host_results = results;
-    rc = piehip_run_into(h, h->d_out);
-    h->host_results = nullptr;
+    rc = run_on_queues(h, h->d_out, false, results);
     if (!rc && h->hp_timing && h->hp_ev_state == 2) {
         // the third event goes into the stream NOW (behind the join with the run's queues), not when the host comes back to wait:
         // what it stamps is then the device's time alone -- a host thread that is late does not show up in it

@@ -76,8 +76,9 @@ int piehip_eval_mult(piehip_handle h, const uint64_t *x, const uint64_t *y, uint
     ex.copy_K = 2;
     ex.copy_L = L;
     ex.copy_M = h->hp.M;
-    ntt(h, dxy, nct * 4 * L, 0, L, true, false, true, xq ? &ex : nullptr);
-    enqueue_mul(h, w, dxy, 4 * LN, dxy + 2 * LN, 4 * LN, nct, relin != 0, nullptr, dout, xq);
+    Sched s(h);
+    ntt(s, dxy, nct * 4 * L, 0, L, true, false, true, xq ? &ex : nullptr);
+    enqueue_mul(s, w, dxy, 4 * LN, dxy + 2 * LN, 4 * LN, nct, relin != 0, nullptr, dout, xq);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     ws_free(w);
@@ -119,8 +120,9 @@ int piehip_eval_automorph(piehip_handle h, const uint64_t *x, uint32_t g, const 
     (void)hipMemcpyAsync(w.d01, dperm, LN * sizeof(u64), hipMemcpyDeviceToDevice, h->stream);
     (void)hipMemsetAsync(w.d01 + LN, 0, LN * sizeof(u64), h->stream);
     (void)hipMemcpyAsync(w.d2c, dperm + LN, LN * sizeof(u64), hipMemcpyDeviceToDevice, h->stream);
-    ntt(h, w.d2c, L, 0, L, true);
-    enqueue_keyswitch(h, w, 1, dk, nullptr, dout);
+    Sched s(h);
+    ntt(s, w.d2c, L, 0, L, true);
+    enqueue_keyswitch(s, w, 1, dk, nullptr, dout);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     ws_free(w);
@@ -193,7 +195,8 @@ int piehip_mod_reduce(piehip_handle h, const uint64_t *in, uint32_t nct, uint32_
     TMPGET(din, win);
     TMPGET(dout, wout);
     HIPCHK(hipMemcpy(din, in, win * sizeof(u64), hipMemcpyHostToDevice));
-    enqueue_mod_reduce(h, din, nct, keep, dout);
+    Sched s(h);
+    enqueue_mod_reduce(s, din, nct, keep, dout);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out, dout, wout * sizeof(u64), hipMemcpyDeviceToHost));

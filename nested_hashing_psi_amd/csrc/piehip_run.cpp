@@ -10,79 +10,70 @@ namespace piehip {
 
 // ---- schedule pieces ----------------------------------------------------------------------------
 // What a context does where -- which transform kernel, which fusions -- is decided once, in h->plan
-void ntt(piehip_ctx *h, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inv, bool sigma, bool fold, const NttExtra *ex)
+void ntt(const Sched &s, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inv, bool sigma, bool fold, const NttExtra *ex)
 {
-    ProfScope ps(h, inv ? PIEHIP_K_NTT_INV : PIEHIP_K_NTT_FWD, 16.0 * h->hp.N * nlimbs);
-    launch_ntt(h->plan, data, nlimbs, mod_base, mod_count, inv, h->stream, sigma && h->plan.lane_order, fold && h->plan.fold, ex);
+    ProfScope ps(s, inv ? PIEHIP_K_NTT_INV : PIEHIP_K_NTT_FWD, 16.0 * s.h->hp.N * nlimbs);
+    launch_ntt(s.h->plan, data, nlimbs, mod_base, mod_count, inv, s.stream, sigma && s.h->plan.lane_order, fold && s.h->plan.fold, ex);
 }
 
 // BV key switch of the COEFFICIENT-format polynomials at w.d2c with `key`, added to the EVALUATION
 // ciphertexts at w.d01, optionally multiplied by mask plaintexts: out[nb][2][L][N]
-// d01_eval_q (enqueue_mul only, plan.d01_eval_q): w.d01 lacks the own-limb term of scale-and-round; the MAC adds it from the QP operands at w.eqp
-void enqueue_keyswitch(piehip_ctx *h, MulWs &w, u32 nb, const u64 *key, const u64 *mask, u64 *out, bool lane, size_t key_stride,
-                       u32 key_group, bool out_is_result, bool digits_ready, bool d01_eval_q)
+void enqueue_keyswitch(Sched &s, MulWs &w, u32 nb, RunKey key, const u64 *mask, u64 *out, KeyswitchOpts o)
 {
+    piehip_ctx *h = s.h;
     const NttPlan &pl = h->plan;
     const u32 N = h->hp.N, L = h->hp.L;
     const size_t LN = h->LN();
     const double W = 8.0 * N;
-    lane = lane && pl.lane_order;
-    if (digits_ready) {
+    const bool lane = o.lane && pl.lane_order;
+    if (o.digits_ready) {
         // the caller's transform launch of d01 also lifted and transformed the digits
     } else if (lane ? pl.digit_lift_lane : pl.digit_lift_std) {
-        ProfScope ps(h, PIEHIP_K_NTT_FWD, 16.0 * N * nb * L * L);
-        launch_ntt_digits(pl, w.d2c, w.dig, nb, L, lane, h->stream);
+        ProfScope ps(s, PIEHIP_K_NTT_FWD, 16.0 * N * nb * L * L);
+        launch_ntt_digits(pl, w.d2c, w.dig, nb, L, lane, s.stream);
     } else {
         {
-            ProfScope ps(h, PIEHIP_K_DIGITS, W * nb * (L + (double)L * L));
-            launch_digits(h->d_dc, N, L, w.d2c, LN, nb, w.dig, h->stream, lane && pl.fold);
+            ProfScope ps(s, PIEHIP_K_DIGITS, W * nb * (L + (double)L * L));
+            launch_digits(h->d_dc, N, L, w.d2c, LN, nb, w.dig, s.stream, lane && pl.fold);
         }
-        ntt(h, w.dig, nb * L * L, 0, L, false, lane, lane);
+        ntt(s, w.dig, nb * L * L, 0, L, false, lane, lane);
     }
     {
-        // the result buffer may still be read by work the caller queued on the handle's stream before this run
-        if (h->wait_before_results && out_is_result) (void)hipStreamWaitEvent(h->stream, h->wait_before_results, 0);
-        if (h->chain_armed && out_is_result) {  // the next queue group of a host-results run may start (piehip_run_into)
-            h->chain_armed = false;
-            (void)hipEventRecord(h->ev_chain, h->stream);
-        }
-        assert(!d01_eval_q || (pl.d01_eval_q && lane));
-        ProfScope ps(h, PIEHIP_K_RELIN,
-                     W * (nb * ((double)L * L + 2 * L + 2 * L + (mask ? L : 0) + (d01_eval_q ? 4 * L : 0)) + 2.0 * L * L));
-        launch_relin_mac(h->d_dc, N, L, w.d01, 2 * LN, w.dig, key, mask, out, nb, h->stream, pl.small_moduli,
-                         lane ? h->d_sigma_inv : nullptr, key_stride, key_group, lane ? pl.lane_T : 0, pl.lane_kp, mask ? h->mask_div : 1,
-                         d01_eval_q ? w.eqp : nullptr, h->hp.M);
+        if (o.out_is_result) s.gate();
+        assert(!o.d01_eval_q || (pl.d01_eval_q && lane));
+        ProfScope ps(s, PIEHIP_K_RELIN,
+                     W * (nb * ((double)L * L + 2 * L + 2 * L + (mask ? L : 0) + (o.d01_eval_q ? 4 * L : 0)) + 2.0 * L * L));
+        launch_relin_mac(h->d_dc, N, L, w.d01, 2 * LN, w.dig, key.key, mask, out, nb, s.stream, pl.small_moduli,
+                         lane ? h->d_sigma_inv : nullptr, key.stride, key.group, lane ? pl.lane_T : 0, pl.lane_kp, mask ? s.mask_div : 1,
+                         o.d01_eval_q ? w.eqp : nullptr, h->hp.M);
     }
 }
 
 // The EvalMult key of the run being enqueued, lane-ordered where the context has a lane order: the handle's key for every
 // ciphertext row, or -- a batch whose queries bring their own keys (piehip_load_relin_key_q) -- key r % group of the array for row r
-struct RunKey {
-    const u64 *key;
-    size_t stride;
-    u32 group;
-};
-static RunKey run_key(const piehip_ctx *h)
+static RunKey run_key(const Sched &s)
 {
+    const piehip_ctx *h = s.h;
     const bool lane = h->plan.lane_order;
-    if (h->key_group > 1) return {lane ? h->d_evkq_sigma : h->d_evkq, (size_t)h->hp.L * 2 * h->LN(), h->key_group};
-    return {lane ? h->d_evk_sigma : h->d_evk, 0, 1};
+    if (s.key_group > 1) return {lane ? h->d_evkq_sigma : h->d_evkq, (size_t)h->hp.L * 2 * h->LN(), s.key_group};
+    return {lane ? h->d_evk_sigma : h->d_evk};
 }
 
 // One batched EvalMult(ct,ct) (BatchedFHEHIPPIE.cpp:123): operands in COEFFICIENT format (produced by
 // ntt(.., inverse, sigma = false, fold = true): with folding on, their outermost inverse stage is applied here),
 // X polynomial (o,c) at x + o*sx + c*LN, Y likewise.  relin: out[nb][2][L][N] (times mask if given);
 // otherwise out[nb][3][L][N] holds the EVALUATION-format tensor result.
-void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
+void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
                  const u64 *mask, u64 *out, bool xq_ready, bool out_is_result)
 {
+    piehip_ctx *h = s.h;
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M;
     const size_t LN = h->LN();
     const double W = 8.0 * N;
     const NttPlan &pl = h->plan;
     {
-        ProfScope ps(h, PIEHIP_K_EXPAND, W * nb * (4.0 * L + 4.0 * M));
-        launch_expand_both(h->d_dc, N, L, x, sx, y, sy, LN, nb, w.eqp, h->stream, pl.small_moduli, pl.fold, xq_ready);
+        ProfScope ps(s, PIEHIP_K_EXPAND, W * nb * (4.0 * L + 4.0 * M));
+        launch_expand_both(h->d_dc, N, L, x, sx, y, sy, LN, nb, w.eqp, s.stream, pl.small_moduli, pl.fold, xq_ready);
     }
     // the QP operands and the tensor result never leave the library: lane order, no LDS transposes
     {
@@ -92,7 +83,7 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
             ex.skip_L = L;
             ex.skip_M = M;
         }
-        ntt(h, w.eqp, nb * (xq_ready ? 4 * M - 2 * L : 4 * M), 0, M, false, true, true, &ex);
+        ntt(s, w.eqp, nb * (xq_ready ? 4 * M - 2 * L : 4 * M), 0, M, false, true, true, &ex);
     }
     // Tensor product and inverse transform of its result.  One launch where the plan allows: each item forms its input from the four
     // operands in its load phase, the tensor result is neither written nor read back (3 M limbs per row each way).
@@ -101,38 +92,42 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
     // key-switch MAC adds c_k (a (x) b)_k from the QP operands.  d2 keeps every limb: the digit lift wants coefficients.
     const bool eval_q = relin && pl.d01_eval_q;
     if (pl.fused_tensor) {
-        ProfScope ps(h, PIEHIP_K_TENSOR_NTT_INV, W * nb * 7.0 * M);  // (the tensor product's bytes, whichever limbs are transformed)
-        launch_ntt16_tensor(pl, w.eqp, w.dqp, nb, M, h->stream, eval_q ? L : 0);
+        ProfScope ps(s, PIEHIP_K_TENSOR_NTT_INV, W * nb * 7.0 * M);  // (the tensor product's bytes, whichever limbs are transformed)
+        launch_ntt16_tensor(pl, w.eqp, w.dqp, nb, M, s.stream, eval_q ? L : 0);
     } else {
         {
-            ProfScope ps(h, PIEHIP_K_TENSOR, W * nb * 7.0 * M);
-            launch_tensor(h->d_dc, N, M, w.eqp, w.dqp, nb, h->stream, pl.small_moduli);
+            ProfScope ps(s, PIEHIP_K_TENSOR, W * nb * 7.0 * M);
+            launch_tensor(h->d_dc, N, M, w.eqp, w.dqp, nb, s.stream, pl.small_moduli);
         }
-        ntt(h, w.dqp, nb * 3 * M, 0, M, true, true, true);
+        ntt(s, w.dqp, nb * 3 * M, 0, M, true, true, true);
     }
     if (relin) {
         {
-            ProfScope ps(h, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, h->stream, pl.small_moduli, pl.fold, false, eval_q);
+            ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
+            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, s.stream, pl.small_moduli, pl.fold, false, eval_q);
         }
         NttExtra ex;
         ex.lazy_out = true;  // the key-switch MAC adds d01 into its accumulator before reducing
         if (pl.digits_with_d01) {
             // one launch for both forward transforms in front of the key-switch MAC: d0, d1 and the L * L digits of d2
-            ProfScope ps(h, PIEHIP_K_NTT_FWD, 16.0 * N * nb * (2.0 * L + (double)L * L));
+            ProfScope ps(s, PIEHIP_K_NTT_FWD, 16.0 * N * nb * (2.0 * L + (double)L * L));
             Ntt16Digits dg = {w.d2c, LN, w.dig, nb, L};
-            launch_ntt16(pl, w.d01, nb * 2 * L, 0, L, false, true, h->stream, &ex, &dg);
+            launch_ntt16(pl, w.d01, nb * 2 * L, 0, L, false, true, s.stream, &ex, &dg);
         } else {
-            ntt(h, w.d01, nb * 2 * L, 0, L, false, true, true, &ex);
+            ntt(s, w.d01, nb * 2 * L, 0, L, false, true, true, &ex);
         }
-        const RunKey k = run_key(h);
-        enqueue_keyswitch(h, w, nb, k.key, mask, out, true, k.stride, k.group, out_is_result, pl.digits_with_d01, eval_q);
+        KeyswitchOpts o;
+        o.lane = true;
+        o.out_is_result = out_is_result;
+        o.digits_ready = pl.digits_with_d01;
+        o.d01_eval_q = eval_q;
+        enqueue_keyswitch(s, w, nb, run_key(s), mask, out, o);
     } else {
         {
-            ProfScope ps(h, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, out, 3 * LN, out + 2 * LN, 3 * LN, h->stream, pl.small_moduli, pl.fold, true);
+            ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
+            launch_scale_round(h->d_dc, N, L, w.dqp, nb, out, 3 * LN, out + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true);
         }
-        ntt(h, out, nb * 3 * L, 0, L, false, false, true);
+        ntt(s, out, nb * 3 * L, 0, L, false, false, true);
     }
 }
 
@@ -145,29 +140,23 @@ void enqueue_mul(piehip_ctx *h, MulWs &w, const u64 *x, size_t sx, const u64 *y,
 // In a run that brings its results down to host memory the next queue group is released here, in front of the limb-drop kernel:
 // this group then has that kernel and the forward transform of the kept limbs left, about what the key-switch MAC alone is when
 // nothing is reduced, and its (smaller) download still travels under the next group's evaluation.
-void enqueue_mod_reduce(piehip_ctx *h, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result)
+void enqueue_mod_reduce(Sched &s, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result)
 {
+    piehip_ctx *h = s.h;
     const u32 N = h->hp.N, L = h->hp.L;
     const double W = 8.0 * N;
     {
-        ProfScope ps(h, PIEHIP_K_RESULT_NTT_INV, 2 * W * rows * 2 * L);
-        launch_ntt(h->plan, full, rows * 2 * L, 0, L, true, h->stream);
+        ProfScope ps(s, PIEHIP_K_RESULT_NTT_INV, 2 * W * rows * 2 * L);
+        launch_ntt(h->plan, full, rows * 2 * L, 0, L, true, s.stream);
     }
-    if (out_is_result) {
-        // the result buffer may still be read by work the caller queued on the handle's stream before this run
-        if (h->wait_before_results) (void)hipStreamWaitEvent(h->stream, h->wait_before_results, 0);
-        if (h->chain_armed) {
-            h->chain_armed = false;
-            (void)hipEventRecord(h->ev_chain, h->stream);
-        }
+    if (out_is_result) s.gate();
+    {
+        ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * rows * 2 * (L + keep));
+        launch_limb_drop(h->d_dc, N, L, keep, full, out, rows * 2, s.stream);
     }
     {
-        ProfScope ps(h, PIEHIP_K_LIMB_DROP, W * rows * 2 * (L + keep));
-        launch_limb_drop(h->d_dc, N, L, keep, full, out, rows * 2, h->stream);
-    }
-    {
-        ProfScope ps(h, PIEHIP_K_RESULT_NTT_FWD, 2 * W * rows * 2 * keep);
-        launch_ntt(h->plan, out, rows * 2 * keep, 0, keep, false, h->stream);
+        ProfScope ps(s, PIEHIP_K_RESULT_NTT_FWD, 2 * W * rows * 2 * keep);
+        launch_ntt(h->plan, out, rows * 2 * keep, 0, keep, false, s.stream);
     }
 }
 
@@ -216,33 +205,31 @@ u32 run_group_size(u32 b, u32 ng, u32 g)
 // =================================================================================================
 extern "C" {
 
-// Bin layers [b0, b0 + nb) of run() on the handle's current stream: stage A, then the product chain; results[b][nq][2][L][N].
+// Bin layers [b0, b0 + nb) of run() on the queue of s: stage A, then the product chain; results[b][nq][2][L][N].
 // chain_only (piehip_run_chain: the accumulators were put there, piehip_put_accumulators): the product chain alone
-static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results, bool chain_only);
+static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_only);
 // everything of run() behind stage A for those layers (BatchedFHEHIPPIE.cpp:117-126): both callers above share it
-static void enqueue_chain_bins(piehip_ctx *h, u32 b0, u32 layers, u64 *results);
+static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results);
 // ... and, on a handle that hands its results out on fewer limbs, their reduction: results[b][nq][2][res_limbs][N].  The chain then
 // writes the handle's full-width rows, which no caller reads: what orders a run against the result buffer's readers (and releases
-// the next queue group of a host-results run) moves from the chain's last kernel to the reduction.
-static void enqueue_run_bins(piehip_ctx *h, u32 b0, u32 nb, u64 *results, bool chain_only)
+// the next queue group of a host-results run) moves from the chain's last kernel to the reduction: the chain is enqueued ungated.
+static void enqueue_run_bins(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_only)
 {
+    piehip_ctx *h = s.h;
     const u32 keep = h->res_limbs, nq = h->nq;
     if (keep >= h->hp.L) {
-        enqueue_run_bins_full(h, b0, nb, results, chain_only);
+        enqueue_run_bins_full(s, b0, nb, results, chain_only);
         return;
     }
-    const hipEvent_t wait = h->wait_before_results;
-    const bool chain = h->chain_armed;
-    h->wait_before_results = nullptr;
-    h->chain_armed = false;
-    enqueue_run_bins_full(h, b0, nb, h->d_full, chain_only);
-    h->wait_before_results = wait;
-    h->chain_armed = chain;
+    Sched chain = s;
+    chain.wait_before_results = chain.release = nullptr;
+    enqueue_run_bins_full(chain, b0, nb, h->d_full, chain_only);
     const size_t r0 = (size_t)b0 * nq;
-    enqueue_mod_reduce(h, h->d_full + r0 * 2 * h->LN(), nb * nq, keep, results + r0 * h->res_ct_words(), true);
+    enqueue_mod_reduce(s, h->d_full + r0 * 2 * h->LN(), nb * nq, keep, results + r0 * h->res_ct_words(), true);
 }
-static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results, bool chain_only)
+static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_only)
 {
+    piehip_ctx *h = s.h;
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M, K = h->K, b = h->b, E = h->E, nq = h->nq;
     const size_t LN = h->LN();
     const double W = 8.0 * N;
@@ -260,26 +247,27 @@ static void enqueue_run_bins_full(piehip_ctx *h, u32 b0, u32 nb, u64 *results, b
     // runs at the HBM rate, loses 2.5 (profiles/r04/stage_a_writes_x_lane_ordered.txt).
     const bool x_direct = run_x_direct(h);
     if (h->profiling) {  // an empty bracket: what the event pair itself costs on this stream (reported beside the kernels' times)
-        ProfScope ps(h, PIEHIP_K_EVENT_PAIR, 0.0);
+        ProfScope ps(s, PIEHIP_K_EVENT_PAIR, 0.0);
     }
     if (!chain_only) {   // stage A: all inner products of these bin layers in one launch (BatchedFHEHIPPIE.cpp:101-116)
-        ProfScope ps(h, PIEHIP_K_STAGE_A, W * ((double)layers * K * E * L + nq * ((double)K * E * 2 * L + 2.0 * L + (double)layers * K * 2 * L)));
+        ProfScope ps(s, PIEHIP_K_STAGE_A, W * ((double)layers * K * E * L + nq * ((double)K * E * 2 * L + 2.0 * L + (double)layers * K * 2 * L)));
         StageAQueries qs = {};
         for (u32 q = 0; q < nq; q++) qs.idx[q] = h->query[q].idx, qs.minus[q] = h->query[q].minus;
         const u64 *db = h->d_db + (size_t)b0 * E * LN;
         StageAXOut xo;
         if (x_direct) xo.out = h->ws.eqp + r0 * 4 * M * N, xo.M = M, xo.logns = h->plan.lane_logn;
         if (nq > 1) {
-            launch_stage_a_batch(h->d_dc, N, L, K, layers, E, qs, nq, db, acc, h->stream, h->plan.small_moduli, b, 0, 0, x_direct ? &xo : nullptr);
+            launch_stage_a_batch(h->d_dc, N, L, K, layers, E, qs, nq, db, acc, s.stream, h->plan.small_moduli, b, 0, 0, x_direct ? &xo : nullptr);
         } else {
-            launch_stage_a(h->d_dc, N, L, K, nb, E, qs.idx[0], qs.minus[0], db, acc, h->stream, h->plan.small_moduli, b, 0, 0, 1, 0,
+            launch_stage_a(h->d_dc, N, L, K, nb, E, qs.idx[0], qs.minus[0], db, acc, s.stream, h->plan.small_moduli, b, 0, 0, 1, 0,
                            x_direct ? &xo : nullptr);
         }
     }
-    enqueue_chain_bins(h, b0, layers, results);
+    enqueue_chain_bins(s, b0, layers, results);
 }
-static void enqueue_chain_bins(piehip_ctx *h, u32 b0, u32 layers, u64 *results)
+static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
 {
+    piehip_ctx *h = s.h;
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M, K = h->K, nq = h->nq;
     const size_t LN = h->LN();
     const double W = 8.0 * N;
@@ -296,19 +284,16 @@ static void enqueue_chain_bins(piehip_ctx *h, u32 b0, u32 layers, u64 *results)
     u64 *prod = h->d_prod ? h->d_prod + r0 * 2 * LN : nullptr;
     u64 *out = results + r0 * 2 * LN;
     const u64 *masks = (h->plan.lane_order ? h->d_masks_sigma : h->d_masks) + (size_t)b0 * LN;
-    struct MaskDiv {
-        piehip_ctx *h;
-        ~MaskDiv() { h->mask_div = h->key_group = 1; }
-    } mask_div_scope{h};
-    h->mask_div = nq;
-    h->key_group = (nq > 1 && h->d_evkq && h->evkq_n == nq) ? nq : 1;  // per-query EvalMult keys: row r of a group is query r % nq
+    s.mask_div = nq;
+    s.key_group = (nq > 1 && h->d_evkq && h->evkq_n == nq) ? nq : 1;  // per-query EvalMult keys: row r of a group is query r % nq
     const bool x_direct = run_x_direct(h);
     if (K == 1) {
         // one inner hash function: multipliedResult is the inner product itself (BatchedFHEHIPPIE.cpp:117-120), so run() is
         // stage A and the mask multiply (:126) -- no ciphertext product, no transform, no key
-        if (h->wait_before_results) (void)hipStreamWaitEvent(h->stream, h->wait_before_results, 0);
-        ProfScope ps(h, PIEHIP_K_MASK, W * nb * 5.0 * L);
-        launch_ct_mul_plain(h->d_dc, N, L, acc, h->d_masks + (size_t)b0 * LN, LN, out, nb, h->stream, nq);
+        // (the release of the next queue group is not recorded here but behind the whole group: run_on_queues)
+        s.wait_for_readers();
+        ProfScope ps(s, PIEHIP_K_MASK, W * nb * 5.0 * L);
+        launch_ct_mul_plain(h->d_dc, N, L, acc, h->d_masks + (size_t)b0 * LN, LN, out, nb, s.stream, nq);
         return;
     }
     // every accumulator enters a ct x ct product exactly once: switch them all to COEFFICIENT format
@@ -319,7 +304,7 @@ static void enqueue_chain_bins(piehip_ctx *h, u32 b0, u32 layers, u64 *results)
     ex.copy_L = L;
     ex.copy_M = M;
     ex.x_lane_in = x_direct;
-    ntt(h, acc, nb * K * 2 * L, 0, L, true, false, true, xq ? &ex : nullptr);
+    ntt(s, acc, nb * K * 2 * L, 0, L, true, false, true, xq ? &ex : nullptr);
     ex.x_lane_in = false;
     // product chain over the inner hash functions (BatchedFHEHIPPIE.cpp:117-124); the mask multiply
     // (:126) is fused into the last key switch
@@ -328,28 +313,28 @@ static void enqueue_chain_bins(piehip_ctx *h, u32 b0, u32 layers, u64 *results)
     for (u32 hf = 1; hf < K; hf++) {
         const bool last = hf + 1 == K;
         u64 *dst = last ? out : prod;
-        enqueue_mul(h, w, x, sx, acc + (size_t)hf * 2 * LN, (size_t)K * 2 * LN, nb, true, last ? masks : nullptr, dst, xq, last);
+        enqueue_mul(s, w, x, sx, acc + (size_t)hf * 2 * LN, (size_t)K * 2 * LN, nb, true, last ? masks : nullptr, dst, xq, last);
         if (!last) {
             ex.copy_K = 1;  // the product is the X operand of the next multiplication
-            ntt(h, prod, nb * 2 * L, 0, L, true, false, true, xq ? &ex : nullptr);
+            ntt(s, prod, nb * 2 * L, 0, L, true, false, true, xq ? &ex : nullptr);
             x = prod;
             sx = 2 * LN;
         }
     }
 }
 
-// the result ciphertexts of bin layers [b0, b0 + nb) (rows [bin layer][query]) to the caller's host array, on the current queue
-static hipError_t download_rows(piehip_ctx *h, const u64 *d_results, u32 b0, u32 nb)
+// the result ciphertexts of bin layers [b0, b0 + nb) (rows [bin layer][query]) to the caller's host array, on the queue of s
+static hipError_t download_rows(const Sched &s, u64 *host_results, const u64 *d_results, u32 b0, u32 nb)
 {
-    const size_t row = (size_t)h->nq * h->res_ct_words();
-    return hipMemcpyAsync(h->host_results + (size_t)b0 * row, d_results + (size_t)b0 * row, (size_t)nb * row * sizeof(u64),
-                          hipMemcpyDeviceToHost, h->stream);
+    const size_t row = (size_t)s.h->nq * s.h->res_ct_words();
+    return hipMemcpyAsync(host_results + (size_t)b0 * row, d_results + (size_t)b0 * row, (size_t)nb * row * sizeof(u64),
+                          hipMemcpyDeviceToHost, s.stream);
 }
 
 }  // extern C
 
 // piehip_run_into, and piehip_run_chain_into (chain_only: piehip_slice.cpp has checked what that call needs): the queues of a run
-int piehip::run_on_queues(piehip_ctx *h, void *d_results, bool chain_only)
+int piehip::run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *host_results)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
     if (!d_results) return fail(PIEHIP_EINVAL, "null result buffer");
@@ -380,38 +365,33 @@ int piehip::run_on_queues(piehip_ctx *h, void *d_results, bool chain_only)
         const int qrc = ensure_run_queues(h, ng);
         if (qrc) return qrc;
     }
-    if (h->use_graph && !h->profiling && !h->host_results && h->nq == 1) {
+    if (h->use_graph && !h->profiling && !host_results && h->nq == 1) {
         // One graph launch instead of ~13 kernel launches and 2 event operations per queue group: the same two chains, forked
         // from and joined back to the handle's stream inside the graph (so consecutive runs do not overlap each other, which
         // the eager path's lazy join allows).
         if (!h->gexec || h->g_idx != h->query[0].idx || h->g_minus != h->query[0].minus || h->g_res != d_results || h->g_ng != ng) {
             drop_graph(h);
             join_pending(h);
-            struct Restore {
-                piehip_ctx *h;
-                hipStream_t s;
-                ~Restore() { h->stream = s; }
-            } restore{h, h->stream};
             hipGraph_t graph = nullptr;
-            HIPCHK(hipStreamBeginCapture(restore.s, hipStreamCaptureModeThreadLocal));
+            HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
             hipError_t ce = hipSuccess;
             if (ng > 1) {
-                ce = hipEventRecord(h->ev_fork, restore.s);
+                ce = hipEventRecord(h->ev_fork, h->stream);
                 u32 b0 = 0;
                 for (u32 g = 0; g < ng && ce == hipSuccess; g++) {
                     const u32 nb = run_group_size(b, ng, g);
-                    ce = hipStreamWaitEvent(h->side_streams[g], h->ev_fork, 0);
-                    h->stream = h->side_streams[g];
-                    enqueue_run_bins(h, b0, nb, (u64 *)d_results, chain_only);
-                    if (ce == hipSuccess) ce = hipEventRecord(h->ev_join[g], h->side_streams[g]);
-                    if (ce == hipSuccess) ce = hipStreamWaitEvent(restore.s, h->ev_join[g], 0);
+                    Sched s(h, h->side_streams[g]);
+                    ce = hipStreamWaitEvent(s.stream, h->ev_fork, 0);
+                    enqueue_run_bins(s, b0, nb, (u64 *)d_results, chain_only);
+                    if (ce == hipSuccess) ce = hipEventRecord(h->ev_join[g], s.stream);
+                    if (ce == hipSuccess) ce = hipStreamWaitEvent(h->stream, h->ev_join[g], 0);
                     b0 += nb;
                 }
-                h->stream = restore.s;
             } else {
-                enqueue_run_bins(h, 0, b, (u64 *)d_results, chain_only);
+                Sched s(h);
+                enqueue_run_bins(s, 0, b, (u64 *)d_results, chain_only);
             }
-            const hipError_t ee = hipStreamEndCapture(restore.s, &graph);
+            const hipError_t ee = hipStreamEndCapture(h->stream, &graph);
             if (ce != hipSuccess || ee != hipSuccess || !graph) {
                 if (graph) (void)hipGraphDestroy(graph);
                 return fail(PIEHIP_EHIP, std::string("run: graph capture failed: ") + hipGetErrorString(ce != hipSuccess ? ce : ee));
@@ -430,47 +410,36 @@ int piehip::run_on_queues(piehip_ctx *h, void *d_results, bool chain_only)
         return PIEHIP_OK;
     }
     if (ng > 1) {
-        struct Restore {
-            piehip_ctx *h;
-            hipStream_t s;
-            ~Restore()
-            {
-                h->stream = s;
-                h->wait_before_results = nullptr;
-            }
-        } restore{h, h->stream};
-        HIPCHK(hipEventRecord(h->ev_fork, restore.s));
+        HIPCHK(hipEventRecord(h->ev_fork, h->stream));
         u32 b0 = 0;
         for (u32 g = 0; g < ng; g++) {
             const u32 nb = run_group_size(b, ng, g);
-            if (h->inputs_dirty) HIPCHK(hipStreamWaitEvent(h->side_streams[g], h->ev_fork, 0));
-            h->stream = h->side_streams[g];
-            h->wait_before_results = h->inputs_dirty ? nullptr : h->ev_fork;
+            Sched s(h, h->side_streams[g]);
+            if (h->inputs_dirty) HIPCHK(hipStreamWaitEvent(s.stream, h->ev_fork, 0));
+            s.wait_before_results = h->inputs_dirty ? nullptr : h->ev_fork;
             // Results go down to host memory (piehip_run_staged / piehip_run_host*): the groups do not run side by side but one
             // behind the other -- group g + 1 starts when group g has only its result-writing kernel left, and the download of
             // group g (8 of 14 MiB at C3) travels under the evaluation of group g + 1.  Results in host memory after 0.53 ms
             // instead of 0.60 at C3, 1.30 instead of 1.50 for a batch of three; a stream of queries over several handles is
             // bound by the uploads either way (profiles/r04/online_phase_staggered_groups.txt).
-            if (h->host_results && g > 0) HIPCHK(hipStreamWaitEvent(h->side_streams[g], h->ev_chain, 0));
-            if (h->host_results && g + 1 < ng) {
+            if (host_results && g > 0) HIPCHK(hipStreamWaitEvent(s.stream, h->ev_chain, 0));
+            if (host_results && g + 1 < ng) {
                 if (!h->ev_chain) HIPCHK(hipEventCreateWithFlags(&h->ev_chain, hipEventDisableTiming));
-                h->chain_armed = true;
+                s.release = h->ev_chain;
             }
-            enqueue_run_bins(h, b0, nb, (u64 *)d_results, chain_only);
-            if (h->chain_armed) {  // a chain without a key switch (K = 1): behind all of it
-                h->chain_armed = false;
-                HIPCHK(hipEventRecord(h->ev_chain, h->side_streams[g]));
-            }
-            if (h->host_results) HIPCHK(download_rows(h, (const u64 *)d_results, b0, nb));  // this group's slice, on this group's queue
-            HIPCHK(hipEventRecord(h->ev_join[g], h->side_streams[g]));
+            enqueue_run_bins(s, b0, nb, (u64 *)d_results, chain_only);
+            if (s.release) HIPCHK(hipEventRecord(s.release, s.stream));  // a chain without a key switch (K = 1): behind all of it
+            if (host_results) HIPCHK(download_rows(s, host_results, (const u64 *)d_results, b0, nb));  // this group's slice, on this group's queue
+            HIPCHK(hipEventRecord(h->ev_join[g], s.stream));
             b0 += nb;
         }
         h->pending_join = true;
         h->inputs_dirty = false;
     } else {
         join_pending(h);
-        enqueue_run_bins(h, 0, b, (u64 *)d_results, chain_only);
-        if (h->host_results) HIPCHK(download_rows(h, (const u64 *)d_results, 0, b));
+        Sched s(h);
+        enqueue_run_bins(s, 0, b, (u64 *)d_results, chain_only);
+        if (host_results) HIPCHK(download_rows(s, host_results, (const u64 *)d_results, 0, b));
         mark_dirty(h);  // the workspace is now in use on the handle's stream: the queues of a later multi-queue run wait for it
     }
     HIPCHK(hipGetLastError());
