@@ -552,6 +552,31 @@ extern "C++" int piehip::hash_tbl_alloc(piehip_ctx *h, size_t words)
     return PIEHIP_OK;
 }
 
+// A table built elsewhere, tbl[k][e][K][b][E] in host memory, as far as the encoder: into the handle's table buffer, its rows shuffled
+// whole (every handle given the same seed holds one and the same database), its slot vectors gathered into *d_slots
+// [max(K b E, b)][k e], carved from the caller's scratch
+extern "C++" int piehip::table_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *tbl, u32 k, u32 e, u32 K, u32 b, u32 E, u64 shuffle_seed, int64_t **d_slots)
+{
+    const size_t B = (size_t)k * e, npt = (size_t)K * b * E, tbl_words = B * npt;
+    const int rc = hash_tbl_alloc(h, tbl_words);
+    if (rc) return rc;
+    h->hk = k, h->he = e, h->hb = b;
+    TMPGET(d_slotsw, (npt > b ? npt : b) * B);
+    TMPGET(d_failw, 1);
+    *d_slots = (int64_t *)d_slotsw;
+    u32 *d_fail = (u32 *)d_failw;
+    HIPCHK(hipMemcpyAsync(h->d_hash_tbl, tbl, tbl_words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(d_fail, 0, sizeof(u32), h->stream));
+    launch_shuffle_rows(h->d_hash_tbl, (u32)(B * K), b, E, shuffle_seed, h->stream);
+    launch_gather_slots(h->d_hash_tbl, (u32)B, K, b, E, h->hp.t, *d_slots, d_fail, h->stream);
+    HIPCHK(hipGetLastError());  // (as in piehip_build_db_bins)
+    u32 failed = 0;
+    HIPCHK(hipMemcpyAsync(&failed, d_fail, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (failed & 2u) return fail(PIEHIP_EINVAL, "server item does not fit the plaintext modulus");
+    return PIEHIP_OK;
+}
+
 // scratch words piehip_build_db_bins carves (256-byte granules), including the encoder's
 static size_t build_db_scratch_words(const piehip_ctx *h, size_t n, u32 k, u32 e, u32 K, u32 b, u32 E)
 {
@@ -759,26 +784,9 @@ int piehip_load_db_table_bins(piehip_handle h, const uint64_t *tbl, uint32_t k, 
     HIPCHK(hipSetDevice(h->device));
     int rc = alloc_run_buffers(h, K, bin_hi - bin_lo, E);
     if (rc) return rc;
-    const size_t tbl_words = B * K * b * E;
-    if ((rc = hash_tbl_alloc(h, tbl_words))) return rc;
-    h->hk = k;
-    h->he = e;
-    h->hb = b;
     Tmp tmp(h);
-    const size_t npt = (size_t)K * b * E;
-    TMPGET(d_slotsw, (npt > b ? npt : b) * B);
-    TMPGET(d_failw, 1);
-    int64_t *d_slots = (int64_t *)d_slotsw;
-    u32 *d_fail = (u32 *)d_failw;
-    HIPCHK(hipMemcpyAsync(h->d_hash_tbl, tbl, tbl_words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(d_fail, 0, sizeof(u32), h->stream));
-    launch_shuffle_rows(h->d_hash_tbl, (u32)(B * K), b, E, shuffle_seed, h->stream);
-    launch_gather_slots(h->d_hash_tbl, (u32)B, K, b, E, h->hp.t, d_slots, d_fail, h->stream);
-    HIPCHK(hipGetLastError());  // (as in piehip_build_db_bins)
-    u32 failed = 0;
-    HIPCHK(hipMemcpyAsync(&failed, d_fail, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (failed & 2u) return fail(PIEHIP_EINVAL, "server item does not fit the plaintext modulus");
+    int64_t *d_slots = nullptr;
+    if ((rc = table_to_slots(h, tmp, tbl, k, e, K, b, E, shuffle_seed, &d_slots))) return rc;
     return encode_bin_layers(h, d_slots, K, b, E, (u32)B, bin_lo, bin_hi, mask_seed);
 }
 

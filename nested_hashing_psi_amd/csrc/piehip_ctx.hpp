@@ -8,6 +8,7 @@
 //   piehip_client.cpp  client-side harness (key generation, encryption, decryption)
 //   piehip_rccl.cpp    the final gather of a sharded server over RCCL
 //   piehip_slice.cpp   query-sliced stage A: a handle's (inner hash function, limb) units, the accumulators' way to the chain side
+//                      (slice_geometry.h: the copies that bring its inputs up, free of HIP)
 #pragma once
 #include "../../include/piehip.h"
 
@@ -24,6 +25,7 @@
 
 #include "kernels.hpp"
 #include "params.hpp"
+#include "slice_geometry.h"
 
 namespace piehip {
 int fail(int code, const std::string &msg);  // sets piehip_last_error() of this thread, returns code
@@ -86,6 +88,18 @@ struct Query {
     std::vector<u32> seeds;                        // [K E + 1][8]: the 32-byte seeds as little-endian words
 };
 
+// one input piece of one query on a query-sliced handle (SliceState::in below)
+struct SliceInput {
+    const u64 *cur = nullptr;   // what the next piehip_run_slice reads: the caller's device array (piehip_set_*_slice_device_q) or `own`
+    u64 *own = nullptr;         // the owned device copy [u_n][cts][2][N]: the host setters write it
+    // set seeded (piehip_set_*_slice_seeded*_q): the c0 rows are in `own`, the c1 rows are expanded from the seeds by the next
+    // piehip_run_slice, which clears the mark.  Every other setter of the piece clears it too: nothing is expanded over it.
+    bool seeded = false;
+};
+inline u32 piece_cts(int p, u32 E) { return p == SLICE_INDEX ? E : 1; }   // ciphertexts per unit
+// where the seed of ciphertext j of unit u sits in the query's seed table [K E + 1][8]
+inline size_t piece_seed_at(int p, u32 u, u32 j, u32 L, u32 K, u32 E) { return p == SLICE_INDEX ? (size_t)(u / L) * E + j : (size_t)K * E; }
+
 // Query slices (piehip_slice.cpp; include/piehip.h "Query slices").  Unit u = h L + l is limb l of inner hash function h.  The handle
 // holds the units [u_lo, u_hi) of the database for ALL b_total bin layers and computes those limbs of every accumulator (the slice
 // side); it runs the product chain of the bin layers [bin_lo, bin_hi) (the chain side: piehip_ctx::b = bin_hi - bin_lo, masks and
@@ -97,12 +111,9 @@ struct SliceState {
     u64 *db = nullptr;    // [u_n][b_total][E][N]: one limb per unit
     u64 *acc = nullptr;   // [b_total][nq][u_n][2][N]: what piehip_run_slice writes
     u32 acc_nq = 0;       // the batch size acc was allocated for
-    // slice inputs of every query of the batch: what the next piehip_run_slice reads (the caller's device arrays or the owned copies)
-    const u64 *idx[STAGE_A_MAX_QUERIES] = {}, *minus[STAGE_A_MAX_QUERIES] = {};   // [u_n][E][2][N], [u_n][2][N]
-    u64 *idx_own[STAGE_A_MAX_QUERIES] = {}, *minus_own[STAGE_A_MAX_QUERIES] = {};
-    // seeded slice inputs (piehip_set_*_slice_seeded*_q): the c0 rows are in the owned copy, the c1 rows are expanded from the seeds by
-    // the next piehip_run_slice, which clears the mark.  Every other setter of the piece clears it too: nothing is expanded over it.
-    bool idx_seeded[STAGE_A_MAX_QUERIES] = {}, minus_seeded[STAGE_A_MAX_QUERIES] = {};
+    // slice inputs: in[q][p] is piece p (SLICE_INDEX [u_n][E][2][N], SLICE_MINUS [u_n][2][N]) of query q of the batch.  Every consumer
+    // loops over the pieces; piece_cts and piece_seed_at above are all that tells them apart.
+    SliceInput in[STAGE_A_MAX_QUERIES][SLICE_PIECES];
     std::vector<u32> seeds[STAGE_A_MAX_QUERIES];   // [K E + 1][8]: the query's seed tables as little-endian words, the minus seed last
     // the job table of that one expansion launch: written in page-locked memory, copied up on the handle's stream.  ev_jobs is recorded
     // behind the copy and waited for before the table is written again (piehip_slice.cpp, queue_slice_expansion)
@@ -346,10 +357,14 @@ void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size
 int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out);
 static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
 // piehip.cpp: run() workspace (and, with_db, database and masks) of a handle for b bin layers; the lane-ordered copy of its masks; the
-// persistent hash-table buffer
+// persistent hash-table buffer; a host table [k][e][K][b][E] uploaded into it, shuffled and gathered into slot vectors in the
+// caller's scratch (piehip_load_db_table_bins, piehip_load_db_table_sliced)
 int alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db = true);
 int make_masks_sigma(piehip_ctx *h);
 int hash_tbl_alloc(piehip_ctx *h, size_t words);
+// (hidden: the library's dynamic symbols stay the ones they were)
+__attribute__((visibility("hidden"))) int table_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *tbl, u32 k, u32 e, u32 K, u32 b, u32 E,
+                                                          u64 shuffle_seed, int64_t **d_slots);
 // piehip_run.cpp: the queues of piehip_run_into / piehip_run_chain_into (host_results, piehip_run_staged: every queue group also
 // downloads its slice of the results there); whether stage A hands operand X over in lane order
 int run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *host_results = nullptr);

@@ -1,4 +1,4 @@
-// piehip_slice.cpp -- query slices (include/piehip.h "Query slices"; DESIGN.md section 8.1): stage A of BatchedFHEHIPPIE::run() sharded by
+// piehip_slice.cpp -- query slices (include/piehip.h "Query slices"; DESIGN.md section 6): stage A of BatchedFHEHIPPIE::run() sharded by
 // what the QUERY is made of.  Unit u = h L + l is limb l of inner hash function h.  A handle holds a contiguous unit range of the packed
 // database for all bin layers and computes those limbs of every accumulator (reference BatchedFHEHIPPIE.cpp:96-116: the slice side);
 // the accumulators then travel to the handles that own the bin layers, which run the product chain as ever (.cpp:117-126: the chain
@@ -17,7 +17,8 @@ void slice_free(piehip_ctx *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     dev_free(&s.db);
     dev_free(&s.acc);
-    for (u32 q = 0; q < STAGE_A_MAX_QUERIES; q++) dev_free(&s.idx_own[q]), dev_free(&s.minus_own[q]);
+    for (auto &query : s.in)
+        for (SliceInput &in : query) dev_free(&in.own);
     if (s.ev_ready) (void)hipEventDestroy(s.ev_ready);
     if (s.ev_read) (void)hipEventDestroy(s.ev_read);
     if (s.ev_jobs) (void)hipEventDestroy(s.ev_jobs);
@@ -42,7 +43,8 @@ int slice_batch_changed(piehip_ctx *h)
     SliceState &s = h->slice;
     if (!s.on) return PIEHIP_OK;
     // caller-owned slice inputs of queries outside the new batch are forgotten, as piehip_set_query_batch forgets the whole ones
-    for (u32 q = h->nq; q < STAGE_A_MAX_QUERIES; q++) s.idx[q] = s.minus[q] = nullptr, s.idx_seeded[q] = s.minus_seeded[q] = false;
+    for (u32 q = h->nq; q < STAGE_A_MAX_QUERIES; q++)
+        for (SliceInput &in : s.in[q]) in.cur = nullptr, in.seeded = false;
     std::fill(s.put.begin(), s.put.end(), false);
     return slice_alloc_acc(h);
 }
@@ -108,30 +110,18 @@ static int encode_units(piehip_ctx *h, const int64_t *d_slots, u32 b, u32 E, u32
     return PIEHIP_OK;
 }
 
+static int need_sliced(const piehip_ctx *h, const char *who = "")
+{
+    if (h->slice.on) return PIEHIP_OK;
+    return fail(PIEHIP_ESTATE, std::string(who) + "not a query-sliced handle (piehip_load_db_sliced / piehip_load_db_table_sliced)");
+}
+
 static int slice_query_check(piehip_ctx *h, u32 q, const void *p, const char *what)
 {
     if (!p) return fail(PIEHIP_EINVAL, std::string("null ") + what);
-    if (!h->slice.on) return fail(PIEHIP_ESTATE, "not a query-sliced handle (piehip_load_db_sliced / piehip_load_db_table_sliced)");
+    if (need_sliced(h)) return PIEHIP_ESTATE;
     if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
     return PIEHIP_OK;
-}
-
-// `rows` rows of N words each, `pitch` words apart in host memory, to the owned device copy of a slice input at word offset dst_off,
-// dpitch words apart there (0: one behind the other; 2 N: the c0 rows of ciphertexts that follow each other)
-static int upload_rows(piehip_ctx *h, u64 **own, size_t own_words, size_t dst_off, const u64 *src, size_t pitch, u32 rows, size_t dpitch = 0)
-{
-    int rc;
-    if (!*own && (rc = dev_alloc(own, own_words))) return rc;
-    const size_t w = (size_t)h->hp.N * sizeof(u64);
-    HIPCHK(hipMemcpy2DAsync(*own + dst_off, dpitch ? dpitch * sizeof(u64) : w, src, pitch * sizeof(u64), w, rows, hipMemcpyHostToDevice, h->stream));
-    return PIEHIP_OK;
-}
-
-// the refusals of a seeded setter, all in front of the device: null input, unsliced handle, query outside the batch
-static int slice_seeded_check(piehip_ctx *h, u32 q, const void *c0, const void *seeds, const char *what)
-{
-    if (!seeds) return fail(PIEHIP_EINVAL, std::string("null seeds of ") + what);
-    return slice_query_check(h, q, c0, what);
 }
 
 // query q's seed tables as the expansion reads them: n seeds from `seeds` to position `at` of [K E + 1][8]
@@ -140,6 +130,43 @@ static void keep_seeds(piehip_ctx *h, u32 q, size_t at, const uint8_t *seeds, si
     std::vector<u32> &t = h->slice.seeds[q];
     t.resize(((size_t)h->K * h->E + 1) * 8);
     memcpy(&t[at * 8], seeds, n * 32);   // little-endian host: the bytes are the words
+}
+
+// Every host setter of a slice input: piece p of query q from `src` in host memory, already cut or the whole query (slice_geometry.h),
+// into the owned device copy, which the next piehip_run_slice then reads.  seeded: src holds the c0 rows only and `seeds` the query's
+// seeds of the piece ([K][E][32], [32]); the c1 rows are expanded at piehip_run_slice (queue_slice_expansion).  All refusals come in
+// front of the device.  SLICE_WHOLE is one strided copy per unit, not one per ciphertext.
+static int set_piece(piehip_ctx *h, u32 q, SlicePiece p, SliceLayout layout, bool seeded, const u64 *src, const uint8_t *seeds, const char *what)
+{
+    NEED(h);
+    if (seeded && !seeds) return fail(PIEHIP_EINVAL, std::string("null seeds of ") + what);
+    int rc = slice_query_check(h, q, src, what);
+    if (rc) return rc;
+    SliceState &s = h->slice;
+    if (!s.u_n()) return PIEHIP_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const u32 N = h->hp.N, E = h->E;
+    SliceInput &in = s.in[q][p];
+    if (!in.own && (rc = dev_alloc(&in.own, (size_t)s.u_n() * piece_cts(p, E) * 2 * N))) return rc;
+    for (u32 c = 0, n = layout == SLICE_WHOLE ? s.u_n() : 1; c < n; c++) {
+        const SliceCopy g = slice_copy(p, layout, seeded, N, h->hp.L, E, s.u_lo, s.u_hi, c);
+        HIPCHK(hipMemcpy2DAsync(in.own + g.dst_off, g.dst_pitch * sizeof(u64), src + g.src_off, g.src_pitch * sizeof(u64), N * sizeof(u64), g.rows,
+                                hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (seeded) keep_seeds(h, q, piece_seed_at(p, 0, 0, h->hp.L, h->K, E), seeds, p == SLICE_INDEX ? (size_t)h->K * E : 1);
+    in.cur = in.own, in.seeded = seeded;
+    return PIEHIP_OK;
+}
+
+// ... and the two that take the caller's device array
+static int set_piece_device(piehip_ctx *h, u32 q, SlicePiece p, const void *d_src, const char *what)
+{
+    NEED(h);
+    const int rc = slice_query_check(h, q, d_src, what);
+    if (rc) return rc;
+    h->slice.in[q][p].cur = (const u64 *)d_src, h->slice.in[q][p].seeded = false;
+    return PIEHIP_OK;
 }
 
 // One expansion launch for every piece of the batch that was set seeded since the last piehip_run_slice, on the handle's stream in
@@ -154,7 +181,8 @@ static int queue_slice_expansion(piehip_ctx *h)
     SliceState &s = h->slice;
     const u32 N = h->hp.N, L = h->hp.L, E = h->E, un = s.u_n();
     size_t n = 0;
-    for (u32 q = 0; q < h->nq; q++) n += (size_t)un * ((s.idx_seeded[q] ? E : 0) + (s.minus_seeded[q] ? 1 : 0));
+    for (u32 q = 0; q < h->nq; q++)
+        for (int p = 0; p < SLICE_PIECES; p++) n += s.in[q][p].seeded ? (size_t)un * piece_cts(p, E) : 0;
     if (!n) return PIEHIP_OK;
     if (n > s.jobs_cap) {
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -171,26 +199,22 @@ static int queue_slice_expansion(piehip_ctx *h)
     size_t at = 0;
     for (u32 q = 0; q < h->nq; q++) {
         const u32 *seeds = s.seeds[q].data();
-        for (u32 u = s.u_lo; u < s.u_hi && s.idx_seeded[q]; u++)
-            for (u32 j = 0; j < E; j++) {
-                SeedLimbJob &job = s.pin_jobs[at++];
-                job.dst = s.idx_own[q] + (((size_t)(u - s.u_lo) * E + j) * 2 + 1) * N;
-                memcpy(job.seed, seeds + ((size_t)(u / L) * E + j) * 8, 32);
-                job.limb = u % L;
-            }
-        for (u32 u = s.u_lo; u < s.u_hi && s.minus_seeded[q]; u++) {
-            SeedLimbJob &job = s.pin_jobs[at++];
-            job.dst = s.minus_own[q] + ((size_t)(u - s.u_lo) * 2 + 1) * N;
-            memcpy(job.seed, seeds + (size_t)h->K * E * 8, 32);
-            job.limb = u % L;
-        }
+        for (int p = 0; p < SLICE_PIECES; p++)   // the index piece's units and ciphertexts, then the minus piece's units
+            for (u32 u = s.u_lo; u < s.u_hi && s.in[q][p].seeded; u++)
+                for (u32 j = 0, cts = piece_cts(p, E); j < cts; j++) {
+                    SeedLimbJob &job = s.pin_jobs[at++];
+                    job.dst = s.in[q][p].own + (((size_t)(u - s.u_lo) * cts + j) * 2 + 1) * N;
+                    memcpy(job.seed, seeds + piece_seed_at(p, u, j, L, h->K, E) * 8, 32);
+                    job.limb = u % L;
+                }
     }
     HIPCHK(hipMemcpyAsync(s.d_jobs, s.pin_jobs, n * sizeof(SeedLimbJob), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipEventRecord(s.ev_jobs, h->stream));
     s.jobs_copied = true;
     launch_expand_uniform_limb(h->d_dc, N, s.d_jobs, (u32)n, h->stream);
     HIPCHK(hipGetLastError());
-    for (u32 q = 0; q < h->nq; q++) s.idx_seeded[q] = s.minus_seeded[q] = false;
+    for (u32 q = 0; q < h->nq; q++)
+        for (SliceInput &in : s.in[q]) in.seeded = false;
     return PIEHIP_OK;
 }
 
@@ -237,26 +261,9 @@ int piehip_load_db_table_sliced(piehip_handle h, const uint64_t *tbl, uint32_t k
     if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size k*e exceeds the ring dimension");
     int rc = slice_setup(h, K, b, E, u_lo, u_hi, bin_lo, bin_hi);
     if (rc) return rc;
-    const size_t tbl_words = B * K * b * E;
-    if ((rc = hash_tbl_alloc(h, tbl_words))) return rc;
-    h->hk = k, h->he = e, h->hb = b;
     Tmp tmp(h);
-    const size_t npt = (size_t)K * b * E;
-    TMPGET(d_slotsw, (npt > b ? npt : b) * B);
-    TMPGET(d_failw, 1);
-    int64_t *d_slots = (int64_t *)d_slotsw;
-    u32 *d_fail = (u32 *)d_failw;
-    // the table is shuffled and gathered whole, as piehip_load_db_table does: every handle given the same seeds holds units of one
-    // and the same database
-    HIPCHK(hipMemcpyAsync(h->d_hash_tbl, tbl, tbl_words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(d_fail, 0, sizeof(u32), h->stream));
-    launch_shuffle_rows(h->d_hash_tbl, (u32)(B * K), b, E, shuffle_seed, h->stream);
-    launch_gather_slots(h->d_hash_tbl, (u32)B, K, b, E, h->hp.t, d_slots, d_fail, h->stream);
-    HIPCHK(hipGetLastError());
-    u32 failed = 0;
-    HIPCHK(hipMemcpyAsync(&failed, d_fail, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (failed & 2u) return fail(PIEHIP_EINVAL, "server item does not fit the plaintext modulus");
+    int64_t *d_slots = nullptr;
+    if ((rc = table_to_slots(h, tmp, tbl, k, e, K, b, E, shuffle_seed, &d_slots))) return rc;
     if ((rc = encode_units(h, d_slots, b, E, (u32)B))) return rc;
     if (bin_hi == bin_lo) return PIEHIP_OK;
     // the masks of the chain side's layers: drawn per layer from mask_seed, the ones the unsharded call draws (encode_bin_layers)
@@ -284,7 +291,7 @@ int piehip_load_db_sliced(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, u
 int piehip_get_query_slice(piehip_handle h, uint32_t *u_lo, uint32_t *u_hi, uint32_t *bin_lo, uint32_t *bin_hi)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
-    if (!h->slice.on) return fail(PIEHIP_ESTATE, "not a query-sliced handle (piehip_load_db_sliced / piehip_load_db_table_sliced)");
+    if (need_sliced(h)) return PIEHIP_ESTATE;
     if (u_lo) *u_lo = h->slice.u_lo;
     if (u_hi) *u_hi = h->slice.u_hi;
     if (bin_lo) *bin_lo = h->slice.bin_lo;
@@ -292,153 +299,46 @@ int piehip_get_query_slice(piehip_handle h, uint32_t *u_lo, uint32_t *u_hi, uint
     return PIEHIP_OK;
 }
 
-// ---- slice inputs ---------------------------------------------------------------------------------------------------------
+// ---- slice inputs: set_piece, set_piece_device ------------------------------------------------------------------------------------
 int piehip_set_index_slice_q(piehip_handle h, uint32_t q, const uint64_t *idx_slice)
 {
-    NEED(h);
-    int rc = slice_query_check(h, q, idx_slice, "index slice");
-    if (rc) return rc;
-    SliceState &s = h->slice;
-    if (!s.u_n()) return PIEHIP_OK;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t words = (size_t)s.u_n() * h->E * 2 * h->hp.N;
-    if ((rc = upload_rows(h, &s.idx_own[q], words, 0, idx_slice, h->hp.N, s.u_n() * h->E * 2))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    s.idx[q] = s.idx_own[q], s.idx_seeded[q] = false;
-    return PIEHIP_OK;
+    return set_piece(h, q, SLICE_INDEX, SLICE_CUT, false, idx_slice, nullptr, "index slice");
 }
 int piehip_set_minus_slice_q(piehip_handle h, uint32_t q, const uint64_t *minus_slice)
 {
-    NEED(h);
-    int rc = slice_query_check(h, q, minus_slice, "minus slice");
-    if (rc) return rc;
-    SliceState &s = h->slice;
-    if (!s.u_n()) return PIEHIP_OK;
-    HIPCHK(hipSetDevice(h->device));
-    if ((rc = upload_rows(h, &s.minus_own[q], (size_t)s.u_n() * 2 * h->hp.N, 0, minus_slice, h->hp.N, s.u_n() * 2))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    s.minus[q] = s.minus_own[q], s.minus_seeded[q] = false;
-    return PIEHIP_OK;
+    return set_piece(h, q, SLICE_MINUS, SLICE_CUT, false, minus_slice, nullptr, "minus slice");
 }
 int piehip_set_index_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *idx)
 {
-    NEED(h);
-    int rc = slice_query_check(h, q, idx, "index matrix");
-    if (rc) return rc;
-    SliceState &s = h->slice;
-    if (!s.u_n()) return PIEHIP_OK;
-    HIPCHK(hipSetDevice(h->device));
-    const u32 N = h->hp.N, L = h->hp.L, E = h->E;
-    const size_t words = (size_t)s.u_n() * E * 2 * N;
-    // one strided copy per unit: limb l of the E ciphertexts of inner hash function hf, 2 E rows of N words that lie L N apart
-    for (u32 u = s.u_lo; u < s.u_hi; u++) {
-        const u64 *src = idx + ((size_t)(u / L) * E * 2 * L + u % L) * N;
-        if ((rc = upload_rows(h, &s.idx_own[q], words, (size_t)(u - s.u_lo) * E * 2 * N, src, (size_t)L * N, E * 2))) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    s.idx[q] = s.idx_own[q], s.idx_seeded[q] = false;
-    return PIEHIP_OK;
+    return set_piece(h, q, SLICE_INDEX, SLICE_WHOLE, false, idx, nullptr, "index matrix");
 }
 int piehip_set_minus_slice_from_q(piehip_handle h, uint32_t q, const uint64_t *minus)
 {
-    NEED(h);
-    int rc = slice_query_check(h, q, minus, "minus element");
-    if (rc) return rc;
-    SliceState &s = h->slice;
-    if (!s.u_n()) return PIEHIP_OK;
-    HIPCHK(hipSetDevice(h->device));
-    const u32 N = h->hp.N, L = h->hp.L;
-    for (u32 u = s.u_lo; u < s.u_hi; u++)
-        if ((rc = upload_rows(h, &s.minus_own[q], (size_t)s.u_n() * 2 * N, (size_t)(u - s.u_lo) * 2 * N, minus + (size_t)(u % L) * N, (size_t)L * N, 2)))
-            return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    s.minus[q] = s.minus_own[q], s.minus_seeded[q] = false;
-    return PIEHIP_OK;
+    return set_piece(h, q, SLICE_MINUS, SLICE_WHOLE, false, minus, nullptr, "minus element");
 }
-// ---- seeded slice inputs: the c0 rows go up, the c1 rows are expanded at piehip_run_slice (queue_slice_expansion) -----------------
 int piehip_set_index_slice_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0_slice, const uint8_t *seeds)
 {
-    NEED(h);
-    int rc = slice_seeded_check(h, q, c0_slice, seeds, "seeded index slice");
-    if (rc) return rc;
-    SliceState &s = h->slice;
-    if (!s.u_n()) return PIEHIP_OK;
-    HIPCHK(hipSetDevice(h->device));
-    const u32 N = h->hp.N;
-    // c0_slice[u_n][E][N] into the c0 rows of idx_own[u_n][E][2][N]: one copy, rows 2 N apart on the device
-    if ((rc = upload_rows(h, &s.idx_own[q], (size_t)s.u_n() * h->E * 2 * N, 0, c0_slice, N, s.u_n() * h->E, 2 * (size_t)N))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    keep_seeds(h, q, 0, seeds, (size_t)h->K * h->E);
-    s.idx[q] = s.idx_own[q], s.idx_seeded[q] = true;
-    return PIEHIP_OK;
+    return set_piece(h, q, SLICE_INDEX, SLICE_CUT, true, c0_slice, seeds, "seeded index slice");
 }
 int piehip_set_minus_slice_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0_slice, const uint8_t *seed)
 {
-    NEED(h);
-    int rc = slice_seeded_check(h, q, c0_slice, seed, "seeded minus slice");
-    if (rc) return rc;
-    SliceState &s = h->slice;
-    if (!s.u_n()) return PIEHIP_OK;
-    HIPCHK(hipSetDevice(h->device));
-    const u32 N = h->hp.N;
-    if ((rc = upload_rows(h, &s.minus_own[q], (size_t)s.u_n() * 2 * N, 0, c0_slice, N, s.u_n(), 2 * (size_t)N))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    keep_seeds(h, q, (size_t)h->K * h->E, seed, 1);
-    s.minus[q] = s.minus_own[q], s.minus_seeded[q] = true;
-    return PIEHIP_OK;
+    return set_piece(h, q, SLICE_MINUS, SLICE_CUT, true, c0_slice, seed, "seeded minus slice");
 }
 int piehip_set_index_slice_seeded_from_q(piehip_handle h, uint32_t q, const uint64_t *c0idx, const uint8_t *seeds)
 {
-    NEED(h);
-    int rc = slice_seeded_check(h, q, c0idx, seeds, "seeded index matrix");
-    if (rc) return rc;
-    SliceState &s = h->slice;
-    if (!s.u_n()) return PIEHIP_OK;
-    HIPCHK(hipSetDevice(h->device));
-    const u32 N = h->hp.N, L = h->hp.L, E = h->E;
-    const size_t words = (size_t)s.u_n() * E * 2 * N;
-    // one strided copy per unit (not one per ciphertext: DESIGN.md section 4b): limb l of the c0 halves of the E ciphertexts of inner
-    // hash function hf, E rows of N words that lie L N apart in c0idx[K][E][L][N] and 2 N apart in the slice
-    for (u32 u = s.u_lo; u < s.u_hi; u++) {
-        const u64 *src = c0idx + ((size_t)(u / L) * E * L + u % L) * N;
-        if ((rc = upload_rows(h, &s.idx_own[q], words, (size_t)(u - s.u_lo) * E * 2 * N, src, (size_t)L * N, E, 2 * (size_t)N))) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    keep_seeds(h, q, 0, seeds, (size_t)h->K * E);
-    s.idx[q] = s.idx_own[q], s.idx_seeded[q] = true;
-    return PIEHIP_OK;
+    return set_piece(h, q, SLICE_INDEX, SLICE_WHOLE, true, c0idx, seeds, "seeded index matrix");
 }
 int piehip_set_minus_slice_seeded_from_q(piehip_handle h, uint32_t q, const uint64_t *c0minus, const uint8_t *seed)
 {
-    NEED(h);
-    int rc = slice_seeded_check(h, q, c0minus, seed, "seeded minus element");
-    if (rc) return rc;
-    SliceState &s = h->slice;
-    if (!s.u_n()) return PIEHIP_OK;
-    HIPCHK(hipSetDevice(h->device));
-    const u32 N = h->hp.N, L = h->hp.L;
-    for (u32 u = s.u_lo; u < s.u_hi; u++)   // the unit's limb of c0minus[L][N]: one row
-        if ((rc = upload_rows(h, &s.minus_own[q], (size_t)s.u_n() * 2 * N, (size_t)(u - s.u_lo) * 2 * N, c0minus + (size_t)(u % L) * N, N, 1))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    keep_seeds(h, q, (size_t)h->K * h->E, seed, 1);
-    s.minus[q] = s.minus_own[q], s.minus_seeded[q] = true;
-    return PIEHIP_OK;
+    return set_piece(h, q, SLICE_MINUS, SLICE_WHOLE, true, c0minus, seed, "seeded minus element");
 }
 int piehip_set_index_slice_device_q(piehip_handle h, uint32_t q, const void *d_idx_slice)
 {
-    NEED(h);
-    int rc = slice_query_check(h, q, d_idx_slice, "index slice");
-    if (rc) return rc;
-    h->slice.idx[q] = (const u64 *)d_idx_slice, h->slice.idx_seeded[q] = false;
-    return PIEHIP_OK;
+    return set_piece_device(h, q, SLICE_INDEX, d_idx_slice, "index slice");
 }
 int piehip_set_minus_slice_device_q(piehip_handle h, uint32_t q, const void *d_minus_slice)
 {
-    NEED(h);
-    int rc = slice_query_check(h, q, d_minus_slice, "minus slice");
-    if (rc) return rc;
-    h->slice.minus[q] = (const u64 *)d_minus_slice, h->slice.minus_seeded[q] = false;
-    return PIEHIP_OK;
+    return set_piece_device(h, q, SLICE_MINUS, d_minus_slice, "minus slice");
 }
 
 // ---- the slice side -------------------------------------------------------------------------------------------------------
@@ -446,13 +346,14 @@ int piehip_run_slice(piehip_handle h)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
     SliceState &s = h->slice;
-    if (!s.on) return fail(PIEHIP_ESTATE, "run_slice: not a query-sliced handle (piehip_load_db_sliced / piehip_load_db_table_sliced)");
+    if (need_sliced(h, "run_slice: ")) return PIEHIP_ESTATE;
     if (!s.u_n()) return PIEHIP_OK;   // a handle without units: nothing to compute
     if (!s.db || !s.acc || s.acc_nq != h->nq) return fail(PIEHIP_ESTATE, "run_slice: no slice buffers (an earlier allocation failed)");
     StageAQueries qs = {};
     for (u32 q = 0; q < h->nq; q++) {
-        if (!s.idx[q] || !s.minus[q]) return fail(PIEHIP_ESTATE, "run_slice: a query of the batch has no index slice or minus slice");
-        qs.idx[q] = s.idx[q], qs.minus[q] = s.minus[q];
+        for (const SliceInput &in : s.in[q])
+            if (!in.cur) return fail(PIEHIP_ESTATE, "run_slice: a query of the batch has no index slice or minus slice");
+        qs.idx[q] = s.in[q][SLICE_INDEX].cur, qs.minus[q] = s.in[q][SLICE_MINUS].cur;
     }
     HIPCHK(hipSetDevice(h->device));
     const u32 N = h->hp.N;
@@ -469,7 +370,7 @@ int piehip_run_slice(piehip_handle h)
 int piehip_slice_accumulators_device(piehip_handle h, void **d_acc_slice)
 {
     if (!h || !d_acc_slice) return fail(PIEHIP_EINVAL, "null handle or out");
-    if (!h->slice.on) return fail(PIEHIP_ESTATE, "not a query-sliced handle (piehip_load_db_sliced / piehip_load_db_table_sliced)");
+    if (need_sliced(h)) return PIEHIP_ESTATE;
     *d_acc_slice = h->slice.acc;
     return PIEHIP_OK;
 }
@@ -478,7 +379,7 @@ int piehip_get_slice_accumulators(piehip_handle h, uint64_t *out)
 {
     if (!h || !out) return fail(PIEHIP_EINVAL, "null handle or out");
     const SliceState &s = h->slice;
-    if (!s.on) return fail(PIEHIP_ESTATE, "not a query-sliced handle (piehip_load_db_sliced / piehip_load_db_table_sliced)");
+    if (need_sliced(h)) return PIEHIP_ESTATE;
     HIPCHK(hipSetDevice(h->device));
     const size_t words = (size_t)s.b_total * h->nq * s.u_n() * 2 * h->hp.N;
     if (words) HIPCHK(hipMemcpyAsync(out, s.acc, words * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
@@ -530,7 +431,7 @@ int piehip_run_chain_into(piehip_handle h, void *d_results)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
     SliceState &s = h->slice;
-    if (!s.on) return fail(PIEHIP_ESTATE, "run_chain: not a query-sliced handle (piehip_load_db_sliced / piehip_load_db_table_sliced)");
+    if (need_sliced(h, "run_chain: ")) return PIEHIP_ESTATE;
     for (size_t u = 0; u < s.put.size(); u++)
         if (!s.put[u]) return fail(PIEHIP_ESTATE, "run_chain: not every unit of the accumulators has been put (piehip_put_accumulators) since the last run_chain");
     if (s.bin_hi > s.bin_lo) {
