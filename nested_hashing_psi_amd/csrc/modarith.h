@@ -58,8 +58,10 @@ PH_HD void add128(U128 &acc, U128 x)
 }
 PH_HD void mac128(U128 &acc, u64 a, u64 b) { add128(acc, mul128(a, b)); }
 
-// z = z1:z0 < 2^128  ->  z mod q.  The quotient estimate is exact to within 2, computed mod 2^64
-// (wrap-around is harmless: only z - qhat*q mod 2^64 is used and the true remainder is < 3q < 2^64).
+// z = z1:z0 < 2^128  ->  z mod q.  The quotient estimate floor(z R / 2^128), R = r1:r0, is formed exactly from the four partial
+// products (only the low word of z0 r0 is dropped, which carries nothing), so its one loss is z frac(2^128 / q) / 2^128 < 1: it
+// is at most 1 below floor(z / q) (every multiple of q attains that) and the remainder is < 2q; the subtraction of 2q is never
+// needed and is kept as a margin.  Computed mod 2^64 (wrap-around is harmless: only z - qhat*q mod 2^64 is used).
 PH_HD u64 barrett128(u64 z1, u64 z0, const Mod &m)
 {
     u64 c = mulhi(z0, m.r0);
@@ -77,8 +79,11 @@ PH_HD u64 barrett128(u64 z1, u64 z0, const Mod &m)
 }
 PH_HD u64 reduce128(U128 z, const Mod &m) { return barrett128(z.hi, z.lo, m); }
 // z < 2^123 and 2^59 < q < 2^60: one-word Barrett.  mu = floor(2^123 / q) = (r1:r0) >> 5 fits 64 bits; the quotient
-// estimate floor(floor(z / 2^59) mu / 2^64) is at most 3 below floor(z / q), so the remainder z - qhat q lies in
-// [0, 4q) < 2^62 and two conditional subtractions finish.  A third of the multiplications of barrett128.
+// estimate floor(floor(z / 2^59) mu / 2^64) is at most 2 below floor(z / q) (it loses frac(z / 2^59) 2^59 / q < 1 and
+// floor(z / 2^59) frac(2^123 / q) / 2^64 < 1), so the remainder z - qhat q lies in [0, 3q) < 2^62 and two conditional
+// subtractions finish.  2 below is attained for q just above 2^59 (the subtraction of 2q is needed); for the primes just below
+// 2^60, where frac(2^123 / q) is tiny, the estimate is at most 1 below (DESIGN.md "Arithmetic blocks").  A third of the
+// multiplications of barrett128.
 PH_HD u64 reduce123(U128 z, const Mod &m)
 {
     const u64 mu = (m.r1 << 59) | (m.r0 >> 5);
@@ -90,7 +95,8 @@ PH_HD u64 reduce123(U128 z, const Mod &m)
     return r;
 }
 // z < 2^124 (15 products of residues < 2^60, plus a residue): the same with one bit less of z.  t = floor(floor(z / 2^60)
-// mu / 2^64) lies in (z / 2q - 3, z / 2q], so z - 2 t q is in [0, 7q) < 2^63: three conditional subtractions.
+// mu / 2^64) is at most 2 below floor(z / 2q) by the same two losses, so z - 2 t q is in [0, 6q) < 2^63: three conditional
+// subtractions (the one of 4q is needed for q just above 2^59; below 2^60 the remainder stays under 4q).
 PH_HD u64 reduce124(U128 z, const Mod &m)
 {
     const u64 mu = (m.r1 << 59) | (m.r0 >> 5);

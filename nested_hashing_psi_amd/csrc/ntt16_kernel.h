@@ -362,7 +362,7 @@ inline u32 lane_to_std(u32 p) { return lane_to_std_t(p, T); }
 //   one product   a < 2q, b < 4q:  30-bit low halves, high halves < 2^31 and < 2^32; columns < 2^60, < 2^63, < 2^63; z < 8 q^2 < 2^123
 //   two products  all < 2q:        high halves < 2^31; columns < 2^61, < 2^63, < 2^63;                           z < 8 q^2 < 2^123
 // The block is kernels_pie.hip's PIE_COLACC123_TO_4Q (one-word Barrett with mu = floor(2^123 / q): z >> 59 from the
-// carry-normalised columns, quotient estimate at most 3 short) on ten of the butterfly blocks' fixed registers.
+// carry-normalised columns, quotient estimate at most 2 short: modarith.h) on ten of the butterfly blocks' fixed registers.
 #ifndef NTT16_TENSOR_XCD
 #define NTT16_TENSOR_XCD 1
 #endif

@@ -63,7 +63,8 @@ __device__ __forceinline__ u64 addmod_nb(u64 a, u64 b, u64 q)
 // one-word Barrett as reduce123 / reduce124 of modarith.h (same quotient estimate, same remainder), mulhi as mulhi_sb, the
 // remainder z + qhat (2^64 - q) on one v_mad_u64_u32 chain, sign-mask subtractions.  32 instructions (35 with W124) where the
 // compiler's colacc_value + reduce123 take ~65 (128-bit additions through v_cmp / v_cndmask carries, an 11-instruction mulhi).
-// W124: z < 2^124 (eight products), otherwise z < 2^123 (seven).
+// W124: z < 2^124 (eight products), otherwise z < 2^123 (seven).  (The estimate is at most 2 short, so the "4q" of the names
+// below is really 3q, and the remainder of the W124 form is below 6q: modarith.h.)
 // a three-column accumulator below 2^123 to v[66:67] in [0, 4q) (v60-v71, vcc, s[96:97] as scratch): the body of colacc_reduce<false>
 #define PIE_COLACC123_TO_4Q \
     "v_lshrrev_b64 v[60:61], 30, %[c0]\n\t" \
@@ -125,7 +126,7 @@ __device__ __forceinline__ u64 colacc_reduce(const ColAcc &a, const Mod &m, u64 
               [nql] "s"((u32)nq), [nqh] "s"((u32)(nq >> 32)), [n2q] "s"(n2q), [n1q] "s"(nq), [ql] "s"((u32)m.q), [qh] "s"((u32)(m.q >> 32))
             : PIE_ASM_CLOB, "s96", "s97");
     } else {
-        // z >> 60 = c2' after the normalisation; qhat = 2 floor(zh mu / 2^64); remainder in [0, 7q): one more subtraction
+        // z >> 60 = c2' after the normalisation; qhat = 2 floor(zh mu / 2^64); remainder in [0, 6q): one more subtraction
         asm("v_lshrrev_b64 v[60:61], 30, %[c0]\n\t"
             "v_lshl_add_u64 v[60:61], v[60:61], 0, %[c1]\n\t"
             "v_lshrrev_b64 v[64:65], 30, v[60:61]\n\t"
