@@ -198,66 +198,14 @@ __global__ void __launch_bounds__(TPB) stage_a_mad_batch_kernel(const DevConsts 
     const u32 nl = threadIdx.x, n0 = tl.bx * TPB, l = tl.l, h = h0 + tl.hz, beta0 = tl.grp * BPT;
     const u32 n = n0 + nl;
     if (n >= N) return;
-    // the last group of a launch may hold fewer than BPT layers (b no multiple of BPT): its missing layers repeat its last one --
-    // the same loads again (L1 hits) and multiply-adds nobody stores -- so that the term loop stays free of per-layer branches
-    // (skipping them under uniform branches instead was measured: 4-17 % slower, profiles/r05/stage_a_batch_layer_groups.txt)
-    const u32 tmax = __builtin_amdgcn_readfirstlane(min((u32)BPT, b - beta0) - 1);
+    const u32 tmax = __builtin_amdgcn_readfirstlane(min((u32)BPT, b - beta0) - 1);   // (the last layer group may be ragged)
     const Mod m = dc->mod[l];
     const size_t LN = (size_t)L * N;
     const size_t ioff = ((size_t)h * E) * 2 * LN + (size_t)l * N + n0;
     const u64 *pd = db + (((size_t)h * bstride + beta0) * E) * LN + (size_t)l * N + n0;
     const size_t bin_stride = (size_t)E * LN;
-    ColAcc a[Q][BPT][2];
-#pragma unroll
-    for (int q = 0; q < Q; q++)
-#pragma unroll
-        for (int t = 0; t < BPT; t++) a[q][t][0] = a[q][t][1] = ColAcc{0, 0, 0};
-    auto load_term = [&](u32 j, u64 (&vi)[Q][2], u64 (&vd)[BPT]) {
-#pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const u64 *pij = qs.idx[q] + ioff + (size_t)j * 2 * LN;
-            vi[q][0] = pij[nl];
-            vi[q][1] = (pij + LN)[nl];
-        }
-        const u64 *pdj = pd + (size_t)j * LN;
-#pragma unroll
-        for (int t = 0; t < BPT; t++) vd[t] = __builtin_nontemporal_load(pdj + (size_t)min((u32)t, tmax) * bin_stride + nl);
-    };
-    u64 qiv[DEPTH][Q][2], qdv[DEPTH][BPT];
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++)
-        if ((u32)d < E) load_term(d, qiv[d], qdv[d]);
-    auto term = [&](u32 j, u64 (&vi)[Q][2], u64 (&vd)[BPT]) {
-#pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const Split30 i0 = split30(vi[q][0]), i1 = split30(vi[q][1]);
-#pragma unroll
-            for (int t = 0; t < BPT; t++) colacc_mac2(a[q][t][0], a[q][t][1], i0, i1, vd[t]);
-        }
-        if (j + DEPTH < E) load_term(j + DEPTH, vi, vd);
-        if ((j % COLACC_MAX_TERMS) == COLACC_MAX_TERMS - 1 && j + 1 < E) {
-#pragma unroll
-            for (int q = 0; q < Q; q++)
-#pragma unroll
-                for (int t = 0; t < BPT; t++) colacc_carry(a[q][t][0]), colacc_carry(a[q][t][1]);
-        }
-        if ((j % COLACC_MAX_TOTAL) == COLACC_MAX_TOTAL - 1 && j + 1 < E) {
-#pragma unroll
-            for (int q = 0; q < Q; q++)
-#pragma unroll
-                for (int t = 0; t < BPT; t++)
-#pragma unroll
-                    for (int c = 0; c < 2; c++) {
-                        const u64 r = colacc_reduce<true>(a[q][t][c], m, 0 - m.q);  // (the instruction block of the epilogue: no compare / select pairs)
-                        a[q][t][c] = ColAcc{r & 0x3FFFFFFFull, r >> 30, 0};
-                    }
-        }
-    };
-    for (u32 j = 0; j < E; j += DEPTH) {
-#pragma unroll
-        for (int d = 0; d < DEPTH; d++)
-            if (j + d < E) term(j + d, qiv[d], qdv[d]);
-    }
+    StageAAcc<true> a[Q][BPT][2];
+    stage_a_terms<BPT, Q, DEPTH, true>(qs, ioff, LN, pd, bin_stride, tmax, nl, E, m, a);
     const bool xdir = h == 0 && xo.out != nullptr;
     const u32 noff = n + ((xdir ? ~0u : 0u) & (lane_home(n, xo.logns) - n));
 #pragma unroll
@@ -275,7 +223,7 @@ __global__ void __launch_bounds__(TPB) stage_a_mad_batch_kernel(const DevConsts 
             const size_t cstride = xdir ? (size_t)xo.M * N : LN;
             u64 *const po = base + noff;
 #pragma unroll
-            for (int c = 0; c < 2; c++) po[(size_t)c * cstride] = addmod_nb(colacc_reduce<true>(a[q][t][c], m, 0 - m.q), mi[c], m.q);
+            for (int c = 0; c < 2; c++) po[(size_t)c * cstride] = addmod_nb(colacc_reduce<true>(a[q][t][c].v, m, 0 - m.q), mi[c], m.q);
         }
     }
 }
@@ -342,37 +290,23 @@ void launch_stage_a(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, cons
 
 // Stage A of a query batch: acc[b][nq][K][2][L][N].  Column-accumulator kernel (every modulus < 2^60): groups of two to four
 // queries per launch, ONE launch per group whatever the layer count (a layer count that is no multiple of the per-thread layer
-// count leaves a ragged last group, see launch_stage_a_batch_q), each reading the database once; otherwise one launch_stage_a
-// series per query.
+// count leaves a ragged last group), each reading the database once; otherwise one launch_stage_a series per query.  Query groups,
+// layers per thread and terms in flight by the rules of stage_a_common.h.
 template <int Q, int BPT>
 static void launch_stage_a_batch_qb(const DevConsts *dc, u32 N, u32 L, u32 K, u32 nb, u32 E, const StageAQueries &qs, const u64 *db,
                                     u64 *acc, hipStream_t st, u32 bstride, u32 h0, u32 hn, u32 nq, u32 q0, StageAXOut xo)
 {
     const u32 nx = (N + TPB - 1) / TPB;
-    // terms in flight behind the one being accumulated (profiles/r03/stage_a_batch_microbench.txt; r05: two for the wide tilings)
-    constexpr int DEPTH = (Q == 4 || Q * BPT >= 9) ? 2 : 3;
+    constexpr int DEPTH = stage_a_depth(Q, BPT);
     hipLaunchKernelGGL((stage_a_mad_batch_kernel<BPT, Q, DEPTH>), stage_a_grid(nx, L, hn, (nb + BPT - 1) / BPT), dim3(TPB), 0, st, dc, N, L, K,
                        nb, E, qs, db, acc, bstride, h0, nq, q0, nx * L * hn, xo);
 }
-// Bin layers per thread.  What bounds this kernel is the traffic through the L1s (profiles/r05/stage_a_batch_prefetch_really_in_flight.txt:
-// ~8.6 TB/s of L1 misses chip-wide, three quarters of them index words that a thread re-reads from the L2 once per GROUP of layers), so
-// groups should be as large as the registers allow: four layers for two queries, three for three queries (164 VGPRs either way:
-// three waves per SIMD), three for four (208: two waves).  r03-r04 had two layers for three queries: 81.7 us for twelve layers against 69.9 with
-// groups of three (tools/microbench_stage_a_batch.hip, r05).  ONE launch whatever the layer count: the last group is ragged (the
-// kernel repeats its last layer) -- a remainder launch of one or two layers is all latency (25 us for two layers alone), and two
-// launches of half the groups each leave the chip a partial round of waves twice.
 template <int Q>
 static void launch_stage_a_batch_q(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const StageAQueries &qs, const u64 *db,
                                    u64 *acc, hipStream_t st, u32 bstride, u32 h0, u32 hn, u32 nq, u32 q0, StageAXOut xo)
 {
-    constexpr u32 cap = Q == 2 ? 4 : 3;  // bin layers per thread (Q = 4, three layers: 208 VGPRs, two waves -- still 4 % ahead of two layers)
-    // the group size that issues the fewest loads per term over the launch: ceil(b / g) groups of 2 Q index words + g database words
-    // (a ragged last group loads and multiplies its padding too: six layers of two queries are better off as 3 + 3 than as 4 + 2)
-    u32 bpt = 1, best = ~0u;
-    for (u32 g = 1; g <= cap && g <= b; g++) {
-        const u32 loads = ((b + g - 1) / g) * (2 * Q + g);
-        if (loads <= best) best = loads, bpt = g;
-    }
+    constexpr u32 cap = stage_a_layer_cap(Q, true);
+    const u32 bpt = stage_a_layers(Q, b, cap);
     if constexpr (cap >= 4)
         if (bpt == 4) return launch_stage_a_batch_qb<Q, 4>(dc, N, L, K, b, E, qs, db, acc, st, bstride, h0, hn, nq, q0, xo);
     if constexpr (cap >= 3)
@@ -389,8 +323,7 @@ void launch_stage_a_batch(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E
     if (!hn) hn = K - h0;
     u32 q0 = 0;
     while (small_moduli && nq - q0 >= 2) {
-        // groups of four, three or two queries (five: 3 + 2; six: 3 + 3; seven: 4 + 3)
-        const u32 left = nq - q0, g = left == 5 || left == 6 ? 3 : std::min(left, 4u);
+        const u32 g = stage_a_query_group(nq - q0);
         StageAQueries sub = {};
         for (u32 q = 0; q < g; q++) sub.idx[q] = qs.idx[q0 + q], sub.minus[q] = qs.minus[q0 + q];
         if (g == 2) launch_stage_a_batch_q<2>(dc, N, L, K, b, E, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);

@@ -1,9 +1,7 @@
-// kernels_slice.hip -- query-sliced stage A for gfx950 (include/piehip.h "Query slices"): the inner products of
+// kernels_slice.hip -- query-sliced stage A for gfx950 (include/piehip.h "Query slices"; DESIGN.md section 6 "Query slices"): the inner products of
 // BatchedFHEHIPPIE.cpp:96-116 for one handle's (inner hash function, limb) units, over one-limb arrays, and the placement of
 // accumulator limbs that arrive from the handles that computed them into the arrays the product chain reads (.cpp:117-126).
-// The arithmetic and its instruction blocks are those of kernels_pie.hip's stage A (stage_a_common.h, madasm.h).
-#include <algorithm>
-
+// The term loop, the launch rules and the instruction blocks are those of kernels_pie.hip's tiled stage A (stage_a_common.h, madasm.h).
 #include "kernels.hpp"
 #include "madasm.h"
 #include "stage_a_common.h"
@@ -16,27 +14,10 @@ typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 // ---------------------------------------------------------------------------------------------
 // Sliced stage A: acc[beta][q][u][c][n] = sum_j idx_q[u][j][c][n] * db[u][beta][j][n] + minus_q[u][c][n]   mod q_{(u_lo + u) % L}
 //
-// A thread owns one coefficient of one unit, Q queries and BPT bin layers, as stage_a_mad_batch_kernel does: a database word is
-// loaded once for the Q queries, an index word once per BPT layers, DEPTH terms are in flight behind the one being accumulated, the
-// last layer group of a launch is ragged (it repeats its last layer: no per-layer branches in the term loop).  The handle sees ALL
-// bin layers of its units, so the layer groups of a tile are many: the block -> tile map keeps them on one XCD (stage_a_tile with
-// the unit in the limb's place).
-// MAD: every modulus in (2^59, 2^60) -- carry-free 30-bit column accumulators, swept every COLACC_MAX_TERMS terms and reduced every
-// COLACC_MAX_TOTAL; otherwise (moduli up to 61 bits) 128-bit accumulators reduced every 32 terms, as stage_a_kernel.
+// A thread owns one coefficient of one unit, Q queries and BPT bin layers; the term loop is stage_a_terms (stage_a_common.h) over
+// one-limb arrays, for both arithmetics (MAD: every modulus in (2^59, 2^60)).  The handle sees ALL bin layers of its units, so the
+// layer groups of a tile are many: the block -> tile map keeps them on one XCD (stage_a_tile with the unit in the limb's place).
 // ---------------------------------------------------------------------------------------------
-template <bool MAD>
-struct SliceAcc;
-template <>
-struct SliceAcc<true> {
-    ColAcc v;
-    __device__ __forceinline__ void zero() { v = ColAcc{0, 0, 0}; }
-};
-template <>
-struct SliceAcc<false> {
-    U128 v;
-    __device__ __forceinline__ void zero() { v = U128{0, 0}; }
-};
-
 template <int BPT, int Q, int DEPTH, bool MAD>
 __global__ void __launch_bounds__(TPB) stage_a_slice_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 u_lo, u32 un, u32 b, u32 E,
                                                             StageAQueries qs, const u64 *__restrict__ db, u64 *__restrict__ acc, u32 nq,
@@ -47,79 +28,13 @@ __global__ void __launch_bounds__(TPB) stage_a_slice_kernel(const DevConsts *__r
     const u32 nl = threadIdx.x, n0 = tl.bx * TPB, u = tl.l, beta0 = tl.grp * BPT;
     const u32 n = n0 + nl;
     if (n >= N) return;
-    const u32 tmax = __builtin_amdgcn_readfirstlane(min((u32)BPT, b - beta0) - 1);
+    const u32 tmax = __builtin_amdgcn_readfirstlane(min((u32)BPT, b - beta0) - 1);   // (the last layer group may be ragged)
     const Mod m = dc->mod[(u_lo + u) % L];
     const size_t ioff = ((size_t)u * E) * 2 * N + n0;            // idx is [un][E][2][N]
     const u64 *pd = db + (((size_t)u * b + beta0) * E) * N + n0;  // db is [un][b][E][N]
     const size_t bin_stride = (size_t)E * N;
-    SliceAcc<MAD> a[Q][BPT][2];
-#pragma unroll
-    for (int q = 0; q < Q; q++)
-#pragma unroll
-        for (int t = 0; t < BPT; t++) a[q][t][0].zero(), a[q][t][1].zero();
-    auto load_term = [&](u32 j, u64 (&vi)[Q][2], u64 (&vd)[BPT]) {
-#pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const u64 *pij = qs.idx[q] + ioff + (size_t)j * 2 * N;
-            vi[q][0] = pij[nl];
-            vi[q][1] = (pij + N)[nl];
-        }
-        const u64 *pdj = pd + (size_t)j * N;
-#pragma unroll
-        // the database is read once per run: non-temporal, as in stage_a_mad_kernel
-        for (int t = 0; t < BPT; t++) vd[t] = __builtin_nontemporal_load(pdj + (size_t)min((u32)t, tmax) * bin_stride + nl);
-    };
-    u64 qiv[DEPTH][Q][2], qdv[DEPTH][BPT];
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++)
-        if ((u32)d < E) load_term(d, qiv[d], qdv[d]);
-    auto term = [&](u32 j, u64 (&vi)[Q][2], u64 (&vd)[BPT]) {
-#pragma unroll
-        for (int q = 0; q < Q; q++) {
-            if constexpr (MAD) {
-                const Split30 i0 = split30(vi[q][0]), i1 = split30(vi[q][1]);
-#pragma unroll
-                for (int t = 0; t < BPT; t++) colacc_mac2(a[q][t][0].v, a[q][t][1].v, i0, i1, vd[t]);
-            } else {
-#pragma unroll
-                for (int t = 0; t < BPT; t++) mac128(a[q][t][0].v, vi[q][0], vd[t]), mac128(a[q][t][1].v, vi[q][1], vd[t]);
-            }
-        }
-        if (j + DEPTH < E) load_term(j + DEPTH, vi, vd);
-        if constexpr (MAD) {
-            if ((j % COLACC_MAX_TERMS) == COLACC_MAX_TERMS - 1 && j + 1 < E) {
-#pragma unroll
-                for (int q = 0; q < Q; q++)
-#pragma unroll
-                    for (int t = 0; t < BPT; t++) colacc_carry(a[q][t][0].v), colacc_carry(a[q][t][1].v);
-            }
-            if ((j % COLACC_MAX_TOTAL) == COLACC_MAX_TOTAL - 1 && j + 1 < E) {
-#pragma unroll
-                for (int q = 0; q < Q; q++)
-#pragma unroll
-                    for (int t = 0; t < BPT; t++)
-#pragma unroll
-                        for (int c = 0; c < 2; c++) {
-                            const u64 r = colacc_reduce<true>(a[q][t][c].v, m, 0 - m.q);
-                            a[q][t][c].v = ColAcc{r & 0x3FFFFFFFull, r >> 30, 0};
-                        }
-            }
-        } else {
-            if ((j & 31) == 31) {   // 2^61 + 32 * 2^122 < 2^128
-#pragma unroll
-                for (int q = 0; q < Q; q++)
-#pragma unroll
-                    for (int t = 0; t < BPT; t++)
-#pragma unroll
-                        for (int c = 0; c < 2; c++) a[q][t][c].v = U128{reduce128(a[q][t][c].v, m), 0};
-            }
-        }
-    };
-    for (u32 j = 0; j < E; j += DEPTH) {
-#pragma unroll
-        for (int d = 0; d < DEPTH; d++)
-            if (j + d < E) term(j + d, qiv[d], qdv[d]);
-    }
+    StageAAcc<MAD> a[Q][BPT][2];
+    stage_a_terms<BPT, Q, DEPTH, MAD>(qs, ioff, N, pd, bin_stride, tmax, nl, E, m, a);
 #pragma unroll
     for (int q = 0; q < Q; q++) {
         u64 mi[2];
@@ -145,27 +60,16 @@ static void launch_slice_qb(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un,
                             u64 *acc, hipStream_t st, u32 nq, u32 q0)
 {
     const u32 nx = (N + TPB - 1) / TPB;
-    // terms in flight behind the one being accumulated: as launch_stage_a_batch_qb for batches, SA_DEPTH's four for one query (three
-    // with seven layers: 176 registers with four, 168 are the most that leave three waves per SIMD)
-    constexpr int DEPTH = Q == 1 ? (BPT == 7 ? 3 : 4) : (Q == 4 || Q * BPT >= 9) ? 2 : 3;
+    constexpr int DEPTH = stage_a_depth(Q, BPT);
     hipLaunchKernelGGL((stage_a_slice_kernel<BPT, Q, DEPTH, MAD>), stage_a_grid(nx, un, 1, (b + BPT - 1) / BPT), dim3(TPB), 0, st, dc, N, L,
                        u_lo, un, b, E, qs, db, acc, nq, q0, nx * un);
 }
-// Bin layers per thread, by launch_stage_a_batch_q's rule: the group size that issues the fewest loads per term over the launch --
-// ceil(b / g) groups of 2 Q index words + g database words, a ragged last group counted whole -- up to what the accumulators leave
-// room for: seven layers for one query (stage_a_mad_kernel's; five with 128-bit accumulators), four for two queries, three for three
-// and four.
 template <int Q, bool MAD>
 static void launch_slice_q(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, u32 b, u32 E, const StageAQueries &qs, const u64 *db, u64 *acc,
                            hipStream_t st, u32 nq, u32 q0)
 {
-    // (the 128-bit accumulators of one query spill beyond five layers)
-    constexpr u32 cap = Q == 1 ? (MAD ? 7 : 5) : Q == 2 ? 4 : 3;
-    u32 bpt = 1, best = ~0u;
-    for (u32 g = 1; g <= cap && g <= b; g++) {
-        const u32 loads = ((b + g - 1) / g) * (2 * Q + g);
-        if (loads <= best) best = loads, bpt = g;
-    }
+    constexpr u32 cap = stage_a_layer_cap(Q, MAD);
+    const u32 bpt = stage_a_layers(Q, b, cap);
 #define SL_(B_)                                                                                                  \
     if constexpr (cap >= B_)                                                                                     \
         if (bpt == B_) return launch_slice_qb<Q, B_, MAD>(dc, N, L, u_lo, un, b, E, qs, db, acc, st, nq, q0)
@@ -184,8 +88,7 @@ static void launch_slice_m(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, 
 {
     u32 q0 = 0;
     while (q0 < nq) {
-        // groups of four, three or two queries (five: 3 + 2; six: 3 + 3; seven: 4 + 3), as launch_stage_a_batch; a single one alone
-        const u32 left = nq - q0, g = left == 5 || left == 6 ? 3 : std::min(left, 4u);
+        const u32 g = stage_a_query_group(nq - q0);
         StageAQueries sub = {};
         for (u32 q = 0; q < g; q++) sub.idx[q] = qs.idx[q0 + q], sub.minus[q] = qs.minus[q0 + q];
         if (g == 1) launch_slice_q<1, MAD>(dc, N, L, u_lo, un, b, E, sub, db, acc, st, nq, q0);

@@ -1,7 +1,8 @@
-// stage_a_common.h -- device helpers shared by the stage A kernels of kernels_pie.hip (the whole query on one handle) and
-// kernels_slice.hip (one handle's (inner hash function, limb) units): the block -> tile map, the lane-ordered home of a coefficient,
-// and the instruction blocks of the epilogue (column accumulator -> residue, the sum with the minus word).  Moved here word for word:
-// the kernels of kernels_pie.hip compile to the same instructions as before.
+// stage_a_common.h -- what the stage A kernels of kernels_pie.hip (the whole query on one handle) and kernels_slice.hip (one handle's
+// (inner hash function, limb) units) share: the block -> tile map, the lane-ordered home of a coefficient, the instruction blocks of
+// the epilogue (column accumulator -> residue, the sum with the minus word), the term loop of the tiled kernels (stage_a_terms:
+// stage_a_mad_batch_kernel and stage_a_slice_kernel are a prologue and an epilogue around it) and, for their launchers, the rules
+// that pick query groups, bin layers per thread and terms in flight (stage_a_query_group, stage_a_layers, stage_a_depth).
 #pragma once
 #include "kernels.hpp"
 #include "madasm.h"
@@ -169,4 +170,150 @@ __device__ __forceinline__ u64 colacc_reduce(const ColAcc &a, const Mod &m, u64 
     }
     return r;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The term loop of the tiled stage A kernels: a[q][t][c] = sum_j idx_q[j][c] * db[layer t][j] for the thread's coefficient, Q queries
+// and BPT bin layers.  A database word is loaded once for the Q queries, an index word once per BPT layers, DEPTH terms are in flight
+// behind the one being accumulated.
+// MAD: every modulus in (2^59, 2^60) -- carry-free 30-bit column accumulators (madasm.h), swept every COLACC_MAX_TERMS terms and
+// reduced every COLACC_MAX_TOTAL; otherwise (moduli up to 61 bits) 128-bit accumulators reduced every 32 terms, as stage_a_kernel.
+// ---------------------------------------------------------------------------------------------
+template <bool MAD>
+struct StageAAcc;
+template <>
+struct StageAAcc<true> {
+    ColAcc v;
+    __device__ __forceinline__ void zero() { v = ColAcc{0, 0, 0}; }
+};
+template <>
+struct StageAAcc<false> {
+    U128 v;
+    __device__ __forceinline__ void zero() { v = U128{0, 0}; }
+};
+
+// qs.idx[q] + ioff and pd are the uniform stream bases of the thread's block, nl its lane offset.  cs is the component stride of an
+// index ciphertext (a term is 2 cs further) and the term stride of the database (a bin layer is bin_stride further): L N where the
+// arrays hold whole ciphertexts, N over one-limb units.  The group holds layers 0 .. tmax <= BPT - 1.  Runs all E terms from zero
+// and leaves the sums in `out` for the kernel's epilogue, unswept and unreduced since the last period boundary before E.
+template <int BPT, int Q, int DEPTH, bool MAD, class S>
+__device__ __forceinline__ void stage_a_terms(const StageAQueries &qs, size_t ioff, S cs, const u64 *pd, size_t bin_stride, u32 tmax, u32 nl,
+                                              u32 E, const Mod &m, StageAAcc<MAD> (&out)[Q][BPT][2])
+{
+    // (accumulated in an array of its own and handed over after the last term: with the loop working on the caller's array, the
+    // 128-bit form of three layers x four queries took 306 registers instead of 235 and lost its second wave per SIMD, four layers x
+    // two queries 404 instead of 288; the column-accumulator forms compile the same either way -- profiles/stage_a_shared)
+    StageAAcc<MAD> a[Q][BPT][2];
+#pragma unroll
+    for (int q = 0; q < Q; q++)
+#pragma unroll
+        for (int t = 0; t < BPT; t++) a[q][t][0].zero(), a[q][t][1].zero();
+    auto load_term = [&](u32 j, u64 (&vi)[Q][2], u64 (&vd)[BPT]) {
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            const u64 *pij = qs.idx[q] + ioff + (size_t)j * 2 * cs;
+            vi[q][0] = pij[nl];
+            vi[q][1] = (pij + cs)[nl];
+        }
+        const u64 *pdj = pd + (size_t)j * cs;
+#pragma unroll
+        // The last group of a launch may hold fewer than BPT layers (b no multiple of BPT): its missing layers repeat its last one --
+        // the same loads again (L1 hits) and multiply-adds nobody stores -- so that the term loop stays free of per-layer branches
+        // (skipping them under uniform branches instead was measured: 4-17 % slower, profiles/r05/stage_a_batch_layer_groups.txt).
+        // The database is read once per run: non-temporal (see stage_a_mad_kernel).
+        for (int t = 0; t < BPT; t++) vd[t] = __builtin_nontemporal_load(pdj + (size_t)min((u32)t, tmax) * bin_stride + nl);
+    };
+    // a ring of DEPTH term buffers; the term loop is unrolled DEPTH times so that the ring needs no register moves
+    u64 qiv[DEPTH][Q][2], qdv[DEPTH][BPT];
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++)
+        if ((u32)d < E) load_term(d, qiv[d], qdv[d]);
+    auto term = [&](u32 j, u64 (&vi)[Q][2], u64 (&vd)[BPT]) {
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            if constexpr (MAD) {
+                const Split30 i0 = split30(vi[q][0]), i1 = split30(vi[q][1]);
+#pragma unroll
+                for (int t = 0; t < BPT; t++) colacc_mac2(a[q][t][0].v, a[q][t][1].v, i0, i1, vd[t]);
+            } else {
+#pragma unroll
+                for (int t = 0; t < BPT; t++) mac128(a[q][t][0].v, vi[q][0], vd[t]), mac128(a[q][t][1].v, vi[q][1], vd[t]);
+            }
+        }
+        if (j + DEPTH < E) load_term(j + DEPTH, vi, vd);   // refill this ring slot (the other slots are in flight)
+        if constexpr (MAD) {
+            if ((j % COLACC_MAX_TERMS) == COLACC_MAX_TERMS - 1 && j + 1 < E) {   // more terms follow: make room in the low columns
+#pragma unroll
+                for (int q = 0; q < Q; q++)
+#pragma unroll
+                    for (int t = 0; t < BPT; t++) colacc_carry(a[q][t][0].v), colacc_carry(a[q][t][1].v);
+            }
+            if ((j % COLACC_MAX_TOTAL) == COLACC_MAX_TOTAL - 1 && j + 1 < E) {   // the top column is full: reduce and start over
+#pragma unroll
+                for (int q = 0; q < Q; q++)
+#pragma unroll
+                    for (int t = 0; t < BPT; t++)
+#pragma unroll
+                        for (int c = 0; c < 2; c++) {
+                            const u64 r = colacc_reduce<true>(a[q][t][c].v, m, 0 - m.q);  // (the instruction block of the epilogue: no compare / select pairs)
+                            a[q][t][c].v = ColAcc{r & 0x3FFFFFFFull, r >> 30, 0};
+                        }
+            }
+        } else {
+            if ((j & 31) == 31) {   // 2^61 + 32 * 2^122 < 2^128
+#pragma unroll
+                for (int q = 0; q < Q; q++)
+#pragma unroll
+                    for (int t = 0; t < BPT; t++)
+#pragma unroll
+                        for (int c = 0; c < 2; c++) a[q][t][c].v = U128{reduce128(a[q][t][c].v, m), 0};
+            }
+        }
+    };
+    for (u32 j = 0; j < E; j += DEPTH) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (j + d < E) term(j + d, qiv[d], qdv[d]);
+    }
+#pragma unroll
+    for (int q = 0; q < Q; q++)
+#pragma unroll
+        for (int t = 0; t < BPT; t++) out[q][t][0] = a[q][t][0], out[q][t][1] = a[q][t][1];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Launch rules of the tiled kernels (launch_stage_a_batch, launch_stage_a_slice).
+// ---------------------------------------------------------------------------------------------
+// Queries of the next launch, given the queries left: groups of four, three or two (five: 3 + 2; six: 3 + 3; seven: 4 + 3); a single
+// one alone.
+constexpr u32 stage_a_query_group(u32 left) { return left == 5 || left == 6 ? 3 : left < 4 ? left : 4; }
+static_assert(stage_a_query_group(5) == 3 && stage_a_query_group(5 - 3) == 2, "five queries: 3 + 2");
+static_assert(stage_a_query_group(7) == 4 && stage_a_query_group(7 - 4) == 3, "seven queries: 4 + 3");
+
+// Bin layers per thread.  What bounds the kernel is the traffic through the L1s (profiles/r05/stage_a_batch_prefetch_really_in_flight.txt:
+// ~8.6 TB/s of L1 misses chip-wide, three quarters of them index words that a thread re-reads from the L2 once per GROUP of layers), so
+// groups should be as large as the registers allow: seven layers for one query (stage_a_mad_kernel's; the 128-bit accumulators of
+// one query spill beyond five), four for two queries, three for three queries (164 VGPRs either way: three waves per SIMD), three
+// for four (208: two waves -- still 4 % ahead of two layers).  r03-r04 had two layers for three queries: 81.7 us for twelve layers
+// against 69.9 with groups of three (tools/microbench_stage_a_batch.hip, r05).
+constexpr u32 stage_a_layer_cap(u32 Q, bool mad) { return Q == 1 ? (mad ? 7 : 5) : Q == 2 ? 4 : 3; }
+// ONE launch whatever the layer count: the last group is ragged (stage_a_terms) -- a remainder launch of one or two layers is all
+// latency (25 us for two layers alone), and two launches of half the groups each leave the chip a partial round of waves twice.  So:
+// the group size that issues the fewest loads per term over the launch, ceil(b / g) groups of 2 Q index words + g database words (a
+// ragged last group loads and multiplies its padding too: six layers of two queries are better off as 3 + 3 than as 4 + 2).
+constexpr u32 stage_a_layers(u32 Q, u32 b, u32 cap)
+{
+    u32 bpt = 1, best = ~0u;
+    for (u32 g = 1; g <= cap && g <= b; g++) {
+        const u32 loads = ((b + g - 1) / g) * (2 * Q + g);
+        if (loads <= best) best = loads, bpt = g;
+    }
+    return bpt;
+}
+static_assert(stage_a_layers(2, 6, stage_a_layer_cap(2, true)) == 3, "six layers of two queries: 3 + 3");
+static_assert(stage_a_layers(3, 12, stage_a_layer_cap(3, true)) == 3, "twelve layers of three queries: groups of three");
+
+// Terms in flight behind the one being accumulated (profiles/r03/stage_a_batch_microbench.txt; r05: two for the wide tilings).  One
+// query: stage_a_mad_kernel's four, and three with seven layers (176 registers with four, 168 are the most that leave three waves
+// per SIMD).
+constexpr int stage_a_depth(int Q, int BPT) { return Q == 1 ? (BPT == 7 ? 3 : 4) : (Q == 4 || Q * BPT >= 9) ? 2 : 3; }
 }  // namespace piehip

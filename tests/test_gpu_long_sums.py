@@ -1,7 +1,8 @@
 """Stage A over long index sums (reference BatchedFHEHIPPIE.cpp:101-116): sum_j idx[h][j] * db[h][bin][j] + minus.
 
-The three stage-A kernels accumulate lazily and reduce on a fixed period, each bound resting on a hand proof
-(nested_hashing_psi_amd/csrc/kernels_pie.hip, madasm.h):
+The three stage-A kernels of kernels_pie.hip accumulate lazily and reduce on a fixed period, each bound resting on a hand proof
+(nested_hashing_psi_amd/csrc/kernels_pie.hip, madasm.h; the term loop of stage_a_mad_batch_kernel is stage_a_terms of
+stage_a_common.h, which the sliced kernel shares: tests/test_gpu_query_slices.py runs that one at the periods):
   stage_a_mad_kernel, stage_a_mad_batch_kernel   every modulus in (2^59, 2^60): 30-bit column accumulators, a carry sweep
         after every COLACC_MAX_TERMS = 8 terms (16 products < 2^60 in column 1), a mid-sum reduction after every
         COLACC_MAX_TOTAL = 15 (the top column: 15 products, a value below 2^124), colacc_reduce<true> in the epilogue
@@ -12,9 +13,9 @@ proof allows still does not wrap), so the index and database words here are ever
 [q - 2^24, q): the columns as full as the moduli allow, data that still tells lanes, layers and queries apart.  E runs
 across the periods (31..33, 63..65, 119..121 where both MAD periods line up and E = 120 hands the epilogue 8 uncarried and
 15 unreduced terms at once, 148, 240, 581) and b / nq pick every template instantiation (the `kernels` column, from the
-launcher rules in kernels_pie.hip: launch_stage_a and launch_stage_a_batch).  Every result is compared bit for bit with the
-oracle's run() (oracle/pie_oracle.c: one mulmod + addmod per term, independent of the GPU's lazy scheme); K = 2, so stage A
-feeds the whole product chain.
+launcher rules: launch_stage_a in kernels_pie.hip; for launch_stage_a_batch, stage_a_query_group / stage_a_layers / stage_a_depth
+in stage_a_common.h).  Every result is compared bit for bit with the oracle's run() (oracle/pie_oracle.c: one mulmod + addmod per
+term, independent of the GPU's lazy scheme); K = 2, so stage A feeds the whole product chain.
 
 test_reference_long_rows runs rows of the reference's parameter table with E > 56 (Performance-Evaluation/Parameters1.txt)
 end to end through the hashing harness: device offline phase, encryption, run(), decryption, scan.

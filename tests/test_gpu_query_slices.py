@@ -9,7 +9,8 @@ Shapes stay small; the sizes are the ones at which the code takes another path: 
 transform: a batch's operand X is placed lane-ordered inside the QP operand array), 16384 (folded outer stage); E past one carry
 sweep (COLACC_MAX_TERMS = 8) and past one full reduction (COLACC_MAX_TOTAL = 15; 40 passes two); odd bin counts on two queues; one
 to five queries per run (query groups 1, 2, 3, 3 + 2); partitions with one unit each, a slice across two hash functions, empty unit
-slices and empty bin slices.  At most ten handles per process."""
+slices and empty bin slices; every instance of the sliced kernel at its reduction periods with worst-case residues (N = 1024).  At most
+ten handles per process."""
 import ctypes as C
 
 import numpy as np
@@ -161,6 +162,26 @@ def test_61_bit_chain(ob, pie):
 def test_worst_case_residues(ob, pie, N, nq):
     """q - 1 everywhere in the database and in the first query, over 17 terms"""
     _case(ob, pie, N=N, E=17, b=2, nq=nq, G=2, extreme=True)
+
+
+# ---- the reduction periods, in every instance of the sliced kernel ---------------------------------------------------------------
+# (arithmetic, E, nq, b, instance reached).  The sliced launcher takes one query group per run (nq <= 4: one group of nq) and, by
+# the layer rule (stage_a_common.h: stage_a_layers under stage_a_layer_cap), exactly b layers per thread for every b up to the cap
+# of (nq, arithmetic): each case launches stage_a_slice_kernel<BPT = b, Q = nq, DEPTH, MAD> and no other instance, 17 with column
+# accumulators and 15 with 128-bit ones.  E = 120: both column-accumulator periods line up, the epilogue gets 8 uncarried and 15
+# unreduced terms; E = 65: past two 32-term reductions of the 128-bit accumulators.  Every database and first-query word is q - 1.
+PERIOD_CASES = ([("mad", 120, nq, b, "slice<%d, %d, %d, mad>" % (b, nq, depth))
+                 for nq, cap in ((1, 7), (2, 4), (3, 3), (4, 3)) for b in range(1, cap + 1)
+                 for depth in [(3 if b == 7 else 4) if nq == 1 else 2 if nq == 4 or nq * b >= 9 else 3]] +
+                [("u128", 65, nq, b, "slice<%d, %d, %d, 128-bit>" % (b, nq, depth))
+                 for nq, cap in ((1, 5), (2, 4), (3, 3), (4, 3)) for b in range(1, cap + 1)
+                 for depth in [4 if nq == 1 else 2 if nq == 4 or nq * b >= 9 else 3]])
+assert len(PERIOD_CASES) == 17 + 15
+
+
+@pytest.mark.parametrize("arith,E,nq,b,kernel", PERIOD_CASES, ids=["%s-E%d-nq%d-b%d" % c[:4] for c in PERIOD_CASES])
+def test_periods_in_every_slice_instance(ob, pie, arith, E, nq, b, kernel):
+    _case(ob, pie, N=1024, L=2, K=2, E=E, b=b, nq=nq, G=2, extreme=True, below=None if arith == "mad" else 1 << 61)
 
 
 # ---- partitions -----------------------------------------------------------------------------------------------------------------

@@ -22,7 +22,7 @@ static void run(const char *name, const DevConsts *dc, u32 N, u32 L, u32 K, u32 
         // other kernels' traffic has evicted it by the time stage A comes round again
         const u64 *db = db0 + (size_t)(rep % NBUF) * DBW;
         CK(hipEventRecord(e0, 0));
-        hipLaunchKernelGGL(stage_a_mad_kernel<BPT>, grid, dim3(TPB), 0, 0, dc, N, L, K, b, E, idx, minus, db, acc, b, 0u);
+        hipLaunchKernelGGL(stage_a_mad_kernel<BPT>, grid, dim3(TPB), 0, 0, dc, N, L, K, b, E, idx, minus, db, acc, b, 0u, 1u, 0u, StageAXOut{});
         CK(hipEventRecord(e1, 0));
         CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
