@@ -297,6 +297,31 @@ int piehip_gather_results_host(piehip_handle h, uint32_t b_total, int root, uint
  *   piehip_rccl_agree   *all_ok = (every rank passed ok != 0): one all-reduced word + piehip_rccl_wait; called at the end of a phase
  *                       (database built, key loaded) so that a failure on one rank ends the session on all of them BEFORE anybody
  *                       enters a collective the failed rank will not join.  Not part of the per-query path. */
+/* Query slices across the ranks ("Query slices" below; the plan of both calls: csrc/exchange_plan.h).  Rank r of G is a query-sliced
+ * handle with the units of piehip_query_slice(K, L, G, r) and the bin layers of piehip_rccl_bin_slice(b, G, r); no rank needs the
+ * whole query, and no rank but the root ever holds it.  Per batch of queries, every rank calls, in this order: piehip_rccl_scatter_query,
+ * piehip_run_slice, piehip_rccl_exchange_accumulators, piehip_run_chain, piehip_gather_results(_host), piehip_rccl_wait.
+ *   piehip_rccl_scatter_query          (BatchedFHEPSIServer.cpp:114-141, the query's way in; BatchedFHEHIPPIE.hpp:40-48) the root cuts every
+ *                                      rank's slices out of its piehip_slice_host_buffers_q arrays -- one strided copy per unit and piece
+ *                                      into a device staging area in unit order -- and sends each rank the contiguous ranges of its units:
+ *                                      per query the index slice [u_n][E][2][N] and the minus slice [u_n][2][N], straight into the
+ *                                      receiver's owned slice inputs, which the next piehip_run_slice reads (a pending expansion of such a
+ *                                      piece is cancelled, as by any unseeded setter).  The root's own units are a device copy; a rank
+ *                                      without units takes no part.  All nq queries in ONE group call on the handle's stream; the host
+ *                                      arrays must stay unchanged until the next piehip_sync or piehip_rccl_wait.
+ *   piehip_rccl_exchange_accumulators  (BatchedFHEHIPPIE.cpp:117: the accumulators as the chain reads them) after piehip_run_slice: rank s
+ *                                      sends rank d the rows [bin_lo_d, bin_hi_d) of its acc_slice, one contiguous block; d receives it
+ *                                      into a staging buffer (allocated at the first exchange of a shape and kept).  One group call on the
+ *                                      handle's stream; then ONE placement launch puts every unit 0 .. K L - 1 -- the received blocks and
+ *                                      the handle's own rows -- into the chain side, behind the queues of the handle's last run_chain, as
+ *                                      piehip_put_accumulators does for one source.  All units count as put: piehip_run_chain follows.
+ * Both refuse before anything is queued, and a refused call changes nothing: PIEHIP_ESTATE without a communicator, on an unsliced handle,
+ * when a unit has already been put in this round (exchange), when the root has not asked for its host arrays (scatter); PIEHIP_EINVAL for
+ * a null handle, a root outside the communicator, and unit or bin ranges that are not the rule's for (nranks, rank) -- the peers' ranges
+ * are derived, not exchanged.  piehip_gather_results(_host) serves a sliced handle after piehip_run_chain as it serves any other,
+ * a rank without bin layers included. */
+int piehip_rccl_scatter_query(piehip_handle h, int root);
+int piehip_rccl_exchange_accumulators(piehip_handle h);
 int piehip_rccl_wait(piehip_handle h, uint32_t timeout_ms);
 int piehip_rccl_abort(piehip_handle h);
 int piehip_rccl_agree(piehip_handle h, int ok, int *all_ok, uint32_t timeout_ms);
@@ -378,6 +403,11 @@ int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
  *                                 encodes only its units' limbs (the forward transform runs for those limbs only); the masks of its bin
  *                                 layers are the ones the unsharded call draws.  Refuses K = 1 as every hashing entry point does.
  *                                 Synchronous, on the handle's stream.
+ *   piehip_build_db_sliced        (.cpp:45-82, with the table's construction at :45-66 on the device) piehip_build_db_bins' offline phase for a
+ *                                 sliced handle: the server set is hashed and the whole table shuffled in HBM, where it stays -- no round
+ *                                 trip through host memory -- and then encoded as piehip_load_db_table_sliced encodes its table: the units'
+ *                                 limbs, the masks of the chain side's layers.  The same seeds give slices of the one database that
+ *                                 piehip_build_db makes.  K = 1 refused; PIEHIP_EHASH when the Cuckoo insertion fails.  Synchronous.
  *   piehip_load_db_sliced         the same from arrays: pts_slice[u_n][b][E][N] (unit u: limb u % L of pts[u / L][.][.] of piehip_load_db),
  *                                 masks[bin_hi - bin_lo][L][N].  Any K >= 1.  Synchronous.
  *   piehip_get_query_slice        the four bounds of a sliced handle
@@ -397,6 +427,10 @@ int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
  *                                 writes over an unseeded input (the contract of the host-memory path)
  *   piehip_set_*_slice_seeded_from_q  the same cut out of the WHOLE c0 arrays in host memory (c0idx[K][E][L][N], c0minus[L][N]): one strided
  *                                 copy per unit.  Per query a handle receives (E + 1) N 8 bytes per unit: half of the unseeded bytes
+ *   piehip_slice_host_buffers_q   (.hpp:40-48: where setIndex / setMinusCompareElement find their arguments) page-locked arrays for the WHOLE
+ *                                 query q, idx[K][E][2][L][N] and minus[2][L][N], owned by the sliced handle and allocated at the first call
+ *                                 that asks for them (a null out-pointer allocates nothing): where the rank that holds the client's channel
+ *                                 writes a query for piehip_rccl_scatter_query
  *   piehip_set_*_slice_device_q   arrays in HBM, no copy taken; ordered as piehip_set_index_device is (written on the handle's stream, or complete)
  *                                 piehip_set_query_batch sizes everything for nq queries, as on any handle
  *   piehip_run_slice              (.cpp:96-116) stage A of the handle's units, all b layers, all nq queries, into the handle's acc_slice: one
@@ -426,6 +460,9 @@ int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
 int piehip_query_slice(uint32_t K, uint32_t L, int nranks, int rank, uint32_t *u_lo, uint32_t *u_hi);
 int piehip_load_db_table_sliced(piehip_handle h, const uint64_t *tbl, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
                                 uint64_t shuffle_seed, uint64_t mask_seed, uint32_t u_lo, uint32_t u_hi, uint32_t bin_lo, uint32_t bin_hi);
+int piehip_build_db_sliced(piehip_handle h, const uint64_t *items, size_t n, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
+                           uint64_t hash_seed, uint64_t evict_seed, uint64_t shuffle_seed, uint64_t mask_seed, uint32_t u_lo, uint32_t u_hi,
+                           uint32_t bin_lo, uint32_t bin_hi);
 int piehip_load_db_sliced(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, uint32_t u_lo, uint32_t u_hi,
                           const uint64_t *pts_slice /*[u_n][b][E][N]*/, uint32_t bin_lo, uint32_t bin_hi, const uint64_t *masks /*[bin_n][L][N]*/);
 int piehip_get_query_slice(piehip_handle h, uint32_t *u_lo, uint32_t *u_hi, uint32_t *bin_lo, uint32_t *bin_hi);
@@ -437,6 +474,7 @@ int piehip_set_index_slice_seeded_q(piehip_handle h, uint32_t q, const uint64_t 
 int piehip_set_minus_slice_seeded_q(piehip_handle h, uint32_t q, const uint64_t *c0_slice /*[u_n][N]*/, const uint8_t *seed /*[32]*/);
 int piehip_set_index_slice_seeded_from_q(piehip_handle h, uint32_t q, const uint64_t *c0idx /*[K][E][L][N]*/, const uint8_t *seeds /*[K][E][32]*/);
 int piehip_set_minus_slice_seeded_from_q(piehip_handle h, uint32_t q, const uint64_t *c0minus /*[L][N]*/, const uint8_t *seed /*[32]*/);
+int piehip_slice_host_buffers_q(piehip_handle h, uint32_t q, uint64_t **idx /*[K][E][2][L][N]*/, uint64_t **minus /*[2][L][N]*/);
 int piehip_set_index_slice_device_q(piehip_handle h, uint32_t q, const void *d_idx_slice);
 int piehip_set_minus_slice_device_q(piehip_handle h, uint32_t q, const void *d_minus_slice);
 int piehip_run_slice(piehip_handle h);

@@ -144,6 +144,10 @@ SYMBOLS = {
     "piehip_put_accumulators_from": (C.c_int, [C.c_void_p, C.c_void_p]),
     "piehip_run_chain": (C.c_int, [C.c_void_p]),
     "piehip_run_chain_into": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "piehip_build_db_sliced": (C.c_int, [C.c_void_p, u64p, C.c_size_t] + [C.c_uint32] * 5 + [C.c_uint64] * 4 + [C.c_uint32] * 4),
+    "piehip_slice_host_buffers_q": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(u64p), C.POINTER(u64p)]),
+    "piehip_rccl_scatter_query": (C.c_int, [C.c_void_p, C.c_int]),
+    "piehip_rccl_exchange_accumulators": (C.c_int, [C.c_void_p]),
 }
 
 _lib = None

@@ -240,6 +240,17 @@ void launch_stage_a_slice(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, u
 // instead (where stage A of an unsliced batch puts them: StageAXOut)
 void launch_place_accumulators(u32 N, u32 L, u32 K, u32 u_lo, u32 un, u32 bin_lo, u32 bn, u32 nq, const u64 *src, u64 *acc,
                                const StageAXOut *xo, hipStream_t st);
+// ... of all K L units in one launch, each from the block that holds it: unit u is unit u - u_lo of base[row0 + rows][un][2][N]
+// (row = bin layer x query of the chain side; row0: the block's row that is the chain side's first).  K L <= PLACE_MAX_UNITS
+static const u32 PLACE_MAX_UNITS = 64;
+struct PlaceSource {
+    const u64 *base;
+    u32 row0, u_lo, un;
+};
+struct PlaceSources {
+    PlaceSource of[PLACE_MAX_UNITS];
+};
+void launch_place_units(u32 N, u32 L, u32 K, u32 rows, const PlaceSources &src, u64 *acc, const StageAXOut *xo, hipStream_t st);
 
 // ---- offline phase: nested hashing and database gather on the device (kernels_hash.hip) -----------------------
 size_t hash_sort_temp_bytes(u32 n, u32 e);

@@ -137,4 +137,33 @@ void launch_place_accumulators(u32 N, u32 L, u32 K, u32 u_lo, u32 un, u32 bin_lo
     hipLaunchKernelGGL(place_accumulators_kernel, grid, dim3(TPB), 0, st, N, L, K, u_lo, un, bin_lo, nq, src, acc, xo);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Placement of every unit at once (piehip_rccl_exchange_accumulators): the chain side's rows of all K L units in one launch, each
+// unit from the block that holds it -- the handle's own acc_slice or a block received from the rank that computed the unit.  The
+// table of sources comes by value and is indexed by the unit, which is uniform over a workgroup (blockIdx.y): the look-up is scalar
+// loads from the kernel arguments.  A block is src[rows from row0][un][2][N] with its units from u_lo; loads, stores and the lane
+// order of operand X are those of place_accumulators_kernel.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(TPB) place_units_kernel(u32 N, u32 L, u32 K, PlaceSources src, u64 *__restrict__ acc, StageAXOut xo)
+{
+    const u32 n = 2 * (blockIdx.x * TPB + threadIdx.x);
+    if (n >= N) return;
+    const u32 u = blockIdx.y, row = blockIdx.z >> 1, c = blockIdx.z & 1;   // row = beta * nq + q of the chain side
+    const PlaceSource s = src.of[u];
+    const u32 h = u / L, l = u % L;
+    const bool xdir = h == 0 && xo.out != nullptr;
+    const u32 noff = n + ((xdir ? ~0u : 0u) & (lane_home(n, xo.logns) - n));
+    const u64 *ps = s.base + ((((size_t)s.row0 + row) * s.un + (u - s.u_lo)) * 2 + c) * N + n;
+    u64 *const base = xdir ? xo.out + (((size_t)row * 4 + c) * xo.M + l) * N : acc + ((((size_t)row * K + h) * 2 + c) * L + l) * N;
+    *reinterpret_cast<u64x2 *>(base + noff) = *reinterpret_cast<const u64x2 *>(ps);
+}
+void launch_place_units(u32 N, u32 L, u32 K, u32 rows, const PlaceSources &src, u64 *acc, const StageAXOut *xop, hipStream_t st)
+{
+    if (!rows || K * L > PLACE_MAX_UNITS) return;
+    StageAXOut xo;
+    if (xop) xo = *xop;
+    dim3 grid((N / 2 + TPB - 1) / TPB, K * L, rows * 2);   // (z <= 65535, as above)
+    hipLaunchKernelGGL(place_units_kernel, grid, dim3(TPB), 0, st, N, L, K, src, acc, xo);
+}
+
 }  // namespace piehip

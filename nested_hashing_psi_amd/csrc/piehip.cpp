@@ -713,28 +713,21 @@ int piehip_reserve(piehip_handle h, size_t n, uint32_t k, uint32_t e, uint32_t K
     return query_input_buffers(h, 0, &di, &dm);
 }
 
-int piehip_build_db_bins(piehip_handle h, const uint64_t *items, size_t n, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
-                         uint64_t hash_seed, uint64_t evict_seed, uint64_t shuffle_seed, uint64_t mask_seed, uint32_t bin_lo,
-                         uint32_t bin_hi)
+// The offline phase as far as the encoder (BatchedFHEHIPPIE.cpp:45-66): the server set hashed into the handle's table buffer
+// [k][e][K][b][E] on the device, its rows shuffled, its slot vectors gathered into *d_slots [max(K b E, b)][k e], carved from the
+// caller's scratch (piehip_build_db_bins, piehip_build_db_sliced)
+extern "C++" int piehip::items_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *items, size_t n, u32 k, u32 e, u32 K, u32 b, u32 E, u64 hash_seed,
+                                        u64 evict_seed, u64 shuffle_seed, int64_t **d_slots_out)
 {
-    NEED(h);
-    if (!items || !n || n > 0x7FFFFFFFu) return fail(PIEHIP_EINVAL, "empty or oversized server set");
-    if (k < 1 || e < 1) return fail(PIEHIP_EINVAL, "need at least one outer hash function and position");
-    if (K < 2) return fail(PIEHIP_EINVAL, "Cuckoo Table needs more than one hash function!");  // CuckooHashTable.cpp:39-42
-    if (bin_lo >= bin_hi || bin_hi > b) return fail(PIEHIP_EINVAL, "bin-layer slice must be non-empty and within [0, b)");
     const size_t B = (size_t)k * e;
-    if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size k*e exceeds the ring dimension");
-    HIPCHK(hipSetDevice(h->device));
-    int rc = alloc_run_buffers(h, K, bin_hi - bin_lo, E);
-    if (rc) return rc;
     const size_t tbl_words = B * K * b * E;
+    int rc;
     if ((rc = hash_tbl_alloc(h, tbl_words))) return rc;
     h->hk = k;
     h->he = e;
     h->hb = b;
     std::vector<u64> tab;
     tabulation_tables(hash_seed, k + K, tab);
-    Tmp tmp(h);
     TMPGET(d_tab, tab.size());
     TMPGET(d_items, n);
     TMPGET(d_keys, n + 1);      // 2 n u32
@@ -763,6 +756,27 @@ int piehip_build_db_bins(piehip_handle h, const uint64_t *items, size_t n, uint3
     HIPCHK(hipStreamSynchronize(h->stream));
     if (failed & 1u) return fail(PIEHIP_EHASH, "(Blocked) Cuckoo hashing error");
     if (failed & 2u) return fail(PIEHIP_EINVAL, "server item does not fit the plaintext modulus");
+    *d_slots_out = d_slots;
+    return PIEHIP_OK;
+}
+
+int piehip_build_db_bins(piehip_handle h, const uint64_t *items, size_t n, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
+                         uint64_t hash_seed, uint64_t evict_seed, uint64_t shuffle_seed, uint64_t mask_seed, uint32_t bin_lo,
+                         uint32_t bin_hi)
+{
+    NEED(h);
+    if (!items || !n || n > 0x7FFFFFFFu) return fail(PIEHIP_EINVAL, "empty or oversized server set");
+    if (k < 1 || e < 1) return fail(PIEHIP_EINVAL, "need at least one outer hash function and position");
+    if (K < 2) return fail(PIEHIP_EINVAL, "Cuckoo Table needs more than one hash function!");  // CuckooHashTable.cpp:39-42
+    if (bin_lo >= bin_hi || bin_hi > b) return fail(PIEHIP_EINVAL, "bin-layer slice must be non-empty and within [0, b)");
+    const size_t B = (size_t)k * e;
+    if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size k*e exceeds the ring dimension");
+    HIPCHK(hipSetDevice(h->device));
+    int rc = alloc_run_buffers(h, K, bin_hi - bin_lo, E);
+    if (rc) return rc;
+    Tmp tmp(h);
+    int64_t *d_slots = nullptr;
+    if ((rc = items_to_slots(h, tmp, items, n, k, e, K, b, E, hash_seed, evict_seed, shuffle_seed, &d_slots))) return rc;
     return encode_bin_layers(h, d_slots, K, b, E, (u32)B, bin_lo, bin_hi, mask_seed);
 }
 

@@ -6,7 +6,8 @@
 //   piehip_ops.cpp     the OpenFHE primitives one by one (parity tests), NTT timing, per-kernel profiling
 //   piehip_fhepie.cpp  the rotation-based sibling operator (FHEHIPPIE)
 //   piehip_client.cpp  client-side harness (key generation, encryption, decryption)
-//   piehip_rccl.cpp    the final gather of a sharded server over RCCL
+//   piehip_rccl.cpp    the collectives of a sharded server over RCCL: the final gather, the query's broadcast, and the scatter and
+//                      exchange of query slices (exchange_plan.h: who sends what to whom and in which order, free of HIP)
 //   piehip_slice.cpp   query-sliced stage A: a handle's (inner hash function, limb) units, the accumulators' way to the chain side
 //                      (slice_geometry.h: the copies that bring its inputs up, free of HIP)
 #pragma once
@@ -25,6 +26,7 @@
 
 #include "kernels.hpp"
 #include "params.hpp"
+#include "exchange_plan.h"
 #include "slice_geometry.h"
 
 namespace piehip {
@@ -124,6 +126,12 @@ struct SliceState {
     std::vector<bool> put;             // [K L]: units placed since the last piehip_run_chain or batch-size change
     hipEvent_t ev_ready = nullptr;     // recorded on this handle's stream for a reader of acc on another stream (piehip_put_accumulators_from),
     hipEvent_t ev_read = nullptr;      // ... and on this handle's stream behind its own placement launch, for the source to wait on
+    // across the ranks of a sharded server (piehip_rccl.cpp; exchange_plan.h)
+    u64 *pin_idx[STAGE_A_MAX_QUERIES] = {}, *pin_minus[STAGE_A_MAX_QUERIES] = {};   // piehip_slice_host_buffers_q: the whole query, page-locked
+    u64 *scatter_stage = nullptr;      // the root's staging area [nq][idx[K L][E][2][N], minus[K L][2][N]], allocated at the first scatter of a shape
+    size_t scatter_words = 0;
+    u64 *xchg_stage = nullptr;         // the received blocks of the exchange, bin_n nq 2N K L words, allocated at the first exchange of a shape
+    size_t xchg_words = 0;
     u32 u_n() const { return u_hi - u_lo; }
 };
 
@@ -365,6 +373,8 @@ int hash_tbl_alloc(piehip_ctx *h, size_t words);
 // (hidden: the library's dynamic symbols stay the ones they were)
 __attribute__((visibility("hidden"))) int table_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *tbl, u32 k, u32 e, u32 K, u32 b, u32 E,
                                                           u64 shuffle_seed, int64_t **d_slots);
+__attribute__((visibility("hidden"))) int items_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *items, size_t n, u32 k, u32 e, u32 K, u32 b, u32 E,
+                                                          u64 hash_seed, u64 evict_seed, u64 shuffle_seed, int64_t **d_slots);
 // piehip_run.cpp: the queues of piehip_run_into / piehip_run_chain_into (host_results, piehip_run_staged: every queue group also
 // downloads its slice of the results there); whether stage A hands operand X over in lane order
 int run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *host_results = nullptr);

@@ -413,4 +413,152 @@ int piehip_rccl_broadcast_query(piehip_handle h, int root)
     return PIEHIP_OK;
 }
 
+// ---- query slices across the ranks (exchange_plan.h; DESIGN.md section 6 "Query slices across processes") ------------------------------
+// what both calls refuse, before anything is queued: no communicator, an unsliced handle, ranges other than the rule's for this rank
+// (every rank derives its peers' ranges from the rule: nobody exchanges them)
+static int sliced_rank_check(const piehip_ctx *h, const char *who)
+{
+    if (!h->comm) return fail(PIEHIP_ESTATE, std::string(who) + ": no communicator (piehip_rccl_init / piehip_rccl_attach)");
+    const SliceState &s = h->slice;
+    if (!s.on) return fail(PIEHIP_ESTATE, std::string(who) + ": not a query-sliced handle (piehip_build_db_sliced / piehip_load_db_sliced)");
+    u32 u_lo, u_hi, bin_lo, bin_hi;
+    plan_range(h->K * h->hp.L, h->comm_ranks, h->comm_rank, &u_lo, &u_hi);
+    plan_range(s.b_total, h->comm_ranks, h->comm_rank, &bin_lo, &bin_hi);
+    if (u_lo != s.u_lo || u_hi != s.u_hi || bin_lo != s.bin_lo || bin_hi != s.bin_hi)
+        return fail(PIEHIP_EINVAL, std::string(who) + ": the handle's unit or bin-layer range is not its rank's (piehip_query_slice, piehip_rccl_bin_slice)");
+    return PIEHIP_OK;
+}
+
+static ExchangeShape exchange_shape(const piehip_ctx *h) { return {h->K, h->hp.L, h->slice.b_total, h->nq, h->hp.N, h->E}; }
+
+// a device buffer of a call, kept while its size stays: the stream drains before it is replaced
+static int keep_buffer(piehip_ctx *h, u64 **buf, size_t *have, size_t words)
+{
+    if (*have == words) return PIEHIP_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    dev_free(buf);
+    *have = 0;
+    const int rc = dev_alloc(buf, words);
+    if (rc) return rc;
+    *have = words;
+    return PIEHIP_OK;
+}
+
+// one group call of a plan's transfers in its posting order; base(t): the device address transfer t's offset counts from
+extern "C++" template <typename Base>
+static int post_transfers(piehip_ctx *h, const Rccl *R, const std::vector<PlanTransfer> &plan, Base base, const char *who)
+{
+    if (plan.empty()) return PIEHIP_OK;
+    const ncclComm_t comm = (ncclComm_t)h->comm;
+    NCCLCHK(R, R->GroupStart());
+    ncclResult_t gr = ncclSuccess;
+    for (size_t i = 0; i < plan.size() && gr == ncclSuccess; i++) {
+        const PlanTransfer &t = plan[i];
+        u64 *p = base(t) + t.off;
+        gr = t.send ? R->Send(p, t.words, ncclUint64, t.peer, comm, h->stream) : R->Recv(p, t.words, ncclUint64, t.peer, comm, h->stream);
+    }
+    const ncclResult_t ge = R->GroupEnd();
+    if (gr != ncclSuccess || ge != ncclSuccess) return fail(PIEHIP_EHIP, std::string(who) + ": " + R->GetErrorString(gr != ncclSuccess ? gr : ge));
+    return PIEHIP_OK;
+}
+
+int piehip_rccl_scatter_query(piehip_handle h, int root)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    int rc = sliced_rank_check(h, "rccl_scatter_query");
+    if (rc) return rc;
+    const int G = h->comm_ranks, me = h->comm_rank;
+    if (root < 0 || root >= G) return fail(PIEHIP_EINVAL, "rccl_scatter_query: root outside the communicator");
+    SliceState &s = h->slice;
+    const u32 N = h->hp.N, L = h->hp.L, E = h->E, KL = h->K * L, un = s.u_n();
+    for (u32 q = 0; me == root && q < h->nq; q++)
+        if (!s.pin_idx[q] || !s.pin_minus[q])
+            return fail(PIEHIP_ESTATE, "rccl_scatter_query: the root has no host arrays for a query of the batch (piehip_slice_host_buffers_q)");
+    const Rccl *R = rccl();
+    if (!R) return no_rccl();
+    join_pending(h);
+    mark_dirty(h);
+    HIPCHK(hipSetDevice(h->device));
+    for (u32 q = 0; un && q < h->nq; q++)
+        for (int p = 0; p < SLICE_PIECES; p++) {
+            SliceInput &in = s.in[q][p];
+            if (!in.own && (rc = dev_alloc(&in.own, (size_t)un * piece_cts(p, E) * 2 * N))) return rc;
+        }
+    // the root's staging area, per query idx[K L][E][2][N] then minus[K L][2][N]: every unit cut out of the page-locked whole-query
+    // arrays by the strided copies of a slice setter (slice_geometry.h, one per unit and piece), so that a rank's units are contiguous
+    const size_t mw = 2 * (size_t)N, iw = mw * E, perq = (size_t)KL * (iw + mw);
+    if (me == root) {
+        if ((rc = keep_buffer(h, &s.scatter_stage, &s.scatter_words, perq * h->nq))) return rc;
+        for (u32 q = 0; q < h->nq; q++)
+            for (int p = 0; p < SLICE_PIECES; p++) {
+                const u64 *src = p == SLICE_INDEX ? s.pin_idx[q] : s.pin_minus[q];
+                u64 *dst = s.scatter_stage + q * perq + (p == SLICE_INDEX ? 0 : (size_t)KL * iw);
+                for (u32 u = 0; u < KL; u++) {
+                    const SliceCopy g = slice_copy((SlicePiece)p, SLICE_WHOLE, false, N, L, E, 0, KL, u);
+                    HIPCHK(hipMemcpy2DAsync(dst + g.dst_off, g.dst_pitch * sizeof(u64), src + g.src_off, g.src_pitch * sizeof(u64), N * sizeof(u64),
+                                            g.rows, hipMemcpyHostToDevice, h->stream));
+                }
+            }
+    }
+    auto base = [&](const PlanTransfer &t) -> u64 * {
+        switch (t.buf) {
+        case PLAN_STAGE_INDEX: return s.scatter_stage + t.q * perq;
+        case PLAN_STAGE_MINUS: return s.scatter_stage + t.q * perq + (size_t)KL * iw;
+        case PLAN_OWN_INDEX: return s.in[t.q][SLICE_INDEX].own;
+        default: return s.in[t.q][SLICE_MINUS].own;
+        }
+    };
+    if ((rc = post_transfers(h, R, scatter_plan(exchange_shape(h), G, me, root), base, "rccl_scatter_query"))) return rc;
+    for (u32 q = 0; un && q < h->nq; q++) {
+        if (me == root) {   // the root's own units: a device copy
+            const u64 *st = s.scatter_stage + q * perq;
+            HIPCHK(hipMemcpyAsync(s.in[q][SLICE_INDEX].own, st + s.u_lo * iw, un * iw * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(s.in[q][SLICE_MINUS].own, st + (size_t)KL * iw + s.u_lo * mw, un * mw * sizeof(u64), hipMemcpyDeviceToDevice,
+                                  h->stream));
+        }
+        // the next piehip_run_slice reads the owned copies; nothing is expanded over them (as after any unseeded setter)
+        for (SliceInput &in : s.in[q]) in.cur = in.own, in.seeded = false;
+    }
+    return PIEHIP_OK;
+}
+
+int piehip_rccl_exchange_accumulators(piehip_handle h)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    int rc = sliced_rank_check(h, "rccl_exchange_accumulators");
+    if (rc) return rc;
+    SliceState &s = h->slice;
+    const int G = h->comm_ranks, me = h->comm_rank;
+    const u32 KL = h->K * h->hp.L, bn = s.bin_hi - s.bin_lo;
+    if (KL > PLACE_MAX_UNITS) return fail(PIEHIP_EINVAL, "rccl_exchange_accumulators: more units than one placement launch takes");
+    for (u32 u = 0; u < KL; u++)
+        if (s.put[u]) return fail(PIEHIP_ESTATE, "rccl_exchange_accumulators: a unit has been put since the last piehip_run_chain");
+    if (s.u_n() && (!s.acc || s.acc_nq != h->nq)) return fail(PIEHIP_ESTATE, "rccl_exchange_accumulators: no accumulator buffer");
+    if (bn && (!h->d_acc || !h->ws.eqp)) return fail(PIEHIP_ESTATE, "rccl_exchange_accumulators: no workspace (an earlier allocation failed)");
+    const Rccl *R = rccl();
+    if (!R) return no_rccl();
+    join_pending(h);   // the placement writes what the queues of the last piehip_run_chain read
+    mark_dirty(h);
+    HIPCHK(hipSetDevice(h->device));
+    const ExchangeShape shape = exchange_shape(h);
+    if ((rc = keep_buffer(h, &s.xchg_stage, &s.xchg_words, G > 1 ? plan_acc_stage_words(shape, bn) : 0))) return rc;
+    auto base = [&](const PlanTransfer &t) -> u64 * { return t.buf == PLAN_ACC_SLICE ? s.acc : s.xchg_stage; };
+    if ((rc = post_transfers(h, R, exchange_plan(shape, G, me), base, "rccl_exchange_accumulators"))) return rc;
+    if (bn) {   // every unit from the block that holds it, in one launch
+        PlaceSources src = {};
+        for (u32 u = 0; u < KL; u++) {
+            const PlanUnitSource us = plan_unit_source(shape, G, me, u);
+            src.of[u] = {us.own ? s.acc : s.xchg_stage + us.off, us.own ? s.bin_lo * h->nq : 0u, us.u_lo, us.u_n};
+        }
+        StageAXOut xo;
+        const bool x_direct = run_x_direct(h);
+        if (x_direct) xo.out = h->ws.eqp, xo.M = h->hp.M, xo.logns = h->plan.lane_logn;
+        ProfScope ps(h, PIEHIP_K_OTHER, 16.0 * h->hp.N * (double)bn * h->nq * KL * 2);
+        launch_place_units(h->hp.N, h->hp.L, h->K, bn * h->nq, src, h->d_acc, x_direct ? &xo : nullptr, h->stream);
+        HIPCHK(hipGetLastError());
+    }
+    std::fill(s.put.begin(), s.put.end(), true);
+    return PIEHIP_OK;
+}
+
 }  // extern "C"

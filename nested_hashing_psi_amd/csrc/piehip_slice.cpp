@@ -24,6 +24,12 @@ void slice_free(piehip_ctx *h)
     if (s.ev_jobs) (void)hipEventDestroy(s.ev_jobs);
     if (s.pin_jobs) (void)hipHostFree(s.pin_jobs);
     if (s.d_jobs) (void)hipFree(s.d_jobs);
+    for (u64 *p : s.pin_idx)
+        if (p) (void)hipHostFree(p);
+    for (u64 *p : s.pin_minus)
+        if (p) (void)hipHostFree(p);
+    dev_free(&s.scatter_stage);
+    dev_free(&s.xchg_stage);
     s = SliceState();
 }
 
@@ -270,6 +276,45 @@ int piehip_load_db_table_sliced(piehip_handle h, const uint64_t *tbl, uint32_t k
     launch_mask_slots(h->hp.t, b, (u32)B, mask_seed, d_slots, h->stream);
     if ((rc = encode_on_device(h, d_slots + (size_t)bin_lo * B, bin_hi - bin_lo, (u32)B, h->d_masks))) return rc;
     return make_masks_sigma(h);
+}
+
+int piehip_build_db_sliced(piehip_handle h, const uint64_t *items, size_t n, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
+                           uint64_t hash_seed, uint64_t evict_seed, uint64_t shuffle_seed, uint64_t mask_seed, uint32_t u_lo, uint32_t u_hi,
+                           uint32_t bin_lo, uint32_t bin_hi)
+{
+    NEED(h);
+    if (!items || !n || n > 0x7FFFFFFFu) return fail(PIEHIP_EINVAL, "empty or oversized server set");
+    if (k < 1 || e < 1) return fail(PIEHIP_EINVAL, "need at least one outer hash function and position");
+    if (K < 2) return fail(PIEHIP_EINVAL, "Cuckoo Table needs more than one hash function!");  // CuckooHashTable.cpp:39-42
+    const size_t B = (size_t)k * e;
+    if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size k*e exceeds the ring dimension");
+    int rc = slice_setup(h, K, b, E, u_lo, u_hi, bin_lo, bin_hi);
+    if (rc) return rc;
+    // the table is hashed, shuffled and gathered where it stays: in HBM (piehip_build_db_bins' steps), then encoded as
+    // piehip_load_db_table_sliced encodes the one it was handed
+    Tmp tmp(h);
+    int64_t *d_slots = nullptr;
+    if ((rc = items_to_slots(h, tmp, items, n, k, e, K, b, E, hash_seed, evict_seed, shuffle_seed, &d_slots))) return rc;
+    if ((rc = encode_units(h, d_slots, b, E, (u32)B))) return rc;
+    if (bin_hi == bin_lo) return PIEHIP_OK;
+    launch_mask_slots(h->hp.t, b, (u32)B, mask_seed, d_slots, h->stream);
+    if ((rc = encode_on_device(h, d_slots + (size_t)bin_lo * B, bin_hi - bin_lo, (u32)B, h->d_masks))) return rc;
+    return make_masks_sigma(h);
+}
+
+int piehip_slice_host_buffers_q(piehip_handle h, uint32_t q, uint64_t **idx, uint64_t **minus)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (need_sliced(h, "slice_host_buffers: ")) return PIEHIP_ESTATE;
+    if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
+    SliceState &s = h->slice;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t ct = 2 * h->LN();
+    if (idx && !s.pin_idx[q]) HIPCHK(hipHostMalloc((void **)&s.pin_idx[q], (size_t)h->K * h->E * ct * sizeof(u64), hipHostMallocPortable));
+    if (minus && !s.pin_minus[q]) HIPCHK(hipHostMalloc((void **)&s.pin_minus[q], ct * sizeof(u64), hipHostMallocPortable));
+    if (idx) *idx = s.pin_idx[q];
+    if (minus) *minus = s.pin_minus[q];
+    return PIEHIP_OK;
 }
 
 int piehip_load_db_sliced(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, uint32_t u_lo, uint32_t u_hi, const uint64_t *pts_slice,

@@ -14,6 +14,14 @@
 //            reference's timer (.cpp:98-106): the query goes to every rank over xGMI (piehip_rccl_broadcast_query), every rank
 //            runs its layers (piehip_run), the result ciphertexts are gathered to rank 0 (piehip_gather_results -- the
 //            evaluation's only exchange) and come down to host memory; rank 0 answers the client (.cpp:143-152)
+// Query-sliced mode (querySlices = true, set before run(); include/piehip.h "Query slices"): no rank needs the whole query.  Rank r holds
+// the units of piehip_query_slice(K, L, G, r) of the database for all bin layers and runs the product chain of its bin layers; either
+// share may be empty, so G > b and G > K L are legal.
+//   offline  every rank hashes the server set and encodes ITS units and the masks of ITS bin layers (piehip_build_db_sliced)
+//   online   rank 0 unpacks the query into its page-locked whole-query arrays (piehip_slice_host_buffers_q); then, inside the timer:
+//            every rank is sent its units' slices (piehip_rccl_scatter_query), computes those limbs of every accumulator
+//            (piehip_run_slice), sends every rank the rows of its bin layers (piehip_rccl_exchange_accumulators), runs its chains
+//            (piehip_run_chain); gather and answer as above
 // Error handling is the reference's -- exceptions end the process (BatchedFHEHIPPIE.cpp:15,20 throw, nothing catches) -- made safe
 // for a GROUP of processes: a collective only completes when every rank joins it, so
 //   * at the end of the offline phase the ranks agree that everybody built its slice (piehip_rccl_agree): a rank whose build threw
@@ -66,6 +74,7 @@ public:
         }
     }
 
+    bool querySlices = false;               // stage A sharded by (inner hash function, limb) unit: see above
     bool failOfflineForTesting = false;     // this rank's database build "fails": the group must end the session, not hang
     uint32_t collectiveTimeoutMs = 30000;   // bound on every wait for the other ranks (piehip_rccl_wait / piehip_rccl_agree)
 
@@ -126,6 +135,7 @@ public:
 
     void runOfflinePhase()
     {
+        if (querySlices) return runSlicedOfflinePhase();
         const auto begin = std::chrono::steady_clock::now();
         std::exception_ptr failed;
         try {
@@ -166,6 +176,7 @@ public:
 
     void runOnlinePhase()
     {
+        if (querySlices) return runSlicedOnlinePhase();
         const uint32_t L = cc->towers(), N = cc->ringDimension(), K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize,
                        b = ht.maxItemsPerPosition;
         const size_t ct = ctWords();
@@ -198,7 +209,80 @@ public:
             }
     }
 
+    // ---- query-sliced mode ------------------------------------------------------------------------------------------------------
+    void runSlicedOfflinePhase()
+    {
+        const auto begin = std::chrono::steady_clock::now();
+        const uint32_t K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize;
+        std::exception_ptr failed;
+        try {
+            if (failOfflineForTesting) throw std::runtime_error("offline phase failed on this rank (test)");
+            uint32_t ulo = 0, uhi = 0;
+            PieContext::check(piehip_query_slice(K, cc->towers(), G, rank, &ulo, &uhi));
+            PieContext::check(piehip_build_db_sliced(cc->handle(), serverSet.data(), serverSet.size(), ht.numberOfSimpleHashFunctions,
+                                                     ht.eachSimpleTableSize, K, ht.maxItemsPerPosition, E, hashSeed, seeds[0], seeds[1],
+                                                     seeds[2], ulo, uhi, lo, hi));
+            PieContext::check(piehip_sync(cc->handle()));
+        } catch (...) {
+            failed = std::current_exception();
+        }
+        int allBuilt = 0;   // as in runOfflinePhase: a no anywhere ends the session everywhere
+        PieContext::check(piehip_rccl_agree(cc->handle(), failed ? 0 : 1, &allBuilt, collectiveTimeoutMs));
+        if (failed) std::rethrow_exception(failed);
+        if (!allBuilt) throw std::runtime_error("another rank of the server group could not build its slice of the database");
+        // one evaluation of an all-zero query through the whole online path while nobody waits for it; only rank 0 ever holds a whole query
+        if (rank == 0) {
+            uint64_t *pinIdx = nullptr, *pinMinus = nullptr;
+            PieContext::check(piehip_slice_host_buffers_q(cc->handle(), 0, &pinIdx, &pinMinus));
+            std::memset(pinMinus, 0, ctWords() * sizeof(uint64_t));
+            std::memset(pinIdx, 0, (size_t)K * E * ctWords() * sizeof(uint64_t));
+        }
+        evaluateSlicedQuery();
+        offlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
+    }
+
+    void runSlicedOnlinePhase()
+    {
+        const uint32_t L = cc->towers(), N = cc->ringDimension(), K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize,
+                       b = ht.maxItemsPerPosition;
+        const size_t ct = ctWords();
+        if (rank == 0) {
+            uint64_t *pinIdx = nullptr, *pinMinus = nullptr;
+            PieContext::check(piehip_slice_host_buffers_q(cc->handle(), 0, &pinIdx, &pinMinus));
+            std::vector<uint8_t> m;
+            wire::readWithSizeIntoVector(fd, m);  // receiveEncryptedMinusElements, .cpp:114-122
+            wire::unpackCiphertextsInto(m, L, N, pinMinus, 1, qMod.data());
+            for (uint32_t h = 0; h < K; h++)  // receiveIndexMatrix, .cpp:124-141
+                for (uint32_t j = 0; j < E; j++) {
+                    wire::readWithSizeIntoVector(fd, m);
+                    wire::unpackCiphertextsInto(m, L, N, pinIdx + ((size_t)h * E + j) * ct, 1, qMod.data());
+                }
+        }
+        const auto begin = std::chrono::steady_clock::now();
+        const uint64_t *results = evaluateSlicedQuery();  // .cpp:101-103 across the ranks
+        onlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
+        if (rank == 0)
+            for (uint32_t i = 0; i < b; i++) {  // sendResult, .cpp:143-152
+                const auto out = wire::packCiphertexts(results + (size_t)i * ct, 1, L, N);
+                wire::writeWithSize(fd, out.data(), out.size());
+            }
+    }
+
 private:
+    // the query in rank 0's host arrays -> every rank's units; stage A there; accumulators -> the ranks of their bin layers; the chains;
+    // results -> rank 0's host memory.  Returns the b result ciphertexts (rank 0).
+    const uint64_t *evaluateSlicedQuery()
+    {
+        PieContext::check(piehip_rccl_scatter_query(cc->handle(), 0));
+        PieContext::check(piehip_run_slice(cc->handle()));
+        PieContext::check(piehip_rccl_exchange_accumulators(cc->handle()));
+        PieContext::check(piehip_run_chain(cc->handle()));
+        uint64_t *gathered = nullptr;
+        PieContext::check(piehip_gather_results_host(cc->handle(), ht.maxItemsPerPosition, 0, &gathered));
+        PieContext::check(piehip_rccl_wait(cc->handle(), collectiveTimeoutMs));
+        return gathered;
+    }
+
     size_t ctWords() const { return 2 * (size_t)cc->towers() * cc->ringDimension(); }
     // the query staged on rank 0 -> every rank; run(); results -> rank 0's host memory.  Returns the b result ciphertexts (rank 0).
     const uint64_t *evaluateStagedQuery()

@@ -661,10 +661,12 @@ class QuerySlicedBatchedFHEHIPPIE:
 
     contexts: the G PieContexts (same parameters; each holds the EvalMult key(s) when it has bin layers).  The database comes as a
     hash table [k][e][K][b][E] with explicit seeds (every handle shuffles the whole table), or as EVALUATION limbs (vectorizedHCT
-    [K][b][E][L][N], preCalcRandomMask [b][L][N]: the form that allows K = 1)."""
+    [K][b][E][L][N], preCalcRandomMask [b][L][N]: the form that allows K = 1), or as the server set itself with hashParams (k, e, K,
+    b, E and the four seeds, all explicit): every handle runs the offline phase on its device (piehip_build_db_sliced)."""
 
     def __init__(self, contexts, hashTable=None, shuffle_seed=None, mask_seed=None, vectorizedHCT=None, preCalcRandomMask=None,
-                 serverStashSize=0, simpleMultiTables=True, cuckooMultiTables=True, unitSlices=None, binSlices=None):
+                 serverStashSize=0, simpleMultiTables=True, cuckooMultiTables=True, unitSlices=None, binSlices=None, serverSet=None,
+                 hashParams=None):
         from . import shard
         if serverStashSize != 0:
             raise ValueError("Error, batched FHE PIE does not support a stash (yet).")
@@ -677,7 +679,13 @@ class QuerySlicedBatchedFHEHIPPIE:
         if any(c.N != c0.N or c.L != c0.L or c.t != c0.t or (c.moduli != c0.moduli).any() for c in self.ccs):
             raise ValueError("contexts of a query-sliced operator must share their parameters")
         G, L, N = len(self.ccs), c0.L, c0.N
-        if hashTable is not None:
+        if serverSet is not None:
+            hp = dict(hashParams or {})
+            if any(hp.get(s) is None for s in ("hash_seed", "evict_seed", "shuffle_seed", "mask_seed")):
+                raise ValueError("a query-sliced database needs explicit seeds, identical on every handle")
+            items, ip = _u64(serverSet)
+            k, e, self.K, self.b, self.E = hp["k"], hp["e"], hp["K"], hp["b"], hp["E"]
+        elif hashTable is not None:
             if shuffle_seed is None or mask_seed is None:
                 raise ValueError("a query-sliced database needs explicit shuffle / mask seeds, identical on every handle")
             tbl, tp = _u64(hashTable)
@@ -693,7 +701,10 @@ class QuerySlicedBatchedFHEHIPPIE:
         self.binSlices = list(binSlices) if binSlices is not None else [shard.bin_slice(b, g, G) for g in range(G)]
         for g, cc in enumerate(self.ccs):
             (ul, uh), (bl, bh) = self.unitSlices[g], self.binSlices[g]
-            if hashTable is not None:
+            if serverSet is not None:
+                _check(lib().piehip_build_db_sliced(cc._h, ip, len(items), k, e, K, b, E, int(hp["hash_seed"]), int(hp["evict_seed"]),
+                                                    int(hp["shuffle_seed"]), int(hp["mask_seed"]), ul, uh, bl, bh))
+            elif hashTable is not None:
                 _check(lib().piehip_load_db_table_sliced(cc._h, tp, k, e, K, b, E, int(shuffle_seed), int(mask_seed), ul, uh, bl, bh))
             else:
                 # unit u: limb u % L of the plaintexts of inner hash function u // L
