@@ -297,7 +297,7 @@ int piehip_gather_results_host(piehip_handle h, uint32_t b_total, int root, uint
  *   piehip_rccl_agree   *all_ok = (every rank passed ok != 0): one all-reduced word + piehip_rccl_wait; called at the end of a phase
  *                       (database built, key loaded) so that a failure on one rank ends the session on all of them BEFORE anybody
  *                       enters a collective the failed rank will not join.  Not part of the per-query path. */
-/* Query slices across the ranks ("Query slices" below; the plan of both calls: csrc/exchange_plan.h).  Rank r of G is a query-sliced
+/* Query slices across the ranks ("Query slices" below; the plan of both calls and of the gather: csrc/exchange_plan.h).  Rank r of G is a query-sliced
  * handle with the units of piehip_query_slice(K, L, G, r) and the bin layers of piehip_rccl_bin_slice(b, G, r); no rank needs the
  * whole query, and no rank but the root ever holds it.  Per batch of queries, every rank calls, in this order: piehip_rccl_scatter_query,
  * piehip_run_slice, piehip_rccl_exchange_accumulators, piehip_run_chain, piehip_gather_results(_host), piehip_rccl_wait.

@@ -1,6 +1,7 @@
-// exchange_plan.h -- query slices across the ranks of a sharded server (piehip_rccl.cpp: piehip_rccl_scatter_query,
-// piehip_rccl_exchange_accumulators; DESIGN.md section 6 "Query slices across processes"): who sends what to whom, from where, to
-// where, and in which order the transfers of a rank are posted inside its one group call.  Nothing of HIP or RCCL in here, so that
+// exchange_plan.h -- the send/receive collectives of a sharded server (piehip_rccl.cpp: piehip_rccl_scatter_query,
+// piehip_rccl_exchange_accumulators, piehip_gather_results; DESIGN.md section 6 "Query slices across processes"): who sends what to
+// whom, from where, to where, and in which order the transfers of a rank are posted inside its one group call -- the one place that
+// knows the transfers and the rule of the ranks' ranges.  Nothing of HIP or RCCL in here, so that
 // tests/exchange_plan_check.cpp can carry the plan out with memcpy, match every send with its receive and run every rank's list over
 // channels without any buffering.
 //
@@ -16,6 +17,9 @@
 //             of everybody's.  b is outermost, so that is one contiguous block per (s, d).  d receives it into a staging buffer
 //             at offset bin_n_d nq 2N u_lo_s: block after block in unit order, each [bin_n_d][nq][u_n_s][2][N].  Its own rows never
 //             leave acc_slice.  A transfer with u_n_s = 0 or bin_n_d = 0 does not exist, on either side.
+//   gather    rank r has the result rows [bin_n_r][nq][2][L][N] of its bin layers.  The root posts one receive per peer with layers, in
+//             ascending rank, straight into the rows at bin_lo_r of its list [b][nq][2][L][N]; such a peer posts one send of its result
+//             buffer.  A rank without layers posts nothing; the root's own rows are a device copy outside the plan.
 //
 // Posting order.  A rank walks its peers in ascending rank; towards a higher-ranked peer it posts its send first and then its
 // receive, towards a lower-ranked peer its receive first and then its send.  RCCL does not care about the order inside a group; a
@@ -24,7 +28,8 @@
 // in ascending order of that one total order, and both ends of a transfer agree on its place in it.  The least transfer not yet
 // completed is therefore next on both of its ranks, so it can complete: no rank ever waits for ever, even where a send only
 // completes once its receive has been reached.  In the scatter all transfers leave one rank, which walks the receivers in
-// ascending rank and the queries in order; every receiver posts its own in that same order.
+// ascending rank and the queries in order; every receiver posts its own in that same order.  In the gather every transfer has the
+// root at one end and each peer has one: the root's ascending walk over its peers is ascending in that total order.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -53,7 +58,9 @@ enum PlanBuffer {
     PLAN_OWN_INDEX,     // the rank's own index slice of query q, [u_n][E][2][N]
     PLAN_OWN_MINUS,     // ... minus slice [u_n][2][N]
     PLAN_ACC_SLICE,     // the rank's acc_slice[b][nq][u_n][2][N]
-    PLAN_ACC_STAGE      // the rank's staging buffer of received blocks, bin_n nq 2N K L words
+    PLAN_ACC_STAGE,     // the rank's staging buffer of received blocks, bin_n nq 2N K L words
+    PLAN_RESULT_ROWS,   // the result rows of this rank, [bin_n][nq][2][L][N]
+    PLAN_GATHERED       // the gathered list at the root, [b][nq][2][L][N]
 };
 
 // one transfer as one of its two ranks sees it; offsets and sizes in words
@@ -61,7 +68,7 @@ struct PlanTransfer {
     bool send;
     int peer;
     PlanBuffer buf;
-    uint32_t q;      // the query (scatter; 0 in the exchange)
+    uint32_t q;      // the query (scatter; 0 in the exchange and the gather)
     size_t off, words;
 };
 
@@ -110,6 +117,22 @@ inline std::vector<PlanTransfer> exchange_plan(const ExchangeShape &s, int G, in
         const PlanTransfer first = p > r ? snd : rcv, second = p > r ? rcv : snd;
         if (first.words) out.push_back(first);
         if (second.words) out.push_back(second);
+    }
+    return out;
+}
+
+// the transfers rank r posts in piehip_gather_results, in posting order (static: the library's dynamic symbol table stays as it was)
+static inline std::vector<PlanTransfer> gather_plan(const ExchangeShape &s, int G, int r, int root)
+{
+    std::vector<PlanTransfer> out;
+    const size_t row = (size_t)s.nq * 2 * s.L * s.N;   // words per bin layer: its nq result ciphertexts
+    for (int p = 0; p < G; p++) {
+        if (p == root || (r != root && p != r)) continue;
+        uint32_t lo, hi;
+        plan_bin_range(s, G, p, &lo, &hi);
+        if (hi == lo) continue;
+        out.push_back(r == root ? PlanTransfer{false, p, PLAN_GATHERED, 0, lo * row, (hi - lo) * row}
+                                : PlanTransfer{true, root, PLAN_RESULT_ROWS, 0, 0, (hi - lo) * row});
     }
     return out;
 }

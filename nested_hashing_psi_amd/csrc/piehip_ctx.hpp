@@ -6,8 +6,8 @@
 //   piehip_ops.cpp     the OpenFHE primitives one by one (parity tests), NTT timing, per-kernel profiling
 //   piehip_fhepie.cpp  the rotation-based sibling operator (FHEHIPPIE)
 //   piehip_client.cpp  client-side harness (key generation, encryption, decryption)
-//   piehip_rccl.cpp    the collectives of a sharded server over RCCL: the final gather, the query's broadcast, and the scatter and
-//                      exchange of query slices (exchange_plan.h: who sends what to whom and in which order, free of HIP)
+//   piehip_rccl.cpp    the collectives of a sharded server over RCCL: the query's broadcast, and the final gather and the scatter and
+//                      exchange of query slices, whose transfers only exchange_plan.h knows (who sends what to whom, in which order; free of HIP)
 //   piehip_slice.cpp   query-sliced stage A: a handle's (inner hash function, limb) units, the accumulators' way to the chain side
 //                      (slice_geometry.h: the copies that bring its inputs up, free of HIP)
 #pragma once

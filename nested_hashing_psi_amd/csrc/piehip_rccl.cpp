@@ -3,7 +3,8 @@
 //   independent, reference BatchedFHEHIPPIE.cpp:91; sendResult at BatchedFHEPSIServer.cpp:143-152), and the per-query
 //   distribution of the inputs from the rank that holds the client's socket (.cpp:94-95,114-141).
 // A C++ server (host/ShardedBatchedFHEPSIServer.hpp) needs nothing but this library and RCCL; torch.distributed is only the
-// Python harness's way to the same collectives (shard.py).
+// Python harness's way to the same collectives (shard.py).  exchange_plan.h alone knows the ranks' ranges and the transfers of the gather,
+// the scatter and the exchange, and their order; this file posts a plan (post_transfers).
 //
 // RCCL is bound at run time (dlopen), not at link time: a one-GPU deployment never loads the 0.5 GB library, and a process that
 // already holds a copy (PyTorch bundles its own librccl.so) gets THAT copy, so a communicator made elsewhere in the process can
@@ -87,21 +88,74 @@ int no_rccl()
     return fail(PIEHIP_EHIP, g_rccl.error.empty() ? "RCCL is not available" : g_rccl.error);
 }
 
-}  // namespace
-
 #define NCCLCHK(R, expr)                                                                                          \
     do {                                                                                                          \
         ncclResult_t r_ = (expr);                                                                                 \
         if (r_ != ncclSuccess) return fail(PIEHIP_EHIP, std::string(#expr) + ": " + (R)->GetErrorString(r_));     \
     } while (0)
 
+#define NEED_RCCL(R)         \
+    const Rccl *R = rccl(); \
+    if (!R) return no_rccl()
+
+// the one group bracket: what `body` posts is one group call; GroupEnd runs whatever body returns, the first failure names the call
+template <typename Body>
+int in_group(const Rccl *R, const char *who, Body body)
+{
+    NCCLCHK(R, R->GroupStart());
+    const ncclResult_t gr = body();
+    const ncclResult_t ge = R->GroupEnd();
+    if (gr != ncclSuccess || ge != ncclSuccess) return fail(PIEHIP_EHIP, std::string(who) + ": " + R->GetErrorString(gr != ncclSuccess ? gr : ge));
+    return PIEHIP_OK;
+}
+
+// one group call of a plan's transfers in its posting order; base(t): the device address transfer t's offset counts from
+template <typename Base>
+int post_transfers(piehip_ctx *h, const Rccl *R, const std::vector<PlanTransfer> &plan, Base base, const char *who)
+{
+    if (plan.empty()) return PIEHIP_OK;
+    const ncclComm_t comm = (ncclComm_t)h->comm;
+    return in_group(R, who, [&] {
+        ncclResult_t gr = ncclSuccess;
+        for (size_t i = 0; i < plan.size() && gr == ncclSuccess; i++) {
+            const PlanTransfer &t = plan[i];
+            u64 *p = base(t) + t.off;
+            gr = t.send ? R->Send(p, t.words, ncclUint64, t.peer, comm, h->stream) : R->Recv(p, t.words, ncclUint64, t.peer, comm, h->stream);
+        }
+        return gr;
+    });
+}
+
+// a device buffer of a call, kept while its size stays: the stream drains before it is replaced
+int keep_buffer(piehip_ctx *h, u64 **buf, size_t *have, size_t words)
+{
+    if (*have == words) return PIEHIP_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    dev_free(buf);
+    *have = 0;
+    const int rc = dev_alloc(buf, words);
+    if (rc) return rc;
+    *have = words;
+    return PIEHIP_OK;
+}
+
+void set_comm(piehip_ctx *h, void *comm, bool owned, int nranks, int rank)
+{
+    h->comm = comm;
+    h->comm_owned = owned;
+    h->comm_ranks = nranks;
+    h->comm_rank = rank;
+}
+void forget_comm(piehip_ctx *h) { set_comm(h, nullptr, false, 0, 0); }
+
+}  // namespace
+
 extern "C" {
 
 int piehip_rccl_unique_id(void *id)
 {
     if (!id) return fail(PIEHIP_EINVAL, "null id");
-    const Rccl *R = rccl();
-    if (!R) return no_rccl();
+    NEED_RCCL(R);
     ncclUniqueId u;
     NCCLCHK(R, R->GetUniqueId(&u));
     static_assert(sizeof(u) == PIEHIP_RCCL_ID_BYTES, "ncclUniqueId size");
@@ -114,17 +168,13 @@ int piehip_rccl_init(piehip_handle h, const void *id, int nranks, int rank)
     NEED_RO(h);
     if (!id || nranks < 1 || rank < 0 || rank >= nranks) return fail(PIEHIP_EINVAL, "rccl_init: bad rank or id");
     if (h->comm) return fail(PIEHIP_ESTATE, "rccl_init: the handle already has a communicator");
-    const Rccl *R = rccl();
-    if (!R) return no_rccl();
+    NEED_RCCL(R);
     HIPCHK(hipSetDevice(h->device));
     ncclUniqueId u;
     memcpy(&u, id, sizeof(u));
     ncclComm_t c = nullptr;
     NCCLCHK(R, R->CommInitRank(&c, nranks, u, rank));
-    h->comm = c;
-    h->comm_owned = true;
-    h->comm_ranks = nranks;
-    h->comm_rank = rank;
+    set_comm(h, c, true, nranks, rank);
     return PIEHIP_OK;
 }
 
@@ -134,10 +184,7 @@ int piehip_rccl_attach(piehip_handle h, void *comm, int nranks, int rank)
     if (!comm || nranks < 1 || rank < 0 || rank >= nranks) return fail(PIEHIP_EINVAL, "rccl_attach: bad communicator or rank");
     if (h->comm) return fail(PIEHIP_ESTATE, "rccl_attach: the handle already has a communicator");
     if (!rccl()) return no_rccl();
-    h->comm = comm;
-    h->comm_owned = false;
-    h->comm_ranks = nranks;
-    h->comm_rank = rank;
+    set_comm(h, comm, false, nranks, rank);
     return PIEHIP_OK;
 }
 
@@ -153,9 +200,7 @@ int piehip_rccl_destroy(piehip_handle h)
     if (h->pin_gather) (void)hipHostFree(h->pin_gather);
     h->pin_gather = nullptr;
     h->gather_words = 0;
-    h->comm = nullptr;
-    h->comm_owned = false;
-    h->comm_ranks = h->comm_rank = 0;
+    forget_comm(h);
     return PIEHIP_OK;
 }
 
@@ -175,9 +220,7 @@ static int abort_comm(piehip_ctx *h, const Rccl *R)
 {
     if (!h->comm) return PIEHIP_OK;
     if (R && R->CommAbort && h->comm_owned) (void)R->CommAbort((ncclComm_t)h->comm);
-    h->comm = nullptr;
-    h->comm_owned = false;
-    h->comm_ranks = h->comm_rank = 0;
+    forget_comm(h);
     return PIEHIP_OK;
 }
 
@@ -197,10 +240,15 @@ int piehip_rccl_wait(piehip_handle h, uint32_t timeout_ms)
         HIPCHK(hipStreamSynchronize(h->stream));
         return PIEHIP_OK;
     }
-    const Rccl *R = rccl();
-    if (!R) return no_rccl();
+    NEED_RCCL(R);
     const auto t0 = std::chrono::steady_clock::now();
     std::string why;
+    auto comm_failed = [&] {   // the communicator reports a failed state: says so in `why`
+        ncclResult_t ae = ncclSuccess;
+        if (!R->CommGetAsyncError || R->CommGetAsyncError((ncclComm_t)h->comm, &ae) != ncclSuccess || ae == ncclSuccess || ae == ncclInProgress) return false;
+        why = std::string("rccl_wait: the communicator reports ") + R->GetErrorString(ae);
+        return true;
+    };
     // The common case is a query's worth of work (well under a millisecond at the headline shape): the stream is polled back to back
     // for the first milliseconds -- this wait sits inside the server's online timer -- and the communicator's error state and the
     // clock are looked at every 64th poll; after 5 ms the loop backs off to one poll per 50 us.
@@ -212,11 +260,7 @@ int piehip_rccl_wait(piehip_handle h, uint32_t timeout_ms)
             std::this_thread::yield();
             continue;
         }
-        ncclResult_t ae = ncclSuccess;
-        if (R->CommGetAsyncError && R->CommGetAsyncError((ncclComm_t)h->comm, &ae) == ncclSuccess && ae != ncclSuccess && ae != ncclInProgress) {
-            why = std::string("rccl_wait: the communicator reports ") + R->GetErrorString(ae);
-            break;
-        }
+        if (comm_failed()) break;
         const auto waited = std::chrono::steady_clock::now() - t0;
         if (waited > std::chrono::milliseconds(timeout_ms)) {
             why = "rccl_wait: timed out after " + std::to_string(timeout_ms) + " ms -- a rank of the server group did not join the collective";
@@ -224,14 +268,8 @@ int piehip_rccl_wait(piehip_handle h, uint32_t timeout_ms)
         }
         if (waited > std::chrono::milliseconds(5)) std::this_thread::sleep_for(std::chrono::microseconds(50) * 64);
     }
-    if (why.empty()) {
-        // (the stream has drained; a transfer that FAILED also drains it: ask once more)
-        ncclResult_t ae = ncclSuccess;
-        if (R->CommGetAsyncError && R->CommGetAsyncError((ncclComm_t)h->comm, &ae) == ncclSuccess && ae != ncclSuccess && ae != ncclInProgress)
-            why = std::string("rccl_wait: the communicator reports ") + R->GetErrorString(ae);
-        else
-            return PIEHIP_OK;
-    }
+    // (the stream has drained; a transfer that FAILED also drains it: ask once more)
+    if (why.empty() && !comm_failed()) return PIEHIP_OK;
     const bool owned = h->comm_owned;
     abort_comm(h, R);
     if (!owned)   // piehip_rccl_attach: the communicator is the caller's to abort -- until then the stream may still be blocked
@@ -245,8 +283,7 @@ int piehip_rccl_agree(piehip_handle h, int ok, int *all_ok, uint32_t timeout_ms)
     NEED(h);
     if (!all_ok) return fail(PIEHIP_EINVAL, "null result");
     if (!h->comm) return fail(PIEHIP_ESTATE, "rccl_agree: no communicator");
-    const Rccl *R = rccl();
-    if (!R) return no_rccl();
+    NEED_RCCL(R);
     if (!R->AllReduce) return fail(PIEHIP_EHIP, "rccl_agree: this RCCL has no ncclAllReduce");
     HIPCHK(hipSetDevice(h->device));
     Tmp tmp(h);
@@ -267,55 +304,41 @@ int piehip_rccl_agree(piehip_handle h, int ok, int *all_ok, uint32_t timeout_ms)
     return rc;
 }
 
-// [lo, hi): the bin layers of rank r of G (contiguous, sizes differ by at most one: shard.bin_slice, ShardedBatchedFHEHIPPIE)
-static void rank_slice(u32 b, int r, int G, u32 *lo, u32 *hi)
-{
-    *lo = (u32)((u64)b * (u64)r / (u64)G);
-    *hi = (u32)((u64)b * (u64)(r + 1) / (u64)G);
-}
-
 int piehip_rccl_bin_slice(uint32_t b_total, int nranks, int rank, uint32_t *bin_lo, uint32_t *bin_hi)
 {
     if (!bin_lo || !bin_hi || nranks < 1 || rank < 0 || rank >= nranks) return fail(PIEHIP_EINVAL, "bad rank");
-    rank_slice(b_total, rank, nranks, bin_lo, bin_hi);
+    plan_range(b_total, nranks, rank, bin_lo, bin_hi);
+    return PIEHIP_OK;
+}
+
+// what both gather calls refuse first
+static int gather_check(const piehip_ctx *h, int root, bool has_dest)
+{
+    if (h->res_limbs != h->hp.L)   // the ranks' row sizes would have to agree, and nothing checks a setting across ranks
+        return fail(PIEHIP_ESTATE, "gather_results: results reduced to fewer limbs (piehip_set_result_limbs) are not gathered");
+    if (!h->comm) return fail(PIEHIP_ESTATE, "gather_results: no communicator (piehip_rccl_init / piehip_rccl_attach)");
+    if (root < 0 || root >= h->comm_ranks) return fail(PIEHIP_EINVAL, "gather_results: root outside the communicator");
+    if (h->comm_rank == root && !has_dest) return fail(PIEHIP_EINVAL, "gather_results: the root needs a destination");
     return PIEHIP_OK;
 }
 
 int piehip_gather_results(piehip_handle h, uint32_t b_total, int root, void *d_out)
 {
     NEED(h);   // the handle's stream is behind the run whose results travel
-    if (h->res_limbs != h->hp.L)   // the ranks' row sizes would have to agree, and nothing checks a setting across ranks
-        return fail(PIEHIP_ESTATE, "gather_results: results reduced to fewer limbs (piehip_set_result_limbs) are not gathered");
-    if (!h->comm) return fail(PIEHIP_ESTATE, "gather_results: no communicator (piehip_rccl_init / piehip_rccl_attach)");
+    int rc = gather_check(h, root, d_out != nullptr);
+    if (rc) return rc;
     const int G = h->comm_ranks, me = h->comm_rank;
-    if (root < 0 || root >= G) return fail(PIEHIP_EINVAL, "gather_results: root outside the communicator");
     u32 lo, hi;
-    rank_slice(b_total, me, G, &lo, &hi);
+    plan_range(b_total, G, me, &lo, &hi);
     if (hi - lo != (h->d_out ? h->b : 0u))
         return fail(PIEHIP_EINVAL, "gather_results: this handle does not evaluate its rank's slice of the bin layers (piehip_rccl_bin_slice)");
-    if (me == root && !d_out) return fail(PIEHIP_EINVAL, "gather_results: the root needs a destination");
-    const Rccl *R = rccl();
-    if (!R) return no_rccl();
+    NEED_RCCL(R);
     HIPCHK(hipSetDevice(h->device));
+    // exact sizes, no padding: each slice crosses its own xGMI link once, straight into its rows of d_out; the root's own rows are a device copy
+    const ExchangeShape shape = {h->K, h->hp.L, b_total, h->nq, h->hp.N, h->E};
+    auto base = [&](const PlanTransfer &t) -> u64 * { return t.buf == PLAN_GATHERED ? (u64 *)d_out : h->d_out; };
+    if ((rc = post_transfers(h, R, gather_plan(shape, G, me, root), base, "gather_results"))) return rc;
     const size_t row = (size_t)h->nq * 2 * h->LN();   // words per bin layer: its nq result ciphertexts
-    const ncclComm_t comm = (ncclComm_t)h->comm;
-    // exact sizes, no padding: the root posts one receive per peer straight into that peer's rows of d_out, every other rank one
-    // send of its result buffer; the root's own rows are a device copy.  Each slice crosses its own xGMI link once.
-    NCCLCHK(R, R->GroupStart());
-    ncclResult_t gr = ncclSuccess;
-    if (me == root) {
-        for (int r = 0; r < G && gr == ncclSuccess; r++) {
-            u32 rlo, rhi;
-            rank_slice(b_total, r, G, &rlo, &rhi);
-            if (r == me || rhi == rlo) continue;
-            gr = R->Recv((u64 *)d_out + (size_t)rlo * row, (size_t)(rhi - rlo) * row, ncclUint64, r, comm, h->stream);
-        }
-    } else if (hi > lo) {
-        gr = R->Send(h->d_out, (size_t)(hi - lo) * row, ncclUint64, root, comm, h->stream);
-    }
-    const ncclResult_t ge = R->GroupEnd();
-    if (gr != ncclSuccess || ge != ncclSuccess)
-        return fail(PIEHIP_EHIP, std::string("gather_results: ") + R->GetErrorString(gr != ncclSuccess ? gr : ge));
     if (me == root && hi > lo)
         HIPCHK(hipMemcpyAsync((u64 *)d_out + (size_t)lo * row, h->d_out, (size_t)(hi - lo) * row * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
     return PIEHIP_OK;
@@ -324,28 +347,18 @@ int piehip_gather_results(piehip_handle h, uint32_t b_total, int root, void *d_o
 int piehip_gather_results_host(piehip_handle h, uint32_t b_total, int root, uint64_t **results)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
-    if (h->res_limbs != h->hp.L)
-        return fail(PIEHIP_ESTATE, "gather_results: results reduced to fewer limbs (piehip_set_result_limbs) are not gathered");
-    if (!h->comm) return fail(PIEHIP_ESTATE, "gather_results: no communicator (piehip_rccl_init / piehip_rccl_attach)");
+    int rc = gather_check(h, root, results != nullptr);
+    if (rc) return rc;
     const bool is_root = h->comm_rank == root;
-    if (is_root && !results) return fail(PIEHIP_EINVAL, "gather_results: the root needs a destination");
-    if (is_root) {
+    if (is_root) {   // the device half is a kept buffer; the page-locked half goes when that is replaced
         HIPCHK(hipSetDevice(h->device));
         const size_t words = (size_t)b_total * h->nq * 2 * h->LN();
-        if (h->gather_words != words) {   // first use, or another shape
-            HIPCHK(hipStreamSynchronize(h->stream));
-            dev_free(&h->d_gather);
-            if (h->pin_gather) (void)hipHostFree(h->pin_gather);
-            h->pin_gather = nullptr;
-            h->gather_words = 0;
-            int rc = dev_alloc(&h->d_gather, words);
-            if (rc) return rc;
-            HIPCHK(hipHostMalloc((void **)&h->pin_gather, words * sizeof(u64), hipHostMallocPortable));
-            h->gather_words = words;
-        }
+        const bool same = h->gather_words == words;
+        if ((rc = keep_buffer(h, &h->d_gather, &h->gather_words, words))) return rc;   // (drains the stream before it replaces)
+        if (!same && h->pin_gather) (void)hipHostFree(h->pin_gather), h->pin_gather = nullptr;
+        if (!h->pin_gather && words) HIPCHK(hipHostMalloc((void **)&h->pin_gather, words * sizeof(u64), hipHostMallocPortable));
     }
-    int rc = piehip_gather_results(h, b_total, root, is_root ? h->d_gather : nullptr);
-    if (rc) return rc;
+    if ((rc = piehip_gather_results(h, b_total, root, is_root ? h->d_gather : nullptr))) return rc;
     if (is_root) {
         HIPCHK(hipMemcpyAsync(h->pin_gather, h->d_gather, h->gather_words * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
         *results = h->pin_gather;
@@ -361,8 +374,7 @@ int piehip_rccl_broadcast(piehip_handle h, int root, void *d_buf, size_t bytes)
     if (!h->comm) return fail(PIEHIP_ESTATE, "rccl_broadcast: no communicator");
     if (!d_buf && bytes) return fail(PIEHIP_EINVAL, "null buffer");
     if (root < 0 || root >= h->comm_ranks) return fail(PIEHIP_EINVAL, "rccl_broadcast: root outside the communicator");
-    const Rccl *R = rccl();
-    if (!R) return no_rccl();
+    NEED_RCCL(R);
     HIPCHK(hipSetDevice(h->device));
     if (bytes) NCCLCHK(R, R->Broadcast(d_buf, d_buf, bytes, ncclChar, root, (ncclComm_t)h->comm, h->stream));
     return PIEHIP_OK;
@@ -374,8 +386,7 @@ int piehip_rccl_broadcast_query(piehip_handle h, int root)
     if (!h->comm) return fail(PIEHIP_ESTATE, "rccl_broadcast_query: no communicator");
     if (!h->K) return fail(PIEHIP_ESTATE, "load the database before the query");
     if (root < 0 || root >= h->comm_ranks) return fail(PIEHIP_EINVAL, "rccl_broadcast_query: root outside the communicator");
-    const Rccl *R = rccl();
-    if (!R) return no_rccl();
+    NEED_RCCL(R);
     HIPCHK(hipSetDevice(h->device));
     // the root's staged uploads are on its stream (piehip_stage_*: in order); the collective is queued behind them.  A root
     // with a half-staged query is a call-order error everywhere (the other ranks would wait for a broadcast that never comes),
@@ -392,21 +403,18 @@ int piehip_rccl_broadcast_query(piehip_handle h, int root)
     }
     const size_t iw = (size_t)h->K * h->E * 2 * h->LN(), mw = 2 * h->LN();
     const ncclComm_t comm = (ncclComm_t)h->comm;
-    int rc;
-    NCCLCHK(R, R->GroupStart());
-    ncclResult_t gr = ncclSuccess;
-    for (u32 q = 0; q < h->nq && gr == ncclSuccess; q++) {
-        u64 *di = nullptr, *dm = nullptr;
-        if ((rc = query_input_buffers(h, q, &di, &dm))) {
-            (void)R->GroupEnd();
-            return rc;
+    int brc = PIEHIP_OK;   // query_input_buffers failed in the middle: the group is still closed, its own outcome does not count
+    const int rc = in_group(R, "rccl_broadcast_query", [&] {
+        ncclResult_t gr = ncclSuccess;
+        for (u32 q = 0; q < h->nq && gr == ncclSuccess; q++) {
+            u64 *di = nullptr, *dm = nullptr;
+            if ((brc = query_input_buffers(h, q, &di, &dm))) break;
+            gr = R->Broadcast(di, di, iw, ncclUint64, root, comm, h->stream);
+            if (gr == ncclSuccess) gr = R->Broadcast(dm, dm, mw, ncclUint64, root, comm, h->stream);
         }
-        gr = R->Broadcast(di, di, iw, ncclUint64, root, comm, h->stream);
-        if (gr == ncclSuccess) gr = R->Broadcast(dm, dm, mw, ncclUint64, root, comm, h->stream);
-    }
-    const ncclResult_t ge = R->GroupEnd();
-    if (gr != ncclSuccess || ge != ncclSuccess)
-        return fail(PIEHIP_EHIP, std::string("rccl_broadcast_query: ") + R->GetErrorString(gr != ncclSuccess ? gr : ge));
+        return gr;
+    });
+    if (brc || rc) return brc ? brc : rc;
     // every rank now evaluates the received copy: as if the query had been staged here
     h->stage_open = false;
     use_owned_inputs(h);
@@ -431,37 +439,6 @@ static int sliced_rank_check(const piehip_ctx *h, const char *who)
 
 static ExchangeShape exchange_shape(const piehip_ctx *h) { return {h->K, h->hp.L, h->slice.b_total, h->nq, h->hp.N, h->E}; }
 
-// a device buffer of a call, kept while its size stays: the stream drains before it is replaced
-static int keep_buffer(piehip_ctx *h, u64 **buf, size_t *have, size_t words)
-{
-    if (*have == words) return PIEHIP_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    dev_free(buf);
-    *have = 0;
-    const int rc = dev_alloc(buf, words);
-    if (rc) return rc;
-    *have = words;
-    return PIEHIP_OK;
-}
-
-// one group call of a plan's transfers in its posting order; base(t): the device address transfer t's offset counts from
-extern "C++" template <typename Base>
-static int post_transfers(piehip_ctx *h, const Rccl *R, const std::vector<PlanTransfer> &plan, Base base, const char *who)
-{
-    if (plan.empty()) return PIEHIP_OK;
-    const ncclComm_t comm = (ncclComm_t)h->comm;
-    NCCLCHK(R, R->GroupStart());
-    ncclResult_t gr = ncclSuccess;
-    for (size_t i = 0; i < plan.size() && gr == ncclSuccess; i++) {
-        const PlanTransfer &t = plan[i];
-        u64 *p = base(t) + t.off;
-        gr = t.send ? R->Send(p, t.words, ncclUint64, t.peer, comm, h->stream) : R->Recv(p, t.words, ncclUint64, t.peer, comm, h->stream);
-    }
-    const ncclResult_t ge = R->GroupEnd();
-    if (gr != ncclSuccess || ge != ncclSuccess) return fail(PIEHIP_EHIP, std::string(who) + ": " + R->GetErrorString(gr != ncclSuccess ? gr : ge));
-    return PIEHIP_OK;
-}
-
 int piehip_rccl_scatter_query(piehip_handle h, int root)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
@@ -474,8 +451,7 @@ int piehip_rccl_scatter_query(piehip_handle h, int root)
     for (u32 q = 0; me == root && q < h->nq; q++)
         if (!s.pin_idx[q] || !s.pin_minus[q])
             return fail(PIEHIP_ESTATE, "rccl_scatter_query: the root has no host arrays for a query of the batch (piehip_slice_host_buffers_q)");
-    const Rccl *R = rccl();
-    if (!R) return no_rccl();
+    NEED_RCCL(R);
     join_pending(h);
     mark_dirty(h);
     HIPCHK(hipSetDevice(h->device));
@@ -535,8 +511,7 @@ int piehip_rccl_exchange_accumulators(piehip_handle h)
         if (s.put[u]) return fail(PIEHIP_ESTATE, "rccl_exchange_accumulators: a unit has been put since the last piehip_run_chain");
     if (s.u_n() && (!s.acc || s.acc_nq != h->nq)) return fail(PIEHIP_ESTATE, "rccl_exchange_accumulators: no accumulator buffer");
     if (bn && (!h->d_acc || !h->ws.eqp)) return fail(PIEHIP_ESTATE, "rccl_exchange_accumulators: no workspace (an earlier allocation failed)");
-    const Rccl *R = rccl();
-    if (!R) return no_rccl();
+    NEED_RCCL(R);
     join_pending(h);   // the placement writes what the queues of the last piehip_run_chain read
     mark_dirty(h);
     HIPCHK(hipSetDevice(h->device));

@@ -251,9 +251,7 @@ extern "C" {
 int piehip_query_slice(uint32_t K, uint32_t L, int nranks, int rank, uint32_t *u_lo, uint32_t *u_hi)
 {
     if (!u_lo || !u_hi || nranks < 1 || rank < 0 || rank >= nranks) return fail(PIEHIP_EINVAL, "query_slice: bad rank or null out");
-    const uint64_t units = (uint64_t)K * L;
-    *u_lo = (uint32_t)(units * (uint64_t)rank / (uint64_t)nranks);
-    *u_hi = (uint32_t)(units * ((uint64_t)rank + 1) / (uint64_t)nranks);
+    plan_range(K * L, nranks, rank, u_lo, u_hi);
     return PIEHIP_OK;
 }
 

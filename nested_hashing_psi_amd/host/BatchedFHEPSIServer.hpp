@@ -16,6 +16,7 @@
 // what a server of its own would have sent.
 #pragma once
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <random>
 
@@ -35,6 +36,77 @@ struct ContextMessage {
     uint64_t t;
     uint64_t moduli[2 * 7 + 1];  // q_0..q_{L-1}, p_0..p_L
 };
+
+// ---- the steps this server and both modes of ShardedBatchedFHEPSIServer share ----------------------------------------------------
+inline ContextMessage readContextMessage(int fd)
+{
+    std::vector<uint8_t> m;
+    wire::readWithSizeIntoVector(fd, m);
+    if (m.size() != sizeof(ContextMessage)) throw std::runtime_error("context message size");
+    ContextMessage c;
+    std::memcpy(&c, m.data(), sizeof(c));
+    if (c.L < 1 || c.L > 7) throw std::invalid_argument("context: L out of range");
+    return c;
+}
+
+// The EvalMult key message as words [L][2][L][N], the modulus index being the innermost L.  moduli (q_0..q_{L-1}) given: the key-switch
+// accumulators take canonical residues only; null where the sender has checked what it forwards.
+inline std::vector<uint64_t> readEvalMultKey(int fd, const ContextMessage &c, const uint64_t *moduli)
+{
+    std::vector<uint8_t> m;
+    wire::readWithSizeIntoVector(fd, m);
+    const size_t words = (size_t)c.L * 2 * c.L * c.N;
+    if (m.size() != words * sizeof(uint64_t)) throw std::runtime_error("EvalMult key message size");
+    std::vector<uint64_t> evk(words);
+    std::memcpy(evk.data(), m.data(), m.size());
+    if (moduli) wire::checkCanonical(evk.data(), (size_t)c.L * 2 * c.L, c.L, c.N, moduli, "EvalMult key");
+    return evk;
+}
+
+// One query, every message unpacked (and range-checked) straight into the page-locked arrays pinMinus[2][L][N] and pinIdx[K][E][2][L][N].
+// onPiece(row, j, ct) is called as each ciphertext lands, with row = MINUS_ELEMENT for the minus element: a server that stages starts
+// the piece's upload there (piehip_stage_*), and drops a partial staging itself when this throws.
+constexpr int64_t MINUS_ELEMENT = -1;
+using OnPiece = std::function<void(int64_t row, uint32_t j, uint64_t *ct)>;
+inline void receiveQuery(int fd, uint32_t L, uint32_t N, uint32_t K, uint32_t E, const uint64_t *qMod, uint64_t *pinIdx, uint64_t *pinMinus,
+                         const OnPiece &onPiece = nullptr)
+{
+    const size_t ct = 2 * (size_t)L * N;
+    std::vector<uint8_t> m;
+    wire::readWithSizeIntoVector(fd, m);  // receiveEncryptedMinusElements, .cpp:114-122
+    wire::unpackCiphertextsInto(m, L, N, pinMinus, 1, qMod);
+    if (onPiece) onPiece(MINUS_ELEMENT, 0, pinMinus);
+    for (uint32_t h = 0; h < K; h++)  // receiveIndexMatrix, .cpp:124-141: one message per ciphertext
+        for (uint32_t j = 0; j < E; j++) {
+            uint64_t *p = pinIdx + ((size_t)h * E + j) * ct;
+            wire::readWithSizeIntoVector(fd, m);
+            wire::unpackCiphertextsInto(m, L, N, p, 1, qMod);
+            if (onPiece) onPiece(h, j, p);
+        }
+}
+// onPiece for a server that stages query q of handle h
+inline OnPiece stagePieces(piehip_handle h, uint32_t q)
+{
+    return [h, q](int64_t row, uint32_t j, uint64_t *ct) {
+        PieContext::check(row == MINUS_ELEMENT ? piehip_stage_minus_q(h, q, ct) : piehip_stage_index_ct_q(h, q, (uint32_t)row, j, ct));
+    };
+}
+
+// sendResult, .cpp:143-152: b ciphertexts of `keep` limbs, one message each, rowStride words apart
+inline void sendResults(int fd, const uint64_t *results, uint32_t b, size_t rowStride, uint32_t keep, uint32_t N)
+{
+    for (uint32_t i = 0; i < b; i++) {
+        const auto out = wire::packCiphertexts(results + (size_t)i * rowStride, 1, keep, N);
+        wire::writeWithSize(fd, out.data(), out.size());
+    }
+}
+
+// the all-zero query of a warm-up
+inline void zeroQuery(uint64_t *pinIdx, uint64_t *pinMinus, uint32_t K, uint32_t E, size_t ct)
+{
+    std::memset(pinMinus, 0, ct * sizeof(uint64_t));
+    std::memset(pinIdx, 0, (size_t)K * E * ct * sizeof(uint64_t));
+}
 
 class BatchedFHEPSIServer {
 public:
@@ -90,11 +162,7 @@ public:
         ContextMessage c0;
         for (uint32_t q = 0; q < nq; q++) {
             const int fd = fds[q];
-            wire::readWithSizeIntoVector(fd, m);
-            if (m.size() != sizeof(ContextMessage)) throw std::runtime_error("context message size");
-            ContextMessage c;
-            std::memcpy(&c, m.data(), sizeof(c));
-            if (c.L < 1 || c.L > 7) throw std::invalid_argument("context: L out of range");
+            const ContextMessage c = readContextMessage(fd);
             if (q == 0) {
                 c0 = c;
                 cc.reset(new PieContext(c.N, c.L, c.t, c.moduli, c.moduli + c.L));
@@ -110,13 +178,7 @@ public:
                 throw std::invalid_argument("the clients of one batch must use the same crypto context parameters");
             }
             wire::readWithSizeIntoVector(fd, m);  // public key: stored by the reference, never used by the operator
-            wire::readWithSizeIntoVector(fd, m);  // EvalMult key [L][2][L][N]
-            const size_t words = (size_t)c.L * 2 * c.L * c.N;
-            if (m.size() != words * sizeof(uint64_t)) throw std::runtime_error("EvalMult key message size");
-            std::vector<uint64_t> evk(words);
-            std::memcpy(evk.data(), m.data(), m.size());
-            // [L][2][L][N], the modulus index is the innermost L: the key-switch accumulators take canonical residues only
-            wire::checkCanonical(evk.data(), (size_t)c.L * 2 * c.L, c.L, c.N, qMod.data(), "EvalMult key");
+            const std::vector<uint64_t> evk = readEvalMultKey(fd, c, qMod.data());
             if (nq == 1) cc->setEvalMultKey(evk.data());
             else PieContext::check(piehip_load_relin_key_q(cc->handle(), q, evk.data()));  // every client's own key
         }
@@ -139,8 +201,7 @@ public:
             for (uint32_t q = 0; q < fds.size(); q++) {
                 uint64_t *pinIdx = nullptr, *pinMinus = nullptr;
                 PieContext::check(piehip_host_buffers_q(cc->handle(), q, &pinIdx, &pinMinus, &pinRes));
-                std::memset(pinMinus, 0, ct * sizeof(uint64_t));
-                std::memset(pinIdx, 0, (size_t)K * E * ct * sizeof(uint64_t));
+                zeroQuery(pinIdx, pinMinus, K, E, ct);
                 PieContext::check(piehip_stage_minus_q(cc->handle(), q, pinMinus));
                 for (uint32_t h = 0; h < K; h++) PieContext::check(piehip_stage_index_row_q(cc->handle(), q, h, pinIdx + (size_t)h * E * ct));
             }
@@ -154,28 +215,17 @@ public:
     {
         const uint32_t L = cc->towers(), N = cc->ringDimension(), K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize,
                        b = ht.maxItemsPerPosition, nq = (uint32_t)fds.size();
-        const size_t ct = 2 * (size_t)L * N;
         // Every message is unpacked (and range-checked) straight into the library's page-locked staging arrays, and a piece's
         // upload starts as soon as it has landed: every message's ciphertext at once -- the 29 MiB of a C3 query cross PCIe
         // underneath the receive loop, and when the timer starts only the last megabyte is still on its way (the reference deserialises into
         // Ciphertext objects in the same place, .cpp:114-141, before its timer starts at .cpp:98).  A failed receive drops the
         // partial staging (piehip_stage_reset) before the exception leaves.
         uint64_t *pinRes = nullptr;
-        std::vector<uint8_t> m;
         try {
             for (uint32_t q = 0; q < nq; q++) {
-                const int fd = fds[q];
                 uint64_t *pinIdx = nullptr, *pinMinus = nullptr;
                 PieContext::check(piehip_host_buffers_q(cc->handle(), q, &pinIdx, &pinMinus, &pinRes));
-                wire::readWithSizeIntoVector(fd, m);  // receiveEncryptedMinusElements, .cpp:114-122
-                wire::unpackCiphertextsInto(m, L, N, pinMinus, 1, qMod.data());
-                PieContext::check(piehip_stage_minus_q(cc->handle(), q, pinMinus));
-                for (uint32_t h = 0; h < K; h++)  // receiveIndexMatrix, .cpp:124-141: one message per ciphertext, staged as it lands
-                    for (uint32_t j = 0; j < E; j++) {
-                        wire::readWithSizeIntoVector(fd, m);
-                        wire::unpackCiphertextsInto(m, L, N, pinIdx + ((size_t)h * E + j) * ct, 1, qMod.data());
-                        PieContext::check(piehip_stage_index_ct_q(cc->handle(), q, h, j, pinIdx + ((size_t)h * E + j) * ct));
-                    }
+                receiveQuery(fds[q], L, N, K, E, qMod.data(), pinIdx, pinMinus, stagePieces(cc->handle(), q));
             }
         } catch (...) {
             piehip_stage_reset(cc->handle());
@@ -188,11 +238,7 @@ public:
         onlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
         const uint32_t keep = resultLimbs ? resultLimbs : L;   // limbs per result ciphertext as it leaves the device and the server
         const size_t rct = 2 * (size_t)keep * N;
-        for (uint32_t q = 0; q < nq; q++)
-            for (uint32_t i = 0; i < b; i++) {  // sendResult, .cpp:143-152; rows of the result array are [bin layer][query]
-                const auto out = wire::packCiphertexts(pinRes + ((size_t)i * nq + q) * rct, 1, keep, N);
-                wire::writeWithSize(fds[q], out.data(), out.size());
-            }
+        for (uint32_t q = 0; q < nq; q++) sendResults(fds[q], pinRes + q * rct, b, nq * rct, keep, N);   // rows are [bin layer][query]
     }
 
 private:

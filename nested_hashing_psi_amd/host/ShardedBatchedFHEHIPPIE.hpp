@@ -48,7 +48,8 @@ public:
         // devices beyond the bin count stay idle (b = 14 on 16 GPUs); slices differ by at most one layer
         const uint32_t G = (uint32_t)std::min<size_t>(ccs.size(), b);
         for (uint32_t g = 0; g < G; g++) {
-            const uint32_t lo = (uint32_t)((uint64_t)b * g / G), hi = (uint32_t)((uint64_t)b * (g + 1) / G);
+            uint32_t lo = 0, hi = 0;
+            PieContext::check(piehip_rccl_bin_slice(b, (int)G, (int)g, &lo, &hi));   // the one rule of the ranges (no RCCL behind it)
             PieContext::check(piehip_load_db_table_bins(ccs[g]->handle(), hct.table, k, e, K, b, E, seeds.shuffle, seeds.mask, lo, hi));
             slices.push_back({lo, hi});
         }

@@ -82,46 +82,28 @@ public:
 
     void runSetUpPhase()
     {
+        // rank 0 reads the client's messages (.cpp:21-54) and forwards id, context, seeds, key; a worker reads those from rank 0
+        const int from = rank == 0 ? fd : side[0];
         std::vector<uint8_t> m;
-        ContextMessage c;
-        std::vector<uint64_t> evk;
+        auto readExactly = [&](void *dst, size_t bytes, const char *what) {
+            wire::readWithSizeIntoVector(from, m);
+            if (m.size() != bytes) throw std::runtime_error(what);
+            std::memcpy(dst, m.data(), bytes);
+        };
         uint8_t id[PIEHIP_RCCL_ID_BYTES];
+        if (rank > 0) readExactly(id, sizeof(id), "unique id message size");
+        const ContextMessage c = readContextMessage(from);
+        if (rank > 0) readExactly(seeds, sizeof(seeds), "seed message size");
+        else wire::readWithSizeIntoVector(from, m);  // public key: unused by the operator
+        const std::vector<uint64_t> evk = readEvalMultKey(from, c, rank == 0 ? c.moduli : nullptr);   // rank 0 has checked what it forwards
         if (rank == 0) {
-            wire::readWithSizeIntoVector(fd, m);
-            if (m.size() != sizeof(ContextMessage)) throw std::runtime_error("context message size");
-            std::memcpy(&c, m.data(), sizeof(c));
-            if (c.L < 1 || c.L > 7) throw std::invalid_argument("context: L out of range");
-            wire::readWithSizeIntoVector(fd, m);  // public key: unused by the operator
-            wire::readWithSizeIntoVector(fd, m);  // EvalMult key [L][2][L][N]
-            const size_t words = (size_t)c.L * 2 * c.L * c.N;
-            if (m.size() != words * sizeof(uint64_t)) throw std::runtime_error("EvalMult key message size");
-            evk.resize(words);
-            std::memcpy(evk.data(), m.data(), m.size());
-            wire::checkCanonical(evk.data(), (size_t)c.L * 2 * c.L, c.L, c.N, c.moduli, "EvalMult key");
             PieContext::check(piehip_rccl_unique_id(id));
-            for (int s : side) {  // session set-up for the workers: id, context, seeds, key
+            for (int s : side) {  // session set-up for the workers
                 wire::writeWithSize(s, id, sizeof(id));
                 wire::writeWithSize(s, &c, sizeof(c));
                 wire::writeWithSize(s, seeds, sizeof(seeds));
                 wire::writeWithSize(s, evk.data(), evk.size() * sizeof(uint64_t));
             }
-        } else {
-            const int s = side[0];
-            wire::readWithSizeIntoVector(s, m);
-            if (m.size() != sizeof(id)) throw std::runtime_error("unique id message size");
-            std::memcpy(id, m.data(), sizeof(id));
-            wire::readWithSizeIntoVector(s, m);
-            if (m.size() != sizeof(ContextMessage)) throw std::runtime_error("context message size");
-            std::memcpy(&c, m.data(), sizeof(c));
-            if (c.L < 1 || c.L > 7) throw std::invalid_argument("context: L out of range");
-            wire::readWithSizeIntoVector(s, m);
-            if (m.size() != sizeof(seeds)) throw std::runtime_error("seed message size");
-            std::memcpy(seeds, m.data(), sizeof(seeds));
-            wire::readWithSizeIntoVector(s, m);
-            const size_t words = (size_t)c.L * 2 * c.L * c.N;
-            if (m.size() != words * sizeof(uint64_t)) throw std::runtime_error("EvalMult key message size");
-            evk.resize(words);
-            std::memcpy(evk.data(), m.data(), m.size());
         }
         cc.reset(new PieContext(c.N, c.L, c.t, c.moduli, c.moduli + c.L, device));
         qMod.assign(c.moduli, c.moduli + c.L);
@@ -135,163 +117,116 @@ public:
 
     void runOfflinePhase()
     {
-        if (querySlices) return runSlicedOfflinePhase();
         const auto begin = std::chrono::steady_clock::now();
-        std::exception_ptr failed;
-        try {
-            if (hi <= lo) throw std::runtime_error("more ranks than bin layers: start at most eachBinSize server processes");
+        const uint32_t K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize;
+        buildAndAgree([&] {
+            if (!querySlices && hi <= lo) throw std::runtime_error("more ranks than bin layers: start at most eachBinSize server processes");
             if (failOfflineForTesting) throw std::runtime_error("offline phase failed on this rank (test)");
-            PieContext::check(piehip_build_db_bins(cc->handle(), serverSet.data(), serverSet.size(), ht.numberOfSimpleHashFunctions,
-                                                   ht.eachSimpleTableSize, ht.numberOfCuckooHashFunctions, ht.maxItemsPerPosition,
-                                                   ht.eachCuckooTableSize, hashSeed, seeds[0], seeds[1], seeds[2], lo, hi));
+            uint32_t ulo = 0, uhi = 0;
+            if (querySlices) {
+                PieContext::check(piehip_query_slice(K, cc->towers(), G, rank, &ulo, &uhi));
+                PieContext::check(piehip_build_db_sliced(cc->handle(), serverSet.data(), serverSet.size(), ht.numberOfSimpleHashFunctions,
+                                                         ht.eachSimpleTableSize, K, ht.maxItemsPerPosition, E, hashSeed, seeds[0], seeds[1],
+                                                         seeds[2], ulo, uhi, lo, hi));
+            } else {
+                PieContext::check(piehip_build_db_bins(cc->handle(), serverSet.data(), serverSet.size(), ht.numberOfSimpleHashFunctions,
+                                                       ht.eachSimpleTableSize, K, ht.maxItemsPerPosition, E, hashSeed, seeds[0], seeds[1],
+                                                       seeds[2], lo, hi));
+            }
             PieContext::check(piehip_sync(cc->handle()));
-        } catch (...) {
-            failed = std::current_exception();
-        }
-        // every rank says whether its slice is ready; a no anywhere ends the session everywhere (a Cuckoo insertion that failed
-        // -- CuckooHashTable.cpp:113 -- fails on every rank alike; out of memory on one GPU does not)
-        int allBuilt = 0;
-        PieContext::check(piehip_rccl_agree(cc->handle(), failed ? 0 : 1, &allBuilt, collectiveTimeoutMs));
-        if (failed) std::rethrow_exception(failed);
-        if (!allBuilt) throw std::runtime_error("another rank of the server group could not build its slice of the database");
+        });
         // one evaluation of an all-zero query through the whole online path (code objects, queues, the communicator's first
-        // collective) while nobody waits for it.  Only rank 0 stages queries from host memory: the workers get their device-side
-        // input buffers and run queues, no page-locked index matrix (29 MiB at C3 that nothing would ever write)
-        const size_t ct = ctWords();
-        uint64_t *pinIdx = nullptr, *pinMinus = nullptr, *pinRes = nullptr;
-        if (rank == 0)
-            PieContext::check(piehip_host_buffers(cc->handle(), &pinIdx, &pinMinus, &pinRes));
-        else
-            PieContext::check(piehip_host_buffers(cc->handle(), nullptr, nullptr, nullptr));
+        // collective) while nobody waits for it.  Only rank 0 ever holds a whole query in host memory: the workers of the broadcast mode
+        // get their device-side input buffers and run queues, no page-locked index matrix (29 MiB at C3 that nothing would ever write)
         if (rank == 0) {
-            const uint32_t K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize;
-            std::memset(pinMinus, 0, ct * sizeof(uint64_t));
-            std::memset(pinIdx, 0, (size_t)K * E * ct * sizeof(uint64_t));
-            PieContext::check(piehip_stage_minus(cc->handle(), pinMinus));
-            for (uint32_t h = 0; h < K; h++) PieContext::check(piehip_stage_index_row(cc->handle(), h, pinIdx + (size_t)h * E * ct));
+            uint64_t *pinIdx = nullptr, *pinMinus = nullptr;
+            hostArrays(&pinIdx, &pinMinus);
+            zeroQuery(pinIdx, pinMinus, K, E, ctWords());
+            if (!querySlices) {
+                PieContext::check(piehip_stage_minus(cc->handle(), pinMinus));
+                for (uint32_t h = 0; h < K; h++) PieContext::check(piehip_stage_index_row(cc->handle(), h, pinIdx + (size_t)h * E * ctWords()));
+            }
+        } else if (!querySlices) {
+            PieContext::check(piehip_host_buffers(cc->handle(), nullptr, nullptr, nullptr));
         }
-        evaluateStagedQuery();
+        evaluateQuery();
         offlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
     }
 
     void runOnlinePhase()
     {
-        if (querySlices) return runSlicedOnlinePhase();
-        const uint32_t L = cc->towers(), N = cc->ringDimension(), K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize,
-                       b = ht.maxItemsPerPosition;
-        const size_t ct = ctWords();
-        if (rank == 0) {
-            uint64_t *pinIdx = nullptr, *pinMinus = nullptr, *pinRes = nullptr;
-            PieContext::check(piehip_host_buffers(cc->handle(), &pinIdx, &pinMinus, &pinRes));
-            std::vector<uint8_t> m;
-            try {
-                wire::readWithSizeIntoVector(fd, m);  // receiveEncryptedMinusElements, .cpp:114-122
-                wire::unpackCiphertextsInto(m, L, N, pinMinus, 1, qMod.data());
-                PieContext::check(piehip_stage_minus(cc->handle(), pinMinus));
-                for (uint32_t h = 0; h < K; h++)  // receiveIndexMatrix, .cpp:124-141: every message staged as it lands
-                    for (uint32_t j = 0; j < E; j++) {
-                        wire::readWithSizeIntoVector(fd, m);
-                        wire::unpackCiphertextsInto(m, L, N, pinIdx + ((size_t)h * E + j) * ct, 1, qMod.data());
-                        PieContext::check(piehip_stage_index_ct_q(cc->handle(), 0, h, j, pinIdx + ((size_t)h * E + j) * ct));
-                    }
-            } catch (...) {
-                piehip_stage_reset(cc->handle());
-                throw;
-            }
-        }
-        const auto begin = std::chrono::steady_clock::now();
-        const uint64_t *results = evaluateStagedQuery();  // .cpp:101-103 across the ranks
-        onlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
-        if (rank == 0)
-            for (uint32_t i = 0; i < b; i++) {  // sendResult, .cpp:143-152
-                const auto out = wire::packCiphertexts(results + (size_t)i * ct, 1, L, N);
-                wire::writeWithSize(fd, out.data(), out.size());
-            }
-    }
-
-    // ---- query-sliced mode ------------------------------------------------------------------------------------------------------
-    void runSlicedOfflinePhase()
-    {
-        const auto begin = std::chrono::steady_clock::now();
-        const uint32_t K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize;
-        std::exception_ptr failed;
-        try {
-            if (failOfflineForTesting) throw std::runtime_error("offline phase failed on this rank (test)");
-            uint32_t ulo = 0, uhi = 0;
-            PieContext::check(piehip_query_slice(K, cc->towers(), G, rank, &ulo, &uhi));
-            PieContext::check(piehip_build_db_sliced(cc->handle(), serverSet.data(), serverSet.size(), ht.numberOfSimpleHashFunctions,
-                                                     ht.eachSimpleTableSize, K, ht.maxItemsPerPosition, E, hashSeed, seeds[0], seeds[1],
-                                                     seeds[2], ulo, uhi, lo, hi));
-            PieContext::check(piehip_sync(cc->handle()));
-        } catch (...) {
-            failed = std::current_exception();
-        }
-        int allBuilt = 0;   // as in runOfflinePhase: a no anywhere ends the session everywhere
-        PieContext::check(piehip_rccl_agree(cc->handle(), failed ? 0 : 1, &allBuilt, collectiveTimeoutMs));
-        if (failed) std::rethrow_exception(failed);
-        if (!allBuilt) throw std::runtime_error("another rank of the server group could not build its slice of the database");
-        // one evaluation of an all-zero query through the whole online path while nobody waits for it; only rank 0 ever holds a whole query
+        const uint32_t L = cc->towers(), N = cc->ringDimension(), K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize;
         if (rank == 0) {
             uint64_t *pinIdx = nullptr, *pinMinus = nullptr;
-            PieContext::check(piehip_slice_host_buffers_q(cc->handle(), 0, &pinIdx, &pinMinus));
-            std::memset(pinMinus, 0, ctWords() * sizeof(uint64_t));
-            std::memset(pinIdx, 0, (size_t)K * E * ctWords() * sizeof(uint64_t));
-        }
-        evaluateSlicedQuery();
-        offlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
-    }
-
-    void runSlicedOnlinePhase()
-    {
-        const uint32_t L = cc->towers(), N = cc->ringDimension(), K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize,
-                       b = ht.maxItemsPerPosition;
-        const size_t ct = ctWords();
-        if (rank == 0) {
-            uint64_t *pinIdx = nullptr, *pinMinus = nullptr;
-            PieContext::check(piehip_slice_host_buffers_q(cc->handle(), 0, &pinIdx, &pinMinus));
-            std::vector<uint8_t> m;
-            wire::readWithSizeIntoVector(fd, m);  // receiveEncryptedMinusElements, .cpp:114-122
-            wire::unpackCiphertextsInto(m, L, N, pinMinus, 1, qMod.data());
-            for (uint32_t h = 0; h < K; h++)  // receiveIndexMatrix, .cpp:124-141
-                for (uint32_t j = 0; j < E; j++) {
-                    wire::readWithSizeIntoVector(fd, m);
-                    wire::unpackCiphertextsInto(m, L, N, pinIdx + ((size_t)h * E + j) * ct, 1, qMod.data());
+            hostArrays(&pinIdx, &pinMinus);
+            if (querySlices) {   // the scatter reads the host arrays: nothing is staged
+                receiveQuery(fd, L, N, K, E, qMod.data(), pinIdx, pinMinus);
+            } else {
+                try {   // every message staged as it lands
+                    receiveQuery(fd, L, N, K, E, qMod.data(), pinIdx, pinMinus, stagePieces(cc->handle(), 0));
+                } catch (...) {
+                    piehip_stage_reset(cc->handle());
+                    throw;
                 }
+            }
         }
         const auto begin = std::chrono::steady_clock::now();
-        const uint64_t *results = evaluateSlicedQuery();  // .cpp:101-103 across the ranks
+        const uint64_t *results = evaluateQuery();  // .cpp:101-103 across the ranks
         onlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
-        if (rank == 0)
-            for (uint32_t i = 0; i < b; i++) {  // sendResult, .cpp:143-152
-                const auto out = wire::packCiphertexts(results + (size_t)i * ct, 1, L, N);
-                wire::writeWithSize(fd, out.data(), out.size());
-            }
+        if (rank == 0) sendResults(fd, results, ht.maxItemsPerPosition, ctWords(), L, N);
     }
 
 private:
-    // the query in rank 0's host arrays -> every rank's units; stage A there; accumulators -> the ranks of their bin layers; the chains;
-    // results -> rank 0's host memory.  Returns the b result ciphertexts (rank 0).
+    size_t ctWords() const { return 2 * (size_t)cc->towers() * cc->ringDimension(); }
+
+    // rank 0's page-locked whole-query arrays
+    void hostArrays(uint64_t **pinIdx, uint64_t **pinMinus)
+    {
+        uint64_t *pinRes = nullptr;
+        if (querySlices) PieContext::check(piehip_slice_host_buffers_q(cc->handle(), 0, pinIdx, pinMinus));
+        else PieContext::check(piehip_host_buffers(cc->handle(), pinIdx, pinMinus, &pinRes));
+    }
+
+    // Runs this rank's database build; then every rank says whether its slice is ready, and a no anywhere ends the session everywhere (a
+    // Cuckoo insertion that failed -- CuckooHashTable.cpp:113 -- fails on every rank alike; out of memory on one GPU does not)
+    template <typename Build>
+    void buildAndAgree(Build build)
+    {
+        std::exception_ptr failed;
+        try {
+            build();
+        } catch (...) {
+            failed = std::current_exception();
+        }
+        int allBuilt = 0;
+        PieContext::check(piehip_rccl_agree(cc->handle(), failed ? 0 : 1, &allBuilt, collectiveTimeoutMs));
+        if (failed) std::rethrow_exception(failed);
+        if (!allBuilt) throw std::runtime_error("another rank of the server group could not build its slice of the database");
+    }
+
+    // One query across the ranks; returns the b result ciphertexts (rank 0).
+    const uint64_t *evaluateQuery() { return querySlices ? evaluateSlicedQuery() : evaluateStagedQuery(); }
+    // the query in rank 0's host arrays -> every rank's units; stage A there; accumulators -> the ranks of their bin layers; the chains
     const uint64_t *evaluateSlicedQuery()
     {
         PieContext::check(piehip_rccl_scatter_query(cc->handle(), 0));
         PieContext::check(piehip_run_slice(cc->handle()));
         PieContext::check(piehip_rccl_exchange_accumulators(cc->handle()));
         PieContext::check(piehip_run_chain(cc->handle()));
-        uint64_t *gathered = nullptr;
-        PieContext::check(piehip_gather_results_host(cc->handle(), ht.maxItemsPerPosition, 0, &gathered));
-        PieContext::check(piehip_rccl_wait(cc->handle(), collectiveTimeoutMs));
-        return gathered;
+        return gatherToRoot();
     }
-
-    size_t ctWords() const { return 2 * (size_t)cc->towers() * cc->ringDimension(); }
-    // the query staged on rank 0 -> every rank; run(); results -> rank 0's host memory.  Returns the b result ciphertexts (rank 0).
+    // the query staged on rank 0 -> every rank; run()
     const uint64_t *evaluateStagedQuery()
     {
-        const uint32_t b = ht.maxItemsPerPosition;
         PieContext::check(piehip_rccl_broadcast_query(cc->handle(), 0));
         PieContext::check(piehip_run(cc->handle()));
-        uint64_t *gathered = nullptr;  // rank 0: page-locked, owned by the library, [b][2][L][N] in bin order
-        PieContext::check(piehip_gather_results_host(cc->handle(), b, 0, &gathered));
+        return gatherToRoot();
+    }
+    // results -> rank 0's host memory: page-locked, owned by the library, [b][2][L][N] in bin order
+    const uint64_t *gatherToRoot()
+    {
+        uint64_t *gathered = nullptr;
+        PieContext::check(piehip_gather_results_host(cc->handle(), ht.maxItemsPerPosition, 0, &gathered));
         PieContext::check(piehip_rccl_wait(cc->handle(), collectiveTimeoutMs));   // piehip_sync with a bound
         return gathered;
     }

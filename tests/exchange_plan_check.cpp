@@ -1,13 +1,16 @@
-// The plan of the scatter and the exchange of query slices across ranks (csrc/exchange_plan.h, the only include of the library here),
-// on the CPU, for every G in 1..9, every root and five shapes (K, L, b, nq) that include G > K L and G > b:
+// The plan of the scatter and the exchange of query slices across ranks and of the final gather of the results (csrc/exchange_plan.h, the
+// only include of the library here), on the CPU, for every G in 1..9, every root and five shapes (K, L, b, nq) that include G > K L and G > b:
 //   (a) the unit and bin ranges tile [0, K L) and [0, b); they are printed ("range ..." lines) for tests/test_exchange_plan.py, which
 //       compares them with piehip_query_slice and piehip_rccl_bin_slice of the built library;
-//   (b) every send has exactly one matching receive of the same size, and a transfer with u_n_s = 0 or bin_n_d = 0 is on neither side;
+//   (b) every send has exactly one matching receive of the same size, and a transfer with u_n_s = 0 or bin_n_d = 0 is on neither side
+//       (the gather: a rank without bin layers posts nothing, nobody posts anything towards it);
 //   (c) every rank executes its list strictly in order over channels WITHOUT any buffering -- a send completes only when the peer's
-//       next operation is the matching receive -- and every rank finishes: the scatter, the exchange, and the one behind the other;
+//       next operation is the matching receive -- and every rank finishes: the scatter, the exchange, the gather, the exchange behind
+//       the scatter and the gather behind both;
 //   (d) the plan carried out with memcpy between buffers of exactly the stated sizes (the sanitizers this is also built with see a
 //       block outside either) on arrays whose words encode (row, query, unit, component, n): every word of every destination's
-//       [rows][nq][K L][2][N] is written exactly once, with the right value; the scatter likewise for every receiver's slice inputs.
+//       [rows][nq][K L][2][N] is written exactly once, with the right value; the scatter likewise for every receiver's slice inputs,
+//       the gather for the root's [b][nq][2][L][N], where the root's own rows are copied in place of the device copy.
 // `exchange_plan_check naive` posts all sends first, then all receives, for G = 2 and reports that simulation (c) then deadlocks:
 // the check can fail.
 #include <stdio.h>
@@ -206,6 +209,44 @@ static int check_scatter(const ExchangeShape &sh, int G, int root)
     return 0;
 }
 
+static int check_gather(const ExchangeShape &sh, int G, int root)
+{
+    const size_t row = (size_t)sh.nq * 2 * sh.L * sh.N;   // words per bin layer; word w of layer beta holds 1 + beta row + w
+    Lists lists(G), all(G);
+    std::vector<u32> b_lo(G), b_hi(G);
+    long want = 0;
+    for (int r = 0; r < G; r++) {
+        lists[r] = gather_plan(sh, G, r, root);
+        for (const std::vector<PlanTransfer> &x : {scatter_plan(sh, G, r, root), exchange_plan(sh, G, r), lists[r]}) all[r].insert(all[r].end(), x.begin(), x.end());
+        plan_bin_range(sh, G, r, &b_lo[r], &b_hi[r]);
+        want += r != root && b_hi[r] > b_lo[r];
+    }
+    if (matched(lists) != want) return printf("gather: %ld transfers expected\n", want), 1;
+    if (!completes(lists)) return printf("gather: a rank never finishes its list\n"), 1;
+    if (!completes(all)) return printf("scatter, exchange, then gather: a rank never finishes its list\n"), 1;
+    // (d)
+    std::vector<u64> gathered((size_t)sh.b * row, UNTOUCHED);
+    std::vector<int> written(gathered.size(), 0);
+    for (int s = 0; s < G; s++) {
+        std::vector<u64> rows((size_t)(b_hi[s] - b_lo[s]) * row);   // the rank's result buffer, exactly its bin layers
+        for (size_t w = 0; w < rows.size(); w++) rows[w] = 1 + (size_t)b_lo[s] * row + w;
+        PlanTransfer own = {true, root, PLAN_RESULT_ROWS, 0, 0, rows.size()}, own_at = {false, s, PLAN_GATHERED, 0, (size_t)b_lo[s] * row, rows.size()};
+        const PlanTransfer *t = &own, *o = &own_at;   // the root's own rows: the device copy's stand-in
+        if (s != root && lists[s].size() != (rows.empty() ? 0u : 1u)) return printf("gather: rank %d posts %zu transfers\n", s, lists[s].size()), 1;
+        if (rows.empty()) continue;
+        if (s != root) {
+            t = &lists[s][0], o = receive_of(lists, s, root, 0);
+            if (!t->send || t->peer != root || t->buf != PLAN_RESULT_ROWS || !o || o->buf != PLAN_GATHERED) return printf("gather: wrong transfer or buffer\n"), 1;
+        }
+        if (t->off + t->words > rows.size() || o->off + o->words > gathered.size() || o->words != t->words) return printf("gather: block out of bounds\n"), 1;
+        memcpy(gathered.data() + o->off, rows.data() + t->off, t->words * sizeof(u64));
+        for (size_t w = 0; w < t->words; w++) written[o->off + w]++;
+    }
+    for (size_t w = 0; w < gathered.size(); w++)
+        if (written[w] != 1 || gathered[w] != 1 + w) return printf("gather: word %zu written %d times or wrong\n", w, written[w]), 1;
+    return 0;
+}
+
 // all sends, then all receives: what the posting order is there to avoid
 static std::vector<PlanTransfer> naive_order(const std::vector<PlanTransfer> &plan)
 {
@@ -247,7 +288,7 @@ int main(int argc, char **argv)
             if (u_next != sh.K * sh.L || b_next != sh.b) return printf("FAILED: the ranges do not cover (G %d)\n", G), 1;
             if (check_exchange(sh, G)) return printf("FAILED: K %u L %u b %u nq %u G %d\n", sh.K, sh.L, sh.b, sh.nq, G), 1;
             for (int root = 0; root < G; root++, cases++)
-                if (check_scatter(sh, G, root)) return printf("FAILED: K %u L %u b %u nq %u G %d root %d\n", sh.K, sh.L, sh.b, sh.nq, G, root), 1;
+                if (check_scatter(sh, G, root) || check_gather(sh, G, root)) return printf("FAILED: K %u L %u b %u nq %u G %d root %d\n", sh.K, sh.L, sh.b, sh.nq, G, root), 1;
         }
     }
     printf("exchange plan ok: %zu cases\n", cases);

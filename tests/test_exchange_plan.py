@@ -1,6 +1,8 @@
-"""The plan of piehip_rccl_scatter_query and piehip_rccl_exchange_accumulators (csrc/exchange_plan.h) without a GPU:
-tests/exchange_plan_check.cpp matches every send with its receive, runs every rank's list in its posting order over channels without
-any buffering, and carries the plan out with memcpy, for G = 1..9 and five shapes that include G > K L and G > b.  Built twice with
+"""The plan of piehip_rccl_scatter_query, piehip_rccl_exchange_accumulators and piehip_gather_results (csrc/exchange_plan.h) without a
+GPU: tests/exchange_plan_check.cpp matches every send with its receive, runs every rank's list in its posting order over channels
+without any buffering -- each collective alone, and the gather as the third step behind the scatter and the exchange -- and carries the
+plan out with memcpy, for G = 1..9, every root and five shapes that include G > K L and G > b (ranks without bin layers post nothing in
+the gather; every word of the root's [b][nq][2][L][N] is written exactly once, its own rows by the device copy's stand-in).  Built twice with
 the host compiler -- plain, and under AddressSanitizer + UndefinedBehaviorSanitizer with their runtimes linked into the program --
 and run as plain executables.  The ranges it prints are compared with piehip_query_slice and piehip_rccl_bin_slice of the built
 library; and posting all sends first must deadlock in the same simulation, so the simulation can fail."""
