@@ -153,6 +153,7 @@ void launch_stage_a(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, cons
                     u32 q = 0, const StageAXOut *xo = nullptr);
 // Stage A of a batch of nq <= STAGE_A_MAX_QUERIES queries on one database: acc[b][nq][K][2][L][N].  Where the column-accumulator
 // kernel applies (small_moduli) the queries go through it in groups of two to four, each group reading the database once
+// (a group of three on a ring that fills the chip through stage_a_resident_kernel: stage_a_resident_lpp of stage_a_common.h)
 static const u32 STAGE_A_MAX_QUERIES = 8;
 struct StageAQueries {
     const u64 *idx[STAGE_A_MAX_QUERIES];

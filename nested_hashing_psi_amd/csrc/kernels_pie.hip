@@ -228,6 +228,91 @@ __global__ void __launch_bounds__(TPB) stage_a_mad_batch_kernel(const DevConsts 
     }
 }
 
+// The other loop order for a batch of Q queries: layers outside, index words resident.  A thread -- one coefficient of one limb
+// of one inner hash function, as above -- loads the 2 Q E index words of its coefficient ONCE, keeps them in registers as 30-bit
+// halves, and lets the database words of its block's layers stream past them, one layer's 2 Q accumulators at a time.  Index and
+// database words are then each read exactly once per launch (the tiled kernel re-reads the index words from the L2 once per
+// group of BPT layers), at the price of 4 Q E registers: Q = 3, E = 14 is what a thread of 256 registers holds, two waves per SIMD.
+// The database words of a (h, l, coefficient block) over consecutive layers are ONE strided stream (word layer E + j at
+// pd + (layer E + j) L N): a ring of D words runs over it across the layer boundaries, so the first words of layer beta + 1 are
+// in flight under the epilogue of layer beta.  D divides E: the ring slot of a term is then a compile-time constant.  Every refill
+// is unconditional; past the last word of the block's layers the stream repeats that word (an address inside the array, an L2 hit
+// nobody consumes).  E <= COLACC_MAX_TOTAL - 1 terms: one carry sweep after term COLACC_MAX_TERMS, no mid-sum reduction.
+// The block-to-tile map is stage_a_tile with `groups` = partitions of the layer range (lpp layers each, the last one shorter).
+template <int Q, int E, int D>
+__global__ void __launch_bounds__(TPB) stage_a_resident_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 K, u32 b, u32 lpp,
+                                                               StageAQueries qs, const u64 *__restrict__ db, u64 *__restrict__ acc,
+                                                               u32 bstride, u32 h0, u32 nq, u32 q0, u32 tiles, StageAXOut xo)
+{
+    static_assert(E % D == 0 && E >= 1 && (u32)E < COLACC_MAX_TOTAL && (u32)E <= 2 * COLACC_MAX_TERMS, "ring slots and sweep periods");
+    StageATile tl;
+    if (!stage_a_tile((N + TPB - 1) / TPB, L, tiles, (b + lpp - 1) / lpp, tl)) return;
+    const u32 nl = threadIdx.x, n0 = tl.bx * TPB, l = tl.l, h = h0 + tl.hz, beta0 = tl.grp * lpp;
+    const u32 n = n0 + nl;
+    if (n >= N) return;
+    const u32 nlay = __builtin_amdgcn_readfirstlane(min(lpp, b - beta0));
+    const Mod m = dc->mod[l];
+    const size_t LN = (size_t)L * N;
+    const size_t ioff = ((size_t)h * E) * 2 * LN + (size_t)l * N + n0;
+    const u64 *pw = db + (((size_t)h * bstride + beta0) * E) * LN + (size_t)l * N + n0;   // the next word the ring fetches
+    u32 left = nlay * E - 1;   // words behind the one pw points to; at 0 the stream repeats its last word
+    // the ring first: its words are the oldest loads in flight when the first term asks for one
+    u64 r[D];
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        r[d] = __builtin_nontemporal_load(pw + nl);
+        pw += left ? LN : 0, left -= left ? 1 : 0;
+    }
+    Split30 ix[Q][E][2];
+    u64 mi[Q][2];
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+#pragma unroll
+        for (int j = 0; j < E; j++)
+#pragma unroll
+            for (int c = 0; c < 2; c++) ix[q][j][c] = split30((qs.idx[q] + ioff + (size_t)(2 * j + c) * LN)[nl]);
+#pragma unroll
+        for (int c = 0; c < 2; c++) mi[q][c] = qs.minus[q][(size_t)c * LN + (size_t)l * N + n];
+    }
+    const bool xdir = h == 0 && xo.out != nullptr;
+    const u32 noff = n + ((xdir ? ~0u : 0u) & (lane_home(n, xo.logns) - n));
+    const size_t cstride = xdir ? (size_t)xo.M * N : LN;
+    for (u32 t = 0; t < nlay; t++) {
+        ColAcc a[Q][2];
+#pragma unroll
+        for (int j = 0; j < E; j++) {
+            const u64 d = r[j % D];
+            const u32 dl = (u32)d & 0x3FFFFFFFu, dh = (u32)(d >> 30);
+            r[j % D] = __builtin_nontemporal_load(pw + nl);   // refill the slot: the other D - 1 words stay in flight
+            pw += left ? LN : 0, left -= left ? 1 : 0;
+            PIE_STAGE_A_FENCE();
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                if (j == 0) colacc_mac2_cut<true>(a[q][0], a[q][1], ix[q][j][0], ix[q][j][1], dl, dh);
+                else colacc_mac2_cut<false>(a[q][0], a[q][1], ix[q][j][0], ix[q][j][1], dl, dh);
+            }
+            if (j == (int)COLACC_MAX_TERMS - 1 && j + 1 < E) {   // more terms follow: make room in the low columns
+#pragma unroll
+                for (int q = 0; q < Q; q++) colacc_carry(a[q][0]), colacc_carry(a[q][1]);
+            }
+            PIE_STAGE_A_FENCE();
+        }
+        // the epilogue of the tiled kernel.  Its stores are younger than the D ring words in flight: the next term waits for its
+        // own word with the stores still outstanding
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            // (row base from scratch per layer and query, all scalar: carried across the layers as a pointer it went into vector
+            // registers -- 258 with the index words, one wave per SIMD)
+            const size_t row = (size_t)(beta0 + t) * nq + q0 + q;
+            u64 *const base = xdir ? xo.out + ((row * 4) * xo.M + l) * N : acc + ((row * K + h) * 2) * LN + (size_t)l * N;
+            u64 *const po = base + noff;
+#pragma unroll
+            for (int c = 0; c < 2; c++) po[(size_t)c * cstride] = addmod_nb(colacc_reduce<true>(a[q][c], m, 0 - m.q), mi[q][c], m.q);
+        }
+        PIE_STAGE_A_FENCE();
+    }
+}
+
 // one launch over b bin layers whose count is a multiple of the per-thread layer count `bpt`
 static void launch_stage_a_uniform(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const u64 *idx, const u64 *minus,
                                    const u64 *db, u64 *acc, hipStream_t st, bool mad, u32 bstride, u32 h0, u32 hn, int bpt, u32 nq,
@@ -314,6 +399,15 @@ static void launch_stage_a_batch_q(const DevConsts *dc, u32 N, u32 L, u32 K, u32
     if (bpt == 2) return launch_stage_a_batch_qb<Q, 2>(dc, N, L, K, b, E, qs, db, acc, st, bstride, h0, hn, nq, q0, xo);
     return launch_stage_a_batch_qb<Q, 1>(dc, N, L, K, b, E, qs, db, acc, st, bstride, h0, hn, nq, q0, xo);
 }
+// three queries, resident index words (stage_a_resident_lpp said so): `lpp` layers per partition
+template <int E>
+static void launch_stage_a_resident(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 lpp, const StageAQueries &qs, const u64 *db,
+                                    u64 *acc, hipStream_t st, u32 bstride, u32 h0, u32 hn, u32 nq, u32 q0, StageAXOut xo)
+{
+    const u32 nx = (N + TPB - 1) / TPB;
+    hipLaunchKernelGGL((stage_a_resident_kernel<3, E, stage_a_resident_ring(E)>), stage_a_grid(nx, L, hn, (b + lpp - 1) / lpp), dim3(TPB), 0, st,
+                       dc, N, L, K, b, lpp, qs, db, acc, bstride, h0, nq, q0, nx * L * hn, xo);
+}
 void launch_stage_a_batch(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const StageAQueries &qs, u32 nq, const u64 *db,
                           u64 *acc, hipStream_t st, bool small_moduli, u32 bstride, u32 h0, u32 hn, const StageAXOut *xop)
 {
@@ -327,7 +421,12 @@ void launch_stage_a_batch(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E
         StageAQueries sub = {};
         for (u32 q = 0; q < g; q++) sub.idx[q] = qs.idx[q0 + q], sub.minus[q] = qs.minus[q0 + q];
         if (g == 2) launch_stage_a_batch_q<2>(dc, N, L, K, b, E, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
-        else if (g == 3) launch_stage_a_batch_q<3>(dc, N, L, K, b, E, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
+        else if (g == 3) {
+            const u32 lpp = stage_a_resident_lpp(3, E, b, (u64)N * L * hn);
+            if (lpp && E == 14) launch_stage_a_resident<14>(dc, N, L, K, b, lpp, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
+            else if (lpp && E == 12) launch_stage_a_resident<12>(dc, N, L, K, b, lpp, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
+            else launch_stage_a_batch_q<3>(dc, N, L, K, b, E, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
+        }
         else launch_stage_a_batch_q<4>(dc, N, L, K, b, E, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
         q0 += g;
     }

@@ -1,8 +1,9 @@
 // stage_a_common.h -- what the stage A kernels of kernels_pie.hip (the whole query on one handle) and kernels_slice.hip (one handle's
 // (inner hash function, limb) units) share: the block -> tile map, the lane-ordered home of a coefficient, the instruction blocks of
 // the epilogue (column accumulator -> residue, the sum with the minus word), the term loop of the tiled kernels (stage_a_terms:
-// stage_a_mad_batch_kernel and stage_a_slice_kernel are a prologue and an epilogue around it) and, for their launchers, the rules
-// that pick query groups, bin layers per thread and terms in flight (stage_a_query_group, stage_a_layers, stage_a_depth).
+// stage_a_mad_batch_kernel and stage_a_slice_kernel are a prologue and an epilogue around it), the multiply-add block of the
+// resident kernel (colacc_mac2_cut) and, for the launchers, the rules that pick query groups, bin layers per thread, terms in flight
+// and the resident or the tiled kernel (stage_a_query_group, stage_a_layers, stage_a_depth, stage_a_resident_lpp).
 #pragma once
 #include "kernels.hpp"
 #include "madasm.h"
@@ -281,6 +282,45 @@ __device__ __forceinline__ void stage_a_terms(const StageAQueries &qs, size_t io
 }
 
 // ---------------------------------------------------------------------------------------------
+// Pieces of the resident kernel (stage_a_resident_kernel of kernels_pie.hip): the other loop order.  The thread keeps the index
+// words of its coefficient in registers, already cut into 30-bit halves, and the database words of the launch's layers stream
+// past them -- so a database word arrives once for the Q queries and is cut once, not once per query as in colacc_mac2.
+// ---------------------------------------------------------------------------------------------
+// colacc_mac2 on a database word that is already cut (dl, dh).  FIRST: the term that opens a layer's sum -- the accumulators
+// are written, not read, so the layer needs no zeroing moves.
+// (between the terms: keeps each refill where it is written, at the top of its term, and the multiply-adds of a term together)
+#define PIE_STAGE_A_FENCE() __builtin_amdgcn_sched_barrier(0)
+template <bool FIRST>
+__device__ __forceinline__ void colacc_mac2_cut(ColAcc &a, ColAcc &b, Split30 x0, Split30 x1, u32 dl, u32 dh)
+{
+    if (FIRST) {
+        asm("v_mad_u64_u32 %[a0], vcc, %[x0l], %[dl], 0\n\t"
+            "v_mad_u64_u32 %[a1], vcc, %[x0l], %[dh], 0\n\t"
+            "v_mad_u64_u32 %[b0], vcc, %[x1l], %[dl], 0\n\t"
+            "v_mad_u64_u32 %[b1], vcc, %[x1l], %[dh], 0\n\t"
+            "v_mad_u64_u32 %[a2], vcc, %[x0h], %[dh], 0\n\t"
+            "v_mad_u64_u32 %[b2], vcc, %[x1h], %[dh], 0\n\t"
+            "v_mad_u64_u32 %[a1], vcc, %[x0h], %[dl], %[a1]\n\t"
+            "v_mad_u64_u32 %[b1], vcc, %[x1h], %[dl], %[b1]\n\t"
+            : [a0] "=&v"(a.c0), [a1] "=&v"(a.c1), [a2] "=&v"(a.c2), [b0] "=&v"(b.c0), [b1] "=&v"(b.c1), [b2] "=&v"(b.c2)
+            : [dl] "v"(dl), [dh] "v"(dh), [x0l] "v"(x0.lo), [x0h] "v"(x0.hi), [x1l] "v"(x1.lo), [x1h] "v"(x1.hi)
+            : "vcc");
+    } else {
+        asm("v_mad_u64_u32 %[a0], vcc, %[x0l], %[dl], %[a0]\n\t"
+            "v_mad_u64_u32 %[a1], vcc, %[x0l], %[dh], %[a1]\n\t"
+            "v_mad_u64_u32 %[b0], vcc, %[x1l], %[dl], %[b0]\n\t"
+            "v_mad_u64_u32 %[b1], vcc, %[x1l], %[dh], %[b1]\n\t"
+            "v_mad_u64_u32 %[a2], vcc, %[x0h], %[dh], %[a2]\n\t"
+            "v_mad_u64_u32 %[b2], vcc, %[x1h], %[dh], %[b2]\n\t"
+            "v_mad_u64_u32 %[a1], vcc, %[x0h], %[dl], %[a1]\n\t"
+            "v_mad_u64_u32 %[b1], vcc, %[x1h], %[dl], %[b1]\n\t"
+            : [a0] "+v"(a.c0), [a1] "+v"(a.c1), [a2] "+v"(a.c2), [b0] "+v"(b.c0), [b1] "+v"(b.c1), [b2] "+v"(b.c2)
+            : [dl] "v"(dl), [dh] "v"(dh), [x0l] "v"(x0.lo), [x0h] "v"(x0.hi), [x1l] "v"(x1.lo), [x1h] "v"(x1.hi)
+            : "vcc");
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Launch rules of the tiled kernels (launch_stage_a_batch, launch_stage_a_slice).
 // ---------------------------------------------------------------------------------------------
 // Queries of the next launch, given the queries left: groups of four, three or two (five: 3 + 2; six: 3 + 3; seven: 4 + 3); a single
@@ -316,4 +356,38 @@ static_assert(stage_a_layers(3, 12, stage_a_layer_cap(3, true)) == 3, "twelve la
 // query: stage_a_mad_kernel's four, and three with seven layers (176 registers with four, 168 are the most that leave three waves
 // per SIMD).
 constexpr int stage_a_depth(int Q, int BPT) { return Q == 1 ? (BPT == 7 ? 3 : 4) : (Q == 4 || Q * BPT >= 9) ? 2 : 3; }
+
+// The resident kernel (stage_a_resident_kernel) or the tiled one, for a launch of Q queries over b layers with `threads` = N L hn
+// coefficients.  -DPIEHIP_STAGE_A_RESIDENT=0 keeps every launch on the tiled kernel (A/B builds).
+#ifndef PIEHIP_STAGE_A_RESIDENT
+#define PIEHIP_STAGE_A_RESIDENT 1
+#endif
+// Words in the database ring of the instantiation for E, 0 where there is none: E = 14 (C3) and E = 12 (C2) are built, every other
+// E stays on the tiled kernel (4 Q E index registers: Q = 3, E = 14 is the cap, and Q = 4 does not fit at any E worth having).
+constexpr int stage_a_resident_ring(u32 E) { return E == 14 ? 7 : E == 12 ? 6 : 0; }
+// Layers per partition of the resident launch, 0 = the tiled kernel.  From tools/microbench_stage_a_batch.hip
+// (profiles/stage_a_resident/microbench.txt), resident against the tiling it replaces:
+//   131 072 threads (C3's ring, two waves on every SIMD): 14 layers 65.7 us against 82.0, 8 layers 46.3 / 52.6, 6 layers 39.4 / 40.6,
+//   5 layers 35.8 / 40.0, 4 layers 32.4 / 34.1;
+//   49 152 threads (C2's ring, E = 12: three quarters of ONE wave per SIMD): 33.1 us against 28.7, and 30.5 / 32.8 in partitions of
+//   6 / 4 layers -- two waves of 250 registers hide less latency than the tiled kernel's three, and there are not enough of them.
+// So: at least STAGE_A_RESIDENT_MIN_THREADS coefficients, one wave of 64 on each of the chip's 1024 SIMDs (nothing between the two
+// rings was measured), and no partitions -- halving the layer range cost 2.7-7 us at every layer count of C3's ring (each partition
+// loads the index words again).  A launch of one tiled layer group (b <= 3) reads its index words once there too and keeps three
+// waves per SIMD.
+constexpr u64 STAGE_A_RESIDENT_MIN_THREADS = 65536;
+constexpr u32 stage_a_resident_lpp(u32 Q, u32 E, u32 b, u64 threads)
+{
+    if (!PIEHIP_STAGE_A_RESIDENT || Q != 3 || !stage_a_resident_ring(E) || b <= stage_a_layer_cap(3, true)) return 0;
+    return threads >= STAGE_A_RESIDENT_MIN_THREADS ? b : 0;
+}
+#if PIEHIP_STAGE_A_RESIDENT
+static_assert(stage_a_resident_lpp(3, 14, 14, 16384 * 4 * 2) == 14 && stage_a_resident_lpp(3, 14, 8, 16384 * 4 * 2) == 8 &&
+                  stage_a_resident_lpp(3, 14, 6, 16384 * 4 * 2) == 6,
+              "C3, three queries: resident on one queue (14 layers) and on two (8 + 6), one partition each");
+#endif
+static_assert(stage_a_resident_lpp(3, 15, 14, 16384 * 4 * 2) == 0 && stage_a_resident_lpp(4, 14, 14, 16384 * 4 * 2) == 0 &&
+                  stage_a_resident_lpp(3, 14, 3, 16384 * 4 * 2) == 0 && stage_a_resident_lpp(2, 14, 14, 16384 * 4 * 2) == 0,
+              "E = 15, four or two queries and a launch of one layer group stay on the tiled kernel");
+static_assert(stage_a_resident_lpp(3, 12, 12, 8192 * 3 * 2) == 0, "C2 stays on the tiled kernel (under one wave per SIMD)");
 }  // namespace piehip

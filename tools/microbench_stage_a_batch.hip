@@ -1,6 +1,7 @@
 // Stage A's query-batch kernel in isolation (tools/, not shipped): the shipped kernel source over a rotation of databases
 // (every launch streams the database from HBM), per (queries, layers per thread, terms in flight), with the
-// queries' index matrices distinct or all the same array (how much of the time is index-matrix traffic).
+// queries' index matrices distinct or all the same array (how much of the time is index-matrix traffic); and the resident kernel
+// (stage_a_resident_kernel: index words in registers, layers streaming past) beside the shipped tilings, at the C3 and the C2 ring.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Inested_hashing_psi_amd/csrc tools/microbench_stage_a_batch.hip -o build_lab/mbsab
 #include "../nested_hashing_psi_amd/csrc/kernels_pie.hip"
 #include <cstdio>
@@ -10,7 +11,8 @@ using namespace piehip;
 typedef unsigned __int128 u128;
 static const int NBUF = 6;
 static size_t DBW;
-static const u32 N = 16384, L = 4, K = 2, B = 14, E = 14;
+static const u32 K = 2;
+static u32 N = 16384, L = 4, B = 14, E = 14;   // the C3 ring; main() switches to C2's (8192, 3, 12, 12) for its last rows
 static u64 *g_idx[8], *g_minus, *g_db, *g_acc;
 static DevConsts *g_dc;
 
@@ -28,7 +30,7 @@ static void run(bool same_idx, u32 Bl = B)   // Bl: bin layers of this launch (<
     for (int rep = 0; rep < NREP; rep++) {
         const u64 *db = g_db + (size_t)(rep % NBUF) * DBW;
         CK(hipEventRecord(e0, 0));
-        hipLaunchKernelGGL((stage_a_mad_batch_kernel<BPT, Q, DEPTH>), grid, dim3(TPB), 0, 0, g_dc, N, L, K, B, E, qs, db, g_acc, B, 0u, (u32)Q, 0u, tiles, StageAXOut{});
+        hipLaunchKernelGGL((stage_a_mad_batch_kernel<BPT, Q, DEPTH>), grid, dim3(TPB), 0, 0, g_dc, N, L, K, Bl, E, qs, db, g_acc, B, 0u, (u32)Q, 0u, tiles, StageAXOut{});
         CK(hipEventRecord(e1, 0));
         CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
@@ -38,6 +40,33 @@ static void run(bool same_idx, u32 Bl = B)   // Bl: bin layers of this launch (<
     const double bytes = 8.0 * L * N * ((double)K * Bl * E + Q * ((double)K * E * 2 + 2 + (double)Bl * K * 2));
     printf("layers=%u Q=%d BPT=%d depth=%d %s: %7.1f us per launch, %6.1f us per query, compulsory %.0f MiB -> %.2f TB/s\n", Bl, Q, BPT, DEPTH,
            same_idx ? "same idx    " : "distinct idx", avg, avg / Q, bytes / 1048576.0, bytes / avg / 1e6);
+}
+// the resident kernel over Bl layers in partitions of lpp
+template <int E_>
+static void run_resident(u32 Bl, u32 lpp)
+{
+    StageAQueries qs = {};
+    for (int q = 0; q < 3; q++) qs.idx[q] = g_idx[q], qs.minus[q] = g_minus;
+    const u32 nx = N / TPB, tiles = nx * L * K;
+    const dim3 grid = stage_a_grid(nx, L, K, (Bl + lpp - 1) / lpp);
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    float sum = 0;
+    const int NREP = 13;
+    for (int rep = 0; rep < NREP; rep++) {
+        const u64 *db = g_db + (size_t)(rep % NBUF) * DBW;
+        CK(hipEventRecord(e0, 0));
+        hipLaunchKernelGGL((stage_a_resident_kernel<3, E_, stage_a_resident_ring(E_)>), grid, dim3(TPB), 0, 0, g_dc, N, L, K, Bl, lpp, qs, db, g_acc, B, 0u, 3u, 0u, tiles, StageAXOut{});
+        CK(hipEventRecord(e1, 0));
+        CK(hipEventSynchronize(e1));
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+        if (rep) sum += ms;
+    }
+    CK(hipGetLastError());
+    const float avg = sum / (NREP - 1) * 1e3f;
+    const double bytes = 8.0 * L * N * ((double)K * Bl * E + 3 * ((double)K * E * 2 + 2 + (double)Bl * K * 2));
+    printf("N=%u L=%u layers=%u Q=3 resident E=%d ring=%d, %u layers per partition: %7.1f us per launch, %6.1f us per query, compulsory %.0f MiB -> %.2f TB/s\n",
+           N, L, Bl, E_, stage_a_resident_ring(E_), lpp, avg, avg / 3, bytes / 1048576.0, bytes / avg / 1e6);
 }
 int main()
 {
@@ -68,5 +97,17 @@ int main()
         run<4, 2, 3>(s, 12);
         run<2, 4, 2>(s);          // four queries (shipped)
     }
+    // the resident kernel against the tiling it would replace, per launch shape of C3 (14 layers on one queue, 8 + 6 on two)
+    // and of smaller shares of the layers (a rank's of several GPUs): 5 and 4 are the smallest launches above one tiled group
+    for (u32 bl : {14u, 8u, 6u, 5u, 4u}) {
+        if (bl == 4) run<2, 3, 3>(false, bl);   // (the tiling stage_a_layers picks for four layers)
+        else run<3, 3, 2>(false, bl);
+        run_resident<14>(bl, bl);
+        run_resident<14>(bl, (bl + 1) / 2);
+    }
+    // C2's ring and term count (49 152 threads: under one wave per SIMD unless the layers are partitioned)
+    N = 8192, L = 3, B = 12, E = 12;
+    run<3, 3, 2>(false, 12);
+    for (u32 lpp : {12u, 6u, 4u}) run_resident<12>(12, lpp);
     return 0;
 }
