@@ -1,0 +1,305 @@
+"""Crafted COEFFICIENT-form columns for the base conversions and the digit lifts (plain module, imported by the test files; not a
+conftest).
+
+A column is the tuple of residues of one coefficient: L of them over Q, or M = 2L + 1 over QP.  The HPS base conversions and the BV
+digit lift work on such columns, and they branch and round at places that uniform residues reach with negligible probability:
+
+  digit extremes  the CRT digits y_i = x_i (Q/q_i)^-1 mod q_i at 0, q_i - 1, (q_i - 1)/2 and one-hot: the largest dot products, quotients
+                  and rounding counts the conversion kernels can meet
+  ties            the exact pre-rounding value sits k units of 2^-60 from a half-integer (the kernels round a sum of truncated 60-bit
+                  fractions, (fsum + 2^59) >> 60)
+  lift windows    residue limb i at q_j - 1, q_j, q_j + 1, q_i - 1, (q_i +- 1)/2, q_i mod q_j: where the lift of a residue mod q_i into
+                  q_j subtracts, wraps and changes sign
+
+Everything here is exact integer arithmetic (oracle/exact.py); `o` is an oracle context (oracle.binding.Oracle).
+"""
+from fractions import Fraction
+
+import numpy as np
+
+from oracle import exact as ex
+
+TIE_KS = (0, 1, -1, 2, -2, 3, -3, 4, -4)   # ... and +-L, +-(2L + 2), +-64, +-2^10: tie_ks(L)
+
+
+def tie_ks(L):
+    """the distances, in units of 2^-60, at which the tie families place a column"""
+    ks = list(TIE_KS)
+    for k in (L, 2 * L + 2, 64, 1 << 10):
+        for s in (k, -k):
+            if s not in ks:
+                ks.append(s)
+    return ks
+
+
+def moduli(o):
+    return [int(v) for v in o.q], [int(v) for v in o.p]
+
+
+class Families(dict):
+    """family name -> list of columns, all over `moduli`"""
+
+    def __init__(self, mods, *args, **kw):
+        super().__init__(*args, **kw)
+        self.moduli = tuple(int(m) for m in mods)
+
+    def count(self):
+        return sum(len(v) for v in self.values())
+
+
+def reduce_col(x, mods):
+    return tuple(int(x % m) for m in mods)
+
+
+# ---- digit extremes ------------------------------------------------------------------------------------------------------------
+def digit_sets(mods):
+    """the CRT digit vectors y: all m_i - 1, all 0, one-hot m_i - 1 for every i, all (m_i - 1)/2"""
+    n = len(mods)
+    ys = [tuple(m - 1 for m in mods), tuple(0 for _ in mods)]
+    ys += [tuple(mods[i] - 1 if j == i else 0 for j in range(n)) for i in range(n)]
+    ys.append(tuple((m - 1) // 2 for m in mods))
+    return ys
+
+
+def digit_extremes(mods):
+    """columns x with x_i = y_i (Mod/m_i) mod m_i, so that x_i (Mod/m_i)^-1 mod m_i = y_i, for the y of digit_sets"""
+    Mod = ex.prod(mods)
+    return [tuple(y * ((Mod // m) % m) % m for y, m in zip(ys, mods)) for ys in digit_sets(mods)]
+
+
+def digits_of(col, mods):
+    """the CRT digits of a column: y_i = x_i (Mod/m_i)^-1 mod m_i"""
+    Mod = ex.prod(mods)
+    return tuple(int(x) * pow((Mod // m) % m, -1, m) % m for x, m in zip(col, mods))
+
+
+# ---- ties ----------------------------------------------------------------------------------------------------------------------
+def tie_distance(num, den):
+    """distance of num/den from the nearest half-integer, in units of 2^-60 (a Fraction)"""
+    f = Fraction(num % den, den)
+    return abs(f - Fraction(1, 2)) * (1 << 60)
+
+
+def tie_unit(M):
+    """2^-60 of M in integers: the step between neighbouring tie columns (one, where M itself is below 2^60: a chain of one limb)"""
+    return max(1, M >> 60)
+
+
+def ties_expand(o):
+    """{label: x in [0, Q)}: x/Q is k units from 1/2 -- the rounding of the centred lift out of Q (expand) and, through
+    round(P x/Q)/P, of the lift out of P (second rounding of scale_pq).  Labels: the integer k, or 'floor', 'floor+1', 'x=0', 'x=1', 'x=-1'"""
+    qs, _ = moduli(o)
+    Q = ex.prod(qs)
+    u = tie_unit(Q)
+    out = {"floor": Q // 2, "floor+1": Q // 2 + 1, "x=0": 0, "x=1": 1, "x=-1": Q - 1}
+    for k in tie_ks(len(qs)):
+        out[k] = (Q // 2 + k * u) % Q
+    return out
+
+
+def ties_scale_first(o):
+    """{label: x}: P x mod Q is k units (of Q 2^-60) from Q/2 -- the first rounding of scale_pq, round(P x/Q)"""
+    qs, ps = moduli(o)
+    Q, P = ex.prod(qs), ex.prod(ps)
+    u = tie_unit(Q)
+    Pinv = pow(P % Q, -1, Q)
+    out = {"floor": (Q - 1) // 2 * Pinv % Q, "floor+1": (Q + 1) // 2 * Pinv % Q}
+    for k in tie_ks(len(qs)):
+        out[k] = ((Q - 1) // 2 + k * u) * Pinv % Q
+    return out
+
+
+def ties_scale_round(o, rng):
+    """{label: d in [0, QP)}: t d mod P is k units (of P 2^-60) from P/2 -- the rounding of round(t d/P); d = x + r P with r uniform"""
+    qs, ps = moduli(o)
+    Q, P = ex.prod(qs), ex.prod(ps)
+    u = tie_unit(P)
+    tinv = pow(o.t % P, -1, P)
+
+    def lift(x):
+        r = int.from_bytes(rng.bytes((Q.bit_length() + 7) // 8 + 8), "little") % Q
+        return x + r * P
+    out = {"floor": lift((P - 1) // 2 * tinv % P), "floor+1": lift((P + 1) // 2 * tinv % P), "x=0": 0, "x=1": 1, "x=-1": Q * P - 1}
+    for k in tie_ks(len(qs)):
+        out[k] = lift(((P - 1) // 2 + k * u) * tinv % P)
+    return out
+
+
+# ---- lift windows --------------------------------------------------------------------------------------------------------------
+def window_values(qs, i):
+    """values of residue limb i that sit at the edges of its lifts into the other moduli"""
+    qi = qs[i]
+    vals = [qi - 1, (qi - 1) // 2, (qi + 1) // 2, 0, 1]
+    for j, qj in enumerate(qs):
+        if j == i or qj >= qi:
+            continue
+        vals += [qj - 1, qj, qj + 1, qi % qj]
+        if qi >= 2 * qj:   # the Barrett branch of the lift: multiples of q_j below q_i
+            for m in (1, 2, qi // qj):
+                vals += [m * qj - 1, m * qj, m * qj + 1]
+    out = []
+    for v in vals:
+        if 0 <= v < qi and v not in out:
+            out.append(v)
+    return out
+
+
+def lift_windows(qs):
+    """columns whose limb i cycles through window_values(qs, i): every column carries a window value in every limb"""
+    per = [window_values(qs, i) for i in range(len(qs))]
+    n = max(len(v) for v in per)
+    return [tuple(per[i][(c + i) % len(per[i])] for i in range(len(qs))) for c in range(n)]
+
+
+def lift_definition(v, qi, qj):
+    """the BV digit of residue v mod q_i in limb j: centred(v, q_i) mod q_j"""
+    return ex.centered(v, qi) % qj
+
+
+# ---- families ------------------------------------------------------------------------------------------------------------------
+def q_families(o):
+    """all families over Q (inputs of expand and scale_pq, and residue columns for the digit lifts)"""
+    qs, _ = moduli(o)
+    f = Families(qs)
+    f["digits"] = digit_extremes(qs)
+    f["ties_expand"] = [reduce_col(x, qs) for x in ties_expand(o).values()]
+    f["ties_scale_first"] = [reduce_col(x, qs) for x in ties_scale_first(o).values()]
+    f["windows"] = lift_windows(qs)
+    return f
+
+
+def qp_families(o, rng):
+    """all families over QP (inputs of scale-and-round)"""
+    qs, ps = moduli(o)
+    mods = qs + ps
+    f = Families(mods)
+    f["digits"] = digit_extremes(mods)
+    f["ties_scale_round"] = [reduce_col(x, mods) for x in ties_scale_round(o, rng).values()]
+    return f
+
+
+def window_families(o):
+    qs, _ = moduli(o)
+    f = Families(qs)
+    f["windows"] = lift_windows(qs)
+    f["digits"] = digit_extremes(qs)
+    return f
+
+
+# ---- placing columns in a polynomial ---------------------------------------------------------------------------------------------
+def tile_map(fam, N):
+    """{coefficient index: (family, column)}: the columns, families interleaved, at n = 0, 1, 2, .. and again -- from another family --
+    at N/2 + n, so that the two members (n, n + N/2) of a folded pair hold different families; the last two coefficients of each
+    half (N/2 - 2, N/2 - 1, N - 2, N - 1) are crafted as well"""
+    lists = [[(name, c) for c in cols] for name, cols in fam.items() if cols]
+    entries = []
+    for r in range(max(len(v) for v in lists)):
+        entries += [v[r] for v in lists if r < len(v)]
+    C, h = len(entries), N // 2
+    if C + 2 > h:
+        raise ValueError("%d columns do not fit a half of %d coefficients" % (C, h))
+    out = {}
+    for n in list(range(C)) + [h - 2, h - 1]:
+        e = n if n < C else n - (h - 2)
+        out[n] = entries[e]
+        s = 1
+        while s < C and entries[(e + s) % C][0] == entries[e][0]:
+            s += 1
+        out[n + h] = entries[(e + s) % C]
+    return out
+
+
+def uniform_poly(mods, N, rng):
+    return np.stack([rng.integers(0, m, N, dtype=np.uint64) for m in mods])
+
+
+def tile(fam, N, rng):
+    """polynomial [len(moduli)][N]: the columns of `fam` where tile_map puts them, uniform residues elsewhere"""
+    poly = uniform_poly(fam.moduli, N, rng)
+    for n, (_, col) in tile_map(fam, N).items():
+        poly[:, n] = np.array(col, dtype=np.uint64)
+    return poly
+
+
+def columns_poly(cols, mods, N):
+    """polynomial [len(mods)][N] with the columns at n = 0, 1, .. and zeros behind them (len(cols) <= N)"""
+    poly = np.zeros((len(mods), N), dtype=np.uint64)
+    for n, col in enumerate(cols):
+        poly[:, n] = np.array(col, dtype=np.uint64)
+    return poly
+
+
+def cols_of(arr):
+    return [tuple(int(v) for v in arr[:, n]) for n in range(arr.shape[1])]
+
+
+def sigma(poly, g, mods):
+    """a(X) -> a(X^g) mod X^N + 1, limb by limb, for poly [len(mods)][N]"""
+    N = poly.shape[1]
+    k = np.arange(N, dtype=np.int64) * int(g) % (2 * N)
+    dst, neg = k % N, k >= N
+    out = np.empty_like(poly)
+    for l, m in enumerate(mods):
+        v = poly[l]
+        out[l, dst] = np.where(neg & (v != 0), np.uint64(m) - v, v)
+    return out
+
+
+def ntt_q(o, poly):
+    return np.stack([o.ntt(i, poly[i]) for i in range(poly.shape[0])])
+
+
+def intt_q(o, poly):
+    return np.stack([o.intt(i, poly[i]) for i in range(poly.shape[0])])
+
+
+# ---- steering d2 of a product --------------------------------------------------------------------------------------------------
+def d2_constant(o):
+    """c = floor(Q/t): with a1 the constant polynomial c, d2 = a1 (x) b1 is coefficient-wise in b1"""
+    qs, _ = moduli(o)
+    return ex.prod(qs) // o.t
+
+
+def exact_d2(o, b):
+    """coefficient of d2 = round(t c round(P b/Q) / P) mod Q for the centred coefficient b of b1 and a1 = c"""
+    qs, ps = moduli(o)
+    Q, P = ex.prod(qs), ex.prod(ps)
+    return ex.rnd_div(o.t * d2_constant(o) * ex.rnd_div(P * b, Q), P) % Q
+
+
+def solve_d2(o, targets, reach=8):
+    """for every target column (L residues) a centred coefficient b with exact_d2(o, b) = CRT(target), or None where the search over
+    round(D Q/(t c)) +- reach finds none"""
+    qs, _ = moduli(o)
+    Q = ex.prod(qs)
+    tc = o.t * d2_constant(o)
+    out = []
+    for col in targets:
+        D = ex.crt(col, qs)
+        b0 = ex.rnd_div(ex.centered(D, Q) * Q, tc)
+        hit = None
+        for d in sorted(range(-reach, reach + 1), key=abs):
+            b = b0 + d
+            if 2 * abs(b) < Q and exact_d2(o, b) == D:
+                hit = b
+                break
+        out.append(hit)
+    return out
+
+
+def d2_operands(o, targets, rng):
+    """EVALUATION ciphertexts (a, b), each [2][L][N], whose tensor product has the target columns as coefficients 0, 1, .. of d2,
+    cycled over all N coefficients: a1 = c, b1 from solve_d2, a0 and b0 uniform"""
+    qs, _ = moduli(o)
+    N = o.N
+    bs = solve_d2(o, targets)
+    assert None not in bs, "solve_d2 missed %d of %d targets" % (bs.count(None), len(bs))
+    c = d2_constant(o)
+    a1 = np.zeros((len(qs), N), dtype=np.uint64)
+    b1 = np.zeros((len(qs), N), dtype=np.uint64)
+    for i, q in enumerate(qs):
+        a1[i, 0] = c % q
+        b1[i] = np.array([bs[n % len(bs)] % q for n in range(N)], dtype=np.uint64)
+    a = np.stack([ntt_q(o, uniform_poly(qs, N, rng)), ntt_q(o, a1)])
+    b = np.stack([ntt_q(o, uniform_poly(qs, N, rng)), ntt_q(o, b1)])
+    return a, b

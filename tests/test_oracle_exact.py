@@ -106,7 +106,7 @@ def test_base_conversions_exact(ob, N, L, t, chain):
     # force edge columns: 0, Q-1 (= -1), 1, and values a safe 2^-40 away from the +-Q/2 wrap.
     # (Inputs within ~2^-57 (relative) of a rounding tie are the documented domain where the
     # 60-bit fixed-point rounding term may differ from exact rounding -- as OpenFHE's float
-    # formulation does; they are not generated here.)
+    # formulation does; tests/test_coeff_columns.py generates them and bounds the difference.)
     Q = ex.prod(qs)
     for n, val in enumerate([0, Q - 1, Q // 2 - (Q >> 40), Q // 2 + (Q >> 40), 1]):
         for i, q in enumerate(qs):
