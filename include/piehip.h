@@ -46,7 +46,9 @@ typedef struct piehip_ctx *piehip_handle;
  * its meaning (piehip_profile_read keeps writing the twelve kernel classes of version 100).  102 adds the seeded ciphertexts
  * ("Seeded ciphertexts" below); nothing of 101 changed.  The result limbs ("Result limbs" below: piehip_mod_reduce, piehip_set / get_result_limbs,
  * three more kernel classes, PIEHIP_NKERNELS 14 -> 17) were added without a new number: look the symbols up; nothing of 102 changed
- * (piehip_profile_read_n writes min(n, PIEHIP_NKERNELS) entries, so a caller built with 14 keeps its 14). */
+ * (piehip_profile_read_n writes min(n, PIEHIP_NKERNELS) entries, so a caller built with 14 keeps its 14).  The result relinearisation
+ * ("Result relinearisation" below: piehip_set / get_result_relin, piehip_get_result_components, piehip_client_decrypt_deg2, one more
+ * kernel class, PIEHIP_NKERNELS 17 -> 18) likewise: no new number, nothing of 102 changed. */
 int piehip_version(void);
 const char *piehip_last_error(void);
 
@@ -381,6 +383,53 @@ int piehip_mod_reduce(piehip_handle h, const uint64_t *in /*[nct][2][L][N]*/, ui
 int piehip_set_result_limbs(piehip_handle h, uint32_t keep);
 int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
 
+/* ---- result relinearisation: run() without the last key switch -------------------------------------------------------------------
+ * run() ends every bin layer with EvalMult(ct, ct) and the mask multiply (BatchedFHEHIPPIE.cpp:123,126), and the result is only ever
+ * decrypted.  A three-component ciphertext (d0, d1, d2) decrypts as d0 + d1 s + d2 s^2, so the relinearisation of that last product
+ * does nothing for the client: the reference pays for it because OpenFHE's EvalMult relinearises by default.  Leaving it out saves the
+ * key switch of the last product (the L^2 digit transforms, the digit array, the key-switch MAC and every key word it reads), and a
+ * database with K = 2 inner hash functions then needs no EvalMult key at all.  The price is a third component in every result row.
+ *   piehip_set_result_relin  on = 1 (the default): no launch, buffer, byte or refusal differs.  on = 0 with a database of K >= 2: the
+ *                            product chain relinearises the products h = 1 .. K - 2 as before, the LAST product (h = K - 1) is left as
+ *                            its three-component tensor result and the mask multiplies all three components.  A result row is
+ *                            [3][keep][N]: components d0, d1, d2, EVALUATION format, standard order, canonical residues, and
+ *                            everything that hands results out uses rows of 3 keep N words: piehip_run, piehip_run_into
+ *                            (d_results[b][nq][3][keep][N]), piehip_get_results, piehip_results_device (the buffer may move when
+ *                            the setting changes: ask again), piehip_copy_results_device, piehip_run_staged,
+ *                            piehip_run_host(_async / _wait / _seeded*) and the page-locked result array of
+ *                            piehip_host_buffers(_q), which is sized by the setting at the time of the call (ask again after
+ *                            changing it).  K = 1: there is no product, the setting has no effect, rows keep two components.
+ *                            Per handle: a query slot (piehip_attach_database) has its own setting.
+ *   piehip_get_result_relin  the setting.
+ *   piehip_get_result_components  2 or 3: the components of a result row as the handle stands (setting and loaded K).
+ * The exact bits.  Component c of row (beta, q) is mask_beta (.) T[c], where T = (x0 y0, x0 y1 + x1 y0, x1 y1) scaled by t/Q and rounded
+ * -- the tensor result piehip_eval_mult(relin = 0) returns -- of X, the chain's value in front of the last product (the h = 0
+ * accumulator at K = 2, the relinearised product of the earlier accumulators at K >= 3), and Y, the last accumulator.  Integer
+ * arithmetic only: every schedule and route gives the same bits.
+ * Keys.  With on = 0 and K = 2, piehip_run* needs NO EvalMult key (loading one is harmless).  K >= 3 needs keys as before, and
+ * per-query keys (piehip_load_relin_key_q) work as before.
+ * Result limbs.  The setting composes with piehip_set_result_limbs: the limb drop runs over rows * 3 polynomials; its definition is
+ * per polynomial and unchanged.  Noise: a drop rounds every coefficient of component c by e_c, |e_c| <= 1/2, and the decryption
+ * sees e_0 + e_1 s + e_2 s^2.  The first two terms are the two-component drop's, at most (1 + N) / 2 for a ternary s.  The third is at
+ * most ||s^2||_1 / 2, and ||s^2||_1 can reach N^2: in the worst case over all ternary s a drop adds t (1 + N + N^2) / (2 q_0) to the
+ * invariant noise, which at C3's parameters (N = 2^14, 33-bit t, q_0 ~ 2^60) is no bound at all.  For the uniform ternary s the client
+ * draws, a coefficient of s^2 is a sum of N products of variance 4/9, a coefficient of e_2 s^2 a sum of N independent terms of
+ * variance (1/12)(4/9) N each: standard deviation N / sqrt(27), and |e_2 s^2| <= 6 N / sqrt(27) < 1.2 N in every coefficient except
+ * with probability below 2^-27 N.  With that probability a drop adds at most t (1 + N + 2.4 N) / (2 q_0): a high-probability bound,
+ * not a worst-case one (INTEGRATION.md section 5 has the measured budgets).
+ * PIEHIP_ESTATE: on = 0 on a handle with piehip_set_graph(1), and piehip_set_graph(1) on a handle with on = 0 (the captured graph
+ * stays the reference's run()); on = 0 on a query-sliced handle (piehip_load_db*_sliced), and a sliced load on a handle with on = 0.
+ * piehip_gather_results(_host) REFUSES (PIEHIP_ESTATE) a handle with on = 0, for the reason it refuses keep < L.  piehip_fhepie_*
+ * ignores the setting.
+ *   piehip_client_decrypt_deg2  Decrypt + GetPackedValue of three-component rows ct[nct][3][L][N] -> slots[nct][B] (centred):
+ *                            c0 + c1 s + c2 s^2 on the handle's chain (rows reduced to keep < L limbs decrypt on a context of the
+ *                            chain q[:keep] with the first keep limbs of the key, as two-component ones do). */
+int piehip_set_result_relin(piehip_handle h, int on);
+int piehip_get_result_relin(piehip_handle h, int *on);
+int piehip_get_result_components(piehip_handle h, uint32_t *ncomp);
+int piehip_client_decrypt_deg2(piehip_handle h, const uint64_t *sk, const uint64_t *ct /*[nct][3][L][N]*/, uint32_t nct, uint32_t B,
+                               int64_t *slots);
+
 /* ---- query slices: stage A sharded by inner hash function and limb --------------------------------------
  * The reference evaluates, per bin layer, K inner products over E index ciphertexts (BatchedFHEHIPPIE.cpp:96-116) and then multiplies
  * the K accumulators together (.cpp:117-126).  Every RNS limb of an inner product depends on that limb of its operands only, so the
@@ -591,7 +640,7 @@ int piehip_client_relin_keygen_seeded(piehip_handle h, const uint64_t *sk, uint6
  * With profiling on, run() brackets every kernel launch with HIP events on the handle's stream.
  * piehip_profile_read returns, per kernel class, the launch count, total milliseconds, and the
  * algorithmic bytes (SURVEY.md 8d formulas) of the last run. */
-#define PIEHIP_NKERNELS 17
+#define PIEHIP_NKERNELS 18
 enum {
     PIEHIP_K_STAGE_A = 0,   /* fused ct x pt multiply-accumulate + minus add  (A3+A4)          */
     PIEHIP_K_NTT_FWD = 1,   /* forward negacyclic NTT                          (A1)             */
@@ -611,6 +660,8 @@ enum {
                                   * A class of its own: it does a product's arithmetic, so it is not a transform for a roofline */
     PIEHIP_K_RESULT_NTT_INV = 14,/* result limbs: inverse transform of the result rows, standard order in and out (bytes 16 N per limb) */
     PIEHIP_K_LIMB_DROP = 15,     /* result limbs: the coefficient-wise limb-drop kernel (bytes: 8 N (L + keep) per polynomial)       */
+    PIEHIP_K_DEG2_FINISH = 17,   /* result relinearisation off: own-limb terms + mask multiply of the last product's three components
+                                  * (bytes: 8 N per limb: 3 in, 4 operands, 1 mask, 3 out) */
     PIEHIP_K_RESULT_NTT_FWD = 16 /* result limbs: forward transform of the kept limbs.  Classes of their own: the reduction's cost is
                                   * read off these three, and the transforms of the multiplication chain keep their roofline class   */
 };

@@ -12,7 +12,7 @@ u32p = C.POINTER(C.c_uint32)
 i32p = C.POINTER(C.c_int32)
 f64p = C.POINTER(C.c_double)
 
-NKERNELS = 17
+NKERNELS = 18
 
 # every symbol include/piehip.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -123,6 +123,10 @@ SYMBOLS = {
     "piehip_mod_reduce": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_uint32, u64p]),
     "piehip_set_result_limbs": (C.c_int, [C.c_void_p, C.c_uint32]),
     "piehip_get_result_limbs": (C.c_int, [C.c_void_p, u32p]),
+    "piehip_set_result_relin": (C.c_int, [C.c_void_p, C.c_int]),
+    "piehip_get_result_relin": (C.c_int, [C.c_void_p, i32p]),
+    "piehip_get_result_components": (C.c_int, [C.c_void_p, u32p]),
+    "piehip_client_decrypt_deg2": (C.c_int, [C.c_void_p, u64p, u64p, C.c_uint32, C.c_uint32, i64p]),
     "piehip_query_slice": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, u32p, u32p]),
     "piehip_load_db_table_sliced": (C.c_int, [C.c_void_p, u64p] + [C.c_uint32] * 5 + [C.c_uint64] * 2 + [C.c_uint32] * 4),
     "piehip_load_db_sliced": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [u64p, C.c_uint32, C.c_uint32, u64p]),

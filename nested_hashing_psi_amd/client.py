@@ -179,21 +179,23 @@ class BatchedFHEPSIClient:
 
     def decrypt(self, cts, nslots=None, limbs=None):
         """cts [n][2][L][N] -> slots [n][nslots].  limbs = keep < L: cts [n][2][keep][N] as a server with setResultLimbs(keep)
-        returns them, decrypted in the reduced context with the first `keep` limbs of the secret key."""
+        returns them, decrypted in the reduced context with the first `keep` limbs of the secret key.  Three-component rows
+        [n][3][..][N] (a server with setResultRelin(False)) are recognised by their shape and decrypt as c0 + c1 s + c2 s^2."""
         cc = self.cc
         a, ap = _u64(cts)
         limbs = cc.L if limbs is None else int(limbs)
         if not 1 <= limbs <= cc.L:
             raise ValueError("limbs must be between 1 and L")
-        if a.ndim != 4 or a.shape[1:] != (2, limbs, cc.N):
-            raise ValueError("ciphertexts must be [n][2][%d][N]" % limbs)
+        if a.ndim != 4 or a.shape[1] not in (2, 3) or a.shape[2:] != (limbs, cc.N):
+            raise ValueError("ciphertexts must be [n][2][%d][N] (or [n][3][%d][N]: not relinearised)" % (limbs, limbs))
         n = a.shape[0]
         nslots = nslots or self.B
         out = _out((n, nslots), np.int64)
         h, sk = cc._h, self.sk
         if limbs < cc.L:
             h, sk = self._reduced_context(limbs)._h, np.ascontiguousarray(self.sk[:limbs])
-        _check(lib().piehip_client_decrypt(h, sk.ctypes.data_as(u64p), ap, n, nslots, out.ctypes.data_as(i64p)))
+        dec = lib().piehip_client_decrypt_deg2 if a.shape[1] == 3 else lib().piehip_client_decrypt
+        _check(dec(h, sk.ctypes.data_as(u64p), ap, n, nslots, out.ctypes.data_as(i64p)))
         return out
 
     # -- online (BatchedFHEPSIClient.cpp:176-192): zero slot in any of the b results <=> item in the intersection

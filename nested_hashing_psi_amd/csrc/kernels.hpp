@@ -60,6 +60,8 @@ struct NttPlan {
     bool fused_tensor = false;     // launch_ntt16_tensor instead of launch_tensor + inverse transform
     bool d01_eval_q = false;       // relinearising product: the Q limbs of d0, d1 stay in EVALUATION form -- not inverse-
                                    // transformed, not seen by scale-and-round; the key-switch MAC forms c_k (a (x) b)_k from the QP operands
+    bool result_eval_q = false;    // a product that is NOT relinearised (the last one of a run() with piehip_set_result_relin(0)): no Q limb of
+                                   // d0, d1, d2 is inverse-transformed; launch_deg2_finish forms the three own-limb terms from the QP operands
     bool digits_with_d01 = false;  // the key-switch digits join the forward launch of d0, d1 (Ntt16Digits)
     bool digit_lift_lane = false;  // launch_ntt_digits instead of launch_digits + transform: lane-ordered key switches,
     bool digit_lift_std = false;   // ... standard-order key switches (FHEHIPPIE, piehip_eval_automorph)
@@ -130,7 +132,12 @@ void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mo
 #ifndef PIEHIP_D01_EVAL_Q
 #define PIEHIP_D01_EVAL_Q 1
 #endif
-void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st, u32 eval_q_L = 0);
+// eval_q_d2 (pl.result_eval_q, with eval_q_L = L): the Q limbs of d2 are not produced either -- 3 (M - L) limbs per row.
+// -DPIEHIP_RESULT_EVAL_Q=0 clears that switch
+#ifndef PIEHIP_RESULT_EVAL_Q
+#define PIEHIP_RESULT_EVAL_Q 1
+#endif
+void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st, u32 eval_q_L = 0, bool eval_q_d2 = false);
 // pl.digit_lift_lane / digit_lift_std: forward transform of the BV digits with the digit lift in the 32-coefficient kernel's load
 // phase (no digits kernel): d2[nb][L][N] COEFFICIENT -> dig[nb][L(i)][L(j)][N] EVALUATION
 void launch_ntt_digits(const NttPlan &pl, const u64 *d2, u64 *dig, u32 nb, u32 L, bool sigma, hipStream_t st);
@@ -183,10 +190,13 @@ void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 
 // d[nb][3][M][N] (COEFFICIENT) -> components 0,1 to out01 + bin*stride01 + c*L*N, component 2 to out2 + bin*stride2
 // fold: the outermost NTT stage of the neighbouring transforms is applied here (see kernels_pie.hip, "Outer-stage
 // folding"); fold_comp2: component 2 also feeds a forward transform directly (3-component output)
+// p_only2 (pl.result_eval_q, with p_only01 and fold_comp2): component 2 likewise -- the product is not relinearised, launch_deg2_finish
+// adds all three terms
 // p_only01 (pl.d01_eval_q): components 0 and 1 are computed from their P limbs alone -- the Q limbs of d are not read and the own-limb
 // term d_k [t P^-1]_{q_k} is left out (the key-switch MAC adds its transform: launch_relin_mac, eqp)
 void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb, u64 *out01, size_t stride01, u64 *out2,
-                        size_t stride2, hipStream_t st, bool small_moduli, bool fold = false, bool fold_comp2 = false, bool p_only01 = false);
+                        size_t stride2, hipStream_t st, bool small_moduli, bool fold = false, bool fold_comp2 = false, bool p_only01 = false,
+                        bool p_only2 = false);
 // BV digits: d2c at d2 + bin*stride2 ([L][N], COEFFICIENT) -> dig[nb][L(i)][L(j)][N] (centred lift of residue i into q_j)
 void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stride2, u32 nb, u64 *dig, hipStream_t st,
                    bool fold = false);
@@ -201,6 +211,13 @@ void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stri
 void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t stride01, const u64 *dig, const u64 *key,
                       const u64 *mask, u64 *out, u32 nb, hipStream_t st, bool small_moduli, const u32 *out_map = nullptr, size_t key_stride = 0,
                       u32 key_group = 1, u32 sigma_T = 0, u32 sigma_kp = 16, u32 mask_div = 1, const u64 *eqp = nullptr, u32 eqp_M = 0);
+// Degree-2 results (pl.result_eval_q): out[row][c][j] = (d[row][c][j] + [t P^-1]_{q_j} (a (x) b)[c][j]) (.) mask[row / mask_div][j] for the
+// three components c of a product that is not relinearised.  d[nb][3][L][N] and mask are lane-ordered (sigma_T threads per slice,
+// sigma_kp pairs per thread: deg2_finish_applies says whether the kernel takes that order), d in [0, 8q); eqp as for launch_relin_mac;
+// out[nb][3][L][N] leaves in standard order, canonical
+bool deg2_finish_applies(u32 N, u32 sigma_T, u32 sigma_kp);
+void launch_deg2_finish(const DevConsts *dc, u32 N, u32 L, const u64 *d, const u64 *eqp, u32 eqp_M, const u64 *mask, u64 *out, u32 nb,
+                        hipStream_t st, u32 sigma_T, u32 sigma_kp, u32 mask_div = 1);
 // rotation-based PIE (FHEHIPPIE.cpp:61-77), see kernels_pie.hip
 void launch_bcast_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t xs, u32 group, const u64 *pt, size_t ps_outer,
                             size_t ps_inner, u64 *out, u32 nct, hipStream_t st);
@@ -212,9 +229,9 @@ void launch_sum_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, u32 g
 void launch_host_flag(u64 *flag_dev, u64 value, hipStream_t st);
 // element-wise helpers on nct ciphertexts [nct][2][L][N]
 void launch_ct_add(const DevConsts *dc, u32 N, u32 L, const u64 *x, const u64 *y, u64 *out, u32 nct, hipStream_t st);
-// (pt_div > 1: ciphertext i takes plaintext i / pt_div)
+// (pt_div > 1: ciphertext i takes plaintext i / pt_div; comps: components per ciphertext, 3 for a product that was not relinearised)
 void launch_ct_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, const u64 *pt, size_t pt_stride, u64 *out,
-                         u32 nct, hipStream_t st, u32 pt_div = 1);
+                         u32 nct, hipStream_t st, u32 pt_div = 1, u32 comps = 2);
 // limb drop of npoly polynomials in COEFFICIENT format: in[npoly][L][N] -> out[npoly][keep][N], the limbs L - 1 .. keep dropped one
 // after the other with centred rounding (include/piehip.h "Result limbs").  1 <= keep < L <= MAX_L; false (nothing launched) otherwise
 bool launch_limb_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, const u64 *in, u64 *out, u32 npoly, hipStream_t st);
@@ -268,7 +285,7 @@ void launch_enc_finish(const DevConsts *dc, u32 N, u32 L, const u64 *em, const u
                        hipStream_t st);
 void launch_ks_finish(const DevConsts *dc, u32 N, u32 L, const u64 *e, const u64 *sk, const u64 *s_from, u64 *ks, hipStream_t st);
 void launch_square(const DevConsts *dc, u32 N, u32 L, const u64 *s, u64 *s2, hipStream_t st);
-void launch_dec_dot(const DevConsts *dc, u32 N, u32 L, const u64 *ct, const u64 *sk, u64 *xs, u32 nct, hipStream_t st);
+void launch_dec_dot(const DevConsts *dc, u32 N, u32 L, const u64 *ct, const u64 *sk, u64 *xs, u32 nct, hipStream_t st, u32 ncomp = 2);
 void launch_dec_round(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *xs, u64 *coeff_t, u32 nct, hipStream_t st);
 void launch_decode_gather(const DevConsts *dc, u32 N, u32 M, const u64 *u, const u32 *slot_pos, u32 B, int64_t *slots, u32 nct,
                           hipStream_t st);

@@ -71,16 +71,19 @@ __global__ void __launch_bounds__(CTPB) square_kernel(const DevConsts *__restric
     s2[x] = mulmod(s[x], s[x], dc->mod[blockIdx.y]);
 }
 
-// x = c0 + c1 s (EVALUATION) for nct ciphertexts -> xs[ct][L][N]
+// x = c0 + c1 s (EVALUATION) for nct ciphertexts -> xs[ct][L][N]; ncomp = 3 (a product that was not relinearised): c0 + c1 s + c2 s^2
 __global__ void __launch_bounds__(CTPB) dec_dot_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, const u64 *__restrict__ ct,
-                                                       const u64 *__restrict__ sk, u64 *__restrict__ xs)
+                                                       const u64 *__restrict__ sk, u64 *__restrict__ xs, u32 ncomp)
 {
     const u32 n = blockIdx.x * CTPB + threadIdx.x;
     if (n >= N) return;
     const u32 l = blockIdx.y, c = blockIdx.z;
     const Mod m = dc->mod[l];
     const size_t LN = (size_t)L * N, x = (size_t)l * N + n;
-    xs[(size_t)c * LN + x] = addmod(ct[(size_t)c * 2 * LN + x], mulmod(ct[(size_t)c * 2 * LN + LN + x], sk[x], m), m.q);
+    const u64 *p = ct + (size_t)c * ncomp * LN + x;
+    u64 hi = p[LN];
+    if (ncomp == 3) hi = addmod(hi, mulmod(p[2 * LN], sk[x], m), m.q);  // Horner: c0 + s (c1 + s c2)
+    xs[(size_t)c * LN + x] = addmod(p[0], mulmod(hi, sk[x], m), m.q);
 }
 
 // COEFFICIENT x (mod Q) -> m = round(t x / Q) mod t   (HPS scale-and-round, 60-bit fixed-point rounding term)
@@ -135,9 +138,9 @@ void launch_square(const DevConsts *dc, u32 N, u32 L, const u64 *s, u64 *s2, hip
 {
     hipLaunchKernelGGL(square_kernel, dim3((N + CTPB - 1) / CTPB, L), dim3(CTPB), 0, st, dc, N, s, s2);
 }
-void launch_dec_dot(const DevConsts *dc, u32 N, u32 L, const u64 *ct, const u64 *sk, u64 *xs, u32 nct, hipStream_t st)
+void launch_dec_dot(const DevConsts *dc, u32 N, u32 L, const u64 *ct, const u64 *sk, u64 *xs, u32 nct, hipStream_t st, u32 ncomp)
 {
-    hipLaunchKernelGGL(dec_dot_kernel, dim3((N + CTPB - 1) / CTPB, L, nct), dim3(CTPB), 0, st, dc, N, L, ct, sk, xs);
+    hipLaunchKernelGGL(dec_dot_kernel, dim3((N + CTPB - 1) / CTPB, L, nct), dim3(CTPB), 0, st, dc, N, L, ct, sk, xs, ncomp);
 }
 void launch_dec_round(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *xs, u64 *coeff_t, u32 nct, hipStream_t st)
 {

@@ -164,6 +164,8 @@ void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli)
     pl.fused_tensor = PIEHIP_FUSE_TENSOR && k16 && small_moduli;
     // (the transform of the own-limb term is added where d01 and the QP operands have the same order: the lane order of one kernel)
     pl.d01_eval_q = PIEHIP_D01_EVAL_Q && pl.fused_tensor;
+    // (... and a product that is not relinearised leaves d2's Q limbs there as well: launch_deg2_finish writes its three components)
+    pl.result_eval_q = PIEHIP_RESULT_EVAL_Q && pl.fused_tensor && deg2_finish_applies(pl.N, pl.lane_T, pl.lane_kp);
     pl.digits_with_d01 = k16 && small_moduli;  // equal-width primes only: the kernel's lift is a conditional subtraction
     pl.x_direct = pl.xq_reuse && k16 && small_moduli;
     const NttRoute std_fwd = ntt_route(pl, false, false, false);  // the digit lift is in the 32-coefficient kernel, one slice per limb

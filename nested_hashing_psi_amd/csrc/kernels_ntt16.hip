@@ -102,9 +102,9 @@ void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mo
         launch_ntt16_t<13>(a, inverse, lift, pl.transform_cus(), st);
 }
 
-void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st, u32 eval_q_L)
+void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st, u32 eval_q_L, bool eval_q_d2)
 {
-    assert(pl.fused_tensor && (!eval_q_L || (pl.d01_eval_q && eval_q_L < M)));
+    assert(pl.fused_tensor && (!eval_q_L || ((eval_q_d2 ? pl.result_eval_q : pl.d01_eval_q) && eval_q_L < M)) && (!eval_q_d2 || eval_q_L));
     const bool folded = pl.fold;
     const u32 s0 = folded ? 1u : 0u;
     ntt16::Args a = {};
@@ -116,7 +116,7 @@ void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M,
     a.s0 = s0;
     a.tq_L = eval_q_L;
     a.tq_first = (nb * 3 * (M - eval_q_L)) << s0;
-    a.nitems = a.tq_first + ((nb * eval_q_L) << s0);  // 3 M - 2 eval_q_L limbs per row
+    a.nitems = a.tq_first + (eval_q_d2 ? 0u : (nb * eval_q_L) << s0);  // 3 M - 2 eval_q_L limbs per row; eval_q_d2: the P limbs' triples alone
     a.mod_base = 0;
     a.mod_count = M;
     a.flags = folded ? ntt16::F_FOLDED : 0;

@@ -907,7 +907,8 @@ __device__ __forceinline__ void scale_round_comp(const DevConsts *__restrict__ d
     }
 }
 // P01: components 0 and 1 are the PONLY variant (a uniform branch on the component: blockIdx.y), component 2 the full one
-template <bool FOLD, u32 L, bool MAD, bool P01 = false>
+// P2 (with P01 and fold_comp2; NttPlan::result_eval_q): component 2 is the PONLY variant too -- a product that is not relinearised
+template <bool FOLD, u32 L, bool MAD, bool P01 = false, bool P2 = false>
 __global__ void __launch_bounds__(TPB) scale_round_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ d,
                                                           u64 *__restrict__ out01, size_t stride01,
                                                           u64 *__restrict__ out2, size_t stride2, u32 fold_comp2)
@@ -923,19 +924,26 @@ __global__ void __launch_bounds__(TPB) scale_round_kernel(const DevConsts *__res
     const bool lz = FOLD && MAD && comp < 2 && !fold_comp2;
     if (P01 && comp < 2)
         scale_round_comp<FOLD, L, MAD, true>(dc, N, n, pin, pout, true, lz);
+    else if (P2 && comp == 2)
+        scale_round_comp<FOLD, L, MAD, true>(dc, N, n, pin, pout, fold_comp2, lz);
     else
         scale_round_comp<FOLD, L, MAD, false>(dc, N, n, pin, pout, comp < 2 || fold_comp2, lz);
 }
 void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb, u64 *out01, size_t stride01, u64 *out2,
-                        size_t stride2, hipStream_t st, bool small_moduli, bool fold, bool fold_comp2, bool p_only01)
+                        size_t stride2, hipStream_t st, bool small_moduli, bool fold, bool fold_comp2, bool p_only01, bool p_only2)
 {
-    assert(!p_only01 || (small_moduli && !fold_comp2));
+    assert(!p_only01 || (small_moduli && fold_comp2 == p_only2));
+    assert(!p_only2 || p_only01);
     dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, 3, nb);
+#define SRK2(F_, L_) \
+    hipLaunchKernelGGL((scale_round_kernel<F_, L_, true, true, true>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, F_ ? 1u : 0u)
 #define SRK(F_, L_, M_, P_) \
     hipLaunchKernelGGL((scale_round_kernel<F_, L_, M_, P_>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, (fold_comp2 && F_) ? 1u : 0u)
 #define SRL(L_)                                                                        \
     case L_:                                                                           \
-        if (p_only01) {                                                                \
+        if (p_only2) {                                                                 \
+            if (fold) SRK2(true, L_); else SRK2(false, L_);                            \
+        } else if (p_only01) {                                                                \
             if (fold) SRK(true, L_, true, true); else SRK(false, L_, true, true);      \
         } else if (small_moduli) {                                                     \
             if (fold) SRK(true, L_, true, false); else SRK(false, L_, true, false);    \
@@ -945,6 +953,7 @@ void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb,
         break;
     switch (L) { SRL(1) SRL(2) SRL(3) SRL(4) SRL(5) SRL(6) SRL(7) }
 #undef SRK
+#undef SRK2
 #undef SRL
 }
 
@@ -1207,6 +1216,83 @@ void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t 
 #undef RME
 }
 
+// ---------------------------------------------------------------------------------------------
+// Degree-2 results (include/piehip.h "Result relinearisation"; NttPlan::result_eval_q): the last product of run() is not relinearised.
+// Its three components arrive as relin_mac_kernel<.., EQ> takes d0 and d1: d[row][3][L][N], the forward transform (lane order, [0, 8q)
+// residues) of scale-and-round's P-limb part, without the own-limb term.  This kernel adds that term -- [t P^-1]_{q_j} times limb j of
+// (a0 b0, a0 b1 + a1 b0, a1 b1), formed from the QP operands e[row][4][eqp_M][N] exactly as there -- multiplies by the mask and writes
+// the result row out[row][3][L][N] in standard order through the LDS tile.  No digit, no key.  One thread: two adjacent coefficients
+// of one (row, limb j), all three components: the four operand words are loaded once for their four products.
+// Column 0 of a component's accumulator holds d (< 2^63) and v mod 2^30, column 1 v >> 30 < 2^32: one reduction block.
+template <int KP>
+__global__ void __launch_bounds__(TPB) deg2_finish_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, const u64 *__restrict__ d,
+                                                          const u64 *__restrict__ eqp, u32 eqp_M, const u64 *__restrict__ mask,
+                                                          u64 *__restrict__ out, u32 T, u32 mask_div)
+{
+    constexpr u32 TT = TPB / KP;  // threads of the transform per tile
+    __shared__ u64x2 s_tile[3][TPB];
+    const u32 tiles = T / TT, slice = blockIdx.x / tiles, tau0 = (blockIdx.x % tiles) * TT;
+    const u32 kk = threadIdx.x / TT, tt = threadIdx.x % TT;
+    const u32 n = 2 * (slice * KP * T + kk * T + tau0 + tt);
+    const u32 std_pair = slice * KP * T + KP * tau0;  // first standard-order pair of this block's tile
+    const u32 j = blockIdx.y, row = blockIdx.z;
+    const Mod m = dc->mod[j];
+    const size_t LN = (size_t)L * N, MN = (size_t)eqp_M * N;
+    const u64 nq = 0 - m.q, n2q = neg_u(2 * m.q), n4q = neg_u(4 * m.q);
+    const u64 tp = dc->tPinv_modq[j], tpsh = dc->tPinv_modq_sh[j];
+    const u64 *pe = eqp + (size_t)row * 4 * MN + (size_t)j * N + n;
+    const u64x2 va0 = *reinterpret_cast<const u64x2 *>(pe), va1 = *reinterpret_cast<const u64x2 *>(pe + MN),
+                vb0 = *reinterpret_cast<const u64x2 *>(pe + 2 * MN), vb1 = *reinterpret_cast<const u64x2 *>(pe + 3 * MN);
+    const u64x2 mk = *reinterpret_cast<const u64x2 *>(mask + (size_t)(row / mask_div) * LN + (size_t)j * N + n);
+    u64x2 s[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) s[c] = *reinterpret_cast<const u64x2 *>(d + ((size_t)row * 3 + c) * LN + (size_t)j * N + n);
+    u64 res[3][2];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        // operands below 2q (two sign-mask subtractions); d1's two products keep every column below 2^63, z < 8 q^2 < 2^123
+        const Split30 sa0 = split30(csub_u(csub_u(k ? va0.y : va0.x, n4q), n2q)), sa1 = split30(csub_u(csub_u(k ? va1.y : va1.x, n4q), n2q));
+        const Split30 sb0 = split30(csub_u(csub_u(k ? vb0.y : vb0.x, n4q), n2q)), sb1 = split30(csub_u(csub_u(k ? vb1.y : vb1.x, n4q), n2q));
+        const Split30 smk = split30(k ? mk.y : mk.x);
+        u64 v[3];
+        ColAcc t = {0, 0, 0};
+        colacc_mac(t, sa0, sb0);
+        v[0] = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+        t = ColAcc{0, 0, 0};
+        colacc_mac(t, sa0, sb1);
+        colacc_mac(t, sa1, sb0);
+        v[1] = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+        t = ColAcc{0, 0, 0};
+        colacc_mac(t, sa1, sb1);
+        v[2] = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            ColAcc a = {(k ? s[c].y : s[c].x) + (v[c] & 0x3FFFFFFFull), v[c] >> 30, 0};
+            ColAcc p = {0, 0, 0};
+            colacc_mac(p, split30(colacc_reduce<false>(a, m, nq)), smk);
+            res[c][k] = colacc_reduce<false>(p, m, nq);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) s_tile[c][KP * tt + kk] = u64x2{res[c][0], res[c][1]};  // standard offset inside the tile: KP (tau - tau0) + k
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+        *reinterpret_cast<u64x2 *>(out + ((size_t)row * 3 + c) * LN + (size_t)j * N + 2 * (std_pair + threadIdx.x)) = s_tile[c][threadIdx.x];
+}
+bool deg2_finish_applies(u32 N, u32 sigma_T, u32 sigma_kp)
+{
+    // (the 16-coefficient kernel's lane order: the only one a plan with result_eval_q has)
+    return sigma_kp == 8 && sigma_T >= TPB / sigma_kp && sigma_T % (TPB / sigma_kp) == 0 && (N / 2) % TPB == 0;
+}
+void launch_deg2_finish(const DevConsts *dc, u32 N, u32 L, const u64 *d, const u64 *eqp, u32 eqp_M, const u64 *mask, u64 *out, u32 nb,
+                        hipStream_t st, u32 sigma_T, u32 sigma_kp, u32 mask_div)
+{
+    assert(deg2_finish_applies(N, sigma_T, sigma_kp) && eqp_M >= L);
+    dim3 grid(N / 2 / TPB, L, nb);
+    hipLaunchKernelGGL(deg2_finish_kernel<8>, grid, dim3(TPB), 0, st, dc, N, L, d, eqp, eqp_M, mask, out, sigma_T, mask_div ? mask_div : 1);
+}
+
 // One word for the host: `value` lands in page-locked host memory when everything queued on the stream before it is done
 // (piehip_host.cpp: "the uploads of this query have left host memory" -- an event cannot say that once kernels are queued
 // behind the uploads: hipEventSynchronize on an earlier event waits for the stream's whole backlog).
@@ -1247,11 +1333,25 @@ __global__ void __launch_bounds__(TPB) ct_mul_plain_kernel(const DevConsts *dc, 
     const size_t o = ((size_t)blockIdx.z * 2 * L + blockIdx.y) * N + n;
     out[o] = mulmod(x[o], pt[(size_t)(blockIdx.z / pt_div) * pt_stride + (size_t)l * N + n], dc->mod[l]);
 }
-void launch_ct_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, const u64 *pt, size_t pt_stride, u64 *out,
-                         u32 nct, hipStream_t st, u32 pt_div)
+// ... of `comps` components per ciphertext (3: a product that was not relinearised)
+__global__ void __launch_bounds__(TPB) ctn_mul_plain_kernel(const DevConsts *dc, u32 N, u32 L, const u64 *__restrict__ x,
+                                                            const u64 *__restrict__ pt, size_t pt_stride,
+                                                            u64 *__restrict__ out, u32 pt_div, u32 comps)
 {
-    dim3 grid((N + TPB - 1) / TPB, 2 * L, nct);
-    hipLaunchKernelGGL(ct_mul_plain_kernel, grid, dim3(TPB), 0, st, dc, N, L, x, pt, pt_stride, out, pt_div ? pt_div : 1);
+    const u32 n = blockIdx.x * TPB + threadIdx.x;
+    if (n >= N) return;
+    const u32 l = blockIdx.y % L;
+    const size_t o = ((size_t)blockIdx.z * comps * L + blockIdx.y) * N + n;
+    out[o] = mulmod(x[o], pt[(size_t)(blockIdx.z / pt_div) * pt_stride + (size_t)l * N + n], dc->mod[l]);
+}
+void launch_ct_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, const u64 *pt, size_t pt_stride, u64 *out,
+                         u32 nct, hipStream_t st, u32 pt_div, u32 comps)
+{
+    dim3 grid((N + TPB - 1) / TPB, comps * L, nct);
+    if (comps == 2)
+        hipLaunchKernelGGL(ct_mul_plain_kernel, grid, dim3(TPB), 0, st, dc, N, L, x, pt, pt_stride, out, pt_div ? pt_div : 1);
+    else
+        hipLaunchKernelGGL(ctn_mul_plain_kernel, grid, dim3(TPB), 0, st, dc, N, L, x, pt, pt_stride, out, pt_div ? pt_div : 1, comps);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -10,7 +10,8 @@ using namespace piehip;
 static thread_local std::string g_err;
 static const char *KNAMES[PIEHIP_NKERNELS] = {"stage_a_mac", "ntt_fwd", "ntt_inv",  "expand",   "tensor",    "scale_round",
                                               "digits",      "relin",   "mask_mul", "encode",   "automorph", "other",
-                                              "event_pair",  "tensor_ntt_inv", "result_ntt_inv", "limb_drop", "result_ntt_fwd"};
+                                              "event_pair",  "tensor_ntt_inv", "result_ntt_inv", "limb_drop", "result_ntt_fwd",
+                                              "deg2_finish"};
 static void free_workspace(piehip_ctx *h);
 
 namespace piehip {
@@ -80,6 +81,7 @@ void ws_free(MulWs &w)
     dev_free(&w.d01);
     dev_free(&w.d2c);
     dev_free(&w.dig);
+    dev_free(&w.t3);
     w.nb = 0;
 }
 
@@ -117,10 +119,21 @@ int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus)
     return PIEHIP_OK;
 }
 
-int ensure_full_rows(piehip_ctx *h)
+int ensure_full_rows(piehip_ctx *h, u32 K)
 {
-    if (h->res_limbs >= h->hp.L || h->d_full || !h->ws_cap_rows) return PIEHIP_OK;
-    return dev_alloc(&h->d_full, h->ws_cap_rows * 2 * h->LN());
+    if (!h->ws_cap_rows) return PIEHIP_OK;
+    const u32 comps = h->res_comps(K);
+    int rc;
+    if (comps > h->res_cap_comps) {   // three-component rows from here on: the result rows grow, the reduction's rows with them
+        dev_free(&h->d_out);
+        dev_free(&h->d_full);
+        h->res_cap_comps = 0;
+        if ((rc = dev_alloc(&h->d_out, h->ws_cap_rows * comps * h->LN()))) return rc;
+        h->res_cap_comps = comps;
+    }
+    if (comps == 3 && !h->ws.t3 && (rc = dev_alloc(&h->ws.t3, h->ws_cap_rows * 3 * h->LN()))) return rc;
+    if (h->res_limbs >= h->hp.L || h->d_full) return PIEHIP_OK;
+    return dev_alloc(&h->d_full, h->ws_cap_rows * h->res_cap_comps * h->LN());
 }
 
 void use_owned_inputs(piehip_ctx *h)
@@ -418,6 +431,7 @@ static void free_workspace(piehip_ctx *h)
     dev_free(&h->d_full);
     ws_free(h->ws);
     h->ws_cap_rows = h->ws_cap_K = 0;
+    h->res_cap_comps = 0;
 }
 // Every array of the workspace is indexed by row first, so one sized for more rows serves fewer as it stands: a smaller batch
 // keeps the larger allocation (a server that alternates between batch sizes would otherwise free and allocate 0.6 GiB per change,
@@ -428,17 +442,19 @@ static int alloc_workspace(piehip_ctx *h, u32 K, u32 b)
     const size_t LN = h->LN(), rows = (size_t)b * h->nq;
     if (h->d_acc && h->d_out && h->ws.eqp && h->ws_cap_K == K && rows <= h->ws_cap_rows && (K <= 2 || h->d_prod)) {
         h->ws.nb = (u32)rows;
-        return ensure_full_rows(h);
+        return ensure_full_rows(h, K);
     }
     free_workspace(h);
     int rc;
     if ((rc = dev_alloc(&h->d_acc, rows * K * 2 * LN))) return rc;
-    if ((rc = dev_alloc(&h->d_out, rows * 2 * LN))) return rc;
+    const u32 comps = h->res_comps(K);
+    if ((rc = dev_alloc(&h->d_out, rows * comps * LN))) return rc;
     if (K > 2 && (rc = dev_alloc(&h->d_prod, rows * 2 * LN))) return rc;
     if ((rc = ws_alloc(h, h->ws, (u32)rows))) return rc;
     h->ws_cap_rows = rows;
     h->ws_cap_K = K;
-    return ensure_full_rows(h);
+    h->res_cap_comps = comps;
+    return ensure_full_rows(h, K);
 }
 
 extern "C++" int piehip::alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db)
@@ -512,7 +528,8 @@ int piehip_attach_database(piehip_handle h, piehip_handle owner)
         return fail(PIEHIP_ESTATE, "attach_database: other handles are attached to this handle's database (detach or destroy them first)");
     join_pending(owner);
     if (owner->db_borrowed) return fail(PIEHIP_EINVAL, "attach_database: the owner itself borrows its database");
-    if (!owner->d_db || (!owner->d_evk && owner->K > 1)) return fail(PIEHIP_ESTATE, "attach_database: the owner has no key or no database yet");
+    // (an owner that hands out unrelinearised results of a K = 2 database runs without a key: so may its slots, each by its own setting)
+    if (!owner->d_db || (!owner->d_evk && owner->K > 1 && !(owner->K == 2 && !owner->res_relin))) return fail(PIEHIP_ESTATE, "attach_database: the owner has no key or no database yet");
     if (owner->device != h->device) return fail(PIEHIP_EINVAL, "attach_database: handles on different devices");
     if (owner->hp.N != h->hp.N || owner->hp.L != h->hp.L || owner->hp.t != h->hp.t || owner->hp.moduli != h->hp.moduli)
         return fail(PIEHIP_EINVAL, "attach_database: handles with different parameters");
@@ -1019,7 +1036,7 @@ int piehip_set_result_limbs(piehip_handle h, uint32_t keep)
     HIPCHK(hipSetDevice(h->device));
     const u32 before = h->res_limbs;
     h->res_limbs = keep;
-    const int rc = ensure_full_rows(h);
+    const int rc = ensure_full_rows(h, h->K);
     if (rc) h->res_limbs = before;
     return rc;
 }
@@ -1028,6 +1045,36 @@ int piehip_get_result_limbs(piehip_handle h, uint32_t *keep)
     NEED_RO(h);
     if (!keep) return fail(PIEHIP_EINVAL, "null out");
     *keep = h->res_limbs;
+    return PIEHIP_OK;
+}
+
+// Result relinearisation (include/piehip.h): the setting of a handle.  Like the result limbs' rows, the larger result rows and the
+// last product's scratch are allocated here, outside the timed path, and stay with the workspace.
+int piehip_set_result_relin(piehip_handle h, int on)
+{
+    NEED(h);
+    if (!on && h->use_graph)
+        return fail(PIEHIP_ESTATE, "set_result_relin: a handle that replays a captured graph (piehip_set_graph) relinearises its results");
+    if (!on && h->slice.on) return fail(PIEHIP_ESTATE, "set_result_relin: a query-sliced handle relinearises its results");
+    HIPCHK(hipSetDevice(h->device));
+    const bool before = h->res_relin;
+    h->res_relin = on != 0;
+    const int rc = ensure_full_rows(h, h->K);
+    if (rc) h->res_relin = before;
+    return rc;
+}
+int piehip_get_result_relin(piehip_handle h, int *on)
+{
+    NEED_RO(h);
+    if (!on) return fail(PIEHIP_EINVAL, "null out");
+    *on = h->res_relin ? 1 : 0;
+    return PIEHIP_OK;
+}
+int piehip_get_result_components(piehip_handle h, uint32_t *ncomp)
+{
+    NEED_RO(h);
+    if (!ncomp) return fail(PIEHIP_EINVAL, "null out");
+    *ncomp = h->res_comps();
     return PIEHIP_OK;
 }
 

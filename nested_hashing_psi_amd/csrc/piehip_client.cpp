@@ -260,7 +260,8 @@ int piehip_client_encrypt_seeded(piehip_handle h, const uint64_t *sk, const int6
     return client_encrypt(h, sk, slots, nct, B, noise_seeds, a_seeds, c0);
 }
 
-int piehip_client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots)
+// ncomp components per ciphertext: 2, or 3 for rows of a product that was not relinearised (piehip_client_decrypt_deg2)
+static int client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots, u32 ncomp)
 {
     NEED(h);
     if (!sk || !ct || !slots || !nct) return fail(PIEHIP_EINVAL, "null operand");
@@ -269,16 +270,16 @@ int piehip_client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *c
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M;
     const size_t LN = h->LN();
     Tmp tmp;
-    TMPGET(d_ct, (size_t)nct * 2 * LN);
+    TMPGET(d_ct, (size_t)nct * ncomp * LN);
     TMPGET(d_sk, LN);
     TMPGET(d_x, (size_t)nct * LN);
     TMPGET(d_u, (size_t)nct * N);
     TMPGET(d_slotsw, (size_t)nct * B);
     TMPGET(d_posw, (N + 1) / 2 + 1);
-    HIPCHK(hipMemcpy(d_ct, ct, (size_t)nct * 2 * LN * sizeof(u64), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ct, ct, (size_t)nct * ncomp * LN * sizeof(u64), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_sk, sk, LN * sizeof(u64), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_posw, h->hp.slot_pos.data(), sizeof(u32) * N, hipMemcpyHostToDevice));
-    launch_dec_dot(h->d_dc, N, L, d_ct, d_sk, d_x, nct, h->stream);
+    launch_dec_dot(h->d_dc, N, L, d_ct, d_sk, d_x, nct, h->stream, ncomp);
     launch_ntt(h->plan, d_x, nct * L, 0, L, true, h->stream);
     launch_dec_round(h->d_dc, N, L, M, d_x, d_u, nct, h->stream);
     launch_ntt(h->plan, d_u, nct, M, 1, false, h->stream);
@@ -287,6 +288,15 @@ int piehip_client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *c
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(slots, d_slotsw, sizeof(int64_t) * (size_t)nct * B, hipMemcpyDeviceToHost));
     return PIEHIP_OK;
+}
+
+int piehip_client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots)
+{
+    return client_decrypt(h, sk, ct, nct, B, slots, 2);
+}
+int piehip_client_decrypt_deg2(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots)
+{
+    return client_decrypt(h, sk, ct, nct, B, slots, 3);
 }
 
 }  // extern "C"

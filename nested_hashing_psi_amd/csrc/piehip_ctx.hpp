@@ -72,6 +72,7 @@ struct MulWs {
     u64 *d01 = nullptr;  // [nb][2][L][N]
     u64 *d2c = nullptr;  // [nb][L][N]
     u64 *dig = nullptr;  // [nb][L][L][N]
+    u64 *t3 = nullptr;   // [nb][3][L][N]: a run()'s last product on its way to a degree-2 result (allocated with piehip_set_result_relin(0))
 };
 
 // one query of the batch (piehip_set_query_batch; a handle without a batch has query 0 only): its device inputs, and its way
@@ -209,11 +210,16 @@ struct piehip_ctx {
     // run() workspace
     u64 *d_acc = nullptr;   // [b][K][2][L][N]
     u64 *d_prod = nullptr;  // [b][2][L][N]  (K > 2 only)
-    u64 *d_out = nullptr;   // [b][2][L][N]
+    u64 *d_out = nullptr;   // [b][2][L][N]  ([b][3][L][N] once the handle has handed out three-component rows: res_cap_comps)
     // piehip_set_result_limbs: run() hands its results out on the first res_limbs limbs of Q (L = as they are).  With fewer, the
     // product chain writes full rows into d_full and the reduction writes [b][nq][2][res_limbs][N] into the result buffer
     u32 res_limbs = 0;
     u64 *d_full = nullptr;  // [b][nq][2][L][N], allocated with the first setting below L and kept with the workspace
+    // piehip_set_result_relin: off, the last product of a run() with K >= 2 is not relinearised and a result row has three components.
+    // d_out and d_full then hold res_cap_comps = 3 components per row (allocated with the setting, kept with the workspace), and the
+    // workspace has ws.t3
+    bool res_relin = true;
+    u32 res_cap_comps = 0;
     piehip::MulWs ws;
     size_t ws_cap_rows = 0;   // rows (bin layer x query) the workspace arrays were allocated for; ws.nb = rows in use
     u32 ws_cap_K = 0;
@@ -242,7 +248,9 @@ struct piehip_ctx {
     size_t pool_used = 0;
 
     size_t LN() const { return (size_t)hp.L * hp.N; }
-    size_t res_ct_words() const { return 2 * (size_t)res_limbs * hp.N; }   // one result ciphertext as it leaves the handle
+    u32 res_comps(u32 K_) const { return (!res_relin && K_ >= 2) ? 3u : 2u; }   // components of a result row for K_ inner hash functions
+    u32 res_comps() const { return res_comps(K); }
+    size_t res_ct_words() const { return res_comps() * (size_t)res_limbs * hp.N; }   // one result ciphertext as it leaves the handle
 };
 
 namespace piehip {
@@ -250,6 +258,7 @@ namespace piehip {
 // the key switch of run() has a key for every query: the handle's, or one per query of the batch (piehip_load_relin_key_q)
 inline bool run_keys_loaded(const piehip_ctx *h)
 {
+    if (h->K == 2 && !h->res_relin) return true;   // the only product is not relinearised
     return h->K <= 1 || h->d_evk || (h->d_evkq && h->evkq_n == h->nq && h->evkq_loaded == (1u << h->nq) - 1);
 }
 
@@ -384,8 +393,11 @@ void slice_free(piehip_ctx *h);          // back to an unsliced handle: the slic
 int slice_batch_changed(piehip_ctx *h);  // piehip_set_query_batch on a sliced handle: acc for the new batch, nothing put
 // result limbs (piehip_run.cpp): `rows` ciphertexts full[rows][2][L][N] (EVALUATION, standard order; overwritten) reduced to their
 // first `keep` limbs, out[rows][2][keep][N].  out_is_result: out is a run()'s result buffer
-void enqueue_mod_reduce(Sched &s, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result = false);
-int ensure_full_rows(piehip_ctx *h);   // piehip.cpp: d_full for the workspace's rows when the handle reduces its results
+// comps: polynomials per row (3: degree-2 results)
+void enqueue_mod_reduce(Sched &s, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result = false, u32 comps = 2);
+// piehip.cpp: what the handle's result settings need beside the workspace's rows, for a database of K inner hash functions: d_full when
+// it reduces its results; three-component d_out / d_full and ws.t3 when it hands out degree-2 results
+int ensure_full_rows(piehip_ctx *h, u32 K);
 // device input buffers of query q of the batch (owned copies: the host setters and the staged uploads write them)
 int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus);
 void use_owned_inputs(piehip_ctx *h);   // the next run() evaluates the owned copies of every query of the batch

@@ -314,6 +314,8 @@ int piehip_rccl_bin_slice(uint32_t b_total, int nranks, int rank, uint32_t *bin_
 // what both gather calls refuse first
 static int gather_check(const piehip_ctx *h, int root, bool has_dest)
 {
+    if (!h->res_relin)   // (the same reason)
+        return fail(PIEHIP_ESTATE, "gather_results: unrelinearised results (piehip_set_result_relin) are not gathered");
     if (h->res_limbs != h->hp.L)   // the ranks' row sizes would have to agree, and nothing checks a setting across ranks
         return fail(PIEHIP_ESTATE, "gather_results: results reduced to fewer limbs (piehip_set_result_limbs) are not gathered");
     if (!h->comm) return fail(PIEHIP_ESTATE, "gather_results: no communicator (piehip_rccl_init / piehip_rccl_attach)");

@@ -62,7 +62,8 @@ static RunKey run_key(const Sched &s)
 // One batched EvalMult(ct,ct) (BatchedFHEHIPPIE.cpp:123): operands in COEFFICIENT format (produced by
 // ntt(.., inverse, sigma = false, fold = true): with folding on, their outermost inverse stage is applied here),
 // X polynomial (o,c) at x + o*sx + c*LN, Y likewise.  relin: out[nb][2][L][N] (times mask if given);
-// otherwise out[nb][3][L][N] holds the EVALUATION-format tensor result.
+// otherwise out[nb][3][L][N] holds the EVALUATION-format tensor result -- times mask if given (a run()'s degree-2 result, include/piehip.h
+// "Result relinearisation": the product is formed in w.t3; the mask is lane-ordered where plan.result_eval_q, in standard order otherwise).
 void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
                  const u64 *mask, u64 *out, bool xq_ready, bool out_is_result)
 {
@@ -90,10 +91,14 @@ void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size
     // A relinearising product needs d0 and d1 back in EVALUATION form, and their Q limbs enter scale-and-round only as the own-limb term
     // c_k d_k: where the plan says so those 2 L limbs per row are neither inverse-transformed here nor read by scale-and-round, and the
     // key-switch MAC adds c_k (a (x) b)_k from the QP operands.  d2 keeps every limb: the digit lift wants coefficients.
+    // A product that is not relinearised and goes out as a run()'s result has no digit lift: d2 qualifies too, no Q limb is
+    // inverse-transformed, and the finishing kernel adds the three own-limb terms.
     const bool eval_q = relin && pl.d01_eval_q;
+    const bool deg2 = !relin && mask;
+    const bool eval_q3 = deg2 && pl.result_eval_q;
     if (pl.fused_tensor) {
         ProfScope ps(s, PIEHIP_K_TENSOR_NTT_INV, W * nb * 7.0 * M);  // (the tensor product's bytes, whichever limbs are transformed)
-        launch_ntt16_tensor(pl, w.eqp, w.dqp, nb, M, s.stream, eval_q ? L : 0);
+        launch_ntt16_tensor(pl, w.eqp, w.dqp, nb, M, s.stream, (eval_q || eval_q3) ? L : 0, eval_q3);
     } else {
         {
             ProfScope ps(s, PIEHIP_K_TENSOR, W * nb * 7.0 * M);
@@ -122,12 +127,29 @@ void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size
         o.digits_ready = pl.digits_with_d01;
         o.d01_eval_q = eval_q;
         enqueue_keyswitch(s, w, nb, run_key(s), mask, out, o);
+    } else if (eval_q3) {
+        {
+            ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * (M - L) + 3.0 * L));
+            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.t3, 3 * LN, w.t3 + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true, true, true);
+        }
+        NttExtra ex;
+        ex.lazy_out = true;  // the finishing kernel adds the own-limb term into its accumulator before reducing
+        ntt(s, w.t3, nb * 3 * L, 0, L, false, true, true, &ex);
+        if (out_is_result) s.gate();
+        ProfScope ps(s, PIEHIP_K_DEG2_FINISH, W * nb * 11.0 * L);
+        launch_deg2_finish(h->d_dc, N, L, w.t3, w.eqp, M, mask, out, nb, s.stream, pl.lane_T, pl.lane_kp, s.mask_div);
     } else {
+        u64 *t = deg2 ? w.t3 : out;
         {
             ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, out, 3 * LN, out + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true);
+            launch_scale_round(h->d_dc, N, L, w.dqp, nb, t, 3 * LN, t + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true);
         }
-        ntt(s, out, nb * 3 * L, 0, L, false, false, true);
+        ntt(s, t, nb * 3 * L, 0, L, false, false, true);
+        if (deg2) {
+            if (out_is_result) s.gate();
+            ProfScope ps(s, PIEHIP_K_MASK, W * nb * 3 * 3.0 * L);
+            launch_ct_mul_plain(h->d_dc, N, L, t, mask, LN, out, nb, s.stream, s.mask_div, 3);
+        }
     }
 }
 
@@ -140,23 +162,23 @@ void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size
 // In a run that brings its results down to host memory the next queue group is released here, in front of the limb-drop kernel:
 // this group then has that kernel and the forward transform of the kept limbs left, about what the key-switch MAC alone is when
 // nothing is reduced, and its (smaller) download still travels under the next group's evaluation.
-void enqueue_mod_reduce(Sched &s, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result)
+void enqueue_mod_reduce(Sched &s, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result, u32 comps)
 {
     piehip_ctx *h = s.h;
     const u32 N = h->hp.N, L = h->hp.L;
     const double W = 8.0 * N;
     {
-        ProfScope ps(s, PIEHIP_K_RESULT_NTT_INV, 2 * W * rows * 2 * L);
-        launch_ntt(h->plan, full, rows * 2 * L, 0, L, true, s.stream);
+        ProfScope ps(s, PIEHIP_K_RESULT_NTT_INV, 2 * W * rows * comps * L);
+        launch_ntt(h->plan, full, rows * comps * L, 0, L, true, s.stream);
     }
     if (out_is_result) s.gate();
     {
-        ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * rows * 2 * (L + keep));
-        launch_limb_drop(h->d_dc, N, L, keep, full, out, rows * 2, s.stream);
+        ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * rows * comps * (L + keep));
+        launch_limb_drop(h->d_dc, N, L, keep, full, out, rows * comps, s.stream);
     }
     {
-        ProfScope ps(s, PIEHIP_K_RESULT_NTT_FWD, 2 * W * rows * 2 * keep);
-        launch_ntt(h->plan, out, rows * 2 * keep, 0, keep, false, s.stream);
+        ProfScope ps(s, PIEHIP_K_RESULT_NTT_FWD, 2 * W * rows * comps * keep);
+        launch_ntt(h->plan, out, rows * comps * keep, 0, keep, false, s.stream);
     }
 }
 
@@ -225,7 +247,8 @@ static void enqueue_run_bins(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_
     chain.wait_before_results = chain.release = nullptr;
     enqueue_run_bins_full(chain, b0, nb, h->d_full, chain_only);
     const size_t r0 = (size_t)b0 * nq;
-    enqueue_mod_reduce(s, h->d_full + r0 * 2 * h->LN(), nb * nq, keep, results + r0 * h->res_ct_words(), true);
+    const u32 comps = h->res_comps();
+    enqueue_mod_reduce(s, h->d_full + r0 * comps * h->LN(), nb * nq, keep, results + r0 * h->res_ct_words(), true, comps);
 }
 static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_only)
 {
@@ -280,10 +303,12 @@ static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
     w.d01 += r0 * 2 * LN;
     w.d2c += r0 * LN;
     w.dig += r0 * L * LN;
+    if (w.t3) w.t3 += r0 * 3 * LN;
     u64 *acc = h->d_acc + r0 * K * 2 * LN;
     u64 *prod = h->d_prod ? h->d_prod + r0 * 2 * LN : nullptr;
-    u64 *out = results + r0 * 2 * LN;
-    const u64 *masks = (h->plan.lane_order ? h->d_masks_sigma : h->d_masks) + (size_t)b0 * LN;
+    const bool deg2 = h->res_comps() == 3;   // piehip_set_result_relin(0): the last product goes out as it is, three components
+    u64 *out = results + r0 * h->res_comps() * LN;
+    const u64 *masks = ((deg2 ? h->plan.result_eval_q : h->plan.lane_order) ? h->d_masks_sigma : h->d_masks) + (size_t)b0 * LN;
     s.mask_div = nq;
     s.key_group = (nq > 1 && h->d_evkq && h->evkq_n == nq) ? nq : 1;  // per-query EvalMult keys: row r of a group is query r % nq
     const bool x_direct = run_x_direct(h);
@@ -313,7 +338,7 @@ static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
     for (u32 hf = 1; hf < K; hf++) {
         const bool last = hf + 1 == K;
         u64 *dst = last ? out : prod;
-        enqueue_mul(s, w, x, sx, acc + (size_t)hf * 2 * LN, (size_t)K * 2 * LN, nb, true, last ? masks : nullptr, dst, xq, last);
+        enqueue_mul(s, w, x, sx, acc + (size_t)hf * 2 * LN, (size_t)K * 2 * LN, nb, !(last && deg2), last ? masks : nullptr, dst, xq, last);
         if (!last) {
             ex.copy_K = 1;  // the product is the X operand of the next multiplication
             ntt(s, prod, nb * 2 * L, 0, L, true, false, true, xq ? &ex : nullptr);
@@ -342,6 +367,11 @@ int piehip::run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *
     if (!h->K || (!chain_only && !h->d_db)) return fail(PIEHIP_ESTATE, "run: database not loaded");
     if (!h->d_acc || !h->ws.eqp) return fail(PIEHIP_ESTATE, "run: no workspace (an earlier allocation failed: piehip_set_query_batch / load)");
     if (!run_keys_loaded(h)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
+    if (h->res_comps() == 3) {
+        if (h->slice.on) return fail(PIEHIP_ESTATE, "run: a query-sliced handle relinearises its results (piehip_set_result_relin)");
+        if (!h->ws.t3 || h->res_cap_comps < 3)
+            return fail(PIEHIP_ESTATE, "run: no rows for three-component results (an earlier allocation failed: piehip_set_result_relin)");
+    }
     if (h->res_limbs < h->hp.L && !h->d_full) return fail(PIEHIP_ESTATE, "run: no rows for the result reduction (an earlier allocation failed: piehip_set_result_limbs)");
     for (u32 q = 0; q < h->nq && !chain_only; q++) {
         if (h->query[q].idx && h->query[q].minus) continue;
@@ -468,6 +498,8 @@ int piehip_set_graph(piehip_handle h, int on)
     NEED_RO(h);
     if (on && h->res_limbs < h->hp.L)
         return fail(PIEHIP_ESTATE, "set_graph: the captured graph hands out full results (piehip_set_result_limbs is below L)");
+    if (on && !h->res_relin)
+        return fail(PIEHIP_ESTATE, "set_graph: the captured graph relinearises its results (piehip_set_result_relin is off)");
     if (on && h->slice.on) return fail(PIEHIP_ESTATE, "set_graph: a query-sliced handle runs in two halves (piehip_run_slice, piehip_run_chain): no captured graph");
     h->use_graph = on != 0;
     if (!on) drop_graph(h);

@@ -107,6 +107,7 @@ public:
         lists.assign(nq, std::vector<LimbCt>(b));
         listStale.assign(nq, false);
         PieContext::check(piehip_get_result_limbs(cc->handle(), &resLimbs));
+        PieContext::check(piehip_get_result_components(cc->handle(), &resComps));
     }
 
     // Result limbs (include/piehip.h "Result limbs"): from the next run() on the result ciphertexts are [2][keep][N], on the first
@@ -121,6 +122,20 @@ public:
             for (auto &c : l) c.limbs.clear();
     }
     uint32_t resultLimbs() const { return resLimbs; }
+
+    // Result relinearisation (include/piehip.h "Result relinearisation"): off, the last ciphertext product of run() is not
+    // relinearised: with K >= 2 the result ciphertexts are [3][keep][N] (d0, d1, d2: they decrypt as d0 + d1 s + d2 s^2), and a
+    // database with K = 2 needs no EvalMult key.  The page-locked result array follows the setting; result lists of earlier runs are dropped.
+    void setResultRelin(bool on)
+    {
+        PieContext::check(piehip_set_result_relin(cc->handle(), on ? 1 : 0));
+        PieContext::check(piehip_host_buffers_q(cc->handle(), 0, nullptr, nullptr, &pinRes));
+        PieContext::check(piehip_get_result_components(cc->handle(), &resComps));
+        std::fill(listStale.begin(), listStale.end(), false);
+        for (auto &l : lists)
+            for (auto &c : l) c.limbs.clear();
+    }
+    uint32_t resultComponents() const { return resComps; }
 
     void setIndex(uint32_t q, std::vector<std::vector<LimbCt>> &&indexMatrix)  // [K][E] ciphertexts of query q
     {
@@ -241,7 +256,7 @@ public:
         return lists[q];
     }
     const uint64_t *resultTowers(uint32_t q, uint32_t i) const { return pinRes + ((size_t)i * nq + q) * resultWords(); }  // rows [bin layer][query]
-    size_t resultWords() const { return 2 * (size_t)resLimbs * cc->ringDimension(); }  // one result ciphertext, [2][resultLimbs][N]
+    size_t resultWords() const { return (size_t)resComps * resLimbs * cc->ringDimension(); }  // one result ciphertext, [resultComponents][resultLimbs][N]
 
 private:
     struct QueryState {
@@ -271,6 +286,7 @@ private:
     std::vector<QueryState> st;
     uint64_t *pinRes = nullptr;  // [b][nq][2][resLimbs][N], page-locked, owned by the library
     uint32_t resLimbs = 0;       // piehip_set_result_limbs: L unless setResultLimbs said otherwise
+    uint32_t resComps = 2;       // piehip_get_result_components: 3 after setResultRelin(false) with K >= 2
     std::vector<std::vector<LimbCt>> lists;
     std::vector<bool> listStale;
     bool rerun = false;
@@ -343,6 +359,10 @@ public:
     // operator has no counterpart (OpenFHE's Compress is the call a maintainer would make: INTEGRATION.md).  Default: L.
     void setResultLimbs(uint32_t keep) { staged.setResultLimbs(keep); }
     uint32_t resultLimbs() const { return staged.resultLimbs(); }
+    // The last EvalMult of run() (.cpp:123) without its relinearisation: the result ciphertexts have three components [3][keep][N],
+    // which decrypt as they are, and K = 2 needs no EvalMult key.  The reference operator relinearises (OpenFHE's default).  Default: on.
+    void setResultRelin(bool on) { staged.setResultRelin(on); }
+    uint32_t resultComponents() const { return staged.resultComponents(); }
 
     // .hpp:40-43, [K][E] ciphertexts
     void setIndex(std::vector<std::vector<LimbCt>> &&indexMatrix) { staged.setIndex(0, std::move(indexMatrix)); }
@@ -430,6 +450,9 @@ public:
     // result limbs of every query of the batch (see BatchedFHEHIPPIE::setResultLimbs): rows [bin layer][query] of [2][keep][N]
     void setResultLimbs(uint32_t keep) { staged.setResultLimbs(keep); }
     uint32_t resultLimbs() const { return staged.resultLimbs(); }
+    // ... and their relinearisation (see BatchedFHEHIPPIE::setResultRelin): rows [bin layer][query] of [3][keep][N] when off
+    void setResultRelin(bool on) { staged.setResultRelin(on); }
+    uint32_t resultComponents() const { return staged.resultComponents(); }
 
 private:
     PieContext &cc;

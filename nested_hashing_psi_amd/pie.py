@@ -468,9 +468,29 @@ class BatchedFHEHIPPIE:
         _check(lib().piehip_get_result_limbs(self.cc._h, C.byref(n)))
         return n.value
 
+    def setResultRelin(self, on):
+        """on=False: the last ciphertext product of run() is not relinearised (piehip_set_result_relin): with K >= 2 every result
+        array is [..][3][keep][N] -- components d0, d1, d2, which decrypt as d0 + d1 s + d2 s^2 (client.decrypt takes them by their
+        shape) -- and a database with K = 2 needs no EvalMult key.  Page-locked result arrays follow the setting: ask hostBuffers()
+        again after changing it."""
+        _check(lib().piehip_set_result_relin(self.cc._h, 1 if on else 0))
+        self._results = None
+
+    @property
+    def resultRelin(self):
+        n = C.c_int32()
+        _check(lib().piehip_get_result_relin(self.cc._h, C.byref(n)))
+        return bool(n.value)
+
+    def resultComponents(self):
+        """components of a result ciphertext as the operator stands: 2, or 3 after setResultRelin(False) with K >= 2"""
+        n = C.c_uint32()
+        _check(lib().piehip_get_result_components(self.cc._h, C.byref(n)))
+        return n.value
+
     def _res_shape(self):
-        nq, keep = self.nq, self.resultLimbs
-        return (self.b, 2, keep, self.cc.N) if nq == 1 else (self.b, nq, 2, keep, self.cc.N)
+        nq, keep, nc = self.nq, self.resultLimbs, self.resultComponents()
+        return (self.b, nc, keep, self.cc.N) if nq == 1 else (self.b, nq, nc, keep, self.cc.N)
 
     def hostBuffers(self, query=0):
         """page-locked numpy views (index matrix [K][E][2][L][N] and minus element [2][L][N] of query `query` of the batch, and the

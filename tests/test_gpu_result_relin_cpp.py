@@ -1,0 +1,48 @@
+"""tests/result_relin_check.cpp, built and run the way tests/result_limbs_check.cpp is: the C++ facade's setResultRelin(false)
+(single-query operator and a query batch of two, no EvalMult key anywhere) against the vectors computed here from the oracle and the
+exact definition, which the program reads from a temporary directory."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests.test_result_relin import run_deg2_exact
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_cpp_facade_without_the_last_relinearisation(ob, tmp_path):
+    libdir = os.path.join(ROOT, "nested_hashing_psi_amd")
+    exe = str(tmp_path / "result_relin_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-pthread", "-o", exe, os.path.join(ROOT, "tests", "result_relin_check.cpp"),
+                           "-L" + libdir, "-lpiehip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
+    N, L, t = 4096, 2, 65537
+    k, e, K, b, E = 2, 2, 2, 2, 3
+    # the program's queries on the oracle: facade_check.cpp's table, seeds 6 / 7, result_relin_check.cpp's towers
+    o = ob.Oracle(N, L, t)
+    tbl = ((np.arange(k * e * K * b * E, dtype=np.uint64) * np.uint64(7919)) % np.uint64(65536) + np.uint64(1)).reshape(k, e, K, b, E)
+    ob.hct_shuffle_bins(tbl, 6)
+    slots = ob.pack_db(tbl)
+    db = np.stack([o.encode_eval(slots[h, bn, j]) for h in range(K) for bn in range(b) for j in range(E)]).reshape(K, b, E, L, N)
+    mk = ob.masks(t, b, k * e, 7)
+    masks = np.stack([o.encode_eval(mk[bn]) for bn in range(b)])
+
+    def towers(shape, seed):     # result_relin_check.cpp's towers()
+        w = np.arange(1, int(np.prod(shape)) + 1, dtype=np.uint64)
+        return ((w * np.uint64(2654435761) + np.uint64(seed * 40503)) % np.uint64(65521)).reshape(shape)
+
+    def query(base, minus):
+        idx = np.zeros((K, E, 2, L, N), dtype=np.uint64)
+        for h in range(K):
+            for j in range(E):
+                idx[h, j] = towers((2, L, N), base + h + 2 * j)
+        return run_deg2_exact(o, idx, towers((2, L, N), minus), db, masks, None)
+    want = np.stack([query(5, 3), query(12, 4)])
+    assert want.shape == (2, b, 3, L, N) and not (want[0] == want[1]).all() and len(np.unique(want[0])) > N
+    want.tofile(str(tmp_path / "want.bin"))
+    out = subprocess.run([exe, str(tmp_path)], stdout=subprocess.PIPE, timeout=300, universal_newlines=True)
+    print(out.stdout)
+    assert out.returncode == 0
+    assert "facade ok: %d + 2 x %d result ciphertexts of 3 components" % (b, b) in out.stdout
