@@ -186,8 +186,10 @@ static int client_encrypt(piehip_ctx *h, const uint64_t *sk, const int64_t *slot
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M;
     const size_t LN = h->LN();
     const u64 t = h->hp.t;
-    for (size_t i = 0; i < (size_t)nct * B; i++)
-        if ((u64)(slots[i] < 0 ? -slots[i] : slots[i]) >= t) return fail(PIEHIP_EINVAL, "slot value out of range for the plaintext modulus");
+    for (size_t i = 0; i < (size_t)nct * B; i++) {
+        const u64 v = (u64)slots[i], mag = slots[i] < 0 ? 0 - v : v;  // unsigned: INT64_MIN has no signed negation
+        if (mag >= t) return fail(PIEHIP_EINVAL, "slot value out of range for the plaintext modulus");
+    }
     // host staging, not zero-filled (the sampling threads touch their own parts): a[nct][L][N] and e[nct][N]
     std::unique_ptr<u64[]> a_host(a_seeds ? nullptr : new u64[(size_t)nct * LN]);
     std::unique_ptr<int32_t[]> ev(new int32_t[(size_t)nct * N]);

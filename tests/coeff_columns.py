@@ -1,5 +1,5 @@
-"""Crafted COEFFICIENT-form columns for the base conversions and the digit lifts (plain module, imported by the test files; not a
-conftest).
+"""Crafted COEFFICIENT-form columns for the base conversions, the digit lifts and the client's decryption (plain module,
+imported by the test files; not a conftest).
 
 A column is the tuple of residues of one coefficient: L of them over Q, or M = 2L + 1 over QP.  The HPS base conversions and the BV
 digit lift work on such columns, and they branch and round at places that uniform residues reach with negligible probability:
@@ -10,6 +10,10 @@ digit lift work on such columns, and they branch and round at places that unifor
                   fractions, (fsum + 2^59) >> 60)
   lift windows    residue limb i at q_j - 1, q_j, q_j + 1, q_i - 1, (q_i +- 1)/2, q_i mod q_j: where the lift of a residue mod q_i into
                   q_j subtracts, wraps and changes sign
+  message edges   neighbouring phases x on either side of a step of round(t x/Q): decryption's result changes there, at the messages
+                  where it wraps (t -> 0) and where the decoded slot changes sign ((t - 1)/2, (t + 1)/2)
+
+and, for the client's encryption, message coefficients m that put [Q m]_t on the branches of the message term.
 
 Everything here is exact integer arithmetic (oracle/exact.py); `o` is an oracle context (oracle.binding.Oracle).
 """
@@ -125,6 +129,38 @@ def ties_scale_round(o, rng):
     return out
 
 
+def ties_decrypt(o):
+    """{label: x in [0, Q)}: t x mod Q is k units (of Q 2^-60) from Q/2 -- the rounding of decryption, round(t x/Q) mod t.  Labels as in
+    ties_expand"""
+    qs, _ = moduli(o)
+    Q = ex.prod(qs)
+    u = tie_unit(Q)
+    tinv = pow(o.t % Q, -1, Q)
+    out = {"floor": (Q - 1) // 2 * tinv % Q, "floor+1": (Q + 1) // 2 * tinv % Q, "x=0": 0, "x=1": 1, "x=-1": Q - 1}
+    for k in tie_ks(len(qs)):
+        out[k] = ((Q - 1) // 2 + k * u) * tinv % Q
+    return out
+
+
+def message_edge_values(t):
+    """the messages at whose lower edge message_edges places a pair: 1, the two around t/2 where the decoded slot changes sign, t - 1, and
+    t itself -- round(t x/Q) = t for x just below Q, which is message 0"""
+    return [1, (t - 1) // 2, (t + 1) // 2, t - 1, t]
+
+
+def message_edges(o):
+    """{(m, 'below'): x0 - 1, (m, 'at'): x0} for the m of message_edge_values: x0 = ceil((2m - 1) Q / 2t) is the smallest x with
+    round(t x/Q) = m, so the pair rounds to m - 1 and m"""
+    qs, _ = moduli(o)
+    Q, t = ex.prod(qs), o.t
+    out = {}
+    for m in message_edge_values(t):
+        x0 = -(-(2 * m - 1) * Q // (2 * t))
+        out[(m, "below")] = (x0 - 1) % Q
+        out[(m, "at")] = x0 % Q
+    return out
+
+
 # ---- lift windows --------------------------------------------------------------------------------------------------------------
 def window_values(qs, i):
     """values of residue limb i that sit at the edges of its lifts into the other moduli"""
@@ -183,6 +219,17 @@ def window_families(o):
     f = Families(qs)
     f["windows"] = lift_windows(qs)
     f["digits"] = digit_extremes(qs)
+    return f
+
+
+def decrypt_families(o):
+    """all families over Q for the rounding of decryption: phases, COEFFICIENT columns of c0 + c1 s (+ c2 s^2)"""
+    qs, _ = moduli(o)
+    f = Families(qs)
+    f["digits"] = digit_extremes(qs)
+    f["windows"] = lift_windows(qs)
+    f["ties_decrypt"] = [reduce_col(x, qs) for x in ties_decrypt(o).values()]
+    f["message_edges"] = [reduce_col(x, qs) for x in message_edges(o).values()]
     return f
 
 
@@ -251,6 +298,50 @@ def ntt_q(o, poly):
 
 def intt_q(o, poly):
     return np.stack([o.intt(i, poly[i]) for i in range(poly.shape[0])])
+
+
+# ---- crafted messages and ciphertexts of a given phase ---------------------------------------------------------------------------
+def message_rrs(t):
+    """the values of rr = [Q m]_t that enc_message_coeffs cycles through: encryption adds -rr/t or (t - rr)/t according to rr <= t/2,
+    and nothing at all for rr = 0"""
+    h = (t - 1) // 2
+    return [0, 1, 2, h - 1, h, h + 1, h + 2, t - 2, t - 1]
+
+
+def enc_message_coeffs(o, n):
+    """n message coefficients m_i = rr_i (Q mod t)^-1 mod t, rr_i cycling through message_rrs(t): [Q m_i]_t = rr_i"""
+    qs, _ = moduli(o)
+    t = o.t
+    Qinv = pow(ex.prod(qs) % t, -1, t)
+    rrs = message_rrs(t)
+    return np.array([rrs[i % len(rrs)] * Qinv % t for i in range(n)], dtype=np.uint64)
+
+
+def mulmod_rows(a, b, mods):
+    """a b limb by limb for [len(mods)][N] arrays, with Python integers"""
+    return np.stack([np.array([int(x) * int(y) % int(m) for x, y in zip(ra, rb)], dtype=np.uint64) for ra, rb, m in zip(a, b, mods)])
+
+
+def phase_ct(o, X, sk=None, c1=None, c2=None):
+    """the ciphertext [2 or 3][L][N] (EVALUATION) whose phase c0 + c1 s + c2 s^2 is the COEFFICIENT polynomial X [L][N]: c0 = NTT(X) -
+    c1 s - c2 s^2, from c1 (and c2) in EVALUATION form and the key sk.  Without c1 the phase is X under any key"""
+    qs, _ = moduli(o)
+    c0 = ntt_q(o, np.ascontiguousarray(X, dtype=np.uint64))
+    if c1 is None:
+        assert c2 is None
+        return np.stack([c0, np.zeros_like(c0)])
+    comps = [c1] if c2 is None else [c1, c2]
+    spow = sk
+    for c in comps:
+        cs = mulmod_rows(c, spow, qs)
+        c0 = np.stack([np.array([(int(x) - int(y)) % q for x, y in zip(c0[i], cs[i])], dtype=np.uint64) for i, q in enumerate(qs)])
+        spow = mulmod_rows(spow, sk, qs)
+    return np.stack([c0] + [np.ascontiguousarray(c, dtype=np.uint64) for c in comps])
+
+
+def columns_polys(cols, mods, N):
+    """the columns in as many polynomials [len(mods)][N] as they need: [ceil(len(cols) / N)][len(mods)][N], zeros behind the last"""
+    return np.stack([columns_poly(cols[s:s + N], mods, N) for s in range(0, len(cols), N)])
 
 
 # ---- steering d2 of a product --------------------------------------------------------------------------------------------------
