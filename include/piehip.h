@@ -430,6 +430,48 @@ int piehip_get_result_components(piehip_handle h, uint32_t *ncomp);
 int piehip_client_decrypt_deg2(piehip_handle h, const uint64_t *sk, const uint64_t *ct /*[nct][3][L][N]*/, uint32_t nct, uint32_t B,
                                int64_t *slots);
 
+/* ---- chain limbs: the product chain of run() on a prefix of the RNS prime chain -----------------------------
+ * Everything of run() behind stage A -- the inverse transforms of the accumulators, both base conversions, the tensor product,
+ * scale-and-round, the digit transforms and the key-switch MAC -- costs between L and L^2 per row, and a stage-A accumulator (a sum of
+ * ciphertext x plaintext products) has most of its noise budget left.  The limb drop of "Result limbs" can therefore move to the FRONT
+ * of the chain: modulus switching between levels, as SEAL and OpenFHE users know it.  Opt-in, per handle, off by default.
+ *   piehip_set_chain_limbs   1 <= Lc <= L; Lc = L (the default): no launch, buffer or byte differs.  With Lc < L and a database of
+ *                            K >= 2, run() is, in exact integers:
+ *                            1. stage A as ever, on all L limbs: the accumulators are bit-identical;
+ *                            2. the limb drop: every accumulator ciphertext is reduced to its first Lc limbs by the limb drop of
+ *                               "Result limbs" -- the same formula, both components, the limbs L - 1 .. Lc one after the other with
+ *                               centred rounding: what piehip_mod_reduce(.., keep = Lc) computes;
+ *                            3. the product chain and the mask multiply (BatchedFHEHIPPIE.cpp:117-126) exactly as run() performs them
+ *                               on the LEVEL CONTEXT (N, Lc, t, q[:Lc], p[:Lc + 1]) -- every product, the intermediate ones of K >= 3
+ *                               included -- with the EvalMult key evk[i][c][j] restricted to i, j < Lc (the BV key's digit factor is
+ *                               [i = j] limb by limb, so the prefix is a valid key modulo Q' = q_0 .. q_{Lc-1}) and the masks
+ *                               restricted to their first Lc limbs;
+ *                            4. result rows [b][nq][ncomp][min(keep, Lc)][N]: with keep < Lc (piehip_set_result_limbs) the result
+ *                               reduction follows inside the level context, from Lc limbs down to keep; ncomp follows
+ *                               piehip_set_result_relin as ever (degree-2 results at a lower level work; K = 2 still needs no key).
+ *                            K = 1 has no product: the setting is accepted and changes nothing (rows of `keep` limbs).
+ *                            Every entry point that hands results out sizes its rows by min(keep, Lc): piehip_run, piehip_run_into,
+ *                            piehip_get_results, piehip_results_device, piehip_copy_results_device, piehip_run_staged,
+ *                            piehip_run_host(_async / _wait / _seeded*) and the page-locked result array of piehip_host_buffers(_q),
+ *                            which is sized by the settings at the time of the call (ask again after changing one).
+ *                            Per handle: a query slot (piehip_attach_database) has its own setting.  Works with query batches and
+ *                            per-query keys, seeded queries (stage A is untouched), one and two queues, the host-results stagger.
+ *   piehip_get_chain_limbs   the setting.
+ * Choosing Lc.  The library does not check noise.  The budget after the drop is min(budget, log2 Q' - log2 t - log2(N + 1) - 1) bits,
+ * and the chain then costs what it costs on any context of Lc limbs.  Budgets in bits as the CPU oracle reports them (its readout
+ * saturates at 57-58), K = 2, fresh queries (tests/test_chain_limbs.py):
+ *     parameters                                   full chain   chain limbs L-1        then keep = 2 / 1   chain limbs L-2
+ *     N = 16384, L = 4, t = 4296540161, E = 14     57           40, same plaintext     40 / 20             0, WRONG plaintext
+ *     N = 4096,  L = 3, t = 65537,      E = 6      57           14, same plaintext     -  / 14             0, WRONG plaintext
+ *     N = 2048,  L = 3, t = 4296540161, E = 3      29           0,  WRONG plaintext
+ * The L-2 column and the third row do NOT decrypt: the setting is the caller's responsibility.
+ * PIEHIP_EINVAL: Lc = 0 or Lc > L.  PIEHIP_ESTATE (the handle stays usable): Lc < L on a handle with piehip_set_graph(1), and
+ * piehip_set_graph(1) on a handle with Lc < L; Lc < L on a query-sliced handle, and a sliced load on a handle with Lc < L;
+ * piehip_gather_results(_host) on a handle with Lc < L.  piehip_fhepie_* ignores the setting.  Added without a new version number:
+ * look the symbols up; nothing of 102 changed. */
+int piehip_set_chain_limbs(piehip_handle h, uint32_t Lc);
+int piehip_get_chain_limbs(piehip_handle h, uint32_t *Lc);
+
 /* ---- query slices: stage A sharded by inner hash function and limb --------------------------------------
  * The reference evaluates, per bin layer, K inner products over E index ciphertexts (BatchedFHEHIPPIE.cpp:96-116) and then multiplies
  * the K accumulators together (.cpp:117-126).  Every RNS limb of an inner product depends on that limb of its operands only, so the

@@ -123,6 +123,8 @@ SYMBOLS = {
     "piehip_mod_reduce": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_uint32, u64p]),
     "piehip_set_result_limbs": (C.c_int, [C.c_void_p, C.c_uint32]),
     "piehip_get_result_limbs": (C.c_int, [C.c_void_p, u32p]),
+    "piehip_set_chain_limbs": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "piehip_get_chain_limbs": (C.c_int, [C.c_void_p, u32p]),
     "piehip_set_result_relin": (C.c_int, [C.c_void_p, C.c_int]),
     "piehip_get_result_relin": (C.c_int, [C.c_void_p, i32p]),
     "piehip_get_result_components": (C.c_int, [C.c_void_p, u32p]),

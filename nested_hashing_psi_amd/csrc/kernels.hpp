@@ -235,6 +235,22 @@ void launch_ct_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, const 
 // limb drop of npoly polynomials in COEFFICIENT format: in[npoly][L][N] -> out[npoly][keep][N], the limbs L - 1 .. keep dropped one
 // after the other with centred rounding (include/piehip.h "Result limbs").  1 <= keep < L <= MAX_L; false (nothing launched) otherwise
 bool launch_limb_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, const u64 *in, u64 *out, u32 npoly, hipStream_t st);
+// ---- chain limbs (include/piehip.h "Chain limbs"; kernels_pie.hip) -----------------------------------------------------------
+// The limb drop in front of the product chain, on npoly polynomials data[npoly][L][N] in COEFFICIENT format as the parent's inverse
+// transform left them (fold: outer stage pending): IN PLACE, the first `keep` limbs of every polynomial become the dropped
+// polynomial's, canonical, nothing pending; the limbs behind them are left alone.  1 <= keep < L <= MAX_L; false otherwise
+bool launch_chain_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, u64 *data, u32 npoly, hipStream_t st, bool fold);
+// launch_expand_both on a level context (dc, L: the level's) for plain operands -- canonical, nothing pending -- with a polynomial
+// distance per operand (six, siy); fold: the store side alone (the forward transform that follows is a folded one).  L < MAX_L
+bool launch_expand_both_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, size_t six, const u64 *y, size_t sy, size_t siy,
+                              u32 n_outer, u64 *out, hipStream_t st, bool small_moduli, bool fold);
+// The fused form: both conversions of the level context (dc_level, Lc limbs) with the drop from the parent's L limbs (dc_parent) in
+// their load phase.  Folded rings with every modulus in (2^59, 2^60) only; Y (and X, x_drop) are accumulators on L limbs as the
+// parent's folded inverse transform left them; without x_drop X is a product on Lc limbs from the level's folded inverse transform
+// whose Q limbs the QP array already holds.  expand_both_drop_applies: the pair is built (-DPIEHIP_CHAIN_DROP_FUSED=0: none is)
+bool expand_both_drop_applies(u32 L, u32 Lc);
+bool launch_expand_both_drop(const DevConsts *dc_parent, const DevConsts *dc_level, u32 N, u32 L, u32 Lc, const u64 *x, size_t sx, size_t six,
+                             bool x_drop, const u64 *y, size_t sy, size_t siy, u32 n_outer, u64 *out, hipStream_t st);
 // out[r][p] = in[r][map[p]] for nrows limbs
 void launch_permute(u32 N, const u64 *in, const u32 *map, u64 *out, u32 nrows, hipStream_t st);
 // packed encoding: slots[npt][B] -> u[npt][N] residues mod t at their EVALUATION positions

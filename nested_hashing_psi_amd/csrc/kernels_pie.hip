@@ -1412,6 +1412,241 @@ bool launch_limb_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, const u64 *in
 }
 
 // ---------------------------------------------------------------------------------------------
+// Chain limbs (include/piehip.h "Chain limbs"): the limb drop in front of the product chain.  The accumulators leave stage A and
+// the inverse transform on the handle's L limbs; the chain runs on the level context of the first LC.
+// ---------------------------------------------------------------------------------------------
+// The limb drop of limb_drop_kernel on the NP coefficient columns a thread holds, with the constants of the PARENT's block, read per
+// dropped limb through the laundered pointer (the base conversions' convention above).  S63 (every modulus below 2^60): the
+// shoup63 instruction block; otherwise limb_drop_kernel's own product.  Only c[..][0 .. KEEP) are meaningful afterwards.
+template <u32 L, u32 KEEP, int NP, bool S63>
+__device__ __forceinline__ void drop_limbs(const DevConsts *dc, u64 (&c)[NP][L])
+{
+#pragma unroll
+    for (u32 l = L - 1; l >= KEEP; l--) {
+        PIE_ITER_FENCE();
+        const DcC k = dc_iter(dc);
+        const u64 ql = k->mod[l].q;
+        u64 v[NP], s[NP];
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            v[p] = c[p][l];
+            s[p] = (u64)((int64_t)((ql >> 1) - v[p]) >> 63);  // all ones when the centred residue is negative
+        }
+#pragma unroll
+        for (u32 i = 0; i < l; i++) {
+            const u64 off = k->drop_off[l][i], w = k->drop_inv[l][i], wsh = k->drop_inv_sh[l][i], qi = k->mod[i].q;
+            const u64 nq = S63 ? neg_u(qi) : k->drop_negq[i];
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                const u64 x = c[p][i] - v[p] + off + (s[p] & (ql - off));
+                c[p][i] = S63 ? shoup63(x, w, wsh, nq) : mul_shoup_u(x, w, wsh, qi, nq);
+            }
+        }
+    }
+}
+
+// The drop as a launch of its own (the fallback of the fused kernel below): npoly polynomials data[npoly][L][N] in COEFFICIENT format,
+// as the inverse transform left them -- FOLD: outer stage pending, residues in [0, 4q) -- are overwritten IN PLACE, at the parent's
+// strides, by their first KEEP limbs after the drop: canonical, nothing pending.  Limbs KEEP .. L - 1 keep what they held.  A thread
+// owns its coefficient's (FOLD: its coefficient pair's) column of every limb, so nothing it overwrites is read by another.
+template <bool FOLD, u32 L, u32 KEEP>
+__global__ void __launch_bounds__(TPB) chain_drop_kernel(const DevConsts *__restrict__ dc, u32 N, u32 blocks_per_poly, u64 *data)
+{
+    constexpr int NP = FOLD ? 2 : 1;
+    const u32 poly = blockIdx.x / blocks_per_poly;
+    const u32 n = (blockIdx.x % blocks_per_poly) * TPB + threadIdx.x;
+    const u32 H = N / 2;
+    if (n >= (FOLD ? H : N)) return;
+    u64 *p = data + (size_t)poly * L * N + n;
+    u64 c[NP][L];
+#pragma unroll
+    for (u32 i = 0; i < L; i++) {
+        if (FOLD)
+            fold_load(dc, i, p[(size_t)i * N], p[(size_t)i * N + H], c[0][i], c[NP - 1][i]);
+        else
+            c[0][i] = p[(size_t)i * N];
+    }
+    drop_limbs<L, KEEP, NP, FOLD>(dc, c);  // (folding implies q < 2^60)
+#pragma unroll
+    for (u32 i = 0; i < KEEP; i++) {
+        p[(size_t)i * N] = c[0][i];
+        if (FOLD) p[(size_t)i * N + H] = c[NP - 1][i];
+    }
+}
+bool launch_chain_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, u64 *data, u32 npoly, hipStream_t st, bool fold)
+{
+    if (keep < 1 || keep >= L || L > MAX_L || !npoly) return false;
+    const u32 bpp = ((fold ? N / 2 : N) + TPB - 1) / TPB;
+    const dim3 grid(bpp * npoly), block(TPB);
+#define CDROP_(L_, K_)                                                                                              \
+    case (L_) * 8 + (K_):                                                                                           \
+        if (fold) hipLaunchKernelGGL((chain_drop_kernel<true, L_, K_>), grid, block, 0, st, dc, N, bpp, data);      \
+        else hipLaunchKernelGGL((chain_drop_kernel<false, L_, K_>), grid, block, 0, st, dc, N, bpp, data);          \
+        return true
+    switch (L * 8 + keep) {
+        CDROP_(2, 1);
+        CDROP_(3, 1); CDROP_(3, 2);
+        CDROP_(4, 1); CDROP_(4, 2); CDROP_(4, 3);
+        CDROP_(5, 1); CDROP_(5, 2); CDROP_(5, 3); CDROP_(5, 4);
+        CDROP_(6, 1); CDROP_(6, 2); CDROP_(6, 3); CDROP_(6, 4); CDROP_(6, 5);
+        CDROP_(7, 1); CDROP_(7, 2); CDROP_(7, 3); CDROP_(7, 4); CDROP_(7, 5); CDROP_(7, 6);
+    }
+#undef CDROP_
+    return false;
+}
+
+// Both conversions of a product on a level context whose operands are plain COEFFICIENT polynomials (canonical, nothing pending:
+// what chain_drop_kernel and an unfolded inverse transform leave), X and Y each with its own distance between the two polynomials
+// of a ciphertext -- the accumulators stay at the parent's strides, an intermediate product is packed.  FOLD is the store side alone:
+// the forward transform that follows is the level plan's.  expand_both_kernel's grid and row order.
+template <bool SCALE, bool FOLD, u32 L, bool MAD>
+__device__ __forceinline__ void expand_plain_body(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ in, size_t so, size_t si,
+                                                  u64 *__restrict__ out, u32 out_slot, u32 by)
+{
+    const u32 n = blockIdx.x * TPB + threadIdx.x;
+    const u32 H = N / 2;
+    if (n >= (FOLD ? H : N)) return;
+    const u32 o = by >> 1, c = by & 1;
+    constexpr u32 M = 2 * L + 1;
+    constexpr int NP = FOLD ? 2 : 1;
+    const u64 *pin = in + (size_t)o * so + (size_t)c * si + n;
+    u64 *pout = out + ((size_t)(o * 4 + out_slot + c) * M) * N + n;
+    u64 x[NP][L], y[NP][M];
+#pragma unroll
+    for (u32 i = 0; i < L; i++) {
+        x[0][i] = pin[(size_t)i * N];
+        if (FOLD) x[NP - 1][i] = pin[(size_t)i * N + H];
+    }
+    constexpr bool LZ = FOLD && MAD;
+    if (SCALE)
+        scale_pq_core<L, MAD, false, NP, LZ>(dc, x, y);
+    else
+        expand_core<L, MAD, false, NP, LZ>(dc, x, y);
+#pragma unroll
+    for (u32 a = 0; a < M; a++) {
+        PIE_ITER_FENCE();
+        if (FOLD) {
+            u64 y0, y1;
+            fold_store(dc, a, y[0][a], y[NP - 1][a], y0, y1);
+            pout[(size_t)a * N] = y0;
+            pout[(size_t)a * N + H] = y1;
+        } else {
+            pout[(size_t)a * N] = y[0][a];
+        }
+    }
+}
+template <bool FOLD, u32 L, bool MAD>
+__global__ void __launch_bounds__(TPB) expand_both_plain_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ x, size_t sx,
+                                                                size_t six, const u64 *__restrict__ y, size_t sy, size_t siy,
+                                                                u64 *__restrict__ out, u32 n_outer)
+{
+    if (blockIdx.y < 2 * n_outer)
+        expand_plain_body<true, FOLD, L, MAD>(dc, N, y, sy, siy, out, 2, blockIdx.y);
+    else
+        expand_plain_body<false, FOLD, L, MAD>(dc, N, x, sx, six, out, 0, blockIdx.y - 2 * n_outer);
+}
+bool launch_expand_both_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, size_t six, const u64 *y, size_t sy, size_t siy,
+                              u32 n_outer, u64 *out, hipStream_t st, bool small_moduli, bool fold)
+{
+    dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, n_outer * 4);
+#define EP(F_, L_, M_) hipLaunchKernelGGL((expand_both_plain_kernel<F_, L_, M_>), grid, dim3(TPB), 0, st, dc, N, x, sx, six, y, sy, siy, out, n_outer)
+#define EPL(L_)                                                              \
+    case L_:                                                                 \
+        if (fold && small_moduli) EP(true, L_, true);                        \
+        else if (fold) EP(true, L_, false);                                  \
+        else if (small_moduli) EP(false, L_, true);                          \
+        else EP(false, L_, false);                                           \
+        return true;
+    switch (L) { EPL(1) EPL(2) EPL(3) EPL(4) EPL(5) EPL(6) }   // a level context has fewer limbs than MAX_L
+#undef EPL
+#undef EP
+    return false;
+}
+
+// The fused form (folded rings, every modulus in (2^59, 2^60)): expand_both_kernel of the level context with the drop in front of its
+// conversions.  A thread loads its coefficient pair's L residues as the parent's folded inverse transform left them, applies the
+// outer stage and normalises (fold_load, the parent's constants), drops the limbs L - 1 .. LC (drop_limbs, the parent's constants)
+// and converts the LC residues with the LEVEL's constants into the level's QP operand rows [4][2 LC + 1][N] -- no pass over the
+// accumulators, no buffer.  The dropped X differs from what the QP array may hold in EVALUATION form, so X's Q limbs are written.
+// XDROP false (later products of K >= 3): X is an intermediate product on the level's limbs, packed, as the level's folded inverse
+// transform left it -- expand_body's own load, Q limbs already in place (SKIPQ); Y is an accumulator and is dropped all the same.
+template <bool SCALE, u32 L, u32 LC>
+__device__ __forceinline__ void expand_drop_body(const DevConsts *__restrict__ dcp, const DevConsts *__restrict__ dcl, u32 N,
+                                                 const u64 *__restrict__ in, size_t so, size_t si, u64 *__restrict__ out, u32 out_slot, u32 by)
+{
+    const u32 n = blockIdx.x * TPB + threadIdx.x;
+    const u32 H = N / 2;
+    if (n >= H) return;
+    const u32 o = by >> 1, c = by & 1;
+    constexpr u32 M = 2 * LC + 1;
+    const u64 *pin = in + (size_t)o * so + (size_t)c * si + n;
+    u64 *pout = out + ((size_t)(o * 4 + out_slot + c) * M) * N + n;
+    u64 x[2][LC], y[2][M];
+    {
+        u64 full[2][L];
+#pragma unroll
+        for (u32 i = 0; i < L; i++) fold_load(dcp, i, pin[(size_t)i * N], pin[(size_t)i * N + H], full[0][i], full[1][i]);
+        drop_limbs<L, LC, 2, true>(dcp, full);
+#pragma unroll
+        for (u32 i = 0; i < LC; i++) x[0][i] = full[0][i], x[1][i] = full[1][i];
+    }
+    if (SCALE)
+        scale_pq_core<LC, true, false, 2, true>(dcl, x, y);
+    else
+        expand_core<LC, true, false, 2, true>(dcl, x, y);
+#pragma unroll
+    for (u32 a = 0; a < M; a++) {
+        PIE_ITER_FENCE();
+        u64 y0, y1;
+        fold_store(dcl, a, y[0][a], y[1][a], y0, y1);
+        pout[(size_t)a * N] = y0;
+        pout[(size_t)a * N + H] = y1;
+    }
+}
+template <u32 L, u32 LC, bool XDROP>
+__global__ void __launch_bounds__(TPB) expand_both_drop_kernel(const DevConsts *__restrict__ dcp, const DevConsts *__restrict__ dcl, u32 N,
+                                                               const u64 *__restrict__ x, size_t sx, size_t six, const u64 *__restrict__ y,
+                                                               size_t sy, size_t siy, u64 *__restrict__ out, u32 n_outer)
+{
+    if (blockIdx.y < 2 * n_outer)
+        expand_drop_body<true, L, LC>(dcp, dcl, N, y, sy, siy, out, 2, blockIdx.y);
+    else if (XDROP)
+        expand_drop_body<false, L, LC>(dcp, dcl, N, x, sx, six, out, 0, blockIdx.y - 2 * n_outer);
+    else
+        expand_body<false, true, LC, true, true>(dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
+}
+// the (L, Lc) pairs the fused kernel is built for: Lc = L - 1 for every L, and the further pairs that stay free of scratch
+#ifndef PIEHIP_CHAIN_DROP_FUSED
+#define PIEHIP_CHAIN_DROP_FUSED 1
+#endif
+#define PIE_CHAIN_DROP_PAIRS(X_) X_(2, 1) X_(3, 2) X_(4, 3) X_(5, 4) X_(6, 5) X_(7, 6) X_(4, 2)
+bool expand_both_drop_applies(u32 L, u32 Lc)
+{
+    if (!PIEHIP_CHAIN_DROP_FUSED) return false;
+#define APPL_(L_, C_) if (L == L_ && Lc == C_) return true;
+    PIE_CHAIN_DROP_PAIRS(APPL_)
+#undef APPL_
+    return false;
+}
+bool launch_expand_both_drop(const DevConsts *dc_parent, const DevConsts *dc_level, u32 N, u32 L, u32 Lc, const u64 *x, size_t sx, size_t six,
+                             bool x_drop, const u64 *y, size_t sy, size_t siy, u32 n_outer, u64 *out, hipStream_t st)
+{
+    if (!expand_both_drop_applies(L, Lc)) return false;
+    dim3 grid((N / 2 + TPB - 1) / TPB, n_outer * 4);
+#define EBD_(L_, C_)                                                                                                                     \
+    if (L == L_ && Lc == C_) {                                                                                                           \
+        if (x_drop)                                                                                                                      \
+            hipLaunchKernelGGL((expand_both_drop_kernel<L_, C_, true>), grid, dim3(TPB), 0, st, dc_parent, dc_level, N, x, sx, six, y, sy, siy, out, n_outer);  \
+        else                                                                                                                             \
+            hipLaunchKernelGGL((expand_both_drop_kernel<L_, C_, false>), grid, dim3(TPB), 0, st, dc_parent, dc_level, N, x, sx, six, y, sy, siy, out, n_outer); \
+        return true;                                                                                                                     \
+    }
+    PIE_CHAIN_DROP_PAIRS(EBD_)
+#undef EBD_
+    return false;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Automorphism permutation in EVALUATION format (row A9): out[r][p] = in[r][map[p]]
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TPB) permute_kernel(u32 N, const u64 *__restrict__ in, const u32 *__restrict__ map,

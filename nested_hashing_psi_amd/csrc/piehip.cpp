@@ -155,10 +155,88 @@ static hipError_t upload_table(piehip_ctx *h, const T *src, size_t n, P **dst)
 
 }  // namespace piehip
 
+// What a context (N, L, t, q, p) needs on the device: its constant block, the transform tables and the plan that says what the
+// context does with them, the lane-order map (and, d_inv_pos, the encoder's slot map).  piehip_create's, and a level context's
+// (chain limbs).  The handle owns the tables (dev_tables).  Returns the error text, empty on success.
+static std::string context_tables(piehip_ctx *h, const HostParams &hp, NttPlan &pl, DevConsts **d_dc, u32 **d_sigma_inv, u32 **d_inv_pos)
+{
+#define TBL_(expr)                                                                     \
+    do {                                                                               \
+        hipError_t e_ = (expr);                                                        \
+        if (e_ != hipSuccess) return std::string(#expr) + ": " + hipGetErrorString(e_); \
+    } while (0)
+    const u32 N = hp.N, M = hp.M, logN = hp.logN;
+    pl.N = N;
+    pl.logN = logN;
+    {
+        bool lazy_ok = true, small_moduli = true;
+        for (u32 a = 0; a <= M; a++) {
+            if (hp.moduli[a] >> 60) lazy_ok = false;                      // lazy residues need 8q < 2^63 (t included)
+            if (a < M && (hp.moduli[a] >> 59) != 1) small_moduli = false;  // the mad paths assume 2^59 < q < 2^60 (Q and P)
+        }
+        ntt_plan_decide(pl, lazy_ok, small_moduli);
+        hipDeviceProp_t prop;
+        pl.num_cus = (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) ? (u32)prop.multiProcessorCount : 256u;
+    }
+    TBL_(upload_table(h, &hp.dc, 1, d_dc));
+    pl.dc = *d_dc;
+    {
+        std::vector<u64> pairs((size_t)(M + 1) * 4 * N);
+        u64 *tables = nullptr;  // [(M+1)][4][N]
+        TBL_(upload_table(h, (const u64 *)nullptr, pairs.size(), &tables));
+        pl.tables = tables;
+        for (u32 a = 0; a <= M; a++) {
+            for (const std::vector<u64> *t : {&hp.tw[a], &hp.tw_sh[a], &hp.itw[a], &hp.itw_sh[a]}) {
+                TBL_(hipMemcpy(tables, t->data(), sizeof(u64) * N, hipMemcpyHostToDevice));
+                tables += N;
+            }
+            for (u32 k = 0; k < N; k++) {
+                u64 *f = &pairs[((size_t)a * 2 + 0) * 2 * N + 2 * (size_t)k];
+                u64 *i = &pairs[((size_t)a * 2 + 1) * 2 * N + 2 * (size_t)k];
+                // the register-blocked kernels use 63-bit Shoup constants floor(w 2^63 / q) (kernels_ntt_fast.hip)
+                f[0] = hp.tw[a][k];
+                f[1] = hp.tw_sh[a][k] >> 1;
+                i[0] = hp.itw[a][k];
+                i[1] = hp.itw_sh[a][k] >> 1;
+            }
+        }
+        TBL_(upload_table(h, pairs.data(), pairs.size(), &pl.twp));
+        // the kernel-ordered twiddles of every (modulus, direction), one after the other
+        auto kernel_order = [&](bool k16, u32 s0, const u64 **dst) {
+            std::vector<u64> all, one;
+            for (u32 a = 0; a <= M; a++)
+                for (u32 dir = 0; dir < 2; dir++) {
+                    const u64 *nat = &pairs[((size_t)a * 2 + dir) * 2 * N];
+                    if (k16)
+                        build_twk16_table(nat, s0, logN - s0, one);
+                    else
+                        build_twc_table(nat, logN, s0, one);
+                    all.insert(all.end(), one.begin(), one.end());
+                }
+            return upload_table(h, all.data(), all.size(), dst);
+        };
+        if (pl.lane_order) TBL_(kernel_order(false, ntt_route(pl, false, false, false).s0, &pl.twc));
+        if (pl.fold) TBL_(kernel_order(false, 1, &pl.twc_fold));
+        if (pl.lane_kernel == NttKernel::blocked16) TBL_(kernel_order(true, logN - pl.lane_logn, &pl.twk16));
+    }
+    {
+        std::vector<u32> inv(N, 0xFFFFFFFFu), smap;
+        for (u32 s = 0; s < N; s++) inv[hp.slot_pos[s]] = s;
+        if (d_inv_pos) TBL_(upload_table(h, inv.data(), inv.size(), d_inv_pos));
+        if (pl.lane_kernel == NttKernel::blocked16)
+            ntt16_sigma_inverse_map(logN, logN - pl.lane_logn, smap);
+        else
+            ntt_sigma_inverse_map(logN, pl.lane_order ? logN - pl.lane_logn : ~0u, smap);
+        TBL_(upload_table(h, smap.data(), smap.size(), d_sigma_inv));
+    }
+#undef TBL_
+    return std::string();
+}
+
 // =================================================================================================
 extern "C" {
 
-int piehip_version(void) { return 102; }   // 101: piehip_profile_read_n, piehip_set_transform_slots, piehip_upload_turn_wait, piehip_rccl_abort; 102: seeded ciphertexts (the result limbs, the query slices and the seeded query slices came without a new number)
+int piehip_version(void) { return 102; }   // 101: piehip_profile_read_n, piehip_set_transform_slots, piehip_upload_turn_wait, piehip_rccl_abort; 102: seeded ciphertexts (the result limbs, the query slices, the seeded query slices and the chain limbs came without a new number: tests pin 102)
 const char *piehip_last_error(void) { return g_err.c_str(); }
 const char *piehip_kernel_name(int k) { return (k >= 0 && k < PIEHIP_NKERNELS) ? KNAMES[k] : "?"; }
 
@@ -191,7 +269,7 @@ int piehip_create(piehip_handle *out, uint32_t N, uint32_t L, uint64_t t, const 
                                      std::to_string(ndev) + " devices): libpiehip has no CPU fallback");
     }
     h->device = device;
-    h->res_limbs = L;
+    h->res_limbs = h->chain_limbs = L;
 #define CHK_(expr)                                                                          \
     do {                                                                                    \
         hipError_t e_ = (expr);                                                             \
@@ -209,71 +287,14 @@ int piehip_create(piehip_handle *out, uint32_t N, uint32_t L, uint64_t t, const 
         h->own_stream = true;
     }
     CHK_(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    const u32 M = h->hp.M, logN = h->hp.logN;
-    NttPlan &pl = h->plan;
-    pl.N = N;
-    pl.logN = logN;
     {
-        bool lazy_ok = true, small_moduli = true;
-        for (u32 a = 0; a <= M; a++) {
-            if (h->hp.moduli[a] >> 60) lazy_ok = false;                      // lazy residues need 8q < 2^63 (t included)
-            if (a < M && (h->hp.moduli[a] >> 59) != 1) small_moduli = false;  // the mad paths assume 2^59 < q < 2^60 (Q and P)
+        const std::string terr = context_tables(h, h->hp, h->plan, &h->d_dc, &h->d_sigma_inv, &h->d_inv_pos);
+        if (!terr.empty()) {
+            piehip_destroy(h);
+            return fail(PIEHIP_EHIP, terr);
         }
-        ntt_plan_decide(pl, lazy_ok, small_moduli);
-        hipDeviceProp_t prop;
-        pl.num_cus = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? (u32)prop.multiProcessorCount : 256u;
     }
-    CHK_(upload_table(h, &h->hp.dc, 1, &h->d_dc));
-    pl.dc = h->d_dc;
-    {
-        std::vector<u64> pairs((size_t)(M + 1) * 4 * N);
-        u64 *tables = nullptr;  // [(M+1)][4][N]
-        CHK_(upload_table(h, (const u64 *)nullptr, pairs.size(), &tables));
-        pl.tables = tables;
-        for (u32 a = 0; a <= M; a++) {
-            for (const std::vector<u64> *t : {&h->hp.tw[a], &h->hp.tw_sh[a], &h->hp.itw[a], &h->hp.itw_sh[a]}) {
-                CHK_(hipMemcpy(tables, t->data(), sizeof(u64) * N, hipMemcpyHostToDevice));
-                tables += N;
-            }
-            for (u32 k = 0; k < N; k++) {
-                u64 *f = &pairs[((size_t)a * 2 + 0) * 2 * N + 2 * (size_t)k];
-                u64 *i = &pairs[((size_t)a * 2 + 1) * 2 * N + 2 * (size_t)k];
-                // the register-blocked kernels use 63-bit Shoup constants floor(w 2^63 / q) (kernels_ntt_fast.hip)
-                f[0] = h->hp.tw[a][k];
-                f[1] = h->hp.tw_sh[a][k] >> 1;
-                i[0] = h->hp.itw[a][k];
-                i[1] = h->hp.itw_sh[a][k] >> 1;
-            }
-        }
-        CHK_(upload_table(h, pairs.data(), pairs.size(), &pl.twp));
-        // the kernel-ordered twiddles of every (modulus, direction), one after the other
-        auto kernel_order = [&](bool k16, u32 s0, const u64 **dst) {
-            std::vector<u64> all, one;
-            for (u32 a = 0; a <= M; a++)
-                for (u32 dir = 0; dir < 2; dir++) {
-                    const u64 *nat = &pairs[((size_t)a * 2 + dir) * 2 * N];
-                    if (k16)
-                        build_twk16_table(nat, s0, logN - s0, one);
-                    else
-                        build_twc_table(nat, logN, s0, one);
-                    all.insert(all.end(), one.begin(), one.end());
-                }
-            return upload_table(h, all.data(), all.size(), dst);
-        };
-        if (pl.lane_order) CHK_(kernel_order(false, ntt_route(pl, false, false, false).s0, &pl.twc));
-        if (pl.fold) CHK_(kernel_order(false, 1, &pl.twc_fold));
-        if (pl.lane_kernel == NttKernel::blocked16) CHK_(kernel_order(true, logN - pl.lane_logn, &pl.twk16));
-    }
-    {
-        std::vector<u32> inv(N, 0xFFFFFFFFu), smap;
-        for (u32 s = 0; s < N; s++) inv[h->hp.slot_pos[s]] = s;
-        CHK_(upload_table(h, inv.data(), inv.size(), &h->d_inv_pos));
-        if (pl.lane_kernel == NttKernel::blocked16)
-            ntt16_sigma_inverse_map(logN, logN - pl.lane_logn, smap);
-        else
-            ntt_sigma_inverse_map(logN, pl.lane_order ? logN - pl.lane_logn : ~0u, smap);
-        CHK_(upload_table(h, smap.data(), smap.size(), &h->d_sigma_inv));
-    }
+    h->cx.d_dc = h->d_dc, h->cx.plan = &h->plan, h->cx.d_sigma_inv = h->d_sigma_inv, h->cx.N = N, h->cx.L = L, h->cx.M = h->hp.M;
 #undef CHK_
     *out = h;
     return PIEHIP_OK;
@@ -308,6 +329,8 @@ int piehip_destroy(piehip_handle h)
     }
     free_workspace(h);
     for (void *p : h->dev_tables) (void)hipFree(p);
+    for (auto &kv : h->levels)
+        for (u64 **p : {&kv.second->evk, &kv.second->evk_sigma, &kv.second->evkq, &kv.second->evkq_sigma, &kv.second->masks, &kv.second->masks_sigma}) dev_free(p);
     dev_free(&h->d_evk_sigma);
     dev_free(&h->d_evkq);
     dev_free(&h->d_evkq_sigma);
@@ -405,13 +428,13 @@ int piehip_load_relin_key(piehip_handle h, const uint64_t *evk)
     int rc = fill_unloaded_key_slots(h);
     if (rc) return rc;
     if (h->d_evkq) HIPCHK(hipStreamSynchronize(h->stream));
-    return PIEHIP_OK;
+    return level_sync(h);
 }
 
 // lane-ordered copy of the mask plaintexts for the fused mask multiply of the last key switch
 extern "C++" int piehip::make_masks_sigma(piehip_ctx *h)
 {
-    if (!h->plan.lane_order) return PIEHIP_OK;
+    if (!h->plan.lane_order) return level_sync(h);   // (chain limbs: the level context's copies follow every mask load)
     if (!h->d_masks_sigma) {  // freed with the run buffers when the shape changes
         int rc = dev_alloc(&h->d_masks_sigma, (size_t)h->b * h->LN());
         if (rc) return rc;
@@ -419,7 +442,7 @@ extern "C++" int piehip::make_masks_sigma(piehip_ctx *h)
     launch_permute(h->hp.N, h->d_masks, h->d_sigma_inv, h->d_masks_sigma, h->b * h->hp.L, h->stream);
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(PIEHIP_EHIP, std::string("mask permutation: ") + hipGetErrorString(e));
-    return PIEHIP_OK;
+    return level_sync(h);
 }
 
 // run() workspace and result rows for b bin layers x nq queries of K inner hash functions
@@ -554,7 +577,7 @@ int piehip_attach_database(piehip_handle h, piehip_handle owner)
     h->db_borrowed = true;
     h->db_owner = owner;
     owner->db_borrowers++;
-    return PIEHIP_OK;
+    return level_sync(h);   // a slot has its own chain-limbs setting, and its own copies of the owner's key and masks for it
 }
 
 // the persistent hash-table buffer [k][e][K][b][E]: reallocated only when the size changes
@@ -953,7 +976,7 @@ int piehip_load_relin_key_q(piehip_handle h, uint32_t q, const uint64_t *evk)
     if (h->plan.lane_order) launch_permute(h->hp.N, h->d_evkq + q * words, h->d_sigma_inv, h->d_evkq_sigma + q * words, h->hp.L * 2 * h->hp.L, h->stream);
     HIPCHK(hipStreamSynchronize(h->stream));
     h->evkq_loaded |= 1u << q;
-    return PIEHIP_OK;
+    return level_sync(h);
 }
 
 // Seeded EvalMult keys: the L first components come from the host, the L second ones are expanded from their seeds on the device;
@@ -1005,6 +1028,7 @@ int piehip_set_transform_slots(piehip_handle h, uint32_t n)
 {
     NEED_RO(h);
     h->plan.max_slots = n;
+    for (auto &kv : h->levels) kv.second->plan.max_slots = n;
     drop_graph(h);   // a captured run() has the old grids baked in
     return PIEHIP_OK;
 }
@@ -1075,6 +1099,106 @@ int piehip_get_result_components(piehip_handle h, uint32_t *ncomp)
     NEED_RO(h);
     if (!ncomp) return fail(PIEHIP_EINVAL, "null out");
     *ncomp = h->res_comps();
+    return PIEHIP_OK;
+}
+
+// Chain limbs (include/piehip.h): the level context's copies of what the chain reads beside the workspace -- the limb prefix
+// evk[i][c][j], i, j < Lc, of every EvalMult key and the first Lc limbs of the masks, each with its lane-ordered twin where the
+// level's plan has a lane order (its own map: a prefix of a mixed chain may take other routes than the parent).  Copied on the
+// handle's stream whenever the key or the database is set and when the setting changes: 8 and 7 MiB at C3 and as much again for
+// the twins.  The other choice -- reading the parent's arrays in place through their strides -- would have put two more strides
+// into the key-switch MAC, whose instantiations must stay what they are.
+extern "C++" int piehip::level_sync(piehip_ctx *h)
+{
+    LevelCtx *lv = h->level;
+    if (!lv || h->chain_limbs >= h->hp.L) return PIEHIP_OK;
+    const u32 N = h->hp.N, L = h->hp.L, Lc = lv->cx.L;
+    const size_t kw = (size_t)Lc * 2 * Lc * N, KW = (size_t)L * 2 * L * N;
+    const bool lane = lv->plan.lane_order;
+    // `rows` rows of L N words -> rows of Lc N words
+    auto prefix = [&](const u64 *src, u64 *dst, size_t rows) {
+        return hipMemcpy2DAsync(dst, (size_t)Lc * N * sizeof(u64), src, (size_t)L * N * sizeof(u64), (size_t)Lc * N * sizeof(u64), rows,
+                                hipMemcpyDeviceToDevice, h->stream);
+    };
+    int rc;
+    lv->has_evk = false;
+    if (h->d_evk) {
+        if (!lv->evk && (rc = dev_alloc(&lv->evk, kw))) return rc;
+        if (lane && !lv->evk_sigma && (rc = dev_alloc(&lv->evk_sigma, kw))) return rc;
+        HIPCHK(prefix(h->d_evk, lv->evk, 2 * Lc));
+        if (lane) launch_permute(N, lv->evk, lv->d_sigma_inv, lv->evk_sigma, Lc * 2 * Lc, h->stream);
+        lv->has_evk = true;
+    }
+    if (h->d_evkq && h->evkq_n) {
+        if (lv->evkq_cap < kw * h->evkq_n) {
+            dev_free(&lv->evkq);
+            dev_free(&lv->evkq_sigma);
+            lv->evkq_cap = 0;
+            if ((rc = dev_alloc(&lv->evkq, kw * h->evkq_n))) return rc;
+            if (lane && (rc = dev_alloc(&lv->evkq_sigma, kw * h->evkq_n))) return rc;
+            lv->evkq_cap = kw * h->evkq_n;
+        }
+        for (u32 i = 0; i < h->evkq_n; i++) HIPCHK(prefix(h->d_evkq + i * KW, lv->evkq + i * kw, 2 * Lc));
+        if (lane) launch_permute(N, lv->evkq, lv->d_sigma_inv, lv->evkq_sigma, h->evkq_n * Lc * 2 * Lc, h->stream);
+    }
+    if (h->d_masks && h->b) {
+        const size_t mw = (size_t)h->b * Lc * N;
+        if (lv->masks_cap < mw) {
+            dev_free(&lv->masks);
+            dev_free(&lv->masks_sigma);
+            lv->masks_cap = 0;
+            if ((rc = dev_alloc(&lv->masks, mw))) return rc;
+            if (lane && (rc = dev_alloc(&lv->masks_sigma, mw))) return rc;
+            lv->masks_cap = mw;
+        }
+        HIPCHK(prefix(h->d_masks, lv->masks, h->b));
+        if (lane) launch_permute(N, lv->masks, lv->d_sigma_inv, lv->masks_sigma, h->b * Lc, h->stream);
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PIEHIP_OK;
+}
+
+// The setting of a handle.  The level context is built when the setting first takes a value and kept: going back and forth
+// allocates nothing (the copies of keys and masks are made again, on the handle's stream).
+int piehip_set_chain_limbs(piehip_handle h, uint32_t Lc)
+{
+    NEED(h);
+    const u32 L = h->hp.L;
+    if (Lc < 1 || Lc > L) return fail(PIEHIP_EINVAL, "set_chain_limbs: Lc must be between 1 and L");
+    if (Lc < L && h->use_graph)
+        return fail(PIEHIP_ESTATE, "set_chain_limbs: a handle that replays a captured graph (piehip_set_graph) runs the product chain on every limb");
+    if (Lc < L && h->slice.on) return fail(PIEHIP_ESTATE, "set_chain_limbs: a query-sliced handle runs the product chain on every limb");
+    HIPCHK(hipSetDevice(h->device));
+    if (Lc == L) {
+        h->chain_limbs = L;
+        h->level = nullptr;
+        return PIEHIP_OK;
+    }
+    auto it = h->levels.find(Lc);
+    if (it == h->levels.end()) {
+        std::unique_ptr<LevelCtx> lv(new LevelCtx());
+        std::string err = lv->hp.init(h->hp.N, Lc, h->hp.t, h->hp.moduli.data(), h->hp.moduli.data() + L);
+        if (!err.empty()) return fail(PIEHIP_EINVAL, "set_chain_limbs: " + err);
+        err = context_tables(h, lv->hp, lv->plan, &lv->d_dc, &lv->d_sigma_inv, nullptr);
+        if (!err.empty()) return fail(PIEHIP_EHIP, "set_chain_limbs: " + err);   // (what was uploaded stays in dev_tables and goes with the handle)
+        lv->plan.max_slots = h->plan.max_slots;
+        lv->cx.d_dc = lv->d_dc, lv->cx.plan = &lv->plan, lv->cx.d_sigma_inv = lv->d_sigma_inv;
+        lv->cx.N = h->hp.N, lv->cx.L = Lc, lv->cx.M = lv->hp.M;
+        it = h->levels.emplace(Lc, std::move(lv)).first;
+    }
+    const u32 before = h->chain_limbs;
+    LevelCtx *const lv_before = h->level;
+    h->chain_limbs = Lc;
+    h->level = it->second.get();
+    const int rc = level_sync(h);
+    if (rc) h->chain_limbs = before, h->level = lv_before;
+    return rc;
+}
+int piehip_get_chain_limbs(piehip_handle h, uint32_t *Lc)
+{
+    NEED_RO(h);
+    if (!Lc) return fail(PIEHIP_EINVAL, "null out");
+    *Lc = h->chain_limbs;
     return PIEHIP_OK;
 }
 

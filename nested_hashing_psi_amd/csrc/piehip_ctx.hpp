@@ -136,6 +136,32 @@ struct SliceState {
     u32 u_n() const { return u_hi - u_lo; }
 };
 
+// What a schedule piece (ntt, enqueue_mul, enqueue_keyswitch, enqueue_mod_reduce) reads of a context: the handle's own -- its L
+// limbs -- or a level context (below).  A Sched carries one, as it carries a queue.
+struct ChainCtx {
+    const DevConsts *d_dc = nullptr;
+    const NttPlan *plan = nullptr;
+    const u32 *d_sigma_inv = nullptr;   // lane-order position -> standard position
+    u32 N = 0, L = 0, M = 0;
+    size_t LN() const { return (size_t)L * N; }
+};
+
+// Chain limbs (include/piehip.h): everything piehip_create derives from (N, Lc, t, q[:Lc], p[:Lc + 1]) -- constant block, transform
+// tables, plan with its routes and fusions -- and the limb prefixes of the handle's keys and masks, copied when the key or the
+// database is set (piehip.cpp, level_sync).  Built when the setting first takes the value Lc and kept with the handle; its device
+// tables are freed with the handle's (dev_tables).
+struct LevelCtx {
+    HostParams hp;
+    DevConsts *d_dc = nullptr;
+    NttPlan plan;
+    u32 *d_sigma_inv = nullptr;
+    ChainCtx cx;
+    // [Lc][2][Lc][N] (+ lane-ordered twin), [nq] of them for per-query keys, masks [b][Lc][N] (+ twin); *_cap: words allocated
+    u64 *evk = nullptr, *evk_sigma = nullptr, *evkq = nullptr, *evkq_sigma = nullptr, *masks = nullptr, *masks_sigma = nullptr;
+    size_t evkq_cap = 0, masks_cap = 0;
+    bool has_evk = false;
+};
+
 }  // namespace piehip
 using piehip::u32;
 using piehip::u64;
@@ -192,6 +218,12 @@ struct piehip_ctx {
     size_t arena_words = 0, arena_used = 0;
     u32 hk = 0, he = 0, hb = 0;  // table dimensions ([k][e][K][hb][E]; hb = all bin layers, of which this handle keeps b)
     piehip::NttPlan plan;
+    piehip::ChainCtx cx;         // the handle's own context as the schedule pieces take it (d_dc, plan, d_sigma_inv, N, L, M)
+    // piehip_set_chain_limbs: with chain_limbs < L the product chain of run() works on `level`, the level context of the first
+    // chain_limbs limbs; every level the handle has been set to stays in `levels`
+    u32 chain_limbs = 0;
+    piehip::LevelCtx *level = nullptr;
+    std::map<u32, std::unique_ptr<piehip::LevelCtx>> levels;
     // keys / database / inputs
     bool db_borrowed = false;  // piehip_attach_database: d_evk*, d_db, d_masks* belong to another handle (never freed or written here)
     piehip_ctx *db_owner = nullptr;  // ... that handle
@@ -250,7 +282,9 @@ struct piehip_ctx {
     size_t LN() const { return (size_t)hp.L * hp.N; }
     u32 res_comps(u32 K_) const { return (!res_relin && K_ >= 2) ? 3u : 2u; }   // components of a result row for K_ inner hash functions
     u32 res_comps() const { return res_comps(K); }
-    size_t res_ct_words() const { return res_comps() * (size_t)res_limbs * hp.N; }   // one result ciphertext as it leaves the handle
+    // limbs of a result row: the minimum of the two settings (chain limbs change nothing where there is no product: K = 1)
+    u32 out_limbs() const { return K >= 2 ? std::min(res_limbs, chain_limbs) : res_limbs; }
+    size_t res_ct_words() const { return res_comps() * (size_t)out_limbs() * hp.N; }   // one result ciphertext as it leaves the handle
 };
 
 namespace piehip {
@@ -273,8 +307,9 @@ struct Sched {
                                    // left; the next queue group starts behind it (null: nobody waits)
     u32 mask_div = 1;   // a batch: ciphertext row r of the product chain takes mask r / mask_div
     u32 key_group = 1;  // ... and, with per-query EvalMult keys, key r % key_group of d_evkq
-    Sched(piehip_ctx *h_) : h(h_), stream(h_->stream) {}
-    Sched(piehip_ctx *h_, hipStream_t s) : h(h_), stream(s) {}
+    const ChainCtx *cx; // the context the pieces work on: the handle's own unless run() hands them a level context (chain limbs)
+    Sched(piehip_ctx *h_) : h(h_), stream(h_->stream), cx(&h_->cx) {}
+    Sched(piehip_ctx *h_, hipStream_t s) : h(h_), stream(s), cx(&h_->cx) {}
     void wait_for_readers() const { if (wait_before_results) (void)hipStreamWaitEvent(stream, wait_before_results, 0); }
     void gate()  // in front of the kernel that writes a run's results
     {
@@ -369,8 +404,15 @@ struct KeyswitchOpts {
     bool d01_eval_q = false;     // (enqueue_mul only, plan.d01_eval_q) w.d01 lacks the own-limb term; the MAC adds it from w.eqp
 };
 void enqueue_keyswitch(Sched &s, MulWs &w, u32 nb, RunKey key, const u64 *mask, u64 *out, KeyswitchOpts o = {});
+// in (chain limbs): how the operands of a product on a level context lie in memory and what their conversion has to do first
+struct MulIn {
+    size_t six = 0, siy = 0;            // words between the two polynomials of X / of Y (0: the context's L N)
+    const ChainCtx *drop_from = nullptr;  // fused limb drop: Y (and X, x_drop) have drop_from->L limbs, folded outer stage pending
+    bool x_drop = false;
+    bool plain = false;                 // the operands are plain coefficients (chain_drop_kernel, an unfolded inverse transform)
+};
 void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
-                 const u64 *mask, u64 *out, bool xq_ready = false, bool out_is_result = false);
+                 const u64 *mask, u64 *out, bool xq_ready = false, bool out_is_result = false, const MulIn *in = nullptr);
 int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out);
 static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
 // piehip.cpp: run() workspace (and, with_db, database and masks) of a handle for b bin layers; the lane-ordered copy of its masks; the
@@ -388,6 +430,7 @@ __attribute__((visibility("hidden"))) int items_to_slots(piehip_ctx *h, Tmp &tmp
 // downloads its slice of the results there); whether stage A hands operand X over in lane order
 int run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *host_results = nullptr);
 bool run_x_direct(const piehip_ctx *h);
+bool run_on_level(const piehip_ctx *h);
 // piehip_slice.cpp
 void slice_free(piehip_ctx *h);          // back to an unsliced handle: the slice side's buffers and state
 int slice_batch_changed(piehip_ctx *h);  // piehip_set_query_batch on a sliced handle: acc for the new batch, nothing put
@@ -398,6 +441,8 @@ void enqueue_mod_reduce(Sched &s, u64 *full, u32 rows, u32 keep, u64 *out, bool 
 // piehip.cpp: what the handle's result settings need beside the workspace's rows, for a database of K inner hash functions: d_full when
 // it reduces its results; three-component d_out / d_full and ws.t3 when it hands out degree-2 results
 int ensure_full_rows(piehip_ctx *h, u32 K);
+// piehip.cpp: with chain limbs below L, bring the level context's copies of keys and masks up to the handle's (on its stream)
+int level_sync(piehip_ctx *h);
 // device input buffers of query q of the batch (owned copies: the host setters and the staged uploads write them)
 int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus);
 void use_owned_inputs(piehip_ctx *h);   // the next run() evaluates the owned copies of every query of the batch

@@ -9,21 +9,23 @@ using namespace piehip;
 namespace piehip {
 
 // ---- schedule pieces ----------------------------------------------------------------------------
-// What a context does where -- which transform kernel, which fusions -- is decided once, in h->plan
+// What a context does where -- which transform kernel, which fusions -- is decided once, in its plan.  Every
+// piece works on the context its Sched carries (s.cx): the handle's own, or the level context of a run() with chain limbs below L.
 void ntt(const Sched &s, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inv, bool sigma, bool fold, const NttExtra *ex)
 {
-    ProfScope ps(s, inv ? PIEHIP_K_NTT_INV : PIEHIP_K_NTT_FWD, 16.0 * s.h->hp.N * nlimbs);
-    launch_ntt(s.h->plan, data, nlimbs, mod_base, mod_count, inv, s.stream, sigma && s.h->plan.lane_order, fold && s.h->plan.fold, ex);
+    const NttPlan &pl = *s.cx->plan;
+    ProfScope ps(s, inv ? PIEHIP_K_NTT_INV : PIEHIP_K_NTT_FWD, 16.0 * s.cx->N * nlimbs);
+    launch_ntt(pl, data, nlimbs, mod_base, mod_count, inv, s.stream, sigma && pl.lane_order, fold && pl.fold, ex);
 }
 
 // BV key switch of the COEFFICIENT-format polynomials at w.d2c with `key`, added to the EVALUATION
 // ciphertexts at w.d01, optionally multiplied by mask plaintexts: out[nb][2][L][N]
 void enqueue_keyswitch(Sched &s, MulWs &w, u32 nb, RunKey key, const u64 *mask, u64 *out, KeyswitchOpts o)
 {
-    piehip_ctx *h = s.h;
-    const NttPlan &pl = h->plan;
-    const u32 N = h->hp.N, L = h->hp.L;
-    const size_t LN = h->LN();
+    const ChainCtx &cx = *s.cx;
+    const NttPlan &pl = *cx.plan;
+    const u32 N = cx.N, L = cx.L;
+    const size_t LN = cx.LN();
     const double W = 8.0 * N;
     const bool lane = o.lane && pl.lane_order;
     if (o.digits_ready) {
@@ -34,7 +36,7 @@ void enqueue_keyswitch(Sched &s, MulWs &w, u32 nb, RunKey key, const u64 *mask, 
     } else {
         {
             ProfScope ps(s, PIEHIP_K_DIGITS, W * nb * (L + (double)L * L));
-            launch_digits(h->d_dc, N, L, w.d2c, LN, nb, w.dig, s.stream, lane && pl.fold);
+            launch_digits(cx.d_dc, N, L, w.d2c, LN, nb, w.dig, s.stream, lane && pl.fold);
         }
         ntt(s, w.dig, nb * L * L, 0, L, false, lane, lane);
     }
@@ -43,9 +45,9 @@ void enqueue_keyswitch(Sched &s, MulWs &w, u32 nb, RunKey key, const u64 *mask, 
         assert(!o.d01_eval_q || (pl.d01_eval_q && lane));
         ProfScope ps(s, PIEHIP_K_RELIN,
                      W * (nb * ((double)L * L + 2 * L + 2 * L + (mask ? L : 0) + (o.d01_eval_q ? 4 * L : 0)) + 2.0 * L * L));
-        launch_relin_mac(h->d_dc, N, L, w.d01, 2 * LN, w.dig, key.key, mask, out, nb, s.stream, pl.small_moduli,
-                         lane ? h->d_sigma_inv : nullptr, key.stride, key.group, lane ? pl.lane_T : 0, pl.lane_kp, mask ? s.mask_div : 1,
-                         o.d01_eval_q ? w.eqp : nullptr, h->hp.M);
+        launch_relin_mac(cx.d_dc, N, L, w.d01, 2 * LN, w.dig, key.key, mask, out, nb, s.stream, pl.small_moduli,
+                         lane ? cx.d_sigma_inv : nullptr, key.stride, key.group, lane ? pl.lane_T : 0, pl.lane_kp, mask ? s.mask_div : 1,
+                         o.d01_eval_q ? w.eqp : nullptr, cx.M);
     }
 }
 
@@ -54,7 +56,12 @@ void enqueue_keyswitch(Sched &s, MulWs &w, u32 nb, RunKey key, const u64 *mask, 
 static RunKey run_key(const Sched &s)
 {
     const piehip_ctx *h = s.h;
-    const bool lane = h->plan.lane_order;
+    const bool lane = s.cx->plan->lane_order;
+    if (s.cx != &h->cx) {   // a level context: the limb prefixes of the same keys (level_sync)
+        const LevelCtx *lv = h->level;
+        if (s.key_group > 1) return {lane ? lv->evkq_sigma : lv->evkq, (size_t)s.cx->L * 2 * s.cx->LN(), s.key_group};
+        return {lane ? lv->evk_sigma : lv->evk};
+    }
     if (s.key_group > 1) return {lane ? h->d_evkq_sigma : h->d_evkq, (size_t)h->hp.L * 2 * h->LN(), s.key_group};
     return {lane ? h->d_evk_sigma : h->d_evk};
 }
@@ -65,16 +72,26 @@ static RunKey run_key(const Sched &s)
 // otherwise out[nb][3][L][N] holds the EVALUATION-format tensor result -- times mask if given (a run()'s degree-2 result, include/piehip.h
 // "Result relinearisation": the product is formed in w.t3; the mask is lane-ordered where plan.result_eval_q, in standard order otherwise).
 void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
-                 const u64 *mask, u64 *out, bool xq_ready, bool out_is_result)
+                 const u64 *mask, u64 *out, bool xq_ready, bool out_is_result, const MulIn *in)
 {
-    piehip_ctx *h = s.h;
-    const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M;
-    const size_t LN = h->LN();
+    const ChainCtx &cx = *s.cx;
+    const u32 N = cx.N, L = cx.L, M = cx.M;
+    const size_t LN = cx.LN();
     const double W = 8.0 * N;
-    const NttPlan &pl = h->plan;
+    const NttPlan &pl = *cx.plan;
     {
-        ProfScope ps(s, PIEHIP_K_EXPAND, W * nb * (4.0 * L + 4.0 * M));
-        launch_expand_both(h->d_dc, N, L, x, sx, y, sy, LN, nb, w.eqp, s.stream, pl.small_moduli, pl.fold, xq_ready);
+        const size_t six = in && in->six ? in->six : LN, siy = in && in->siy ? in->siy : LN;
+        const u32 Lin = in && in->drop_from ? in->drop_from->L : L;
+        ProfScope ps(s, PIEHIP_K_EXPAND, W * nb * (2.0 * Lin + 2.0 * (in && in->drop_from && !in->x_drop ? L : Lin) + 4.0 * M));
+        bool ok = true;
+        if (in && in->drop_from)   // chain limbs, fused: the limb drop in the conversions' load phase
+            ok = launch_expand_both_drop(in->drop_from->d_dc, cx.d_dc, N, Lin, L, x, sx, six, in->x_drop, y, sy, siy, nb, w.eqp, s.stream);
+        else if (in && in->plain)  // chain limbs, fallback: operands the drop kernel / an unfolded inverse transform left
+            ok = launch_expand_both_plain(cx.d_dc, N, L, x, sx, six, y, sy, siy, nb, w.eqp, s.stream, pl.small_moduli, pl.fold);
+        else
+            launch_expand_both(cx.d_dc, N, L, x, sx, y, sy, LN, nb, w.eqp, s.stream, pl.small_moduli, pl.fold, xq_ready);
+        assert(ok);
+        (void)ok;
     }
     // the QP operands and the tensor result never leave the library: lane order, no LDS transposes
     {
@@ -102,14 +119,14 @@ void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size
     } else {
         {
             ProfScope ps(s, PIEHIP_K_TENSOR, W * nb * 7.0 * M);
-            launch_tensor(h->d_dc, N, M, w.eqp, w.dqp, nb, s.stream, pl.small_moduli);
+            launch_tensor(cx.d_dc, N, M, w.eqp, w.dqp, nb, s.stream, pl.small_moduli);
         }
         ntt(s, w.dqp, nb * 3 * M, 0, M, true, true, true);
     }
     if (relin) {
         {
             ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, s.stream, pl.small_moduli, pl.fold, false, eval_q);
+            launch_scale_round(cx.d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, s.stream, pl.small_moduli, pl.fold, false, eval_q);
         }
         NttExtra ex;
         ex.lazy_out = true;  // the key-switch MAC adds d01 into its accumulator before reducing
@@ -130,25 +147,25 @@ void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size
     } else if (eval_q3) {
         {
             ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * (M - L) + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, w.t3, 3 * LN, w.t3 + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true, true, true);
+            launch_scale_round(cx.d_dc, N, L, w.dqp, nb, w.t3, 3 * LN, w.t3 + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true, true, true);
         }
         NttExtra ex;
         ex.lazy_out = true;  // the finishing kernel adds the own-limb term into its accumulator before reducing
         ntt(s, w.t3, nb * 3 * L, 0, L, false, true, true, &ex);
         if (out_is_result) s.gate();
         ProfScope ps(s, PIEHIP_K_DEG2_FINISH, W * nb * 11.0 * L);
-        launch_deg2_finish(h->d_dc, N, L, w.t3, w.eqp, M, mask, out, nb, s.stream, pl.lane_T, pl.lane_kp, s.mask_div);
+        launch_deg2_finish(cx.d_dc, N, L, w.t3, w.eqp, M, mask, out, nb, s.stream, pl.lane_T, pl.lane_kp, s.mask_div);
     } else {
         u64 *t = deg2 ? w.t3 : out;
         {
             ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(h->d_dc, N, L, w.dqp, nb, t, 3 * LN, t + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true);
+            launch_scale_round(cx.d_dc, N, L, w.dqp, nb, t, 3 * LN, t + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true);
         }
         ntt(s, t, nb * 3 * L, 0, L, false, false, true);
         if (deg2) {
             if (out_is_result) s.gate();
             ProfScope ps(s, PIEHIP_K_MASK, W * nb * 3 * 3.0 * L);
-            launch_ct_mul_plain(h->d_dc, N, L, t, mask, LN, out, nb, s.stream, s.mask_div, 3);
+            launch_ct_mul_plain(cx.d_dc, N, L, t, mask, LN, out, nb, s.stream, s.mask_div, 3);
         }
     }
 }
@@ -164,21 +181,21 @@ void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size
 // nothing is reduced, and its (smaller) download still travels under the next group's evaluation.
 void enqueue_mod_reduce(Sched &s, u64 *full, u32 rows, u32 keep, u64 *out, bool out_is_result, u32 comps)
 {
-    piehip_ctx *h = s.h;
-    const u32 N = h->hp.N, L = h->hp.L;
+    const ChainCtx &cx = *s.cx;
+    const u32 N = cx.N, L = cx.L;
     const double W = 8.0 * N;
     {
         ProfScope ps(s, PIEHIP_K_RESULT_NTT_INV, 2 * W * rows * comps * L);
-        launch_ntt(h->plan, full, rows * comps * L, 0, L, true, s.stream);
+        launch_ntt(*cx.plan, full, rows * comps * L, 0, L, true, s.stream);
     }
     if (out_is_result) s.gate();
     {
         ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * rows * comps * (L + keep));
-        launch_limb_drop(h->d_dc, N, L, keep, full, out, rows * comps, s.stream);
+        launch_limb_drop(cx.d_dc, N, L, keep, full, out, rows * comps, s.stream);
     }
     {
         ProfScope ps(s, PIEHIP_K_RESULT_NTT_FWD, 2 * W * rows * comps * keep);
-        launch_ntt(h->plan, out, rows * comps * keep, 0, keep, false, s.stream);
+        launch_ntt(*cx.plan, out, rows * comps * keep, 0, keep, false, s.stream);
     }
 }
 
@@ -209,7 +226,11 @@ int ensure_run_queues(piehip_ctx *h, u32 ng)
 }
 
 // stage A of the run being enqueued hands operand X of the first product over in lane order, inside the QP operand array
-bool run_x_direct(const piehip_ctx *h) { return h->K > 1 && h->nq > 1 && h->plan.x_direct; }
+// (not with chain limbs below L: the dropped X is not what stage A computed, every accumulator goes to d_acc)
+bool run_x_direct(const piehip_ctx *h) { return h->K > 1 && h->nq > 1 && h->plan.x_direct && h->chain_limbs >= h->hp.L; }
+
+// the product chain of run() works on the level context (chain limbs below L; a handle with K = 1 has no product: nothing changes)
+bool run_on_level(const piehip_ctx *h) { return h->K >= 2 && h->level && h->chain_limbs < h->hp.L; }
 
 // bin layers of queue group g of ng.  Two groups take 4/7 and 3/7 of the layers: measured 3.5 % faster than equal halves at
 // b = 14 (8 + 6: the ragged transform launches of the two queues fit the workgroup slots better than 7 + 7).
@@ -239,7 +260,9 @@ static void enqueue_run_bins(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_
 {
     piehip_ctx *h = s.h;
     const u32 keep = h->res_limbs, nq = h->nq;
-    if (keep >= h->hp.L) {
+    // chain limbs: the chain hands over rows of the level context, and the reduction -- from its Lc limbs down to keep -- runs there
+    const ChainCtx &cx = run_on_level(h) ? h->level->cx : h->cx;
+    if (keep >= cx.L) {
         enqueue_run_bins_full(s, b0, nb, results, chain_only);
         return;
     }
@@ -248,7 +271,9 @@ static void enqueue_run_bins(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_
     enqueue_run_bins_full(chain, b0, nb, h->d_full, chain_only);
     const size_t r0 = (size_t)b0 * nq;
     const u32 comps = h->res_comps();
-    enqueue_mod_reduce(s, h->d_full + r0 * comps * h->LN(), nb * nq, keep, results + r0 * h->res_ct_words(), true, comps);
+    s.cx = &cx;
+    enqueue_mod_reduce(s, h->d_full + r0 * comps * cx.LN(), nb * nq, keep, results + r0 * h->res_ct_words(), true, comps);
+    s.cx = &h->cx;
 }
 static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_only)
 {
@@ -288,9 +313,83 @@ static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool c
     }
     enqueue_chain_bins(s, b0, layers, results);
 }
+// Chain limbs (include/piehip.h): the chain of a handle whose setting is below L.  The accumulators are
+// inverse-transformed on the handle's L limbs, dropped to Lc and multiplied on the level context: its constants, plan and tables, the
+// limb prefixes of keys and masks, the workspace viewed in rows of Lc limbs (rows of two queue groups stay apart as they do at L: both
+// groups take the same view).  Where the fused conversion applies the drop happens in its load phase; otherwise a drop kernel rewrites
+// the accumulators in place and every conversion of the chain takes plain operands.  results[b][nq][comps][Lc][N].
+static void enqueue_chain_bins_level(Sched &s, u32 b0, u32 layers, u64 *results)
+{
+    piehip_ctx *h = s.h;
+    const LevelCtx &lv = *h->level;
+    const ChainCtx &cx = lv.cx;
+    const NttPlan &pl = lv.plan;
+    const u32 N = h->hp.N, L = h->hp.L, K = h->K, nq = h->nq, Lc = cx.L, Mc = cx.M;
+    const size_t LN = h->LN(), LcN = cx.LN();
+    const double W = 8.0 * N;
+    const size_t r0 = (size_t)b0 * nq;
+    const u32 nb = layers * nq;
+    MulWs w = h->ws;
+    w.nb = nb;
+    w.eqp += r0 * 4 * Mc * N;
+    w.dqp += r0 * 3 * Mc * N;
+    w.d01 += r0 * 2 * LcN;
+    w.d2c += r0 * LcN;
+    w.dig += r0 * Lc * LcN;
+    if (w.t3) w.t3 += r0 * 3 * LcN;
+    u64 *acc = h->d_acc + r0 * K * 2 * LN;   // stage A's rows: the parent's strides
+    u64 *prod = h->d_prod ? h->d_prod + r0 * 2 * LcN : nullptr;
+    const bool deg2 = h->res_comps() == 3;
+    u64 *out = results + r0 * h->res_comps() * LcN;
+    const u64 *masks = ((deg2 ? pl.result_eval_q : pl.lane_order) ? lv.masks_sigma : lv.masks) + (size_t)b0 * LcN;
+    s.mask_div = nq;
+    s.key_group = (nq > 1 && h->d_evkq && h->evkq_n == nq) ? nq : 1;
+    ntt(s, acc, nb * K * 2 * L, 0, L, true, false, true);   // (the parent's context: s.cx)
+    // the fused conversion: folded rings whose level moduli take the column-accumulator arithmetic, pairs it is built for
+    const bool fused = h->plan.fold && pl.fold && pl.small_moduli && pl.xq_reuse && expand_both_drop_applies(L, Lc);
+    if (!fused) {
+        ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * nb * K * 2 * (L + Lc));
+        launch_chain_drop(h->d_dc, N, L, Lc, acc, nb * K * 2, s.stream, h->plan.fold);
+    }
+    s.cx = &cx;
+    MulIn in;
+    in.six = in.siy = LN;
+    if (fused)
+        in.drop_from = &h->cx, in.x_drop = true;
+    else
+        in.plain = true;
+    NttExtra ex;
+    ex.copy_out = w.eqp;
+    ex.copy_K = 1;
+    ex.copy_L = Lc;
+    ex.copy_M = Mc;
+    const u64 *x = acc;
+    size_t sx = (size_t)K * 2 * LN;
+    for (u32 hf = 1; hf < K; hf++) {
+        const bool last = hf + 1 == K;
+        // the dropped X of the first product is not what the QP array could hold in EVALUATION form: xq_ready only from the second on
+        enqueue_mul(s, w, x, sx, acc + (size_t)hf * 2 * LN, (size_t)K * 2 * LN, nb, !(last && deg2), last ? masks : nullptr, last ? out : prod,
+                    fused && hf > 1, last, &in);
+        if (!last) {
+            if (fused)
+                ntt(s, prod, nb * 2 * Lc, 0, Lc, true, false, true, &ex);
+            else
+                ntt(s, prod, nb * 2 * Lc, 0, Lc, true, false, false);   // unfolded: plain coefficients, like the dropped accumulators
+            x = prod;
+            sx = 2 * LcN;
+            in.six = LcN;
+            in.x_drop = false;
+        }
+    }
+    s.cx = &h->cx;
+}
 static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
 {
     piehip_ctx *h = s.h;
+    if (run_on_level(h)) {
+        enqueue_chain_bins_level(s, b0, layers, results);
+        return;
+    }
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M, K = h->K, nq = h->nq;
     const size_t LN = h->LN();
     const double W = 8.0 * N;
@@ -372,6 +471,8 @@ int piehip::run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *
         if (!h->ws.t3 || h->res_cap_comps < 3)
             return fail(PIEHIP_ESTATE, "run: no rows for three-component results (an earlier allocation failed: piehip_set_result_relin)");
     }
+    if (run_on_level(h) && ((h->K > 2 || h->res_relin) ? !(h->level->has_evk || (h->d_evkq && h->level->evkq)) : false))
+        return fail(PIEHIP_ESTATE, "run: no key on the level context (an earlier allocation failed: piehip_set_chain_limbs)");
     if (h->res_limbs < h->hp.L && !h->d_full) return fail(PIEHIP_ESTATE, "run: no rows for the result reduction (an earlier allocation failed: piehip_set_result_limbs)");
     for (u32 q = 0; q < h->nq && !chain_only; q++) {
         if (h->query[q].idx && h->query[q].minus) continue;
@@ -500,6 +601,8 @@ int piehip_set_graph(piehip_handle h, int on)
         return fail(PIEHIP_ESTATE, "set_graph: the captured graph hands out full results (piehip_set_result_limbs is below L)");
     if (on && !h->res_relin)
         return fail(PIEHIP_ESTATE, "set_graph: the captured graph relinearises its results (piehip_set_result_relin is off)");
+    if (on && h->chain_limbs < h->hp.L)
+        return fail(PIEHIP_ESTATE, "set_graph: the captured graph runs the product chain on every limb (piehip_set_chain_limbs is below L)");
     if (on && h->slice.on) return fail(PIEHIP_ESTATE, "set_graph: a query-sliced handle runs in two halves (piehip_run_slice, piehip_run_chain): no captured graph");
     h->use_graph = on != 0;
     if (!on) drop_graph(h);

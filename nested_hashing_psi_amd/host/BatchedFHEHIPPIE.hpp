@@ -108,7 +108,25 @@ public:
         listStale.assign(nq, false);
         PieContext::check(piehip_get_result_limbs(cc->handle(), &resLimbs));
         PieContext::check(piehip_get_result_components(cc->handle(), &resComps));
+        PieContext::check(piehip_get_chain_limbs(cc->handle(), &chainLimbs_));
     }
+
+    // Chain limbs (include/piehip.h "Chain limbs"): from the next run() on every accumulator is dropped to its first Lc limbs behind
+    // stage A and the product chain runs on the level context of those limbs; the result ciphertexts are
+    // [resultComponents][min(keep, Lc)][N].  Lc = towers() is the default.  The noise budget is the caller's business.  Refusals come
+    // as the library's: std::invalid_argument for Lc = 0 or Lc > L, std::runtime_error for a handle that cannot take the setting.
+    // The page-locked result array follows the setting; result lists of earlier runs are dropped.
+    void setChainLimbs(uint32_t Lc)
+    {
+        PieContext::check(piehip_set_chain_limbs(cc->handle(), Lc));
+        PieContext::check(piehip_host_buffers_q(cc->handle(), 0, nullptr, nullptr, &pinRes));
+        chainLimbs_ = Lc;
+        std::fill(listStale.begin(), listStale.end(), false);
+        for (auto &l : lists)
+            for (auto &c : l) c.limbs.clear();
+    }
+    uint32_t chainLimbs() const { return chainLimbs_; }
+    uint32_t resultRowLimbs() const { return K >= 2 && chainLimbs_ < resLimbs ? chainLimbs_ : resLimbs; }   // min(keep, Lc); K = 1: keep
 
     // Result limbs (include/piehip.h "Result limbs"): from the next run() on the result ciphertexts are [2][keep][N], on the first
     // `keep` primes of the chain.  The page-locked result array follows the setting; result lists of earlier runs are dropped.
@@ -256,7 +274,7 @@ public:
         return lists[q];
     }
     const uint64_t *resultTowers(uint32_t q, uint32_t i) const { return pinRes + ((size_t)i * nq + q) * resultWords(); }  // rows [bin layer][query]
-    size_t resultWords() const { return (size_t)resComps * resLimbs * cc->ringDimension(); }  // one result ciphertext, [resultComponents][resultLimbs][N]
+    size_t resultWords() const { return (size_t)resComps * resultRowLimbs() * cc->ringDimension(); }  // one result ciphertext, [resultComponents][min(resultLimbs, chainLimbs)][N]
 
 private:
     struct QueryState {
@@ -286,6 +304,7 @@ private:
     std::vector<QueryState> st;
     uint64_t *pinRes = nullptr;  // [b][nq][2][resLimbs][N], page-locked, owned by the library
     uint32_t resLimbs = 0;       // piehip_set_result_limbs: L unless setResultLimbs said otherwise
+    uint32_t chainLimbs_ = 0;    // piehip_set_chain_limbs: L unless setChainLimbs said otherwise
     uint32_t resComps = 2;       // piehip_get_result_components: 3 after setResultRelin(false) with K >= 2
     std::vector<std::vector<LimbCt>> lists;
     std::vector<bool> listStale;
@@ -363,6 +382,9 @@ public:
     // which decrypt as they are, and K = 2 needs no EvalMult key.  The reference operator relinearises (OpenFHE's default).  Default: on.
     void setResultRelin(bool on) { staged.setResultRelin(on); }
     uint32_t resultComponents() const { return staged.resultComponents(); }
+    // the product chain on the first Lc limbs of the chain (include/piehip.h "Chain limbs"): rows of min(keep, Lc) limbs
+    void setChainLimbs(uint32_t Lc) { staged.setChainLimbs(Lc); }
+    uint32_t chainLimbs() const { return staged.chainLimbs(); }
 
     // .hpp:40-43, [K][E] ciphertexts
     void setIndex(std::vector<std::vector<LimbCt>> &&indexMatrix) { staged.setIndex(0, std::move(indexMatrix)); }
@@ -453,6 +475,9 @@ public:
     // ... and their relinearisation (see BatchedFHEHIPPIE::setResultRelin): rows [bin layer][query] of [3][keep][N] when off
     void setResultRelin(bool on) { staged.setResultRelin(on); }
     uint32_t resultComponents() const { return staged.resultComponents(); }
+    // the product chain on the first Lc limbs of the chain (include/piehip.h "Chain limbs"): rows of min(keep, Lc) limbs
+    void setChainLimbs(uint32_t Lc) { staged.setChainLimbs(Lc); }
+    uint32_t chainLimbs() const { return staged.chainLimbs(); }
 
 private:
     PieContext &cc;

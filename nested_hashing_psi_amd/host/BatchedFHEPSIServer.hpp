@@ -118,9 +118,13 @@ public:
     {
     }
     // one channel per client; their queries are evaluated together (at most 8: the library's batch limit)
+    // chainLimbs (include/piehip.h "Chain limbs"; 0 = all L, the reference's behaviour): the product chain runs on the first chainLimbs
+    // limbs of the clients' chain, and the result messages carry min(keep, chainLimbs) limbs, framed with that count: the clients
+    // decrypt in the context of those limbs.  The noise budget is the operator's business; std::invalid_argument from the set-up
+    // phase when it exceeds the clients' L.
     BatchedFHEPSIServer(const std::vector<int> &channel_fds, const std::vector<uint64_t> &serverSet, const HashTableParameter &htParams,
-                        uint64_t hashSeed = 987654321)
-        : fds(channel_fds), serverSet(serverSet), ht(htParams), hashSeed(hashSeed)
+                        uint64_t hashSeed = 987654321, uint32_t chainLimbs = 0)
+        : fds(channel_fds), serverSet(serverSet), ht(htParams), hashSeed(hashSeed), chainLimbs(chainLimbs)
     {
         if (fds.empty() || fds.size() > 8) throw std::invalid_argument("between one and eight client channels");
         std::random_device rd;
@@ -171,6 +175,7 @@ public:
                 // the timed offline phase does not pay for hipMalloc
                 PieContext::check(piehip_set_query_batch(cc->handle(), nq));
                 if (resultLimbs) PieContext::check(piehip_set_result_limbs(cc->handle(), resultLimbs));
+                if (chainLimbs) PieContext::check(piehip_set_chain_limbs(cc->handle(), chainLimbs));
                 PieContext::check(piehip_reserve(cc->handle(), serverSet.size(), ht.numberOfSimpleHashFunctions, ht.eachSimpleTableSize,
                                                  ht.numberOfCuckooHashFunctions, ht.maxItemsPerPosition, ht.eachCuckooTableSize, 0,
                                                  ht.maxItemsPerPosition));
@@ -236,7 +241,8 @@ public:
         PieContext::check(piehip_run_staged(cc->handle(), pinRes));
         PieContext::check(piehip_run_host_wait(cc->handle()));
         onlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
-        const uint32_t keep = resultLimbs ? resultLimbs : L;   // limbs per result ciphertext as it leaves the device and the server
+        uint32_t keep = resultLimbs ? resultLimbs : L;   // limbs per result ciphertext as it leaves the device and the server
+        if (chainLimbs && chainLimbs < keep) keep = chainLimbs;   // (K >= 2 here: a Cuckoo table has more than one hash function)
         const size_t rct = 2 * (size_t)keep * N;
         for (uint32_t q = 0; q < nq; q++) sendResults(fds[q], pinRes + q * rct, b, nq * rct, keep, N);   // rows are [bin layer][query]
     }
@@ -248,6 +254,7 @@ private:
     uint64_t hashSeed;
     uint64_t evictSeed = 0, shuffleSeed = 0, maskSeed = 0;
     uint32_t resultLimbs = 0;   // setResultLimbs: 0 = every limb
+    uint32_t chainLimbs = 0;    // the constructor's option: 0 = every limb
     std::vector<uint64_t> qMod;
     std::unique_ptr<PieContext> cc;
 };

@@ -112,6 +112,15 @@ class PieContext:
         except RuntimeError:
             pass
 
+    def setChainLimbs(self, Lc):
+        """the product chain of run() on the first Lc limbs of the chain (piehip_set_chain_limbs; L = the default, as ever)"""
+        _check(lib().piehip_set_chain_limbs(self._h, int(Lc)))
+
+    def chainLimbs(self):
+        n = C.c_uint32()
+        _check(lib().piehip_get_chain_limbs(self._h, C.byref(n)))
+        return n.value
+
     # -- tables (for cross-checks)
     def psi(self, mi):
         v = C.c_uint64()
@@ -488,8 +497,21 @@ class BatchedFHEHIPPIE:
         _check(lib().piehip_get_result_components(self.cc._h, C.byref(n)))
         return n.value
 
+    def setChainLimbs(self, Lc):
+        """the product chain of run() works on the first Lc limbs of the chain (piehip_set_chain_limbs; L = as ever): every accumulator
+        is dropped to Lc limbs behind stage A and every product runs on the level context (N, Lc, t, q[:Lc], p[:Lc+1]).  Result arrays
+        are [..][min(resultLimbs, Lc)][N] and decrypt with client.decrypt(.., limbs=that).  The noise budget is the caller's business
+        (include/piehip.h "Chain limbs").  Page-locked result arrays follow the setting: ask hostBuffers() again after changing it."""
+        self.cc.setChainLimbs(Lc)
+        self._results = None
+
+    def chainLimbs(self):
+        return self.cc.chainLimbs()
+
     def _res_shape(self):
         nq, keep, nc = self.nq, self.resultLimbs, self.resultComponents()
+        if self.K >= 2:
+            keep = min(keep, self.chainLimbs())
         return (self.b, nc, keep, self.cc.N) if nq == 1 else (self.b, nq, nc, keep, self.cc.N)
 
     def hostBuffers(self, query=0):

@@ -1,5 +1,5 @@
 """per-kernel comparison of two hipcc -S listings of one file (before and after a change): python tools/isa_compare.py before.s after.s
-A kernel counts as identical when its instructions, its kernel descriptor and its metadata entry are (the compilation-unit id,
+Kernels that only the second listing has are listed with their figures; one that only the first has is an error.  A kernel counts as identical when its instructions, its kernel descriptor and its metadata entry are (the compilation-unit id,
 __hip_cuid_<hash>, neutralised); for the others: tools/isa_regs.py's columns, waves per SIMD, instruction totals and the counts of the
 memory and multiplier instructions, each as before->after where it changed."""
 import collections
@@ -53,11 +53,20 @@ def waves(v):
 
 pa, pt = kernels(sys.argv[1])
 he, ht = kernels(sys.argv[2])
-assert list(pa) == list(he), "kernel sets differ"
+gone = [k for k in pa if k not in he]
+new = [k for k in he if k not in pa]
+assert not gone, "kernels of the first listing missing from the second: %s" % gone
 same = [k for k in pa if pa[k] == he[k]]
 diff = [k for k in pa if pa[k] != he[k]]
 print("%d kernels, %d with identical listing (instructions, kernel descriptor, metadata), %d differ" % (len(pa), len(same), len(diff)))
 print("whole listing identical" if pt == ht else "whole listing differs")
+if new:   # kernels only the second listing has: their register figures and instruction totals
+    print()
+    print("%d kernels only in the second listing:" % len(new))
+    for k in new:
+        r, c = he[k]['regs'], mix(he[k]['body'])
+        print("  %-52s vgpr %3d spill %d sgpr %3d scratch %3d waves %d instructions %5d  v_cndmask_b32 %d" % (
+            short(k), r[0], r[1], r[2], r[3], waves(r[0]), sum(c.values()), c['v_cndmask_b32']))
 print()
 print("identical, by kernel template: " + ", ".join("%s x %d" % kv for kv in collections.Counter(re.sub(r'<.*', '', short(k)) for k in same).items()))
 print()
