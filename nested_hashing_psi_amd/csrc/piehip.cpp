@@ -300,11 +300,35 @@ int piehip_create(piehip_handle *out, uint32_t N, uint32_t L, uint64_t t, const 
     return PIEHIP_OK;
 }
 
-// a handle that borrowed its database and key (piehip_attach_database) lets go of them: pointers only
+// The lane-ordered twin of the `rows` polynomials at src, under cx's map: allocated if absent, rows [first, first + count) permuted
+// into it on the handle's stream.  Nothing where the context has no lane order.
+static int lane_twin(piehip_ctx *h, const ChainCtx &cx, const u64 *src, u64 **twin, size_t rows, size_t first, size_t count)
+{
+    if (!cx.plan->lane_order) return PIEHIP_OK;
+    if (!*twin) {
+        int rc = dev_alloc(twin, rows * cx.N);
+        if (rc) return rc;
+    }
+    launch_permute(cx.N, src + first * cx.N, cx.d_sigma_inv, *twin + first * cx.N, (u32)count, h->stream);
+    return PIEHIP_OK;
+}
+static int lane_twin(piehip_ctx *h, const ChainCtx &cx, const u64 *src, u64 **twin, size_t rows) { return lane_twin(h, cx, src, twin, rows, 0, rows); }
+static void chain_data_free(ChainCtx &cx)
+{
+    for (u64 **p : {&cx.evk, &cx.evk_sigma, &cx.evkq, &cx.evkq_sigma, &cx.masks, &cx.masks_sigma}) dev_free(p);
+}
+
+// what a handle that borrows its database takes of its owner by reference (piehip_attach_database), and lets go of again (null)
+static void share_database(piehip_ctx *h, const piehip_ctx *owner)
+{
+    const ChainCtx from = owner ? owner->cx : ChainCtx();
+    h->cx.evk = from.evk, h->cx.evk_sigma = from.evk_sigma, h->cx.masks = from.masks, h->cx.masks_sigma = from.masks_sigma;
+    h->d_db = owner ? owner->d_db : nullptr;
+}
 static void detach_database(piehip_ctx *h)
 {
     if (!h->db_borrowed) return;
-    h->d_evk = h->d_evk_sigma = h->d_db = h->d_masks = h->d_masks_sigma = nullptr;
+    share_database(h, nullptr);
     h->db_borrowed = false;
     if (h->db_owner && h->db_owner->db_borrowers) h->db_owner->db_borrowers--;
     h->db_owner = nullptr;
@@ -320,21 +344,15 @@ int piehip_destroy(piehip_handle h)
     for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
     detach_database(h);
     slice_free(h);
-    dev_free(&h->d_evk);
     dev_free(&h->d_db);
-    dev_free(&h->d_masks);
+    chain_data_free(h->cx);   // (what was borrowed is no longer there)
     for (Query &s : h->query) {
         dev_free(&s.idx_own);
         dev_free(&s.minus_own);
     }
     free_workspace(h);
     for (void *p : h->dev_tables) (void)hipFree(p);
-    for (auto &kv : h->levels)
-        for (u64 **p : {&kv.second->evk, &kv.second->evk_sigma, &kv.second->evkq, &kv.second->evkq_sigma, &kv.second->masks, &kv.second->masks_sigma}) dev_free(p);
-    dev_free(&h->d_evk_sigma);
-    dev_free(&h->d_evkq);
-    dev_free(&h->d_evkq_sigma);
-    dev_free(&h->d_masks_sigma);
+    for (auto &kv : h->levels) chain_data_free(kv.second->cx);
     dev_free(&h->d_hash_tbl);
     dev_free(&h->arena);
     for (auto &kv : h->rotkeys) (void)hipFree(kv.second);
@@ -392,12 +410,13 @@ int piehip_get_slot_positions(piehip_handle h, uint32_t *pos)
 // twin, if the handle has one: they follow it.  Queued on the handle's stream; the caller waits.
 static int fill_unloaded_key_slots(piehip_ctx *h)
 {
-    const size_t words = (size_t)h->hp.L * 2 * h->LN();
-    for (u32 i = 0; i < h->evkq_n && h->d_evkq && h->d_evk; i++) {
+    const ChainCtx &c = h->cx;
+    const size_t words = c.key_words();
+    for (u32 i = 0; i < h->evkq_n && c.evkq && c.evk; i++) {
         if (h->evkq_loaded >> i & 1) continue;
-        HIPCHK(hipMemcpyAsync(h->d_evkq + i * words, h->d_evk, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
-        if (h->plan.lane_order && h->d_evkq_sigma)
-            HIPCHK(hipMemcpyAsync(h->d_evkq_sigma + i * words, h->d_evk_sigma, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(c.evkq + i * words, c.evk, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+        if (h->plan.lane_order && c.evkq_sigma)
+            HIPCHK(hipMemcpyAsync(c.evkq_sigma + i * words, c.evk_sigma, words * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
     }
     return PIEHIP_OK;
 }
@@ -409,39 +428,30 @@ int piehip_load_relin_key(piehip_handle h, const uint64_t *evk)
     if (h->db_borrowed) return fail(PIEHIP_EINVAL, "this handle uses another handle's key and database (piehip_attach_database)");
     if (h->db_borrowers) return fail(PIEHIP_ESTATE, "the key cannot be reloaded while other handles are attached to this one");
     HIPCHK(hipSetDevice(h->device));
-    const size_t words = (size_t)h->hp.L * 2 * h->LN();
-    if (!h->d_evk) {
-        int rc = dev_alloc(&h->d_evk, words);
-        if (rc) return rc;
-    }
+    ChainCtx &c = h->cx;
+    const size_t words = c.key_words();
+    int rc;
+    if (!c.evk && (rc = dev_alloc(&c.evk, words))) return rc;
     // on the handle's stream: NEED() has ordered it behind every run still in flight (a null-stream copy would not be)
-    HIPCHK(hipMemcpyAsync(h->d_evk, evk, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(c.evk, evk, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->plan.lane_order) {  // lane-ordered copy for the key-switch MAC
-        if (!h->d_evk_sigma) {
-            int rc = dev_alloc(&h->d_evk_sigma, words);
-            if (rc) return rc;
-        }
-        launch_permute(h->hp.N, h->d_evk, h->d_sigma_inv, h->d_evk_sigma, h->hp.L * 2 * h->hp.L, h->stream);
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    int rc = fill_unloaded_key_slots(h);
-    if (rc) return rc;
-    if (h->d_evkq) HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = lane_twin(h, c, c.evk, &c.evk_sigma, c.L * 2 * c.L))) return rc;  // for the key-switch MAC
+    if (h->plan.lane_order) HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = fill_unloaded_key_slots(h))) return rc;
+    if (c.evkq) HIPCHK(hipStreamSynchronize(h->stream));
     return level_sync(h);
 }
 
-// lane-ordered copy of the mask plaintexts for the fused mask multiply of the last key switch
+// lane-ordered copy of the mask plaintexts for the fused mask multiply of the last key switch (freed with the run buffers when the
+// shape changes); with chain limbs, the level context's copies follow every mask load
 extern "C++" int piehip::make_masks_sigma(piehip_ctx *h)
 {
-    if (!h->plan.lane_order) return level_sync(h);   // (chain limbs: the level context's copies follow every mask load)
-    if (!h->d_masks_sigma) {  // freed with the run buffers when the shape changes
-        int rc = dev_alloc(&h->d_masks_sigma, (size_t)h->b * h->LN());
-        if (rc) return rc;
+    int rc = lane_twin(h, h->cx, h->cx.masks, &h->cx.masks_sigma, (size_t)h->b * h->hp.L);
+    if (rc) return rc;
+    if (h->plan.lane_order) {
+        hipError_t e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return fail(PIEHIP_EHIP, std::string("mask permutation: ") + hipGetErrorString(e));
     }
-    launch_permute(h->hp.N, h->d_masks, h->d_sigma_inv, h->d_masks_sigma, h->b * h->hp.L, h->stream);
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(PIEHIP_EHIP, std::string("mask permutation: ") + hipGetErrorString(e));
     return level_sync(h);
 }
 
@@ -496,20 +506,20 @@ extern "C++" int piehip::alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, b
     if (with_db && h->db_borrowers)
         return fail(PIEHIP_ESTATE, "a database cannot be loaded while other handles are attached to this one (destroy or re-home them first)");
     const size_t LN = h->LN();
-    if (with_db && h->K == K && h->b == b && h->E == E && h->d_db && h->d_masks && h->d_acc && h->d_out && h->ws.nb == b * h->nq) {
+    if (with_db && h->K == K && h->b == b && h->E == E && h->d_db && h->cx.masks && h->d_acc && h->d_out && h->ws.nb == b * h->nq) {
         // same shape as the database being replaced (or reserved): keep the 0.5 GiB of buffers (hipFree + hipMalloc cost
         // ~10 ms); the inputs of the previous database are stale
         for (Query &s : h->query) s.idx = nullptr;
         return PIEHIP_OK;
     }
     dev_free(&h->d_db);
-    dev_free(&h->d_masks);
-    dev_free(&h->d_masks_sigma);
+    dev_free(&h->cx.masks);
+    dev_free(&h->cx.masks_sigma);
     free_workspace(h);
     h->K = h->b = h->E = 0;
     int rc;
     if (with_db && (rc = dev_alloc(&h->d_db, (size_t)K * b * E * LN))) return rc;
-    if (with_db && (rc = dev_alloc(&h->d_masks, (size_t)b * LN))) return rc;
+    if (with_db && (rc = dev_alloc(&h->cx.masks, (size_t)b * LN))) return rc;
     if ((rc = alloc_workspace(h, K, b))) return rc;
     h->K = K;
     h->b = b;
@@ -532,7 +542,7 @@ int piehip_load_db(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, const ui
     if (rc) return rc;
     const size_t LN = h->LN();
     HIPCHK(hipMemcpyAsync(h->d_db, pts, sizeof(u64) * (size_t)K * b * E * LN, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_masks, masks, sizeof(u64) * (size_t)b * LN, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->cx.masks, masks, sizeof(u64) * (size_t)b * LN, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return make_masks_sigma(h);
 }
@@ -552,28 +562,19 @@ int piehip_attach_database(piehip_handle h, piehip_handle owner)
     join_pending(owner);
     if (owner->db_borrowed) return fail(PIEHIP_EINVAL, "attach_database: the owner itself borrows its database");
     // (an owner that hands out unrelinearised results of a K = 2 database runs without a key: so may its slots, each by its own setting)
-    if (!owner->d_db || (!owner->d_evk && owner->K > 1 && !(owner->K == 2 && !owner->res_relin))) return fail(PIEHIP_ESTATE, "attach_database: the owner has no key or no database yet");
+    if (!owner->d_db || (!owner->cx.evk && owner->K > 1 && !(owner->K == 2 && !owner->res_relin))) return fail(PIEHIP_ESTATE, "attach_database: the owner has no key or no database yet");
     if (owner->device != h->device) return fail(PIEHIP_EINVAL, "attach_database: handles on different devices");
     if (owner->hp.N != h->hp.N || owner->hp.L != h->hp.L || owner->hp.t != h->hp.t || owner->hp.moduli != h->hp.moduli)
         return fail(PIEHIP_EINVAL, "attach_database: handles with different parameters");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(owner->stream));  // uploads of the owner's key / database have landed
-    if (!h->db_borrowed) {
-        dev_free(&h->d_evk);
-        dev_free(&h->d_evk_sigma);
-        dev_free(&h->d_db);
-        dev_free(&h->d_masks);
-        dev_free(&h->d_masks_sigma);
-    }
+    if (!h->db_borrowed)
+        for (u64 **p : {&h->cx.evk, &h->cx.evk_sigma, &h->d_db, &h->cx.masks, &h->cx.masks_sigma}) dev_free(p);
     detach_database(h);
     h->K = h->b = h->E = 0;
     int rc = alloc_run_buffers(h, owner->K, owner->b, owner->E, false);
     if (rc) return rc;
-    h->d_evk = owner->d_evk;
-    h->d_evk_sigma = owner->d_evk_sigma;
-    h->d_db = owner->d_db;
-    h->d_masks = owner->d_masks;
-    h->d_masks_sigma = owner->d_masks_sigma;
+    share_database(h, owner);
     h->db_borrowed = true;
     h->db_owner = owner;
     owner->db_borrowers++;
@@ -641,7 +642,7 @@ int piehip_load_db_slots(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, ui
     hipError_t e = hipMemcpy(d_s, slots, sizeof(int64_t) * npt * B, hipMemcpyHostToDevice);
     if (e == hipSuccess) rc = encode_on_device(h, d_s, (u32)npt, B, h->d_db);
     if (e == hipSuccess && rc == PIEHIP_OK) e = hipMemcpy(d_s, mask_slots, sizeof(int64_t) * (size_t)b * B, hipMemcpyHostToDevice);
-    if (e == hipSuccess && rc == PIEHIP_OK) rc = encode_on_device(h, d_s, b, B, h->d_masks);
+    if (e == hipSuccess && rc == PIEHIP_OK) rc = encode_on_device(h, d_s, b, B, h->cx.masks);
     (void)hipFree(d_s);
     if (e != hipSuccess) return fail(PIEHIP_EHIP, std::string("load_db_slots: ") + hipGetErrorString(e));
     if (rc) return rc;
@@ -659,7 +660,7 @@ static int encode_bin_layers(piehip_ctx *h, int64_t *d_slots, u32 K, u32 b, u32 
     for (u32 hf = 0; hf < K; hf++)
         if ((rc = encode_on_device(h, d_slots + ((size_t)hf * b + lo) * E * B, nb * E, B, h->d_db + (size_t)hf * nb * E * LN))) return rc;
     launch_mask_slots(h->hp.t, b, B, mask_seed, d_slots, h->stream);
-    if ((rc = encode_on_device(h, d_slots + (size_t)lo * B, nb, B, h->d_masks))) return rc;
+    if ((rc = encode_on_device(h, d_slots + (size_t)lo * B, nb, B, h->cx.masks))) return rc;
     return make_masks_sigma(h);
 }
 
@@ -934,8 +935,8 @@ int piehip_set_query_batch(piehip_handle h, uint32_t nq)
     // caller-owned device pointers of queries outside the new batch are forgotten (they may be freed by now); a later, larger
     // batch must set them again.  Per-query keys are sized by the batch: load them again after a change.
     for (u32 q = nq; q < STAGE_A_MAX_QUERIES; q++) h->query[q].idx = h->query[q].minus = nullptr;
-    dev_free(&h->d_evkq);
-    dev_free(&h->d_evkq_sigma);
+    dev_free(&h->cx.evkq);
+    dev_free(&h->cx.evkq_sigma);
     h->evkq_n = h->evkq_loaded = 0;
     h->nq = nq;
     if (!h->K) return PIEHIP_OK;  // the database's arrival sizes the workspace
@@ -960,20 +961,21 @@ int piehip_load_relin_key_q(piehip_handle h, uint32_t q, const uint64_t *evk)
     if (!evk) return fail(PIEHIP_EINVAL, "null evk");
     if (q >= h->nq) return fail(PIEHIP_EINVAL, "query index outside the batch (piehip_set_query_batch)");
     HIPCHK(hipSetDevice(h->device));
-    const size_t words = (size_t)h->hp.L * 2 * h->LN();
+    ChainCtx &c = h->cx;
+    const size_t words = c.key_words(), rows = c.L * 2 * c.L;   // of one key
     int rc;
-    if (!h->d_evkq || h->evkq_n != h->nq) {
-        dev_free(&h->d_evkq);
-        dev_free(&h->d_evkq_sigma);
+    if (!c.evkq || h->evkq_n != h->nq) {
+        dev_free(&c.evkq);
+        dev_free(&c.evkq_sigma);
         h->evkq_n = h->evkq_loaded = 0;
-        if ((rc = dev_alloc(&h->d_evkq, words * h->nq))) return rc;
-        if (h->plan.lane_order && (rc = dev_alloc(&h->d_evkq_sigma, words * h->nq))) return rc;
+        if ((rc = dev_alloc(&c.evkq, words * h->nq))) return rc;
+        if (h->plan.lane_order && (rc = dev_alloc(&c.evkq_sigma, words * h->nq))) return rc;
         h->evkq_n = h->nq;
         // queries without a key of their own use the handle's (piehip_load_relin_key), if it has one
         if ((rc = fill_unloaded_key_slots(h))) return rc;
     }
-    HIPCHK(hipMemcpyAsync(h->d_evkq + q * words, evk, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    if (h->plan.lane_order) launch_permute(h->hp.N, h->d_evkq + q * words, h->d_sigma_inv, h->d_evkq_sigma + q * words, h->hp.L * 2 * h->hp.L, h->stream);
+    HIPCHK(hipMemcpyAsync(c.evkq + q * words, evk, words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    if ((rc = lane_twin(h, c, c.evkq, &c.evkq_sigma, h->nq * rows, q * rows, rows))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->evkq_loaded |= 1u << q;
     return level_sync(h);
@@ -1102,7 +1104,7 @@ int piehip_get_result_components(piehip_handle h, uint32_t *ncomp)
     return PIEHIP_OK;
 }
 
-// Chain limbs (include/piehip.h): the level context's copies of what the chain reads beside the workspace -- the limb prefix
+// Chain limbs (include/piehip.h): the level context's copies of the keys and masks in the handle's context -- the limb prefix
 // evk[i][c][j], i, j < Lc, of every EvalMult key and the first Lc limbs of the masks, each with its lane-ordered twin where the
 // level's plan has a lane order (its own map: a prefix of a mixed chain may take other routes than the parent).  Copied on the
 // handle's stream whenever the key or the database is set and when the setting changes: 8 and 7 MiB at C3 and as much again for
@@ -1112,48 +1114,37 @@ extern "C++" int piehip::level_sync(piehip_ctx *h)
 {
     LevelCtx *lv = h->level;
     if (!lv || h->chain_limbs >= h->hp.L) return PIEHIP_OK;
-    const u32 N = h->hp.N, L = h->hp.L, Lc = lv->cx.L;
-    const size_t kw = (size_t)Lc * 2 * Lc * N, KW = (size_t)L * 2 * L * N;
-    const bool lane = lv->plan.lane_order;
-    // `rows` rows of L N words -> rows of Lc N words
-    auto prefix = [&](const u64 *src, u64 *dst, size_t rows) {
-        return hipMemcpy2DAsync(dst, (size_t)Lc * N * sizeof(u64), src, (size_t)L * N * sizeof(u64), (size_t)Lc * N * sizeof(u64), rows,
-                                hipMemcpyDeviceToDevice, h->stream);
+    const ChainCtx &top = h->cx;
+    ChainCtx &c = lv->cx;
+    const size_t row = c.LN() * sizeof(u64);
+    // n blocks of `rows` rows of L N words, SW words apart at src -> blocks of as many rows of Lc N words, and their twin.  A copy
+    // that is not made (nothing at src, no memory) is not kept: the level then has none, as the handle has none
+    auto copy = [&](const u64 *src, size_t SW, u32 n, size_t rows, u64 **dst, u64 **twin, size_t *cap) -> int {
+        const size_t bw = rows * c.LN();
+        const bool grow = *cap < n * bw;
+        if (!src || !n || grow) {
+            dev_free(dst);
+            dev_free(twin);
+            *cap = 0;
+        }
+        if (!src || !n) return PIEHIP_OK;
+        int rc = grow ? dev_alloc(dst, n * bw) : PIEHIP_OK;
+        hipError_t e = hipSuccess;
+        for (u32 i = 0; i < n && !rc && e == hipSuccess; i++)
+            e = hipMemcpy2DAsync(*dst + i * bw, row, src + i * SW, top.LN() * sizeof(u64), row, rows, hipMemcpyDeviceToDevice, h->stream);
+        if (e != hipSuccess) rc = fail(PIEHIP_EHIP, std::string("level_sync: ") + hipGetErrorString(e));
+        if (!rc) rc = lane_twin(h, c, *dst, twin, n * rows * c.L);
+        if (rc) {
+            dev_free(dst);
+            dev_free(twin);
+        }
+        if (rc || grow) *cap = rc ? 0 : n * bw;
+        return rc;
     };
     int rc;
-    lv->has_evk = false;
-    if (h->d_evk) {
-        if (!lv->evk && (rc = dev_alloc(&lv->evk, kw))) return rc;
-        if (lane && !lv->evk_sigma && (rc = dev_alloc(&lv->evk_sigma, kw))) return rc;
-        HIPCHK(prefix(h->d_evk, lv->evk, 2 * Lc));
-        if (lane) launch_permute(N, lv->evk, lv->d_sigma_inv, lv->evk_sigma, Lc * 2 * Lc, h->stream);
-        lv->has_evk = true;
-    }
-    if (h->d_evkq && h->evkq_n) {
-        if (lv->evkq_cap < kw * h->evkq_n) {
-            dev_free(&lv->evkq);
-            dev_free(&lv->evkq_sigma);
-            lv->evkq_cap = 0;
-            if ((rc = dev_alloc(&lv->evkq, kw * h->evkq_n))) return rc;
-            if (lane && (rc = dev_alloc(&lv->evkq_sigma, kw * h->evkq_n))) return rc;
-            lv->evkq_cap = kw * h->evkq_n;
-        }
-        for (u32 i = 0; i < h->evkq_n; i++) HIPCHK(prefix(h->d_evkq + i * KW, lv->evkq + i * kw, 2 * Lc));
-        if (lane) launch_permute(N, lv->evkq, lv->d_sigma_inv, lv->evkq_sigma, h->evkq_n * Lc * 2 * Lc, h->stream);
-    }
-    if (h->d_masks && h->b) {
-        const size_t mw = (size_t)h->b * Lc * N;
-        if (lv->masks_cap < mw) {
-            dev_free(&lv->masks);
-            dev_free(&lv->masks_sigma);
-            lv->masks_cap = 0;
-            if ((rc = dev_alloc(&lv->masks, mw))) return rc;
-            if (lane && (rc = dev_alloc(&lv->masks_sigma, mw))) return rc;
-            lv->masks_cap = mw;
-        }
-        HIPCHK(prefix(h->d_masks, lv->masks, h->b));
-        if (lane) launch_permute(N, lv->masks, lv->d_sigma_inv, lv->masks_sigma, h->b * Lc, h->stream);
-    }
+    if ((rc = copy(top.evk, 0, 1, 2 * c.L, &c.evk, &c.evk_sigma, &lv->evk_cap))) return rc;
+    if ((rc = copy(top.evkq, top.key_words(), h->evkq_n, 2 * c.L, &c.evkq, &c.evkq_sigma, &lv->evkq_cap))) return rc;
+    if ((rc = copy(top.masks, top.LN(), h->b ? 1 : 0, h->b, &c.masks, &c.masks_sigma, &lv->masks_cap))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     return PIEHIP_OK;
 }

@@ -136,30 +136,34 @@ struct SliceState {
     u32 u_n() const { return u_hi - u_lo; }
 };
 
-// What a schedule piece (ntt, enqueue_mul, enqueue_keyswitch, enqueue_mod_reduce) reads of a context: the handle's own -- its L
-// limbs -- or a level context (below).  A Sched carries one, as it carries a queue.
+// Everything a product chain and its schedule pieces (ntt, enqueue_mul, enqueue_keyswitch, enqueue_mod_reduce) read beside the
+// workspace, for one prime chain: constants, plan and lane-order map, and the keys and masks on that chain's limbs.  There is one
+// for the handle's L limbs (piehip_ctx::cx) and one per level context (below); a Sched carries one, as it carries a queue, and
+// run()'s chain is the same schedule on either.
 struct ChainCtx {
     const DevConsts *d_dc = nullptr;
     const NttPlan *plan = nullptr;
     const u32 *d_sigma_inv = nullptr;   // lane-order position -> standard position
     u32 N = 0, L = 0, M = 0;
+    // EvalMult key [L][2][L][N]; per-query keys (piehip_load_relin_key_q), piehip_ctx::evkq_n of them one after the other, entries nobody
+    // loaded holding the handle's key; masks [b][L][N].  *_sigma: the lane-ordered twin, where the plan has a lane order (piehip.cpp,
+    // lane_twin).  A handle that borrows its database (piehip_attach_database) has its owner's evk* and masks* here.
+    u64 *evk = nullptr, *evk_sigma = nullptr, *evkq = nullptr, *evkq_sigma = nullptr, *masks = nullptr, *masks_sigma = nullptr;
     size_t LN() const { return (size_t)L * N; }
+    size_t key_words() const { return (size_t)L * 2 * LN(); }
 };
 
 // Chain limbs (include/piehip.h): everything piehip_create derives from (N, Lc, t, q[:Lc], p[:Lc + 1]) -- constant block, transform
-// tables, plan with its routes and fusions -- and the limb prefixes of the handle's keys and masks, copied when the key or the
-// database is set (piehip.cpp, level_sync).  Built when the setting first takes the value Lc and kept with the handle; its device
-// tables are freed with the handle's (dev_tables).
+// tables, plan with its routes and fusions -- behind a ChainCtx whose keys and masks are the limb prefixes of the handle's, copied
+// when the key or the database is set (piehip.cpp, level_sync).  Built when the setting first takes the value Lc and kept with the
+// handle; its device tables are freed with the handle's (dev_tables).
 struct LevelCtx {
     HostParams hp;
     DevConsts *d_dc = nullptr;
     NttPlan plan;
     u32 *d_sigma_inv = nullptr;
     ChainCtx cx;
-    // [Lc][2][Lc][N] (+ lane-ordered twin), [nq] of them for per-query keys, masks [b][Lc][N] (+ twin); *_cap: words allocated
-    u64 *evk = nullptr, *evk_sigma = nullptr, *evkq = nullptr, *evkq_sigma = nullptr, *masks = nullptr, *masks_sigma = nullptr;
-    size_t evkq_cap = 0, masks_cap = 0;
-    bool has_evk = false;
+    size_t evk_cap = 0, evkq_cap = 0, masks_cap = 0;   // words cx.evk / cx.evkq / cx.masks (and each twin) were allocated for
 };
 
 }  // namespace piehip
@@ -209,7 +213,6 @@ struct piehip_ctx {
     std::vector<void *> dev_tables;
     u32 *d_inv_pos = nullptr;    // EVALUATION position -> slot
     u32 *d_sigma_inv = nullptr;  // lane-order position -> standard position (identity without a lane order)
-    u64 *d_evk_sigma = nullptr, *d_masks_sigma = nullptr;  // lane-ordered copies of key and masks
     u64 *d_hash_tbl = nullptr;   // [k][e][K][b][E] of the last piehip_build_db
     size_t hash_tbl_words = 0;
     // scratch of the offline phase (hashing, packing, encoding), kept between calls: piehip_reserve sizes it up front so that
@@ -218,26 +221,23 @@ struct piehip_ctx {
     size_t arena_words = 0, arena_used = 0;
     u32 hk = 0, he = 0, hb = 0;  // table dimensions ([k][e][K][hb][E]; hb = all bin layers, of which this handle keeps b)
     piehip::NttPlan plan;
-    piehip::ChainCtx cx;         // the handle's own context as the schedule pieces take it (d_dc, plan, d_sigma_inv, N, L, M)
+    piehip::ChainCtx cx;         // the handle's own context: d_dc, plan, d_sigma_inv above, and the handle's keys and masks
     // piehip_set_chain_limbs: with chain_limbs < L the product chain of run() works on `level`, the level context of the first
     // chain_limbs limbs; every level the handle has been set to stays in `levels`
     u32 chain_limbs = 0;
     piehip::LevelCtx *level = nullptr;
     std::map<u32, std::unique_ptr<piehip::LevelCtx>> levels;
     // keys / database / inputs
-    bool db_borrowed = false;  // piehip_attach_database: d_evk*, d_db, d_masks* belong to another handle (never freed or written here)
+    bool db_borrowed = false;  // piehip_attach_database: cx.evk*, d_db, cx.masks* belong to another handle (never freed or written here)
     piehip_ctx *db_owner = nullptr;  // ... that handle
     u32 db_borrowers = 0;            // handles that borrow from this one: its buffers may not move while > 0
-    u64 *d_evk = nullptr;
     u32 K = 0, b = 0, E = 0;
-    u64 *d_db = nullptr, *d_masks = nullptr;
+    u64 *d_db = nullptr;
     // query batch (piehip_set_query_batch): run() evaluates queries 0 .. nq - 1 against the database at once.  Workspace and
     // results hold nq rows per bin layer: [b][nq][..].
     piehip::Query query[piehip::STAGE_A_MAX_QUERIES];
     u32 nq = 1;
-    // piehip_load_relin_key_q: the queries of a batch come from different clients, each with its own EvalMult key.  [evkq_n] keys
-    // [L][2][L][N] one after the other (+ the lane-ordered copy); entries nobody loaded hold the handle's key
-    u64 *d_evkq = nullptr, *d_evkq_sigma = nullptr;
+    // piehip_load_relin_key_q: the queries of a batch come from different clients, each with its own EvalMult key (cx.evkq)
     u32 evkq_n = 0, evkq_loaded = 0;    // keys the array holds; bit q: query q loaded its own
     // run() workspace
     u64 *d_acc = nullptr;   // [b][K][2][L][N]
@@ -289,11 +289,13 @@ struct piehip_ctx {
 
 namespace piehip {
 
-// the key switch of run() has a key for every query: the handle's, or one per query of the batch (piehip_load_relin_key_q)
-inline bool run_keys_loaded(const piehip_ctx *h)
+// the key switch of a run() on context cx (the handle's own or its level) has a key for every query: the context's copy of the
+// handle's key, or of one key per query of the batch -- read only while the handle's per-query array is the current batch's
+// (piehip_set_query_batch frees that one and leaves a level's copy behind)
+inline bool run_keys_loaded(const piehip_ctx *h, const ChainCtx &cx)
 {
     if (h->K == 2 && !h->res_relin) return true;   // the only product is not relinearised
-    return h->K <= 1 || h->d_evk || (h->d_evkq && h->evkq_n == h->nq && h->evkq_loaded == (1u << h->nq) - 1);
+    return h->K <= 1 || cx.evk || (h->cx.evkq && cx.evkq && h->evkq_n == h->nq && h->evkq_loaded == (1u << h->nq) - 1);
 }
 
 // Where and how a schedule piece is enqueued.  A handle alone converts to "its stream, no gate, one mask and one key for every
@@ -306,8 +308,8 @@ struct Sched {
     hipEvent_t release = nullptr;  // host-results runs: recorded, and cleared, when this group has only its result-writing kernel
                                    // left; the next queue group starts behind it (null: nobody waits)
     u32 mask_div = 1;   // a batch: ciphertext row r of the product chain takes mask r / mask_div
-    u32 key_group = 1;  // ... and, with per-query EvalMult keys, key r % key_group of d_evkq
-    const ChainCtx *cx; // the context the pieces work on: the handle's own unless run() hands them a level context (chain limbs)
+    u32 key_group = 1;  // ... and, with per-query EvalMult keys, key r % key_group of cx->evkq
+    const ChainCtx *cx; // the context the pieces work on: the handle's own unless run() hands them its level context (chain limbs)
     Sched(piehip_ctx *h_) : h(h_), stream(h_->stream), cx(&h_->cx) {}
     Sched(piehip_ctx *h_, hipStream_t s) : h(h_), stream(s), cx(&h_->cx) {}
     void wait_for_readers() const { if (wait_before_results) (void)hipStreamWaitEvent(stream, wait_before_results, 0); }
@@ -431,6 +433,7 @@ __attribute__((visibility("hidden"))) int items_to_slots(piehip_ctx *h, Tmp &tmp
 int run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *host_results = nullptr);
 bool run_x_direct(const piehip_ctx *h);
 bool run_on_level(const piehip_ctx *h);
+const ChainCtx &run_chain_ctx(const piehip_ctx *h);   // the context the product chain of run() works on: the handle's own, or its level's
 // piehip_slice.cpp
 void slice_free(piehip_ctx *h);          // back to an unsliced handle: the slice side's buffers and state
 int slice_batch_changed(piehip_ctx *h);  // piehip_set_query_batch on a sliced handle: acc for the new batch, nothing put

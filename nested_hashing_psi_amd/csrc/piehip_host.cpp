@@ -454,7 +454,7 @@ int piehip_run_staged(piehip_handle h, uint64_t *results)
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
     if (!h->K || !h->d_db) return fail(PIEHIP_ESTATE, "run: database not loaded");
-    if (!run_keys_loaded(h)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
+    if (!run_keys_loaded(h, h->cx)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
     if (!h->stage_open) return fail(PIEHIP_ESTATE, "run_staged: query not staged");
     const u32 nq = h->nq;
     for (u32 q = 0; q < nq; q++) {
@@ -491,7 +491,7 @@ int piehip_run_host_async(piehip_handle h, const uint64_t *idx, const uint64_t *
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
     if (!idx || !minus) return fail(PIEHIP_EINVAL, "null input");
-    if (h->K && !run_keys_loaded(h)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
+    if (h->K && !run_keys_loaded(h, h->cx)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
     h->stage_open = false;  // queries of its own: pieces staged earlier and never run are dropped
     const size_t row = (size_t)h->E * 2 * h->LN();
     int rc = PIEHIP_OK;
@@ -510,7 +510,7 @@ int piehip_run_host_seeded_async(piehip_handle h, const uint64_t *c0idx, const u
 {
     if (!h) return fail(PIEHIP_EINVAL, "null handle");
     if (!c0idx || !idx_seeds || !c0minus || !minus_seeds) return fail(PIEHIP_EINVAL, "null input");
-    if (h->K && !run_keys_loaded(h)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
+    if (h->K && !run_keys_loaded(h, h->cx)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
     h->stage_open = false;  // queries of its own: pieces staged earlier and never run are dropped
     const size_t LN = h->LN(), row = (size_t)h->E * LN;
     int rc = PIEHIP_OK;

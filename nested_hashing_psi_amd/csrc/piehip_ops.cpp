@@ -53,7 +53,7 @@ int piehip_eval_mult(piehip_handle h, const uint64_t *x, const uint64_t *y, uint
 {
     NEED(h);
     if (!x || !y || !out || !nct) return fail(PIEHIP_EINVAL, "null operand");
-    if (relin && !h->d_evk) return fail(PIEHIP_ESTATE, "relinearisation key not loaded");
+    if (relin && !h->cx.evk) return fail(PIEHIP_ESTATE, "relinearisation key not loaded");
     HIPCHK(hipSetDevice(h->device));
     Tmp tmp;
     const size_t LN = h->LN();

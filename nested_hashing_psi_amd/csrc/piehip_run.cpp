@@ -55,15 +55,10 @@ void enqueue_keyswitch(Sched &s, MulWs &w, u32 nb, RunKey key, const u64 *mask, 
 // ciphertext row, or -- a batch whose queries bring their own keys (piehip_load_relin_key_q) -- key r % group of the array for row r
 static RunKey run_key(const Sched &s)
 {
-    const piehip_ctx *h = s.h;
-    const bool lane = s.cx->plan->lane_order;
-    if (s.cx != &h->cx) {   // a level context: the limb prefixes of the same keys (level_sync)
-        const LevelCtx *lv = h->level;
-        if (s.key_group > 1) return {lane ? lv->evkq_sigma : lv->evkq, (size_t)s.cx->L * 2 * s.cx->LN(), s.key_group};
-        return {lane ? lv->evk_sigma : lv->evk};
-    }
-    if (s.key_group > 1) return {lane ? h->d_evkq_sigma : h->d_evkq, (size_t)h->hp.L * 2 * h->LN(), s.key_group};
-    return {lane ? h->d_evk_sigma : h->d_evk};
+    const ChainCtx &cx = *s.cx;
+    const bool lane = cx.plan->lane_order;
+    if (s.key_group > 1) return {lane ? cx.evkq_sigma : cx.evkq, cx.key_words(), s.key_group};
+    return {lane ? cx.evk_sigma : cx.evk};
 }
 
 // One batched EvalMult(ct,ct) (BatchedFHEHIPPIE.cpp:123): operands in COEFFICIENT format (produced by
@@ -231,6 +226,7 @@ bool run_x_direct(const piehip_ctx *h) { return h->K > 1 && h->nq > 1 && h->plan
 
 // the product chain of run() works on the level context (chain limbs below L; a handle with K = 1 has no product: nothing changes)
 bool run_on_level(const piehip_ctx *h) { return h->K >= 2 && h->level && h->chain_limbs < h->hp.L; }
+const ChainCtx &run_chain_ctx(const piehip_ctx *h) { return run_on_level(h) ? h->level->cx : h->cx; }
 
 // bin layers of queue group g of ng.  Two groups take 4/7 and 3/7 of the layers: measured 3.5 % faster than equal halves at
 // b = 14 (8 + 6: the ragged transform launches of the two queues fit the workgroup slots better than 7 + 7).
@@ -251,8 +247,8 @@ extern "C" {
 // Bin layers [b0, b0 + nb) of run() on the queue of s: stage A, then the product chain; results[b][nq][2][L][N].
 // chain_only (piehip_run_chain: the accumulators were put there, piehip_put_accumulators): the product chain alone
 static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_only);
-// everything of run() behind stage A for those layers (BatchedFHEHIPPIE.cpp:117-126): both callers above share it
-static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results);
+// everything of run() behind stage A for those layers (BatchedFHEHIPPIE.cpp:117-126), on the context run_chain_ctx chooses
+static void enqueue_chain_bins(Sched &s, const ChainCtx &top, const ChainCtx &cx, u32 b0, u32 layers, u64 *results);
 // ... and, on a handle that hands its results out on fewer limbs, their reduction: results[b][nq][2][res_limbs][N].  The chain then
 // writes the handle's full-width rows, which no caller reads: what orders a run against the result buffer's readers (and releases
 // the next queue group of a host-results run) moves from the chain's last kernel to the reduction: the chain is enqueued ungated.
@@ -261,7 +257,7 @@ static void enqueue_run_bins(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_
     piehip_ctx *h = s.h;
     const u32 keep = h->res_limbs, nq = h->nq;
     // chain limbs: the chain hands over rows of the level context, and the reduction -- from its Lc limbs down to keep -- runs there
-    const ChainCtx &cx = run_on_level(h) ? h->level->cx : h->cx;
+    const ChainCtx &cx = run_chain_ctx(h);
     if (keep >= cx.L) {
         enqueue_run_bins_full(s, b0, nb, results, chain_only);
         return;
@@ -311,140 +307,104 @@ static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool c
                            x_direct ? &xo : nullptr);
         }
     }
-    enqueue_chain_bins(s, b0, layers, results);
+    enqueue_chain_bins(s, h->cx, run_chain_ctx(h), b0, layers, results);
 }
-// Chain limbs (include/piehip.h): the chain of a handle whose setting is below L.  The accumulators are
-// inverse-transformed on the handle's L limbs, dropped to Lc and multiplied on the level context: its constants, plan and tables, the
-// limb prefixes of keys and masks, the workspace viewed in rows of Lc limbs (rows of two queue groups stay apart as they do at L: both
-// groups take the same view).  Where the fused conversion applies the drop happens in its load phase; otherwise a drop kernel rewrites
-// the accumulators in place and every conversion of the chain takes plain operands.  results[b][nq][comps][Lc][N].
-static void enqueue_chain_bins_level(Sched &s, u32 b0, u32 layers, u64 *results)
+// rows [r0, r0 + nb) of the workspace as a context of cx.L limbs lays them out (on a level context the rows of two queue groups
+// stay apart as they do at L: both groups take the same view)
+static MulWs ws_rows(const MulWs &ws, const ChainCtx &cx, size_t r0, u32 nb)
 {
-    piehip_ctx *h = s.h;
-    const LevelCtx &lv = *h->level;
-    const ChainCtx &cx = lv.cx;
-    const NttPlan &pl = lv.plan;
-    const u32 N = h->hp.N, L = h->hp.L, K = h->K, nq = h->nq, Lc = cx.L, Mc = cx.M;
-    const size_t LN = h->LN(), LcN = cx.LN();
-    const double W = 8.0 * N;
-    const size_t r0 = (size_t)b0 * nq;
-    const u32 nb = layers * nq;
-    MulWs w = h->ws;
+    const size_t N = cx.N, LN = cx.LN();
+    MulWs w = ws;
     w.nb = nb;
-    w.eqp += r0 * 4 * Mc * N;
-    w.dqp += r0 * 3 * Mc * N;
-    w.d01 += r0 * 2 * LcN;
-    w.d2c += r0 * LcN;
-    w.dig += r0 * Lc * LcN;
-    if (w.t3) w.t3 += r0 * 3 * LcN;
-    u64 *acc = h->d_acc + r0 * K * 2 * LN;   // stage A's rows: the parent's strides
-    u64 *prod = h->d_prod ? h->d_prod + r0 * 2 * LcN : nullptr;
-    const bool deg2 = h->res_comps() == 3;
-    u64 *out = results + r0 * h->res_comps() * LcN;
-    const u64 *masks = ((deg2 ? pl.result_eval_q : pl.lane_order) ? lv.masks_sigma : lv.masks) + (size_t)b0 * LcN;
-    s.mask_div = nq;
-    s.key_group = (nq > 1 && h->d_evkq && h->evkq_n == nq) ? nq : 1;
-    ntt(s, acc, nb * K * 2 * L, 0, L, true, false, true);   // (the parent's context: s.cx)
-    // the fused conversion: folded rings whose level moduli take the column-accumulator arithmetic, pairs it is built for
-    const bool fused = h->plan.fold && pl.fold && pl.small_moduli && pl.xq_reuse && expand_both_drop_applies(L, Lc);
-    if (!fused) {
-        ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * nb * K * 2 * (L + Lc));
-        launch_chain_drop(h->d_dc, N, L, Lc, acc, nb * K * 2, s.stream, h->plan.fold);
-    }
-    s.cx = &cx;
-    MulIn in;
-    in.six = in.siy = LN;
-    if (fused)
-        in.drop_from = &h->cx, in.x_drop = true;
-    else
-        in.plain = true;
-    NttExtra ex;
-    ex.copy_out = w.eqp;
-    ex.copy_K = 1;
-    ex.copy_L = Lc;
-    ex.copy_M = Mc;
-    const u64 *x = acc;
-    size_t sx = (size_t)K * 2 * LN;
-    for (u32 hf = 1; hf < K; hf++) {
-        const bool last = hf + 1 == K;
-        // the dropped X of the first product is not what the QP array could hold in EVALUATION form: xq_ready only from the second on
-        enqueue_mul(s, w, x, sx, acc + (size_t)hf * 2 * LN, (size_t)K * 2 * LN, nb, !(last && deg2), last ? masks : nullptr, last ? out : prod,
-                    fused && hf > 1, last, &in);
-        if (!last) {
-            if (fused)
-                ntt(s, prod, nb * 2 * Lc, 0, Lc, true, false, true, &ex);
-            else
-                ntt(s, prod, nb * 2 * Lc, 0, Lc, true, false, false);   // unfolded: plain coefficients, like the dropped accumulators
-            x = prod;
-            sx = 2 * LcN;
-            in.six = LcN;
-            in.x_drop = false;
-        }
-    }
-    s.cx = &h->cx;
-}
-static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
-{
-    piehip_ctx *h = s.h;
-    if (run_on_level(h)) {
-        enqueue_chain_bins_level(s, b0, layers, results);
-        return;
-    }
-    const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M, K = h->K, nq = h->nq;
-    const size_t LN = h->LN();
-    const double W = 8.0 * N;
-    const size_t r0 = (size_t)b0 * nq;
-    const u32 nb = layers * nq;
-    MulWs w = h->ws;  // view of the workspace rows of these bin layers
-    w.nb = nb;
-    w.eqp += r0 * 4 * M * N;
-    w.dqp += r0 * 3 * M * N;
+    w.eqp += r0 * 4 * cx.M * N;
+    w.dqp += r0 * 3 * cx.M * N;
     w.d01 += r0 * 2 * LN;
     w.d2c += r0 * LN;
-    w.dig += r0 * L * LN;
+    w.dig += r0 * cx.L * LN;
     if (w.t3) w.t3 += r0 * 3 * LN;
-    u64 *acc = h->d_acc + r0 * K * 2 * LN;
+    return w;
+}
+// The product chain of run() (BatchedFHEHIPPIE.cpp:117-126) on two contexts.  `top` is the handle's own: stage A left its
+// accumulators there, in rows of top.L limbs, and their inverse transform runs there.  `cx` is where the products run: top itself,
+// or the handle's level context (chain limbs, include/piehip.h) -- its constants, plan and tables, the limb
+// prefixes of keys and masks, the workspace viewed in rows of cx.L limbs.  On a level the accumulators are dropped to cx.L limbs on
+// their way into the products: in the load phase of the fused conversion where that applies, otherwise by a drop kernel that rewrites
+// them in place, after which every conversion of the chain takes plain operands.  results[b][nq][comps][cx.L][N].
+static void enqueue_chain_bins(Sched &s, const ChainCtx &top, const ChainCtx &cx, u32 b0, u32 layers, u64 *results)
+{
+    piehip_ctx *h = s.h;
+    const NttPlan &pl = *cx.plan;
+    const u32 N = cx.N, K = h->K, nq = h->nq;
+    const size_t TLN = top.LN(), LN = cx.LN();
+    const double W = 8.0 * N;
+    const size_t r0 = (size_t)b0 * nq;
+    const u32 nb = layers * nq;
+    MulWs w = ws_rows(h->ws, cx, r0, nb);
+    u64 *acc = h->d_acc + r0 * K * 2 * TLN;   // stage A's rows: the handle's strides
     u64 *prod = h->d_prod ? h->d_prod + r0 * 2 * LN : nullptr;
     const bool deg2 = h->res_comps() == 3;   // piehip_set_result_relin(0): the last product goes out as it is, three components
     u64 *out = results + r0 * h->res_comps() * LN;
-    const u64 *masks = ((deg2 ? h->plan.result_eval_q : h->plan.lane_order) ? h->d_masks_sigma : h->d_masks) + (size_t)b0 * LN;
+    const u64 *masks = ((deg2 ? pl.result_eval_q : pl.lane_order) ? cx.masks_sigma : cx.masks) + (size_t)b0 * LN;
     s.mask_div = nq;
-    s.key_group = (nq > 1 && h->d_evkq && h->evkq_n == nq) ? nq : 1;  // per-query EvalMult keys: row r of a group is query r % nq
-    const bool x_direct = run_x_direct(h);
+    s.key_group = (nq > 1 && h->cx.evkq && h->evkq_n == nq) ? nq : 1;  // per-query EvalMult keys: row r of a group is query r % nq
     if (K == 1) {
         // one inner hash function: multipliedResult is the inner product itself (BatchedFHEHIPPIE.cpp:117-120), so run() is
         // stage A and the mask multiply (:126) -- no ciphertext product, no transform, no key
         // (the release of the next queue group is not recorded here but behind the whole group: run_on_queues)
         s.wait_for_readers();
-        ProfScope ps(s, PIEHIP_K_MASK, W * nb * 5.0 * L);
-        launch_ct_mul_plain(h->d_dc, N, L, acc, h->d_masks + (size_t)b0 * LN, LN, out, nb, s.stream, nq);
+        ProfScope ps(s, PIEHIP_K_MASK, W * nb * 5.0 * cx.L);
+        launch_ct_mul_plain(cx.d_dc, N, cx.L, acc, cx.masks + (size_t)b0 * LN, LN, out, nb, s.stream, nq);
         return;
     }
-    // every accumulator enters a ct x ct product exactly once: switch them all to COEFFICIENT format
-    const bool xq = h->plan.xq_reuse;
+    // What the chain at L and the two chains of a level disagree on, decided here and nowhere below.
+    // fused: the limb drop rides in the conversions' load phase -- folded rings whose level moduli take the column-accumulator
+    // arithmetic, pairs the conversion is built for; dropped: the drop kernel does it, and leaves plain coefficients
+    const bool level = cx.L < top.L;   // the products run on fewer limbs than the accumulators have
+    const bool fused = level && top.plan->fold && pl.fold && pl.small_moduli && pl.xq_reuse && expand_both_drop_applies(top.L, cx.L);
+    const bool dropped = level && !fused;
+    // X is needed twice by a product: in COEFFICIENT form by the base extension, and in EVALUATION form, lane-ordered, as the Q limbs of
+    // the QP operand (plan.xq_reuse).  The inverse transform that makes the first also writes the second (NttExtra copy_out) -- where
+    // it makes X at all: the dropped X of a level's first product is not what the QP array could hold in EVALUATION form, and the
+    // drop kernel's chain transforms without folding, into plain coefficients like the dropped accumulators, and copies nothing
+    const bool copy_first = !level && pl.xq_reuse, copy_between = !dropped && pl.xq_reuse;
+    const u32 xq_from = copy_first ? 1 : copy_between ? 2 : K;   // the products from this one on find X's Q limbs in the QP array
+    MulIn in;   // (at L: the strides the conversions assume anyway)
+    in.six = in.siy = TLN;
+    in.drop_from = fused ? &top : nullptr;
+    in.x_drop = fused;
+    in.plain = dropped;
     NttExtra ex;
     ex.copy_out = w.eqp;
     ex.copy_K = K;
-    ex.copy_L = L;
-    ex.copy_M = M;
-    ex.x_lane_in = x_direct;
-    ntt(s, acc, nb * K * 2 * L, 0, L, true, false, true, xq ? &ex : nullptr);
+    ex.copy_L = cx.L;
+    ex.copy_M = cx.M;
+    ex.x_lane_in = run_x_direct(h);
+    // every accumulator enters a ct x ct product exactly once: switch them all to COEFFICIENT format, on the handle's limbs
+    ntt(s, acc, nb * K * 2 * top.L, 0, top.L, true, false, true, copy_first ? &ex : nullptr);
     ex.x_lane_in = false;
-    // product chain over the inner hash functions (BatchedFHEHIPPIE.cpp:117-124); the mask multiply
-    // (:126) is fused into the last key switch
+    ex.copy_K = 1;  // from here on the product is the X operand of the next multiplication
+    if (dropped) {
+        ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * nb * K * 2 * (top.L + cx.L));
+        launch_chain_drop(top.d_dc, N, top.L, cx.L, acc, nb * K * 2, s.stream, top.plan->fold);
+    }
+    // product chain over the inner hash functions (BatchedFHEHIPPIE.cpp:117-124); the mask multiply (:126) is fused into the last
+    // key switch
+    s.cx = &cx;
     const u64 *x = acc;
-    size_t sx = (size_t)K * 2 * LN;
+    size_t sx = (size_t)K * 2 * TLN;
     for (u32 hf = 1; hf < K; hf++) {
         const bool last = hf + 1 == K;
-        u64 *dst = last ? out : prod;
-        enqueue_mul(s, w, x, sx, acc + (size_t)hf * 2 * LN, (size_t)K * 2 * LN, nb, !(last && deg2), last ? masks : nullptr, dst, xq, last);
+        enqueue_mul(s, w, x, sx, acc + (size_t)hf * 2 * TLN, (size_t)K * 2 * TLN, nb, !(last && deg2), last ? masks : nullptr, last ? out : prod,
+                    hf >= xq_from, last, &in);
         if (!last) {
-            ex.copy_K = 1;  // the product is the X operand of the next multiplication
-            ntt(s, prod, nb * 2 * L, 0, L, true, false, true, xq ? &ex : nullptr);
+            ntt(s, prod, nb * 2 * cx.L, 0, cx.L, true, false, !dropped, copy_between ? &ex : nullptr);
             x = prod;
             sx = 2 * LN;
+            in.six = LN;
+            in.x_drop = false;
         }
     }
+    s.cx = &top;
 }
 
 // the result ciphertexts of bin layers [b0, b0 + nb) (rows [bin layer][query]) to the caller's host array, on the queue of s
@@ -465,13 +425,13 @@ int piehip::run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *
     if (!chain_only && h->slice.on) return fail(PIEHIP_ESTATE, "run: a query-sliced handle holds no whole database (piehip_run_slice / piehip_run_chain)");
     if (!h->K || (!chain_only && !h->d_db)) return fail(PIEHIP_ESTATE, "run: database not loaded");
     if (!h->d_acc || !h->ws.eqp) return fail(PIEHIP_ESTATE, "run: no workspace (an earlier allocation failed: piehip_set_query_batch / load)");
-    if (!run_keys_loaded(h)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
+    if (!run_keys_loaded(h, h->cx)) return fail(PIEHIP_ESTATE, "run: relinearisation key not loaded");
     if (h->res_comps() == 3) {
         if (h->slice.on) return fail(PIEHIP_ESTATE, "run: a query-sliced handle relinearises its results (piehip_set_result_relin)");
         if (!h->ws.t3 || h->res_cap_comps < 3)
             return fail(PIEHIP_ESTATE, "run: no rows for three-component results (an earlier allocation failed: piehip_set_result_relin)");
     }
-    if (run_on_level(h) && ((h->K > 2 || h->res_relin) ? !(h->level->has_evk || (h->d_evkq && h->level->evkq)) : false))
+    if (!run_keys_loaded(h, run_chain_ctx(h)))
         return fail(PIEHIP_ESTATE, "run: no key on the level context (an earlier allocation failed: piehip_set_chain_limbs)");
     if (h->res_limbs < h->hp.L && !h->d_full) return fail(PIEHIP_ESTATE, "run: no rows for the result reduction (an earlier allocation failed: piehip_set_result_limbs)");
     for (u32 q = 0; q < h->nq && !chain_only; q++) {

@@ -75,7 +75,7 @@ static int slice_setup(piehip_ctx *h, u32 K, u32 b, u32 E, u32 u_lo, u32 u_hi, u
     slice_free(h);
     int rc = alloc_run_buffers(h, K, bin_hi - bin_lo, E, false);
     if (rc) return rc;
-    if (bin_hi > bin_lo && (rc = dev_alloc(&h->d_masks, (size_t)(bin_hi - bin_lo) * h->LN()))) return rc;
+    if (bin_hi > bin_lo && (rc = dev_alloc(&h->cx.masks, (size_t)(bin_hi - bin_lo) * h->LN()))) return rc;
     SliceState &s = h->slice;
     s.u_lo = u_lo, s.u_hi = u_hi, s.bin_lo = bin_lo, s.bin_hi = bin_hi, s.b_total = b;
     s.put.assign((size_t)K * L, false);
@@ -274,7 +274,7 @@ int piehip_load_db_table_sliced(piehip_handle h, const uint64_t *tbl, uint32_t k
     if (bin_hi == bin_lo) return PIEHIP_OK;
     // the masks of the chain side's layers: drawn per layer from mask_seed, the ones the unsharded call draws (encode_bin_layers)
     launch_mask_slots(h->hp.t, b, (u32)B, mask_seed, d_slots, h->stream);
-    if ((rc = encode_on_device(h, d_slots + (size_t)bin_lo * B, bin_hi - bin_lo, (u32)B, h->d_masks))) return rc;
+    if ((rc = encode_on_device(h, d_slots + (size_t)bin_lo * B, bin_hi - bin_lo, (u32)B, h->cx.masks))) return rc;
     return make_masks_sigma(h);
 }
 
@@ -298,7 +298,7 @@ int piehip_build_db_sliced(piehip_handle h, const uint64_t *items, size_t n, uin
     if ((rc = encode_units(h, d_slots, b, E, (u32)B))) return rc;
     if (bin_hi == bin_lo) return PIEHIP_OK;
     launch_mask_slots(h->hp.t, b, (u32)B, mask_seed, d_slots, h->stream);
-    if ((rc = encode_on_device(h, d_slots + (size_t)bin_lo * B, bin_hi - bin_lo, (u32)B, h->d_masks))) return rc;
+    if ((rc = encode_on_device(h, d_slots + (size_t)bin_lo * B, bin_hi - bin_lo, (u32)B, h->cx.masks))) return rc;
     return make_masks_sigma(h);
 }
 
@@ -328,7 +328,7 @@ int piehip_load_db_sliced(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, u
     if (s.u_n())
         HIPCHK(hipMemcpyAsync(s.db, pts_slice, sizeof(u64) * (size_t)s.u_n() * b * E * h->hp.N, hipMemcpyHostToDevice, h->stream));
     if (bin_hi > bin_lo)
-        HIPCHK(hipMemcpyAsync(h->d_masks, masks, sizeof(u64) * (size_t)(bin_hi - bin_lo) * h->LN(), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->cx.masks, masks, sizeof(u64) * (size_t)(bin_hi - bin_lo) * h->LN(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return bin_hi > bin_lo ? make_masks_sigma(h) : PIEHIP_OK;
 }
