@@ -12,6 +12,8 @@ digit lift work on such columns, and they branch and round at places that unifor
                   q_j subtracts, wraps and changes sign
   message edges   neighbouring phases x on either side of a step of round(t x/Q): decryption's result changes there, at the messages
                   where it wraps (t -> 0) and where the decoded slot changes sign ((t - 1)/2, (t + 1)/2)
+  limb drops      the residue dropped at EVERY step of a drop of several limbs at 0, +-1 and +-(q_l - 1)/2 (the derived residues, not only
+                  those given), kept residues at 0 and q_i - 1 in front of a step, and the result of the drop on the level's own edges
 
 and, for the client's encryption, message coefficients m that put [Q m]_t on the branches of the message term.
 
@@ -230,6 +232,83 @@ def decrypt_families(o):
     f["windows"] = lift_windows(qs)
     f["ties_decrypt"] = [reduce_col(x, qs) for x in ties_decrypt(o).values()]
     f["message_edges"] = [reduce_col(x, qs) for x in message_edges(o).values()]
+    return f
+
+
+# ---- the limb drop ---------------------------------------------------------------------------------------------------------------
+# The drop of limb l (tests/test_result_limbs.py) takes r = c mod q_l centred and leaves (c - r) / q_l, a number modulo q_0 .. q_{l-1}.
+# It branches on c_l > (q_l - 1)/2, and its kernels form c_i - r as one unsigned word whose ends are met only when c_i is 0 or
+# q_i - 1 while c_l sits at the branch.  The columns below are built backwards from what the drop is to meet at every step.
+def undrop(y, l_from, qs, rs):
+    """the column over qs of the c with  c <- (c q_l + r_l) mod (q_0 .. q_l)  for l = l_from .. L - 1, from c = y, an integer modulo
+    q_0 .. q_{l_from - 1}; rs[l] is a centred residue, |rs[l]| <= (q_l - 1)/2 (a list of length L, or a dict, indexed by l).
+    Dropping the limbs L - 1 .. l_from from the column by the definition gives back y, and the residue dropped at step l is
+    rs[l] mod q_l"""
+    qs = [int(q) for q in qs]
+    c = int(y) % ex.prod(qs[:l_from])
+    for l in range(l_from, len(qs)):
+        r = int(rs[l])
+        assert 2 * abs(r) <= qs[l] - 1
+        c = (c * qs[l] + r) % ex.prod(qs[:l + 1])
+    return reduce_col(c, qs)
+
+
+def drop_patterns(qs, Lc):
+    """the patterns of dropped residues r (dicts l -> r_l over the dropped limbs Lc .. L - 1) that drop_families cycles through: every
+    dropped limb at the same element of {0, 1, -1, half, -half}; each limb alone at +-half or +-1, the others at 0; the two
+    alternations of +half / -half (half = (q_l - 1)/2: +half is the largest residue that counts as positive, -half = (q_l + 1)/2 mod
+    q_l the smallest that counts as negative)"""
+    qs = [int(q) for q in qs]
+    D = list(range(Lc, len(qs)))
+    half = {l: (qs[l] - 1) // 2 for l in D}
+    pats = [{l: 0 for l in D}, {l: 1 for l in D}, {l: -1 for l in D}, {l: half[l] for l in D}, {l: -half[l] for l in D}]
+    for l in D:
+        for v in (half[l], -half[l], 1, -1):
+            pats.append({j: v if j == l else 0 for j in D})
+    for first in (1, -1):
+        pats.append({l: first * (-1) ** (l - Lc) * half[l] for l in D})
+    out = []
+    for p in pats:
+        if p not in out:
+            out.append(p)
+    return out
+
+
+def drop_families(o, ol, Lc):
+    """Families over the parent's q for the drop of the limbs L - 1 .. Lc (ol: the level oracle of the first Lc limbs):
+
+      final  y undropped with one pattern of drop_patterns, cycling; y runs over the CRT values of every column of q_families(ol) --
+             digit extremes, ties and windows of the LEVEL, so that the level's expand / scale_pq meet their own edges behind the drop --
+             and 0, 1, Q_Lc - 1.  As many columns as the longer of the two lists
+      kept   for every dropped limb l the state just before its drop -- residues i < l all 0 or all q_i - 1, limb l at 0, (q_l - 1)/2,
+             (q_l + 1)/2, q_l - 1 -- undropped through the limbs above l with r = 0 and with r = (q_j - 1)/2
+
+    .claims[family][k] says what column k was built from: (y, pattern) for final; (l, state, pattern) for kept, state the residues
+    0 .. l in front of step l"""
+    qs, _ = moduli(o)
+    L = len(qs)
+    assert 1 <= Lc < L and [int(v) for v in ol.q] == qs[:Lc]
+    QLc = ex.prod(qs[:Lc])
+    lvl = q_families(ol)
+    ys = [ex.crt(col, qs[:Lc]) for cols in lvl.values() for col in cols] + [0, 1, QLc - 1]
+    pats = drop_patterns(qs, Lc)
+    f = Families(qs)
+    f.claims = {"final": [], "kept": []}
+    f["final"], f["kept"] = [], []
+    for k in range(max(len(ys), len(pats))):
+        y, pat = ys[k % len(ys)], pats[k % len(pats)]
+        f["final"].append(undrop(y, Lc, qs, pat))
+        f.claims["final"].append((y, pat))
+    for l in range(Lc, L):
+        ql = qs[l]
+        for low in (0, 1):
+            for vl in (0, (ql - 1) // 2, (ql + 1) // 2, ql - 1):
+                state = tuple(0 if low == 0 else qs[i] - 1 for i in range(l)) + (vl,)
+                x = ex.crt(state, qs[:l + 1])
+                for top in ((0, 1) if l + 1 < L else (0,)):
+                    pat = {j: top * ((qs[j] - 1) // 2) for j in range(l + 1, L)}
+                    f["kept"].append(undrop(x, l + 1, qs, pat))
+                    f.claims["kept"].append((l, state, pat))
     return f
 
 

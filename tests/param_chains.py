@@ -18,6 +18,19 @@ T48 = 281474981953537    # client.PLAINTEXT_MODULI[48]
 NAMED = ("q0_wide", "q_narrow_p_wide", "one_p_61", "barrett_edges")
 
 
+def q_last_wide(N, L):
+    """(q, p): Q = [45-bit, .., 45-bit, 60-bit], P = 55-bit -- the one chain whose DROPPED modulus is far wider than a kept one: the
+    limb drop's offset, a multiple of q_i that reaches (q_l - 1)/2, then spans about 2^14 multiples of q_i.  Not in NAMED (other files
+    parametrise over it): the tests of the limb drop ask for it by name through chain_by_name"""
+    assert L >= 2
+    return split(uniform(N, L - 1, 1 << 45) + uniform(N, 1) + uniform(N, L + 1, 1 << 55), L)
+
+
+def chain_by_name(N, L, name):
+    """named_chain, and q_last_wide under its own name"""
+    return q_last_wide(N, L) if name == "q_last_wide" else named_chain(N, L, name)
+
+
 def uniform(N, count, below=1 << 60):
     """the `count` largest primes = 1 (mod 2N) below `below`, descending (the oracle's own generator)"""
     return [int(v) for v in ob.gen_primes(N, count, below)]
