@@ -79,11 +79,29 @@ struct ModC {
 // (derivation in kernels_ntt_fast.hip).  Why assembly blocks (tools/gen_ntt16_bfly.py writes them): hipcc narrows multiplier
 // ops whose high half is dead to v_mul_lo_u32 (half the rate), lowers conditional subtractions to compare + select chains
 // through VCC (a VALU write of VCC or an SGPR needs two wait states before a VALU may read it on gfx950) and pads every short
-// asm statement with s_nop.  19-20 instructions per butterfly in both directions, 9 of them on the multiplier, 11 fixed scratch
-// registers at the top of the 128-register budget.  Conditional subtraction x in [0, 2m) -> [0, m) as t = x - m followed by a
-// select on the sign of t (v_bfi_b32 under an arithmetic-shift mask); the two 64-bit differences (u + 4q - v forward,
-// a + 4q - b inverse) as v_sub_co_u32 / v_subb_co_u32 with two independent instructions between the halves (the wait
-// states a VALU read of VCC needs after a VALU write); every other carry-out is discarded into VCC.
+// asm statement with s_nop.  19-20 instructions per inverse butterfly, 18-19 per forward one, 9 of them on the multiplier, 11
+// (forward: 9) fixed scratch registers at the top of the 128-register budget.  Conditional subtraction x in [0, 2m) -> [0, m)
+// as t = x - m followed by a select on the sign of t (v_bfi_b32 under an arithmetic-shift mask); the two 64-bit differences
+// (u + 4q - v forward, a + 4q - b inverse) as v_sub_co_u32 / v_subb_co_u32 with two independent instructions between the
+// halves (the wait states a VALU read of VCC needs after a VALU write); every other carry-out is discarded into VCC.
+//
+// The forward block is seeded (NTT16_CTS1 / NTT16_CTS1H, 19 / 18 instructions).  u + v, the product's remainder
+// b w + qe (2^64 - q) and u + 4q - v are all taken mod 2^64 and all lie below 8q < 2^63, so the low accumulation chain of the
+// remainder starts at bl wl + u instead of bl wl + 0 and ends as a' = u + v; b' = (2u + 4q) - a' with 2u + 4q < 12q < 2^64
+// (one v_lshl_add_u64 with shift 1).
+// Contract: a is a tied operand ("+v"), its halves are also passed as the 32-bit INPUTS al / ah, and the block relies on the
+// register allocator keeping those in the two registers of a's pair.  Once the chain has written the pair the block reads the
+// low half of a' through %[al] and both reads AND WRITES the high half through %[ah] (v_add_u32 %[ah], %[ah], c_lo).  Writing
+// an input operand is outside what the asm constraints express: the compiler believes ah's register unchanged, which is true
+// only because that register is the high half of the tied output.  Where the allocator chose otherwise the block would be
+// silently wrong, not merely slow.  So the aliasing is not a tuning check but part of the block's correctness:
+// tools/ct_seeded_listing.py asserts it for every block of the listing of kernels_ntt16.hip (profiles/ct_seeded/), and
+// tests/test_ct_seeded_listing.py runs that on every checkout as part of the default suite (no GPU needed); it must stay
+// there, and has to pass after any change to this file, to a kernel that calls bfly<false, ...>, or to the compiler.
+// -DNTT16_CT_SEEDED=0 builds the unseeded block (NTT16_CT1 / NTT16_CT1H, 20 / 19), which has no such dependence.
+#ifndef NTT16_CT_SEEDED
+#define NTT16_CT_SEEDED 1
+#endif
 #define NTT16_S(x) "s"(x)
 #define NTT16_V(x) "v"(x)
 #include "ntt16_bfly.inc"
@@ -99,7 +117,8 @@ struct ModC {
 template <bool INV, bool SC, bool H2 = SC && (!INV || NTT16_INV_H2)>
 __device__ __forceinline__ void bfly(u64 &x0, u64 &y0, const Tw &t0, const ModC &m)
 {
-    const u64 a0 = x0, b0 = y0;
+    u64 a0 = x0;  // forward, seeded: the tied operand -- a on entry, a' on exit
+    const u64 b0 = y0;
     if (INV) {
         u32 aol0, aoh0;
         u64 bo0;
@@ -113,8 +132,21 @@ __device__ __forceinline__ void bfly(u64 &x0, u64 &y0, const Tw &t0, const ModC 
             NTT16_GS1(NTT16_V);
         x0 = ((u64)aoh0 << 32) | aol0, y0 = bo0;
     } else {
-        u64 ao0;
         u32 bol0, boh0;
+#if NTT16_CT_SEEDED
+        u64 cs;  // takes one discarded carry-out (an SGPR pair, never read)
+        if (SC && H2)
+            NTT16_CTS1H(NTT16_S);
+        else if (SC)
+            NTT16_CTS1(NTT16_S);
+        else if (H2)
+            NTT16_CTS1H(NTT16_V);
+        else
+            NTT16_CTS1(NTT16_V);
+        (void)cs;
+        x0 = a0, y0 = ((u64)boh0 << 32) | bol0;
+#else
+        u64 ao0;
         if (SC && H2)
             NTT16_CT1H(NTT16_S);
         else if (SC)
@@ -124,6 +156,7 @@ __device__ __forceinline__ void bfly(u64 &x0, u64 &y0, const Tw &t0, const ModC 
         else
             NTT16_CT1(NTT16_V);
         x0 = ao0, y0 = ((u64)boh0 << 32) | bol0;
+#endif
     }
 }
 // two butterflies (call sites pair them; one block each: see tools/gen_ntt16_bfly.py on why they are not interleaved)

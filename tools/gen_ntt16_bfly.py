@@ -6,12 +6,14 @@ Issue costs on gfx950 (tools/microbench_ops.hip, cycles per wave64 instruction p
 v_mad_u64_u32, v_lshl_add_u64, v_lshrrev_b64, v_bfi_b32, v_mul_lo/hi_u32 alike -- 4.1-4.3; 32-bit VOP1/VOP2 2.0-2.5; a wave
 alone on its SIMD 4+ for everything; a 2-cycle instruction that follows a 4-cycle one costs 4 itself (tools/microbench_operands.hip), so
 the VOP1/VOP2 instructions are grouped.  Both blocks are 20 instructions, 19 where 2 sh is an operand (the inverse's last product is
-written straight to the output; 64-bit differences are borrow chains through VCC, see ct_stream).
+written straight to the output; 64-bit differences are borrow chains through VCC, see ct_stream).  The seeded forward block
+(cts_stream, what the kernels use; ct_stream is kept for -DNTT16_CT_SEEDED=0 builds) is 19 / 18: its remainder chain starts at u
+and ends as a'.
 
     python tools/gen_ntt16_bfly.py          (rewrites the .inc; the output is committed)
 
 Register use of stream i: 11 fixed VGPRs v[128 - 11 (i + 1) .. 128 - 11 i) (an asm operand cannot name the halves of a 64-bit pair, so every
-temporary whose halves are needed lives in a named register; all are in the clobber list).
+temporary whose halves are needed lives in a named register; all are in the clobber list); 9 in the seeded forward block.
 """
 import os
 
@@ -93,6 +95,74 @@ def ct_stream(i, h2=False):
     ]
 
 
+class RegsS:
+    """Fixed registers of stream i of the seeded forward block: 9.  The remainder's low chain accumulates in a's own registers
+    (a is dead once u exists), so the block has no acc pair; 2u + 4q is formed over u in place; the sign mask lives in qe's low
+    register until qe is written."""
+    n = 9
+
+    def __init__(self, i):
+        self.base = 128 - self.n * (i + 1) - int(os.environ.get('NTT16_BASE_SHIFT', '0'))
+        b = self.base
+        self.X = b           # 2 bh
+        self.T = b + 1       # t = a - 4q, then u in place, then 2u + 4q in place
+        self.U = self.T
+        self.CR = b + 3      # m1 / cr / cr >> 31
+        self.QE = b + 5
+        self.C = b + 7
+
+    def all(self):
+        return range(self.base, self.base + self.n)
+
+
+# The seeded forward block: a' = u + v and v = b w + qe (2^64 - q) are all arithmetic mod 2^64 on values whose true results lie
+# below 8q < 2^63, so the low chain of the remainder starts at bl wl + u instead of bl wl + 0 and ends as a' -- the parent's
+# a' = u + v (one v_lshl_add_u64) is gone.  b' = u + 4q - v = (2u + 4q) - a': 2u + 4q < 12q < 2^64 is one v_lshl_add_u64 with
+# shift 1, and the difference is the same borrow chain against a'.  A wrap in a partial sum of the chain is harmless mod 2^64.
+#
+# a is a tied operand (%[a]: read as a, written as a'); %[al] / %[ah] are (u32)a and (u32)(a >> 32) of the same variable, which
+# the register allocator keeps in the two halves of that pair -- an asm operand cannot name the halves of a pair, and the
+# borrow chain and the high-word add need them.  That allocation is checked in every instantiation's listing, not assumed:
+# tools/ct_seeded_listing.py.  The low chain writes %[a] (twice) only after the last read of a, al and ah as *inputs* (the
+# selects); from then on %[al] / %[ah] name the halves of the accumulating a'.
+#
+# The VCC wait states: v_sub_co needs a' low word, which needs qe, and every VCC-free instruction of the block but the
+# high-word add is an ancestor of qe or of the subtraction's minuend -- inside one block there is one VCC-free filler, not two.
+# The second is the last product of the high chain, which needs only qe: it discards its carry-out into an SGPR pair of its own
+# (%[cs], an output nobody reads) instead of VCC.  Tried first: the whole product in the low chain, `last mad (writes a') ->
+# v_sub_co -> v_subb_co`.  That tail has no filler at all (the minuend 2u + 4q must precede v_sub_co) and pays an s_nop 1; ending
+# the low chain early and patching the high word of a' through %[ah] between the halves of the difference pays none.
+def cts_stream(i, h2=False):
+    r = RegsS(i)
+    o = lambda name: "%%[%s%d]" % (name, i)
+    bl, bh = o("bl"), o("bh")
+    m = r.QE
+    return [
+        "v_mad_u64_u32 %s, vcc, %s, %s, 0" % (p(r.CR), bl, o("sh")),                  # m1 = bl sh
+        "v_lshl_add_u64 %s, %s, 0, %%[nq4]" % (p(r.T), o("a")),                       # t = a - 4q
+        "v_mad_u64_u32 %s, vcc, %s, %s, %s" % (p(r.CR), bh, o("sl"), p(r.CR)),        # cr = bh sl + m1
+        "v_mad_u64_u32 %s, vcc, %s, %s, 0" % (p(r.C), bl, o("wh")),                   # c = bl wh
+    ] + ([] if h2 else [
+        "v_lshlrev_b32 %s, 1, %s" % (v(r.X), bh),                                     # 2 bh
+    ]) + [
+        "v_ashrrev_i32 %s, 31, %s" % (v(m), v(r.T + 1)),                              # all ones iff t < 0
+        "v_bfi_b32 %s, %s, %s, %s" % (v(r.U), v(m), o("al"), v(r.T)),                 # u = t < 0 ? a : t   (in place)
+        "v_bfi_b32 %s, %s, %s, %s" % (v(r.U + 1), v(m), o("ah"), v(r.T + 1)),         # the last read of a
+        "v_mad_u64_u32 %s, vcc, %s, %s, %s" % (o("a"), bl, o("wl"), p(r.U)),          # a' = bl wl + u: the chain is seeded
+        "v_lshrrev_b64 %s, 31, %s" % (p(r.CR), p(r.CR)),
+        "v_mad_u64_u32 %s, vcc, %s, %s, %s" % (p(r.C), bh, o("wl"), p(r.C)),          # c += bh wl
+        ("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (p(r.QE), bh, o("sh2"), p(r.CR))) if h2 else     # qe = bh (2 sh) + (cr >> 31)
+        ("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (p(r.QE), v(r.X), o("sh"), p(r.CR))),  # the last read of b and of the twiddle
+        "v_mad_u64_u32 %s, vcc, %s, %%[nql], %s" % (o("a"), v(r.QE), o("a")),         # a' += qe_lo nq_lo: its low word is final
+        "v_mad_u64_u32 %s, vcc, %s, %%[nqh], %s" % (p(r.C), v(r.QE), p(r.C)),         # c += qe_lo nq_hi
+        "v_lshl_add_u64 %s, %s, 1, %%[q4]" % (p(r.U), p(r.U)),                        # 2u + 4q   (in place)
+        "v_sub_co_u32 %s, vcc, %s, %s" % (o("bol"), v(r.U), o("al")),                 # b' = 2u + 4q - a', low half
+        "v_mad_u64_u32 %s, %%[cs], %s, %%[nql], %s" % (p(r.C), v(r.QE + 1), p(r.C)),  # c += qe_hi nq_lo   (carry-out not into VCC)
+        "v_add_u32 %s, %s, %s" % (o("ah"), o("ah"), v(r.C)),                          # a' += c << 32
+        "v_subb_co_u32 %s, vcc, %s, %s, vcc" % (o("boh"), v(r.U + 1), o("ah")),       # b', high half
+    ]
+
+
 def gs_stream(i, h2=False):
     """h2: 2 sh is an operand of its own (wave-uniform twiddles: the doubling is a scalar instruction)"""
     r = Regs(i, True)
@@ -135,18 +205,27 @@ def interleave(streams):
     return out
 
 
-def emit(name, gs, nb, h2=False):
-    """h2: the twiddle's doubled high Shoup word is an operand (t.sh2)"""
-    lines = interleave([(gs_stream if gs else ct_stream)(i, h2) for i in range(nb)])
+def emit(name, gs, nb, h2=False, seeded=False):
+    """h2: the twiddle's doubled high Shoup word is an operand (t.sh2); seeded: the forward block whose chain starts at u"""
+    assert not (gs and seeded)
+    lines = interleave([(gs_stream if gs else cts_stream if seeded else ct_stream)(i, h2) for i in range(nb)])
     body = " \\\n".join('        "%s\\n\\t"' % ln for ln in lines)
     # forward: no early-clobber -- every input is read before the first output is written (checked below), so outputs may reuse
     # input registers.  inverse: a' is written before the twiddles are read -> its two halves are early-clobber outputs.
-    early = ("aol", "aoh") if gs else ()
-    late = ("bo",) if gs else ("ao", "bol", "boh")
+    # seeded forward: a' grows in the tied operand a, whose registers no other input can share; al / ah name its halves (see
+    # cts_stream), read as a before the first write of a and as a' after the last, never in between.
+    late = ("bo",) if gs else ("bol", "boh", "cs") if seeded else ("ao", "bol", "boh")
     first_out = min(k for k, ln in enumerate(lines) if any("%%[%s" % nm in ln for nm in late))
-    vgpr_inputs = ["%%[%s%d]" % (nm, i) for nm in ("a", "b", "al", "ah", "bl", "bh", "wl", "wh", "sl", "sh", "sh2") for i in range(nb)]
+    vgpr_inputs = ["%%[%s%d]" % (nm, i) for nm in (("b", "bl", "bh", "wl", "wh", "sl", "sh", "sh2") if seeded else
+                                                   ("a", "b", "al", "ah", "bl", "bh", "wl", "wh", "sl", "sh", "sh2")) for i in range(nb)]
     for ln in lines[first_out + 1:]:
         assert not any(op + "," in ln + "," or ln.endswith(op) for op in vgpr_inputs), "input read after an output was written: " + ln
+    if seeded:
+        for i in range(nb):
+            wr = [k for k, ln in enumerate(lines) if ln.split()[1] == "%%[a%d]," % i]
+            assert len(wr) == 2 and wr[-1] < first_out, "the low chain ends before the difference starts"
+            assert not any("%%[a%s%d]" % (hl, i) in ln for ln in lines[wr[0]:wr[-1] + 1] for hl in "lh"), "half of a read inside the low chain"
+            assert not any("%%[a%d]" % i in ln for ln in lines[wr[-1] + 1:]), "a' touched as a pair after its low chain"
     # VCC: written by the low half of a difference, read by its high half two or more instructions later, untouched in between
     for k, ln in enumerate(lines):
         if ln.startswith("v_sub_co_u32"):
@@ -154,6 +233,8 @@ def emit(name, gs, nb, h2=False):
             assert j - k - 1 >= 2 and not any("vcc" in x for x in lines[k + 1:j]), "VCC hazard: " + ln
     if gs:
         outs = ", ".join('[aol%d] "=&v"(aol%d), [aoh%d] "=&v"(aoh%d), [bo%d] "=v"(bo%d)' % ((i,) * 6) for i in range(nb))
+    elif seeded:
+        outs = ", ".join('[a%d] "+v"(a%d), [bol%d] "=v"(bol%d), [boh%d] "=v"(boh%d)' % ((i,) * 6) for i in range(nb)) + ', [cs] "=s"(cs)'
     else:
         outs = ", ".join('[ao%d] "=v"(ao%d), [bol%d] "=v"(bol%d), [boh%d] "=v"(boh%d)' % ((i,) * 6) for i in range(nb))
     twc = "TWC"
@@ -161,6 +242,8 @@ def emit(name, gs, nb, h2=False):
     for i in range(nb):
         if gs:
             ins.append('[a%d] "v"(a%d), [b%d] "v"(b%d), [bl%d] "v"((u32)b%d), [bh%d] "v"((u32)(b%d >> 32))' % ((i,) * 8))
+        elif seeded:
+            ins.append('[al%d] "v"((u32)a%d), [ah%d] "v"((u32)(a%d >> 32)), [bl%d] "v"((u32)b%d), [bh%d] "v"((u32)(b%d >> 32))' % ((i,) * 8))
         else:
             ins.append('[a%d] "v"(a%d), [al%d] "v"((u32)a%d), [ah%d] "v"((u32)(a%d >> 32)), [bl%d] "v"((u32)b%d), [bh%d] "v"((u32)(b%d >> 32))'
                        % ((i,) * 10))
@@ -168,7 +251,7 @@ def emit(name, gs, nb, h2=False):
         if h2:
             ins.append('[sh2%d] %s(t%d.sh2)' % (i, twc, i))
     ins.append('[nql] "s"(m.nql), [nqh] "s"(m.nqh), [nq4] "s"(m.nq4), [q4] "s"(m.q4)')
-    clob = ['"vcc"'] + ['"v%d"' % x for i in range(nb) for x in Regs(i, gs).all()]
+    clob = ['"vcc"'] + ['"v%d"' % x for i in range(nb) for x in (RegsS(i) if seeded else Regs(i, gs)).all()]
     return ("#define %s(TWC) \\\n    asm( \\\n%s \\\n        : %s \\\n        : %s \\\n        : %s)\n"
             % (name, body, outs, ", \\\n          ".join(ins), ", ".join(clob)))
 
@@ -177,10 +260,13 @@ def main():
     text = ("// ntt16_bfly.inc -- GENERATED by tools/gen_ntt16_bfly.py; do not edit.  See that script and ntt16_kernel.h.\n"
             "// NTT16_CT1(TWC): one forward butterfly on (a0, b0, t0) -> (ao0, {bol0, boh0}); NTT16_GS1(TWC): one inverse butterfly\n"
             "// -> ({aol0, aoh0}, bo0).  TWC = NTT16_S (wave-uniform twiddles, SGPR operands) or NTT16_V (per-lane twiddles); m = ModC.\n"
-            "// NTT16_CT1H(TWC) / NTT16_GS1H(TWC): 2 sh is an operand of its own (t0.sh2) -- one instruction fewer.\n")
+            "// NTT16_CT1H(TWC) / NTT16_GS1H(TWC): 2 sh is an operand of its own (t0.sh2) -- one instruction fewer.\n"
+            "// NTT16_CTS1(TWC) / NTT16_CTS1H(TWC): the seeded forward butterfly, one instruction fewer again: (a0 tied, b0, t0) ->\n"
+            "// (a0, {bol0, boh0}); cs is an SGPR pair that takes one discarded carry-out.\n")
     # one butterfly per block: measured, a wave issues at most every other VALU slot whatever its instruction-level parallelism
     # (interleaving two butterflies per block changed nothing but the register count), so parallelism comes from waves
     text += emit("NTT16_CT1", False, 1) + emit("NTT16_GS1", True, 1) + emit("NTT16_CT1H", False, 1, True) + emit("NTT16_GS1H", True, 1, True)
+    text += emit("NTT16_CTS1", False, 1, seeded=True) + emit("NTT16_CTS1H", False, 1, True, seeded=True)
     with open(OUT, "w") as f:
         f.write(text)
     print("wrote", OUT)
