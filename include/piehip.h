@@ -456,7 +456,7 @@ int piehip_client_decrypt_deg2(piehip_handle h, const uint64_t *sk, const uint64
  *                            which is sized by the settings at the time of the call (ask again after changing one).
  *                            Per handle: a query slot (piehip_attach_database) has its own setting.  Works with query batches and
  *                            per-query keys, seeded queries (stage A is untouched), one and two queues, the host-results stagger.
- *   piehip_get_chain_limbs   the setting.
+ *   piehip_get_chain_limbs   the setting (with a chain schedule, below: the limb count of the last product that runs).
  * Choosing Lc.  The library does not check noise.  The budget after the drop is min(budget, log2 Q' - log2 t - log2(N + 1) - 1) bits,
  * and the chain then costs what it costs on any context of Lc limbs.  Budgets in bits as the CPU oracle reports them (its readout
  * saturates at 57-58), K = 2, fresh queries (tests/test_chain_limbs.py):
@@ -471,6 +471,36 @@ int piehip_client_decrypt_deg2(piehip_handle h, const uint64_t *sk, const uint64
  * look the symbols up; nothing of 102 changed. */
 int piehip_set_chain_limbs(piehip_handle h, uint32_t Lc);
 int piehip_get_chain_limbs(piehip_handle h, uint32_t *Lc);
+/* Chain schedule: a limb count per product.  The products of a chain of K >= 3 do not need the same number of limbs -- the last one
+ * has the least noise budget left to protect -- so the drop can also sit BETWEEN the products.
+ *   piehip_set_chain_schedule   Lc[0] >= Lc[1] >= .. >= Lc[n-1], every entry in [1, L], 1 <= n <= 7.  Product hf (1-based, hf < K) runs
+ *                               on l_hf = Lc[min(hf, n) - 1] limbs; l_last is the level of the last product that runs.  In exact integers:
+ *                               1. stage A on all L limbs;
+ *                               2. x = drop(acc[0], L -> l_1);
+ *                               3. for hf = 1 .. K - 1: where l_hf is below the level of x, x = mod_reduce(x, l_hf) on the level
+ *                                  context of l_{hf-1} limbs; y = mod_reduce(acc[hf], l_hf) on the handle's context; x = the product
+ *                                  of x and y on the level context of l_hf limbs, with the key evk[:l_hf, :, :l_hf] (without the last
+ *                                  relinearisation, piehip_set_result_relin(0), the last product is the tensor product alone);
+ *                               4. the mask multiply with the masks' first l_last limbs; rows [b][nq][ncomp][min(keep, l_last)][N].
+ *                               mod_reduce is piehip_mod_reduce's formula.  piehip_set_chain_limbs(h, x) is the schedule {x}; entries
+ *                               behind the last product that runs change nothing; K = 1 is accepted and changes nothing.
+ *   piehip_get_chain_schedule   the schedule as it was set (n entries; PIEHIP_EINVAL when cap < n).  piehip_get_chain_limbs answers
+ *                               l_last, and every entry point that sizes result rows means l_last.
+ * Per handle, like chain limbs: a query slot has its own schedule.  Everything chain limbs works with, a schedule works with.
+ * Choosing a schedule.  The library checks no noise.  Budgets in bits as the CPU oracle reports them, K = 3, b = 1, fresh queries
+ * (tests/test_chain_schedule.py prints them); (l_1, l_2): product 1 on l_1 limbs, product 2 and the mask multiply on l_2:
+ *     N = 16384, L = 4, t = 4296540161, E = 14   (4,4) 38 | (4,3) 38 | (3,3), (3,2), (4,2): 0, WRONG plaintext
+ *     N = 32768, L = 6, t = 4296540161, E = 30   (6,6) 56 | (6,5) 56 | (5,5) 56 | (5,4) 57 | (6,4) 57 | (4,4) 53 | (4,3) 38 | (5,3) 39 |
+ *                                                (6,3) 39 | (3,3): 0, WRONG plaintext
+ *     N = 4096,  L = 4, t = 65537,      E = 4    (4,4) 57 | (4,3) 57 | (3,3) 48 | (3,2) 14 | (4,2) 14 | (2,2): 0, WRONG plaintext
+ * On the first row no uniform setting below L decrypts and (4,3) keeps the full run's 38 bits; on the second the lowest uniform
+ * setting is (4,4) and (4,3) still leaves 38 bits.  Every other entry named here has the full run's plaintext.
+ * Rule of thumb: give the last product one limb fewer than the lowest uniform setting that still decrypts, and every product before it
+ * that setting; check the budget of the real parameters on a client before relying on it.
+ * PIEHIP_EINVAL: n = 0 or n > 7, an entry of 0 or above L, an increasing pair.  PIEHIP_ESTATE: every refusal of chain limbs above,
+ * whenever any entry is below L.  piehip_fhepie_* ignores the setting.  Added without a new version number: look the symbols up. */
+int piehip_set_chain_schedule(piehip_handle h, const uint32_t *Lc /*[n]*/, uint32_t n);
+int piehip_get_chain_schedule(piehip_handle h, uint32_t *Lc /*[cap]*/, uint32_t cap, uint32_t *n);
 
 /* ---- query slices: stage A sharded by inner hash function and limb --------------------------------------
  * The reference evaluates, per bin layer, K inner products over E index ciphertexts (BatchedFHEHIPPIE.cpp:96-116) and then multiplies

@@ -239,7 +239,9 @@ bool launch_limb_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, const u64 *in
 // The limb drop in front of the product chain, on npoly polynomials data[npoly][L][N] in COEFFICIENT format as the parent's inverse
 // transform left them (fold: outer stage pending): IN PLACE, the first `keep` limbs of every polynomial become the dropped
 // polynomial's, canonical, nothing pending; the limbs behind them are left alone.  1 <= keep < L <= MAX_L; false otherwise
-bool launch_chain_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, u64 *data, u32 npoly, hipStream_t st, bool fold);
+// per, gstride: the polynomials lie in groups of `per` neighbours, gstride words from group to group (0: one packed array)
+bool launch_chain_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, u64 *data, u32 npoly, hipStream_t st, bool fold, u32 per = 0,
+                       size_t gstride = 0);
 // launch_expand_both on a level context (dc, L: the level's) for plain operands -- canonical, nothing pending -- with a polynomial
 // distance per operand (six, siy); fold: the store side alone (the forward transform that follows is a folded one).  L < MAX_L
 bool launch_expand_both_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, size_t six, const u64 *y, size_t sy, size_t siy,
@@ -251,6 +253,11 @@ bool launch_expand_both_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, s
 bool expand_both_drop_applies(u32 L, u32 Lc);
 bool launch_expand_both_drop(const DevConsts *dc_parent, const DevConsts *dc_level, u32 N, u32 L, u32 Lc, const u64 *x, size_t sx, size_t six,
                              bool x_drop, const u64 *y, size_t sy, size_t siy, u32 n_outer, u64 *out, hipStream_t st);
+// Chain schedule: X is the product before, packed on Lx <= L limbs as level Lx's folded inverse transform left it (dc_x: that
+// level's constants), and is dropped to Lc like the accumulator Y.  Lx = L is launch_expand_both_drop with x_drop
+bool expand_both_drop_xy_applies(u32 L, u32 Lx, u32 Lc);
+bool launch_expand_both_drop_xy(const DevConsts *dc_parent, const DevConsts *dc_x, const DevConsts *dc_level, u32 N, u32 L, u32 Lx, u32 Lc,
+                                const u64 *x, size_t sx, size_t six, const u64 *y, size_t sy, size_t siy, u32 n_outer, u64 *out, hipStream_t st);
 // out[r][p] = in[r][map[p]] for nrows limbs
 void launch_permute(u32 N, const u64 *in, const u32 *map, u64 *out, u32 nrows, hipStream_t st);
 // packed encoding: slots[npt][B] -> u[npt][N] residues mod t at their EVALUATION positions

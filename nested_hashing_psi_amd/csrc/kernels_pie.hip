@@ -1449,15 +1449,18 @@ __device__ __forceinline__ void drop_limbs(const DevConsts *dc, u64 (&c)[NP][L])
 // as the inverse transform left them -- FOLD: outer stage pending, residues in [0, 4q) -- are overwritten IN PLACE, at the parent's
 // strides, by their first KEEP limbs after the drop: canonical, nothing pending.  Limbs KEEP .. L - 1 keep what they held.  A thread
 // owns its coefficient's (FOLD: its coefficient pair's) column of every limb, so nothing it overwrites is read by another.
+// The polynomials come in groups of `per` neighbours, `gstride` words from one group to the next: the accumulators of some inner hash
+// functions out of rows [rows][K][2][L][N] (chain schedule: each product has its own level), or per = npoly for one packed array.
 template <bool FOLD, u32 L, u32 KEEP>
-__global__ void __launch_bounds__(TPB) chain_drop_kernel(const DevConsts *__restrict__ dc, u32 N, u32 blocks_per_poly, u64 *data)
+__global__ void __launch_bounds__(TPB) chain_drop_kernel(const DevConsts *__restrict__ dc, u32 N, u32 blocks_per_poly, u64 *data, u32 per,
+                                                         size_t gstride)
 {
     constexpr int NP = FOLD ? 2 : 1;
     const u32 poly = blockIdx.x / blocks_per_poly;
     const u32 n = (blockIdx.x % blocks_per_poly) * TPB + threadIdx.x;
     const u32 H = N / 2;
     if (n >= (FOLD ? H : N)) return;
-    u64 *p = data + (size_t)poly * L * N + n;
+    u64 *p = data + (size_t)(poly / per) * gstride + (size_t)(poly % per) * L * N + n;
     u64 c[NP][L];
 #pragma unroll
     for (u32 i = 0; i < L; i++) {
@@ -1473,15 +1476,17 @@ __global__ void __launch_bounds__(TPB) chain_drop_kernel(const DevConsts *__rest
         if (FOLD) p[(size_t)i * N + H] = c[NP - 1][i];
     }
 }
-bool launch_chain_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, u64 *data, u32 npoly, hipStream_t st, bool fold)
+bool launch_chain_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, u64 *data, u32 npoly, hipStream_t st, bool fold, u32 per, size_t gstride)
 {
     if (keep < 1 || keep >= L || L > MAX_L || !npoly) return false;
+    if (!per) per = npoly, gstride = 0;   // one packed array
+    if (npoly % per) return false;
     const u32 bpp = ((fold ? N / 2 : N) + TPB - 1) / TPB;
     const dim3 grid(bpp * npoly), block(TPB);
-#define CDROP_(L_, K_)                                                                                              \
-    case (L_) * 8 + (K_):                                                                                           \
-        if (fold) hipLaunchKernelGGL((chain_drop_kernel<true, L_, K_>), grid, block, 0, st, dc, N, bpp, data);      \
-        else hipLaunchKernelGGL((chain_drop_kernel<false, L_, K_>), grid, block, 0, st, dc, N, bpp, data);          \
+#define CDROP_(L_, K_)                                                                                                            \
+    case (L_) * 8 + (K_):                                                                                                         \
+        if (fold) hipLaunchKernelGGL((chain_drop_kernel<true, L_, K_>), grid, block, 0, st, dc, N, bpp, data, per, gstride);      \
+        else hipLaunchKernelGGL((chain_drop_kernel<false, L_, K_>), grid, block, 0, st, dc, N, bpp, data, per, gstride);          \
         return true
     switch (L * 8 + keep) {
         CDROP_(2, 1);
@@ -1615,16 +1620,42 @@ __global__ void __launch_bounds__(TPB) expand_both_drop_kernel(const DevConsts *
     else
         expand_body<false, true, LC, true, true>(dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
-// the (L, Lc) pairs the fused kernel is built for: Lc = L - 1 for every L, and the further pairs that stay free of scratch
+// Chain schedule (include/piehip.h): a product of K >= 3 whose level LC lies below the level LX of the product before it.  Y is an
+// accumulator on the handle's LY limbs (dcy); X is that earlier product, packed on LX limbs as level LX's folded inverse transform
+// left it, loaded and dropped with level LX's constants (dcx); both are converted with level LC's (dcl).  LX = LY -- the earlier
+// product ran on every limb -- is expand_both_drop_kernel<LY, LC, true> itself, X at the product's strides.
+template <u32 LY, u32 LX, u32 LC>
+__global__ void __launch_bounds__(TPB) expand_both_drop_xy_kernel(const DevConsts *__restrict__ dcy, const DevConsts *__restrict__ dcx,
+                                                                  const DevConsts *__restrict__ dcl, u32 N, const u64 *__restrict__ x, size_t sx,
+                                                                  size_t six, const u64 *__restrict__ y, size_t sy, size_t siy,
+                                                                  u64 *__restrict__ out, u32 n_outer)
+{
+    if (blockIdx.y < 2 * n_outer)
+        expand_drop_body<true, LY, LC>(dcy, dcl, N, y, sy, siy, out, 2, blockIdx.y);
+    else
+        expand_drop_body<false, LX, LC>(dcx, dcl, N, x, sx, six, out, 0, blockIdx.y - 2 * n_outer);
+}
+// the (L, Lc) pairs the fused kernel is built for: Lc = L - 1 for every L, and the further pairs that stay free of scratch; the
+// (LY, LX, LC) triples of the chain schedule's form
 #ifndef PIEHIP_CHAIN_DROP_FUSED
 #define PIEHIP_CHAIN_DROP_FUSED 1
 #endif
-#define PIE_CHAIN_DROP_PAIRS(X_) X_(2, 1) X_(3, 2) X_(4, 3) X_(5, 4) X_(6, 5) X_(7, 6) X_(4, 2)
+#define PIE_CHAIN_DROP_PAIRS(X_) X_(2, 1) X_(3, 2) X_(4, 3) X_(5, 4) X_(6, 5) X_(7, 6) X_(4, 2) X_(6, 4)
+#define PIE_CHAIN_DROP_TRIPLES(X_) X_(4, 3, 2) X_(6, 5, 4) X_(6, 4, 3)
 bool expand_both_drop_applies(u32 L, u32 Lc)
 {
     if (!PIEHIP_CHAIN_DROP_FUSED) return false;
 #define APPL_(L_, C_) if (L == L_ && Lc == C_) return true;
     PIE_CHAIN_DROP_PAIRS(APPL_)
+#undef APPL_
+    return false;
+}
+bool expand_both_drop_xy_applies(u32 L, u32 Lx, u32 Lc)
+{
+    if (!PIEHIP_CHAIN_DROP_FUSED) return false;
+    if (Lx == L) return expand_both_drop_applies(L, Lc);
+#define APPL_(L_, X_, C_) if (L == L_ && Lx == X_ && Lc == C_) return true;
+    PIE_CHAIN_DROP_TRIPLES(APPL_)
 #undef APPL_
     return false;
 }
@@ -1643,6 +1674,22 @@ bool launch_expand_both_drop(const DevConsts *dc_parent, const DevConsts *dc_lev
     }
     PIE_CHAIN_DROP_PAIRS(EBD_)
 #undef EBD_
+    return false;
+}
+bool launch_expand_both_drop_xy(const DevConsts *dc_parent, const DevConsts *dc_x, const DevConsts *dc_level, u32 N, u32 L, u32 Lx, u32 Lc,
+                                const u64 *x, size_t sx, size_t six, const u64 *y, size_t sy, size_t siy, u32 n_outer, u64 *out, hipStream_t st)
+{
+    if (Lx == L) return launch_expand_both_drop(dc_parent, dc_level, N, L, Lc, x, sx, six, true, y, sy, siy, n_outer, out, st);
+    if (!expand_both_drop_xy_applies(L, Lx, Lc)) return false;
+    dim3 grid((N / 2 + TPB - 1) / TPB, n_outer * 4);
+#define EBX_(L_, X_, C_)                                                                                                                  \
+    if (L == L_ && Lx == X_ && Lc == C_) {                                                                                               \
+        hipLaunchKernelGGL((expand_both_drop_xy_kernel<L_, X_, C_>), grid, dim3(TPB), 0, st, dc_parent, dc_x, dc_level, N, x, sx, six, y, sy, \
+                           siy, out, n_outer);                                                                                           \
+        return true;                                                                                                                     \
+    }
+    PIE_CHAIN_DROP_TRIPLES(EBX_)
+#undef EBX_
     return false;
 }
 

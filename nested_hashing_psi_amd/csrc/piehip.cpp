@@ -269,7 +269,8 @@ int piehip_create(piehip_handle *out, uint32_t N, uint32_t L, uint64_t t, const 
                                      std::to_string(ndev) + " devices): libpiehip has no CPU fallback");
     }
     h->device = device;
-    h->res_limbs = h->chain_limbs = L;
+    h->res_limbs = L;
+    h->chain_sched[0] = L, h->chain_n = 1;
 #define CHK_(expr)                                                                          \
     do {                                                                                    \
         hipError_t e_ = (expr);                                                             \
@@ -1104,92 +1105,113 @@ int piehip_get_result_components(piehip_handle h, uint32_t *ncomp)
     return PIEHIP_OK;
 }
 
-// Chain limbs (include/piehip.h): the level context's copies of the keys and masks in the handle's context -- the limb prefix
+// Chain limbs (include/piehip.h): a level context's copies of the keys and masks in the handle's context -- the limb prefix
 // evk[i][c][j], i, j < Lc, of every EvalMult key and the first Lc limbs of the masks, each with its lane-ordered twin where the
 // level's plan has a lane order (its own map: a prefix of a mixed chain may take other routes than the parent).  Copied on the
 // handle's stream whenever the key or the database is set and when the setting changes: 8 and 7 MiB at C3 and as much again for
 // the twins.  The other choice -- reading the parent's arrays in place through their strides -- would have put two more strides
 // into the key-switch MAC, whose instantiations must stay what they are.
+// With a schedule: the keys for every level below L on which a product of the chain runs, the masks for the last product's level
+// alone (a level that a later product leaves behind multiplies no mask).
 extern "C++" int piehip::level_sync(piehip_ctx *h)
 {
-    LevelCtx *lv = h->level;
-    if (!lv || h->chain_limbs >= h->hp.L) return PIEHIP_OK;
+    if (h->chain_floor() >= h->hp.L) return PIEHIP_OK;
     const ChainCtx &top = h->cx;
-    ChainCtx &c = lv->cx;
-    const size_t row = c.LN() * sizeof(u64);
-    // n blocks of `rows` rows of L N words, SW words apart at src -> blocks of as many rows of Lc N words, and their twin.  A copy
-    // that is not made (nothing at src, no memory) is not kept: the level then has none, as the handle has none
-    auto copy = [&](const u64 *src, size_t SW, u32 n, size_t rows, u64 **dst, u64 **twin, size_t *cap) -> int {
-        const size_t bw = rows * c.LN();
-        const bool grow = *cap < n * bw;
-        if (!src || !n || grow) {
-            dev_free(dst);
-            dev_free(twin);
-            *cap = 0;
-        }
-        if (!src || !n) return PIEHIP_OK;
-        int rc = grow ? dev_alloc(dst, n * bw) : PIEHIP_OK;
-        hipError_t e = hipSuccess;
-        for (u32 i = 0; i < n && !rc && e == hipSuccess; i++)
-            e = hipMemcpy2DAsync(*dst + i * bw, row, src + i * SW, top.LN() * sizeof(u64), row, rows, hipMemcpyDeviceToDevice, h->stream);
-        if (e != hipSuccess) rc = fail(PIEHIP_EHIP, std::string("level_sync: ") + hipGetErrorString(e));
-        if (!rc) rc = lane_twin(h, c, *dst, twin, n * rows * c.L);
-        if (rc) {
-            dev_free(dst);
-            dev_free(twin);
-        }
-        if (rc || grow) *cap = rc ? 0 : n * bw;
-        return rc;
-    };
-    int rc;
-    if ((rc = copy(top.evk, 0, 1, 2 * c.L, &c.evk, &c.evk_sigma, &lv->evk_cap))) return rc;
-    if ((rc = copy(top.evkq, top.key_words(), h->evkq_n, 2 * c.L, &c.evkq, &c.evkq_sigma, &lv->evkq_cap))) return rc;
-    if ((rc = copy(top.masks, top.LN(), h->b ? 1 : 0, h->b, &c.masks, &c.masks_sigma, &lv->masks_cap))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
+    const u32 products = h->K >= 2 ? h->K - 1 : 1, last = h->chain_last();
+    bool any = false;
+    for (u32 hf = 1; hf <= std::min(products, h->chain_n); hf++) {
+        const u32 Lc = h->chain_level(hf);
+        if (Lc >= h->hp.L || (hf > 1 && Lc == h->chain_level(hf - 1))) continue;
+        LevelCtx *lv = h->levels.at(Lc).get();
+        ChainCtx &c = lv->cx;
+        const size_t row = c.LN() * sizeof(u64);
+        // n blocks of `rows` rows of L N words, SW words apart at src -> blocks of as many rows of Lc N words, and their twin.  A copy
+        // that is not made (nothing at src, no memory) is not kept: the level then has none, as the handle has none
+        auto copy = [&](const u64 *src, size_t SW, u32 n, size_t rows, u64 **dst, u64 **twin, size_t *cap) -> int {
+            const size_t bw = rows * c.LN();
+            const bool grow = *cap < n * bw;
+            if (!src || !n || grow) {
+                dev_free(dst);
+                dev_free(twin);
+                *cap = 0;
+            }
+            if (!src || !n) return PIEHIP_OK;
+            int rc = grow ? dev_alloc(dst, n * bw) : PIEHIP_OK;
+            hipError_t e = hipSuccess;
+            for (u32 i = 0; i < n && !rc && e == hipSuccess; i++)
+                e = hipMemcpy2DAsync(*dst + i * bw, row, src + i * SW, top.LN() * sizeof(u64), row, rows, hipMemcpyDeviceToDevice, h->stream);
+            if (e != hipSuccess) rc = fail(PIEHIP_EHIP, std::string("level_sync: ") + hipGetErrorString(e));
+            if (!rc) rc = lane_twin(h, c, *dst, twin, n * rows * c.L);
+            if (rc) {
+                dev_free(dst);
+                dev_free(twin);
+            }
+            if (rc || grow) *cap = rc ? 0 : n * bw;
+            return rc;
+        };
+        int rc;
+        if ((rc = copy(top.evk, 0, 1, 2 * c.L, &c.evk, &c.evk_sigma, &lv->evk_cap))) return rc;
+        if ((rc = copy(top.evkq, top.key_words(), h->evkq_n, 2 * c.L, &c.evkq, &c.evkq_sigma, &lv->evkq_cap))) return rc;
+        if (Lc == last && (rc = copy(top.masks, top.LN(), h->b ? 1 : 0, h->b, &c.masks, &c.masks_sigma, &lv->masks_cap))) return rc;
+        any = true;
+    }
+    if (any) HIPCHK(hipStreamSynchronize(h->stream));
     return PIEHIP_OK;
 }
 
-// The setting of a handle.  The level context is built when the setting first takes a value and kept: going back and forth
+// The setting of a handle.  A level context is built when the setting first names its limb count and kept: going back and forth
 // allocates nothing (the copies of keys and masks are made again, on the handle's stream).
-int piehip_set_chain_limbs(piehip_handle h, uint32_t Lc)
+int piehip_set_chain_schedule(piehip_handle h, const uint32_t *Lc, uint32_t n)
 {
     NEED(h);
     const u32 L = h->hp.L;
-    if (Lc < 1 || Lc > L) return fail(PIEHIP_EINVAL, "set_chain_limbs: Lc must be between 1 and L");
-    if (Lc < L && h->use_graph)
-        return fail(PIEHIP_ESTATE, "set_chain_limbs: a handle that replays a captured graph (piehip_set_graph) runs the product chain on every limb");
-    if (Lc < L && h->slice.on) return fail(PIEHIP_ESTATE, "set_chain_limbs: a query-sliced handle runs the product chain on every limb");
-    HIPCHK(hipSetDevice(h->device));
-    if (Lc == L) {
-        h->chain_limbs = L;
-        h->level = nullptr;
-        return PIEHIP_OK;
+    if (!Lc) return fail(PIEHIP_EINVAL, "set_chain_schedule: null schedule");
+    if (n < 1 || n > MAX_CHAIN_SCHED) return fail(PIEHIP_EINVAL, "set_chain_schedule: between 1 and 7 entries");
+    for (u32 i = 0; i < n; i++) {
+        if (Lc[i] < 1 || Lc[i] > L) return fail(PIEHIP_EINVAL, "set_chain_limbs: Lc must be between 1 and L");
+        if (i && Lc[i] > Lc[i - 1]) return fail(PIEHIP_EINVAL, "set_chain_schedule: the limb counts must not increase along the chain");
     }
-    auto it = h->levels.find(Lc);
-    if (it == h->levels.end()) {
+    const bool below = Lc[n - 1] < L;
+    if (below && h->use_graph)
+        return fail(PIEHIP_ESTATE, "set_chain_limbs: a handle that replays a captured graph (piehip_set_graph) runs the product chain on every limb");
+    if (below && h->slice.on) return fail(PIEHIP_ESTATE, "set_chain_limbs: a query-sliced handle runs the product chain on every limb");
+    HIPCHK(hipSetDevice(h->device));
+    for (u32 i = 0; i < n; i++) {
+        if (Lc[i] == L || h->levels.count(Lc[i])) continue;
         std::unique_ptr<LevelCtx> lv(new LevelCtx());
-        std::string err = lv->hp.init(h->hp.N, Lc, h->hp.t, h->hp.moduli.data(), h->hp.moduli.data() + L);
+        std::string err = lv->hp.init(h->hp.N, Lc[i], h->hp.t, h->hp.moduli.data(), h->hp.moduli.data() + L);
         if (!err.empty()) return fail(PIEHIP_EINVAL, "set_chain_limbs: " + err);
         err = context_tables(h, lv->hp, lv->plan, &lv->d_dc, &lv->d_sigma_inv, nullptr);
         if (!err.empty()) return fail(PIEHIP_EHIP, "set_chain_limbs: " + err);   // (what was uploaded stays in dev_tables and goes with the handle)
         lv->plan.max_slots = h->plan.max_slots;
         lv->cx.d_dc = lv->d_dc, lv->cx.plan = &lv->plan, lv->cx.d_sigma_inv = lv->d_sigma_inv;
-        lv->cx.N = h->hp.N, lv->cx.L = Lc, lv->cx.M = lv->hp.M;
-        it = h->levels.emplace(Lc, std::move(lv)).first;
+        lv->cx.N = h->hp.N, lv->cx.L = Lc[i], lv->cx.M = lv->hp.M;
+        h->levels.emplace(Lc[i], std::move(lv));
     }
-    const u32 before = h->chain_limbs;
-    LevelCtx *const lv_before = h->level;
-    h->chain_limbs = Lc;
-    h->level = it->second.get();
+    u32 before[MAX_CHAIN_SCHED];
+    const u32 n_before = h->chain_n;
+    std::copy(h->chain_sched, h->chain_sched + MAX_CHAIN_SCHED, before);
+    std::copy(Lc, Lc + n, h->chain_sched);
+    h->chain_n = n;
     const int rc = level_sync(h);
-    if (rc) h->chain_limbs = before, h->level = lv_before;
+    if (rc) std::copy(before, before + MAX_CHAIN_SCHED, h->chain_sched), h->chain_n = n_before;
     return rc;
 }
+int piehip_get_chain_schedule(piehip_handle h, uint32_t *Lc, uint32_t cap, uint32_t *n)
+{
+    NEED_RO(h);
+    if (!n || (!Lc && cap)) return fail(PIEHIP_EINVAL, "null out");
+    if (cap < h->chain_n) return fail(PIEHIP_EINVAL, "get_chain_schedule: room for fewer entries than the schedule has");
+    std::copy(h->chain_sched, h->chain_sched + h->chain_n, Lc);
+    *n = h->chain_n;
+    return PIEHIP_OK;
+}
+int piehip_set_chain_limbs(piehip_handle h, uint32_t Lc) { return piehip_set_chain_schedule(h, &Lc, 1); }
 int piehip_get_chain_limbs(piehip_handle h, uint32_t *Lc)
 {
     NEED_RO(h);
     if (!Lc) return fail(PIEHIP_EINVAL, "null out");
-    *Lc = h->chain_limbs;
+    *Lc = h->chain_last();
     return PIEHIP_OK;
 }
 

@@ -157,6 +157,7 @@ struct ChainCtx {
 // tables, plan with its routes and fusions -- behind a ChainCtx whose keys and masks are the limb prefixes of the handle's, copied
 // when the key or the database is set (piehip.cpp, level_sync).  Built when the setting first takes the value Lc and kept with the
 // handle; its device tables are freed with the handle's (dev_tables).
+static const u32 MAX_CHAIN_SCHED = 7;   // entries of a chain schedule (include/piehip.h)
 struct LevelCtx {
     HostParams hp;
     DevConsts *d_dc = nullptr;
@@ -222,10 +223,11 @@ struct piehip_ctx {
     u32 hk = 0, he = 0, hb = 0;  // table dimensions ([k][e][K][hb][E]; hb = all bin layers, of which this handle keeps b)
     piehip::NttPlan plan;
     piehip::ChainCtx cx;         // the handle's own context: d_dc, plan, d_sigma_inv above, and the handle's keys and masks
-    // piehip_set_chain_limbs: with chain_limbs < L the product chain of run() works on `level`, the level context of the first
-    // chain_limbs limbs; every level the handle has been set to stays in `levels`
-    u32 chain_limbs = 0;
-    piehip::LevelCtx *level = nullptr;
+    // piehip_set_chain_schedule (piehip_set_chain_limbs: a schedule of one entry): product hf of run()'s chain, 1-based, works on the
+    // level context of the first chain_level(hf) limbs -- the handle's own context at L.  Every level the handle has been set to stays
+    // in `levels`
+    u32 chain_sched[piehip::MAX_CHAIN_SCHED] = {};   // non-increasing, every entry in [1, L]
+    u32 chain_n = 0;
     std::map<u32, std::unique_ptr<piehip::LevelCtx>> levels;
     // keys / database / inputs
     bool db_borrowed = false;  // piehip_attach_database: cx.evk*, d_db, cx.masks* belong to another handle (never freed or written here)
@@ -282,14 +284,20 @@ struct piehip_ctx {
     size_t LN() const { return (size_t)hp.L * hp.N; }
     u32 res_comps(u32 K_) const { return (!res_relin && K_ >= 2) ? 3u : 2u; }   // components of a result row for K_ inner hash functions
     u32 res_comps() const { return res_comps(K); }
+    u32 chain_level(u32 hf) const { return chain_sched[std::min(hf, chain_n) - 1]; }   // limbs of product hf = 1, 2, ..
+    // ... of the last product that runs (K - 1; a handle without products answers as one with a single product would), which are
+    // the mask multiply's and the result rows'; and the lowest entry: below L, the handle refuses what a chain on fewer limbs refuses
+    u32 chain_last() const { return chain_level(K >= 2 ? K - 1 : 1); }
+    u32 chain_floor() const { return chain_sched[chain_n - 1]; }
+    const piehip::ChainCtx &level_cx(u32 limbs) const { return limbs >= hp.L ? cx : levels.at(limbs)->cx; }
     // limbs of a result row: the minimum of the two settings (chain limbs change nothing where there is no product: K = 1)
-    u32 out_limbs() const { return K >= 2 ? std::min(res_limbs, chain_limbs) : res_limbs; }
+    u32 out_limbs() const { return K >= 2 ? std::min(res_limbs, chain_last()) : res_limbs; }
     size_t res_ct_words() const { return res_comps() * (size_t)out_limbs() * hp.N; }   // one result ciphertext as it leaves the handle
 };
 
 namespace piehip {
 
-// the key switch of a run() on context cx (the handle's own or its level) has a key for every query: the context's copy of the
+// the key switch of a run() on context cx (the handle's own or one of its levels) has a key for every query: the context's copy of the
 // handle's key, or of one key per query of the batch -- read only while the handle's per-query array is the current batch's
 // (piehip_set_query_batch frees that one and leaves a level's copy behind)
 inline bool run_keys_loaded(const piehip_ctx *h, const ChainCtx &cx)
@@ -411,6 +419,7 @@ struct MulIn {
     size_t six = 0, siy = 0;            // words between the two polynomials of X / of Y (0: the context's L N)
     const ChainCtx *drop_from = nullptr;  // fused limb drop: Y (and X, x_drop) have drop_from->L limbs, folded outer stage pending
     bool x_drop = false;
+    const ChainCtx *x_from = nullptr;   // x_drop of a chain schedule: X is a product of this level, packed, its folded outer stage pending
     bool plain = false;                 // the operands are plain coefficients (chain_drop_kernel, an unfolded inverse transform)
 };
 void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
@@ -432,8 +441,10 @@ __attribute__((visibility("hidden"))) int items_to_slots(piehip_ctx *h, Tmp &tmp
 // downloads its slice of the results there); whether stage A hands operand X over in lane order
 int run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *host_results = nullptr);
 bool run_x_direct(const piehip_ctx *h);
-bool run_on_level(const piehip_ctx *h);
-const ChainCtx &run_chain_ctx(const piehip_ctx *h);   // the context the product chain of run() works on: the handle's own, or its level's
+// the context the LAST product of run()'s chain works on -- the handle's own, or a level's: the mask multiply's, the result rows' and
+// the result reduction's
+const ChainCtx &run_chain_ctx(const piehip_ctx *h);
+bool run_chain_keys_loaded(const piehip_ctx *h);   // every level on which a product of the chain relinearises has its key(s)
 // piehip_slice.cpp
 void slice_free(piehip_ctx *h);          // back to an unsliced handle: the slice side's buffers and state
 int slice_batch_changed(piehip_ctx *h);  // piehip_set_query_batch on a sliced handle: acc for the new batch, nothing put
@@ -444,7 +455,7 @@ void enqueue_mod_reduce(Sched &s, u64 *full, u32 rows, u32 keep, u64 *out, bool 
 // piehip.cpp: what the handle's result settings need beside the workspace's rows, for a database of K inner hash functions: d_full when
 // it reduces its results; three-component d_out / d_full and ws.t3 when it hands out degree-2 results
 int ensure_full_rows(piehip_ctx *h, u32 K);
-// piehip.cpp: with chain limbs below L, bring the level context's copies of keys and masks up to the handle's (on its stream)
+// piehip.cpp: with a chain schedule below L, bring the level contexts' copies of keys and masks up to the handle's (on its stream)
 int level_sync(piehip_ctx *h);
 // device input buffers of query q of the batch (owned copies: the host setters and the staged uploads write them)
 int query_input_buffers(piehip_ctx *h, u32 q, u64 **d_idx, u64 **d_minus);

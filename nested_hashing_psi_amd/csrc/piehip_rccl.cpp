@@ -318,7 +318,7 @@ static int gather_check(const piehip_ctx *h, int root, bool has_dest)
         return fail(PIEHIP_ESTATE, "gather_results: unrelinearised results (piehip_set_result_relin) are not gathered");
     if (h->res_limbs != h->hp.L)   // the ranks' row sizes would have to agree, and nothing checks a setting across ranks
         return fail(PIEHIP_ESTATE, "gather_results: results reduced to fewer limbs (piehip_set_result_limbs) are not gathered");
-    if (h->chain_limbs != h->hp.L)   // (likewise)
+    if (h->chain_floor() != h->hp.L)   // (likewise)
         return fail(PIEHIP_ESTATE, "gather_results: results of a chain on fewer limbs (piehip_set_chain_limbs) are not gathered");
     if (!h->comm) return fail(PIEHIP_ESTATE, "gather_results: no communicator (piehip_rccl_init / piehip_rccl_attach)");
     if (root < 0 || root >= h->comm_ranks) return fail(PIEHIP_EINVAL, "gather_results: root outside the communicator");

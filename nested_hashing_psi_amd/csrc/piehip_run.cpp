@@ -77,9 +77,12 @@ void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size
     {
         const size_t six = in && in->six ? in->six : LN, siy = in && in->siy ? in->siy : LN;
         const u32 Lin = in && in->drop_from ? in->drop_from->L : L;
-        ProfScope ps(s, PIEHIP_K_EXPAND, W * nb * (2.0 * Lin + 2.0 * (in && in->drop_from && !in->x_drop ? L : Lin) + 4.0 * M));
+        const ChainCtx *xf = in && in->x_drop ? (in->x_from ? in->x_from : in->drop_from) : nullptr;   // where a dropped X comes from
+        ProfScope ps(s, PIEHIP_K_EXPAND, W * nb * (2.0 * Lin + 2.0 * (in && in->drop_from ? (xf ? xf->L : L) : Lin) + 4.0 * M));
         bool ok = true;
-        if (in && in->drop_from)   // chain limbs, fused: the limb drop in the conversions' load phase
+        if (xf && xf != in->drop_from)   // chain schedule, fused: X is the product of a level between the parent's and this one
+            ok = launch_expand_both_drop_xy(in->drop_from->d_dc, xf->d_dc, cx.d_dc, N, Lin, xf->L, L, x, sx, six, y, sy, siy, nb, w.eqp, s.stream);
+        else if (in && in->drop_from)   // chain limbs, fused: the limb drop in the conversions' load phase
             ok = launch_expand_both_drop(in->drop_from->d_dc, cx.d_dc, N, Lin, L, x, sx, six, in->x_drop, y, sy, siy, nb, w.eqp, s.stream);
         else if (in && in->plain)  // chain limbs, fallback: operands the drop kernel / an unfolded inverse transform left
             ok = launch_expand_both_plain(cx.d_dc, N, L, x, sx, six, y, sy, siy, nb, w.eqp, s.stream, pl.small_moduli, pl.fold);
@@ -221,12 +224,21 @@ int ensure_run_queues(piehip_ctx *h, u32 ng)
 }
 
 // stage A of the run being enqueued hands operand X of the first product over in lane order, inside the QP operand array
-// (not with chain limbs below L: the dropped X is not what stage A computed, every accumulator goes to d_acc)
-bool run_x_direct(const piehip_ctx *h) { return h->K > 1 && h->nq > 1 && h->plan.x_direct && h->chain_limbs >= h->hp.L; }
+// (not where the first product runs below L: the dropped X is not what stage A computed, every accumulator goes to d_acc)
+bool run_x_direct(const piehip_ctx *h) { return h->K > 1 && h->nq > 1 && h->plan.x_direct && h->chain_level(1) >= h->hp.L; }
 
-// the product chain of run() works on the level context (chain limbs below L; a handle with K = 1 has no product: nothing changes)
-bool run_on_level(const piehip_ctx *h) { return h->K >= 2 && h->level && h->chain_limbs < h->hp.L; }
-const ChainCtx &run_chain_ctx(const piehip_ctx *h) { return run_on_level(h) ? h->level->cx : h->cx; }
+// the last product of run()'s chain works on this context (a handle with K = 1 has no product: nothing changes)
+const ChainCtx &run_chain_ctx(const piehip_ctx *h) { return h->K >= 2 ? h->level_cx(h->chain_last()) : h->cx; }
+// every product that relinearises finds its key(s) on its level (the handle's own context: checked by the caller, with its own message)
+bool run_chain_keys_loaded(const piehip_ctx *h)
+{
+    for (u32 hf = 1; hf < h->K; hf++) {
+        if (hf + 1 == h->K && !h->res_relin) break;   // the last product goes out as it is
+        const ChainCtx &cx = h->level_cx(h->chain_level(hf));
+        if (!(cx.evk || (h->cx.evkq && cx.evkq && h->evkq_n == h->nq && h->evkq_loaded == (1u << h->nq) - 1))) return false;
+    }
+    return true;
+}
 
 // bin layers of queue group g of ng.  Two groups take 4/7 and 3/7 of the layers: measured 3.5 % faster than equal halves at
 // b = 14 (8 + 6: the ragged transform launches of the two queues fit the workgroup slots better than 7 + 7).
@@ -248,7 +260,7 @@ extern "C" {
 // chain_only (piehip_run_chain: the accumulators were put there, piehip_put_accumulators): the product chain alone
 static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool chain_only);
 // everything of run() behind stage A for those layers (BatchedFHEHIPPIE.cpp:117-126), on the context run_chain_ctx chooses
-static void enqueue_chain_bins(Sched &s, const ChainCtx &top, const ChainCtx &cx, u32 b0, u32 layers, u64 *results);
+static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results);
 // ... and, on a handle that hands its results out on fewer limbs, their reduction: results[b][nq][2][res_limbs][N].  The chain then
 // writes the handle's full-width rows, which no caller reads: what orders a run against the result buffer's readers (and releases
 // the next queue group of a host-results run) moves from the chain's last kernel to the reduction: the chain is enqueued ungated.
@@ -307,41 +319,58 @@ static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool c
                            x_direct ? &xo : nullptr);
         }
     }
-    enqueue_chain_bins(s, h->cx, run_chain_ctx(h), b0, layers, results);
+    enqueue_chain_bins(s, b0, layers, results);
 }
-// rows [r0, r0 + nb) of the workspace as a context of cx.L limbs lays them out (on a level context the rows of two queue groups
-// stay apart as they do at L: both groups take the same view)
-static MulWs ws_rows(const MulWs &ws, const ChainCtx &cx, size_t r0, u32 nb)
+// Rows [r0, r0 + nb) of the workspace.  A queue group's rows start where the widest context of the chain (`wide`: the first product's)
+// lays them out, and every product packs its rows behind that base at its own level's strides.  With one level for every product
+// that is the level's own view, as ever; with a schedule two queue groups may be in products of different levels at the same
+// moment, and a base computed in the narrower view would land inside the other group's rows.
+static MulWs ws_rows(const MulWs &ws, const ChainCtx &wide, size_t r0, u32 nb)
 {
-    const size_t N = cx.N, LN = cx.LN();
+    const size_t N = wide.N, LN = wide.LN();
     MulWs w = ws;
     w.nb = nb;
-    w.eqp += r0 * 4 * cx.M * N;
-    w.dqp += r0 * 3 * cx.M * N;
+    w.eqp += r0 * 4 * wide.M * N;
+    w.dqp += r0 * 3 * wide.M * N;
     w.d01 += r0 * 2 * LN;
     w.d2c += r0 * LN;
-    w.dig += r0 * cx.L * LN;
+    w.dig += r0 * wide.L * LN;
     if (w.t3) w.t3 += r0 * 3 * LN;
     return w;
 }
-// The product chain of run() (BatchedFHEHIPPIE.cpp:117-126) on two contexts.  `top` is the handle's own: stage A left its
-// accumulators there, in rows of top.L limbs, and their inverse transform runs there.  `cx` is where the products run: top itself,
-// or the handle's level context (chain limbs, include/piehip.h) -- its constants, plan and tables, the limb
-// prefixes of keys and masks, the workspace viewed in rows of cx.L limbs.  On a level the accumulators are dropped to cx.L limbs on
-// their way into the products: in the load phase of the fused conversion where that applies, otherwise by a drop kernel that rewrites
-// them in place, after which every conversion of the chain takes plain operands.  results[b][nq][comps][cx.L][N].
-static void enqueue_chain_bins(Sched &s, const ChainCtx &top, const ChainCtx &cx, u32 b0, u32 layers, u64 *results)
+// What the products of a chain disagree on, one entry per product (the products behind the schedule's last entry share one)
+struct ChainStep {
+    const ChainCtx *cx = nullptr;   // the level the product runs on: constants, plan and tables, the limb prefixes of keys and masks
+    MulIn in;                       // how X and Y lie in memory and what their conversion does first
+    size_t sx = 0;                  // words from one row's X to the next
+    bool xq_ready = false;          // the QP array holds X's Q limbs in EVALUATION form already
+    bool x_drop_kernel = false;     // fallback: X is the product before, on more limbs; the drop kernel rewrites it in place first ...
+    bool x_folded = false;          // ... reading through the folded outer stage its inverse transform left pending
+    // the inverse transform of this product's result, where another product follows: on this product's context
+    bool inv_fold = false;          // leaves the outer stage to the next conversion (or to the drop kernel)
+    bool inv_copy = false;          // also writes the Q limbs of the next X, lane-ordered, into the QP array (NttExtra copy_out)
+};
+// The product chain of run() (BatchedFHEHIPPIE.cpp:117-126).  Stage A left its accumulators on the handle's own context `top`, in rows
+// of top.L limbs, and their inverse transform runs there.  Product hf runs on the level context of chain_level(hf) limbs (chain
+// limbs and chain schedule, include/piehip.h) -- top itself at L.  On their way into a product of a lower level
+// the accumulators, and the product before where it has more limbs, are dropped to that level: in the load phase of the fused
+// conversion where every drop of the chain is built that way, otherwise by a drop kernel that rewrites them in place, after which
+// the conversions of that level take plain operands.  A product on top.L limbs runs as it does without any setting, whichever route
+// the products behind it take.  results[b][nq][comps][l_last][N].
+static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
 {
     piehip_ctx *h = s.h;
+    const ChainCtx &top = h->cx, &cx = run_chain_ctx(h);   // cx: the last product's level, the lowest of the chain
+    const u32 N = top.N, K = h->K, nq = h->nq;
+    const ChainCtx &wide = K >= 2 ? h->level_cx(h->chain_level(1)) : top;
     const NttPlan &pl = *cx.plan;
-    const u32 N = cx.N, K = h->K, nq = h->nq;
     const size_t TLN = top.LN(), LN = cx.LN();
     const double W = 8.0 * N;
     const size_t r0 = (size_t)b0 * nq;
     const u32 nb = layers * nq;
-    MulWs w = ws_rows(h->ws, cx, r0, nb);
+    MulWs w = ws_rows(h->ws, wide, r0, nb);
     u64 *acc = h->d_acc + r0 * K * 2 * TLN;   // stage A's rows: the handle's strides
-    u64 *prod = h->d_prod ? h->d_prod + r0 * 2 * LN : nullptr;
+    u64 *prod = h->d_prod ? h->d_prod + r0 * 2 * wide.LN() : nullptr;
     const bool deg2 = h->res_comps() == 3;   // piehip_set_result_relin(0): the last product goes out as it is, three components
     u64 *out = results + r0 * h->res_comps() * LN;
     const u64 *masks = ((deg2 ? pl.result_eval_q : pl.lane_order) ? cx.masks_sigma : cx.masks) + (size_t)b0 * LN;
@@ -356,57 +385,101 @@ static void enqueue_chain_bins(Sched &s, const ChainCtx &top, const ChainCtx &cx
         launch_ct_mul_plain(cx.d_dc, N, cx.L, acc, cx.masks + (size_t)b0 * LN, LN, out, nb, s.stream, nq);
         return;
     }
-    // What the chain at L and the two chains of a level disagree on, decided here and nowhere below.
-    // fused: the limb drop rides in the conversions' load phase -- folded rings whose level moduli take the column-accumulator
-    // arithmetic, pairs the conversion is built for; dropped: the drop kernel does it, and leaves plain coefficients
-    const bool level = cx.L < top.L;   // the products run on fewer limbs than the accumulators have
-    const bool fused = level && top.plan->fold && pl.fold && pl.small_moduli && pl.xq_reuse && expand_both_drop_applies(top.L, cx.L);
+    // What the chain at L and the chains with products on a level disagree on, decided here and nowhere below.
+    auto lvl = [&](u32 hf) -> const ChainCtx & { return h->level_cx(h->chain_level(hf)); };
+    auto x_limbs = [&](u32 hf) { return hf == 1 ? top.L : lvl(hf - 1).L; };   // limbs of product hf's X as it arrives
+    // fused: every limb drop rides in a conversion's load phase -- folded rings whose level moduli take the column-accumulator
+    // arithmetic, source and target levels the conversion is built for, on every context the chain touches.  One drop that is not
+    // built that way puts the whole chain on the drop kernel (dropped)
+    const bool level = cx.L < top.L;   // some product runs on fewer limbs than the accumulators have
+    bool fused = level && top.plan->fold;
+    for (u32 hf = 1; hf < K && hf <= h->chain_n + 1 && fused; hf++) {
+        const ChainCtx &c = lvl(hf);
+        if (c.L == top.L) continue;
+        fused = c.plan->fold && c.plan->small_moduli && c.plan->xq_reuse &&
+                (x_limbs(hf) > c.L ? expand_both_drop_xy_applies(top.L, x_limbs(hf), c.L) : expand_both_drop_applies(top.L, c.L));
+    }
     const bool dropped = level && !fused;
     // X is needed twice by a product: in COEFFICIENT form by the base extension, and in EVALUATION form, lane-ordered, as the Q limbs of
     // the QP operand (plan.xq_reuse).  The inverse transform that makes the first also writes the second (NttExtra copy_out) -- where
-    // it makes X at all: the dropped X of a level's first product is not what the QP array could hold in EVALUATION form, and the
-    // drop kernel's chain transforms without folding, into plain coefficients like the dropped accumulators, and copies nothing
-    const bool copy_first = !level && pl.xq_reuse, copy_between = !dropped && pl.xq_reuse;
-    const u32 xq_from = copy_first ? 1 : copy_between ? 2 : K;   // the products from this one on find X's Q limbs in the QP array
-    MulIn in;   // (at L: the strides the conversions assume anyway)
-    in.six = in.siy = TLN;
-    in.drop_from = fused ? &top : nullptr;
-    in.x_drop = fused;
-    in.plain = dropped;
+    // it makes the X the product takes: a dropped X is not what the QP array could hold in EVALUATION form, and below L the drop
+    // kernel's chain transforms without folding, into plain coefficients like the dropped accumulators, and copies nothing
+    const u32 nsteps = std::min(K - 1, h->chain_n + 1);   // the products behind the schedule's last entry are all alike
+    ChainStep steps[MAX_CHAIN_SCHED + 1];
+    for (u32 i = 0; i < nsteps; i++) {
+        const u32 hf = i + 1;
+        ChainStep &t = steps[i];
+        const ChainCtx &c = lvl(hf);
+        const bool at_top = c.L == top.L, x_drop = x_limbs(hf) > c.L;
+        t.cx = &c;
+        t.in.six = (size_t)x_limbs(hf) * N;
+        t.in.siy = TLN;
+        t.sx = hf == 1 ? (size_t)K * 2 * TLN : 2 * t.in.six;
+        if (at_top) {
+            t.xq_ready = c.plan->xq_reuse;
+        } else if (fused) {
+            t.in.drop_from = &top;
+            t.in.x_drop = x_drop;
+            t.in.x_from = x_drop && hf > 1 ? &lvl(hf - 1) : nullptr;
+            t.xq_ready = !x_drop;
+        } else {
+            t.in.plain = true;
+            t.x_drop_kernel = x_drop && hf > 1;   // (the first product's X is an accumulator: dropped with the others)
+        }
+        if (hf + 1 < K) {
+            const bool same = lvl(hf + 1).L == c.L;
+            t.inv_fold = at_top || fused;
+            t.inv_copy = same && c.plan->xq_reuse && (at_top || fused);
+        }
+        if (i) t.x_folded = t.x_drop_kernel && steps[i - 1].inv_fold && steps[i - 1].cx->plan->fold;
+    }
+    const bool copy_first = steps[0].xq_ready;
     NttExtra ex;
     ex.copy_out = w.eqp;
     ex.copy_K = K;
-    ex.copy_L = cx.L;
-    ex.copy_M = cx.M;
+    ex.copy_L = top.L;
+    ex.copy_M = top.M;
     ex.x_lane_in = run_x_direct(h);
     // every accumulator enters a ct x ct product exactly once: switch them all to COEFFICIENT format, on the handle's limbs
     ntt(s, acc, nb * K * 2 * top.L, 0, top.L, true, false, true, copy_first ? &ex : nullptr);
     ex.x_lane_in = false;
     ex.copy_K = 1;  // from here on the product is the X operand of the next multiplication
     if (dropped) {
-        ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * nb * K * 2 * (top.L + cx.L));
-        launch_chain_drop(top.d_dc, N, top.L, cx.L, acc, nb * K * 2, s.stream, top.plan->fold);
+        // accumulator 0 goes to the first product's level, accumulator hf to product hf's: one launch per run of neighbours with one
+        // target, over all rows (a chain with one level for every product: one launch, the rows as one packed array)
+        auto target = [&](u32 a) { return lvl(a ? a : 1).L; };
+        for (u32 a0 = 0, a1; a0 < K; a0 = a1) {
+            for (a1 = a0 + 1; a1 < K && target(a1) == target(a0); a1++) {}
+            if (target(a0) == top.L) continue;
+            ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * nb * (a1 - a0) * 2 * (top.L + target(a0)));
+            launch_chain_drop(top.d_dc, N, top.L, target(a0), acc + (size_t)a0 * 2 * TLN, nb * (a1 - a0) * 2, s.stream, top.plan->fold,
+                              (a1 - a0) * 2, (size_t)K * 2 * TLN);
+        }
     }
     // product chain over the inner hash functions (BatchedFHEHIPPIE.cpp:117-124); the mask multiply (:126) is fused into the last
     // key switch
-    s.cx = &cx;
     const u64 *x = acc;
-    size_t sx = (size_t)K * 2 * TLN;
     for (u32 hf = 1; hf < K; hf++) {
+        const ChainStep &t = steps[std::min(hf, nsteps) - 1];
+        const ChainCtx &c = *t.cx;
         const bool last = hf + 1 == K;
-        enqueue_mul(s, w, x, sx, acc + (size_t)hf * 2 * TLN, (size_t)K * 2 * TLN, nb, !(last && deg2), last ? masks : nullptr, last ? out : prod,
-                    hf >= xq_from, last, &in);
+        if (t.x_drop_kernel) {   // under the constants of the level that made it, at its packed strides
+            const ChainCtx &from = *s.cx;
+            ProfScope ps(s, PIEHIP_K_LIMB_DROP, W * nb * 2 * (from.L + c.L));
+            launch_chain_drop(from.d_dc, N, from.L, c.L, prod, nb * 2, s.stream, t.x_folded);
+        }
+        s.cx = &c;
+        enqueue_mul(s, w, x, t.sx, acc + (size_t)hf * 2 * TLN, (size_t)K * 2 * TLN, nb, !(last && deg2), last ? masks : nullptr, last ? out : prod,
+                    t.xq_ready, last, &t.in);
         if (!last) {
-            ntt(s, prod, nb * 2 * cx.L, 0, cx.L, true, false, !dropped, copy_between ? &ex : nullptr);
+            ex.copy_L = c.L;
+            ex.copy_M = c.M;
+            ntt(s, prod, nb * 2 * c.L, 0, c.L, true, false, t.inv_fold, t.inv_copy ? &ex : nullptr);
             x = prod;
-            sx = 2 * LN;
-            in.six = LN;
-            in.x_drop = false;
         }
     }
     s.cx = &top;
 }
-
 // the result ciphertexts of bin layers [b0, b0 + nb) (rows [bin layer][query]) to the caller's host array, on the queue of s
 static hipError_t download_rows(const Sched &s, u64 *host_results, const u64 *d_results, u32 b0, u32 nb)
 {
@@ -431,7 +504,7 @@ int piehip::run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *
         if (!h->ws.t3 || h->res_cap_comps < 3)
             return fail(PIEHIP_ESTATE, "run: no rows for three-component results (an earlier allocation failed: piehip_set_result_relin)");
     }
-    if (!run_keys_loaded(h, run_chain_ctx(h)))
+    if (!run_chain_keys_loaded(h))
         return fail(PIEHIP_ESTATE, "run: no key on the level context (an earlier allocation failed: piehip_set_chain_limbs)");
     if (h->res_limbs < h->hp.L && !h->d_full) return fail(PIEHIP_ESTATE, "run: no rows for the result reduction (an earlier allocation failed: piehip_set_result_limbs)");
     for (u32 q = 0; q < h->nq && !chain_only; q++) {
@@ -561,7 +634,7 @@ int piehip_set_graph(piehip_handle h, int on)
         return fail(PIEHIP_ESTATE, "set_graph: the captured graph hands out full results (piehip_set_result_limbs is below L)");
     if (on && !h->res_relin)
         return fail(PIEHIP_ESTATE, "set_graph: the captured graph relinearises its results (piehip_set_result_relin is off)");
-    if (on && h->chain_limbs < h->hp.L)
+    if (on && h->chain_floor() < h->hp.L)
         return fail(PIEHIP_ESTATE, "set_graph: the captured graph runs the product chain on every limb (piehip_set_chain_limbs is below L)");
     if (on && h->slice.on) return fail(PIEHIP_ESTATE, "set_graph: a query-sliced handle runs in two halves (piehip_run_slice, piehip_run_chain): no captured graph");
     h->use_graph = on != 0;

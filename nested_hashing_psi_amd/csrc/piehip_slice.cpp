@@ -70,7 +70,7 @@ static int slice_setup(piehip_ctx *h, u32 K, u32 b, u32 E, u32 u_lo, u32 u_hi, u
         return fail(PIEHIP_ESTATE, "query slice: the handle lends or borrows a database (piehip_attach_database)");
     if (h->use_graph) return fail(PIEHIP_ESTATE, "query slice: the handle replays a captured graph (piehip_set_graph)");
     if (!h->res_relin) return fail(PIEHIP_ESTATE, "query slice: the handle hands out unrelinearised results (piehip_set_result_relin)");
-    if (h->chain_limbs < h->hp.L) return fail(PIEHIP_ESTATE, "query slice: the handle runs its product chain on fewer limbs (piehip_set_chain_limbs)");
+    if (h->chain_floor() < h->hp.L) return fail(PIEHIP_ESTATE, "query slice: the handle runs its product chain on fewer limbs (piehip_set_chain_limbs)");
     HIPCHK(hipSetDevice(h->device));
     slice_free(h);
     int rc = alloc_run_buffers(h, K, bin_hi - bin_lo, E, false);

@@ -125,8 +125,26 @@ public:
         for (auto &l : lists)
             for (auto &c : l) c.limbs.clear();
     }
-    uint32_t chainLimbs() const { return chainLimbs_; }
-    uint32_t resultRowLimbs() const { return K >= 2 && chainLimbs_ < resLimbs ? chainLimbs_ : resLimbs; }   // min(keep, Lc); K = 1: keep
+    // Chain schedule (include/piehip.h "Chain limbs"): product hf = 1, 2, .. of the chain runs on limbs[min(hf, n) - 1] limbs,
+    // non-increasing; setChainLimbs(x) is the schedule {x}.  chainLimbs() then answers with the last product's level, which is the
+    // result rows'.  Refusals as setChainLimbs'.
+    void setChainSchedule(const std::vector<uint32_t> &limbs)
+    {
+        PieContext::check(piehip_set_chain_schedule(cc->handle(), limbs.data(), (uint32_t)limbs.size()));
+        PieContext::check(piehip_host_buffers_q(cc->handle(), 0, nullptr, nullptr, &pinRes));
+        PieContext::check(piehip_get_chain_limbs(cc->handle(), &chainLimbs_));
+        std::fill(listStale.begin(), listStale.end(), false);
+        for (auto &l : lists)
+            for (auto &c : l) c.limbs.clear();
+    }
+    std::vector<uint32_t> chainSchedule() const
+    {
+        uint32_t buf[7], n = 0;
+        PieContext::check(piehip_get_chain_schedule(cc->handle(), buf, 7, &n));
+        return std::vector<uint32_t>(buf, buf + n);
+    }
+    uint32_t chainLimbs() const { return chainLimbs_; }   // the last product's level
+    uint32_t resultRowLimbs() const { return K >= 2 && chainLimbs_ < resLimbs ? chainLimbs_ : resLimbs; }   // min(keep, l_last); K = 1: keep
 
     // Result limbs (include/piehip.h "Result limbs"): from the next run() on the result ciphertexts are [2][keep][N], on the first
     // `keep` primes of the chain.  The page-locked result array follows the setting; result lists of earlier runs are dropped.
@@ -385,6 +403,9 @@ public:
     // the product chain on the first Lc limbs of the chain (include/piehip.h "Chain limbs"): rows of min(keep, Lc) limbs
     void setChainLimbs(uint32_t Lc) { staged.setChainLimbs(Lc); }
     uint32_t chainLimbs() const { return staged.chainLimbs(); }
+    // a limb count per product of the chain, non-increasing (include/piehip.h "Chain limbs"): rows of min(keep, the last product's) limbs
+    void setChainSchedule(std::vector<uint32_t> limbs) { staged.setChainSchedule(limbs); }
+    std::vector<uint32_t> chainSchedule() const { return staged.chainSchedule(); }
 
     // .hpp:40-43, [K][E] ciphertexts
     void setIndex(std::vector<std::vector<LimbCt>> &&indexMatrix) { staged.setIndex(0, std::move(indexMatrix)); }
@@ -478,6 +499,9 @@ public:
     // the product chain on the first Lc limbs of the chain (include/piehip.h "Chain limbs"): rows of min(keep, Lc) limbs
     void setChainLimbs(uint32_t Lc) { staged.setChainLimbs(Lc); }
     uint32_t chainLimbs() const { return staged.chainLimbs(); }
+    // a limb count per product of the chain, non-increasing (include/piehip.h "Chain limbs"): rows of min(keep, the last product's) limbs
+    void setChainSchedule(std::vector<uint32_t> limbs) { staged.setChainSchedule(limbs); }
+    std::vector<uint32_t> chainSchedule() const { return staged.chainSchedule(); }
 
 private:
     PieContext &cc;

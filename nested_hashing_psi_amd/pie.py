@@ -121,6 +121,16 @@ class PieContext:
         _check(lib().piehip_get_chain_limbs(self._h, C.byref(n)))
         return n.value
 
+    def setChainSchedule(self, limbs):
+        """a limb count per product of run()'s chain (piehip_set_chain_schedule): non-increasing, 1 to 7 entries, each in [1, L]"""
+        limbs = [int(v) for v in limbs]
+        _check(lib().piehip_set_chain_schedule(self._h, (C.c_uint32 * max(len(limbs), 1))(*limbs), len(limbs)))
+
+    def chainSchedule(self):
+        buf, n = (C.c_uint32 * 7)(), C.c_uint32()
+        _check(lib().piehip_get_chain_schedule(self._h, buf, 7, C.byref(n)))
+        return list(buf[:n.value])
+
     # -- tables (for cross-checks)
     def psi(self, mi):
         v = C.c_uint64()
@@ -506,7 +516,19 @@ class BatchedFHEHIPPIE:
         self._results = None
 
     def chainLimbs(self):
+        """limbs of the last product of the chain, which are the result rows' (before resultLimbs)"""
         return self.cc.chainLimbs()
+
+    def setChainSchedule(self, limbs):
+        """product hf = 1, 2, .. of run()'s chain on limbs[min(hf, len(limbs)) - 1] limbs (piehip_set_chain_schedule; non-increasing): the
+        accumulators, and the product before where it has more limbs, are dropped on their way into each product.  Result arrays are
+        [..][min(resultLimbs, chainLimbs())][N].  setChainLimbs(x) is the schedule [x].  The noise budget is the caller's business
+        (include/piehip.h "Chain limbs").  Page-locked result arrays follow the setting: ask hostBuffers() again after changing it."""
+        self.cc.setChainSchedule(limbs)
+        self._results = None
+
+    def chainSchedule(self):
+        return self.cc.chainSchedule()
 
     def _res_shape(self):
         nq, keep, nc = self.nq, self.resultLimbs, self.resultComponents()

@@ -47,6 +47,10 @@ def main():
     from nested_hashing_psi_amd import _lib, pie
     if args.lib:
         _lib.LIB_PATH = os.path.abspath(args.lib)
+        import ctypes
+        other = ctypes.CDLL(_lib.LIB_PATH)
+        for name in [n for n in _lib.SYMBOLS if not hasattr(other, n)]:   # an older build: the entry points it lacks are not used here
+            del _lib.SYMBOLS[name]
     from tests.param_chains import named_chain
     lines = []
     for N, L, chain, t, K, b, nq, key_per_query, settings in SHAPES:
