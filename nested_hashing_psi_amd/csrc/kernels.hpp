@@ -85,7 +85,9 @@ void build_twc_table(const u64 *nat_pairs, u32 logN, u32 s0, std::vector<u64> &o
 void build_twk16_table(const u64 *nat_pairs, u32 s0, u32 slice_log, std::vector<u64> &out);  // slices of 2^13 or 2^14
 void ntt_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map);
 void ntt16_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map);
-// Optional extras of the register-blocked kernels (ciphertext multiplication), honoured where NttRoute::extra():
+// Optional extras of the register-blocked kernels (ciphertext multiplication), honoured where NttRoute::extra() -- elsewhere launch_ntt
+// drops the copy and the compact enumeration (the copy array is not written) and keeps lazy_out, which the slice kernel of a route
+// with global stages honours as well (it stores last):
 //   inverse, standard order in:  limbs [nb][copy_K][2][copy_L]; the lane-ordered EVALUATION input of operand 0 of every
 //                                bin is also written to the Q limbs of copy_out[nb][4][copy_M][N] (slots 0, 1)
 //   forward, lane order:         lazy_out -- no final normalisation

@@ -184,6 +184,13 @@ void launch_ntt(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_
 {
     if (!nlimbs) return;
     const NttRoute r = ntt_route(pl, inverse, sigma, folded);
+    // A route with global stages does not honour the copy or the compact enumeration (the stages walk every limb, and the plan has
+    // no xq_reuse there): a caller that passes them all the same gets the plain transform.  lazy_out stays: the slice kernel stores last
+    NttExtra plain;
+    if (ex && !r.extra()) {
+        plain.lazy_out = ex->lazy_out;
+        ex = &plain;
+    }
     if (r.kernel == NttKernel::blocked16) {
         launch_ntt16(pl, data, nlimbs, mod_base, mod_count, inverse, sigma, st, ex);
         return;

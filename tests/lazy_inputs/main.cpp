@@ -3,6 +3,8 @@
 // range -- representatives that the transforms inside the library produce with negligible probability (tests/lazy_inputs.py,
 // tests/test_gpu_lazy_inputs.py).  A program of its own, linked with the library's objects: it makes a handle with piehip_create,
 // takes the constants, the plan and the lane-order map from it and calls one piehip::launch_* of kernels.hpp.  It judges nothing.
+// The ops `ntt` and `ntt_digits` launch the transforms themselves, every route and NttExtra mode (tests/transform_inputs.py,
+// tests/test_gpu_transform_routes.py); they print a line "route ..." with the kernel, the slices and the global stages of the call.
 //
 // Inputs are DIR/in_<name>.u64 (raw little-endian words, exactly the words the launch indexes: any other size is refused), outputs
 // DIR/out_<name>.u64: GUARD words, the array, GUARD words, everything pre-filled with FILL so that guards and places a mode does not
@@ -134,8 +136,10 @@ int main(int argc, char **argv)
     const u32 *sigma_inv = h->d_sigma_inv;
     hipStream_t st = h->stream;
     const bool sm = pl.small_moduli;
-    printf("plan lane_order=%d fold=%d lane_kp=%u lane_T=%u small_moduli=%d fused_tensor=%d d01_eval_q=%d result_eval_q=%d\n", (int)pl.lane_order,
-           (int)pl.fold, pl.lane_kp, pl.lane_T, (int)sm, (int)pl.fused_tensor, (int)pl.d01_eval_q, (int)pl.result_eval_q);
+    printf("plan lane_order=%d fold=%d lane_kp=%u lane_T=%u small_moduli=%d fused_tensor=%d d01_eval_q=%d result_eval_q=%d xq_reuse=%d x_direct=%d "
+           "digits_with_d01=%d digit_lift_lane=%d digit_lift_std=%d\n",
+           (int)pl.lane_order, (int)pl.fold, pl.lane_kp, pl.lane_T, (int)sm, (int)pl.fused_tensor, (int)pl.d01_eval_q, (int)pl.result_eval_q,
+           (int)pl.xq_reuse, (int)pl.x_direct, (int)pl.digits_with_d01, (int)pl.digit_lift_lane, (int)pl.digit_lift_std);
     {
         std::vector<u32> m32(N);
         LI_HIP(hipMemcpy(m32.data(), sigma_inv, (size_t)N * sizeof(u32), hipMemcpyDeviceToHost));
@@ -217,20 +221,67 @@ int main(int argc, char **argv)
         LI_HIP(hipStreamSynchronize(st));
         save("dig", dig);
     } else if (op == "ntt") {
-        // forward transform of nlimbs limbs of Q (limb i: modulus i % L), in place; sigma: lane order out; fold; lazy_out
-        const u32 nl = opt("nlimbs", L);
-        const bool sigma = opt("sigma") != 0, lazy = opt("lazy_out") != 0;
-        if (!nl || (sigma && !pl.lane_order)) refuse("nlimbs, or sigma without a lane order");
-        const NttRoute r = ntt_route(pl, false, sigma, fold);
-        if (lazy && !r.extra()) refuse("lazy_out on a route that does not honour NttExtra");
-        printf("route kernel=%s s0=%u global_stages=%u\n", r.kernel == NttKernel::blocked16 ? "blocked16" : r.kernel == NttKernel::blocked32 ? "blocked32" : "radix2",
-               r.s0, r.global_stages);
-        Out data = output((size_t)nl * N, "data");
+        // one transform launch, in place, of nlimbs limbs (limb i: modulus mod_base + i % mod_count; default 0 and L) at the head of an
+        // array of data_limbs limbs (default nlimbs: what lies behind the last item must come back as it went in).  inverse; sigma: the
+        // EVALUATION side in lane order; fold; lazy_out.  The NttExtra modes, with nb bins:
+        //   copy=1 copy_K=   inverse, standard order in: data [nb][copy_K][2][L][N], copy_out [nb][4][M][N] an output of its own;
+        //                    x_lane_in=1: that array comes from in_copy.u64
+        //   skip=1           forward: data [nb][4][M][N], nlimbs the compact count nb (2 (M - L) + 2 M)
+        //   digits=1         forward, lane order: Ntt16Digits rides along, in_d2.u64 [nb][L][N] -> dig [nb][L][L][N]
+        // An NttExtra is passed whether or not the route honours it: the route line says which, the caller looks at the arrays.
+        const u32 nl = opt("nlimbs", L), mod_base = opt("mod_base", 0), mod_count = opt("mod_count", L), nb = opt("nb", 1);
+        const bool sigma = opt("sigma") != 0, lazy = opt("lazy_out") != 0, inverse = opt("inverse") != 0;
+        const bool copy = opt("copy") != 0, x_lane_in = opt("x_lane_in") != 0, skip = opt("skip") != 0, digits = opt("digits") != 0;
+        const u32 data_limbs = opt("data_limbs", skip ? nb * 4 * M : nl), copy_K = opt("copy_K", 1);
+        if (!nl || !nb || data_limbs < nl || (sigma && !pl.lane_order)) refuse("nlimbs, nb, data_limbs, or sigma without a lane order");
+        if (!mod_count || mod_base + mod_count > M + 1) refuse("mod_base / mod_count leave the context's moduli");
+        const NttRoute r = ntt_route(pl, inverse, sigma, fold);
+        if (lazy && (!r.extra() || inverse || !sigma)) refuse("lazy_out on a call that does not honour it");
+        if (copy && (!inverse || sigma || !copy_K || nl != nb * copy_K * 2 * L || mod_base || mod_count != L)) refuse("copy: an inverse in standard order over [nb][copy_K][2][L]");
+        if (x_lane_in && (!copy || !pl.x_direct || r.kernel != NttKernel::blocked16)) refuse("x_lane_in without copy, or on a plan without x_direct");
+        if (skip && (inverse || mod_base || mod_count != M || nl != nb * (2 * (M - L) + 2 * M) || data_limbs < nb * 4 * M)) refuse("skip: a forward call over [nb][4][M]");
+        if (digits && (inverse || !sigma || fold != pl.fold || mod_base || mod_count != L || !pl.digits_with_d01 || r.kernel != NttKernel::blocked16))
+            refuse("digits on a plan without digits_with_d01, or not on its forward lane-order launch");
+        if (opt("slots") && piehip_set_transform_slots(h, opt("slots")) != PIEHIP_OK) refuse("piehip_set_transform_slots");
+        printf("route kernel=%s s0=%u global_stages=%u extra=%d transform_cus=%u\n",
+               r.kernel == NttKernel::blocked16 ? "blocked16" : r.kernel == NttKernel::blocked32 ? "blocked32" : "radix2", r.s0, r.global_stages, (int)r.extra(),
+               pl.transform_cus());
+        Out data = output((size_t)data_limbs * N, "data");
+        Out cp, dig;
         NttExtra ex;
         ex.lazy_out = lazy;
-        launch_ntt(pl, data.data(), nl, 0, L, false, st, sigma, fold, &ex);
+        if (copy) {
+            cp = output((size_t)nb * 4 * MN, x_lane_in ? "copy" : nullptr);
+            ex.copy_out = cp.data(), ex.copy_K = copy_K, ex.copy_L = L, ex.copy_M = M, ex.x_lane_in = x_lane_in;
+        }
+        if (skip) ex.skip_L = L, ex.skip_M = M;
+        if (digits) {
+            const u64 *d2 = input("d2", (size_t)nb * LN);
+            dig = output((size_t)nb * L * LN);
+            Ntt16Digits dg = {d2, LN, dig.data(), nb, L};
+            launch_ntt16(pl, data.data(), nl, 0, L, false, true, st, &ex, &dg);
+        } else {
+            launch_ntt(pl, data.data(), nl, mod_base, mod_count, inverse, st, sigma, fold, &ex);
+        }
         LI_HIP(hipStreamSynchronize(st));
         save("data", data);
+        if (copy) save("copy", cp);
+        if (digits) save("dig", dig);
+    } else if (op == "ntt_digits") {
+        // launch_ntt_digits: in_d2.u64 [nb][L][N] COEFFICIENT -> dig [nb][L][L][N] EVALUATION, the lift in the 32-coefficient kernel's load phase
+        const u32 nb = opt("nb", 1);
+        const bool sigma = opt("sigma") != 0;
+        if (!nb || !(sigma ? pl.digit_lift_lane : pl.digit_lift_std)) refuse("ntt_digits: nb, or the plan has no digit lift in this order");
+        if (opt("slots") && piehip_set_transform_slots(h, opt("slots")) != PIEHIP_OK) refuse("piehip_set_transform_slots");
+        const NttRoute r = ntt_route(pl, false, sigma, false);
+        printf("route kernel=%s s0=%u global_stages=%u extra=%d transform_cus=%u\n",
+               r.kernel == NttKernel::blocked16 ? "blocked16" : r.kernel == NttKernel::blocked32 ? "blocked32" : "radix2", r.s0, r.global_stages, (int)r.extra(),
+               pl.transform_cus());
+        const u64 *d2 = input("d2", (size_t)nb * LN);
+        Out dig = output((size_t)nb * L * LN);
+        launch_ntt_digits(pl, d2, dig.data(), nb, L, sigma, st);
+        LI_HIP(hipStreamSynchronize(st));
+        save("dig", dig);
     } else {
         refuse("unknown OP");
     }

@@ -92,12 +92,21 @@ def _run(op, o, inputs, outs, **opts):
     return got, plan, r.stdout
 
 
+def _lane_rule(N):
+    """(fold, slice length, kp, T) of the lane order of a ring of N >= 4096 coefficients, written out from the launchers' rule: the
+    32-coefficient kernel's at 2^12 (one slice) and 2^16 (four, behind two global stages), the 16-coefficient kernel's between, as two
+    folded slices from 2^14 on"""
+    fold = 1 if N in (16384, 32768) else 0
+    sl = N // 2 if fold else (N // 4 if N == 65536 else N)
+    kp, T = (16, sl // 32) if N in (4096, 65536) else (8, sl // 16)
+    return fold, sl, kp, T
+
+
 def _lane(o, plan, got):
     """the lane-order map of a context whose plan has one, written out from the launchers' rule and compared with the handle's"""
     N = o.N
-    sl = N // 2 if plan["fold"] else N
-    want_kp, want_T = (16, sl // 32) if N == 4096 else (8, sl // 16)
-    assert plan["lane_order"] == 1 and (plan["lane_kp"], plan["lane_T"]) == (want_kp, want_T)
+    fold, sl, want_kp, want_T = _lane_rule(N)
+    assert plan["lane_order"] == 1 and plan["fold"] == fold and (plan["lane_kp"], plan["lane_T"]) == (want_kp, want_T)
     m = lz.lane_map(N, sl, want_T, want_kp)
     assert (got["sigma_inv"] == m).all()
     return m
