@@ -360,7 +360,8 @@ int piehip_base_convert(piehip_handle h, int which, const uint64_t *in, uint32_t
  * i.e. c_i <- (c_i - r) q_l^-1 mod q_i for i < l, coefficient by coefficient in COEFFICIENT format, both components alike.  Input and
  * output cross the ABI in EVALUATION format; the output is [2][keep][N], canonical, under q_0 .. q_{keep-1}, and decrypts as a plain
  * BFV ciphertext of the context (N, keep, t, q[:keep]) with the first `keep` limbs of the secret key.  A drop adds at most
- * t (1 + N) / (2 q_0) to the invariant noise.  Integer arithmetic only: every schedule gives the same bits.
+ * t (1 + N) / (2 q_0) to the invariant noise.  Integer arithmetic only: every schedule gives the same bits.  The library does not
+ * check noise: piehip_client_decrypt_budget (client-side harness, below) measures what a reduced row has left.
  *   piehip_mod_reduce        the operation on nct ciphertexts in host memory; synchronous.  keep == L copies the input.
  *   piehip_set_result_limbs  run() ends with the reduction of its result list to `keep` limbs (default L: nothing is added, no
  *                            launch, buffer or byte differs).  With keep < L every queue group of a run() is followed, on its own
@@ -416,7 +417,8 @@ int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
  * draws, a coefficient of s^2 is a sum of N products of variance 4/9, a coefficient of e_2 s^2 a sum of N independent terms of
  * variance (1/12)(4/9) N each: standard deviation N / sqrt(27), and |e_2 s^2| <= 6 N / sqrt(27) < 1.2 N in every coefficient except
  * with probability below 2^-27 N.  With that probability a drop adds at most t (1 + N + 2.4 N) / (2 q_0): a high-probability bound,
- * not a worst-case one (INTEGRATION.md section 5 has the measured budgets).
+ * not a worst-case one (INTEGRATION.md section 5 has the measured budgets).  The library does not check noise:
+ * piehip_client_decrypt_budget with ncomp = 3 measures what a three-component row has left.
  * PIEHIP_ESTATE: on = 0 on a handle with piehip_set_graph(1), and piehip_set_graph(1) on a handle with on = 0 (the captured graph
  * stays the reference's run()); on = 0 on a query-sliced handle (piehip_load_db*_sliced), and a sliced load on a handle with on = 0.
  * piehip_gather_results(_host) REFUSES (PIEHIP_ESTATE) a handle with on = 0, for the reason it refuses keep < L.  piehip_fhepie_*
@@ -457,8 +459,8 @@ int piehip_client_decrypt_deg2(piehip_handle h, const uint64_t *sk, const uint64
  *                            Per handle: a query slot (piehip_attach_database) has its own setting.  Works with query batches and
  *                            per-query keys, seeded queries (stage A is untouched), one and two queues, the host-results stagger.
  *   piehip_get_chain_limbs   the setting (with a chain schedule, below: the limb count of the last product that runs).
- * Choosing Lc.  The library does not check noise.  The budget after the drop is min(budget, log2 Q' - log2 t - log2(N + 1) - 1) bits,
- * and the chain then costs what it costs on any context of Lc limbs.  Budgets in bits as the CPU oracle reports them (its readout
+ * Choosing Lc.  The library does not check noise (piehip_client_decrypt_budget measures it on the result rows).  The budget after the
+ * drop is min(budget, log2 Q' - log2 t - log2(N + 1) - 1) bits, and the chain then costs what it costs on any context of Lc limbs.  Budgets in bits as the CPU oracle reports them (its readout
  * saturates at 57-58), K = 2, fresh queries (tests/test_chain_limbs.py):
  *     parameters                                   full chain   chain limbs L-1        then keep = 2 / 1   chain limbs L-2
  *     N = 16384, L = 4, t = 4296540161, E = 14     57           40, same plaintext     40 / 20             0, WRONG plaintext
@@ -496,7 +498,8 @@ int piehip_get_chain_limbs(piehip_handle h, uint32_t *Lc);
  * On the first row no uniform setting below L decrypts and (4,3) keeps the full run's 38 bits; on the second the lowest uniform
  * setting is (4,4) and (4,3) still leaves 38 bits.  Every other entry named here has the full run's plaintext.
  * Rule of thumb: give the last product one limb fewer than the lowest uniform setting that still decrypts, and every product before it
- * that setting; check the budget of the real parameters on a client before relying on it.
+ * that setting; check the budget of the real parameters on a client before relying on it: piehip_client_decrypt_budget reads it from
+ * the result rows, and nested_hashing_psi_amd/schedule.py (choose_chain_schedule) runs every candidate schedule and picks by it.
  * PIEHIP_EINVAL: n = 0 or n > 7, an entry of 0 or above L, an increasing pair.  PIEHIP_ESTATE: every refusal of chain limbs above,
  * whenever any entry is below L.  piehip_fhepie_* ignores the setting.  Added without a new version number: look the symbols up. */
 int piehip_set_chain_schedule(piehip_handle h, const uint32_t *Lc /*[n]*/, uint32_t n);
@@ -651,6 +654,32 @@ int piehip_client_encrypt(piehip_handle h, const uint64_t *sk, const int64_t *sl
                           const uint64_t *seeds, uint64_t *out);
 /* Decrypt + GetPackedValue (BatchedFHEPSIClient.cpp:249-265): ct[nct][2][L][N] -> slots[nct][B] (centred) */
 int piehip_client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots);
+/* Decryption that also measures the invariant noise budget: what a client runs before it relies on piehip_set_result_limbs,
+ * piehip_set_result_relin, piehip_set_chain_limbs or piehip_set_chain_schedule, none of which checks noise.
+ * Definition.  Decryption rounds t x / Q coefficient by coefficient, x = c0 + c1 s (+ c2 s^2) in COEFFICIENT format; the device forms
+ * the fractional part of t x / Q as fsum, the sum over the limbs of the 60-bit truncated fractions of t y_i / q_i (y_i the CRT digits
+ * of x).  For coefficient n of ciphertext c:  f = fsum mod 2^60,  d(c, n) = min(f, 2^60 - f),  and
+ *     max_dist[c] = max of d(c, n) over ALL N coefficients, whatever B is
+ * -- the largest distance of t x / Q from an integer, in units of 2^-60: decryption is right while it stays below 2^59.
+ *   piehip_budget_from_distance  the readout, in bits: 58 for max_dist = 0, otherwise 59 - bitlength(max_dist) clamped to [0, 58], i.e.
+ *                                floor(-log2(2 max_dist / 2^60)).  Host arithmetic, no handle.  It is the CPU oracle's readout word
+ *                                for word, and like it saturates at 57-58: every limb's fraction is truncated below 2^-60, so a
+ *                                noiseless ciphertext of several limbs may read a few units away from 0.
+ *   piehip_client_decrypt_budget ct[nct][ncomp][L][N], ncomp = 2 or 3 -> budget[c] = piehip_budget_from_distance(max_dist[c]);
+ *                                max_dist[nct] itself where the pointer is not null; slots[nct][B] bit-identical to
+ *                                piehip_client_decrypt (ncomp = 2) and piehip_client_decrypt_deg2 (ncomp = 3).  B = 0 (slots may then
+ *                                be null): the budgets alone, without the transform mod t and the gather.  Any context: rows reduced
+ *                                to keep < L limbs are measured on a context of the chain q[:keep] with the first keep limbs of the key,
+ *                                as they are decrypted.
+ * A budget of 0 means that some coefficient is at least a quarter away from an integer: the plaintext is not to be trusted.  The number
+ * is a MEASUREMENT on one ciphertext under one key, not a worst-case bound: leave a margin for other queries, databases and keys.
+ * PIEHIP_EINVAL, before anything reaches the device (budget, max_dist and slots are not written): a null handle, sk, ct or budget;
+ * nct = 0; ncomp outside {2, 3}; B > N; null slots with B > 0.  Added without a new version number: look the symbols up. */
+int piehip_client_decrypt_budget(piehip_handle h, const uint64_t *sk, const uint64_t *ct /*[nct][ncomp][L][N]*/,
+                                 uint32_t nct, uint32_t ncomp /*2 or 3*/, uint32_t B,
+                                 int64_t *slots /*[nct][B]; null iff B == 0*/,
+                                 int32_t *budget /*[nct]*/, uint64_t *max_dist /*[nct], may be null*/);
+int piehip_budget_from_distance(uint64_t max_dist);   /* host only, no handle */
 
 /* ---- seeded ciphertexts: the client uploads c0, the device regenerates c1 ---------------------------------------------------
  * A secret-key ciphertext (c0, c1) = (-a s + e + round(Q m / t), a) -- how the reference client encrypts every query ciphertext

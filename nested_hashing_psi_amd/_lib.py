@@ -131,6 +131,8 @@ SYMBOLS = {
     "piehip_get_result_relin": (C.c_int, [C.c_void_p, i32p]),
     "piehip_get_result_components": (C.c_int, [C.c_void_p, u32p]),
     "piehip_client_decrypt_deg2": (C.c_int, [C.c_void_p, u64p, u64p, C.c_uint32, C.c_uint32, i64p]),
+    "piehip_client_decrypt_budget": (C.c_int, [C.c_void_p, u64p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, i64p, i32p, u64p]),
+    "piehip_budget_from_distance": (C.c_int, [C.c_uint64]),
     "piehip_query_slice": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, u32p, u32p]),
     "piehip_load_db_table_sliced": (C.c_int, [C.c_void_p, u64p] + [C.c_uint32] * 5 + [C.c_uint64] * 2 + [C.c_uint32] * 4),
     "piehip_load_db_sliced": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [u64p, C.c_uint32, C.c_uint32, u64p]),

@@ -10,7 +10,7 @@ import secrets
 
 import numpy as np
 
-from ._lib import i64p, lib, u8p, u64p
+from ._lib import i32p, i64p, lib, u8p, u64p
 from .pie import _check, _u64, tabulation_hash
 
 
@@ -177,10 +177,8 @@ class BatchedFHEPSIClient:
             cache[limbs] = type(cc)(cc.N, limbs, cc.t, chain[:limbs], chain[limbs:2 * limbs + 1])
         return cache[limbs]
 
-    def decrypt(self, cts, nslots=None, limbs=None):
-        """cts [n][2][L][N] -> slots [n][nslots].  limbs = keep < L: cts [n][2][keep][N] as a server with setResultLimbs(keep)
-        returns them, decrypted in the reduced context with the first `keep` limbs of the secret key.  Three-component rows
-        [n][3][..][N] (a server with setResultRelin(False)) are recognised by their shape and decrypt as c0 + c1 s + c2 s^2."""
+    def _decrypt_operands(self, cts, limbs):
+        """(array, its pointer, handle, key) of a decryption on `limbs` limbs"""
         cc = self.cc
         a, ap = _u64(cts)
         limbs = cc.L if limbs is None else int(limbs)
@@ -188,15 +186,38 @@ class BatchedFHEPSIClient:
             raise ValueError("limbs must be between 1 and L")
         if a.ndim != 4 or a.shape[1] not in (2, 3) or a.shape[2:] != (limbs, cc.N):
             raise ValueError("ciphertexts must be [n][2][%d][N] (or [n][3][%d][N]: not relinearised)" % (limbs, limbs))
-        n = a.shape[0]
-        nslots = nslots or self.B
-        out = _out((n, nslots), np.int64)
         h, sk = cc._h, self.sk
         if limbs < cc.L:
             h, sk = self._reduced_context(limbs)._h, np.ascontiguousarray(self.sk[:limbs])
+        return a, ap, h, sk
+
+    def decrypt(self, cts, nslots=None, limbs=None, budget=False):
+        """cts [n][2][L][N] -> slots [n][nslots].  limbs = keep < L: cts [n][2][keep][N] as a server with setResultLimbs(keep)
+        returns them, decrypted in the reduced context with the first `keep` limbs of the secret key.  Three-component rows
+        [n][3][..][N] (a server with setResultRelin(False)) are recognised by their shape and decrypt as c0 + c1 s + c2 s^2.
+        budget=True: (slots, budgets), budgets [n] int32 the invariant noise budget of every ciphertext in bits
+        (piehip_client_decrypt_budget: measured on these ciphertexts under this key, not a bound)."""
+        a, ap, h, sk = self._decrypt_operands(cts, limbs)
+        n = a.shape[0]
+        nslots = nslots or self.B
+        out = _out((n, nslots), np.int64)
+        if budget:
+            bud = _out((n,), np.int32)
+            _check(lib().piehip_client_decrypt_budget(h, sk.ctypes.data_as(u64p), ap, n, a.shape[1], nslots, out.ctypes.data_as(i64p),
+                                                      bud.ctypes.data_as(i32p), None))
+            return out, bud
         dec = lib().piehip_client_decrypt_deg2 if a.shape[1] == 3 else lib().piehip_client_decrypt
         _check(dec(h, sk.ctypes.data_as(u64p), ap, n, nslots, out.ctypes.data_as(i64p)))
         return out
+
+    def noiseBudget(self, cts, limbs=None):
+        """the smallest invariant noise budget among the ciphertexts, in bits; nothing is decoded (the B = 0 form of
+        piehip_client_decrypt_budget).  0: some ciphertext is not to be trusted"""
+        a, ap, h, sk = self._decrypt_operands(cts, limbs)
+        n = a.shape[0]
+        bud = _out((n,), np.int32)
+        _check(lib().piehip_client_decrypt_budget(h, sk.ctypes.data_as(u64p), ap, n, a.shape[1], 0, None, bud.ctypes.data_as(i32p), None))
+        return int(bud.min())
 
     # -- online (BatchedFHEPSIClient.cpp:176-192): zero slot in any of the b results <=> item in the intersection
     def extractIntersection(self, resultList, limbs=None):

@@ -312,6 +312,8 @@ void launch_ks_finish(const DevConsts *dc, u32 N, u32 L, const u64 *e, const u64
 void launch_square(const DevConsts *dc, u32 N, u32 L, const u64 *s, u64 *s2, hipStream_t st);
 void launch_dec_dot(const DevConsts *dc, u32 N, u32 L, const u64 *ct, const u64 *sk, u64 *xs, u32 nct, hipStream_t st, u32 ncomp = 2);
 void launch_dec_round(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *xs, u64 *coeff_t, u32 nct, hipStream_t st);
+void launch_dec_round_budget(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *xs, u64 *coeff_t, u64 *max_dist, u32 nct,
+                             hipStream_t st);
 void launch_decode_gather(const DevConsts *dc, u32 N, u32 M, const u64 *u, const u32 *slot_pos, u32 B, int64_t *slots, u32 nct,
                           hipStream_t st);
 

@@ -86,16 +86,15 @@ __global__ void __launch_bounds__(CTPB) dec_dot_kernel(const DevConsts *__restri
     xs[(size_t)c * LN + x] = addmod(p[0], mulmod(hi, sk[x], m), m.q);
 }
 
-// COEFFICIENT x (mod Q) -> m = round(t x / Q) mod t   (HPS scale-and-round, 60-bit fixed-point rounding term)
-__global__ void __launch_bounds__(CTPB) dec_round_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 M,
-                                                         const u64 *__restrict__ xs, u64 *__restrict__ coeff_t)
+// coefficient n of ciphertext c: COEFFICIENT x (mod Q) -> m = round(t x / Q) mod t   (HPS scale-and-round, 60-bit fixed-point
+// rounding term); fsum: the sum of the L truncated 60-bit fractions of t y_i / q_i, whose fractional part is that of t x / Q
+__device__ __forceinline__ u64 dec_round_coeff(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 M, const u64 *__restrict__ xs, u32 c,
+                                               u32 n, u64 &fsum)
 {
-    const u32 n = blockIdx.x * CTPB + threadIdx.x;
-    if (n >= N) return;
-    const u32 c = blockIdx.y;
     const Mod mt = dc->mod[M];
     const u64 t = mt.q;
-    u64 acc = 0, fsum = 0;
+    u64 acc = 0;
+    fsum = 0;
     for (u32 i = 0; i < L; i++) {
         const Mod &mi = dc->mod[i];
         const u64 y = mul_shoup(xs[((size_t)c * L + i) * N + n], dc->qhat_inv[i], dc->qhat_inv_sh[i], mi.q);
@@ -107,7 +106,49 @@ __global__ void __launch_bounds__(CTPB) dec_round_kernel(const DevConsts *__rest
     const u64 rnd = (fsum + FIX_HALF) >> 60;
     u64 r = acc + rnd;  // rnd <= L
     while (r >= t) r -= t;
-    coeff_t[(size_t)c * N + n] = r;
+    return r;
+}
+
+__global__ void __launch_bounds__(CTPB) dec_round_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 M,
+                                                         const u64 *__restrict__ xs, u64 *__restrict__ coeff_t)
+{
+    const u32 n = blockIdx.x * CTPB + threadIdx.x;
+    if (n >= N) return;
+    const u32 c = blockIdx.y;
+    u64 fsum;
+    coeff_t[(size_t)c * N + n] = dec_round_coeff(dc, N, L, M, xs, c, n, fsum);
+}
+
+// dec_round_kernel that keeps the fraction sum: max_dist[c] = max over all N coefficients of the distance of fsum mod 2^60 from
+// the nearest of 0 and 2^60, the distance of t x / Q from an integer in units of 2^-60 (the oracle's po_decrypt reads its noise
+// budget from the same number).  Reduced over the 64 lanes of a wave, then over the block's waves through LDS, then one 64-bit
+// atomicMax per block; max_dist is zeroed by the caller.  Threads behind the ring (N < 256) hold 0 and reach the barrier.
+// coeff_t == null: the budget alone.
+__global__ void __launch_bounds__(CTPB) dec_round_budget_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 M,
+                                                                const u64 *__restrict__ xs, u64 *__restrict__ coeff_t,
+                                                                u64 *__restrict__ max_dist)
+{
+    __shared__ u64 wave_max[CTPB / 64];
+    const u32 n = blockIdx.x * CTPB + threadIdx.x;
+    const u32 c = blockIdx.y;
+    u64 d = 0;
+    if (n < N) {
+        u64 fsum;
+        const u64 r = dec_round_coeff(dc, N, L, M, xs, c, n, fsum);
+        if (coeff_t) coeff_t[(size_t)c * N + n] = r;
+        const u64 f = fsum & (FIX_ONE - 1);
+        d = f < FIX_ONE - f ? f : FIX_ONE - f;
+    }
+    for (u32 s = 32; s; s >>= 1) {
+        const u64 o = __shfl_xor(d, s, 64);
+        d = o > d ? o : d;
+    }
+    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (u32 w = 1; w < CTPB / 64; w++) d = wave_max[w] > d ? wave_max[w] : d;
+        if (d) atomicMax((unsigned long long *)&max_dist[c], (unsigned long long)d);
+    }
 }
 
 // slots[c][i] = centred value at EVALUATION position slot_pos[i]
@@ -145,6 +186,12 @@ void launch_dec_dot(const DevConsts *dc, u32 N, u32 L, const u64 *ct, const u64 
 void launch_dec_round(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *xs, u64 *coeff_t, u32 nct, hipStream_t st)
 {
     hipLaunchKernelGGL(dec_round_kernel, dim3((N + CTPB - 1) / CTPB, nct), dim3(CTPB), 0, st, dc, N, L, M, xs, coeff_t);
+}
+// max_dist[nct] must be zero when the kernel starts (an atomicMax per block lands in it); coeff_t may be null
+void launch_dec_round_budget(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *xs, u64 *coeff_t, u64 *max_dist, u32 nct,
+                             hipStream_t st)
+{
+    hipLaunchKernelGGL(dec_round_budget_kernel, dim3((N + CTPB - 1) / CTPB, nct), dim3(CTPB), 0, st, dc, N, L, M, xs, coeff_t, max_dist);
 }
 void launch_decode_gather(const DevConsts *dc, u32 N, u32 M, const u64 *u, const u32 *slot_pos, u32 B, int64_t *slots, u32 nct,
                           hipStream_t st)

@@ -147,5 +147,6 @@ PH_HD void divmod_shoup(u64 a, u64 w, u64 wsh, u64 q, u64 &quot, u64 &rem)
 // identical on CPU and GPU (SURVEY.md section 7 "HPS floating-point corrections").
 PH_HD u64 fixfrac(u64 y, const Mod &m) { return mulhi(y << m.fshift, m.fconst) >> 3; }
 static const u64 FIX_HALF = 1ULL << 59;
+static const u64 FIX_ONE = 1ULL << 60;
 
 }  // namespace piehip

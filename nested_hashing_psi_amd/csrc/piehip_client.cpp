@@ -262,16 +262,15 @@ int piehip_client_encrypt_seeded(piehip_handle h, const uint64_t *sk, const int6
     return client_encrypt(h, sk, slots, nct, B, noise_seeds, a_seeds, c0);
 }
 
-// ncomp components per ciphertext: 2, or 3 for rows of a product that was not relinearised (piehip_client_decrypt_deg2)
-static int client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots, u32 ncomp)
+// the device side of decryption, arguments checked by the caller.  max_dist == null: slots alone, as piehip_client_decrypt(_deg2)
+// always ran it.  Otherwise the rounding kernel is the one that keeps the fraction sums: max_dist[nct] comes back with them, and
+// with B == 0 the transform mod t and the gather are left out (slots is not touched)
+static int decrypt_on_device(piehip_ctx *h, Tmp &tmp, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots,
+                             u32 ncomp, uint64_t *max_dist)
 {
-    NEED(h);
-    if (!sk || !ct || !slots || !nct) return fail(PIEHIP_EINVAL, "null operand");
-    if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size exceeds the ring dimension");
     HIPCHK(hipSetDevice(h->device));
     const u32 N = h->hp.N, L = h->hp.L, M = h->hp.M;
     const size_t LN = h->LN();
-    Tmp tmp;
     TMPGET(d_ct, (size_t)nct * ncomp * LN);
     TMPGET(d_sk, LN);
     TMPGET(d_x, (size_t)nct * LN);
@@ -281,15 +280,39 @@ static int client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *c
     HIPCHK(hipMemcpy(d_ct, ct, (size_t)nct * ncomp * LN * sizeof(u64), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_sk, sk, LN * sizeof(u64), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_posw, h->hp.slot_pos.data(), sizeof(u32) * N, hipMemcpyHostToDevice));
+    u64 *d_md = nullptr;
+    if (max_dist) {
+        d_md = tmp.get(nct);
+        if (!d_md) return fail(PIEHIP_ENOMEM, "hipMalloc failed (scratch)");
+    }
     launch_dec_dot(h->d_dc, N, L, d_ct, d_sk, d_x, nct, h->stream, ncomp);
     launch_ntt(h->plan, d_x, nct * L, 0, L, true, h->stream);
-    launch_dec_round(h->d_dc, N, L, M, d_x, d_u, nct, h->stream);
-    launch_ntt(h->plan, d_u, nct, M, 1, false, h->stream);
-    launch_decode_gather(h->d_dc, N, M, d_u, (const u32 *)d_posw, B, (int64_t *)d_slotsw, nct, h->stream);
+    if (max_dist) {
+        // scratch is recycled: the block maxima land in zeroes, set on the stream the kernel runs on
+        HIPCHK(hipMemsetAsync(d_md, 0, (size_t)nct * sizeof(u64), h->stream));
+        launch_dec_round_budget(h->d_dc, N, L, M, d_x, B ? d_u : nullptr, d_md, nct, h->stream);
+    } else {
+        launch_dec_round(h->d_dc, N, L, M, d_x, d_u, nct, h->stream);
+    }
+    if (B || !max_dist) {
+        launch_ntt(h->plan, d_u, nct, M, 1, false, h->stream);
+        launch_decode_gather(h->d_dc, N, M, d_u, (const u32 *)d_posw, B, (int64_t *)d_slotsw, nct, h->stream);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(slots, d_slotsw, sizeof(int64_t) * (size_t)nct * B, hipMemcpyDeviceToHost));
+    if (B || !max_dist) HIPCHK(hipMemcpy(slots, d_slotsw, sizeof(int64_t) * (size_t)nct * B, hipMemcpyDeviceToHost));
+    if (max_dist) HIPCHK(hipMemcpy(max_dist, d_md, (size_t)nct * sizeof(u64), hipMemcpyDeviceToHost));
     return PIEHIP_OK;
+}
+
+// ncomp components per ciphertext: 2, or 3 for rows of a product that was not relinearised (piehip_client_decrypt_deg2)
+static int client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots, u32 ncomp)
+{
+    NEED(h);
+    if (!sk || !ct || !slots || !nct) return fail(PIEHIP_EINVAL, "null operand");
+    if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size exceeds the ring dimension");
+    Tmp tmp;
+    return decrypt_on_device(h, tmp, sk, ct, nct, B, slots, ncomp, nullptr);
 }
 
 int piehip_client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots)
@@ -299,6 +322,33 @@ int piehip_client_decrypt(piehip_handle h, const uint64_t *sk, const uint64_t *c
 int piehip_client_decrypt_deg2(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t B, int64_t *slots)
 {
     return client_decrypt(h, sk, ct, nct, B, slots, 3);
+}
+
+int piehip_budget_from_distance(uint64_t max_dist)
+{
+    if (!max_dist) return 58;
+    const int budget = 59 - (64 - __builtin_clzll(max_dist));  // 59 - bit length
+    return budget < 0 ? 0 : (budget > 58 ? 58 : budget);
+}
+
+int piehip_client_decrypt_budget(piehip_handle h, const uint64_t *sk, const uint64_t *ct, uint32_t nct, uint32_t ncomp, uint32_t B,
+                                 int64_t *slots, int32_t *budget, uint64_t *max_dist)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!sk || !ct || !budget || !nct) return fail(PIEHIP_EINVAL, "null operand");
+    if (ncomp != 2 && ncomp != 3) return fail(PIEHIP_EINVAL, "a ciphertext has 2 or 3 components");
+    if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size exceeds the ring dimension");
+    if (B && !slots) return fail(PIEHIP_EINVAL, "null slots");
+    NEED(h);
+    std::vector<u64> md(nct);
+    {
+        Tmp tmp(h);
+        int rc = decrypt_on_device(h, tmp, sk, ct, nct, B, slots, ncomp, md.data());
+        if (rc) return rc;
+    }
+    for (u32 c = 0; c < nct; c++) budget[c] = piehip_budget_from_distance(md[c]);
+    if (max_dist) std::copy(md.begin(), md.end(), max_dist);
+    return PIEHIP_OK;
 }
 
 }  // extern "C"

@@ -511,7 +511,7 @@ class BatchedFHEHIPPIE:
         """the product chain of run() works on the first Lc limbs of the chain (piehip_set_chain_limbs; L = as ever): every accumulator
         is dropped to Lc limbs behind stage A and every product runs on the level context (N, Lc, t, q[:Lc], p[:Lc+1]).  Result arrays
         are [..][min(resultLimbs, Lc)][N] and decrypt with client.decrypt(.., limbs=that).  The noise budget is the caller's business
-        (include/piehip.h "Chain limbs").  Page-locked result arrays follow the setting: ask hostBuffers() again after changing it."""
+        (include/piehip.h "Chain limbs"; client.decrypt(.., budget=True) measures it).  Page-locked result arrays follow the setting: ask hostBuffers() again after changing it."""
         self.cc.setChainLimbs(Lc)
         self._results = None
 
@@ -523,7 +523,7 @@ class BatchedFHEHIPPIE:
         """product hf = 1, 2, .. of run()'s chain on limbs[min(hf, len(limbs)) - 1] limbs (piehip_set_chain_schedule; non-increasing): the
         accumulators, and the product before where it has more limbs, are dropped on their way into each product.  Result arrays are
         [..][min(resultLimbs, chainLimbs())][N].  setChainLimbs(x) is the schedule [x].  The noise budget is the caller's business
-        (include/piehip.h "Chain limbs").  Page-locked result arrays follow the setting: ask hostBuffers() again after changing it."""
+        (include/piehip.h "Chain limbs"; schedule.choose_chain_schedule measures every candidate and picks by it).  Page-locked result arrays follow the setting: ask hostBuffers() again after changing it."""
         self.cc.setChainSchedule(limbs)
         self._results = None
 
