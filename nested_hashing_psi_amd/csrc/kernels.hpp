@@ -173,20 +173,50 @@ void launch_stage_a_batch(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E
                           const StageAXOut *xo = nullptr);
 
 // Base conversions, COEFFICIENT format.  Polynomial (o, c), o < n_outer, c < 2,
-// is read at in + o*in_stride_outer + c*in_stride_inner ([L][N] limbs) and written to
-// out + ((o*out_polys + out_slot + c)*M)*N ([M][N] limbs).
-// skip_q: leave the Q limbs of the output alone (they already hold the operand's EVALUATION form, see NttExtra)
+// is read at in + o*in_stride_outer + c*in_stride_inner ([L][N] limbs, canonical, nothing pending) and written to
+// out + ((o*out_polys + out_slot + c)*M)*N ([M][N] limbs): every limb, no folding (piehip_base_convert)
 // small_moduli (here and below): NttPlan::small_moduli of the context -- selects the v_mad_u64_u32 / one-word Barrett variants
 void launch_expand_q_to_qp(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t in_stride_outer,
                            size_t in_stride_inner, u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st,
-                           bool small_moduli, bool fold = false, bool skip_q = false);
+                           bool small_moduli);
 void launch_scale_pq_expand(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t in_stride_outer,
                             size_t in_stride_inner, u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st,
-                            bool small_moduli, bool fold = false);
-// both conversions of a ciphertext multiplication in one launch: X (polynomials at x + o*sx + c*si) centred-lifted into slots 0, 1
-// of out[n_outer][4][M][N], Y (at y + o*sy + c*si) scaled by P/Q into slots 2, 3
-void launch_expand_both(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, const u64 *y, size_t sy, size_t si, u32 n_outer,
-                        u64 *out, hipStream_t st, bool small_moduli, bool fold = false, bool skip_q = false);
+                            bool small_moduli);
+// Both conversions of a ciphertext multiplication in one launch, on the context (dc, L limbs, M = 2 L + 1; small_moduli and fold: its
+// plan's): X centred-lifted into slots 0, 1 of out[n_outer][4][M][N], Y scaled by P/Q into slots 2, 3.  fold: the outermost stage of
+// the forward transform that follows is applied on the store side (kernels_pie.hip, "Outer-stage folding").
+// An operand: polynomial c of row o at p + o*row + c*poly, COEFFICIENT format, and how it arrives --
+//   neither of the below   as the context's inverse transform left it: [L][N] limbs; with fold the outer stage is pending, [0, 4q) residues
+//   plain                  [L][N] limbs, canonical, nothing pending even where the context folds (launch_chain_drop, an unfolded inverse
+//                          transform): a product on a level context, L < MAX_L
+//   src_L > L              chain limbs, fused: [src_L][N] limbs as the folded inverse transform of the level with src_L limbs left them
+//                          (src_dc: that level's constants); dropped to L limbs in the load phase.  Folded rings with every modulus in
+//                          (2^59, 2^60), and (Y's, X's, L) a combination expand_drop_built knows
+//   q_ready (X only)       the Q limbs of X in `out` already hold its EVALUATION form (NttExtra, StageAXOut) and are left alone
+// Built: both pending on one polynomial distance, L <= MAX_L; both plain; Y dropped with X dropped from Y's level (under Y's
+// constants) or another, or with X pending and q_ready.  false, nothing launched, for anything else.
+struct ExpandOperand {
+    const u64 *p = nullptr;
+    size_t row = 0, poly = 0;
+    const DevConsts *src_dc = nullptr;
+    u32 src_L = 0;
+    bool plain = false;
+    bool q_ready = false;
+};
+bool launch_expand_pair(const DevConsts *dc, u32 N, u32 L, const ExpandOperand &x, const ExpandOperand &y, u32 n_outer, u64 *out,
+                        hipStream_t st, bool small_moduli, bool fold);
+// the first case by its parts: both pending on the context's own level, rows sx and sy apart, polynomials si (lazy_inputs_check)
+inline bool launch_expand_both(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, const u64 *y, size_t sy, size_t si, u32 n_outer,
+                               u64 *out, hipStream_t st, bool small_moduli, bool fold = false, bool skip_q = false)
+{
+    ExpandOperand xo, yo;
+    xo.p = x, yo.p = y;
+    xo.row = sx, yo.row = sy, xo.poly = yo.poly = si;
+    xo.q_ready = skip_q;
+    return launch_expand_pair(dc, N, L, xo, yo, n_outer, out, st, small_moduli, fold);
+}
+// is the fused form built for Y on Ly limbs and X on Lx (Lx <= Lc: X is not dropped), both to Lc?  (-DPIEHIP_CHAIN_DROP_FUSED=0: never)
+bool expand_drop_built(u32 Ly, u32 Lx, u32 Lc);
 // e[nb][4][M][N] (a0 a1 b0 b1, EVALUATION) -> d[nb][3][M][N]
 void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 nb, hipStream_t st, bool small_moduli);
 // d[nb][3][M][N] (COEFFICIENT) -> components 0,1 to out01 + bin*stride01 + c*L*N, component 2 to out2 + bin*stride2
@@ -244,22 +274,6 @@ bool launch_limb_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, const u64 *in
 // per, gstride: the polynomials lie in groups of `per` neighbours, gstride words from group to group (0: one packed array)
 bool launch_chain_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, u64 *data, u32 npoly, hipStream_t st, bool fold, u32 per = 0,
                        size_t gstride = 0);
-// launch_expand_both on a level context (dc, L: the level's) for plain operands -- canonical, nothing pending -- with a polynomial
-// distance per operand (six, siy); fold: the store side alone (the forward transform that follows is a folded one).  L < MAX_L
-bool launch_expand_both_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, size_t six, const u64 *y, size_t sy, size_t siy,
-                              u32 n_outer, u64 *out, hipStream_t st, bool small_moduli, bool fold);
-// The fused form: both conversions of the level context (dc_level, Lc limbs) with the drop from the parent's L limbs (dc_parent) in
-// their load phase.  Folded rings with every modulus in (2^59, 2^60) only; Y (and X, x_drop) are accumulators on L limbs as the
-// parent's folded inverse transform left them; without x_drop X is a product on Lc limbs from the level's folded inverse transform
-// whose Q limbs the QP array already holds.  expand_both_drop_applies: the pair is built (-DPIEHIP_CHAIN_DROP_FUSED=0: none is)
-bool expand_both_drop_applies(u32 L, u32 Lc);
-bool launch_expand_both_drop(const DevConsts *dc_parent, const DevConsts *dc_level, u32 N, u32 L, u32 Lc, const u64 *x, size_t sx, size_t six,
-                             bool x_drop, const u64 *y, size_t sy, size_t siy, u32 n_outer, u64 *out, hipStream_t st);
-// Chain schedule: X is the product before, packed on Lx <= L limbs as level Lx's folded inverse transform left it (dc_x: that
-// level's constants), and is dropped to Lc like the accumulator Y.  Lx = L is launch_expand_both_drop with x_drop
-bool expand_both_drop_xy_applies(u32 L, u32 Lx, u32 Lc);
-bool launch_expand_both_drop_xy(const DevConsts *dc_parent, const DevConsts *dc_x, const DevConsts *dc_level, u32 N, u32 L, u32 Lx, u32 Lc,
-                                const u64 *x, size_t sx, size_t six, const u64 *y, size_t sy, size_t siy, u32 n_outer, u64 *out, hipStream_t st);
 // out[r][p] = in[r][map[p]] for nrows limbs
 void launch_permute(u32 N, const u64 *in, const u32 *map, u64 *out, u32 nrows, hipStream_t st);
 // packed encoding: slots[npt][B] -> u[npt][N] residues mod t at their EVALUATION positions

@@ -9,6 +9,7 @@
 #include <cassert>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "kernels.hpp"
 #include "madasm.h"
@@ -18,6 +19,31 @@
 namespace piehip {
 
 static const u32 TPB = 256;
+
+// Run-time values as template arguments.  with_u32<LO, HI>(v, f) calls f(std::integral_constant<u32, v>) for v in [LO, HI] and says
+// whether it did; with_bools(f, b...) calls f(std::bool_constant<b>...).  The callers' generic lambdas read the arguments as
+// constants (L_(), F_()) and guard with `if constexpr` whatever combination no kernel is built for.
+template <u32 LO, u32 HI, class F>
+static bool with_u32(u32 v, F &&f)
+{
+    if constexpr (LO <= HI) {
+        if (v != LO) return with_u32<LO + 1, HI>(v, f);
+        f(std::integral_constant<u32, LO>{});
+        return true;
+    }
+    return false;
+}
+template <class F>
+static void with_bools(F &&f)
+{
+    f();
+}
+template <class F, class... Bs>
+static void with_bools(F &&f, bool b, Bs... rest)
+{
+    if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Stage A (rows A3+A4): acc[beta][h][c][l][n] = sum_j idx[h][j][c][l][n] * db[h][beta][j][l][n] + minus[c][l][n]
@@ -486,6 +512,36 @@ __device__ __forceinline__ void fold_store(const DevConsts *dc, u32 a, u64 u, u6
     y1 = u + (4 * q - t);
 }
 
+// The limb drop of limb_drop_kernel (below) on the NP coefficient columns a thread holds, with the constants of the block that has all
+// L limbs, read per dropped limb through the laundered pointer (the convention above).  S63 (every modulus below 2^60): the shoup63
+// instruction block; otherwise limb_drop_kernel's own product.  Only c[..][0 .. KEEP) are meaningful afterwards.
+template <u32 L, u32 KEEP, int NP, bool S63>
+__device__ __forceinline__ void drop_limbs(const DevConsts *dc, u64 (&c)[NP][L])
+{
+#pragma unroll
+    for (u32 l = L - 1; l >= KEEP; l--) {
+        PIE_ITER_FENCE();
+        const DcC k = dc_iter(dc);
+        const u64 ql = k->mod[l].q;
+        u64 v[NP], s[NP];
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            v[p] = c[p][l];
+            s[p] = (u64)((int64_t)((ql >> 1) - v[p]) >> 63);  // all ones when the centred residue is negative
+        }
+#pragma unroll
+        for (u32 i = 0; i < l; i++) {
+            const u64 off = k->drop_off[l][i], w = k->drop_inv[l][i], wsh = k->drop_inv_sh[l][i], qi = k->mod[i].q;
+            const u64 nq = S63 ? neg_u(qi) : k->drop_negq[i];
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                const u64 x = c[p][i] - v[p] + off + (s[p] & (ql - off));
+                c[p][i] = S63 ? shoup63(x, w, wsh, nq) : mul_shoup_u(x, w, wsh, qi, nq);
+            }
+        }
+    }
+}
+
 // The RNS width L is a template parameter: with run-time trip counts hipcc indexes the per-coefficient residue
 // arrays dynamically and spills them to scratch.  NP coefficients (1, or the 2 of a folded pair) go through every
 // iteration together and share its constants.
@@ -601,13 +657,27 @@ __device__ __forceinline__ void scale_pq_core(const DevConsts *dc, const u64 (&x
     }
 }
 
+// How the L input residues of a conversion reach registers
+enum class ExpandIn {
+    pending,  // as the context's inverse transform left them.  FOLD: outer stage pending, residues in [0, 4q) (fold_load, or the
+              // merged-constant load where YIN)
+    plain,    // canonical, nothing pending (what chain_drop_kernel and an unfolded inverse transform leave): both halves are read as
+              // they are and FOLD is the store side alone -- the forward transform that follows is a folded one
+    drop,     // chain limbs, fused (folded rings, every modulus in (2^59, 2^60)): the polynomial has LSRC > L limbs as the SOURCE level's
+              // folded inverse transform left them.  fold_load and drop_limbs<LSRC, L> with that level's constants (dcs), then the
+              // conversion with this level's (dc): no pass over the operand, no buffer
+};
+// One conversion of polynomial (o, c) = (by / 2, by % 2): read at in + o so + c si, written to out[o][out_polys][M][N] at slot out_slot + c
 // SKIPQ (centred lift only): leave the Q limbs of the output alone, they already hold the operand's EVALUATION form
-template <bool SCALE, bool FOLD, u32 L, bool MAD, bool SKIPQ>
-__device__ __forceinline__ void expand_body(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ in, size_t so, size_t si,
-                                            u64 *__restrict__ out, u32 out_polys, u32 out_slot, u32 by)
+template <bool SCALE, bool FOLD, u32 L, bool MAD, bool SKIPQ, ExpandIn IN = ExpandIn::pending, u32 LSRC = L>
+__device__ __forceinline__ void expand_body(const DevConsts *__restrict__ dcs, const DevConsts *__restrict__ dc, u32 N,
+                                            const u64 *__restrict__ in, size_t so, size_t si, u64 *__restrict__ out, u32 out_polys,
+                                            u32 out_slot, u32 by)
 {
+    static_assert(IN == ExpandIn::pending || !SKIPQ, "Q limbs in place: an operand on this level's limbs, as its inverse transform left it");
+    static_assert(IN == ExpandIn::drop ? (LSRC > L && FOLD && MAD) : LSRC == L, "the drop: folded rings on the column-accumulator path");
     // the residues x_i themselves are not needed: the folded load multiplies by N^-1 (Q/q_i)^-1 in one go
-    constexpr bool YIN = FOLD && (SCALE || SKIPQ);
+    constexpr bool YIN = IN == ExpandIn::pending && FOLD && (SCALE || SKIPQ);
     const u32 n = blockIdx.x * TPB + threadIdx.x;
     const u32 H = N / 2;
     if (n >= (FOLD ? H : N)) return;
@@ -617,18 +687,28 @@ __device__ __forceinline__ void expand_body(const DevConsts *__restrict__ dc, u3
     u64 *pout = out + ((size_t)(o * out_polys + out_slot + c) * M) * N + n;
     constexpr int NP = FOLD ? 2 : 1;
     u64 x[NP][L], y[NP][M];
+    if constexpr (IN == ExpandIn::drop) {
+        u64 full[NP][LSRC];
 #pragma unroll
-    for (u32 i = 0; i < L; i++) {
-        if (YIN) {
-            PIE_ITER_FENCE();
-            const DcC c = dc_iter(dc);
-            const u64 q = c->mod[i].q, nq = neg_u(q), u = pin[(size_t)i * N], v = pin[(size_t)i * N + H];
-            x[0][i] = shoup63(u + v, c->fold_iaq[i], c->fold_iaq_sh[i], nq);            // u, v in [0, 4q)
-            x[NP - 1][i] = shoup63(u + (4 * q - v), c->fold_ibq[i], c->fold_ibq_sh[i], nq);
-        } else if (FOLD) {
-            fold_load(dc, i, pin[(size_t)i * N], pin[(size_t)i * N + H], x[0][i], x[NP - 1][i]);
-        } else {
-            x[0][i] = pin[(size_t)i * N];
+        for (u32 i = 0; i < LSRC; i++) fold_load(dcs, i, pin[(size_t)i * N], pin[(size_t)i * N + H], full[0][i], full[NP - 1][i]);
+        drop_limbs<LSRC, L, NP, true>(dcs, full);
+#pragma unroll
+        for (u32 i = 0; i < L; i++) x[0][i] = full[0][i], x[NP - 1][i] = full[NP - 1][i];
+    } else {
+#pragma unroll
+        for (u32 i = 0; i < L; i++) {
+            if (YIN) {
+                PIE_ITER_FENCE();
+                const DcC c = dc_iter(dc);
+                const u64 q = c->mod[i].q, nq = neg_u(q), u = pin[(size_t)i * N], v = pin[(size_t)i * N + H];
+                x[0][i] = shoup63(u + v, c->fold_iaq[i], c->fold_iaq_sh[i], nq);            // u, v in [0, 4q)
+                x[NP - 1][i] = shoup63(u + (4 * q - v), c->fold_ibq[i], c->fold_ibq_sh[i], nq);
+            } else if (FOLD && IN == ExpandIn::pending) {
+                fold_load(dc, i, pin[(size_t)i * N], pin[(size_t)i * N + H], x[0][i], x[NP - 1][i]);
+            } else {
+                x[0][i] = pin[(size_t)i * N];
+                if (FOLD) x[NP - 1][i] = pin[(size_t)i * N + H];
+            }
         }
     }
     // folded output: every result passes through fold_store into a transform that takes [0, 8q) -- [0, 4q) will do (LZ)
@@ -656,7 +736,7 @@ template <bool SCALE, bool FOLD, u32 L, bool MAD, bool SKIPQ>
 __global__ void __launch_bounds__(TPB) expand_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ in,
                                                      size_t so, size_t si, u64 *__restrict__ out, u32 out_polys, u32 out_slot)
 {
-    expand_body<SCALE, FOLD, L, MAD, SKIPQ>(dc, N, in, so, si, out, out_polys, out_slot, blockIdx.y);
+    expand_body<SCALE, FOLD, L, MAD, SKIPQ>(dc, dc, N, in, so, si, out, out_polys, out_slot, blockIdx.y);
 }
 // Both operands of a ciphertext multiplication in one launch: rows [0, 2 n) of the grid scale operand Y (P/Q scaling, the
 // longer body: first, so that the shorter rows fill in behind it), rows [2 n, 4 n) lift operand X.  As two launches each was
@@ -668,61 +748,30 @@ __global__ void __launch_bounds__(TPB) expand_both_kernel(const DevConsts *__res
                                                           u32 n_outer)
 {
     if (blockIdx.y < 2 * n_outer)
-        expand_body<true, FOLD, L, MAD, false>(dc, N, y, sy, si, out, 4, 2, blockIdx.y);
+        expand_body<true, FOLD, L, MAD, false>(dc, dc, N, y, sy, si, out, 4, 2, blockIdx.y);
     else
-        expand_body<false, FOLD, L, MAD, SKIPQ>(dc, N, x, sx, si, out, 4, 0, blockIdx.y - 2 * n_outer);
+        expand_body<false, FOLD, L, MAD, SKIPQ>(dc, dc, N, x, sx, si, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
-void launch_expand_both(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, const u64 *y, size_t sy, size_t si, u32 n_outer,
-                        u64 *out, hipStream_t st, bool small_moduli, bool fold, bool skip_q)
+// One conversion as a launch of its own (piehip_base_convert): plain operands of a context without folding in the call, nothing in place
+static void launch_expand_common(bool scale, const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t so, size_t si, u32 n_outer, u64 *out,
+                                 u32 out_polys, u32 out_slot, hipStream_t st, bool small_moduli)
 {
-    dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, n_outer * 4);
-#define EB(F_, L_, M_, Q_) hipLaunchKernelGGL((expand_both_kernel<F_, L_, M_, Q_>), grid, dim3(TPB), 0, st, dc, N, x, sx, y, sy, si, out, n_outer)
-#define EBL(L_)                                                                          \
-    case L_:                                                                             \
-        if (fold && small_moduli) { if (skip_q) EB(true, L_, true, true); else EB(true, L_, true, false); }      \
-        else if (fold) { if (skip_q) EB(true, L_, false, true); else EB(true, L_, false, false); }                 \
-        else if (small_moduli) { if (skip_q) EB(false, L_, true, true); else EB(false, L_, true, false); }       \
-        else { if (skip_q) EB(false, L_, false, true); else EB(false, L_, false, false); }                         \
-        break;
-    switch (L) { EBL(1) EBL(2) EBL(3) EBL(4) EBL(5) EBL(6) EBL(7) }
-#undef EBL
-#undef EB
-}
-
-static void launch_expand_common(bool scale, bool fold, const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t so, size_t si,
-                                 u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st, bool small_moduli, bool skip_q = false)
-{
-    dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, n_outer * 2);
-#define EX(S_, F_, L_, Q_)                                                                                                    \
-    do {                                                                                                                      \
-        if (small_moduli)                                                                                                   \
-            hipLaunchKernelGGL((expand_kernel<S_, F_, L_, true, Q_>), grid, dim3(TPB), 0, st, dc, N, in, so, si, out, out_polys, out_slot); \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((expand_kernel<S_, F_, L_, false, Q_>), grid, dim3(TPB), 0, st, dc, N, in, so, si, out, out_polys, out_slot); \
-    } while (0)
-#define EXL(L_)                                                         \
-    case L_:                                                            \
-        if (scale) {                                                    \
-            if (fold) EX(true, true, L_, false); else EX(true, false, L_, false); \
-        } else if (skip_q) {                                            \
-            if (fold) EX(false, true, L_, true); else EX(false, false, L_, true); \
-        } else {                                                        \
-            if (fold) EX(false, true, L_, false); else EX(false, false, L_, false); \
-        }                                                               \
-        break;
-    switch (L) { EXL(1) EXL(2) EXL(3) EXL(4) EXL(5) EXL(6) EXL(7) }
-#undef EXL
-#undef EX
+    dim3 grid((N + TPB - 1) / TPB, n_outer * 2);
+    with_u32<1, 7>(L, [&](auto L_) {
+        with_bools([&](auto S_, auto M_) {
+            hipLaunchKernelGGL((expand_kernel<S_(), false, L_(), M_(), false>), grid, dim3(TPB), 0, st, dc, N, in, so, si, out, out_polys, out_slot);
+        }, scale, small_moduli);
+    });
 }
 void launch_expand_q_to_qp(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t so, size_t si, u32 n_outer, u64 *out,
-                           u32 out_polys, u32 out_slot, hipStream_t st, bool small_moduli, bool fold, bool skip_q)
+                           u32 out_polys, u32 out_slot, hipStream_t st, bool small_moduli)
 {
-    launch_expand_common(false, fold, dc, N, L, in, so, si, n_outer, out, out_polys, out_slot, st, small_moduli, skip_q);
+    launch_expand_common(false, dc, N, L, in, so, si, n_outer, out, out_polys, out_slot, st, small_moduli);
 }
 void launch_scale_pq_expand(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t so, size_t si, u32 n_outer, u64 *out,
-                            u32 out_polys, u32 out_slot, hipStream_t st, bool small_moduli, bool fold)
+                            u32 out_polys, u32 out_slot, hipStream_t st, bool small_moduli)
 {
-    launch_expand_common(true, fold, dc, N, L, in, so, si, n_outer, out, out_polys, out_slot, st, small_moduli);
+    launch_expand_common(true, dc, N, L, in, so, si, n_outer, out, out_polys, out_slot, st, small_moduli);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -935,26 +984,14 @@ void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb,
     assert(!p_only01 || (small_moduli && fold_comp2 == p_only2));
     assert(!p_only2 || p_only01);
     dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, 3, nb);
-#define SRK2(F_, L_) \
-    hipLaunchKernelGGL((scale_round_kernel<F_, L_, true, true, true>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, F_ ? 1u : 0u)
-#define SRK(F_, L_, M_, P_) \
-    hipLaunchKernelGGL((scale_round_kernel<F_, L_, M_, P_>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2, stride2, (fold_comp2 && F_) ? 1u : 0u)
-#define SRL(L_)                                                                        \
-    case L_:                                                                           \
-        if (p_only2) {                                                                 \
-            if (fold) SRK2(true, L_); else SRK2(false, L_);                            \
-        } else if (p_only01) {                                                                \
-            if (fold) SRK(true, L_, true, true); else SRK(false, L_, true, true);      \
-        } else if (small_moduli) {                                                     \
-            if (fold) SRK(true, L_, true, false); else SRK(false, L_, true, false);    \
-        } else {                                                                       \
-            if (fold) SRK(true, L_, false, false); else SRK(false, L_, false, false);  \
-        }                                                                              \
-        break;
-    switch (L) { SRL(1) SRL(2) SRL(3) SRL(4) SRL(5) SRL(6) SRL(7) }
-#undef SRK
-#undef SRK2
-#undef SRL
+    const u32 fc2 = (fold_comp2 && fold) ? 1u : 0u;
+    with_u32<1, 7>(L, [&](auto L_) {
+        with_bools([&](auto F_, auto M_, auto P01_, auto P2_) {
+            if constexpr ((M_() || !P01_()) && (P01_() || !P2_()))
+                hipLaunchKernelGGL((scale_round_kernel<F_(), L_(), M_(), P01_(), P2_()>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2,
+                                   stride2, fc2);
+        }, fold, small_moduli, p_only01, p_only2);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -996,13 +1033,62 @@ void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stri
         hipLaunchKernelGGL(digits_kernel<false>, grid, dim3(TPB), 0, st, dc, N, L, d2, stride2, dig);
 }
 
+// The lane-order LDS tile of the key-switch MAC and the degree-2 finish.  Inputs in the lane order of a register-blocked transform with
+// T threads per slice and KP coefficient pairs per thread: pair k of thread tau sits at k T + tau and belongs at KP tau + k.  A block takes
+// the (256 / KP) x KP pairs of threads tau0 .. tau0 + 256 / KP - 1, i.e. KP contiguous runs of the lane order, and hands the results through
+// LDS so that they leave as one contiguous 4 KiB run of the standard order; with a plain out_map scatter every 16-byte store lands in its
+// own stretch.  KP = 16: kernels_ntt_fast.hip (32 coefficients per thread), KP = 8: ntt16_kernel.h.
+struct LaneTile {
+    u32 n;         // this thread's first coefficient, in lane order
+    u32 std_pair;  // first standard-order pair of the block's tile
+    u32 k, tt;     // the thread's place in the tile: pair k of the transform's thread tau0 + tt
+};
+template <int KP>
+__device__ __forceinline__ LaneTile lane_tile(u32 T)
+{
+    constexpr u32 TT = TPB / KP;  // threads of the transform per tile
+    const u32 tiles = T / TT, slice = blockIdx.x / tiles, tau0 = (blockIdx.x % tiles) * TT;
+    const u32 k = threadIdx.x / TT, tt = threadIdx.x % TT;
+    return {2 * (slice * KP * T + k * T + tau0 + tt), slice * KP * T + KP * tau0, k, tt};
+}
+// this thread's pair inside the tile, standard order: KP (tau - tau0) + k
+template <int KP>
+__device__ __forceinline__ u32 lane_tile_slot(const LaneTile &lt)
+{
+    return KP * lt.tt + lt.k;
+}
+// the host's side of it: a kernel built with KP = kp takes this lane order
+static bool lane_tile_applies(u32 N, u32 T, u32 kp)
+{
+    return (kp == 16 || kp == 8) && T >= TPB / kp && T % (TPB / kp) == 0 && (N / 2) % TPB == 0;
+}
+
+// The own-limb terms of one coefficient at limb j: v[c] = [t P^-1]_{q_j} (a (x) b)_c in [0, 4q) for the first NT components of the tensor
+// product (a0 b0, a0 b1 + a1 b0, a1 b1), formed as tensor_kernel<true> forms them: the operands ([0, 8q) residues) brought below 2q by
+// own_limb_operand's two sign-mask subtractions, d1's two products keep every column below 2^63, z < 8 q^2 < 2^123; one lazy reduction
+// block and one Shoup product with the constant each.
+__device__ __forceinline__ Split30 own_limb_operand(u64 w, u64 n2q, u64 n4q) { return split30(csub_u(csub_u(w, n4q), n2q)); }
+template <int NT>
+__device__ __forceinline__ void own_limb_terms(const Split30 &sa0, const Split30 &sa1, const Split30 &sb0, const Split30 &sb1, const Mod &m,
+                                               u64 nq, u64 tp, u64 tpsh, u64 (&v)[NT])
+{
+    ColAcc t = {0, 0, 0};
+    colacc_mac(t, sa0, sb0);
+    v[0] = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+    t = ColAcc{0, 0, 0};
+    colacc_mac(t, sa0, sb1);
+    colacc_mac(t, sa1, sb0);
+    v[1] = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+    if constexpr (NT == 3) {
+        t = ColAcc{0, 0, 0};
+        colacc_mac(t, sa1, sb1);
+        v[2] = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+    }
+}
+
 // One thread: two adjacent coefficients (16-byte lanes) of one (bin, limb j), both ciphertext components, so a
 // digit is loaded once for its two key products.  out_map (lane order -> standard) keeps pairs adjacent.
-// KP > 0 (lane-ordered inputs of a register-blocked transform with T threads per slice and KP coefficient pairs per thread:
-// pair k of thread tau sits at k T + tau and belongs at KP tau + k): a block takes the (256 / KP) x KP pairs of threads
-// tau0 .. tau0 + 256 / KP - 1, i.e. KP contiguous runs of the lane order, and hands the results through LDS so that they leave
-// as one contiguous 4 KiB run of the standard order; with the plain out_map scatter every 16-byte store lands in its own
-// stretch.  KP = 16: kernels_ntt_fast.hip (32 coefficients per thread), KP = 8: ntt16_kernel.h.
+// KP > 0: lane-ordered inputs, the stores go through the LDS tile (lane_tile above).
 // RPT = 2 (column-accumulator path only): one thread takes the same coefficient pair of TWO ciphertext rows that use the same key -- rows
 // r and r + key_group -- and loads every key word once for both.  The kernel is bound by the traffic through the L1s (330 MB per step at
 // the headline shape, more than half of it key words that every row re-reads from the L2: profiles/r05/stage_a_batch_layer_groups.txt
@@ -1010,7 +1096,7 @@ void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stri
 // EQ (column-accumulator path only; NttPlan::d01_eval_q): d01 arrives without the own-limb term of scale-and-round (scale_round_core, PONLY).
 // Its transform is [t P^-1]_{q_j} times limb j of the tensor product in EVALUATION form, which this kernel forms from the QP operands
 // eqp[row][4][eqp_M][N] (a0 a1 b0 b1 at limb j, ordered like d01, [0, 8q) residues) as tensor_kernel<true> does: t0 = a0 b0 for component
-// 0, t1 = a0 b1 + a1 b0 for component 1, each through one reduction block to [0, 4q) and one Shoup product with the constant.
+// 0, t1 = a0 b1 + a1 b0 for component 1 (own_limb_terms).
 template <bool MAD, int KP, int RPT = 1, bool EQ = false>
 __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, const u64 *__restrict__ d01,
                                                         size_t stride01, const u64 *__restrict__ dig,
@@ -1022,15 +1108,12 @@ __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restr
     static_assert(RPT == 1 || MAD, "two rows per thread: the column-accumulator path");
     static_assert(!EQ || MAD, "the own-limb term: the column-accumulator path");
     constexpr bool TILE = KP > 0;
-    constexpr u32 TT = TILE ? TPB / (KP ? KP : 1) : 1;  // threads of the transform per tile
     __shared__ u64x2 s_tile[TILE ? 2 * RPT : 1][TILE ? TPB : 1];
     u32 n = 2 * (blockIdx.x * TPB + threadIdx.x);
-    u32 std_pair = 0;  // TILE: first standard-order pair of this block's tile
-    if (TILE) {
-        const u32 tiles = T / TT, slice = blockIdx.x / tiles, tau0 = (blockIdx.x % tiles) * TT;
-        const u32 k = threadIdx.x / TT, tt = threadIdx.x % TT;
-        n = 2 * (slice * KP * T + k * T + tau0 + tt);
-        std_pair = slice * KP * T + KP * tau0;
+    LaneTile lt = {};
+    if constexpr (TILE) {
+        lt = lane_tile<KP>(T);
+        n = lt.n;
     }
     if (n >= N) return;
     const u32 j = blockIdx.y;
@@ -1091,16 +1174,11 @@ __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restr
                             vb0 = *reinterpret_cast<const u64x2 *>(pe + 2 * MN), vb1 = *reinterpret_cast<const u64x2 *>(pe + 3 * MN);
 #pragma unroll
                 for (int k = 0; k < 2; k++) {
-                    // operands below 2q (two sign-mask subtractions); d1's two products keep every column below 2^63, z < 8 q^2 < 2^123
-                    const Split30 sa0 = split30(csub_u(csub_u(k ? va0.y : va0.x, n4q), n2q)), sa1 = split30(csub_u(csub_u(k ? va1.y : va1.x, n4q), n2q));
-                    const Split30 sb0 = split30(csub_u(csub_u(k ? vb0.y : vb0.x, n4q), n2q)), sb1 = split30(csub_u(csub_u(k ? vb1.y : vb1.x, n4q), n2q));
-                    ColAcc t = {0, 0, 0};
-                    colacc_mac(t, sa0, sb0);
-                    const u64 v0 = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
-                    t = ColAcc{0, 0, 0};
-                    colacc_mac(t, sa0, sb1);
-                    colacc_mac(t, sa1, sb0);
-                    const u64 v1 = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+                    const Split30 sa0 = own_limb_operand(k ? va0.y : va0.x, n2q, n4q), sa1 = own_limb_operand(k ? va1.y : va1.x, n2q, n4q);
+                    const Split30 sb0 = own_limb_operand(k ? vb0.y : vb0.x, n2q, n4q), sb1 = own_limb_operand(k ? vb1.y : vb1.x, n2q, n4q);
+                    u64 v[2];
+                    own_limb_terms<2>(sa0, sa1, sb0, sb1, m, nq, tp, tpsh, v);
+                    const u64 v0 = v[0], v1 = v[1];
                     a[r][0][k].c0 += v0 & 0x3FFFFFFFull, a[r][0][k].c1 += v0 >> 30;
                     a[r][1][k].c0 += v1 & 0x3FFFFFFFull, a[r][1][k].c1 += v1 >> 30;
                 }
@@ -1164,8 +1242,9 @@ __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restr
         for (int c = 0; c < 2; c++) {
             if (r && !has[r]) continue;
             const u64x2 v = res[r][c];
-            if (TILE)
-                s_tile[2 * r + c][KP * (threadIdx.x % TT) + threadIdx.x / TT] = v;  // standard offset inside the tile: KP (tau - tau0) + k
+            if constexpr (TILE)
+                // (lane_tile_slot, formed again from threadIdx at the store as this kernel always did: from lt.k and lt.tt its listing changes)
+                s_tile[2 * r + c][KP * (threadIdx.x % (TPB / KP)) + threadIdx.x / (TPB / KP)] = v;
             else
                 *reinterpret_cast<u64x2 *>(out + ((size_t)rows[r] * 2 + c) * LN + (size_t)j * N + po) = v;
         }
@@ -1176,7 +1255,7 @@ __global__ void __launch_bounds__(TPB) relin_mac_kernel(const DevConsts *__restr
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 if (r && !has[r]) continue;
-                *reinterpret_cast<u64x2 *>(out + ((size_t)rows[r] * 2 + c) * LN + (size_t)j * N + 2 * (std_pair + threadIdx.x)) = s_tile[2 * r + c][threadIdx.x];
+                *reinterpret_cast<u64x2 *>(out + ((size_t)rows[r] * 2 + c) * LN + (size_t)j * N + 2 * (lt.std_pair + threadIdx.x)) = s_tile[2 * r + c][threadIdx.x];
             }
     }
 }
@@ -1188,32 +1267,22 @@ void launch_relin_mac(const DevConsts *dc, u32 N, u32 L, const u64 *d01, size_t 
     if (!key_group) key_group = 1;
     if (!mask_div) mask_div = 1;
     // sigma_T: out_map is the lane order of a register-blocked transform with sigma_T threads per slice, sigma_kp pairs per thread
-    const bool tile = out_map && (sigma_kp == 16 || sigma_kp == 8) && sigma_T >= TPB / sigma_kp && sigma_T % (TPB / sigma_kp) == 0 &&
-                      (N / 2) % TPB == 0;
+    const bool tile = out_map && lane_tile_applies(N, sigma_T, sigma_kp);
     const int kp = tile ? (int)sigma_kp : 0;
     // two rows per thread where at least two rows share a key (the column-accumulator path)
     const bool two = small_moduli && nb >= 2 * key_group;
     const u32 zrows = two ? ((nb + 2 * key_group - 1) / (2 * key_group)) * key_group : nb;
     dim3 grid((N / 2 + TPB - 1) / TPB, L, zrows);
-#define RME(M_, K_, R_, E_)                                                                                                            \
-    hipLaunchKernelGGL((relin_mac_kernel<M_, K_, R_, E_>), grid, dim3(TPB), 0, st, dc, N, L, d01, stride01, dig, key, mask, out, out_map, \
-                       key_stride, key_group, sigma_T, mask_div, nb, eqp, eqp_M)
-#define RM(M_, K_, R_) RME(M_, K_, R_, false)
-#define RQ(K_, R_) RME(true, K_, R_, true)
-    if (eqp && two) {
-        if (kp == 16) RQ(16, 2); else if (kp == 8) RQ(8, 2); else RQ(0, 2);
-    } else if (eqp) {
-        if (kp == 16) RQ(16, 1); else if (kp == 8) RQ(8, 1); else RQ(0, 1);
-    } else if (two) {
-        if (kp == 16) RM(true, 16, 2); else if (kp == 8) RM(true, 8, 2); else RM(true, 0, 2);
-    } else if (small_moduli) {
-        if (kp == 16) RM(true, 16, 1); else if (kp == 8) RM(true, 8, 1); else RM(true, 0, 1);
-    } else {
-        if (kp == 16) RM(false, 16, 1); else if (kp == 8) RM(false, 8, 1); else RM(false, 0, 1);
-    }
-#undef RQ
-#undef RM
-#undef RME
+    auto launch = [&](auto KP_) {
+        with_bools([&](auto M_, auto R2_, auto E_) {
+            if constexpr (M_() || (!R2_() && !E_()))   // two rows per thread and the own-limb term: the column-accumulator path
+                hipLaunchKernelGGL((relin_mac_kernel<M_(), KP_(), R2_() ? 2 : 1, E_()>), grid, dim3(TPB), 0, st, dc, N, L, d01, stride01, dig, key,
+                                   mask, out, out_map, key_stride, key_group, sigma_T, mask_div, nb, eqp, eqp_M);
+        }, small_moduli, two, eqp != nullptr);
+    };
+    if (kp == 16) launch(std::integral_constant<int, 16>{});
+    else if (kp == 8) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 0>{});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1229,12 +1298,9 @@ __global__ void __launch_bounds__(TPB) deg2_finish_kernel(const DevConsts *__res
                                                           const u64 *__restrict__ eqp, u32 eqp_M, const u64 *__restrict__ mask,
                                                           u64 *__restrict__ out, u32 T, u32 mask_div)
 {
-    constexpr u32 TT = TPB / KP;  // threads of the transform per tile
     __shared__ u64x2 s_tile[3][TPB];
-    const u32 tiles = T / TT, slice = blockIdx.x / tiles, tau0 = (blockIdx.x % tiles) * TT;
-    const u32 kk = threadIdx.x / TT, tt = threadIdx.x % TT;
-    const u32 n = 2 * (slice * KP * T + kk * T + tau0 + tt);
-    const u32 std_pair = slice * KP * T + KP * tau0;  // first standard-order pair of this block's tile
+    const LaneTile lt = lane_tile<KP>(T);
+    const u32 n = lt.n;
     const u32 j = blockIdx.y, row = blockIdx.z;
     const Mod m = dc->mod[j];
     const size_t LN = (size_t)L * N, MN = (size_t)eqp_M * N;
@@ -1250,21 +1316,11 @@ __global__ void __launch_bounds__(TPB) deg2_finish_kernel(const DevConsts *__res
     u64 res[3][2];
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-        // operands below 2q (two sign-mask subtractions); d1's two products keep every column below 2^63, z < 8 q^2 < 2^123
-        const Split30 sa0 = split30(csub_u(csub_u(k ? va0.y : va0.x, n4q), n2q)), sa1 = split30(csub_u(csub_u(k ? va1.y : va1.x, n4q), n2q));
-        const Split30 sb0 = split30(csub_u(csub_u(k ? vb0.y : vb0.x, n4q), n2q)), sb1 = split30(csub_u(csub_u(k ? vb1.y : vb1.x, n4q), n2q));
+        const Split30 sa0 = own_limb_operand(k ? va0.y : va0.x, n2q, n4q), sa1 = own_limb_operand(k ? va1.y : va1.x, n2q, n4q);
+        const Split30 sb0 = own_limb_operand(k ? vb0.y : vb0.x, n2q, n4q), sb1 = own_limb_operand(k ? vb1.y : vb1.x, n2q, n4q);
         const Split30 smk = split30(k ? mk.y : mk.x);
         u64 v[3];
-        ColAcc t = {0, 0, 0};
-        colacc_mac(t, sa0, sb0);
-        v[0] = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
-        t = ColAcc{0, 0, 0};
-        colacc_mac(t, sa0, sb1);
-        colacc_mac(t, sa1, sb0);
-        v[1] = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
-        t = ColAcc{0, 0, 0};
-        colacc_mac(t, sa1, sb1);
-        v[2] = shoup63_lazy(colacc_reduce123_lazy(t, m, nq), tp, tpsh, nq);
+        own_limb_terms<3>(sa0, sa1, sb0, sb1, m, nq, tp, tpsh, v);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             ColAcc a = {(k ? s[c].y : s[c].x) + (v[c] & 0x3FFFFFFFull), v[c] >> 30, 0};
@@ -1274,16 +1330,16 @@ __global__ void __launch_bounds__(TPB) deg2_finish_kernel(const DevConsts *__res
         }
     }
 #pragma unroll
-    for (int c = 0; c < 3; c++) s_tile[c][KP * tt + kk] = u64x2{res[c][0], res[c][1]};  // standard offset inside the tile: KP (tau - tau0) + k
+    for (int c = 0; c < 3; c++) s_tile[c][lane_tile_slot<KP>(lt)] = u64x2{res[c][0], res[c][1]};
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 3; c++)
-        *reinterpret_cast<u64x2 *>(out + ((size_t)row * 3 + c) * LN + (size_t)j * N + 2 * (std_pair + threadIdx.x)) = s_tile[c][threadIdx.x];
+        *reinterpret_cast<u64x2 *>(out + ((size_t)row * 3 + c) * LN + (size_t)j * N + 2 * (lt.std_pair + threadIdx.x)) = s_tile[c][threadIdx.x];
 }
 bool deg2_finish_applies(u32 N, u32 sigma_T, u32 sigma_kp)
 {
     // (the 16-coefficient kernel's lane order: the only one a plan with result_eval_q has)
-    return sigma_kp == 8 && sigma_T >= TPB / sigma_kp && sigma_T % (TPB / sigma_kp) == 0 && (N / 2) % TPB == 0;
+    return sigma_kp == 8 && lane_tile_applies(N, sigma_T, sigma_kp);
 }
 void launch_deg2_finish(const DevConsts *dc, u32 N, u32 L, const u64 *d, const u64 *eqp, u32 eqp_M, const u64 *mask, u64 *out, u32 nb,
                         hipStream_t st, u32 sigma_T, u32 sigma_kp, u32 mask_div)
@@ -1390,61 +1446,28 @@ __global__ void __launch_bounds__(TPB) limb_drop_kernel(const DevConsts *__restr
 #pragma unroll
     for (int i = 0; i < KEEP; i++) pout[(size_t)i * N] = c[i];
 }
+// the 21 pairs 1 <= keep < L <= MAX_L = 7 a drop kernel is built for, as template arguments
+template <class F>
+static bool with_limb_pair(u32 L, u32 keep, F &&f)
+{
+    bool built = false;
+    with_u32<2, 7>(L, [&](auto L_) { built = with_u32<1, L_() - 1>(keep, [&](auto K_) { f(L_, K_); }); });
+    return built;
+}
 bool launch_limb_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, const u64 *in, u64 *out, u32 npoly, hipStream_t st)
 {
     if (keep < 1 || keep >= L || L > MAX_L || !npoly) return false;
     const u32 bpp = (N + TPB - 1) / TPB;
     const dim3 grid(bpp * npoly), block(TPB);
-#define DROP_(L_, K_)                                                                                          \
-    case (L_) * 8 + (K_):                                                                                      \
-        hipLaunchKernelGGL((limb_drop_kernel<L_, K_>), grid, block, 0, st, dc, N, bpp, in, out);               \
-        return true
-    switch (L * 8 + keep) {
-        DROP_(2, 1);
-        DROP_(3, 1); DROP_(3, 2);
-        DROP_(4, 1); DROP_(4, 2); DROP_(4, 3);
-        DROP_(5, 1); DROP_(5, 2); DROP_(5, 3); DROP_(5, 4);
-        DROP_(6, 1); DROP_(6, 2); DROP_(6, 3); DROP_(6, 4); DROP_(6, 5);
-        DROP_(7, 1); DROP_(7, 2); DROP_(7, 3); DROP_(7, 4); DROP_(7, 5); DROP_(7, 6);
-    }
-#undef DROP_
-    return false;
+    return with_limb_pair(L, keep, [&](auto L_, auto K_) {
+        hipLaunchKernelGGL((limb_drop_kernel<(int)L_(), (int)K_()>), grid, block, 0, st, dc, N, bpp, in, out);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
 // Chain limbs (include/piehip.h "Chain limbs"): the limb drop in front of the product chain.  The accumulators leave stage A and
 // the inverse transform on the handle's L limbs; the chain runs on the level context of the first LC.
 // ---------------------------------------------------------------------------------------------
-// The limb drop of limb_drop_kernel on the NP coefficient columns a thread holds, with the constants of the PARENT's block, read per
-// dropped limb through the laundered pointer (the base conversions' convention above).  S63 (every modulus below 2^60): the
-// shoup63 instruction block; otherwise limb_drop_kernel's own product.  Only c[..][0 .. KEEP) are meaningful afterwards.
-template <u32 L, u32 KEEP, int NP, bool S63>
-__device__ __forceinline__ void drop_limbs(const DevConsts *dc, u64 (&c)[NP][L])
-{
-#pragma unroll
-    for (u32 l = L - 1; l >= KEEP; l--) {
-        PIE_ITER_FENCE();
-        const DcC k = dc_iter(dc);
-        const u64 ql = k->mod[l].q;
-        u64 v[NP], s[NP];
-#pragma unroll
-        for (int p = 0; p < NP; p++) {
-            v[p] = c[p][l];
-            s[p] = (u64)((int64_t)((ql >> 1) - v[p]) >> 63);  // all ones when the centred residue is negative
-        }
-#pragma unroll
-        for (u32 i = 0; i < l; i++) {
-            const u64 off = k->drop_off[l][i], w = k->drop_inv[l][i], wsh = k->drop_inv_sh[l][i], qi = k->mod[i].q;
-            const u64 nq = S63 ? neg_u(qi) : k->drop_negq[i];
-#pragma unroll
-            for (int p = 0; p < NP; p++) {
-                const u64 x = c[p][i] - v[p] + off + (s[p] & (ql - off));
-                c[p][i] = S63 ? shoup63(x, w, wsh, nq) : mul_shoup_u(x, w, wsh, qi, nq);
-            }
-        }
-    }
-}
-
 // The drop as a launch of its own (the fallback of the fused kernel below): npoly polynomials data[npoly][L][N] in COEFFICIENT format,
 // as the inverse transform left them -- FOLD: outer stage pending, residues in [0, 4q) -- are overwritten IN PLACE, at the parent's
 // strides, by their first KEEP limbs after the drop: canonical, nothing pending.  Limbs KEEP .. L - 1 keep what they held.  A thread
@@ -1483,142 +1506,41 @@ bool launch_chain_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, u64 *data, u
     if (npoly % per) return false;
     const u32 bpp = ((fold ? N / 2 : N) + TPB - 1) / TPB;
     const dim3 grid(bpp * npoly), block(TPB);
-#define CDROP_(L_, K_)                                                                                                            \
-    case (L_) * 8 + (K_):                                                                                                         \
-        if (fold) hipLaunchKernelGGL((chain_drop_kernel<true, L_, K_>), grid, block, 0, st, dc, N, bpp, data, per, gstride);      \
-        else hipLaunchKernelGGL((chain_drop_kernel<false, L_, K_>), grid, block, 0, st, dc, N, bpp, data, per, gstride);          \
-        return true
-    switch (L * 8 + keep) {
-        CDROP_(2, 1);
-        CDROP_(3, 1); CDROP_(3, 2);
-        CDROP_(4, 1); CDROP_(4, 2); CDROP_(4, 3);
-        CDROP_(5, 1); CDROP_(5, 2); CDROP_(5, 3); CDROP_(5, 4);
-        CDROP_(6, 1); CDROP_(6, 2); CDROP_(6, 3); CDROP_(6, 4); CDROP_(6, 5);
-        CDROP_(7, 1); CDROP_(7, 2); CDROP_(7, 3); CDROP_(7, 4); CDROP_(7, 5); CDROP_(7, 6);
-    }
-#undef CDROP_
-    return false;
+    return with_limb_pair(L, keep, [&](auto L_, auto K_) {
+        with_bools([&](auto F_) { hipLaunchKernelGGL((chain_drop_kernel<F_(), L_(), K_()>), grid, block, 0, st, dc, N, bpp, data, per, gstride); }, fold);
+    });
 }
 
-// Both conversions of a product on a level context whose operands are plain COEFFICIENT polynomials (canonical, nothing pending:
-// what chain_drop_kernel and an unfolded inverse transform leave), X and Y each with its own distance between the two polynomials
-// of a ciphertext -- the accumulators stay at the parent's strides, an intermediate product is packed.  FOLD is the store side alone:
-// the forward transform that follows is the level plan's.  expand_both_kernel's grid and row order.
-template <bool SCALE, bool FOLD, u32 L, bool MAD>
-__device__ __forceinline__ void expand_plain_body(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ in, size_t so, size_t si,
-                                                  u64 *__restrict__ out, u32 out_slot, u32 by)
-{
-    const u32 n = blockIdx.x * TPB + threadIdx.x;
-    const u32 H = N / 2;
-    if (n >= (FOLD ? H : N)) return;
-    const u32 o = by >> 1, c = by & 1;
-    constexpr u32 M = 2 * L + 1;
-    constexpr int NP = FOLD ? 2 : 1;
-    const u64 *pin = in + (size_t)o * so + (size_t)c * si + n;
-    u64 *pout = out + ((size_t)(o * 4 + out_slot + c) * M) * N + n;
-    u64 x[NP][L], y[NP][M];
-#pragma unroll
-    for (u32 i = 0; i < L; i++) {
-        x[0][i] = pin[(size_t)i * N];
-        if (FOLD) x[NP - 1][i] = pin[(size_t)i * N + H];
-    }
-    constexpr bool LZ = FOLD && MAD;
-    if (SCALE)
-        scale_pq_core<L, MAD, false, NP, LZ>(dc, x, y);
-    else
-        expand_core<L, MAD, false, NP, LZ>(dc, x, y);
-#pragma unroll
-    for (u32 a = 0; a < M; a++) {
-        PIE_ITER_FENCE();
-        if (FOLD) {
-            u64 y0, y1;
-            fold_store(dc, a, y[0][a], y[NP - 1][a], y0, y1);
-            pout[(size_t)a * N] = y0;
-            pout[(size_t)a * N + H] = y1;
-        } else {
-            pout[(size_t)a * N] = y[0][a];
-        }
-    }
-}
+// Both conversions of a product on a level context whose operands are plain COEFFICIENT polynomials (ExpandIn::plain), X and Y each
+// with its own distance between the two polynomials of a ciphertext -- the accumulators stay at the parent's strides, an intermediate
+// product is packed.  expand_both_kernel's grid and row order.
 template <bool FOLD, u32 L, bool MAD>
 __global__ void __launch_bounds__(TPB) expand_both_plain_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ x, size_t sx,
                                                                 size_t six, const u64 *__restrict__ y, size_t sy, size_t siy,
                                                                 u64 *__restrict__ out, u32 n_outer)
 {
     if (blockIdx.y < 2 * n_outer)
-        expand_plain_body<true, FOLD, L, MAD>(dc, N, y, sy, siy, out, 2, blockIdx.y);
+        expand_body<true, FOLD, L, MAD, false, ExpandIn::plain>(dc, dc, N, y, sy, siy, out, 4, 2, blockIdx.y);
     else
-        expand_plain_body<false, FOLD, L, MAD>(dc, N, x, sx, six, out, 0, blockIdx.y - 2 * n_outer);
-}
-bool launch_expand_both_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, size_t six, const u64 *y, size_t sy, size_t siy,
-                              u32 n_outer, u64 *out, hipStream_t st, bool small_moduli, bool fold)
-{
-    dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, n_outer * 4);
-#define EP(F_, L_, M_) hipLaunchKernelGGL((expand_both_plain_kernel<F_, L_, M_>), grid, dim3(TPB), 0, st, dc, N, x, sx, six, y, sy, siy, out, n_outer)
-#define EPL(L_)                                                              \
-    case L_:                                                                 \
-        if (fold && small_moduli) EP(true, L_, true);                        \
-        else if (fold) EP(true, L_, false);                                  \
-        else if (small_moduli) EP(false, L_, true);                          \
-        else EP(false, L_, false);                                           \
-        return true;
-    switch (L) { EPL(1) EPL(2) EPL(3) EPL(4) EPL(5) EPL(6) }   // a level context has fewer limbs than MAX_L
-#undef EPL
-#undef EP
-    return false;
+        expand_body<false, FOLD, L, MAD, false, ExpandIn::plain>(dc, dc, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
 
-// The fused form (folded rings, every modulus in (2^59, 2^60)): expand_both_kernel of the level context with the drop in front of its
-// conversions.  A thread loads its coefficient pair's L residues as the parent's folded inverse transform left them, applies the
-// outer stage and normalises (fold_load, the parent's constants), drops the limbs L - 1 .. LC (drop_limbs, the parent's constants)
-// and converts the LC residues with the LEVEL's constants into the level's QP operand rows [4][2 LC + 1][N] -- no pass over the
-// accumulators, no buffer.  The dropped X differs from what the QP array may hold in EVALUATION form, so X's Q limbs are written.
+// The fused form (folded rings, every modulus in (2^59, 2^60)): expand_both_kernel of the level context with the drop from the parent's
+// L limbs in front of its conversions (ExpandIn::drop; dcp: the parent's constants, dcl: the level's) into the level's QP operand rows
+// [4][2 LC + 1][N].  The dropped X differs from what the QP array may hold in EVALUATION form, so X's Q limbs are written.
 // XDROP false (later products of K >= 3): X is an intermediate product on the level's limbs, packed, as the level's folded inverse
-// transform left it -- expand_body's own load, Q limbs already in place (SKIPQ); Y is an accumulator and is dropped all the same.
-template <bool SCALE, u32 L, u32 LC>
-__device__ __forceinline__ void expand_drop_body(const DevConsts *__restrict__ dcp, const DevConsts *__restrict__ dcl, u32 N,
-                                                 const u64 *__restrict__ in, size_t so, size_t si, u64 *__restrict__ out, u32 out_slot, u32 by)
-{
-    const u32 n = blockIdx.x * TPB + threadIdx.x;
-    const u32 H = N / 2;
-    if (n >= H) return;
-    const u32 o = by >> 1, c = by & 1;
-    constexpr u32 M = 2 * LC + 1;
-    const u64 *pin = in + (size_t)o * so + (size_t)c * si + n;
-    u64 *pout = out + ((size_t)(o * 4 + out_slot + c) * M) * N + n;
-    u64 x[2][LC], y[2][M];
-    {
-        u64 full[2][L];
-#pragma unroll
-        for (u32 i = 0; i < L; i++) fold_load(dcp, i, pin[(size_t)i * N], pin[(size_t)i * N + H], full[0][i], full[1][i]);
-        drop_limbs<L, LC, 2, true>(dcp, full);
-#pragma unroll
-        for (u32 i = 0; i < LC; i++) x[0][i] = full[0][i], x[1][i] = full[1][i];
-    }
-    if (SCALE)
-        scale_pq_core<LC, true, false, 2, true>(dcl, x, y);
-    else
-        expand_core<LC, true, false, 2, true>(dcl, x, y);
-#pragma unroll
-    for (u32 a = 0; a < M; a++) {
-        PIE_ITER_FENCE();
-        u64 y0, y1;
-        fold_store(dcl, a, y[0][a], y[1][a], y0, y1);
-        pout[(size_t)a * N] = y0;
-        pout[(size_t)a * N + H] = y1;
-    }
-}
+// transform left it -- the pending load, Q limbs already in place (SKIPQ); Y is an accumulator and is dropped all the same.
 template <u32 L, u32 LC, bool XDROP>
 __global__ void __launch_bounds__(TPB) expand_both_drop_kernel(const DevConsts *__restrict__ dcp, const DevConsts *__restrict__ dcl, u32 N,
                                                                const u64 *__restrict__ x, size_t sx, size_t six, const u64 *__restrict__ y,
                                                                size_t sy, size_t siy, u64 *__restrict__ out, u32 n_outer)
 {
     if (blockIdx.y < 2 * n_outer)
-        expand_drop_body<true, L, LC>(dcp, dcl, N, y, sy, siy, out, 2, blockIdx.y);
+        expand_body<true, true, LC, true, false, ExpandIn::drop, L>(dcp, dcl, N, y, sy, siy, out, 4, 2, blockIdx.y);
     else if (XDROP)
-        expand_drop_body<false, L, LC>(dcp, dcl, N, x, sx, six, out, 0, blockIdx.y - 2 * n_outer);
+        expand_body<false, true, LC, true, false, ExpandIn::drop, L>(dcp, dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
     else
-        expand_body<false, true, LC, true, true>(dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
+        expand_body<false, true, LC, true, true>(dcl, dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
 // Chain schedule (include/piehip.h): a product of K >= 3 whose level LC lies below the level LX of the product before it.  Y is an
 // accumulator on the handle's LY limbs (dcy); X is that earlier product, packed on LX limbs as level LX's folded inverse transform
@@ -1631,9 +1553,9 @@ __global__ void __launch_bounds__(TPB) expand_both_drop_xy_kernel(const DevConst
                                                                   u64 *__restrict__ out, u32 n_outer)
 {
     if (blockIdx.y < 2 * n_outer)
-        expand_drop_body<true, LY, LC>(dcy, dcl, N, y, sy, siy, out, 2, blockIdx.y);
+        expand_body<true, true, LC, true, false, ExpandIn::drop, LY>(dcy, dcl, N, y, sy, siy, out, 4, 2, blockIdx.y);
     else
-        expand_drop_body<false, LX, LC>(dcx, dcl, N, x, sx, six, out, 0, blockIdx.y - 2 * n_outer);
+        expand_body<false, true, LC, true, false, ExpandIn::drop, LX>(dcx, dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
 // the (L, Lc) pairs the fused kernel is built for: Lc = L - 1 for every L, and the further pairs that stay free of scratch; the
 // (LY, LX, LC) triples of the chain schedule's form
@@ -1642,55 +1564,59 @@ __global__ void __launch_bounds__(TPB) expand_both_drop_xy_kernel(const DevConst
 #endif
 #define PIE_CHAIN_DROP_PAIRS(X_) X_(2, 1) X_(3, 2) X_(4, 3) X_(5, 4) X_(6, 5) X_(7, 6) X_(4, 2) X_(6, 4)
 #define PIE_CHAIN_DROP_TRIPLES(X_) X_(4, 3, 2) X_(6, 5, 4) X_(6, 4, 3)
-bool expand_both_drop_applies(u32 L, u32 Lc)
+bool expand_drop_built(u32 Ly, u32 Lx, u32 Lc)
 {
     if (!PIEHIP_CHAIN_DROP_FUSED) return false;
-#define APPL_(L_, C_) if (L == L_ && Lc == C_) return true;
-    PIE_CHAIN_DROP_PAIRS(APPL_)
-#undef APPL_
+#define PAIR_(L_, C_) if (Ly == L_ && Lc == C_ && (Lx <= C_ || Lx == L_)) return true;
+#define TRIPLE_(L_, X_, C_) if (Ly == L_ && Lx == X_ && Lc == C_) return true;
+    PIE_CHAIN_DROP_PAIRS(PAIR_)
+    PIE_CHAIN_DROP_TRIPLES(TRIPLE_)
+#undef TRIPLE_
+#undef PAIR_
     return false;
 }
-bool expand_both_drop_xy_applies(u32 L, u32 Lx, u32 Lc)
+
+// Both conversions of a product (kernels.hpp): the kernel follows from how the two operands arrive
+bool launch_expand_pair(const DevConsts *dc, u32 N, u32 L, const ExpandOperand &x, const ExpandOperand &y, u32 n_outer, u64 *out,
+                        hipStream_t st, bool small_moduli, bool fold)
 {
-    if (!PIEHIP_CHAIN_DROP_FUSED) return false;
-    if (Lx == L) return expand_both_drop_applies(L, Lc);
-#define APPL_(L_, X_, C_) if (L == L_ && Lx == X_ && Lc == C_) return true;
-    PIE_CHAIN_DROP_TRIPLES(APPL_)
-#undef APPL_
-    return false;
-}
-bool launch_expand_both_drop(const DevConsts *dc_parent, const DevConsts *dc_level, u32 N, u32 L, u32 Lc, const u64 *x, size_t sx, size_t six,
-                             bool x_drop, const u64 *y, size_t sy, size_t siy, u32 n_outer, u64 *out, hipStream_t st)
-{
-    if (!expand_both_drop_applies(L, Lc)) return false;
-    dim3 grid((N / 2 + TPB - 1) / TPB, n_outer * 4);
-#define EBD_(L_, C_)                                                                                                                     \
-    if (L == L_ && Lc == C_) {                                                                                                           \
-        if (x_drop)                                                                                                                      \
-            hipLaunchKernelGGL((expand_both_drop_kernel<L_, C_, true>), grid, dim3(TPB), 0, st, dc_parent, dc_level, N, x, sx, six, y, sy, siy, out, n_outer);  \
-        else                                                                                                                             \
-            hipLaunchKernelGGL((expand_both_drop_kernel<L_, C_, false>), grid, dim3(TPB), 0, st, dc_parent, dc_level, N, x, sx, six, y, sy, siy, out, n_outer); \
-        return true;                                                                                                                     \
+    const bool ydrop = y.src_L > L, xdrop = x.src_L > L;
+    const dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, n_outer * 4), block(TPB);
+    if (ydrop) {   // fused limb drop: X is dropped too, or lies on this level with its Q limbs in place
+        if (!fold || !small_moduli || x.plain || y.plain || x.q_ready == xdrop || !expand_drop_built(y.src_L, xdrop ? x.src_L : L, L)) return false;
+#define PAIR_(L_, C_)                                                                                                                          \
+    if (y.src_L == L_ && L == C_ && (!xdrop || x.src_L == L_)) {   /* (an X on Y's limbs is under Y's constants) */                            \
+        with_bools([&](auto XD_) {                                                                                                             \
+            hipLaunchKernelGGL((expand_both_drop_kernel<L_, C_, XD_()>), grid, block, 0, st, y.src_dc, dc, N, x.p, x.row, x.poly, y.p, y.row,  \
+                               y.poly, out, n_outer);                                                                                          \
+        }, xdrop);                                                                                                                             \
+        return true;                                                                                                                           \
     }
-    PIE_CHAIN_DROP_PAIRS(EBD_)
-#undef EBD_
-    return false;
-}
-bool launch_expand_both_drop_xy(const DevConsts *dc_parent, const DevConsts *dc_x, const DevConsts *dc_level, u32 N, u32 L, u32 Lx, u32 Lc,
-                                const u64 *x, size_t sx, size_t six, const u64 *y, size_t sy, size_t siy, u32 n_outer, u64 *out, hipStream_t st)
-{
-    if (Lx == L) return launch_expand_both_drop(dc_parent, dc_level, N, L, Lc, x, sx, six, true, y, sy, siy, n_outer, out, st);
-    if (!expand_both_drop_xy_applies(L, Lx, Lc)) return false;
-    dim3 grid((N / 2 + TPB - 1) / TPB, n_outer * 4);
-#define EBX_(L_, X_, C_)                                                                                                                  \
-    if (L == L_ && Lx == X_ && Lc == C_) {                                                                                               \
-        hipLaunchKernelGGL((expand_both_drop_xy_kernel<L_, X_, C_>), grid, dim3(TPB), 0, st, dc_parent, dc_x, dc_level, N, x, sx, six, y, sy, \
-                           siy, out, n_outer);                                                                                           \
-        return true;                                                                                                                     \
+#define TRIPLE_(L_, X_, C_)                                                                                                                    \
+    if (y.src_L == L_ && x.src_L == X_ && L == C_) {                                                                                           \
+        hipLaunchKernelGGL((expand_both_drop_xy_kernel<L_, X_, C_>), grid, block, 0, st, y.src_dc, x.src_dc, dc, N, x.p, x.row, x.poly, y.p,   \
+                           y.row, y.poly, out, n_outer);                                                                                       \
+        return true;                                                                                                                           \
     }
-    PIE_CHAIN_DROP_TRIPLES(EBX_)
-#undef EBX_
-    return false;
+        PIE_CHAIN_DROP_PAIRS(PAIR_)
+        PIE_CHAIN_DROP_TRIPLES(TRIPLE_)
+#undef TRIPLE_
+#undef PAIR_
+        return false;
+    }
+    if (xdrop || x.plain != y.plain) return false;
+    if (x.plain)   // (a level context has fewer limbs than MAX_L)
+        return !x.q_ready && with_u32<1, 6>(L, [&](auto L_) {
+            with_bools([&](auto F_, auto M_) {
+                hipLaunchKernelGGL((expand_both_plain_kernel<F_(), L_(), M_()>), grid, block, 0, st, dc, N, x.p, x.row, x.poly, y.p, y.row, y.poly, out,
+                                   n_outer);
+            }, fold, small_moduli);
+        });
+    return x.poly == y.poly && with_u32<1, 7>(L, [&](auto L_) {
+        with_bools([&](auto F_, auto M_, auto Q_) {
+            hipLaunchKernelGGL((expand_both_kernel<F_(), L_(), M_(), Q_()>), grid, block, 0, st, dc, N, x.p, x.row, y.p, y.row, y.poly, out, n_outer);
+        }, fold, small_moduli, x.q_ready);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -414,16 +414,9 @@ struct KeyswitchOpts {
     bool d01_eval_q = false;     // (enqueue_mul only, plan.d01_eval_q) w.d01 lacks the own-limb term; the MAC adds it from w.eqp
 };
 void enqueue_keyswitch(Sched &s, MulWs &w, u32 nb, RunKey key, const u64 *mask, u64 *out, KeyswitchOpts o = {});
-// in (chain limbs): how the operands of a product on a level context lie in memory and what their conversion has to do first
-struct MulIn {
-    size_t six = 0, siy = 0;            // words between the two polynomials of X / of Y (0: the context's L N)
-    const ChainCtx *drop_from = nullptr;  // fused limb drop: Y (and X, x_drop) have drop_from->L limbs, folded outer stage pending
-    bool x_drop = false;
-    const ChainCtx *x_from = nullptr;   // x_drop of a chain schedule: X is a product of this level, packed, its folded outer stage pending
-    bool plain = false;                 // the operands are plain coefficients (chain_drop_kernel, an unfolded inverse transform)
-};
-void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
-                 const u64 *mask, u64 *out, bool xq_ready = false, bool out_is_result = false, const MulIn *in = nullptr);
+// x, y: the operands as launch_expand_pair takes them (kernels.hpp), rows of [2] polynomials each
+void enqueue_mul(Sched &s, MulWs &w, const ExpandOperand &x, const ExpandOperand &y, u32 nb, bool relin, const u64 *mask, u64 *out,
+                 bool out_is_result = false);
 int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 *d_out);
 static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
 // piehip.cpp: run() workspace (and, with_db, database and masks) of a handle for b bin layers; the lane-ordered copy of its masks; the

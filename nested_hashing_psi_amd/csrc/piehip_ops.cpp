@@ -78,7 +78,11 @@ int piehip_eval_mult(piehip_handle h, const uint64_t *x, const uint64_t *y, uint
     ex.copy_M = h->hp.M;
     Sched s(h);
     ntt(s, dxy, nct * 4 * L, 0, L, true, false, true, xq ? &ex : nullptr);
-    enqueue_mul(s, w, dxy, 4 * LN, dxy + 2 * LN, 4 * LN, nct, relin != 0, nullptr, dout, xq);
+    ExpandOperand ox, oy;
+    ox.p = dxy, oy.p = dxy + 2 * LN;
+    ox.row = oy.row = 4 * LN, ox.poly = oy.poly = LN;
+    ox.q_ready = xq;
+    enqueue_mul(s, w, ox, oy, nct, relin != 0, nullptr, dout);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     ws_free(w);

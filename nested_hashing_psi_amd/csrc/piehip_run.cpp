@@ -63,31 +63,21 @@ static RunKey run_key(const Sched &s)
 
 // One batched EvalMult(ct,ct) (BatchedFHEHIPPIE.cpp:123): operands in COEFFICIENT format (produced by
 // ntt(.., inverse, sigma = false, fold = true): with folding on, their outermost inverse stage is applied here),
-// X polynomial (o,c) at x + o*sx + c*LN, Y likewise.  relin: out[nb][2][L][N] (times mask if given);
+// X and Y as launch_expand_pair takes them.  relin: out[nb][2][L][N] (times mask if given);
 // otherwise out[nb][3][L][N] holds the EVALUATION-format tensor result -- times mask if given (a run()'s degree-2 result, include/piehip.h
 // "Result relinearisation": the product is formed in w.t3; the mask is lane-ordered where plan.result_eval_q, in standard order otherwise).
-void enqueue_mul(Sched &s, MulWs &w, const u64 *x, size_t sx, const u64 *y, size_t sy, u32 nb, bool relin,
-                 const u64 *mask, u64 *out, bool xq_ready, bool out_is_result, const MulIn *in)
+void enqueue_mul(Sched &s, MulWs &w, const ExpandOperand &x, const ExpandOperand &y, u32 nb, bool relin, const u64 *mask, u64 *out,
+                 bool out_is_result)
 {
     const ChainCtx &cx = *s.cx;
     const u32 N = cx.N, L = cx.L, M = cx.M;
     const size_t LN = cx.LN();
     const double W = 8.0 * N;
     const NttPlan &pl = *cx.plan;
+    const bool xq_ready = x.q_ready;
     {
-        const size_t six = in && in->six ? in->six : LN, siy = in && in->siy ? in->siy : LN;
-        const u32 Lin = in && in->drop_from ? in->drop_from->L : L;
-        const ChainCtx *xf = in && in->x_drop ? (in->x_from ? in->x_from : in->drop_from) : nullptr;   // where a dropped X comes from
-        ProfScope ps(s, PIEHIP_K_EXPAND, W * nb * (2.0 * Lin + 2.0 * (in && in->drop_from ? (xf ? xf->L : L) : Lin) + 4.0 * M));
-        bool ok = true;
-        if (xf && xf != in->drop_from)   // chain schedule, fused: X is the product of a level between the parent's and this one
-            ok = launch_expand_both_drop_xy(in->drop_from->d_dc, xf->d_dc, cx.d_dc, N, Lin, xf->L, L, x, sx, six, y, sy, siy, nb, w.eqp, s.stream);
-        else if (in && in->drop_from)   // chain limbs, fused: the limb drop in the conversions' load phase
-            ok = launch_expand_both_drop(in->drop_from->d_dc, cx.d_dc, N, Lin, L, x, sx, six, in->x_drop, y, sy, siy, nb, w.eqp, s.stream);
-        else if (in && in->plain)  // chain limbs, fallback: operands the drop kernel / an unfolded inverse transform left
-            ok = launch_expand_both_plain(cx.d_dc, N, L, x, sx, six, y, sy, siy, nb, w.eqp, s.stream, pl.small_moduli, pl.fold);
-        else
-            launch_expand_both(cx.d_dc, N, L, x, sx, y, sy, LN, nb, w.eqp, s.stream, pl.small_moduli, pl.fold, xq_ready);
+        ProfScope ps(s, PIEHIP_K_EXPAND, W * nb * (2.0 * std::max(y.src_L, L) + 2.0 * std::max(x.src_L, L) + 4.0 * M));
+        const bool ok = launch_expand_pair(cx.d_dc, N, L, x, y, nb, w.eqp, s.stream, pl.small_moduli, pl.fold);
         assert(ok);
         (void)ok;
     }
@@ -341,9 +331,7 @@ static MulWs ws_rows(const MulWs &ws, const ChainCtx &wide, size_t r0, u32 nb)
 // What the products of a chain disagree on, one entry per product (the products behind the schedule's last entry share one)
 struct ChainStep {
     const ChainCtx *cx = nullptr;   // the level the product runs on: constants, plan and tables, the limb prefixes of keys and masks
-    MulIn in;                       // how X and Y lie in memory and what their conversion does first
-    size_t sx = 0;                  // words from one row's X to the next
-    bool xq_ready = false;          // the QP array holds X's Q limbs in EVALUATION form already
+    ExpandOperand x, y;             // how X and Y lie in memory and what their conversion does first: everything but the pointers
     bool x_drop_kernel = false;     // fallback: X is the product before, on more limbs; the drop kernel rewrites it in place first ...
     bool x_folded = false;          // ... reading through the folded outer stage its inverse transform left pending
     // the inverse transform of this product's result, where another product follows: on this product's context
@@ -397,7 +385,7 @@ static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
         const ChainCtx &c = lvl(hf);
         if (c.L == top.L) continue;
         fused = c.plan->fold && c.plan->small_moduli && c.plan->xq_reuse &&
-                (x_limbs(hf) > c.L ? expand_both_drop_xy_applies(top.L, x_limbs(hf), c.L) : expand_both_drop_applies(top.L, c.L));
+                expand_drop_built(top.L, x_limbs(hf), c.L);
     }
     const bool dropped = level && !fused;
     // X is needed twice by a product: in COEFFICIENT form by the base extension, and in EVALUATION form, lane-ordered, as the Q limbs of
@@ -412,18 +400,19 @@ static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
         const ChainCtx &c = lvl(hf);
         const bool at_top = c.L == top.L, x_drop = x_limbs(hf) > c.L;
         t.cx = &c;
-        t.in.six = (size_t)x_limbs(hf) * N;
-        t.in.siy = TLN;
-        t.sx = hf == 1 ? (size_t)K * 2 * TLN : 2 * t.in.six;
+        t.x.poly = (size_t)x_limbs(hf) * N;   // the first X is an accumulator like every Y, a later one the product before, packed
+        t.x.row = hf == 1 ? (size_t)K * 2 * TLN : 2 * t.x.poly;
+        t.y.poly = TLN;
+        t.y.row = (size_t)K * 2 * TLN;
         if (at_top) {
-            t.xq_ready = c.plan->xq_reuse;
+            t.x.q_ready = c.plan->xq_reuse;
         } else if (fused) {
-            t.in.drop_from = &top;
-            t.in.x_drop = x_drop;
-            t.in.x_from = x_drop && hf > 1 ? &lvl(hf - 1) : nullptr;
-            t.xq_ready = !x_drop;
+            const ChainCtx &xf = hf > 1 ? lvl(hf - 1) : top;   // where X comes from
+            t.y.src_dc = top.d_dc, t.y.src_L = top.L;
+            if (x_drop) t.x.src_dc = xf.d_dc, t.x.src_L = xf.L;
+            t.x.q_ready = !x_drop;
         } else {
-            t.in.plain = true;
+            t.x.plain = t.y.plain = true;
             t.x_drop_kernel = x_drop && hf > 1;   // (the first product's X is an accumulator: dropped with the others)
         }
         if (hf + 1 < K) {
@@ -433,7 +422,7 @@ static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
         }
         if (i) t.x_folded = t.x_drop_kernel && steps[i - 1].inv_fold && steps[i - 1].cx->plan->fold;
     }
-    const bool copy_first = steps[0].xq_ready;
+    const bool copy_first = steps[0].x.q_ready;
     NttExtra ex;
     ex.copy_out = w.eqp;
     ex.copy_K = K;
@@ -469,8 +458,9 @@ static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
             launch_chain_drop(from.d_dc, N, from.L, c.L, prod, nb * 2, s.stream, t.x_folded);
         }
         s.cx = &c;
-        enqueue_mul(s, w, x, t.sx, acc + (size_t)hf * 2 * TLN, (size_t)K * 2 * TLN, nb, !(last && deg2), last ? masks : nullptr, last ? out : prod,
-                    t.xq_ready, last, &t.in);
+        ExpandOperand xo = t.x, yo = t.y;
+        xo.p = x, yo.p = acc + (size_t)hf * 2 * TLN;
+        enqueue_mul(s, w, xo, yo, nb, !(last && deg2), last ? masks : nullptr, last ? out : prod, last);
         if (!last) {
             ex.copy_L = c.L;
             ex.copy_M = c.M;

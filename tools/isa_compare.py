@@ -1,16 +1,29 @@
-"""per-kernel comparison of two hipcc -S listings of one file (before and after a change): python tools/isa_compare.py before.s after.s
-Kernels that only the second listing has are listed with their figures; one that only the first has is an error.  A kernel counts as identical when its instructions, its kernel descriptor and its metadata entry are (the compilation-unit id,
-__hip_cuid_<hash>, neutralised); for the others: tools/isa_regs.py's columns, waves per SIMD, instruction totals and the counts of the
-memory and multiplier instructions, each as before->after where it changed."""
+"""per-kernel comparison of two hipcc -S listings of one file (before and after a change):
+    python tools/isa_compare.py [--removed FILE] [--neutral-ordinals] before.s after.s
+Kernels that only the second listing has are listed with their figures; one that only the first has is an error.  A kernel counts as
+identical when its instructions, its kernel descriptor and its metadata entry are (the compilation-unit id, __hip_cuid_<hash>,
+neutralised); for the others: tools/isa_regs.py's columns, waves per SIMD, instruction totals and the counts of the memory and
+multiplier instructions, each as before->after where it changed.
+--removed FILE: the kernels the change removes on purpose, one per line, as this tool prints them (e.g. expand_kernel<true, true, 3u,
+false, false>) or mangled.  They may be missing from the second listing and are listed by name; any OTHER kernel missing there, and a
+named one that is still there, stays an error.
+--neutral-ordinals: the compiler numbers the functions of a listing and puts that ordinal into local labels (.LBB<f>_<n>, and BB<f>_<n>
+inside comments), so taking out or reordering one kernel renames the labels of every kernel behind it.  With this option the ordinal
+is replaced by a fixed letter in both listings before anything is compared, and the padding between a label and the comment behind it
+(which depends on the label's length) by one blank; the label's own number <n> stays."""
+import argparse
 import collections
 import re
 import subprocess
 import sys
 
 
-def kernels(path):
+def kernels(path, neutral_ordinals):
     txt = open(path).read()
     txt = re.sub(r'__hip_cuid_[0-9a-f]+', '__hip_cuid_X', txt)
+    if neutral_ordinals:
+        txt = re.sub(r'\bL?BB\d+_(\d+)', r'BBf_\1', txt)
+        txt = re.sub(r'^(\.BBf_\d+:)[ \t]+', r'\1 ', txt, flags=re.M)   # (the comment behind a label starts at a fixed column)
     out = collections.OrderedDict()
     for m in re.finditer(r'^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end', txt, re.S | re.M):
         out[m.group(1)] = {'body': m.group(2)}
@@ -51,11 +64,31 @@ def waves(v):
     return min(8, 512 // ((v + 7) // 8 * 8))
 
 
-pa, pt = kernels(sys.argv[1])
-he, ht = kernels(sys.argv[2])
+ap = argparse.ArgumentParser()
+ap.add_argument("--removed", default=None)
+ap.add_argument("--neutral-ordinals", action="store_true")
+ap.add_argument("before")
+ap.add_argument("after")
+args = ap.parse_args()
+pa, pt = kernels(args.before, args.neutral_ordinals)
+he, ht = kernels(args.after, args.neutral_ordinals)
+removed = set(ln.strip() for ln in open(args.removed) if ln.strip()) if args.removed else set()
 gone = [k for k in pa if k not in he]
 new = [k for k in he if k not in pa]
-assert not gone, "kernels of the first listing missing from the second: %s" % gone
+named = [k for k in pa if k in removed or short(k) in removed]
+unexpected = [short(k) for k in gone if k not in named]
+assert not unexpected, "kernels of the first listing missing from the second: %s" % unexpected
+assert not [k for k in named if k in he], "kernels named as removed that the second listing still has: %s" % [short(k) for k in named if k in he]
+assert len(named) == len(removed), "names in --removed that the first listing does not have"
+if gone:
+    print("%d kernels removed on purpose (--removed), missing from the second listing:" % len(gone))
+    for k in gone:
+        print("  " + short(k))
+    print()
+    for k in gone:
+        del pa[k]
+if args.neutral_ordinals:
+    print("(function ordinals in local labels neutralised)")
 same = [k for k in pa if pa[k] == he[k]]
 diff = [k for k in pa if pa[k] != he[k]]
 print("%d kernels, %d with identical listing (instructions, kernel descriptor, metadata), %d differ" % (len(pa), len(same), len(diff)))
