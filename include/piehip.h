@@ -240,7 +240,8 @@ int piehip_attach_database(piehip_handle h, piehip_handle owner);
  *   results                  piehip_run / piehip_run_into / piehip_get_results then use rows [b][nq][2][L][N]: the nq result
  *                            ciphertexts of a bin layer are adjacent
  *   piehip_load_relin_key_q  the EvalMult key of query q's client (BatchedFHEPSIServer.cpp:45-49: every client sends its own);
- *                            queries without one use the handle's key.  Sized by the batch: load again after piehip_set_query_batch
+ *                            queries without one use the handle's key.  Sized by the batch: load again after piehip_set_query_batch.
+ *                            A handle without a batch has query 0 only: its key, once loaded, is the one run() relinearises with
  * The host-memory path takes batches too: piehip_host_buffers_q / piehip_stage_*_q / piehip_run_staged / piehip_run_host* below.
  * Only the captured graph (piehip_set_graph) is limited to one query per run(). */
 int piehip_set_query_batch(piehip_handle h, uint32_t nq);

@@ -966,6 +966,10 @@ int piehip_load_relin_key_q(piehip_handle h, uint32_t q, const uint64_t *evk)
     const size_t words = c.key_words(), rows = c.L * 2 * c.L;   // of one key
     int rc;
     if (!c.evkq || h->evkq_n != h->nq) {
+        // a captured run() names the key array it was captured with: the handle's key where there was no per-query array yet
+        // (a handle without a batch reads query 0's own key from here on), the array freed below otherwise
+        HIPCHK(hipStreamSynchronize(h->stream));
+        drop_graph(h);
         dev_free(&c.evkq);
         dev_free(&c.evkq_sigma);
         h->evkq_n = h->evkq_loaded = 0;

@@ -317,6 +317,7 @@ struct Sched {
                                    // left; the next queue group starts behind it (null: nobody waits)
     u32 mask_div = 1;   // a batch: ciphertext row r of the product chain takes mask r / mask_div
     u32 key_group = 1;  // ... and, with per-query EvalMult keys, key r % key_group of cx->evkq
+    bool key_per_query = false;  // the keys are cx->evkq's (a batch of one included: key_group 1 of that array)
     const ChainCtx *cx; // the context the pieces work on: the handle's own unless run() hands them its level context (chain limbs)
     Sched(piehip_ctx *h_) : h(h_), stream(h_->stream), cx(&h_->cx) {}
     Sched(piehip_ctx *h_, hipStream_t s) : h(h_), stream(s), cx(&h_->cx) {}

@@ -57,7 +57,7 @@ static RunKey run_key(const Sched &s)
 {
     const ChainCtx &cx = *s.cx;
     const bool lane = cx.plan->lane_order;
-    if (s.key_group > 1) return {lane ? cx.evkq_sigma : cx.evkq, cx.key_words(), s.key_group};
+    if (s.key_per_query) return {lane ? cx.evkq_sigma : cx.evkq, cx.key_words(), s.key_group};
     return {lane ? cx.evk_sigma : cx.evk};
 }
 
@@ -363,7 +363,10 @@ static void enqueue_chain_bins(Sched &s, u32 b0, u32 layers, u64 *results)
     u64 *out = results + r0 * h->res_comps() * LN;
     const u64 *masks = ((deg2 ? pl.result_eval_q : pl.lane_order) ? cx.masks_sigma : cx.masks) + (size_t)b0 * LN;
     s.mask_div = nq;
-    s.key_group = (nq > 1 && h->cx.evkq && h->evkq_n == nq) ? nq : 1;  // per-query EvalMult keys: row r of a group is query r % nq
+    // per-query EvalMult keys: row r of a group is query r % nq.  A handle without a batch has query 0 only, and that query's key, once
+    // loaded (piehip_load_relin_key_q(h, 0, ..)), is the one it relinearises with: run_keys_loaded accepts it in place of the handle's
+    s.key_per_query = h->cx.evkq && h->evkq_n == nq;
+    s.key_group = s.key_per_query ? nq : 1;
     if (K == 1) {
         // one inner hash function: multipliedResult is the inner product itself (BatchedFHEHIPPIE.cpp:117-120), so run() is
         // stage A and the mask multiply (:126) -- no ciphertext product, no transform, no key
