@@ -506,6 +506,35 @@ int piehip_get_chain_limbs(piehip_handle h, uint32_t *Lc);
 int piehip_set_chain_schedule(piehip_handle h, const uint32_t *Lc /*[n]*/, uint32_t n);
 int piehip_get_chain_schedule(piehip_handle h, uint32_t *Lc /*[cap]*/, uint32_t cap, uint32_t *n);
 
+/* ---- layer tiling: several bin layers in one ciphertext's slots --------------------------------------------
+ * run() time, database bytes, result bytes and the client's decryption work are linear in the bin-layer count b, and a packed plaintext
+ * uses B = k e of the ring's N slots.  run() is slot-wise from the first multiply to the mask, so when B <= N / 2, R = floor(N / B) bin
+ * layers fit side by side in one plaintext: the client repeats its B query slots R times, one "tiled layer" evaluates R bin layers, and
+ * b becomes b' = ceil(b / R) everywhere.  With slot s = i e + p as ever and R >= 1, R B <= N, the tiled database is a re-arrangement of
+ * what the loaders gather, after the same shuffle and with the same mask draw:
+ *   database slots   slots'[h][g][j][r B + s] = slots[h][g R + r][j][s] for g R + r < b, else 0; slots at R B and above are 0
+ *   mask slots       mask'[g][r B + s] = mask(layer g R + r, slot s) by the rule of the untiled draw; the layer index runs on past b
+ *                    in the last tiled layer (the draw of b' R layers on B slots, read as [b'][R B])
+ *   client vectors   the client tiles every plaintext vector: index'[h][j][r B + s] = index[h][j][s], and the minus vector likewise
+ *   results          row g, slot r B + s, is bin layer g R + r, slot s; blocks with g R + r >= b are to be ignored.  They are never
+ *                    zero: the accumulator there is -x != 0 in an occupied slot and +1 in a dummy slot, times a mask in [1, t - 1],
+ *                    and t is prime
+ * The handle then holds an ordinary database of b' layers on R B slots: run() and everything behind it are untouched.
+ *   piehip_set_layer_tiling   per handle, R >= 1, default 1 (no launch, buffer, byte or refusal differs).  Read by the NEXT
+ *                             piehip_build_db(_bins), piehip_load_db_table(_bins) and piehip_reserve: they size and build for b' layers,
+ *                             and bin_lo / bin_hi count tiled layers.  piehip_get_hash_table still returns the untiled [k][e][K][b][E].
+ *                             piehip_load_db and piehip_load_db_slots ignore the setting (their callers tile by hand), and a handle
+ *                             attached to another's database takes what that database is.
+ *   piehip_get_layer_tiling   the setting
+ *   piehip_layer_tiling       host only, no handle: the balanced choice for a shape.  Rmax = floor(N / (k e));
+ *                             b_tiled = ceil(b / min(Rmax, b)); R = ceil(b / b_tiled): the fewest tiled layers, filled evenly.
+ * PIEHIP_EINVAL: R = 0; from the build, load or reserve when R k e > N (the handle keeps its previous database and stays usable);
+ * piehip_layer_tiling when k e > N.  PIEHIP_ESTATE: piehip_load_db_table_sliced and piehip_build_db_sliced while R > 1 (query slices
+ * of a tiled database are not built).  Added without a new version number: look the symbols up. */
+int piehip_set_layer_tiling(piehip_handle h, uint32_t R);
+int piehip_get_layer_tiling(piehip_handle h, uint32_t *R);
+int piehip_layer_tiling(uint32_t N, uint32_t k, uint32_t e, uint32_t b, uint32_t *R, uint32_t *b_tiled);   /* host only, no handle */
+
 /* ---- query slices: stage A sharded by inner hash function and limb --------------------------------------
  * The reference evaluates, per bin layer, K inner products over E index ciphertexts (BatchedFHEHIPPIE.cpp:96-116) and then multiplies
  * the K accumulators together (.cpp:117-126).  Every RNS limb of an inner product depends on that limb of its operands only, so the

@@ -127,6 +127,9 @@ SYMBOLS = {
     "piehip_get_chain_limbs": (C.c_int, [C.c_void_p, u32p]),
     "piehip_set_chain_schedule": (C.c_int, [C.c_void_p, u32p, C.c_uint32]),
     "piehip_get_chain_schedule": (C.c_int, [C.c_void_p, u32p, C.c_uint32, u32p]),
+    "piehip_set_layer_tiling": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "piehip_get_layer_tiling": (C.c_int, [C.c_void_p, u32p]),
+    "piehip_layer_tiling": (C.c_int, [C.c_uint32] * 4 + [u32p, u32p]),
     "piehip_set_result_relin": (C.c_int, [C.c_void_p, C.c_int]),
     "piehip_get_result_relin": (C.c_int, [C.c_void_p, i32p]),
     "piehip_get_result_components": (C.c_int, [C.c_void_p, u32p]),

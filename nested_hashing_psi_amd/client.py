@@ -51,15 +51,22 @@ def select_parameters(bitSize, eachCuckooTableSize):
 
 class BatchedFHEPSIClient:
     """Mirror of BatchedFHEPSIClient (BatchedFHEPSIClient.cpp:14-193): runSetUpPhase, runOfflinePhase,
-    the online-phase result extraction.  No TCP: the caller moves the arrays."""
+    the online-phase result extraction.  No TCP: the caller moves the arrays.
+
+    layerTiling=R: the client of a server whose database packs R bin layers per plaintext (include/piehip.h "Layer tiling").  Every
+    query vector is its k*e slots repeated R times; the server answers with ceil(b / R) ciphertexts whose block r of k*e slots is
+    bin layer g*R + r, and the blocks behind the last bin layer are ignored."""
 
     def __init__(self, cryptoContext, numberOfSimpleHashFunctions, eachSimpleTableSize, numberOfCuckooHashFunctions,
-                 eachCuckooTableSize, maxItemsPerPosition, hashSeed=987654321):
+                 eachCuckooTableSize, maxItemsPerPosition, hashSeed=987654321, layerTiling=1):
         self.cc = cryptoContext
         self.k, self.e = numberOfSimpleHashFunctions, eachSimpleTableSize
         self.K, self.E, self.b = numberOfCuckooHashFunctions, eachCuckooTableSize, maxItemsPerPosition
         self.hashSeed = hashSeed
         self.B = self.k * self.e
+        self.R = int(layerTiling)
+        if self.R < 1 or self.R * self.B > self.cc.N:
+            raise ValueError("layerTiling: between 1 and N // (k*e) bin layers per ciphertext")
 
     # -- setup (BatchedFHEPSIClient.cpp:88-91): KeyGen + EvalMultKeyGen
     def runSetUpPhase(self, keySeed=11, evalKeySeed=12):
@@ -109,19 +116,8 @@ class BatchedFHEPSIClient:
 
     # -- offline (BatchedFHEPSIClient.cpp:107-169): index matrix + minus vector, secret-key encrypted
     def runOfflinePhase(self, clientSet, encSeedBase=100):
-        self.clientTable = self._hash_client_set(clientSet)
-        k, e, K, E, B = self.k, self.e, self.K, self.E, self.B
-        flat = self.clientTable.reshape(-1)
-        index = np.zeros((K, E, B), dtype=np.int64)
-        minus = np.ones(B, dtype=np.int64)                         # dummy slot: +1, all-zero index column (:128-131)
-        occ = np.nonzero(flat)[0]
-        if len(occ):
-            minus[occ] = -flat[occ].astype(np.int64)
-            for hf in range(K):
-                hi = tabulation_hash(self.hashSeed, k + K, k + hf, flat[occ]) % np.uint64(E)
-                index[hf, hi.astype(np.int64), occ] = 1
-        self.plainIndex, self.plainMinus = index, minus
-        vecs = np.concatenate([minus.reshape(1, B), index.reshape(K * E, B)])
+        K, E = self.K, self.E
+        vecs = self._query_vectors(clientSet)
         seeds = np.array([encSeedBase - 1] + [encSeedBase + i for i in range(K * E)], dtype=np.uint64)
         cts = self._encrypt(vecs, seeds)
         self.encryptedMinusElements = cts[0]
@@ -129,6 +125,8 @@ class BatchedFHEPSIClient:
         return self.encryptedMinusElements, self.batchedEncryptedIndexMatrix
 
     def _query_vectors(self, clientSet):
+        """the plaintext vectors of one query, [1 + K*E][R*B]: the minus vector (dummy slot: +1, all-zero index column, :128-131),
+        then the index matrix; each is its B slots repeated R times.  plainIndex / plainMinus keep the B slots"""
         self.clientTable = self._hash_client_set(clientSet)
         k, e, K, E, B = self.k, self.e, self.K, self.E, self.B
         flat = self.clientTable.reshape(-1)
@@ -141,7 +139,7 @@ class BatchedFHEPSIClient:
                 hi = tabulation_hash(self.hashSeed, k + K, k + hf, flat[occ]) % np.uint64(E)
                 index[hf, hi.astype(np.int64), occ] = 1
         self.plainIndex, self.plainMinus = index, minus
-        return np.concatenate([minus.reshape(1, B), index.reshape(K * E, B)])
+        return np.tile(np.concatenate([minus.reshape(1, B), index.reshape(K * E, B)]), (1, self.R))
 
     # -- the offline phase with seeded ciphertexts: c0 halves + one 32-byte seed per ciphertext; the server expands the c1 halves.
     #    Returns (minus c0 [L][N], minus seed [32], index c0 [K][E][L][N], index seeds [K][E][32]).  encSeedBase draws the noise as in
@@ -199,7 +197,7 @@ class BatchedFHEPSIClient:
         (piehip_client_decrypt_budget: measured on these ciphertexts under this key, not a bound)."""
         a, ap, h, sk = self._decrypt_operands(cts, limbs)
         n = a.shape[0]
-        nslots = nslots or self.B
+        nslots = nslots or self.R * self.B
         out = _out((n, nslots), np.int64)
         if budget:
             bud = _out((n,), np.int32)
@@ -221,7 +219,10 @@ class BatchedFHEPSIClient:
 
     # -- online (BatchedFHEPSIClient.cpp:176-192): zero slot in any of the b results <=> item in the intersection
     def extractIntersection(self, resultList, limbs=None):
-        self.batchedDecryptedResult = self.decrypt(resultList, limbs=limbs)
+        dec = self.decrypt(resultList, limbs=limbs)
+        if self.R > 1:   # row g, block r is bin layer g*R + r; the blocks behind layer b - 1 are not bin layers
+            dec = dec.reshape(dec.shape[0] * self.R, self.B)[:self.b]
+        self.batchedDecryptedResult = dec
         flat = self.clientTable.reshape(-1)
         hit = (self.batchedDecryptedResult == 0).any(axis=0)
         return flat[hit].copy()

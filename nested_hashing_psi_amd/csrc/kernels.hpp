@@ -316,6 +316,8 @@ hipError_t launch_hash_build(const u64 *d_tab, const u64 *d_items, u32 n, u32 k,
                              u32 *d_fail, hipStream_t st);
 void launch_shuffle_rows(u64 *d_tbl, u32 rows, u32 b, u32 E, u64 seed, hipStream_t st);
 void launch_gather_slots(const u64 *d_tbl, u32 B, u32 K, u32 b, u32 E, u64 t, int64_t *d_slots, u32 *d_fail, hipStream_t st);
+// R bin layers per slot vector: d_slots[K][ceil(b / R)][E][R B], zero behind the last layer (include/piehip.h "Layer tiling")
+void launch_gather_slots_tiled(const u64 *d_tbl, u32 B, u32 R, u32 K, u32 b, u32 E, u64 t, int64_t *d_slots, u32 *d_fail, hipStream_t st);
 void launch_mask_slots(u64 t, u32 b, u32 B, u64 seed, int64_t *d_out, hipStream_t st);
 
 // ---- client harness (kernels_client.hip) ----------------------------------------------------------------------------

@@ -287,6 +287,26 @@ __global__ void __launch_bounds__(HTPB) gather_slots_kernel(const u64 *__restric
     slots[(size_t)pt * B + s] = v > t / 2 ? (int64_t)v - (int64_t)t : (int64_t)v;
 }
 
+// Layer tiling (include/piehip.h "Layer tiling"): R bin layers side by side in one slot vector of R B slots,
+// slots[h][g][j][r B + s] = tbl[s][h][g R + r][j] for g R + r < b and 0 in the blocks behind the last layer; bt = ceil(b / R) tiled
+// layers.  One thread per tiled slot, so a wave writes 64 adjacent words as gather_slots_kernel does; flags items >= t as it does.
+__global__ void __launch_bounds__(HTPB) gather_slots_tiled_kernel(const u64 *__restrict__ tbl, u32 B, u32 R, u32 K, u32 b, u32 bt, u32 E,
+                                                                  u64 t, int64_t *__restrict__ slots, u32 *__restrict__ fail)
+{
+    const u32 x = blockIdx.x * HTPB + threadIdx.x;  // r * B + s
+    if (x >= R * B) return;
+    const u32 pt = blockIdx.y;  // (h * bt + g) * E + j
+    const u32 j = pt % E, g = pt / E % bt, hf = pt / E / bt;
+    const u32 r = x / B, s = x - r * B, bin = g * R + r;
+    int64_t out = 0;
+    if (bin < b) {
+        const u64 v = tbl[(size_t)s * K * b * E + ((size_t)hf * b + bin) * E + j];
+        if (v >= t) atomicOr(fail, 2u);
+        out = v > t / 2 ? (int64_t)v - (int64_t)t : (int64_t)v;
+    }
+    slots[(size_t)pt * R * B + x] = out;
+}
+
 __device__ __forceinline__ u64 mix64(u64 z)
 {
     z += 0x9E3779B97F4A7C15ULL;
@@ -355,6 +375,14 @@ void launch_gather_slots(const u64 *d_tbl, u32 B, u32 K, u32 b, u32 E, u64 t, in
     dim3 grid((B + HTPB - 1) / HTPB, K * b * E);
     hipLaunchKernelGGL(gather_slots_kernel, grid, dim3(HTPB), 0, st, d_tbl, B, K, b, E, t, d_slots, d_fail);
 }
+void launch_gather_slots_tiled(const u64 *d_tbl, u32 B, u32 R, u32 K, u32 b, u32 E, u64 t, int64_t *d_slots, u32 *d_fail, hipStream_t st)
+{
+    const u32 bt = (b + R - 1) / R;
+    dim3 grid((R * B + HTPB - 1) / HTPB, K * bt * E);
+    hipLaunchKernelGGL(gather_slots_tiled_kernel, grid, dim3(HTPB), 0, st, d_tbl, B, R, K, b, bt, E, t, d_slots, d_fail);
+}
+// (the tiled mask draw is this launch with b' R layers: mask'[g][r B + s] = mask(layer g R + r, slot s) is the same word of the same
+// array, [b' R][B] read as [b'][R B])
 void launch_mask_slots(u64 t, u32 b, u32 B, u64 seed, int64_t *d_out, hipStream_t st)
 {
     dim3 grid((B + HTPB - 1) / HTPB, b);

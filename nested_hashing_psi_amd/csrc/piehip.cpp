@@ -582,6 +582,22 @@ int piehip_attach_database(piehip_handle h, piehip_handle owner)
     return level_sync(h);   // a slot has its own chain-limbs setting, and its own copies of the owner's key and masks for it
 }
 
+// Layer tiling: R bin layers side by side in one slot vector leave b' = ceil(b / R) tiled layers.  The encoder's input is
+// [max(K b E, b)][B] words -- the database's slot vectors, then the masks' in the same scratch -- for the b and B it encodes:
+// b' and R k e with a tiling
+static u32 tiled_layers(u32 b, u32 R) { return (u32)(((u64)b + R - 1) / R); }
+static size_t slot_scratch_words(u32 K, u32 b, u32 E, size_t B)
+{
+    const size_t npt = (size_t)K * b * E;
+    return (npt > b ? npt : b) * B;
+}
+// what every loader that reads the setting refuses: more tiled slots than the ring has
+static int tiling_check(const piehip_ctx *h, u32 k, u32 e)
+{
+    if ((size_t)h->tiling * k * e > h->hp.N) return fail(PIEHIP_EINVAL, "layer tiling: R*k*e exceeds the ring dimension");
+    return PIEHIP_OK;
+}
+
 // the persistent hash-table buffer [k][e][K][b][E]: reallocated only when the size changes
 extern "C++" int piehip::hash_tbl_alloc(piehip_ctx *h, size_t words)
 {
@@ -596,21 +612,22 @@ extern "C++" int piehip::hash_tbl_alloc(piehip_ctx *h, size_t words)
 
 // A table built elsewhere, tbl[k][e][K][b][E] in host memory, as far as the encoder: into the handle's table buffer, its rows shuffled
 // whole (every handle given the same seed holds one and the same database), its slot vectors gathered into *d_slots
-// [max(K b E, b)][k e], carved from the caller's scratch
-extern "C++" int piehip::table_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *tbl, u32 k, u32 e, u32 K, u32 b, u32 E, u64 shuffle_seed, int64_t **d_slots)
+// [max(K b E, b)][k e], carved from the caller's scratch (R > 1: the tiled vectors, [max(K b' E, b')][R k e])
+extern "C++" int piehip::table_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *tbl, u32 k, u32 e, u32 K, u32 b, u32 E, u64 shuffle_seed, int64_t **d_slots, u32 R)
 {
     const size_t B = (size_t)k * e, npt = (size_t)K * b * E, tbl_words = B * npt;
     const int rc = hash_tbl_alloc(h, tbl_words);
     if (rc) return rc;
     h->hk = k, h->he = e, h->hb = b;
-    TMPGET(d_slotsw, (npt > b ? npt : b) * B);
+    TMPGET(d_slotsw, slot_scratch_words(K, tiled_layers(b, R), E, R * B));
     TMPGET(d_failw, 1);
     *d_slots = (int64_t *)d_slotsw;
     u32 *d_fail = (u32 *)d_failw;
     HIPCHK(hipMemcpyAsync(h->d_hash_tbl, tbl, tbl_words * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(d_fail, 0, sizeof(u32), h->stream));
     launch_shuffle_rows(h->d_hash_tbl, (u32)(B * K), b, E, shuffle_seed, h->stream);
-    launch_gather_slots(h->d_hash_tbl, (u32)B, K, b, E, h->hp.t, *d_slots, d_fail, h->stream);
+    if (R > 1) launch_gather_slots_tiled(h->d_hash_tbl, (u32)B, R, K, b, E, h->hp.t, *d_slots, d_fail, h->stream);
+    else launch_gather_slots(h->d_hash_tbl, (u32)B, K, b, E, h->hp.t, *d_slots, d_fail, h->stream);
     HIPCHK(hipGetLastError());  // (as in piehip_build_db_bins)
     u32 failed = 0;
     HIPCHK(hipMemcpyAsync(&failed, d_fail, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
@@ -620,12 +637,12 @@ extern "C++" int piehip::table_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *tbl,
 }
 
 // scratch words piehip_build_db_bins carves (256-byte granules), including the encoder's
-static size_t build_db_scratch_words(const piehip_ctx *h, size_t n, u32 k, u32 e, u32 K, u32 b, u32 E)
+static size_t build_db_scratch_words(const piehip_ctx *h, size_t n, u32 k, u32 e, u32 K, u32 b, u32 E, u32 R)
 {
     auto g = [](size_t w) { return ((w ? w : 1) + 31) & ~(size_t)31; };
-    const size_t B = (size_t)k * e, npt = (size_t)K * b * E;
+    const size_t B = (size_t)k * e;
     return g((size_t)(k + K) * 16 * 256) + g(n) + 2 * g(n + 1) + g((e + 2) / 2 + 1) + g(1) + g(hash_sort_temp_bytes((u32)n, e) / 8 + 1) +
-           g((npt > b ? npt : b) * B) + g((size_t)ENCODE_CHUNK * h->hp.N);
+           g(slot_scratch_words(K, tiled_layers(b, R), E, R * B)) + g((size_t)ENCODE_CHUNK * h->hp.N);
 }
 
 int piehip_load_db_slots(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, uint32_t B, const int64_t *slots,
@@ -653,14 +670,16 @@ int piehip_load_db_slots(piehip_handle h, uint32_t K, uint32_t b, uint32_t E, ui
 // Last step of the constructor (BatchedFHEHIPPIE.cpp:45-82) for the bin layers [lo, hi) this handle keeps: MakePackedPlaintext
 // of the gathered slot vectors d_slots[K][b][E][B] into the database [K][hi - lo][E], then the masks of those layers (drawn per
 // layer from mask_seed, so every shard of a sharded server holds the masks the unsharded one would).  Overwrites d_slots.
-static int encode_bin_layers(piehip_ctx *h, int64_t *d_slots, u32 K, u32 b, u32 E, u32 B, u32 lo, u32 hi, u64 mask_seed)
+// With a layer tiling R > 1, b counts tiled layers and B = R k e: tiled layer g's mask is the masks of layers g R .. g R + R - 1 one
+// after the other -- the draw of b R layers on k e slots, read as [b][R k e] (the layer index runs on past the last bin layer).
+static int encode_bin_layers(piehip_ctx *h, int64_t *d_slots, u32 K, u32 b, u32 E, u32 B, u32 lo, u32 hi, u64 mask_seed, u32 R = 1)
 {
     const u32 nb = hi - lo;
     const size_t LN = h->LN();
     int rc;
     for (u32 hf = 0; hf < K; hf++)
         if ((rc = encode_on_device(h, d_slots + ((size_t)hf * b + lo) * E * B, nb * E, B, h->d_db + (size_t)hf * nb * E * LN))) return rc;
-    launch_mask_slots(h->hp.t, b, B, mask_seed, d_slots, h->stream);
+    launch_mask_slots(h->hp.t, b * R, B / R, mask_seed, d_slots, h->stream);
     if ((rc = encode_on_device(h, d_slots + (size_t)lo * B, nb, B, h->cx.masks))) return rc;
     return make_masks_sigma(h);
 }
@@ -736,13 +755,14 @@ int piehip_client_cuckoo_table(uint64_t hash_seed, uint32_t nfun, uint32_t k, ui
 int piehip_reserve(piehip_handle h, size_t n, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E, uint32_t bin_lo, uint32_t bin_hi)
 {
     NEED(h);
-    if (k < 1 || e < 1 || bin_lo >= bin_hi || bin_hi > b || !n || n > 0x7FFFFFFFu) return fail(PIEHIP_EINVAL, "bad shape");
+    if (k < 1 || e < 1 || bin_lo >= bin_hi || bin_hi > tiled_layers(b, h->tiling) || !n || n > 0x7FFFFFFFu) return fail(PIEHIP_EINVAL, "bad shape");
     if (K < 2) return fail(PIEHIP_EINVAL, "Cuckoo Table needs more than one hash function!");  // CuckooHashTable.cpp:39-42
+    if (h->tiling > 1 && tiling_check(h, k, e)) return PIEHIP_EINVAL;
     HIPCHK(hipSetDevice(h->device));
     int rc = alloc_run_buffers(h, K, bin_hi - bin_lo, E);
     if (rc) return rc;
     if ((rc = hash_tbl_alloc(h, (size_t)k * e * K * b * E))) return rc;
-    const size_t need = build_db_scratch_words(h, n, k, e, K, b, E);
+    const size_t need = build_db_scratch_words(h, n, k, e, K, b, E, h->tiling);
     if (h->arena_words < need) {
         if (h->arena_used) return fail(PIEHIP_ESTATE, "scratch in use");
         dev_free(&h->arena);
@@ -757,9 +777,9 @@ int piehip_reserve(piehip_handle h, size_t n, uint32_t k, uint32_t e, uint32_t K
 
 // The offline phase as far as the encoder (BatchedFHEHIPPIE.cpp:45-66): the server set hashed into the handle's table buffer
 // [k][e][K][b][E] on the device, its rows shuffled, its slot vectors gathered into *d_slots [max(K b E, b)][k e], carved from the
-// caller's scratch (piehip_build_db_bins, piehip_build_db_sliced)
+// caller's scratch (piehip_build_db_bins, piehip_build_db_sliced); R > 1: the tiled vectors, [max(K b' E, b')][R k e]
 extern "C++" int piehip::items_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *items, size_t n, u32 k, u32 e, u32 K, u32 b, u32 E, u64 hash_seed,
-                                        u64 evict_seed, u64 shuffle_seed, int64_t **d_slots_out)
+                                        u64 evict_seed, u64 shuffle_seed, int64_t **d_slots_out, u32 R)
 {
     const size_t B = (size_t)k * e;
     const size_t tbl_words = B * K * b * E;
@@ -778,8 +798,7 @@ extern "C++" int piehip::items_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *item
     TMPGET(d_failw, 1);
     const size_t temp_bytes = hash_sort_temp_bytes((u32)n, e);
     TMPGET(d_temp, temp_bytes / 8 + 1);
-    const size_t npt = (size_t)K * b * E;
-    TMPGET(d_slotsw, (npt > b ? npt : b) * B);
+    TMPGET(d_slotsw, slot_scratch_words(K, tiled_layers(b, R), E, R * B));
     int64_t *d_slots = (int64_t *)d_slotsw;
     u32 *d_fail = (u32 *)d_failw;
     HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
@@ -790,7 +809,8 @@ extern "C++" int piehip::items_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *item
         ProfScope ps(h, PIEHIP_K_OTHER, 8.0 * (double)n * k * 4);
         HIPCHK(launch_hash_build(d_tab, d_items, (u32)n, k, e, K, b, E, evict_seed, shuffle_seed, h->d_hash_tbl, (u32 *)d_keys,
                                  (u32 *)d_vals, (u32 *)d_start, d_temp, temp_bytes, d_fail, h->stream));
-        launch_gather_slots(h->d_hash_tbl, (u32)B, K, b, E, h->hp.t, d_slots, d_fail, h->stream);
+        if (R > 1) launch_gather_slots_tiled(h->d_hash_tbl, (u32)B, R, K, b, E, h->hp.t, d_slots, d_fail, h->stream);
+        else launch_gather_slots(h->d_hash_tbl, (u32)B, K, b, E, h->hp.t, d_slots, d_fail, h->stream);
         HIPCHK(hipGetLastError());  // a launch that failed would leave d_slots uninitialised for the encoder
     }
     u32 failed = 0;
@@ -810,22 +830,24 @@ int piehip_build_db_bins(piehip_handle h, const uint64_t *items, size_t n, uint3
     if (!items || !n || n > 0x7FFFFFFFu) return fail(PIEHIP_EINVAL, "empty or oversized server set");
     if (k < 1 || e < 1) return fail(PIEHIP_EINVAL, "need at least one outer hash function and position");
     if (K < 2) return fail(PIEHIP_EINVAL, "Cuckoo Table needs more than one hash function!");  // CuckooHashTable.cpp:39-42
-    if (bin_lo >= bin_hi || bin_hi > b) return fail(PIEHIP_EINVAL, "bin-layer slice must be non-empty and within [0, b)");
+    const u32 R = h->tiling;  // bin_lo, bin_hi count tiled layers
+    if (bin_lo >= bin_hi || bin_hi > tiled_layers(b, R)) return fail(PIEHIP_EINVAL, "bin-layer slice must be non-empty and within [0, b)");
     const size_t B = (size_t)k * e;
     if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size k*e exceeds the ring dimension");
+    if (tiling_check(h, k, e)) return PIEHIP_EINVAL;
     HIPCHK(hipSetDevice(h->device));
     int rc = alloc_run_buffers(h, K, bin_hi - bin_lo, E);
     if (rc) return rc;
     Tmp tmp(h);
     int64_t *d_slots = nullptr;
-    if ((rc = items_to_slots(h, tmp, items, n, k, e, K, b, E, hash_seed, evict_seed, shuffle_seed, &d_slots))) return rc;
-    return encode_bin_layers(h, d_slots, K, b, E, (u32)B, bin_lo, bin_hi, mask_seed);
+    if ((rc = items_to_slots(h, tmp, items, n, k, e, K, b, E, hash_seed, evict_seed, shuffle_seed, &d_slots, R))) return rc;
+    return encode_bin_layers(h, d_slots, K, tiled_layers(b, R), E, R * (u32)B, bin_lo, bin_hi, mask_seed, R);
 }
 
 int piehip_build_db(piehip_handle h, const uint64_t *items, size_t n, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
                     uint64_t hash_seed, uint64_t evict_seed, uint64_t shuffle_seed, uint64_t mask_seed)
 {
-    return piehip_build_db_bins(h, items, n, k, e, K, b, E, hash_seed, evict_seed, shuffle_seed, mask_seed, 0, b);
+    return piehip_build_db_bins(h, items, n, k, e, K, b, E, hash_seed, evict_seed, shuffle_seed, mask_seed, 0, h ? tiled_layers(b, h->tiling) : b);
 }
 
 int piehip_load_db_table_bins(piehip_handle h, const uint64_t *tbl, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
@@ -834,22 +856,24 @@ int piehip_load_db_table_bins(piehip_handle h, const uint64_t *tbl, uint32_t k, 
     NEED(h);
     if (!tbl || k < 1 || e < 1) return fail(PIEHIP_EINVAL, "bad hash table");
     if (K < 2) return fail(PIEHIP_EINVAL, "Cuckoo Table needs more than one hash function!");  // CuckooHashTable.cpp:39-42
-    if (bin_lo >= bin_hi || bin_hi > b) return fail(PIEHIP_EINVAL, "bin-layer slice must be non-empty and within [0, b)");
+    const u32 R = h->tiling;  // bin_lo, bin_hi count tiled layers
+    if (bin_lo >= bin_hi || bin_hi > tiled_layers(b, R)) return fail(PIEHIP_EINVAL, "bin-layer slice must be non-empty and within [0, b)");
     const size_t B = (size_t)k * e;
     if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size k*e exceeds the ring dimension");
+    if (tiling_check(h, k, e)) return PIEHIP_EINVAL;
     HIPCHK(hipSetDevice(h->device));
     int rc = alloc_run_buffers(h, K, bin_hi - bin_lo, E);
     if (rc) return rc;
     Tmp tmp(h);
     int64_t *d_slots = nullptr;
-    if ((rc = table_to_slots(h, tmp, tbl, k, e, K, b, E, shuffle_seed, &d_slots))) return rc;
-    return encode_bin_layers(h, d_slots, K, b, E, (u32)B, bin_lo, bin_hi, mask_seed);
+    if ((rc = table_to_slots(h, tmp, tbl, k, e, K, b, E, shuffle_seed, &d_slots, R))) return rc;
+    return encode_bin_layers(h, d_slots, K, tiled_layers(b, R), E, R * (u32)B, bin_lo, bin_hi, mask_seed, R);
 }
 
 int piehip_load_db_table(piehip_handle h, const uint64_t *tbl, uint32_t k, uint32_t e, uint32_t K, uint32_t b, uint32_t E,
                          uint64_t shuffle_seed, uint64_t mask_seed)
 {
-    return piehip_load_db_table_bins(h, tbl, k, e, K, b, E, shuffle_seed, mask_seed, 0, b);
+    return piehip_load_db_table_bins(h, tbl, k, e, K, b, E, shuffle_seed, mask_seed, 0, h ? tiled_layers(b, h->tiling) : b);
 }
 
 int piehip_get_hash_table(piehip_handle h, uint64_t *tbl)
@@ -859,6 +883,32 @@ int piehip_get_hash_table(piehip_handle h, uint64_t *tbl)
     if (!h->d_hash_tbl) return fail(PIEHIP_ESTATE, "no table: call piehip_build_db first");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpy(tbl, h->d_hash_tbl, sizeof(u64) * (size_t)h->hk * h->he * h->K * h->hb * h->E, hipMemcpyDeviceToHost));
+    return PIEHIP_OK;
+}
+
+// ---- layer tiling (include/piehip.h "Layer tiling") -------------------------------------------------------------------------
+int piehip_set_layer_tiling(piehip_handle h, uint32_t R)
+{
+    NEED_RO(h);
+    if (R < 1) return fail(PIEHIP_EINVAL, "layer tiling: at least one bin layer per slot vector");
+    h->tiling = R;
+    return PIEHIP_OK;
+}
+int piehip_get_layer_tiling(piehip_handle h, uint32_t *R)
+{
+    NEED_RO(h);
+    if (!R) return fail(PIEHIP_EINVAL, "null out");
+    *R = h->tiling;
+    return PIEHIP_OK;
+}
+int piehip_layer_tiling(uint32_t N, uint32_t k, uint32_t e, uint32_t b, uint32_t *R, uint32_t *b_tiled)
+{
+    if (!R || !b_tiled || !k || !e || !b) return fail(PIEHIP_EINVAL, "layer_tiling: null out or empty shape");
+    const uint64_t rmax = (uint64_t)N / ((uint64_t)k * e);
+    if (!rmax) return fail(PIEHIP_EINVAL, "batch size k*e exceeds the ring dimension");
+    const uint32_t most = rmax < b ? (uint32_t)rmax : b;
+    *b_tiled = (b + most - 1) / most;
+    *R = (b + *b_tiled - 1) / *b_tiled;
     return PIEHIP_OK;
 }
 

@@ -221,6 +221,9 @@ struct piehip_ctx {
     u64 *arena = nullptr;
     size_t arena_words = 0, arena_used = 0;
     u32 hk = 0, he = 0, hb = 0;  // table dimensions ([k][e][K][hb][E]; hb = all bin layers, of which this handle keeps b)
+    // piehip_set_layer_tiling: the next build / table load / reserve packs `tiling` bin layers side by side into one slot vector and
+    // keeps ceil(hb / tiling) tiled layers (1 = as ever).  Only those calls read it: the database they leave is an ordinary one
+    u32 tiling = 1;
     piehip::NttPlan plan;
     piehip::ChainCtx cx;         // the handle's own context: d_dc, plan, d_sigma_inv above, and the handle's keys and masks
     // piehip_set_chain_schedule (piehip_set_chain_limbs: a schedule of one entry): product hf of run()'s chain, 1-based, works on the
@@ -422,15 +425,16 @@ int encode_on_device(piehip_ctx *h, const int64_t *d_slots, u32 npt, u32 B, u64 
 static const u32 ENCODE_CHUNK = 256;  // plaintexts per batch of the device encoder (bounds its mod-t scratch)
 // piehip.cpp: run() workspace (and, with_db, database and masks) of a handle for b bin layers; the lane-ordered copy of its masks; the
 // persistent hash-table buffer; a host table [k][e][K][b][E] uploaded into it, shuffled and gathered into slot vectors in the
-// caller's scratch (piehip_load_db_table_bins, piehip_load_db_table_sliced)
+// caller's scratch (piehip_load_db_table_bins, piehip_load_db_table_sliced).  R > 1 (layer tiling): the slot vectors are the tiled
+// ones, [max(K b' E, b')][R k e] with b' = ceil(b / R)
 int alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db = true);
 int make_masks_sigma(piehip_ctx *h);
 int hash_tbl_alloc(piehip_ctx *h, size_t words);
 // (hidden: the library's dynamic symbols stay the ones they were)
 __attribute__((visibility("hidden"))) int table_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *tbl, u32 k, u32 e, u32 K, u32 b, u32 E,
-                                                          u64 shuffle_seed, int64_t **d_slots);
+                                                          u64 shuffle_seed, int64_t **d_slots, u32 R = 1);
 __attribute__((visibility("hidden"))) int items_to_slots(piehip_ctx *h, Tmp &tmp, const u64 *items, size_t n, u32 k, u32 e, u32 K, u32 b, u32 E,
-                                                          u64 hash_seed, u64 evict_seed, u64 shuffle_seed, int64_t **d_slots);
+                                                          u64 hash_seed, u64 evict_seed, u64 shuffle_seed, int64_t **d_slots, u32 R = 1);
 // piehip_run.cpp: the queues of piehip_run_into / piehip_run_chain_into (host_results, piehip_run_staged: every queue group also
 // downloads its slice of the results there); whether stage A hands operand X over in lane order
 int run_on_queues(piehip_ctx *h, void *d_results, bool chain_only, u64 *host_results = nullptr);

@@ -265,6 +265,7 @@ int piehip_load_db_table_sliced(piehip_handle h, const uint64_t *tbl, uint32_t k
     if (K < 2) return fail(PIEHIP_EINVAL, "Cuckoo Table needs more than one hash function!");  // CuckooHashTable.cpp:39-42
     const size_t B = (size_t)k * e;
     if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size k*e exceeds the ring dimension");
+    if (h->tiling > 1) return fail(PIEHIP_ESTATE, "query slice: not with a layer tiling (piehip_set_layer_tiling above 1)");
     int rc = slice_setup(h, K, b, E, u_lo, u_hi, bin_lo, bin_hi);
     if (rc) return rc;
     Tmp tmp(h);
@@ -288,6 +289,7 @@ int piehip_build_db_sliced(piehip_handle h, const uint64_t *items, size_t n, uin
     if (K < 2) return fail(PIEHIP_EINVAL, "Cuckoo Table needs more than one hash function!");  // CuckooHashTable.cpp:39-42
     const size_t B = (size_t)k * e;
     if (B > h->hp.N) return fail(PIEHIP_EINVAL, "batch size k*e exceeds the ring dimension");
+    if (h->tiling > 1) return fail(PIEHIP_ESTATE, "query slice: not with a layer tiling (piehip_set_layer_tiling above 1)");
     int rc = slice_setup(h, K, b, E, u_lo, u_hi, bin_lo, bin_hi);
     if (rc) return rc;
     // the table is hashed, shuffled and gathered where it stays: in HBM (piehip_build_db_bins' steps), then encoded as

@@ -346,24 +346,31 @@ public:
 
     // BatchedFHEHIPPIE(cryptoContext, pK, hct), BatchedFHEHIPPIE.cpp:9-86.  The public key is unused by the
     // reference constructor and run() (it is only stored, .hpp:22), so it does not appear here.
-    BatchedFHEHIPPIE(PieContext &cryptoContext, const HashTableView &hct) : BatchedFHEHIPPIE(cryptoContext, hct, Seeds::fromRandomDevice()) {}
+    // layerTiling = R (include/piehip.h "Layer tiling"; 1 = the reference's packing): R bin layers side by side in every packed
+    // plaintext.  The operator then has tiledLayers() = ceil(eachBinSize / R) result ciphertexts, and its client repeats the k e slots
+    // of every query vector R times.  std::invalid_argument when R is 0 or R k e exceeds the ring dimension.
+    BatchedFHEHIPPIE(PieContext &cryptoContext, const HashTableView &hct, uint32_t layerTiling = 1)
+        : BatchedFHEHIPPIE(cryptoContext, hct, Seeds::fromRandomDevice(), layerTiling)
+    {
+    }
     // test-only: reproducible shuffle and masks
-    BatchedFHEHIPPIE(PieContext &cryptoContext, const HashTableView &hct, const Seeds &testSeeds)
+    BatchedFHEHIPPIE(PieContext &cryptoContext, const HashTableView &hct, const Seeds &testSeeds, uint32_t layerTiling = 1)
         : cc(cryptoContext)
     {
         const uint64_t shuffleSeed = testSeeds.shuffle, maskSeed = testSeeds.mask;
         if (hct.serverStashSize != 0) throw std::invalid_argument("Error, batched FHE PIE does not support a stash (yet).");
         if (!hct.simpleMultiTables || !hct.cuckooMultiTables)
             throw std::invalid_argument("Error, batched FHE PIE currently does not support combined tables.");
+        PieContext::check(piehip_set_layer_tiling(cc.handle(), layerTiling));
         K = hct.numberOfCuckooTables;
-        b = hct.eachBinSize;
+        b = (uint32_t)(((uint64_t)hct.eachBinSize + layerTiling - 1) / layerTiling);   // tiled layers: what the handle keeps
         E = hct.eachCuckooTableSize;
         const uint32_t k = hct.numberOfSimpleTables, e = hct.eachSimpleTableSize;
         const size_t B = (size_t)k * e;  // batch size, .cpp:41 (assumes simple multi table)
         if (B > cc.ringDimension()) throw std::invalid_argument("batch size exceeds the ring dimension");
         // bin-layer shuffle (.cpp:23-35), gather (.cpp:45-70), masks (.cpp:72-82) and MakePackedPlaintext (.cpp:68,81),
         // all on the device
-        PieContext::check(piehip_load_db_table(cc.handle(), hct.table, k, e, K, b, E, shuffleSeed, maskSeed));
+        PieContext::check(piehip_load_db_table(cc.handle(), hct.table, k, e, K, hct.eachBinSize, E, shuffleSeed, maskSeed));
         staged.init(cc, K, b, E, 1);
     }
 
@@ -396,6 +403,8 @@ public:
     // operator has no counterpart (OpenFHE's Compress is the call a maintainer would make: INTEGRATION.md).  Default: L.
     void setResultLimbs(uint32_t keep) { staged.setResultLimbs(keep); }
     uint32_t resultLimbs() const { return staged.resultLimbs(); }
+    // result ciphertexts per query: eachBinSize, or ceil(eachBinSize / layerTiling) with a layer tiling
+    uint32_t tiledLayers() const { return b; }
     // The last EvalMult of run() (.cpp:123) without its relinearisation: the result ciphertexts have three components [3][keep][N],
     // which decrypt as they are, and K = 2 needs no EvalMult key.  The reference operator relinearises (OpenFHE's default).  Default: on.
     void setResultRelin(bool on) { staged.setResultRelin(on); }

@@ -157,6 +157,14 @@ public:
     // keep exceeds the clients' L.
     void setResultLimbs(uint32_t keep) { resultLimbs = keep; }
 
+    // Layer tiling (include/piehip.h "Layer tiling"; off = the reference's packing): the database packs R bin layers side by side into
+    // every plaintext, R being piehip_layer_tiling's balanced choice for the clients' ring and this server's table sizes, and the server
+    // sends tiledLayers() = ceil(maxItemsPerPosition / R) result messages instead of maxItemsPerPosition.  The wire format does not
+    // change: the clients make the same choice from the same numbers, repeat the slots of every query vector R times, and read block r of
+    // result g as bin layer g R + r.  Call before run().
+    void setLayerTiling(bool on) { layerTiling = on; }
+    uint32_t tiledLayers() const { return tiled ? tiled : ht.maxItemsPerPosition; }   // known once the set-up phase has the context
+
     long long offlineComputation = 0, onlineComputation = 0;  // microseconds, PSIServer.hpp:89-103
 
     void runSetUpPhase()  // receiveAndSetContextAndKeys, BatchedFHEPSIServer.cpp:21-54, once per client
@@ -176,9 +184,15 @@ public:
                 PieContext::check(piehip_set_query_batch(cc->handle(), nq));
                 if (resultLimbs) PieContext::check(piehip_set_result_limbs(cc->handle(), resultLimbs));
                 if (chainLimbs) PieContext::check(piehip_set_chain_limbs(cc->handle(), chainLimbs));
+                if (layerTiling) {
+                    uint32_t R = 1;
+                    PieContext::check(piehip_layer_tiling(c.N, ht.numberOfSimpleHashFunctions, ht.eachSimpleTableSize, ht.maxItemsPerPosition,
+                                                          &R, &tiled));
+                    PieContext::check(piehip_set_layer_tiling(cc->handle(), R));
+                }
                 PieContext::check(piehip_reserve(cc->handle(), serverSet.size(), ht.numberOfSimpleHashFunctions, ht.eachSimpleTableSize,
                                                  ht.numberOfCuckooHashFunctions, ht.maxItemsPerPosition, ht.eachCuckooTableSize, 0,
-                                                 ht.maxItemsPerPosition));
+                                                 tiledLayers()));
             } else if (c.N != c0.N || c.L != c0.L || c.t != c0.t || std::memcmp(c.moduli, c0.moduli, sizeof(uint64_t) * (2 * c.L + 1))) {
                 throw std::invalid_argument("the clients of one batch must use the same crypto context parameters");
             }
@@ -219,7 +233,7 @@ public:
     void runOnlinePhase()  // BatchedFHEPSIServer.cpp:92-112
     {
         const uint32_t L = cc->towers(), N = cc->ringDimension(), K = ht.numberOfCuckooHashFunctions, E = ht.eachCuckooTableSize,
-                       b = ht.maxItemsPerPosition, nq = (uint32_t)fds.size();
+                       b = tiledLayers(), nq = (uint32_t)fds.size();
         // Every message is unpacked (and range-checked) straight into the library's page-locked staging arrays, and a piece's
         // upload starts as soon as it has landed: every message's ciphertext at once -- the 29 MiB of a C3 query cross PCIe
         // underneath the receive loop, and when the timer starts only the last megabyte is still on its way (the reference deserialises into
@@ -255,6 +269,8 @@ private:
     uint64_t evictSeed = 0, shuffleSeed = 0, maskSeed = 0;
     uint32_t resultLimbs = 0;   // setResultLimbs: 0 = every limb
     uint32_t chainLimbs = 0;    // the constructor's option: 0 = every limb
+    bool layerTiling = false;   // setLayerTiling
+    uint32_t tiled = 0;         // result messages per client with a layer tiling (0: no tiling)
     std::vector<uint64_t> qMod;
     std::unique_ptr<PieContext> cc;
 };

@@ -73,6 +73,14 @@ def rccl_bin_slice(b_total, nranks, rank):
     return lo.value, hi.value
 
 
+def layer_tiling(N, k, e, b):
+    """(R, b_tiled): the balanced layer tiling of b bin layers of k*e slots on a ring of N slots (piehip_layer_tiling); ValueError
+    when k*e exceeds N"""
+    R, bt = C.c_uint32(), C.c_uint32()
+    _check(lib().piehip_layer_tiling(int(N), int(k), int(e), int(b), C.byref(R), C.byref(bt)))
+    return R.value, bt.value
+
+
 def default_moduli(N, L):
     q = np.zeros(L, dtype=np.uint64)
     p = np.zeros(L + 1, dtype=np.uint64)
@@ -130,6 +138,17 @@ class PieContext:
         buf, n = (C.c_uint32 * 7)(), C.c_uint32()
         _check(lib().piehip_get_chain_schedule(self._h, buf, 7, C.byref(n)))
         return list(buf[:n.value])
+
+    def setLayerTiling(self, R):
+        """the next database built from a server set or a hash table, and the next reserve(), pack R bin layers side by side into
+        every slot vector and keep ceil(b / R) tiled layers (piehip_set_layer_tiling; 1 = the default, as ever).  For a reserve() ahead
+        of the offline phase: BatchedFHEHIPPIE(.., layerTiling=R) sets it itself, to 1 when it is not given"""
+        _check(lib().piehip_set_layer_tiling(self._h, int(R)))
+
+    def layerTiling(self):
+        n = C.c_uint32()
+        _check(lib().piehip_get_layer_tiling(self._h, C.byref(n)))
+        return n.value
 
     # -- tables (for cross-checks)
     def psi(self, mi):
@@ -294,8 +313,9 @@ class PieContext:
         return ms.value
 
     def reserve(self, n_items, k, e, K, b, E, binSlice=None):
-        """allocate ahead of the offline phase what a database of this shape and its queries need (piehip_reserve)"""
-        lo, hi = binSlice if binSlice is not None else (0, b)
+        """allocate ahead of the offline phase what a database of this shape and its queries need (piehip_reserve).  With a layer
+        tiling R (setLayerTiling) the reservation is for ceil(b / R) tiled layers, which binSlice then counts"""
+        lo, hi = binSlice if binSlice is not None else (0, -(-b // self.layerTiling()))
         _check(lib().piehip_reserve(self._h, int(n_items), k, e, K, b, E, lo, hi))
 
     def set_run_streams(self, n):
@@ -352,11 +372,16 @@ class BatchedFHEHIPPIE:
     limbs (vectorizedHCT [K][b][E][L][N], preCalcRandomMask [b][L][N]) or as raw slot values
     ([K][b][E][B], [b][B]) which the device encodes (MakePackedPlaintext, .cpp:68,81).
     stash_size / multi-table flags reproduce the argument checks at .cpp:13-21.
+
+    layerTiling=R (serverSet and hashTable forms; include/piehip.h "Layer tiling"): R bin layers side by side in every packed
+    plaintext.  The operator then has self.b = ceil(b / R) tiled layers -- getResultList returns that many ciphertexts, binSlice
+    counts them -- and its clients must tile their query vectors R times (client.BatchedFHEPSIClient(.., layerTiling=R)).
+    hashTable() is still the untiled table.
     """
 
     def __init__(self, cryptoContext, vectorizedHCT=None, preCalcRandomMask=None, slots=None, mask_slots=None,
                  serverStashSize=0, simpleMultiTables=True, cuckooMultiTables=True, serverSet=None, hashParams=None,
-                 hashTable=None, shuffle_seed=None, mask_seed=None, binSlice=None, attachTo=None):
+                 hashTable=None, shuffle_seed=None, mask_seed=None, binSlice=None, attachTo=None, layerTiling=1):
         # Seeds of the Cuckoo evictions, the bin-layer shuffle and the random masks: secret by default (OS CSPRNG), as the
         # reference draws them from std::random_device (BatchedFHEHIPPIE.cpp:25-26,72-82; CuckooHashTable.cpp:51-52).
         # The masks hide prod_h(item - x) of non-matching slots from the client.  Explicit seeds are for parity tests.
@@ -372,6 +397,9 @@ class BatchedFHEHIPPIE:
         # database must be given the same seeds
         if binSlice is not None and serverSet is None and hashTable is None:
             raise ValueError("binSlice applies to databases built from a server set or a hash table")
+        self.layerTiling = R = int(layerTiling)
+        if R != 1 and (attachTo is not None or (serverSet is None and hashTable is None)):
+            raise ValueError("layerTiling applies to databases built from a server set or a hash table")
         if binSlice is not None:
             # every shard builds (or shuffles) the whole table and keeps its slice: with seeds drawn per rank the ranks would cut
             # slices out of different tables -- items in two shards or in none, silent false negatives.  The seeds of a sharded
@@ -393,7 +421,8 @@ class BatchedFHEHIPPIE:
             # evict_seed, shuffle_seed, mask_seed
             p = hashParams
             items, ip = _u64(serverSet)
-            lo, hi = binSlice if binSlice is not None else (0, p["b"])
+            _check(lib().piehip_set_layer_tiling(h, R))
+            lo, hi = binSlice if binSlice is not None else (0, -(-p["b"] // R))
             self.K, self.b, self.E = p["K"], hi - lo, p["E"]
             _check(lib().piehip_build_db_bins(h, ip, len(items), p["k"], p["e"], p["K"], p["b"], p["E"], p.get("hash_seed", 987654321),
                                               secret(p.get("evict_seed")), secret(p.get("shuffle_seed", shuffle_seed)),
@@ -403,7 +432,8 @@ class BatchedFHEHIPPIE:
             # the reference constructor proper: hct.hierarchicalCuckooTable [k][e][K][b][E] -> shuffle, gather, encode
             tbl, tp = _u64(hashTable)
             k, e, self.K, ball, self.E = tbl.shape
-            lo, hi = binSlice if binSlice is not None else (0, ball)
+            _check(lib().piehip_set_layer_tiling(h, R))
+            lo, hi = binSlice if binSlice is not None else (0, -(-ball // R))
             self.b = hi - lo
             _check(lib().piehip_load_db_table_bins(h, tp, k, e, self.K, ball, self.E, secret(shuffle_seed), secret(mask_seed), lo, hi))
             self._tbl_shape = tbl.shape
