@@ -215,6 +215,12 @@ int piehip_set_run_streams(piehip_handle h, uint32_t n);
  * free; results are bit-identical for every n), 0 = the default, every slot.  Applies to this handle's later runs. */
 int piehip_set_transform_slots(piehip_handle h, uint32_t n);
 int piehip_get_transform_slots(piehip_handle h, uint32_t *n /* the cap, 0 = none */, uint32_t *device_slots /* 2 x CUs */);
+/* How the context's kernels reduce sums of variable x variable products, decided once from the moduli at creation:
+ *   0  128-bit accumulators, two-word Barrett (some modulus outside (2^59, 2^60))
+ *   1  30-bit column accumulators, one-word Barrett (every Q and P modulus in (2^59, 2^60))
+ *   2  column accumulators folded with d (every Q and P modulus is 2^60 - d with d < 2^27: the default chains) in the base
+ *      conversions, scale-and-round and the fused tensor product; results are the same residues either way */
+int piehip_get_reduction(piehip_handle h, uint32_t *kind);
 /* on != 0: run() / run_into() replay one captured hipGraph (all launches of both queue groups, forked from and joined back to
  * the handle's stream) instead of enqueueing ~26 launches; re-captured when the input arrays, the result buffer or the queue
  * count change.  Amortises the launch path when a handle evaluates few bin layers (one rank's share of a sharded server);

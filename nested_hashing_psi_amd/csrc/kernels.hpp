@@ -54,6 +54,8 @@ struct NttPlan {
     u32 lane_T = 0;              // its threads per slice
     u32 lane_kp = 16;            // and coefficient pairs per thread (16: kernels_ntt_fast.hip, 8: ntt16_kernel.h)
     bool small_moduli = false;   // every Q and P modulus lies in (2^59, 2^60): v_mad_u64_u32 column accumulators, one-word Barrett
+    bool fold_moduli = false;    // ... and is 2^60 - d with d < COLACC_FOLD_MAX_D (the default chains): the base conversions, scale-and-
+                                 // round and the tensor load phase reduce their column sums by folding with d (stage_a_common.h)
     // schedule switches derived from the above (piehip_run.cpp)
     bool xq_reuse = false;         // the inverse transform of operand X drops a lane-ordered copy into the QP array, the forward skips it
     bool x_direct = false;         // stage A of a query batch may write X there in the first place (StageAXOut)
@@ -73,9 +75,18 @@ struct NttPlan {
         return c < num_cus ? (c ? c : 1u) : num_cus;
     }
 };
-// fills in everything from lane_order on, from N / logN and the two facts about the moduli: lazy_ok -- every modulus, t included, is
-// below 2^60 (lazy residues need 8q < 2^63) -- and small_moduli
-void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli);
+// fills in everything from lane_order on, from N / logN and the three facts about the moduli: lazy_ok -- every modulus, t included, is
+// below 2^60 (lazy residues need 8q < 2^63) --, small_moduli and fold_moduli (kept only with small_moduli)
+void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli, bool fold_moduli = false);
+// q = 2^60 - d takes the folded block for d below this: the largest d its bound proof supports at z < 2^124 (2^28 at z < 2^123)
+static const u64 COLACC_FOLD_MAX_D = 1ull << 27;
+// The arithmetic kind of the kernels that reduce variable x variable column sums: the 128-bit forms; column accumulators with the
+// one-word Barrett block (mad); column accumulators with the folded block (mad and fold).  A plain bool is the plan's small_moduli.
+struct Arith {
+    bool mad, fold;
+    Arith(bool small_moduli, bool fold_moduli = false) : mad(small_moduli), fold(small_moduli && fold_moduli) {}
+    Arith(const NttPlan &pl) : mad(pl.small_moduli), fold(pl.small_moduli && pl.fold_moduli) {}
+};
 // sigma, folded: as for launch_ntt.  Requires sigma <= pl.lane_order and folded <= pl.fold (the callers' wrappers mask them)
 NttRoute ntt_route(const NttPlan &pl, bool inverse, bool sigma, bool folded);
 
@@ -176,12 +187,13 @@ void launch_stage_a_batch(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E
 // is read at in + o*in_stride_outer + c*in_stride_inner ([L][N] limbs, canonical, nothing pending) and written to
 // out + ((o*out_polys + out_slot + c)*M)*N ([M][N] limbs): every limb, no folding (piehip_base_convert)
 // small_moduli (here and below): NttPlan::small_moduli of the context -- selects the v_mad_u64_u32 / one-word Barrett variants
+// ar: the context's arithmetic kind (Arith: the plan, or its small_moduli alone for the Barrett kind)
 void launch_expand_q_to_qp(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t in_stride_outer,
                            size_t in_stride_inner, u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st,
-                           bool small_moduli);
+                           Arith ar);
 void launch_scale_pq_expand(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t in_stride_outer,
                             size_t in_stride_inner, u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st,
-                            bool small_moduli);
+                            Arith ar);
 // Both conversions of a ciphertext multiplication in one launch, on the context (dc, L limbs, M = 2 L + 1; small_moduli and fold: its
 // plan's): X centred-lifted into slots 0, 1 of out[n_outer][4][M][N], Y scaled by P/Q into slots 2, 3.  fold: the outermost stage of
 // the forward transform that follows is applied on the store side (kernels_pie.hip, "Outer-stage folding").
@@ -204,16 +216,16 @@ struct ExpandOperand {
     bool q_ready = false;
 };
 bool launch_expand_pair(const DevConsts *dc, u32 N, u32 L, const ExpandOperand &x, const ExpandOperand &y, u32 n_outer, u64 *out,
-                        hipStream_t st, bool small_moduli, bool fold);
+                        hipStream_t st, Arith ar, bool fold);
 // the first case by its parts: both pending on the context's own level, rows sx and sy apart, polynomials si (lazy_inputs_check)
 inline bool launch_expand_both(const DevConsts *dc, u32 N, u32 L, const u64 *x, size_t sx, const u64 *y, size_t sy, size_t si, u32 n_outer,
-                               u64 *out, hipStream_t st, bool small_moduli, bool fold = false, bool skip_q = false)
+                               u64 *out, hipStream_t st, Arith ar, bool fold = false, bool skip_q = false)
 {
     ExpandOperand xo, yo;
     xo.p = x, yo.p = y;
     xo.row = sx, yo.row = sy, xo.poly = yo.poly = si;
     xo.q_ready = skip_q;
-    return launch_expand_pair(dc, N, L, xo, yo, n_outer, out, st, small_moduli, fold);
+    return launch_expand_pair(dc, N, L, xo, yo, n_outer, out, st, ar, fold);
 }
 // is the fused form built for Y on Ly limbs and X on Lx (Lx <= Lc: X is not dropped), both to Lc?  (-DPIEHIP_CHAIN_DROP_FUSED=0: never)
 bool expand_drop_built(u32 Ly, u32 Lx, u32 Lc);
@@ -227,7 +239,7 @@ void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 
 // p_only01 (pl.d01_eval_q): components 0 and 1 are computed from their P limbs alone -- the Q limbs of d are not read and the own-limb
 // term d_k [t P^-1]_{q_k} is left out (the key-switch MAC adds its transform: launch_relin_mac, eqp)
 void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb, u64 *out01, size_t stride01, u64 *out2,
-                        size_t stride2, hipStream_t st, bool small_moduli, bool fold = false, bool fold_comp2 = false, bool p_only01 = false,
+                        size_t stride2, hipStream_t st, Arith ar, bool fold = false, bool fold_comp2 = false, bool p_only01 = false,
                         bool p_only2 = false);
 // BV digits: d2c at d2 + bin*stride2 ([L][N], COEFFICIENT) -> dig[nb][L(i)][L(j)][N] (centred lift of residue i into q_j)
 void launch_digits(const DevConsts *dc, u32 N, u32 L, const u64 *d2, size_t stride2, u32 nb, u64 *dig, hipStream_t st,

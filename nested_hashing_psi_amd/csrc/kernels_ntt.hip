@@ -149,10 +149,11 @@ NttRoute ntt_route(const NttPlan &pl, bool inverse, bool sigma, bool folded)
     return {NttKernel::blocked32, s0, s0};
 }
 
-void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli)
+void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli, bool fold_moduli)
 {
     pl.lane_order = lazy_ok && pl.logN >= 12;
     pl.small_moduli = small_moduli;
+    pl.fold_moduli = small_moduli && fold_moduli;
     if (!pl.lane_order) return;
     const bool k16 = pl.logN >= 13 && pl.logN <= 15;
     pl.lane_kernel = k16 ? NttKernel::blocked16 : NttKernel::blocked32;

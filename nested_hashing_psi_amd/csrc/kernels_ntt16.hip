@@ -24,13 +24,15 @@ void ntt16_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map)
 }
 
 template <u32 LOGNS>
-static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 num_cus, hipStream_t st, bool tensor = false)
+static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 num_cus, hipStream_t st, bool tensor = false, bool fd = false)
 {
     typedef ntt16::Geo<LOGNS> G;
     constexpr size_t lds = (size_t)G::LDS_WORDS * sizeof(u64);
-    static PerDeviceOnce attr[4];
-    if (attr[tensor ? 3 : inverse ? 1 : (lift ? 2 : 0)].first_on_current_device()) {
-        if (tensor)
+    static PerDeviceOnce attr[5];
+    if (attr[tensor ? (fd ? 4 : 3) : inverse ? 1 : (lift ? 2 : 0)].first_on_current_device()) {
+        if (tensor && fd)
+            (void)hipFuncSetAttribute((const void *)ntt16::ntt16_tensor_fd_kernel_t<LOGNS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        else if (tensor)
             (void)hipFuncSetAttribute((const void *)ntt16::ntt16_kernel_t<LOGNS, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         else if (inverse)
             (void)hipFuncSetAttribute((const void *)ntt16::ntt16_kernel_t<LOGNS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -42,7 +44,9 @@ static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 nu
     // resident workgroups per CU: two of 512 threads (68 KiB of LDS, 128 VGPRs each) or one of 1024 (136 KiB); persistent beyond
     const u32 slots = (LOGNS == 13 ? 2u : 1u) * num_cus;
     const u32 grid = a.nitems < slots ? a.nitems : slots;
-    if (tensor)
+    if (tensor && fd)
+        hipLaunchKernelGGL((ntt16::ntt16_tensor_fd_kernel_t<LOGNS>), dim3(grid), dim3(G::T), lds, st, a);
+    else if (tensor)
         hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, true, false, true>), dim3(grid), dim3(G::T), lds, st, a);
     else if (inverse)
         hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, true>), dim3(grid), dim3(G::T), lds, st, a);
@@ -125,9 +129,9 @@ void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M,
     a.lift_L = 1;
     a.tsrc = e;
     if (pl.lane_logn == 14)
-        launch_ntt16_t<14>(a, true, false, pl.transform_cus(), st, true);
+        launch_ntt16_t<14>(a, true, false, pl.transform_cus(), st, true, pl.fold_moduli);
     else
-        launch_ntt16_t<13>(a, true, false, pl.transform_cus(), st, true);
+        launch_ntt16_t<13>(a, true, false, pl.transform_cus(), st, true, pl.fold_moduli);
 }
 
 }  // namespace piehip

@@ -205,7 +205,8 @@ __device__ __forceinline__ U128 dot128(const u64 *y, const u64 (&c)[NS])
 // centred CRT lift of y_i-weighted residues from a source basis into target modulus `tm`:
 //   sum_i y_i * hat[i] - v * prodmod
 // LZ (MAD only): the result stays in [0, 4q) (colacc_reduce123_lazy)
-template <u32 NS, bool MAD, bool LZ = false>
+// FD (MAD only; NttPlan::fold_moduli): the folded reduction block in place of the Barrett block
+template <u32 NS, bool MAD, bool LZ = false, bool FD = false>
 __device__ __forceinline__ u64 crt_out(const u64 *y, const u64 (&hat)[NS], u64 v, u64 prodmod, const Mod &tm, u64 negq, u64 neg2q)
 {
     if (MAD && NS <= 7) {
@@ -215,7 +216,7 @@ __device__ __forceinline__ u64 crt_out(const u64 *y, const u64 (&hat)[NS], u64 v
 #pragma unroll
         for (u32 i = 0; i < NS; i++) colacc_mac(a, split30(y[i]), split30(hat[i]));
         colacc_mac_small(a, (u32)v, tm.q - prodmod);  // - v * prodmod (mod tm)
-        return LZ ? colacc_reduce123_lazy(a, tm, negq) : colacc_reduce<false>(a, tm, negq);
+        return LZ ? colacc_red_lazy<FD>(a, tm, negq) : colacc_red<FD, false>(a, tm, negq);
     }
     U128 acc = dot128<NS, MAD>(y, hat);
     mac128(acc, v, tm.q - prodmod);  // - v * prodmod (mod tm); v <= ns: one Barrett reduction for the whole sum

@@ -169,12 +169,13 @@ static std::string context_tables(piehip_ctx *h, const HostParams &hp, NttPlan &
     pl.N = N;
     pl.logN = logN;
     {
-        bool lazy_ok = true, small_moduli = true;
+        bool lazy_ok = true, small_moduli = true, fold_moduli = true;
         for (u32 a = 0; a <= M; a++) {
             if (hp.moduli[a] >> 60) lazy_ok = false;                      // lazy residues need 8q < 2^63 (t included)
             if (a < M && (hp.moduli[a] >> 59) != 1) small_moduli = false;  // the mad paths assume 2^59 < q < 2^60 (Q and P)
+            if (a < M && (1ull << 60) - hp.moduli[a] >= COLACC_FOLD_MAX_D) fold_moduli = false;  // q = 2^60 - d, d below the proven bound
         }
-        ntt_plan_decide(pl, lazy_ok, small_moduli);
+        ntt_plan_decide(pl, lazy_ok, small_moduli, fold_moduli);
         hipDeviceProp_t prop;
         pl.num_cus = (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) ? (u32)prop.multiProcessorCount : 256u;
     }
@@ -1143,6 +1144,13 @@ int piehip_set_result_relin(piehip_handle h, int on)
     const int rc = ensure_full_rows(h, h->K);
     if (rc) h->res_relin = before;
     return rc;
+}
+int piehip_get_reduction(piehip_handle h, uint32_t *kind)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!kind) return fail(PIEHIP_EINVAL, "null out");
+    *kind = h->plan.fold_moduli ? 2u : h->plan.small_moduli ? 1u : 0u;
+    return PIEHIP_OK;
 }
 int piehip_get_result_relin(piehip_handle h, int *on)
 {

@@ -171,11 +171,11 @@ int piehip_base_convert(piehip_handle h, int which, const uint64_t *in, uint32_t
     TMPGET(dout, wout);
     HIPCHK(hipMemcpy(din, in, win * sizeof(u64), hipMemcpyHostToDevice));
     if (which == 0)
-        launch_expand_q_to_qp(h->d_dc, N, L, din, 2 * LN, LN, npoly / 2, dout, 2, 0, h->stream, h->plan.small_moduli);
+        launch_expand_q_to_qp(h->d_dc, N, L, din, 2 * LN, LN, npoly / 2, dout, 2, 0, h->stream, h->plan);
     else if (which == 1)
-        launch_scale_pq_expand(h->d_dc, N, L, din, 2 * LN, LN, npoly / 2, dout, 2, 0, h->stream, h->plan.small_moduli);
+        launch_scale_pq_expand(h->d_dc, N, L, din, 2 * LN, LN, npoly / 2, dout, 2, 0, h->stream, h->plan);
     else
-        launch_scale_round(h->d_dc, N, L, din, npoly / 3, dout, 3 * LN, dout + 2 * LN, 3 * LN, h->stream, h->plan.small_moduli);
+        launch_scale_round(h->d_dc, N, L, din, npoly / 3, dout, 3 * LN, dout + 2 * LN, 3 * LN, h->stream, h->plan);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out, dout, wout * sizeof(u64), hipMemcpyDeviceToHost));

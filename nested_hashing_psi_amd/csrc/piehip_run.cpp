@@ -77,7 +77,7 @@ void enqueue_mul(Sched &s, MulWs &w, const ExpandOperand &x, const ExpandOperand
     const bool xq_ready = x.q_ready;
     {
         ProfScope ps(s, PIEHIP_K_EXPAND, W * nb * (2.0 * std::max(y.src_L, L) + 2.0 * std::max(x.src_L, L) + 4.0 * M));
-        const bool ok = launch_expand_pair(cx.d_dc, N, L, x, y, nb, w.eqp, s.stream, pl.small_moduli, pl.fold);
+        const bool ok = launch_expand_pair(cx.d_dc, N, L, x, y, nb, w.eqp, s.stream, pl, pl.fold);
         assert(ok);
         (void)ok;
     }
@@ -114,7 +114,7 @@ void enqueue_mul(Sched &s, MulWs &w, const ExpandOperand &x, const ExpandOperand
     if (relin) {
         {
             ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(cx.d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, s.stream, pl.small_moduli, pl.fold, false, eval_q);
+            launch_scale_round(cx.d_dc, N, L, w.dqp, nb, w.d01, 2 * LN, w.d2c, LN, s.stream, pl, pl.fold, false, eval_q);
         }
         NttExtra ex;
         ex.lazy_out = true;  // the key-switch MAC adds d01 into its accumulator before reducing
@@ -135,7 +135,7 @@ void enqueue_mul(Sched &s, MulWs &w, const ExpandOperand &x, const ExpandOperand
     } else if (eval_q3) {
         {
             ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * (M - L) + 3.0 * L));
-            launch_scale_round(cx.d_dc, N, L, w.dqp, nb, w.t3, 3 * LN, w.t3 + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true, true, true);
+            launch_scale_round(cx.d_dc, N, L, w.dqp, nb, w.t3, 3 * LN, w.t3 + 2 * LN, 3 * LN, s.stream, pl, pl.fold, true, true, true);
         }
         NttExtra ex;
         ex.lazy_out = true;  // the finishing kernel adds the own-limb term into its accumulator before reducing
@@ -147,7 +147,7 @@ void enqueue_mul(Sched &s, MulWs &w, const ExpandOperand &x, const ExpandOperand
         u64 *t = deg2 ? w.t3 : out;
         {
             ProfScope ps(s, PIEHIP_K_SCALE, W * nb * (3.0 * M + 3.0 * L));
-            launch_scale_round(cx.d_dc, N, L, w.dqp, nb, t, 3 * LN, t + 2 * LN, 3 * LN, s.stream, pl.small_moduli, pl.fold, true);
+            launch_scale_round(cx.d_dc, N, L, w.dqp, nb, t, 3 * LN, t + 2 * LN, 3 * LN, s.stream, pl, pl.fold, true);
         }
         ntt(s, t, nb * 3 * L, 0, L, false, false, true);
         if (deg2) {

@@ -172,6 +172,78 @@ __device__ __forceinline__ u64 colacc_reduce(const ColAcc &a, const Mod &m, u64 
     return r;
 }
 
+// The same reduction for a modulus q = 2^60 - d with d small (the default chains: the largest primes below 2^60 that are 1 mod 2N),
+// without a quotient estimate: 2^60 = d (mod q), so the part of z above bit 60 folds into the low 60 bits by multiplications
+// with d.  d is the low word of 2^64 - q (the high word is 0xf0000000).  With the columns carry-normalised as above,
+//   z = lo60 + n2 2^60,  lo60 = z mod 2^60 (two words),  n2 = z >> 60 = c2' (two words n2l, n2h)
+//   t = n2l d + lo60                                       one v_mad_u64_u32
+//   u = n2h d                                              one more; n2 d = n2l d + u 2^32
+//   u 2^32 = (u >> 28) 2^60 + (u mod 2^28) 2^32  =  (u >> 28) d + (u mod 2^28) 2^32  (mod q)
+//   r = t + (u mod 2^28) 2^32 + (u >> 28) d                a 32-bit add into t's high word, the third v_mad_u64_u32
+// Bounds for z < 2^B and d < 2^k:  t < 2^60 + 2^(32+k);  u < 2^(B-92+k);  t's high word < 2^28 + 2^k and u mod 2^28 < 2^28: the
+// 32-bit add does not carry for k <= 30;  u >> 28 < 2^(B-120+k) fits one word;  (u >> 28) d < 2^(B-120+2k);
+//   r < 2^60 + 2^(32+k) + 2^60 + 2^(B-120+2k)
+//   B = 123 (seven products), k = 28:  r < 2^61 + 2^60 + 2^59 = 3.5 2^60 < 4q   (k = 29: 2^62, not below 4q)
+//   B = 124 (eight products), k = 27:  r < 2^61 + 2^59 + 2^58 = 2.75 2^60 < 3q  (k = 28: 2^62)
+// so ONE block serves both widths for d < 2^27 = COLACC_FOLD_MAX_D (kernels.hpp), the bound a context is selected by (NttPlan::fold_moduli), and
+// leaves less than 3q as the Barrett block does.  Nothing reads VCC: no wait states.  13 instructions, 3 of them multiplier
+// operations (the Barrett block: 23 and 7); no mu.  v60-v69 and vcc as scratch.
+#define PIE_COLACC_FOLD_HEAD \
+    "v_lshrrev_b64 v[60:61], 30, %[c0]\n\t" \
+    "v_lshl_add_u64 v[60:61], v[60:61], 0, %[c1]\n\t" \
+    "v_lshrrev_b64 v[62:63], 30, v[60:61]\n\t" \
+    "v_lshl_add_u64 v[62:63], v[62:63], 0, %[c2]\n\t" \
+    "v_and_b32 v66, 0x3fffffff, %[c0l]\n\t" \
+    "v_bfe_u32 v67, v60, 2, 28\n\t" \
+    "v_mad_u64_u32 v[64:65], vcc, v63, %[d], 0\n\t" \
+    "v_lshl_or_b32 v66, v60, 30, v66\n\t" \
+    "v_mad_u64_u32 v[66:67], vcc, v62, %[d], v[66:67]\n\t" \
+    "v_and_b32 v68, 0xfffffff, v64\n\t" \
+    "v_alignbit_b32 v69, v65, v64, 28\n\t" \
+    "v_add_u32 v67, v67, v68\n\t"
+// ... and the third product, into the result (lazy) or into v[66:67] (CANON).  CANON: one more fold, r' = (r mod 2^60) + (r >> 60) d
+// with r >> 60 <= 2, so r' < 2^60 + 2d = q + 3d < 2q, and one sign-mask subtraction: 20 instructions (the Barrett forms: 32 and 35)
+template <bool CANON>
+__device__ __forceinline__ u64 colacc_fold(const ColAcc &a, u64 nq)
+{
+    if (!CANON) {
+        u64 r;
+        asm(PIE_COLACC_FOLD_HEAD
+            "v_mad_u64_u32 %[r], vcc, v69, %[d], v[66:67]"
+            : [r] "=v"(r)
+            : [c0] "v"(a.c0), [c1] "v"(a.c1), [c2] "v"(a.c2), [c0l] "v"((u32)a.c0), [d] "s"((u32)nq)
+            : PIE_ASM_CLOB);
+        return r;
+    }
+    u32 lo, hi;
+    asm(PIE_COLACC_FOLD_HEAD
+        "v_mad_u64_u32 v[66:67], vcc, v69, %[d], v[66:67]\n\t"
+        "v_lshrrev_b32 v68, 28, v67\n\t"
+        "v_and_b32 v67, 0xfffffff, v67\n\t"
+        "v_mad_u64_u32 v[66:67], vcc, v68, %[d], v[66:67]\n\t"
+        "v_lshl_add_u64 v[60:61], v[66:67], 0, %[n1q]\n\t"
+        "v_ashrrev_i32 v62, 31, v61\n\t"
+        "v_bfi_b32 %[lo], v62, v66, v60\n\t"
+        "v_bfi_b32 %[hi], v62, v67, v61"
+        : [lo] "=v"(lo), [hi] "=v"(hi)
+        : [c0] "v"(a.c0), [c1] "v"(a.c1), [c2] "v"(a.c2), [c0l] "v"((u32)a.c0), [d] "s"((u32)nq), [n1q] "s"(nq)
+        : PIE_ASM_CLOB);
+    return ((u64)hi << 32) | lo;
+}
+// the reduction of a kernel's arithmetic kind: FD (NttPlan::fold_moduli) the folded block, otherwise the Barrett block
+template <bool FD, bool W124>
+__device__ __forceinline__ u64 colacc_red(const ColAcc &a, const Mod &m, u64 nq)
+{
+    if constexpr (FD) return colacc_fold<true>(a, nq);
+    else return colacc_reduce<W124>(a, m, nq);
+}
+template <bool FD>
+__device__ __forceinline__ u64 colacc_red_lazy(const ColAcc &a, const Mod &m, u64 nq)
+{
+    if constexpr (FD) return colacc_fold<false>(a, nq);
+    else return colacc_reduce123_lazy(a, m, nq);
+}
+
 // ---------------------------------------------------------------------------------------------
 // The term loop of the tiled stage A kernels: a[q][t][c] = sum_j idx_q[j][c] * db[layer t][j] for the thread's coefficient, Q queries
 // and BPT bin layers.  A database word is loaded once for the Q queries, an index word once per BPT layers, DEPTH terms are in flight

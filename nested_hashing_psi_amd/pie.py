@@ -333,6 +333,13 @@ class PieContext:
         _check(lib().piehip_get_transform_slots(self._h, C.byref(n), C.byref(d)))
         return int(n.value), int(d.value)
 
+    def reduction(self):
+        """how the context reduces column sums (piehip_get_reduction): "wide" (128-bit, two-word Barrett), "barrett" (column accumulators,
+        one-word Barrett) or "fold" (column accumulators folded with d: every modulus 2^60 - d, d < 2^27)"""
+        k = C.c_uint32()
+        _check(lib().piehip_get_reduction(self._h, C.byref(k)))
+        return ("wide", "barrett", "fold")[k.value]
+
     def upload_turn_wait(self):
         """how long this handle's staging sequences waited for their turn on the PCIe link: (last ms, total ms, waits)"""
         a, b, n = C.c_double(), C.c_double(), C.c_uint64()
