@@ -221,6 +221,10 @@ int piehip_get_transform_slots(piehip_handle h, uint32_t *n /* the cap, 0 = none
  *   2  column accumulators folded with d (every Q and P modulus is 2^60 - d with d < 2^27: the default chains) in the base
  *      conversions, scale-and-round and the fused tensor product; results are the same residues either way */
 int piehip_get_reduction(piehip_handle h, uint32_t *kind);
+/* The same for the level context of Lc limbs (Chain limbs: a level has a plan of its own, decided from the moduli it keeps, so a
+ * level of a Barrett parent folds where the parent's only wide-d moduli are among those it drops).  Lc = L is the handle's own
+ * plan; PIEHIP_ESTATE for a level that no piehip_set_chain_schedule of this handle has named yet. */
+int piehip_get_level_reduction(piehip_handle h, uint32_t Lc, uint32_t *kind);
 /* on != 0: run() / run_into() replay one captured hipGraph (all launches of both queue groups, forked from and joined back to
  * the handle's stream) instead of enqueueing ~26 launches; re-captured when the input arrays, the result buffer or the queue
  * count change.  Amortises the launch path when a handle evaluates few bin layers (one rank's share of a sharded server);

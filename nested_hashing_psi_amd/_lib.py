@@ -104,6 +104,7 @@ SYMBOLS = {
     "piehip_set_transform_slots": (C.c_int, [C.c_void_p, C.c_uint32]),
     "piehip_get_transform_slots": (C.c_int, [C.c_void_p, u32p, u32p]),
     "piehip_get_reduction": (C.c_int, [C.c_void_p, u32p]),
+    "piehip_get_level_reduction": (C.c_int, [C.c_void_p, C.c_uint32, u32p]),
     "piehip_upload_turn_wait": (C.c_int, [C.c_void_p, f64p, f64p, u64p]),
     "piehip_set_host_path_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "piehip_host_path_times": (C.c_int, [C.c_void_p, f64p, f64p]),

@@ -81,7 +81,9 @@ void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli, bool fold_mod
 // q = 2^60 - d takes the folded block for d below this: the largest d its bound proof supports at z < 2^124 (2^28 at z < 2^123)
 static const u64 COLACC_FOLD_MAX_D = 1ull << 27;
 // The arithmetic kind of the kernels that reduce variable x variable column sums: the 128-bit forms; column accumulators with the
-// one-word Barrett block (mad); column accumulators with the folded block (mad and fold).  A plain bool is the plan's small_moduli.
+// one-word Barrett block (mad); column accumulators with the folded block (mad and fold).  A plain bool is the plan's small_moduli,
+// hence the Barrett kind; no caller relies on that conversion any more: the library passes its plans, and tests/lazy_inputs builds an
+// Arith from the plan or from its option fd= and prints the kind that ran (DESIGN.md section 5a lists who holds which kind).
 struct Arith {
     bool mad, fold;
     Arith(bool small_moduli, bool fold_moduli = false) : mad(small_moduli), fold(small_moduli && fold_moduli) {}

@@ -1152,6 +1152,16 @@ int piehip_get_reduction(piehip_handle h, uint32_t *kind)
     *kind = h->plan.fold_moduli ? 2u : h->plan.small_moduli ? 1u : 0u;
     return PIEHIP_OK;
 }
+int piehip_get_level_reduction(piehip_handle h, uint32_t Lc, uint32_t *kind)
+{
+    if (!h) return fail(PIEHIP_EINVAL, "null handle");
+    if (!kind) return fail(PIEHIP_EINVAL, "null out");
+    if (Lc < 1 || Lc > h->hp.L) return fail(PIEHIP_EINVAL, "get_level_reduction: Lc must be between 1 and L");
+    if (Lc < h->hp.L && !h->levels.count(Lc)) return fail(PIEHIP_ESTATE, "get_level_reduction: no chain schedule has named this level yet");
+    const NttPlan &pl = Lc == h->hp.L ? h->plan : h->levels.at(Lc)->plan;
+    *kind = pl.fold_moduli ? 2u : pl.small_moduli ? 1u : 0u;
+    return PIEHIP_OK;
+}
 int piehip_get_result_relin(piehip_handle h, int *on)
 {
     NEED_RO(h);

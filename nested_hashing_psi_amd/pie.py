@@ -333,10 +333,14 @@ class PieContext:
         _check(lib().piehip_get_transform_slots(self._h, C.byref(n), C.byref(d)))
         return int(n.value), int(d.value)
 
-    def reduction(self):
+    def reduction(self, level=None):
         """how the context reduces column sums (piehip_get_reduction): "wide" (128-bit, two-word Barrett), "barrett" (column accumulators,
-        one-word Barrett) or "fold" (column accumulators folded with d: every modulus 2^60 - d, d < 2^27)"""
+        one-word Barrett) or "fold" (column accumulators folded with d: every modulus 2^60 - d, d < 2^27).  level: the level context of
+        that many limbs (piehip_get_level_reduction; L is the context itself), which a chain schedule must have named"""
         k = C.c_uint32()
+        if level is not None:
+            _check(lib().piehip_get_level_reduction(self._h, int(level), C.byref(k)))
+            return ("wide", "barrett", "fold")[k.value]
         _check(lib().piehip_get_reduction(self._h, C.byref(k)))
         return ("wide", "barrett", "fold")[k.value]
 

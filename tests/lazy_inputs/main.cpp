@@ -10,6 +10,9 @@
 // DIR/out_<name>.u64: GUARD words, the array, GUARD words, everything pre-filled with FILL so that guards and places a mode does not
 // write can be told from written ones (FILL has its top bit set: no residue below 2^63 equals it).  DIR/out_sigma_inv.u64 is the
 // handle's lane-order map, one word per position.  The line "plan ..." says what the context decided.
+// fd= picks the reduction kind of the kernels that have two (kernels.hpp: Arith) -- scale_round, expand_both, ntt16_tensor: absent, the
+// plan's; fd=0 the Barrett kernels, valid on every small_moduli context; fd=1 the folded ones, refused where the plan has no
+// fold_moduli.  Those ops print "route ... reduction=wide|barrett|fold": the kind that ran.
 // Exit status: 0 ran; 2 usage, or a shape the launcher refuses; 3 a HIP error the runtime reported.
 #include <map>
 #include <string>
@@ -136,9 +139,9 @@ int main(int argc, char **argv)
     const u32 *sigma_inv = h->d_sigma_inv;
     hipStream_t st = h->stream;
     const bool sm = pl.small_moduli;
-    printf("plan lane_order=%d fold=%d lane_kp=%u lane_T=%u small_moduli=%d fused_tensor=%d d01_eval_q=%d result_eval_q=%d xq_reuse=%d x_direct=%d "
+    printf("plan lane_order=%d fold=%d lane_kp=%u lane_T=%u small_moduli=%d fold_moduli=%d fused_tensor=%d d01_eval_q=%d result_eval_q=%d xq_reuse=%d x_direct=%d "
            "digits_with_d01=%d digit_lift_lane=%d digit_lift_std=%d\n",
-           (int)pl.lane_order, (int)pl.fold, pl.lane_kp, pl.lane_T, (int)sm, (int)pl.fused_tensor, (int)pl.d01_eval_q, (int)pl.result_eval_q,
+           (int)pl.lane_order, (int)pl.fold, pl.lane_kp, pl.lane_T, (int)sm, (int)pl.fold_moduli, (int)pl.fused_tensor, (int)pl.d01_eval_q, (int)pl.result_eval_q,
            (int)pl.xq_reuse, (int)pl.x_direct, (int)pl.digits_with_d01, (int)pl.digit_lift_lane, (int)pl.digit_lift_std);
     {
         std::vector<u32> m32(N);
@@ -148,6 +151,11 @@ int main(int argc, char **argv)
     const size_t LN = (size_t)L * N, MN = (size_t)M * N;
     const bool fold = opt("fold") != 0;
     if (fold && !pl.fold) refuse("fold on a ring whose transforms are not folded");
+    // the reduction kind of the ops that have two: the plan's unless fd= says otherwise
+    const bool fd = g_opt.count("fd") ? opt("fd") != 0 : pl.fold_moduli;
+    if (fd && !pl.fold_moduli) refuse("fd=1 on a context whose moduli do not take the folded reduction");
+    const Arith ar(sm, fd);
+    const char *const kind = !ar.mad ? "wide" : ar.fold ? "fold" : "barrett";
 
     if (op == "relin_mac") {
         // nb rows; kp=1: out_map is the lane order of the plan (LDS tile), 0: none; key_group keys key_stride words apart; mask=1 with
@@ -182,7 +190,10 @@ int main(int argc, char **argv)
             refuse("ntt16_tensor: no fused tensor product on this context, or eval_q_L / eval_q_d2");
         const u64 *e = input("e", (size_t)nb * 4 * MN);
         Out d = output((size_t)nb * 3 * MN);
-        launch_ntt16_tensor(pl, e, d.data(), nb, M, st, eql, d2);
+        NttPlan tpl = pl;   // the launcher takes the kind from the plan
+        tpl.fold_moduli = fd;
+        printf("route reduction=%s\n", tpl.fold_moduli ? "fold" : "barrett");
+        launch_ntt16_tensor(tpl, e, d.data(), nb, M, st, eql, d2);
         LI_HIP(hipStreamSynchronize(st));
         save("d", d);
     } else if (op == "deg2_finish") {
@@ -200,7 +211,8 @@ int main(int argc, char **argv)
         if (!nb || (p01 && !(sm && c2 == p2)) || (p2 && !p01)) refuse("scale_round: p_only01 / p_only2 / fold_comp2");
         const u64 *d = input("d", (size_t)nb * 3 * MN);
         Out o01 = output((size_t)nb * 2 * LN), o2 = output((size_t)nb * LN);
-        launch_scale_round(dc, N, L, d, nb, o01.data(), 2 * LN, o2.data(), LN, st, sm, fold, c2, p01, p2);
+        printf("route reduction=%s\n", kind);
+        launch_scale_round(dc, N, L, d, nb, o01.data(), 2 * LN, o2.data(), LN, st, ar, fold, c2, p01, p2);
         LI_HIP(hipStreamSynchronize(st));
         save("out01", o01);
         save("out2", o2);
@@ -209,7 +221,9 @@ int main(int argc, char **argv)
         if (!no) refuse("n_outer");
         const u64 *x = input("x", (size_t)no * 2 * LN), *y = input("y", (size_t)no * 2 * LN);
         Out out = output((size_t)no * 4 * MN);
-        launch_expand_both(dc, N, L, x, 2 * LN, y, 2 * LN, LN, no, out.data(), st, sm, fold, opt("skip_q") != 0);
+        printf("route reduction=%s\n", kind);
+        if (!launch_expand_both(dc, N, L, x, 2 * LN, y, 2 * LN, LN, no, out.data(), st, ar, fold, opt("skip_q") != 0))
+            refuse("expand_both: a combination the launcher is not built for");
         LI_HIP(hipStreamSynchronize(st));
         save("out", out);
     } else if (op == "digits") {

@@ -26,9 +26,64 @@ def q_last_wide(N, L):
     return split(uniform(N, L - 1, 1 << 45) + uniform(N, 1) + uniform(N, L + 1, 1 << 55), L)
 
 
+FOLD_MAX_D = 1 << 27   # csrc/kernels.hpp: COLACC_FOLD_MAX_D
+FOLD_BOUND = (1 << 60) - FOLD_MAX_D
+
+
+def reduction_kind(q, p):
+    """the kind a context of these moduli must select, from the rule itself (piehip.h: piehip_get_reduction): "wide" unless every Q
+    and P modulus lies in (2^59, 2^60); then "fold" if every one is 2^60 - d with d < 2^27, "barrett" otherwise"""
+    ms = [int(v) for v in q] + [int(v) for v in p]
+    if not all((1 << 59) < m < (1 << 60) for m in ms):
+        return "wide"
+    return "fold" if all((1 << 60) - m < FOLD_MAX_D for m in ms) else "barrett"
+
+
+def level_chain(q, p, Lc):
+    """the moduli of the level context of Lc limbs (piehip_set_chain_schedule: HostParams::init on the parent's q and p with L = Lc):
+    q_0 .. q_{Lc-1} and p_0 .. p_Lc -- a prefix of each side, so the level drops q_Lc .. q_{L-1} and p_{Lc+1} .. p_L"""
+    return q[:Lc], p[:Lc + 1]
+
+
+def fold_edge(N, L):
+    """(q, p): the 2L + 1 smallest primes = 1 (mod 2N) above 2^60 - 2^27, ascending -- the folded kind with every d just under the
+    selection bound (d in (2^26, 2^27) for 15 primes at N = 8192, 16384, 32768)"""
+    return split(prime_above(N, FOLD_BOUND, 2 * L + 1), L)
+
+
+def barrett_60(N, L):
+    """(q, p): the 2L + 1 largest such primes below 2^60 - 2^27, descending -- the Barrett kind on a chain otherwise shaped like a
+    default one (d in (2^27, 2^28) for 15 primes at those N)"""
+    return uniform_chain(N, L, FOLD_BOUND)
+
+
+def over_at(N, L, where):
+    """(q, p): the default chain with ONE modulus replaced by barrett_60's first prime, so the context is of the Barrett kind.  A
+    level of Lc limbs keeps q_0 .. q_{Lc-1} and p_0 .. p_Lc (level_chain), hence
+      last_q_over  q_{L-1}: every level Lc < L drops it and folds
+      last_p_over  p_L:     likewise
+      q4_over      q_4 (L >= 6): the level of 5 limbs keeps it and is of the Barrett kind, the levels of 4 and fewer fold"""
+    chain = uniform(N, 2 * L + 1)
+    over = uniform(N, 1, FOLD_BOUND)[0]
+    at = {"last_q_over": L - 1, "last_p_over": 2 * L, "q4_over": 4}[where]
+    assert at < 2 * L + 1 and (where != "q4_over" or L >= 6)
+    chain[at] = over
+    return split(chain, L)
+
+
 def chain_by_name(N, L, name):
-    """named_chain, and q_last_wide under its own name"""
-    return q_last_wide(N, L) if name == "q_last_wide" else named_chain(N, L, name)
+    """named_chain, and under their own names the chains that are not in NAMED: q_last_wide; fold_edge and barrett_60 on either
+    side of the folded reduction's selection bound; last_q_over, last_p_over and q4_over (over_at), whose levels differ in kind
+    from their parent"""
+    if name == "q_last_wide":
+        return q_last_wide(N, L)
+    if name == "fold_edge":
+        return fold_edge(N, L)
+    if name == "barrett_60":
+        return barrett_60(N, L)
+    if name in ("last_q_over", "last_p_over", "q4_over"):
+        return over_at(N, L, name)
+    return named_chain(N, L, name)
 
 
 def uniform(N, count, below=1 << 60):

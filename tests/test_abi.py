@@ -202,6 +202,16 @@ def test_rccl_entry_points_check_their_arguments(built):
     assert L.piehip_rccl_wait(None, 10) == -1 and L.piehip_rccl_abort(None) == -1 and L.piehip_rccl_agree(None, 1, C.byref(ok), 10) == -1
 
 
+def test_reduction_getters_check_their_arguments(built):
+    """piehip_get_reduction and piehip_get_level_reduction refuse a null handle before they look at anything else (what they report
+    on a handle: tests/test_gpu_coeff_columns.py, tests/test_gpu_chain_drop_columns.py)"""
+    import ctypes as C
+    from nested_hashing_psi_amd import _lib
+    k = C.c_uint32(7)
+    assert _lib.lib().piehip_get_reduction(None, C.byref(k)) == -1 and _lib.lib().piehip_get_level_reduction(None, 1, C.byref(k)) == -1
+    assert k.value == 7 and b"null handle" in _lib.lib().piehip_last_error()
+
+
 def _slice(L, b, G, r):
     import ctypes as C
     lo, hi = C.c_uint32(), C.c_uint32()

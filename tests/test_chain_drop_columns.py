@@ -38,7 +38,11 @@ RUN = ([(None, 16384, L, Lc) for L, Lc in [(2, 1), (3, 2), (4, 3), (4, 2), (5, 4
        + [(None, 32768, 3, 2), (1 << 50, 16384, 3, 2), (1 << 50, 32768, 5, 3)]
        + [(None, 2048, 4, 2), (None, 4096, 4, 3), (None, 8192, 4, 3), (None, 65536, 3, 2), (1 << 61, 4096, 3, 2)]
        + [(c, 4096, 3, Lc) for c in ("q0_wide", "q_narrow_p_wide", "barrett_edges", "q_last_wide") for Lc in (2, 1)]
-       + [("one_p_61", 16384, 3, 2)])
+       + [("one_p_61", 16384, 3, 2)]
+       # both kinds of the column-sum reduction on the folded rings (param_chains: barrett_60, fold_edge), and parents of the Barrett kind
+       # whose level folds (last_q_over, last_p_over)
+       + [("barrett_60", 16384, 3, 2), ("barrett_60", 16384, 4, 2), ("barrett_60", 16384, 5, 2), ("barrett_60", 32768, 3, 2)]
+       + [("fold_edge", 16384, 3, 2), ("fold_edge", 16384, 5, 2), ("last_q_over", 16384, 3, 2), ("last_p_over", 16384, 3, 2)])
 CASES = MOD_REDUCE + RUN
 
 

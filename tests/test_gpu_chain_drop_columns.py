@@ -11,6 +11,10 @@ ties and windows behind the drop, on both members of every folded pair (ccol.til
 run() gets them as in test_run_with_crafted_index (tests/test_gpu_coeff_columns.py): database plaintexts 1, E = 1, minus = 0, so stage
 A hands the crafted index ciphertexts themselves to the chain.  The reference is chain_layer_exact (tests/test_chain_limbs.py).  No
 tolerance and no skip: a shape that cannot run fails.
+
+The conversions behind the drop exist once per kind of the column-sum reduction, and a level has a kind of its
+own: the points on barrett_60, fold_edge, last_q_over and last_p_over (tests/param_chains.py) assert the kinds of parent and level
+(REDUCTION) from PieContext.reduction() before they compare a word.
 """
 import os
 
@@ -57,7 +61,18 @@ ROUTES = {
     ("barrett_edges", 4096, 3, 2): ("unfolded", 3, 1), ("barrett_edges", 4096, 3, 1): ("unfolded", 3, 1),
     ("q_last_wide", 4096, 3, 2): ("unfolded", 3, 1), ("q_last_wide", 4096, 3, 1): ("unfolded", 3, 1),
     ("one_p_61", 16384, 3, 2): ("unfolded", 2, 1),
+    # the Barrett kind of the column-sum reduction (expand_both_drop_kernel with and without XDROP, a non-adjacent pair,
+    # expand_both_plain_kernel<true, 2, true> behind chain_drop_kernel<true>, slices of 2^14), d just under the folded kind's bound,
+    # and a Barrett parent whose level folds: the load and the drop under the parent's constants, the conversion under the level's
+    ("barrett_60", 16384, 3, 2): ("fused", 3, 1), ("barrett_60", 16384, 4, 2): ("fused", 3, 1), ("barrett_60", 16384, 5, 2): ("folded", 3, 1),
+    ("barrett_60", 32768, 3, 2): ("fused", 2, 1),
+    ("fold_edge", 16384, 3, 2): ("fused", 3, 1), ("fold_edge", 16384, 5, 2): ("folded", 3, 1),
+    ("last_q_over", 16384, 3, 2): ("fused", 3, 1), ("last_p_over", 16384, 3, 2): ("fused", 3, 1),
 }
+# (parent, level): PieContext.reduction() and reduction(level=Lc) of the points that name a chain by its kind; every default-chain
+# point is ("fold", "fold")
+REDUCTION = {"barrett_60": ("barrett", "barrett"), "fold_edge": ("fold", "fold"), "last_q_over": ("barrett", "fold"),
+             "last_p_over": ("barrett", "fold")}
 BATCH_POINT = (None, 16384, 4, 3)     # fused; K = 2, b = 2, a batch of three
 DEG2_POINTS = [(None, 16384, 4, 3), (None, 4096, 4, 3)]
 assert set(ROUTES) | {BATCH_POINT} | set(DEG2_POINTS) <= set(CASES)   # the CPU file has checked the families of every point
@@ -156,7 +171,12 @@ def test_run_drops_crafted_accumulators(ob, pie, case):
     Lc = case[3]
     o, cc, op, queries, db, masks, evks = _setup(ob, pie, case, K, b, 1)
     want = _exact(ob, o, queries, db, masks, evks, Lc)
+    with pytest.raises(RuntimeError):
+        cc.reduction(level=Lc)                      # a level no schedule has named yet
     op.setChainLimbs(Lc)
+    if case[0] is None or case[0] in REDUCTION:
+        assert (cc.reduction(), cc.reduction(level=Lc)) == REDUCTION.get(case[0], ("fold", "fold")), "the kinds of parent and level"
+        assert cc.reduction(level=o.L) == cc.reduction()
     got = _run(cc, op)
     assert got.shape == (1, b, 2, Lc, o.N)
     assert (got == want).all()

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests.param_chains import T16, T32, named_chain, uniform_chain
+from tests.param_chains import T16, T32, chain_by_name, uniform_chain
 from tests.test_chain_limbs import chain_layer_exact, level_key, level_oracle
 from tests.test_gpu_parity import rand_limbs
 from tests.test_result_limbs import mod_reduce_exact
@@ -29,7 +29,7 @@ def _contexts(ob, pie, N, L, t, chain=None):
     if chain is None:
         q, p = None, None
     elif isinstance(chain, str):
-        q, p = named_chain(N, L, chain)
+        q, p = chain_by_name(N, L, chain)
     else:
         q, p = uniform_chain(N, L, chain)
     o = ob.Oracle(N, L, t, q, p)

@@ -75,7 +75,14 @@ POINTS = [
     (16384, 5, None, 3, (5, 3), 1, 1, "fallback"),    # a folded ring, a pair the conversion is not built for
     (16384, 4, 1 << 50, 3, (4, 3), 1, 1, "fallback"),  # a chain outside (2^59, 2^60)
     (16384, 4, "one_p_61", 3, (4, 3), 1, 1, "fallback"),  # the parent does not fold, the level does
+    # the triple (6,5,4) of expand_both_drop_xy_kernel (Y from 6 limbs, X from 5, both to 4) under the Barrett kind of the column-sum
+    # reduction, and on a chain whose level 5 is of the Barrett kind and whose level 4 folds (param_chains.over_at)
+    (16384, 6, "barrett_60", 3, (5, 4), 1, 1, "fused"),
+    (16384, 6, "q4_over", 3, (5, 4), 1, 1, "fused"),
 ]
+# PieContext.reduction() of the handle and of every level of the schedule, for the points that name a chain by its kind; every
+# default-chain point is "fold" throughout
+REDUCTION = {"barrett_60": {6: "barrett", 5: "barrett", 4: "barrett"}, "q4_over": {6: "barrett", 5: "barrett", 4: "fold"}}
 
 
 @pytest.mark.parametrize("N,L,chain,K,sched,b,nq,route", POINTS,
@@ -94,6 +101,9 @@ def test_run_with_a_schedule(ob, pie, N, L, chain, K, sched, b, nq, route):
     want = _exact(ob, o, queries, db, masks, evks, sched)
     op.setChainSchedule(sched)
     assert op.chainSchedule() == list(sched) and op.chainLimbs() == last_level(sched, K)
+    if chain is None or chain in REDUCTION:
+        for lv in (L,) + tuple(sched):
+            assert cc.reduction(level=lv) == ("fold" if chain is None else REDUCTION[chain][lv]), "the kind of level %d" % lv
     for streams in ((1, 2) if b >= 2 else (1,)):
         cc.set_run_streams(streams)
         got = _run(op)
@@ -279,7 +289,13 @@ def test_refusals_leave_the_handle_usable(ob, pie):
     assert set_(*[4] * 8) == pie.EINVAL        # n = 8
     assert lib().piehip_set_chain_schedule(cc._h, None, 2) == pie.EINVAL
     assert lib().piehip_get_chain_schedule(cc._h, buf, 7, C.byref(n)) == 0 and (n.value, buf[0]) == (1, L)
+    kind = C.c_uint32()
+    assert lib().piehip_get_level_reduction(cc._h, 3, C.byref(kind)) == pie.ESTATE     # a level no schedule has named
     assert set_(4, 3) == 0
+    # a level's kind: the levels the schedule has built and the handle itself; not one it has not built, nor a count outside 1 .. L
+    assert [lib().piehip_get_level_reduction(cc._h, lv, C.byref(kind)) for lv in (0, 2, L + 1)] == [pie.EINVAL, pie.ESTATE, pie.EINVAL]
+    assert lib().piehip_get_level_reduction(cc._h, 3, None) == pie.EINVAL
+    assert (cc.reduction(level=3), cc.reduction(level=L), cc.reduction()) == ("fold",) * 3
     assert lib().piehip_get_chain_schedule(cc._h, buf, 1, C.byref(n)) == pie.EINVAL    # no room
     assert lib().piehip_get_chain_schedule(cc._h, buf, 2, C.byref(n)) == 0 and (n.value, buf[0], buf[1]) == (2, 4, 3)
     assert set_(L) == 0

@@ -7,8 +7,10 @@ polynomial whose columns are digit extremes, rounding ties and digit-lift window
 and that the tie columns sit where the oracle's fixed-point rounding departs from exact rounding.
 
 The points are the smallest shapes that own each route of ntt_plan_decide (kernels_ntt.hip); ROUTES lists, per point, what the plan
-decides there, and the tests assert from cc.profile() the classes that tell the routes apart.  No tolerance and no skip: a shape that
-cannot run fails.
+decides there, and the tests assert from cc.profile() the classes that tell the routes apart.  REDUCTION lists, per point, the kind
+of the column-sum reduction its context selects; every context is asked for it before it computes, so each
+point says which of the two instantiations of the conversions, scale-and-round and the fused tensor product it holds.  No tolerance
+and no skip: a shape that cannot run fails.
 """
 import functools
 
@@ -22,10 +24,15 @@ from tests.test_gpu_parity import rand_limbs
 
 pytestmark = pytest.mark.gpu
 
-# (chain, N, L): None is the default chain, an int the uniform chain below it, a string a chain of param_chains.NAMED
+# (chain, N, L): None is the default chain, an int the uniform chain below it, a string a chain of param_chains.chain_by_name
+# barrett_60 and fold_edge: the fused rings under the Barrett kind of the column-sum reduction and under the folded kind with d just
+# below its bound -- 8192 the smallest fused ring, not folded; 16384 at L = 4, 6 (the 124-bit form of
+# scale-and-round's reduction) and 7 (its 128-bit fallback beside column-accumulator conversions); 32768 on slices of 2^14
 POINTS = ([(None, N, L) for N, L in [(256, 2), (4096, 3), (8192, 2), (8192, 7), (16384, 4), (16384, 7), (32768, 2), (32768, 7), (65536, 3)]]
           + [(1 << 50, 16384, 7), (1 << 50, 32768, 5), (1 << 61, 4096, 3), (1 << 61, 32768, 4)]
-          + [(name, 4096, 3) for name in pc.NAMED] + [("q0_wide", 16384, 5)])
+          + [(name, 4096, 3) for name in pc.NAMED] + [("q0_wide", 16384, 5)]
+          + [("barrett_60", 8192, 2), ("barrett_60", 16384, 4), ("barrett_60", 16384, 6), ("barrett_60", 16384, 7), ("barrett_60", 32768, 2)]
+          + [("fold_edge", 16384, 4), ("fold_edge", 16384, 6), ("fold_edge", 32768, 2)])
 ONE_LIMB = (None, 256, 1)
 
 
@@ -51,7 +58,25 @@ ROUTES = {
     ("q0_wide", 4096, 3): (True, False, False, False), ("q_narrow_p_wide", 4096, 3): (True, False, False, False),
     ("one_p_61", 4096, 3): (False, False, True, True), ("barrett_edges", 4096, 3): (True, False, False, False),
     ("q0_wide", 16384, 5): (True, False, True, False),
+    ("barrett_60", 8192, 2): (True, True, False, False),
+    ("barrett_60", 16384, 4): (True, True, False, False), ("barrett_60", 16384, 6): (True, True, False, False),
+    ("barrett_60", 16384, 7): (True, True, False, False), ("barrett_60", 32768, 2): (True, True, False, True),
+    ("fold_edge", 16384, 4): (True, True, False, False), ("fold_edge", 16384, 6): (True, True, False, False),
+    ("fold_edge", 32768, 2): (True, True, False, True),
 }
+# How each point's context reduces its variable x variable column sums (PieContext.reduction()), written out like ROUTES: "fold" (every
+# Q and P modulus 2^60 - d, d < 2^27), "barrett" (every one in (2^59, 2^60), some d >= 2^27), "wide" (some modulus outside)
+REDUCTION = {
+    (None, 256, 2): "fold", (None, 256, 1): "fold", (None, 4096, 3): "fold", (None, 8192, 2): "fold", (None, 8192, 7): "fold",
+    (None, 16384, 4): "fold", (None, 16384, 7): "fold", (None, 32768, 2): "fold", (None, 32768, 7): "fold", (None, 65536, 3): "fold",
+    (1 << 50, 16384, 7): "wide", (1 << 50, 32768, 5): "wide", (1 << 61, 4096, 3): "wide", (1 << 61, 32768, 4): "wide",
+    ("q0_wide", 4096, 3): "wide", ("q_narrow_p_wide", 4096, 3): "wide", ("one_p_61", 4096, 3): "wide", ("barrett_edges", 4096, 3): "barrett",
+    ("q0_wide", 16384, 5): "wide",
+    ("barrett_60", 8192, 2): "barrett", ("barrett_60", 16384, 4): "barrett", ("barrett_60", 16384, 6): "barrett",
+    ("barrett_60", 16384, 7): "barrett", ("barrett_60", 32768, 2): "barrett",
+    ("fold_edge", 16384, 4): "fold", ("fold_edge", 16384, 6): "fold", ("fold_edge", 32768, 2): "fold",
+}
+assert set(REDUCTION) == set(ROUTES) == set(POINTS) | {ONE_LIMB}
 
 
 def _pid(point):
@@ -76,13 +101,14 @@ def _oracle(point, t=T32):
     chain, N, L = point
     if chain is None:
         return ob.Oracle(N, L, t)
-    q, p = pc.uniform_chain(N, L, chain) if isinstance(chain, int) else pc.named_chain(N, L, chain)
+    q, p = pc.uniform_chain(N, L, chain) if isinstance(chain, int) else pc.chain_by_name(N, L, chain)
     return ob.Oracle(N, L, t, q, p)
 
 
-def _context(pie, o):
+def _context(pie, o, point):
     cc = pie.PieContext(o.N, o.L, o.t, o.q, o.p)
     assert (cc.moduli == o.moduli).all()
+    assert cc.reduction() == REDUCTION[point], "the reduction kind of %s" % _pid(point)
     return cc
 
 
@@ -104,7 +130,7 @@ def test_base_convert(pie, point, t, kind):
     o = _oracle(point, t)
     N = o.N
     rng = np.random.default_rng(N + 7 * o.L + kind)
-    cc = _context(pie, o)
+    cc = _context(pie, o, point)
     if kind == 2:
         fam = ccol.qp_families(o, rng)
         x = np.stack([ccol.tile(fam, N, rng) for _ in range(3)])
@@ -138,7 +164,7 @@ def test_eval_mult(pie, point):
     fam = ccol.q_families(o)
     a, b = _crafted_ct(o, fam, rng), _crafted_ct(o, fam, rng)
     d_ab, d_ba = o.mul_tensor(a, b), o.mul_tensor(b, a)
-    cc = _context(pie, o)
+    cc = _context(pie, o, point)
     got, prof = _profiled(cc, lambda: cc.EvalMult(a, b, relin=False))
     assert (got == d_ab).all()
     assert ("tensor_ntt_inv" in prof) == fused and ("tensor" in prof) == (not fused)
@@ -170,7 +196,7 @@ def test_automorphism_lifts_windows(pie, point, g_name):
     c = np.stack([rand_limbs(rng, o.q, (), N), ccol.ntt_q(o, ccol.sigma(w, pow(g, -1, 2 * N), qs))])
     rk = rand_limbs(rng, o.q, (L, 2), N)
     want = o.automorph(c, g, rk)
-    cc = _context(pie, o)
+    cc = _context(pie, o, point)
     got, prof = _profiled(cc, lambda: cc.EvalAutomorphism(c, g, rk))
     cc.close()
     assert (got == want).all()
@@ -195,7 +221,7 @@ def test_relin_lifts_crafted_d2(pie, point):
         assert tuple(int(v) for v in d2[:, n]) == targets[n % len(targets)]
     evk = rand_limbs(rng, o.q, (o.L, 2), o.N)
     want = o.relin(d, evk)
-    cc = _context(pie, o)
+    cc = _context(pie, o, point)
     cc.load_relin_key(evk)
     got, prof = _profiled(cc, lambda: cc.EvalMult(a, b, relin=True))
     cc.close()
@@ -224,7 +250,7 @@ def test_run_with_crafted_index(pie, point):
     # the product's operands are the index ciphertexts: asserted from the oracle
     prod = o.mul(crafted[0, 0], crafted[1, 0], evk)
     assert (want[1] == np.stack([o.mul_plain(prod, masks[bn]) for bn in range(b)])).all()
-    cc = _context(pie, o)
+    cc = _context(pie, o, point)
     cc.load_relin_key(evk)
     op = pie.BatchedFHEHIPPIE(cc, vectorizedHCT=db, preCalcRandomMask=masks)
     for queues in (1, 2):

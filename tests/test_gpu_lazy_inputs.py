@@ -13,6 +13,13 @@ give back the first operand exactly: y0 + y1 = 2u + 4q, u < 4q; < 4q behind a fo
 mode does not write untouched.  No skip and no tolerance: a shape the program refuses fails.  After a status that is neither 0 nor
 2, or a time limit, no further case starts the program.
 
+The kernels that reduce a variable x variable column sum outside stage A exist twice (kernels.hpp: Arith): with
+the one-word Barrett block and, *_fd_kernel, with the folded block.  The program takes the kind from the plan or from fd= (fd=0: the
+Barrett kernels, valid on every context with column accumulators), so the default chain's inputs and expected outputs serve both.
+Every such case names its kind and asserts it: plan["fold_moduli"] is the context's decision, "reduction" on the route line the
+kind that ran (_kind_opts, _check_kind).  KIND_POINTS lists the (chain, N, L) they use: tests/test_reduction_kinds.py checks on the
+CPU that each chain selects the kind claimed here.
+
 launch_digits with `fold` applies the outer stage on its STORE side only: it lifts canonical coefficients (the centred lift is
 defined on the residue, and scale-and-round hands component 2 over canonical), so its case feeds it every value canonical and
 checks the fold_store side.
@@ -44,8 +51,30 @@ def _oracle(chain, N, L):
     from oracle import binding as ob
     if chain == "default":
         return ob.Oracle(N, L, T32)
-    q, p = pc.uniform_chain(N, L, chain) if isinstance(chain, int) else pc.named_chain(N, L, chain)
+    q, p = pc.uniform_chain(N, L, chain) if isinstance(chain, int) else pc.chain_by_name(N, L, chain)
     return ob.Oracle(N, L, T32, q, p)
+
+
+# the kind the plan of each chain of the two-kind cases selects (asserted from the plan line)
+PLAN_KIND = {"default": "fold", "fold_edge": "fold", "barrett_edges": "barrett"}
+
+
+def _kind_opts(chain, kind):
+    """the program's option for a case of `kind` on `chain`: none where the plan selects that kind itself, fd=0 for the Barrett
+    kernels on a chain whose plan folds"""
+    assert kind in ("barrett", "fold") and (kind == PLAN_KIND[chain] or kind == "barrett")
+    return {} if kind == PLAN_KIND[chain] else {"fd": 0}
+
+
+def _kind_id(chain, kind, what):
+    """the id of a two-kind case: the plan's kind on the default chain keeps the id the case had when there was one kind; the
+    Barrett kernels on the default chain add -barrett, another chain adds its name (its plan's kind: PLAN_KIND)"""
+    return what if (chain, kind) == ("default", "fold") else "%s-%s" % (what, "barrett" if chain == "default" else chain)
+
+
+def _check_kind(plan, chain, kind):
+    assert plan["small_moduli"] == 1 and plan["fold_moduli"] == (PLAN_KIND[chain] == "fold"), "the plan's kind on %s" % chain
+    assert plan["reduction"] == kind, "the kind that ran"
 
 
 def _mods(o):
@@ -237,10 +266,11 @@ def test_relin_mac_128_bit_path_at_50_bits(kp, mask):
 
 
 def test_a_shape_the_launcher_refuses_is_status_2():
-    """the own-limb term off the column-accumulator path, a folded launch on a ring that is not folded, an input file of another size:
-    the program says so with status 2 and launches nothing (every case of this file fails on such a status)"""
+    """the own-limb term off the column-accumulator path, a folded launch on a ring that is not folded, an input file of another size,
+    the folded reduction on a context whose moduli do not take it: the program says so with status 2 and launches nothing (every case of this file fails on such a status)"""
     for chain, op, inputs, opts in [(1 << 61, "relin_mac", {}, {"eq": 1}), ("default", "digits", {}, {"fold": 1}),
-                                    ("default", "tensor", {"e": np.zeros(8, dtype=np.uint64)}, {"nb": 1})]:
+                                    ("default", "tensor", {"e": np.zeros(8, dtype=np.uint64)}, {"nb": 1}),
+                                    ("barrett_edges", "scale_round", {}, {"fd": 1}), (1 << 50, "expand_both", {}, {"fd": 1})]:
         with pytest.raises(AssertionError, match="status 2"):
             _run(op, _oracle(chain, 4096, 2), inputs, {}, **opts)
     assert not _stopped
@@ -262,11 +292,11 @@ def test_tensor(chain, mad):
 
 
 # ---- launch_ntt16_tensor ---------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=2)
-def _fused_tensor_case(N):
+@functools.lru_cache(maxsize=4)
+def _fused_tensor_case(chain, N):
     """e[nb][4][M][N] over [0, 8q) in lane order and the COEFFICIENT form of its tensor product, d[nb][3][M][N]"""
     L, nb = 2, 2
-    o = _oracle("default", N, L)
+    o = _oracle(chain, N, L)
     qs, ps = _mods(o)
     e = lz.lazy_array(qs + ps, lambda q: 8 * q, (nb, 4), N, np.random.default_rng(N + 3))
     sl = N // 2 if N == 16384 else N
@@ -278,17 +308,26 @@ def _fused_tensor_case(N):
     return o, e, d
 
 
-@pytest.mark.parametrize("mode", ["all", "eval_q_L", "eval_q_d2"])
+# (chain, kind, mode): both kinds on the default chain in every mode; d just under the selection bound, and the edges of the one-word
+# Barrett (mu near 2^64 and near 2^63) on a chain whose plan selects the Barrett kind itself, with every limb written
+TENSOR_CASES = ([("default", kind, mode) for kind in ("barrett", "fold") for mode in ("all", "eval_q_L", "eval_q_d2")]
+                + [("fold_edge", "fold", "all"), ("barrett_edges", "barrett", "all")])
+
+
+@pytest.mark.parametrize("chain,kind,mode", TENSOR_CASES, ids=[_kind_id(c, k, m) for c, k, m in TENSOR_CASES])
 @pytest.mark.parametrize("N", [8192, 16384])
-def test_ntt16_tensor(N, mode):
-    """the TENSOR load phase of ntt16_kernel.h: N = 8192 one slice per limb (canonical coefficients out), N = 16384 folded (pairs in
-    [0, 4q), compared after the outer stage).  eval_q_L = L leaves out the Q limbs of d0, d1, eval_q_d2 those of d2 as well: their
-    places keep the fill pattern"""
-    o, e, d = _fused_tensor_case(N)
+def test_ntt16_tensor(N, chain, kind, mode):
+    """the TENSOR load phase of ntt16_kernel.h (tensor_load) -- kind barrett: the TENSOR instantiation of ntt16_kernel_t, kind fold:
+    ntt16_tensor_fd_kernel_t --: N = 8192 one slice per limb (canonical coefficients out), N = 16384 folded (pairs in [0, 4q),
+    compared after the outer stage).  eval_q_L = L leaves out the Q limbs of d0, d1, eval_q_d2 those of d2 as well: their places
+    keep the fill pattern"""
+    o, e, d = _fused_tensor_case(chain, N)
     L, M, nb = o.L, o.M, e.shape[0]
     qs, ps = _mods(o)
     opts = {"all": {}, "eval_q_L": {"eval_q_L": L}, "eval_q_d2": {"eval_q_L": L, "eval_q_d2": 1}}[mode]
+    opts.update(_kind_opts(chain, kind))
     got, plan, _ = _run("ntt16_tensor", o, {"e": e}, {"d": (nb, 3, M, N)}, nb=nb, **opts)
+    _check_kind(plan, chain, kind)
     assert plan["fused_tensor"] == 1 and plan["fold"] == (N == 16384)
     _lane(o, plan, got)
     out = got["d"]
@@ -329,27 +368,46 @@ SR_MODES = {"fold": {}, "fold_comp2": {"fold_comp2": 1}, "p_only01": {"p_only01"
             "p_only012": {"fold_comp2": 1, "p_only01": 1, "p_only2": 1}}
 
 
-@pytest.mark.parametrize("mode", sorted(SR_MODES))
-@pytest.mark.parametrize("L", [2, 7])
-def test_scale_round_folded(L, mode):
-    """scale_round_kernel<true, L, true, P01, P2>: d[3][M][N] over [0, 4q) with the outer stage pending; the Q limbs a P-only component
-    does not read hold a poison pattern.  Components 0, 1 (and 2 with fold_comp2) leave through fold_store -- their first operand in
-    [0, 4q) (lz: L <= 5, no fold_comp2), canonical otherwise --, component 2 canonical without it"""
+# (chain, kind, L, mode).  L = 2 and 7 (the 128-bit fallback) in every mode, L = 5 (the last lazy output) and L = 6 (the 124-bit form
+# of the reduction) in the modes fold and p_only01; both kinds on the default chain, and the folded kind with every d just under
+# the selection bound at L = 2 and L = 6
+SR_LM = [(L, m) for L in (2, 7) for m in sorted(SR_MODES)] + [(L, m) for L in (5, 6) for m in ("fold", "p_only01")]
+SR_CASES = ([("default", kind, L, m) for kind in ("barrett", "fold") for L, m in SR_LM]
+            + [("fold_edge", "fold", L, m) for L, m in SR_LM if L in (2, 6)])
+
+
+@functools.lru_cache(maxsize=None)
+def _scale_round_case(chain, L, p01, p2):
+    """(o, d, want): d[1][3][M][N] over [0, 4q) with the outer stage pending, poison in the Q limbs a P-only component does not
+    read, and the three components scaled and rounded by the oracle.  Shared by the kinds and by the modes that read the same limbs"""
     N = 16384
-    o = _oracle("default", N, L)
+    o = _oracle(chain, N, L)
     qs, ps = _mods(o)
-    opts = SR_MODES[mode]
     d = lz.lazy_array(qs + ps, lambda q: 4 * q, (1, 3), N, np.random.default_rng(N + L))
-    p_only = [bool(opts.get("p_only01"))] * 2 + [bool(opts.get("p_only2"))]
     want = []
-    for c in range(3):
+    for c, p_only in enumerate((p01, p01, p2)):
         x = lz.fold_load_poly(o, d[0, c])
-        if p_only[c]:
+        if p_only:
             d[0, c, :L] = FILL
             x[:L] = 0   # the own-limb term is the only place a Q limb enters (tests/test_lazy_inputs.py)
         want.append(o.scale_round_tp(x))
-    got, plan, _ = _run("scale_round", o, {"d": d}, {"out01": (1, 2, L, N), "out2": (1, L, N)}, nb=1, fold=1, **opts)
-    assert plan["fold"] == 1 and plan["small_moduli"] == 1
+    d.setflags(write=False)
+    return o, d, want
+
+
+@pytest.mark.parametrize("chain,kind,L,mode", SR_CASES, ids=[_kind_id(c, k, "%d-%s" % (L, m)) for c, k, L, m in SR_CASES])
+def test_scale_round_folded(chain, kind, L, mode):
+    """kind barrett: scale_round_kernel<true, L, true, P01, P2>, kind fold: scale_round_fd_kernel<true, L, P01, P2>.  d[3][M][N] over
+    [0, 4q) with the outer stage pending; the Q limbs a P-only component does not read hold a poison pattern.  Components 0, 1 (and
+    2 with fold_comp2) leave through fold_store -- their first operand in [0, 4q) (lz: L <= 5, no fold_comp2), canonical otherwise
+    --, component 2 canonical without it.  L = 6: colacc_red<FD, true>, the 124-bit form of either block; L = 7: reduce128 under
+    both kinds"""
+    N = 16384
+    opts = SR_MODES[mode]
+    o, d, want = _scale_round_case(chain, L, bool(opts.get("p_only01")), bool(opts.get("p_only2")))
+    got, plan, _ = _run("scale_round", o, {"d": d}, {"out01": (1, 2, L, N), "out2": (1, L, N)}, nb=1, fold=1, **opts, **_kind_opts(chain, kind))
+    _check_kind(plan, chain, kind)
+    assert plan["fold"] == 1
     lazy = L <= 5 and not opts.get("fold_comp2")
     for c in range(2):
         _check_fold_store(o, got["out01"][0, c], want[c], 0, "component %d" % c, canonical_u=not lazy)
@@ -359,24 +417,48 @@ def test_scale_round_folded(L, mode):
         assert (got["out2"][0] == want[2]).all(), "component 2"
 
 
-@pytest.mark.parametrize("skip_q", [0, 1])
-@pytest.mark.parametrize("L", [2, 7])
-def test_expand_both_folded(L, skip_q):
-    """expand_both_kernel<true, L, true, SKIPQ>: X and Y over [0, 4q) with the outer stage pending; every output limb leaves through
-    fold_store; skip_q: the Q limbs of X's slots keep the fill pattern"""
+# (chain, kind, L): L = 6 is the last crt_out on column accumulators (NS = 7 sums); at L = 7 the P -> Q lift of scale_pq takes the 128-bit
+# path while the Q -> P sums stay on accumulators
+EB_CASES = [("default", kind, L) for kind in ("barrett", "fold") for L in (2, 6, 7)] + [("fold_edge", "fold", L) for L in (2, 6)]
+
+
+@functools.lru_cache(maxsize=None)
+def _expand_both_case(chain, L):
+    """(o, x, y, wx, wy): X and Y [1][2][L][N] over [0, 4q) with the outer stage pending and their conversions by the oracle,
+    shared by the kinds and by both skip_q"""
     N = 16384
-    o = _oracle("default", N, L)
+    o = _oracle(chain, N, L)
     qs, ps = _mods(o)
     rng = np.random.default_rng(N + L + 1)
     x, y = (lz.lazy_array(qs, lambda q: 4 * q, (1, 2), N, rng) for _ in range(2))
-    got, plan, _ = _run("expand_both", o, {"x": x, "y": y}, {"out": (1, 4, o.M, N)}, n_outer=1, fold=1, skip_q=skip_q)
-    assert plan["fold"] == 1 and plan["small_moduli"] == 1
+    wx = [o.expand_q_to_qp(lz.fold_load_poly(o, x[0, c])) for c in range(2)]
+    wy = [o.scale_pq_expand(lz.fold_load_poly(o, y[0, c])) for c in range(2)]
+    for v in [x, y] + wx + wy:
+        v.setflags(write=False)
+    return o, x, y, wx, wy
+
+
+@pytest.mark.parametrize("skip_q", [0, 1])
+@pytest.mark.parametrize("chain,kind,L", EB_CASES, ids=[_kind_id(c, k, "%d" % L) for c, k, L in EB_CASES])
+def test_expand_both_folded(chain, kind, L, skip_q):
+    """kind barrett: expand_both_kernel<true, L, true, SKIPQ>, kind fold: expand_both_fd_kernel<true, L, SKIPQ>.  X and Y over [0, 4q)
+    with the outer stage pending; every output limb leaves through fold_store; skip_q: the Q limbs of X's slots keep the fill
+    pattern"""
+    N = 16384
+    o, x, y, wx, wy = _expand_both_case(chain, L)
+    got, plan, _ = _run("expand_both", o, {"x": x, "y": y}, {"out": (1, 4, o.M, N)}, n_outer=1, fold=1, skip_q=skip_q, **_kind_opts(chain, kind))
+    _check_kind(plan, chain, kind)
+    assert plan["fold"] == 1
     for c in range(2):
-        wx, wy = o.expand_q_to_qp(lz.fold_load_poly(o, x[0, c])), o.scale_pq_expand(lz.fold_load_poly(o, y[0, c]))
         first = L if skip_q else 0
         assert (got["out"][0, c, :first] == FILL).all(), "X%d: a Q limb was written" % c
-        _check_fold_store(o, got["out"][0, c, first:], wx[first:], first, "X%d" % c, canonical_u=False)
-        _check_fold_store(o, got["out"][0, 2 + c], wy, 0, "Y%d" % c, canonical_u=False)
+        _check_fold_store(o, got["out"][0, c, first:], wx[c][first:], first, "X%d" % c, canonical_u=False)
+        _check_fold_store(o, got["out"][0, 2 + c], wy[c], 0, "Y%d" % c, canonical_u=False)
+
+
+# every (chain, N, L) of the cases above that name a kind, with the kind its plan selects (tests/test_reduction_kinds.py)
+KIND_POINTS = sorted({(c, 16384, L, PLAN_KIND[c]) for c, _, L, _ in SR_CASES} | {(c, 16384, L, PLAN_KIND[c]) for c, _, L in EB_CASES}
+                     | {(c, N, 2, PLAN_KIND[c]) for c, _, _ in TENSOR_CASES for N in (8192, 16384)})
 
 
 def test_digits_folded_at_50_bits():
