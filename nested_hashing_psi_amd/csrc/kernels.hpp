@@ -80,14 +80,18 @@ struct NttPlan {
 void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli, bool fold_moduli = false);
 // q = 2^60 - d takes the folded block for d below this: the largest d its bound proof supports at z < 2^124 (2^28 at z < 2^123)
 static const u64 COLACC_FOLD_MAX_D = 1ull << 27;
-// The arithmetic kind of the kernels that reduce variable x variable column sums: the 128-bit forms; column accumulators with the
-// one-word Barrett block (mad); column accumulators with the folded block (mad and fold).  A plain bool is the plan's small_moduli,
-// hence the Barrett kind; no caller relies on that conversion any more: the library passes its plans, and tests/lazy_inputs builds an
-// Arith from the plan or from its option fd= and prints the kind that ran (DESIGN.md section 5a lists who holds which kind).
+// The arithmetic kind (ArithKind, modarith.h) a launcher runs its kernel at: every kernel that reduces variable x variable column sums
+// takes the kind as one template argument, and the launchers turn this run-time value into it (with_arith, kernels_pie.hip).  The
+// library passes its plans; tests/lazy_inputs builds an Arith from the plan or, explicitly, from its option fd=, and prints the kind
+// that ran (DESIGN.md section 5a lists who holds which kind).
+// mad, fold: the kind read as the two questions a caller may ask of it -- column accumulators at all? the folded block? --, fixed with
+// the kind by the one constructor: tests/lazy_inputs prints the kind that ran from them.  The launchers dispatch on `kind` alone.
 struct Arith {
-    bool mad, fold;
-    Arith(bool small_moduli, bool fold_moduli = false) : mad(small_moduli), fold(small_moduli && fold_moduli) {}
-    Arith(const NttPlan &pl) : mad(pl.small_moduli), fold(pl.small_moduli && pl.fold_moduli) {}
+    const ArithKind kind;
+    const bool mad, fold;
+    explicit Arith(bool small_moduli, bool fold_moduli = false)
+        : kind(!small_moduli ? ArithKind::wide : fold_moduli ? ArithKind::fold : ArithKind::barrett), mad(colacc(kind)), fold(kind == ArithKind::fold) {}
+    Arith(const NttPlan &pl) : Arith(pl.small_moduli, pl.fold_moduli) {}
 };
 // sigma, folded: as for launch_ntt.  Requires sigma <= pl.lane_order and folded <= pl.fold (the callers' wrappers mask them)
 NttRoute ntt_route(const NttPlan &pl, bool inverse, bool sigma, bool folded);
@@ -189,7 +193,7 @@ void launch_stage_a_batch(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E
 // is read at in + o*in_stride_outer + c*in_stride_inner ([L][N] limbs, canonical, nothing pending) and written to
 // out + ((o*out_polys + out_slot + c)*M)*N ([M][N] limbs): every limb, no folding (piehip_base_convert)
 // small_moduli (here and below): NttPlan::small_moduli of the context -- selects the v_mad_u64_u32 / one-word Barrett variants
-// ar: the context's arithmetic kind (Arith: the plan, or its small_moduli alone for the Barrett kind)
+// ar (here and below): the context's arithmetic kind (Arith: callers pass the plan)
 void launch_expand_q_to_qp(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t in_stride_outer,
                            size_t in_stride_inner, u32 n_outer, u64 *out, u32 out_polys, u32 out_slot, hipStream_t st,
                            Arith ar);

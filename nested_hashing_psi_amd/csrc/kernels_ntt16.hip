@@ -23,37 +23,30 @@ void ntt16_sigma_inverse_map(u32 logN, u32 s0, std::vector<u32> &map)
     for (u32 p = 0; p < N; p++) map[p] = (p / n) * n + ntt16::lane_to_std_t(p % n, n / 16);
 }
 
-template <u32 LOGNS>
-static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 num_cus, hipStream_t st, bool tensor = false, bool fd = false)
+// one launch of one instantiation: its dynamic LDS limit is raised where it first runs on a device
+template <u32 LOGNS, auto KERNEL>
+static void launch_ntt16_k(const ntt16::Args &a, u32 num_cus, hipStream_t st)
 {
     typedef ntt16::Geo<LOGNS> G;
     constexpr size_t lds = (size_t)G::LDS_WORDS * sizeof(u64);
-    static PerDeviceOnce attr[5];
-    if (attr[tensor ? (fd ? 4 : 3) : inverse ? 1 : (lift ? 2 : 0)].first_on_current_device()) {
-        if (tensor && fd)
-            (void)hipFuncSetAttribute((const void *)ntt16::ntt16_tensor_fd_kernel_t<LOGNS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        else if (tensor)
-            (void)hipFuncSetAttribute((const void *)ntt16::ntt16_kernel_t<LOGNS, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        else if (inverse)
-            (void)hipFuncSetAttribute((const void *)ntt16::ntt16_kernel_t<LOGNS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        else if (lift)
-            (void)hipFuncSetAttribute((const void *)ntt16::ntt16_kernel_t<LOGNS, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        else
-            (void)hipFuncSetAttribute((const void *)ntt16::ntt16_kernel_t<LOGNS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    static PerDeviceOnce attr;
+    if (attr.first_on_current_device()) (void)hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     // resident workgroups per CU: two of 512 threads (68 KiB of LDS, 128 VGPRs each) or one of 1024 (136 KiB); persistent beyond
     const u32 slots = (LOGNS == 13 ? 2u : 1u) * num_cus;
     const u32 grid = a.nitems < slots ? a.nitems : slots;
-    if (tensor && fd)
-        hipLaunchKernelGGL((ntt16::ntt16_tensor_fd_kernel_t<LOGNS>), dim3(grid), dim3(G::T), lds, st, a);
-    else if (tensor)
-        hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, true, false, true>), dim3(grid), dim3(G::T), lds, st, a);
-    else if (inverse)
-        hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, true>), dim3(grid), dim3(G::T), lds, st, a);
-    else if (lift)
-        hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, false, true>), dim3(grid), dim3(G::T), lds, st, a);
-    else
-        hipLaunchKernelGGL((ntt16::ntt16_kernel_t<LOGNS, false>), dim3(grid), dim3(G::T), lds, st, a);
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(G::T), lds, st, a);
+}
+// the five instantiations of a slice length: forward, forward with the digit lift, inverse, and the inverse with the tensor load phase at
+// the two column-accumulator kinds (fd: ArithKind::fold, NttPlan::fold_moduli)
+template <u32 LOGNS>
+static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 num_cus, hipStream_t st, bool tensor = false, bool fd = false)
+{
+    using ntt16::ntt16_kernel_t;
+    if (tensor && fd) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, true, false, true, ArithKind::fold>>(a, num_cus, st);
+    else if (tensor) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, true, false, true>>(a, num_cus, st);
+    else if (inverse) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, true>>(a, num_cus, st);
+    else if (lift) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, false, true>>(a, num_cus, st);
+    else launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, false>>(a, num_cus, st);
 }
 
 void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, bool sigma, hipStream_t st,

@@ -22,7 +22,8 @@ static const u32 TPB = 256;
 
 // Run-time values as template arguments.  with_u32<LO, HI>(v, f) calls f(std::integral_constant<u32, v>) for v in [LO, HI] and says
 // whether it did; with_bools(f, b...) calls f(std::bool_constant<b>...).  The callers' generic lambdas read the arguments as
-// constants (L_(), F_()) and guard with `if constexpr` whatever combination no kernel is built for.
+// constants (L_(), F_()) and guard with `if constexpr` whatever combination no kernel is built for.  with_arith(ar, f) calls
+// f(std::integral_constant<ArithKind, ar.kind>): the arithmetic kind every kernel here takes as ONE template argument (K_()).
 template <u32 LO, u32 HI, class F>
 static bool with_u32(u32 v, F &&f)
 {
@@ -43,6 +44,15 @@ static void with_bools(F &&f, bool b, Bs... rest)
 {
     if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
     else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+template <class F>
+static void with_arith(Arith ar, F &&f)
+{
+    switch (ar.kind) {
+        case ArithKind::wide: f(std::integral_constant<ArithKind, ArithKind::wide>{}); break;
+        case ArithKind::barrett: f(std::integral_constant<ArithKind, ArithKind::barrett>{}); break;
+        case ArithKind::fold: f(std::integral_constant<ArithKind, ArithKind::fold>{}); break;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -548,9 +558,11 @@ __device__ __forceinline__ void drop_limbs(const DevConsts *dc, u64 (&c)[NP][L])
 // x[L] (mod Q) -> out[M]: Q limbs copied, P limbs = centred CRT lift
 // YIN: x[] already holds the CRT digits y_i = [x_i (Q/q_i)^-1]_{q_i} (folded load with the merged constants); the Q
 // limbs of the output are then not produced
-template <u32 L, bool MAD, bool YIN, int NP, bool LZ = false, bool FD = false>
+// K (here and in every template below): the arithmetic kind (ArithKind, modarith.h).  MAD: one of the two column-accumulator kinds
+template <u32 L, ArithKind K, bool YIN, int NP, bool LZ = false>
 __device__ __forceinline__ void expand_core(const DevConsts *dc, const u64 (&x)[NP][L], u64 (&out)[NP][2 * L + 1])
 {
+    constexpr bool MAD = colacc(K);
     constexpr u32 Lp = L + 1;
     u64 y[NP][L];
     u64 fsum[NP];
@@ -579,14 +591,15 @@ __device__ __forceinline__ void expand_core(const DevConsts *dc, const u64 (&x)[
         for (u32 i = 0; i < L; i++) hat[i] = c->qhat_modp[i][j];
         const u64 prodmod = c->Q_modp[j], nq = neg_u(pj.q), n2q = neg_u(2 * pj.q);
 #pragma unroll
-        for (int p = 0; p < NP; p++) out[p][L + j] = crt_out<L, MAD, LZ, FD>(y[p], hat, (fsum[p] + FIX_HALF) >> 60, prodmod, pj, nq, n2q);
+        for (int p = 0; p < NP; p++) out[p][L + j] = crt_out<L, K, LZ>(y[p], hat, (fsum[p] + FIX_HALF) >> 60, prodmod, pj, nq, n2q);
     }
 }
 
 // x[L] (mod Q) -> out[M]: P limbs = round(P x / Q), Q limbs = centred CRT lift of that
-template <u32 L, bool MAD, bool YIN, int NP, bool LZ = false, bool FD = false>
+template <u32 L, ArithKind K, bool YIN, int NP, bool LZ = false>
 __device__ __forceinline__ void scale_pq_core(const DevConsts *dc, const u64 (&x)[NP][L], u64 (&out)[NP][2 * L + 1])
 {
+    constexpr bool MAD = colacc(K), FD = K == ArithKind::fold;
     constexpr u32 Lp = L + 1;
     u64 y[NP][L];
     u64 fsum[NP];
@@ -653,7 +666,7 @@ __device__ __forceinline__ void scale_pq_core(const DevConsts *dc, const u64 (&x
         for (u32 j = 0; j < Lp; j++) hat[j] = c->phat_modq[j][i];
         const u64 prodmod = c->P_modq[i], nq = neg_u(mi.q), n2q = neg_u(2 * mi.q);
 #pragma unroll
-        for (int p = 0; p < NP; p++) out[p][i] = crt_out<Lp, MAD, LZ, FD>(yp[p], hat, (fs2[p] + FIX_HALF) >> 60, prodmod, mi, nq, n2q);
+        for (int p = 0; p < NP; p++) out[p][i] = crt_out<Lp, K, LZ>(yp[p], hat, (fs2[p] + FIX_HALF) >> 60, prodmod, mi, nq, n2q);
     }
 }
 
@@ -669,15 +682,15 @@ enum class ExpandIn {
 };
 // One conversion of polynomial (o, c) = (by / 2, by % 2): read at in + o so + c si, written to out[o][out_polys][M][N] at slot out_slot + c
 // SKIPQ (centred lift only): leave the Q limbs of the output alone, they already hold the operand's EVALUATION form
-// FD (with MAD; NttPlan::fold_moduli): the column sums are reduced by the folded block (stage_a_common.h)
-template <bool SCALE, bool FOLD, u32 L, bool MAD, bool SKIPQ, ExpandIn IN = ExpandIn::pending, u32 LSRC = L, bool FD = false>
+// K: at ArithKind::fold (NttPlan::fold_moduli) the column sums are reduced by the folded block (stage_a_common.h)
+template <bool SCALE, bool FOLD, u32 L, ArithKind K, bool SKIPQ, ExpandIn IN = ExpandIn::pending, u32 LSRC = L>
 __device__ __forceinline__ void expand_body(const DevConsts *__restrict__ dcs, const DevConsts *__restrict__ dc, u32 N,
                                             const u64 *__restrict__ in, size_t so, size_t si, u64 *__restrict__ out, u32 out_polys,
                                             u32 out_slot, u32 by)
 {
     static_assert(IN == ExpandIn::pending || !SKIPQ, "Q limbs in place: an operand on this level's limbs, as its inverse transform left it");
-    static_assert(IN == ExpandIn::drop ? (LSRC > L && FOLD && MAD) : LSRC == L, "the drop: folded rings on the column-accumulator path");
-    static_assert(MAD || !FD, "the folded reduction: the column-accumulator path");
+    constexpr bool MAD = colacc(K);
+    static_assert(IN == ExpandIn::drop ? (LSRC > L && FOLD && MAD) : LSRC == L, "the drop: folded rings at a column-accumulator kind");
     // the residues x_i themselves are not needed: the folded load multiplies by N^-1 (Q/q_i)^-1 in one go
     constexpr bool YIN = IN == ExpandIn::pending && FOLD && (SCALE || SKIPQ);
     const u32 n = blockIdx.x * TPB + threadIdx.x;
@@ -716,9 +729,9 @@ __device__ __forceinline__ void expand_body(const DevConsts *__restrict__ dcs, c
     // folded output: every result passes through fold_store into a transform that takes [0, 8q) -- [0, 4q) will do (LZ)
     constexpr bool LZ = FOLD && MAD;
     if (SCALE)
-        scale_pq_core<L, MAD, YIN, NP, LZ, FD>(dc, x, y);
+        scale_pq_core<L, K, YIN, NP, LZ>(dc, x, y);
     else
-        expand_core<L, MAD, YIN, NP, LZ, FD>(dc, x, y);
+        expand_core<L, K, YIN, NP, LZ>(dc, x, y);
 #pragma unroll
     for (u32 a = 0; a < M; a++) {
         if (!SCALE && a < L && SKIPQ) continue;  // (NttExtra)
@@ -734,43 +747,26 @@ __device__ __forceinline__ void expand_body(const DevConsts *__restrict__ dcs, c
     }
 }
 
-// (The kernels of the folded reduction -- NttPlan::fold_moduli, FD of expand_body -- are twins named *_fd_kernel: the others keep their
-// names, parameter lists and listings.)
-template <bool SCALE, bool FOLD, u32 L, bool MAD, bool SKIPQ>
+// (The kind is a template argument of every conversion kernel: a context with NttPlan::fold_moduli runs the instantiations at ArithKind::fold.)
+template <bool SCALE, bool FOLD, u32 L, ArithKind K, bool SKIPQ>
 __global__ void __launch_bounds__(TPB) expand_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ in,
                                                      size_t so, size_t si, u64 *__restrict__ out, u32 out_polys, u32 out_slot)
 {
-    expand_body<SCALE, FOLD, L, MAD, SKIPQ>(dc, dc, N, in, so, si, out, out_polys, out_slot, blockIdx.y);
-}
-template <bool SCALE, bool FOLD, u32 L, bool SKIPQ>
-__global__ void __launch_bounds__(TPB) expand_fd_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ in,
-                                                        size_t so, size_t si, u64 *__restrict__ out, u32 out_polys, u32 out_slot)
-{
-    expand_body<SCALE, FOLD, L, true, SKIPQ, ExpandIn::pending, L, true>(dc, dc, N, in, so, si, out, out_polys, out_slot, blockIdx.y);
+    expand_body<SCALE, FOLD, L, K, SKIPQ>(dc, dc, N, in, so, si, out, out_polys, out_slot, blockIdx.y);
 }
 // Both operands of a ciphertext multiplication in one launch: rows [0, 2 n) of the grid scale operand Y (P/Q scaling, the
 // longer body: first, so that the shorter rows fill in behind it), rows [2 n, 4 n) lift operand X.  As two launches each was
 // a single round of 3.5 / 1.75 waves per SIMD with every wave in the same load - compute - store phase; together the rounds
 // interleave (12.4 + 20.6 us -> one launch).  Writes out[n][4][M][N]: X into slots 0, 1, Y into slots 2, 3.
-template <bool FOLD, u32 L, bool MAD, bool SKIPQ>
+template <bool FOLD, u32 L, ArithKind K, bool SKIPQ>
 __global__ void __launch_bounds__(TPB) expand_both_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ x, size_t sx,
                                                           const u64 *__restrict__ y, size_t sy, size_t si, u64 *__restrict__ out,
                                                           u32 n_outer)
 {
     if (blockIdx.y < 2 * n_outer)
-        expand_body<true, FOLD, L, MAD, false>(dc, dc, N, y, sy, si, out, 4, 2, blockIdx.y);
+        expand_body<true, FOLD, L, K, false>(dc, dc, N, y, sy, si, out, 4, 2, blockIdx.y);
     else
-        expand_body<false, FOLD, L, MAD, SKIPQ>(dc, dc, N, x, sx, si, out, 4, 0, blockIdx.y - 2 * n_outer);
-}
-template <bool FOLD, u32 L, bool SKIPQ>
-__global__ void __launch_bounds__(TPB) expand_both_fd_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ x, size_t sx,
-                                                             const u64 *__restrict__ y, size_t sy, size_t si, u64 *__restrict__ out,
-                                                             u32 n_outer)
-{
-    if (blockIdx.y < 2 * n_outer)
-        expand_body<true, FOLD, L, true, false, ExpandIn::pending, L, true>(dc, dc, N, y, sy, si, out, 4, 2, blockIdx.y);
-    else
-        expand_body<false, FOLD, L, true, SKIPQ, ExpandIn::pending, L, true>(dc, dc, N, x, sx, si, out, 4, 0, blockIdx.y - 2 * n_outer);
+        expand_body<false, FOLD, L, K, SKIPQ>(dc, dc, N, x, sx, si, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
 // One conversion as a launch of its own (piehip_base_convert): plain operands of a context without folding in the call, nothing in place
 static void launch_expand_common(bool scale, const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t so, size_t si, u32 n_outer, u64 *out,
@@ -778,12 +774,11 @@ static void launch_expand_common(bool scale, const DevConsts *dc, u32 N, u32 L, 
 {
     dim3 grid((N + TPB - 1) / TPB, n_outer * 2);
     with_u32<1, 7>(L, [&](auto L_) {
-        with_bools([&](auto S_, auto M_, auto FD_) {
-            if constexpr (FD_())
-                hipLaunchKernelGGL((expand_fd_kernel<S_(), false, L_(), false>), grid, dim3(TPB), 0, st, dc, N, in, so, si, out, out_polys, out_slot);
-            else
-                hipLaunchKernelGGL((expand_kernel<S_(), false, L_(), M_(), false>), grid, dim3(TPB), 0, st, dc, N, in, so, si, out, out_polys, out_slot);
-        }, scale, ar.mad && !ar.fold, ar.fold);
+        with_arith(ar, [&](auto K_) {
+            with_bools([&](auto S_) {
+                hipLaunchKernelGGL((expand_kernel<S_(), false, L_(), K_(), false>), grid, dim3(TPB), 0, st, dc, N, in, so, si, out, out_polys, out_slot);
+            }, scale);
+        });
     });
 }
 void launch_expand_q_to_qp(const DevConsts *dc, u32 N, u32 L, const u64 *in, size_t so, size_t si, u32 n_outer, u64 *out,
@@ -874,10 +869,11 @@ void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 
 // PONLY: the own-limb term d_k [t P^-1]_{q_k} is left out and d[.][k < L] is not read.  The term is the only place a Q limb enters, one
 // constant times the limb's own coefficients: it commutes with the transform of limb k, and the key-switch MAC adds it in EVALUATION
 // form (relin_mac_kernel, EQ) -- components 0 and 1 of a relinearising product.  Every column sum below only loses a term.
-// FD (with MAD; NttPlan::fold_moduli): the folded reduction block; one block for z < 2^124, so L = 6 takes it as well
-template <u32 L, bool MAD, int NP, bool PRE = false, bool PONLY = false, bool FD = false>
+// K at ArithKind::fold (NttPlan::fold_moduli): the folded reduction block; one block for z < 2^124, so L = 6 takes it as well
+template <u32 L, ArithKind K, int NP, bool PRE = false, bool PONLY = false>
 __device__ __forceinline__ void scale_round_core(const DevConsts *dc, const u64 (&d)[NP][2 * L + 1], u64 (&out)[NP][L], bool lz = false)
 {
+    constexpr bool MAD = colacc(K), FD = K == ArithKind::fold;
     constexpr u32 Lp = L + 1;
     u64 yp[NP][Lp];
     u64 fsum[NP];
@@ -941,7 +937,7 @@ __device__ __forceinline__ void scale_round_core(const DevConsts *dc, const u64 
 // FOLD: inverse outer stage on load; forward outer stage on the store of components 0 and 1 (they go to a
 // forward transform); component 2 is stored as plain coefficients (the digit kernel folds it per target modulus)
 // PONLY: this component takes its P limbs only (scale_round_core); the loads of the Q limbs and their folded-load products go with the term
-template <bool FOLD, u32 L, bool MAD, bool PONLY, bool FD = false>
+template <bool FOLD, u32 L, ArithKind K, bool PONLY>
 __device__ __forceinline__ void scale_round_comp(const DevConsts *__restrict__ dc, u32 N, u32 n, const u64 *__restrict__ pin,
                                                  u64 *__restrict__ pout, bool fold_out, bool lz)
 {
@@ -965,7 +961,7 @@ __device__ __forceinline__ void scale_round_comp(const DevConsts *__restrict__ d
             x[0][a] = pin[(size_t)a * N];
         }
     }
-    scale_round_core<L, MAD, NP, FOLD, PONLY, FD>(dc, x, y, lz);
+    scale_round_core<L, K, NP, FOLD, PONLY>(dc, x, y, lz);
 #pragma unroll
     for (u32 k = 0; k < L; k++) {
         PIE_ITER_FENCE();
@@ -981,11 +977,12 @@ __device__ __forceinline__ void scale_round_comp(const DevConsts *__restrict__ d
 }
 // P01: components 0 and 1 are the PONLY variant (a uniform branch on the component: blockIdx.y), component 2 the full one
 // P2 (with P01 and fold_comp2; NttPlan::result_eval_q): component 2 is the PONLY variant too -- a product that is not relinearised
-template <bool FOLD, u32 L, bool MAD, bool P01, bool P2, bool FD>
-__device__ __forceinline__ void scale_round_rows(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ d,
-                                                 u64 *__restrict__ out01, size_t stride01,
-                                                 u64 *__restrict__ out2, size_t stride2, u32 fold_comp2)
+template <bool FOLD, u32 L, ArithKind K, bool P01 = false, bool P2 = false>
+__global__ void __launch_bounds__(TPB) scale_round_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ d,
+                                                          u64 *__restrict__ out01, size_t stride01,
+                                                          u64 *__restrict__ out2, size_t stride2, u32 fold_comp2)
 {
+    static_assert((colacc(K) || !P01) && (P01 || !P2), "P limbs only: a column-accumulator kind, component 2 with components 0 and 1");
     const u32 n = blockIdx.x * TPB + threadIdx.x;
     if (n >= (FOLD ? N / 2 : N)) return;
     const u32 comp = blockIdx.y, bin = blockIdx.z;
@@ -994,46 +991,29 @@ __device__ __forceinline__ void scale_round_rows(const DevConsts *__restrict__ d
     u64 *pout = comp < 2 ? out01 + (size_t)bin * stride01 + (size_t)comp * L * N + n : out2 + (size_t)bin * stride2 + n;
     // d0, d1 of the key-switch path go on through fold_store into the forward transform ([0, 8q) in): [0, 4q) will do.  d2 feeds the
     // digit lift (canonical), and with fold_comp2 the three components leave the library's lane-ordered world
-    const bool lz = FOLD && MAD && comp < 2 && !fold_comp2;
+    const bool lz = FOLD && colacc(K) && comp < 2 && !fold_comp2;
     if (P01 && comp < 2)
-        scale_round_comp<FOLD, L, MAD, true, FD>(dc, N, n, pin, pout, true, lz);
+        scale_round_comp<FOLD, L, K, true>(dc, N, n, pin, pout, true, lz);
     else if (P2 && comp == 2)
-        scale_round_comp<FOLD, L, MAD, true, FD>(dc, N, n, pin, pout, fold_comp2, lz);
+        scale_round_comp<FOLD, L, K, true>(dc, N, n, pin, pout, fold_comp2, lz);
     else
-        scale_round_comp<FOLD, L, MAD, false, FD>(dc, N, n, pin, pout, comp < 2 || fold_comp2, lz);
-}
-template <bool FOLD, u32 L, bool MAD, bool P01 = false, bool P2 = false>
-__global__ void __launch_bounds__(TPB) scale_round_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ d,
-                                                          u64 *__restrict__ out01, size_t stride01,
-                                                          u64 *__restrict__ out2, size_t stride2, u32 fold_comp2)
-{
-    scale_round_rows<FOLD, L, MAD, P01, P2, false>(dc, N, d, out01, stride01, out2, stride2, fold_comp2);
-}
-// the folded reduction (NttPlan::fold_moduli; column accumulators)
-template <bool FOLD, u32 L, bool P01, bool P2>
-__global__ void __launch_bounds__(TPB) scale_round_fd_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ d,
-                                                             u64 *__restrict__ out01, size_t stride01,
-                                                             u64 *__restrict__ out2, size_t stride2, u32 fold_comp2)
-{
-    scale_round_rows<FOLD, L, true, P01, P2, true>(dc, N, d, out01, stride01, out2, stride2, fold_comp2);
+        scale_round_comp<FOLD, L, K, false>(dc, N, n, pin, pout, comp < 2 || fold_comp2, lz);
 }
 void launch_scale_round(const DevConsts *dc, u32 N, u32 L, const u64 *d, u32 nb, u64 *out01, size_t stride01, u64 *out2,
                         size_t stride2, hipStream_t st, Arith ar, bool fold, bool fold_comp2, bool p_only01, bool p_only2)
 {
-    const bool small_moduli = ar.mad;
-    assert(!p_only01 || (small_moduli && fold_comp2 == p_only2));
+    assert(!p_only01 || (ar.mad && fold_comp2 == p_only2));
     assert(!p_only2 || p_only01);
     dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, 3, nb);
     const u32 fc2 = (fold_comp2 && fold) ? 1u : 0u;
     with_u32<1, 7>(L, [&](auto L_) {
-        with_bools([&](auto F_, auto M_, auto P01_, auto P2_, auto FD_) {
-            if constexpr (FD_() && M_() && (P01_() || !P2_()))
-                hipLaunchKernelGGL((scale_round_fd_kernel<F_(), L_(), P01_(), P2_()>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2,
-                                   stride2, fc2);
-            else if constexpr (!FD_() && (M_() || !P01_()) && (P01_() || !P2_()))
-                hipLaunchKernelGGL((scale_round_kernel<F_(), L_(), M_(), P01_(), P2_()>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01, out2,
-                                   stride2, fc2);
-        }, fold, small_moduli, p_only01, p_only2, ar.fold);
+        with_arith(ar, [&](auto K_) {
+            with_bools([&](auto F_, auto P01_, auto P2_) {
+                if constexpr ((colacc(K_()) || !P01_()) && (P01_() || !P2_()))   // (the asserts above)
+                    hipLaunchKernelGGL((scale_round_kernel<F_(), L_(), K_(), P01_(), P2_()>), grid, dim3(TPB), 0, st, dc, N, d, out01, stride01,
+                                       out2, stride2, fc2);
+            }, fold, p_only01, p_only2);
+        });
     });
 }
 
@@ -1557,29 +1537,15 @@ bool launch_chain_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, u64 *data, u
 // Both conversions of a product on a level context whose operands are plain COEFFICIENT polynomials (ExpandIn::plain), X and Y each
 // with its own distance between the two polynomials of a ciphertext -- the accumulators stay at the parent's strides, an intermediate
 // product is packed.  expand_both_kernel's grid and row order.
-template <bool FOLD, u32 L, bool MAD, bool FD>
-__device__ __forceinline__ void expand_both_plain_rows(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ x, size_t sx,
-                                                                size_t six, const u64 *__restrict__ y, size_t sy, size_t siy,
-                                                                u64 *__restrict__ out, u32 n_outer)
-{
-    if (blockIdx.y < 2 * n_outer)
-        expand_body<true, FOLD, L, MAD, false, ExpandIn::plain, L, FD>(dc, dc, N, y, sy, siy, out, 4, 2, blockIdx.y);
-    else
-        expand_body<false, FOLD, L, MAD, false, ExpandIn::plain, L, FD>(dc, dc, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
-}
-template <bool FOLD, u32 L, bool MAD>
+template <bool FOLD, u32 L, ArithKind K>
 __global__ void __launch_bounds__(TPB) expand_both_plain_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ x, size_t sx,
                                                                 size_t six, const u64 *__restrict__ y, size_t sy, size_t siy,
                                                                 u64 *__restrict__ out, u32 n_outer)
 {
-    expand_both_plain_rows<FOLD, L, MAD, false>(dc, N, x, sx, six, y, sy, siy, out, n_outer);
-}
-template <bool FOLD, u32 L>
-__global__ void __launch_bounds__(TPB) expand_both_plain_fd_kernel(const DevConsts *__restrict__ dc, u32 N, const u64 *__restrict__ x, size_t sx,
-                                                                   size_t six, const u64 *__restrict__ y, size_t sy, size_t siy,
-                                                                   u64 *__restrict__ out, u32 n_outer)
-{
-    expand_both_plain_rows<FOLD, L, true, true>(dc, N, x, sx, six, y, sy, siy, out, n_outer);
+    if (blockIdx.y < 2 * n_outer)
+        expand_body<true, FOLD, L, K, false, ExpandIn::plain>(dc, dc, N, y, sy, siy, out, 4, 2, blockIdx.y);
+    else
+        expand_body<false, FOLD, L, K, false, ExpandIn::plain>(dc, dc, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
 
 // The fused form (folded rings, every modulus in (2^59, 2^60)): expand_both_kernel of the level context with the drop from the parent's
@@ -1587,62 +1553,32 @@ __global__ void __launch_bounds__(TPB) expand_both_plain_fd_kernel(const DevCons
 // [4][2 LC + 1][N].  The dropped X differs from what the QP array may hold in EVALUATION form, so X's Q limbs are written.
 // XDROP false (later products of K >= 3): X is an intermediate product on the level's limbs, packed, as the level's folded inverse
 // transform left it -- the pending load, Q limbs already in place (SKIPQ); Y is an accumulator and is dropped all the same.
-template <u32 L, u32 LC, bool XDROP, bool FD>
-__device__ __forceinline__ void expand_both_drop_rows(const DevConsts *__restrict__ dcp, const DevConsts *__restrict__ dcl, u32 N,
-                                                               const u64 *__restrict__ x, size_t sx, size_t six, const u64 *__restrict__ y,
-                                                               size_t sy, size_t siy, u64 *__restrict__ out, u32 n_outer)
-{
-    if (blockIdx.y < 2 * n_outer)
-        expand_body<true, true, LC, true, false, ExpandIn::drop, L, FD>(dcp, dcl, N, y, sy, siy, out, 4, 2, blockIdx.y);
-    else if (XDROP)
-        expand_body<false, true, LC, true, false, ExpandIn::drop, L, FD>(dcp, dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
-    else
-        expand_body<false, true, LC, true, true, ExpandIn::pending, LC, FD>(dcl, dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
-}
-template <u32 L, u32 LC, bool XDROP>
+template <u32 L, u32 LC, bool XDROP, ArithKind K>
 __global__ void __launch_bounds__(TPB) expand_both_drop_kernel(const DevConsts *__restrict__ dcp, const DevConsts *__restrict__ dcl, u32 N,
                                                                const u64 *__restrict__ x, size_t sx, size_t six, const u64 *__restrict__ y,
                                                                size_t sy, size_t siy, u64 *__restrict__ out, u32 n_outer)
 {
-    expand_both_drop_rows<L, LC, XDROP, false>(dcp, dcl, N, x, sx, six, y, sy, siy, out, n_outer);
-}
-template <u32 L, u32 LC, bool XDROP>
-__global__ void __launch_bounds__(TPB) expand_both_drop_fd_kernel(const DevConsts *__restrict__ dcp, const DevConsts *__restrict__ dcl, u32 N,
-                                                                  const u64 *__restrict__ x, size_t sx, size_t six, const u64 *__restrict__ y,
-                                                                  size_t sy, size_t siy, u64 *__restrict__ out, u32 n_outer)
-{
-    expand_both_drop_rows<L, LC, XDROP, true>(dcp, dcl, N, x, sx, six, y, sy, siy, out, n_outer);
+    if (blockIdx.y < 2 * n_outer)
+        expand_body<true, true, LC, K, false, ExpandIn::drop, L>(dcp, dcl, N, y, sy, siy, out, 4, 2, blockIdx.y);
+    else if (XDROP)
+        expand_body<false, true, LC, K, false, ExpandIn::drop, L>(dcp, dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
+    else
+        expand_body<false, true, LC, K, true, ExpandIn::pending, LC>(dcl, dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
 // Chain schedule (include/piehip.h): a product of K >= 3 whose level LC lies below the level LX of the product before it.  Y is an
 // accumulator on the handle's LY limbs (dcy); X is that earlier product, packed on LX limbs as level LX's folded inverse transform
 // left it, loaded and dropped with level LX's constants (dcx); both are converted with level LC's (dcl).  LX = LY -- the earlier
-// product ran on every limb -- is expand_both_drop_kernel<LY, LC, true> itself, X at the product's strides.
-template <u32 LY, u32 LX, u32 LC, bool FD>
-__device__ __forceinline__ void expand_both_drop_xy_rows(const DevConsts *__restrict__ dcy, const DevConsts *__restrict__ dcx,
-                                                                  const DevConsts *__restrict__ dcl, u32 N, const u64 *__restrict__ x, size_t sx,
-                                                                  size_t six, const u64 *__restrict__ y, size_t sy, size_t siy,
-                                                                  u64 *__restrict__ out, u32 n_outer)
-{
-    if (blockIdx.y < 2 * n_outer)
-        expand_body<true, true, LC, true, false, ExpandIn::drop, LY, FD>(dcy, dcl, N, y, sy, siy, out, 4, 2, blockIdx.y);
-    else
-        expand_body<false, true, LC, true, false, ExpandIn::drop, LX, FD>(dcx, dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
-}
-template <u32 LY, u32 LX, u32 LC>
+// product ran on every limb -- is expand_both_drop_kernel<LY, LC, true, K> itself, X at the product's strides.
+template <u32 LY, u32 LX, u32 LC, ArithKind K>
 __global__ void __launch_bounds__(TPB) expand_both_drop_xy_kernel(const DevConsts *__restrict__ dcy, const DevConsts *__restrict__ dcx,
                                                                   const DevConsts *__restrict__ dcl, u32 N, const u64 *__restrict__ x, size_t sx,
                                                                   size_t six, const u64 *__restrict__ y, size_t sy, size_t siy,
                                                                   u64 *__restrict__ out, u32 n_outer)
 {
-    expand_both_drop_xy_rows<LY, LX, LC, false>(dcy, dcx, dcl, N, x, sx, six, y, sy, siy, out, n_outer);
-}
-template <u32 LY, u32 LX, u32 LC>
-__global__ void __launch_bounds__(TPB) expand_both_drop_xy_fd_kernel(const DevConsts *__restrict__ dcy, const DevConsts *__restrict__ dcx,
-                                                                     const DevConsts *__restrict__ dcl, u32 N, const u64 *__restrict__ x, size_t sx,
-                                                                     size_t six, const u64 *__restrict__ y, size_t sy, size_t siy,
-                                                                     u64 *__restrict__ out, u32 n_outer)
-{
-    expand_both_drop_xy_rows<LY, LX, LC, true>(dcy, dcx, dcl, N, x, sx, six, y, sy, siy, out, n_outer);
+    if (blockIdx.y < 2 * n_outer)
+        expand_body<true, true, LC, K, false, ExpandIn::drop, LY>(dcy, dcl, N, y, sy, siy, out, 4, 2, blockIdx.y);
+    else
+        expand_body<false, true, LC, K, false, ExpandIn::drop, LX>(dcx, dcl, N, x, sx, six, out, 4, 0, blockIdx.y - 2 * n_outer);
 }
 // the (L, Lc) pairs the fused kernel is built for: Lc = L - 1 for every L, and the further pairs that stay free of scratch; the
 // (LY, LX, LC) triples of the chain schedule's form
@@ -1667,33 +1603,32 @@ bool expand_drop_built(u32 Ly, u32 Lx, u32 Lc)
 bool launch_expand_pair(const DevConsts *dc, u32 N, u32 L, const ExpandOperand &x, const ExpandOperand &y, u32 n_outer, u64 *out,
                         hipStream_t st, Arith ar, bool fold)
 {
-    const bool small_moduli = ar.mad;
     const bool ydrop = y.src_L > L, xdrop = x.src_L > L;
     const dim3 grid(((fold ? N / 2 : N) + TPB - 1) / TPB, n_outer * 4), block(TPB);
     if (ydrop) {   // fused limb drop: X is dropped too, or lies on this level with its Q limbs in place
-        if (!fold || !small_moduli || x.plain || y.plain || x.q_ready == xdrop || !expand_drop_built(y.src_L, xdrop ? x.src_L : L, L)) return false;
+        if (!fold || !ar.mad || x.plain || y.plain || x.q_ready == xdrop || !expand_drop_built(y.src_L, xdrop ? x.src_L : L, L)) return false;
+        // the drop forms are built for the two column-accumulator kinds only (refused above for the other)
+        auto with_colacc = [&](auto &&f) {
+            with_arith(ar, [&](auto K_) {
+                if constexpr (colacc(K_())) f(K_);
+            });
+        };
 #define PAIR_(L_, C_)                                                                                                                          \
     if (y.src_L == L_ && L == C_ && (!xdrop || x.src_L == L_)) {   /* (an X on Y's limbs is under Y's constants) */                            \
-        with_bools([&](auto XD_, auto FD_) {                                                                                                   \
-            if constexpr (FD_())                                                                                                               \
-                hipLaunchKernelGGL((expand_both_drop_fd_kernel<L_, C_, XD_()>), grid, block, 0, st, y.src_dc, dc, N, x.p, x.row, x.poly, y.p,  \
-                                   y.row, y.poly, out, n_outer);                                                                               \
-            else                                                                                                                               \
-                hipLaunchKernelGGL((expand_both_drop_kernel<L_, C_, XD_()>), grid, block, 0, st, y.src_dc, dc, N, x.p, x.row, x.poly, y.p,     \
-                                   y.row, y.poly, out, n_outer);                                                                               \
-        }, xdrop, ar.fold);                                                                                                                    \
+        with_colacc([&](auto K_) {                                                                                                             \
+            with_bools([&](auto XD_) {                                                                                                         \
+                hipLaunchKernelGGL((expand_both_drop_kernel<L_, C_, XD_(), K_()>), grid, block, 0, st, y.src_dc, dc, N, x.p, x.row, x.poly,    \
+                                   y.p, y.row, y.poly, out, n_outer);                                                                          \
+            }, xdrop);                                                                                                                         \
+        });                                                                                                                                    \
         return true;                                                                                                                           \
     }
 #define TRIPLE_(L_, X_, C_)                                                                                                                    \
     if (y.src_L == L_ && x.src_L == X_ && L == C_) {                                                                                           \
-        with_bools([&](auto FD_) {                                                                                                             \
-            if constexpr (FD_())                                                                                                               \
-                hipLaunchKernelGGL((expand_both_drop_xy_fd_kernel<L_, X_, C_>), grid, block, 0, st, y.src_dc, x.src_dc, dc, N, x.p, x.row,     \
-                                   x.poly, y.p, y.row, y.poly, out, n_outer);                                                                  \
-            else                                                                                                                               \
-                hipLaunchKernelGGL((expand_both_drop_xy_kernel<L_, X_, C_>), grid, block, 0, st, y.src_dc, x.src_dc, dc, N, x.p, x.row,        \
-                                   x.poly, y.p, y.row, y.poly, out, n_outer);                                                                  \
-        }, ar.fold);                                                                                                                           \
+        with_colacc([&](auto K_) {                                                                                                             \
+            hipLaunchKernelGGL((expand_both_drop_xy_kernel<L_, X_, C_, K_()>), grid, block, 0, st, y.src_dc, x.src_dc, dc, N, x.p, x.row,      \
+                               x.poly, y.p, y.row, y.poly, out, n_outer);                                                                      \
+        });                                                                                                                                    \
         return true;                                                                                                                           \
     }
         PIE_CHAIN_DROP_PAIRS(PAIR_)
@@ -1705,22 +1640,19 @@ bool launch_expand_pair(const DevConsts *dc, u32 N, u32 L, const ExpandOperand &
     if (xdrop || x.plain != y.plain) return false;
     if (x.plain)   // (a level context has fewer limbs than MAX_L)
         return !x.q_ready && with_u32<1, 6>(L, [&](auto L_) {
-            with_bools([&](auto F_, auto M_, auto FD_) {
-                if constexpr (FD_())
-                    hipLaunchKernelGGL((expand_both_plain_fd_kernel<F_(), L_()>), grid, block, 0, st, dc, N, x.p, x.row, x.poly, y.p, y.row, y.poly,
+            with_arith(ar, [&](auto K_) {
+                with_bools([&](auto F_) {
+                    hipLaunchKernelGGL((expand_both_plain_kernel<F_(), L_(), K_()>), grid, block, 0, st, dc, N, x.p, x.row, x.poly, y.p, y.row, y.poly,
                                        out, n_outer);
-                else
-                    hipLaunchKernelGGL((expand_both_plain_kernel<F_(), L_(), M_()>), grid, block, 0, st, dc, N, x.p, x.row, x.poly, y.p, y.row, y.poly,
-                                       out, n_outer);
-            }, fold, small_moduli && !ar.fold, ar.fold);
+                }, fold);
+            });
         });
     return x.poly == y.poly && with_u32<1, 7>(L, [&](auto L_) {
-        with_bools([&](auto F_, auto M_, auto Q_, auto FD_) {
-            if constexpr (FD_())
-                hipLaunchKernelGGL((expand_both_fd_kernel<F_(), L_(), Q_()>), grid, block, 0, st, dc, N, x.p, x.row, y.p, y.row, y.poly, out, n_outer);
-            else
-                hipLaunchKernelGGL((expand_both_kernel<F_(), L_(), M_(), Q_()>), grid, block, 0, st, dc, N, x.p, x.row, y.p, y.row, y.poly, out, n_outer);
-        }, fold, small_moduli && !ar.fold, x.q_ready, ar.fold);
+        with_arith(ar, [&](auto K_) {
+            with_bools([&](auto F_, auto Q_) {
+                hipLaunchKernelGGL((expand_both_kernel<F_(), L_(), K_(), Q_()>), grid, block, 0, st, dc, N, x.p, x.row, y.p, y.row, y.poly, out, n_outer);
+            }, fold, x.q_ready);
+        });
     });
 }
 

@@ -19,6 +19,14 @@ namespace piehip {
 typedef uint64_t u64;
 typedef uint32_t u32;
 
+// The arithmetic kind of the kernels that reduce variable x variable column sums, a compile-time argument of their templates:
+//   wide     128-bit products and two-word Barrett (moduli up to 61 bits)
+//   barrett  v_mad_u64_u32 column accumulators (every modulus in (2^59, 2^60)) reduced by the one-word Barrett block
+//   fold     the same accumulators reduced by folding with d (every modulus 2^60 - d, d < COLACC_FOLD_MAX_D)
+// Helpers that only tell column accumulators from 128-bit forms take colacc(kind) as a bool.
+enum class ArithKind { wide, barrett, fold };
+constexpr bool colacc(ArithKind k) { return k != ArithKind::wide; }
+
 // Per-modulus constants.  r1:r0 = floor(2^128 / q) (two-word Barrett); fconst/fshift give the
 // 60-bit fixed-point fraction used by the HPS rounding terms (see fixfrac).
 struct Mod {

@@ -204,11 +204,12 @@ __device__ __forceinline__ U128 dot128(const u64 *y, const u64 (&c)[NS])
 
 // centred CRT lift of y_i-weighted residues from a source basis into target modulus `tm`:
 //   sum_i y_i * hat[i] - v * prodmod
+// K: the arithmetic kind (modarith.h); the column-accumulator kinds (MAD) reduce by the Barrett or the folded block
 // LZ (MAD only): the result stays in [0, 4q) (colacc_reduce123_lazy)
-// FD (MAD only; NttPlan::fold_moduli): the folded reduction block in place of the Barrett block
-template <u32 NS, bool MAD, bool LZ = false, bool FD = false>
+template <u32 NS, ArithKind K, bool LZ = false>
 __device__ __forceinline__ u64 crt_out(const u64 *y, const u64 (&hat)[NS], u64 v, u64 prodmod, const Mod &tm, u64 negq, u64 neg2q)
 {
+    constexpr bool MAD = colacc(K), FD = K == ArithKind::fold;
     if (MAD && NS <= 7) {
         // MAD implies 2^59 < q < 2^60 for every modulus: up to 7 products plus the small term stay below 2^123; everything
         // goes through the column accumulator (v <= NS is one more, partial, term) and one reduction block
@@ -221,6 +222,12 @@ __device__ __forceinline__ u64 crt_out(const u64 *y, const u64 (&hat)[NS], u64 v
     U128 acc = dot128<NS, MAD>(y, hat);
     mac128(acc, v, tm.q - prodmod);  // - v * prodmod (mod tm); v <= ns: one Barrett reduction for the whole sum
     return reduce128(acc, tm);
+}
+// ... named by a bool, as tests/arith_check names the two kinds it checks this lift at: the 128-bit form or the Barrett block
+template <u32 NS, bool MAD, bool LZ = false>
+__device__ __forceinline__ u64 crt_out(const u64 *y, const u64 (&hat)[NS], u64 v, u64 prodmod, const Mod &tm, u64 negq, u64 neg2q)
+{
+    return crt_out<NS, MAD ? ArithKind::barrett : ArithKind::wide, LZ>(y, hat, v, prodmod, tm, negq, neg2q);
 }
 
 }  // namespace piehip

@@ -230,7 +230,7 @@ __device__ __forceinline__ u64 colacc_fold(const ColAcc &a, u64 nq)
         : PIE_ASM_CLOB);
     return ((u64)hi << 32) | lo;
 }
-// the reduction of a kernel's arithmetic kind: FD (NttPlan::fold_moduli) the folded block, otherwise the Barrett block
+// the reduction of the two column-accumulator kinds: FD (ArithKind::fold) the folded block, otherwise (ArithKind::barrett) the Barrett block
 template <bool FD, bool W124>
 __device__ __forceinline__ u64 colacc_red(const ColAcc &a, const Mod &m, u64 nq)
 {

@@ -35,7 +35,7 @@ def test_every_forward_block_of_the_listing_aliases(tmp_path):
     assert r.returncode == 0, r.stdout
     rows = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("ntt16::ntt16_kernel_t")]
     fwd = [row for row in rows if int(row[-8]) > 0]
-    assert len(rows) == 8 and len(fwd) == 4
+    assert len(rows) == 10 and len(fwd) == 4   # 2 slice lengths x {forward, forward with lift, inverse, tensor Barrett, tensor folded}
     for row in rows:     # forward, seeded, aliased, instr, vgpr, spill, scratch, verdict
         assert row[-8] == row[-7] == row[-6] and row[-4:] == ["128", "0", "0", "ok"], row
     assert all(row[-5] == "18/19" for row in fwd)

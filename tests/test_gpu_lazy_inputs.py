@@ -13,9 +13,10 @@ give back the first operand exactly: y0 + y1 = 2u + 4q, u < 4q; < 4q behind a fo
 mode does not write untouched.  No skip and no tolerance: a shape the program refuses fails.  After a status that is neither 0 nor
 2, or a time limit, no further case starts the program.
 
-The kernels that reduce a variable x variable column sum outside stage A exist twice (kernels.hpp: Arith): with
-the one-word Barrett block and, *_fd_kernel, with the folded block.  The program takes the kind from the plan or from fd= (fd=0: the
-Barrett kernels, valid on every context with column accumulators), so the default chain's inputs and expected outputs serve both.
+The kernels that reduce a variable x variable column sum outside stage A take the arithmetic kind as a template argument (modarith.h:
+ArithKind; kernels.hpp: Arith) and are built at both column-accumulator kinds: barrett, the one-word Barrett block,
+and fold, the folded block.  The program takes the kind from the plan or from fd= (fd=0: kind barrett, valid on every context with
+column accumulators), so the default chain's inputs and expected outputs serve both.
 Every such case names its kind and asserts it: plan["fold_moduli"] is the context's decision, "reduction" on the route line the
 kind that ran (_kind_opts, _check_kind).  KIND_POINTS lists the (chain, N, L) they use: tests/test_reduction_kinds.py checks on the
 CPU that each chain selects the kind claimed here.
@@ -317,8 +318,8 @@ TENSOR_CASES = ([("default", kind, mode) for kind in ("barrett", "fold") for mod
 @pytest.mark.parametrize("chain,kind,mode", TENSOR_CASES, ids=[_kind_id(c, k, m) for c, k, m in TENSOR_CASES])
 @pytest.mark.parametrize("N", [8192, 16384])
 def test_ntt16_tensor(N, chain, kind, mode):
-    """the TENSOR load phase of ntt16_kernel.h (tensor_load) -- kind barrett: the TENSOR instantiation of ntt16_kernel_t, kind fold:
-    ntt16_tensor_fd_kernel_t --: N = 8192 one slice per limb (canonical coefficients out), N = 16384 folded (pairs in [0, 4q),
+    """the TENSOR load phase of ntt16_kernel.h (tensor_load) -- the TENSOR instantiation of ntt16_kernel_t at kind barrett and at kind
+    fold --: N = 8192 one slice per limb (canonical coefficients out), N = 16384 folded (pairs in [0, 4q),
     compared after the outer stage).  eval_q_L = L leaves out the Q limbs of d0, d1, eval_q_d2 those of d2 as well: their places
     keep the fill pattern"""
     o, e, d = _fused_tensor_case(chain, N)
@@ -397,7 +398,7 @@ def _scale_round_case(chain, L, p01, p2):
 
 @pytest.mark.parametrize("chain,kind,L,mode", SR_CASES, ids=[_kind_id(c, k, "%d-%s" % (L, m)) for c, k, L, m in SR_CASES])
 def test_scale_round_folded(chain, kind, L, mode):
-    """kind barrett: scale_round_kernel<true, L, true, P01, P2>, kind fold: scale_round_fd_kernel<true, L, P01, P2>.  d[3][M][N] over
+    """scale_round_kernel<true, L, kind, P01, P2> at kind barrett and at kind fold.  d[3][M][N] over
     [0, 4q) with the outer stage pending; the Q limbs a P-only component does not read hold a poison pattern.  Components 0, 1 (and
     2 with fold_comp2) leave through fold_store -- their first operand in [0, 4q) (lz: L <= 5, no fold_comp2), canonical otherwise
     --, component 2 canonical without it.  L = 6: colacc_red<FD, true>, the 124-bit form of either block; L = 7: reduce128 under
@@ -441,7 +442,7 @@ def _expand_both_case(chain, L):
 @pytest.mark.parametrize("skip_q", [0, 1])
 @pytest.mark.parametrize("chain,kind,L", EB_CASES, ids=[_kind_id(c, k, "%d" % L) for c, k, L in EB_CASES])
 def test_expand_both_folded(chain, kind, L, skip_q):
-    """kind barrett: expand_both_kernel<true, L, true, SKIPQ>, kind fold: expand_both_fd_kernel<true, L, SKIPQ>.  X and Y over [0, 4q)
+    """expand_both_kernel<true, L, kind, SKIPQ> at kind barrett and at kind fold.  X and Y over [0, 4q)
     with the outer stage pending; every output limb leaves through fold_store; skip_q: the Q limbs of X's slots keep the fill
     pattern"""
     N = 16384

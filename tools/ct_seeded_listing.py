@@ -32,8 +32,15 @@ def kernels(txt):
 
 def short(name):
     d = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
-    m = re.match(r'void piehip::(\w+(::\w+)*(<[^(]*>)?)\(', d)
-    return m.group(1) if m else d.split('(')[0]
+    if d.endswith(')'):   # cut the parameter list: the parenthesis that matches the last one (an enum template argument has its own)
+        depth, i = 0, len(d)
+        while True:
+            i -= 1
+            depth += (d[i] == ')') - (d[i] == '(')
+            if not depth:
+                break
+        d = d[:i]
+    return re.sub(r'^void ', '', d).replace('piehip::', '')
 
 
 def asm_blocks(body):
@@ -102,7 +109,7 @@ def main():
     unseeded_ok = '--unseeded' in sys.argv
     ks = kernels(open(args[0]).read())
     ok = True
-    print("%-56s %7s %8s %8s %9s %5s %5s %7s  %s" % ("kernel", "forward", "seeded", "aliased", "instr", "vgpr", "spill", "scratch", "verdict"))
+    print("%-62s %7s %8s %8s %9s %5s %5s %7s  %s" % ("kernel", "forward", "seeded", "aliased", "instr", "vgpr", "spill", "scratch", "verdict"))
     for name, k in ks.items():
         fwd = [b for b in asm_blocks(k['body']) if is_forward(b)]
         seeded = [b for b in fwd if is_seeded(b)]
@@ -118,7 +125,7 @@ def main():
         if fwd and len(seeded) != len(fwd) and not (unseeded_ok and not seeded):
             verdict.append("%d unseeded" % (len(fwd) - len(seeded)))
         ok &= not verdict
-        print("%-56s %7d %8d %8d %9s %5d %5d %7d  %s" % (short(name)[:56], len(fwd), len(seeded), aliased, "/".join(map(str, sizes)) or "-", v, sp, sc,
+        print("%-62s %7d %8d %8d %9s %5d %5d %7d  %s" % (short(name)[:62], len(fwd), len(seeded), aliased, "/".join(map(str, sizes)) or "-", v, sp, sc,
                                                         ", ".join(verdict) or "ok"))
         for i, c in complaints[:8]:
             print("    block %d: %s" % (i, c))

@@ -1,5 +1,5 @@
 """per-kernel comparison of two hipcc -S listings of one file (before and after a change):
-    python tools/isa_compare.py [--removed FILE] [--neutral-ordinals] before.s after.s
+    python tools/isa_compare.py [--removed FILE] [--renamed FILE] [--neutral-ordinals] before.s after.s
 Kernels that only the second listing has are listed with their figures; one that only the first has is an error.  A kernel counts as
 identical when its instructions, its kernel descriptor and its metadata entry are (the compilation-unit id, __hip_cuid_<hash>,
 neutralised); for the others: tools/isa_regs.py's columns, waves per SIMD, instruction totals and the counts of the memory and
@@ -7,6 +7,10 @@ multiplier instructions, each as before->after where it changed.
 --removed FILE: the kernels the change removes on purpose, one per line, as this tool prints them (e.g. expand_kernel<true, true, 3u,
 false, false>) or mangled.  They may be missing from the second listing and are listed by name; any OTHER kernel missing there, and a
 named one that is still there, stays an error.
+--renamed FILE: the kernels the change renames, one pair per line, old<TAB>new, each as this tool prints kernel names or mangled (a
+change of a template's parameter list renames every instantiation).  A pair is compared as ONE kernel: each side's own mangled name is
+replaced by a fixed word in its body, its descriptor and its metadata entry first.  The pairs are listed as renamed, not as removed and
+new; a pair whose old name the first listing lacks, or whose new name the second lacks, is an error.
 --neutral-ordinals: the compiler numbers the functions of a listing and puts that ordinal into local labels (.LBB<f>_<n>, and BB<f>_<n>
 inside comments), so taking out or reordering one kernel renames the labels of every kernel behind it.  With this option the ordinal
 is replaced by a fixed letter in both listings before anything is compared, and the padding between a label and the comment behind it
@@ -54,10 +58,34 @@ def fam(c, prefix):
 FAMS = ('global_load_', 'global_store_', 'v_mad_u64_u32', 'v_mul_hi_u32', 'v_mul_lo_u32', 'v_lshl_add_u64')
 
 
+SHORT = {}
+
+
 def short(name):
-    d = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
-    m = re.match(r'void piehip::(\w+(<[^(]*>)?)\(', d)
-    return m.group(1) if m else d.split('(')[0].replace('piehip::', '')
+    """the demangled name without return type, parameter list and piehip:: (template arguments may hold parentheses: enum values)"""
+    if name not in SHORT:
+        d = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
+        if d.endswith(')'):   # cut the parameter list: the parenthesis that matches the last one
+            depth, i = 0, len(d)
+            while True:
+                i -= 1
+                depth += (d[i] == ')') - (d[i] == '(')
+                if not depth:
+                    break
+            d = d[:i]
+        SHORT[name] = re.sub(r'^void ', '', d).replace('piehip::', '')
+    return SHORT[name]
+
+
+def find(listing, name, which):
+    """the mangled name of `name` (mangled, or as short() prints it) in a listing"""
+    hits = [k for k in listing if k == name or short(k) == re.sub(r'^void ', '', name)]
+    assert len(hits) == 1, "--renamed: %s is not a kernel of the %s listing" % (name, which)
+    return hits[0]
+
+
+def unnamed(entry, own):
+    return {k: v.replace(own, 'KERNEL') if isinstance(v, str) else v for k, v in entry.items()}
 
 
 def waves(v):
@@ -66,12 +94,29 @@ def waves(v):
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--removed", default=None)
+ap.add_argument("--renamed", default=None)
 ap.add_argument("--neutral-ordinals", action="store_true")
 ap.add_argument("before")
 ap.add_argument("after")
 args = ap.parse_args()
 pa, pt = kernels(args.before, args.neutral_ordinals)
 he, ht = kernels(args.after, args.neutral_ordinals)
+renamed = []
+if args.renamed:
+    for ln in open(args.renamed):
+        if ln.strip():
+            old, new = ln.rstrip('\n').split('\t')
+            renamed.append((find(pa, old.strip(), "first"), find(he, new.strip(), "second")))
+    assert len(set(o for o, n in renamed)) == len(renamed) == len(set(n for o, n in renamed)), "--renamed: a name occurs twice"
+    # from here on a pair is one kernel under its old name
+    moved = {o: unnamed(he[n], n) for o, n in renamed}
+    for o, n in renamed:
+        del he[n]
+    clash = [short(o) for o in moved if o in he]
+    assert not clash, "--renamed: old names the second listing still has: %s" % clash
+    for o, n in renamed:
+        pa[o] = unnamed(pa[o], o)
+    he.update(moved)
 removed = set(ln.strip() for ln in open(args.removed) if ln.strip()) if args.removed else set()
 gone = [k for k in pa if k not in he]
 new = [k for k in he if k not in pa]
@@ -87,6 +132,11 @@ if gone:
     print()
     for k in gone:
         del pa[k]
+if renamed:
+    print("%d kernels renamed (--renamed), each pair compared as one kernel, its own name neutralised:" % len(renamed))
+    for o, n in renamed:
+        print("  %s -> %s%s" % (short(o), short(n), "" if pa[o] == he[o] else "   DIFFERS"))
+    print()
 if args.neutral_ordinals:
     print("(function ordinals in local labels neutralised)")
 same = [k for k in pa if pa[k] == he[k]]
