@@ -161,12 +161,15 @@ void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M,
 // phase (no digits kernel): d2[nb][L][N] COEFFICIENT -> dig[nb][L(i)][L(j)][N] EVALUATION
 void launch_ntt_digits(const NttPlan &pl, const u64 *d2, u64 *dig, u32 nb, u32 L, bool sigma, hipStream_t st);
 
-// Stage A: acc[b][K][2][L][N] = sum_j idx[h][j] (.) db[h][beta][j] + minus    (BatchedFHEHIPPIE.cpp:101-116)
-// small_moduli: every RNS modulus is < 2^60 (enables the v_mad_u64_u32 column-accumulator kernel)
+// Stage A of 1 <= nq <= STAGE_A_MAX_QUERIES queries on one database:
+// acc[b][nq][K][2][L][N] = sum_j idx_q[h][j] (.) db[h][beta][j] + minus_q    (BatchedFHEHIPPIE.cpp:101-116)
+// A batch goes through stage_a_tiled_kernel in groups of two to four queries, each group reading the database once (a group of three
+// on a ring that fills the chip through stage_a_resident_kernel: stage_a_resident_lpp of stage_a_common.h); a single query through
+// stage_a_mad_kernel or, on the 128-bit arithmetic, stage_a_kernel.
+// small_moduli: every RNS modulus is in (2^59, 2^60) (the v_mad_u64_u32 column accumulators; 128-bit accumulators otherwise)
 // bstride: bin-layer count of the database array db[K][bstride][E][L][N] when only b <= bstride layers (starting at the
 // layer db points to) are evaluated; 0 = b.  h0, hn: only the inner hash functions [h0, h0 + hn) (hn = 0: all from h0)
-// nq, q: the accumulators are row q of a batch of nq queries, acc[b][nq][K][2][L][N] (nq = 1: the layout above)
-// xo (column-accumulator kernels only): the accumulators of inner hash function 0 -- operand X of the first ciphertext product --
+// xo (column accumulators only): the accumulators of inner hash function 0 -- operand X of the first ciphertext product --
 // are not written to acc but, lane-ordered (ntt16_kernel.h), into the Q limbs of the QP operand array xo->out[row][4][M][N],
 // slots 0, 1: where the tensor product reads them.  The inverse transform then takes them from there (NttExtra::x_lane_in)
 // instead of writing that copy itself.
@@ -174,12 +177,6 @@ struct StageAXOut {
     u64 *out = nullptr;
     u32 M = 0, logns = 0;  // limbs per polynomial of the QP array; log2 of the transform's slice length
 };
-void launch_stage_a(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const u64 *idx, const u64 *minus,
-                    const u64 *db, u64 *acc, hipStream_t st, bool small_moduli, u32 bstride = 0, u32 h0 = 0, u32 hn = 0, u32 nq = 1,
-                    u32 q = 0, const StageAXOut *xo = nullptr);
-// Stage A of a batch of nq <= STAGE_A_MAX_QUERIES queries on one database: acc[b][nq][K][2][L][N].  Where the column-accumulator
-// kernel applies (small_moduli) the queries go through it in groups of two to four, each group reading the database once
-// (a group of three on a ring that fills the chip through stage_a_resident_kernel: stage_a_resident_lpp of stage_a_common.h)
 static const u32 STAGE_A_MAX_QUERIES = 8;
 struct StageAQueries {
     const u64 *idx[STAGE_A_MAX_QUERIES];
@@ -306,7 +303,7 @@ void launch_encode_lift(const DevConsts *dc, u32 N, u32 L, u32 M, const u64 *u, 
 //   db   [un][b][E][N]                       the database plaintexts' limbs
 //   idx  [un][E][2][N], minus [un][2][N]     per query: the index ciphertexts' and the minus element's limbs
 //   acc  [b][nq][un][2][N]                   = sum_j idx[u][j] (.) db[u][beta][j] + minus[u], canonical, EVALUATION format
-// The arithmetic of launch_stage_a / launch_stage_a_batch (column accumulators where small_moduli, 128-bit otherwise); one launch per
+// The arithmetic of launch_stage_a_batch (column accumulators where small_moduli, 128-bit otherwise); one launch per
 // group of one to four queries whatever b.
 void launch_stage_a_slice(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, u32 b, u32 E, const StageAQueries &qs, u32 nq,
                           const u64 *db, u64 *acc, hipStream_t st, bool small_moduli);

@@ -19,21 +19,12 @@
 namespace piehip {
 
 static const u32 TPB = 256;
+typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 
-// Run-time values as template arguments.  with_u32<LO, HI>(v, f) calls f(std::integral_constant<u32, v>) for v in [LO, HI] and says
-// whether it did; with_bools(f, b...) calls f(std::bool_constant<b>...).  The callers' generic lambdas read the arguments as
-// constants (L_(), F_()) and guard with `if constexpr` whatever combination no kernel is built for.  with_arith(ar, f) calls
-// f(std::integral_constant<ArithKind, ar.kind>): the arithmetic kind every kernel here takes as ONE template argument (K_()).
-template <u32 LO, u32 HI, class F>
-static bool with_u32(u32 v, F &&f)
-{
-    if constexpr (LO <= HI) {
-        if (v != LO) return with_u32<LO + 1, HI>(v, f);
-        f(std::integral_constant<u32, LO>{});
-        return true;
-    }
-    return false;
-}
+// Run-time values as template arguments.  with_u32<LO, HI>(v, f) (stage_a_common.h) calls f(std::integral_constant<u32, v>) for v in
+// [LO, HI] and says whether it did; with_bools(f, b...) calls f(std::bool_constant<b>...).  The callers' generic lambdas read the
+// arguments as constants (L_(), F_()) and guard with `if constexpr` whatever combination no kernel is built for.  with_arith(ar, f)
+// calls f(std::integral_constant<ArithKind, ar.kind>): the arithmetic kind every kernel here takes as ONE template argument (K_()).
 template <class F>
 static void with_bools(F &&f)
 {
@@ -65,9 +56,6 @@ static void with_arith(Arith ar, F &&f)
 // 128-bit lazy accumulation: moduli may be up to 61 bits (HostParams::init), so products are < 2^122 and the
 // accumulator is reduced every 32 terms (2^61 + 32 * 2^122 < 2^128); one more Barrett reduction at the end.
 // ---------------------------------------------------------------------------------------------
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-
-
 template <int BPT>
 __global__ void __launch_bounds__(TPB) stage_a_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 K, u32 b, u32 E,
                                                       const u64 *__restrict__ idx, const u64 *__restrict__ minus,
@@ -216,18 +204,22 @@ __global__ void __launch_bounds__(TPB) stage_a_mad_kernel(const DevConsts *__res
     }
 }
 
-// A batch of Q queries against one database (piehip_set_query_batch): the thread holds the accumulators of Q queries x BPT bin
+// A batch of Q >= 2 queries against one database (piehip_set_query_batch): the thread holds the accumulators of Q queries x BPT bin
 // layers, so a database word is loaded once for the whole batch -- the database is 196 of the 253 MiB stage A moves for one
 // query at the headline shape -- and an index-ciphertext word once per BPT layers as before.  A term is 2 Q + BPT loads for
-// 2 Q BPT multiply-accumulates (one query, seven layers: 9 for 14; two queries, four layers: 8 for 16).
+// 2 Q BPT multiply-accumulates (one query, seven layers: 9 for 14; two queries, four layers: 8 for 16).  The term loop is
+// stage_a_terms (stage_a_common.h) for both arithmetics -- MAD: the column accumulators of stage_a_mad_kernel, otherwise the 128-bit
+// ones of stage_a_kernel -- with DEPTH terms in flight and a last layer group that may be ragged.
 // acc rows: [bin layer][query][K][2][L][N] (the product chain treats (layer, query) as one batch index).
 // 27-31 us per query at the headline shape against 46-49 for one query per launch; what bounds it then is issue time plus
 // memory latency at three waves per SIMD, not HBM bytes -- profiles/r03/stage_a_batch_microbench.txt, with the cuts that were
-// tried on top (index words shared through L1 or LDS) and dropped.
-template <int BPT, int Q, int DEPTH>
-__global__ void __launch_bounds__(TPB) stage_a_mad_batch_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 K, u32 b, u32 E,
-                                                                StageAQueries qs, const u64 *__restrict__ db, u64 *__restrict__ acc,
-                                                                u32 bstride, u32 h0, u32 nq, u32 q0, u32 tiles, StageAXOut xo)
+// tried on top (index words shared through L1 or LDS) and dropped.  One query stays on the two kernels above: through this one
+// (Q = 1, same tiling) a C3 step was 0.7-2 % slower on the column accumulators and stage A 9 us of 50 slower on the 128-bit ones
+// (profiles/stage_a_one_kernel).
+template <int BPT, int Q, int DEPTH, bool MAD>
+__global__ void __launch_bounds__(TPB) stage_a_tiled_kernel(const DevConsts *__restrict__ dc, u32 N, u32 L, u32 K, u32 b, u32 E,
+                                                            StageAQueries qs, const u64 *__restrict__ db, u64 *__restrict__ acc,
+                                                            u32 bstride, u32 h0, u32 nq, u32 q0, u32 tiles, StageAXOut xo)
 {
     StageATile tl;
     if (!stage_a_tile((N + TPB - 1) / TPB, L, tiles, (b + BPT - 1) / BPT, tl)) return;
@@ -238,11 +230,11 @@ __global__ void __launch_bounds__(TPB) stage_a_mad_batch_kernel(const DevConsts 
     const Mod m = dc->mod[l];
     const size_t LN = (size_t)L * N;
     const size_t ioff = ((size_t)h * E) * 2 * LN + (size_t)l * N + n0;
-    const u64 *pd = db + (((size_t)h * bstride + beta0) * E) * LN + (size_t)l * N + n0;
+    const u64 *pd = db + (((size_t)h * bstride + beta0) * E) * LN + (size_t)l * N + n0;   // db is [K][bstride][E][L][N]
     const size_t bin_stride = (size_t)E * LN;
-    StageAAcc<true> a[Q][BPT][2];
-    stage_a_terms<BPT, Q, DEPTH, true>(qs, ioff, LN, pd, bin_stride, tmax, nl, E, m, a);
-    const bool xdir = h == 0 && xo.out != nullptr;
+    StageAAcc<MAD> a[Q][BPT][2];
+    stage_a_terms<BPT, Q, DEPTH, MAD>(qs, ioff, LN, pd, bin_stride, tmax, nl, E, m, a);
+    const bool xdir = MAD && h == 0 && xo.out != nullptr;   // (the 128-bit arithmetic writes acc only)
     const u32 noff = n + ((xdir ? ~0u : 0u) & (lane_home(n, xo.logns) - n));
 #pragma unroll
     for (int q = 0; q < Q; q++) {
@@ -255,11 +247,19 @@ __global__ void __launch_bounds__(TPB) stage_a_mad_batch_kernel(const DevConsts 
             const size_t row = (size_t)(beta0 + t) * nq + q0 + q;
             // operand X of the first product goes straight to the QP operand array, lane-ordered (StageAXOut).  Uniform choices
             // of base and stride, and the lane offset blended with a mask: no per-lane selects (v_cndmask on VCC: see addmod_nb)
+            // (This epilogue is written out again in the resident kernel and in stage_a_slice_kernel.  As device functions, the
+            // destination compiles to other code and the reduction plus sum to a sum with its operands the other way round:
+            // profiles/stage_a_one_kernel/README.txt.)
             u64 *const base = xdir ? xo.out + ((row * 4) * xo.M + l) * N : acc + ((row * K + h) * 2) * LN + (size_t)l * N;
             const size_t cstride = xdir ? (size_t)xo.M * N : LN;
             u64 *const po = base + noff;
 #pragma unroll
-            for (int c = 0; c < 2; c++) po[(size_t)c * cstride] = addmod_nb(colacc_reduce<true>(a[q][t][c].v, m, 0 - m.q), mi[c], m.q);
+            for (int c = 0; c < 2; c++) {
+                if constexpr (MAD)
+                    po[(size_t)c * cstride] = addmod_nb(colacc_reduce<true>(a[q][t][c].v, m, 0 - m.q), mi[c], m.q);
+                else
+                    po[(size_t)c * cstride] = addmod(reduce128(a[q][t][c].v, m), mi[c], m.q);
+            }
         }
     }
 }
@@ -349,125 +349,75 @@ __global__ void __launch_bounds__(TPB) stage_a_resident_kernel(const DevConsts *
     }
 }
 
-// one launch over b bin layers whose count is a multiple of the per-thread layer count `bpt`
-static void launch_stage_a_uniform(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const u64 *idx, const u64 *minus,
-                                   const u64 *db, u64 *acc, hipStream_t st, bool mad, u32 bstride, u32 h0, u32 hn, int bpt, u32 nq,
-                                   u32 q, StageAXOut xo)
+// One query (row q of nq) through stage_a_mad_kernel or stage_a_kernel.  Bin layers per thread: a thread re-reads the two
+// index-ciphertext limbs once per group of layers, so groups should be as large as the accumulators allow (cap).  A divisor of b in
+// [4, cap] gives one uniform launch; otherwise (b = 17, 23, ...: one queue's share of an odd split) groups of `cap` layers plus one
+// launch for the remainder -- never one layer per thread, which read the index matrix b times.
+template <bool MAD>
+static void launch_stage_a_one(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const u64 *idx, const u64 *minus, const u64 *db,
+                               u64 *acc, hipStream_t st, u32 bstride, u32 h0, u32 hn, u32 nq, u32 q, StageAXOut xo)
 {
-    const int cpt = mad ? 1 : 2;
-    dim3 grid((N / cpt + TPB - 1) / TPB, L, hn * (b / bpt));
-#define SA(B_)                                                                                                       \
-    do {                                                                                                             \
-        if (mad) hipLaunchKernelGGL(stage_a_mad_kernel<B_>, grid, dim3(TPB), 0, st, dc, N, L, K, b, E, idx, minus, db, acc, bstride, h0, nq, q, xo); \
-        else hipLaunchKernelGGL(stage_a_kernel<B_>, grid, dim3(TPB), 0, st, dc, N, L, K, b, E, idx, minus, db, acc, bstride, h0, nq, q);  \
-    } while (0)
-    switch (bpt) {
-        case 8: hipLaunchKernelGGL(stage_a_kernel<8>, grid, dim3(TPB), 0, st, dc, N, L, K, b, E, idx, minus, db, acc, bstride, h0, nq, q); break;
-        case 7: SA(7); break;
-        case 6: SA(6); break;
-        case 5: SA(5); break;
-        case 4: SA(4); break;
-        case 3: SA(3); break;
-        case 2: SA(2); break;
-        default: SA(1); break;
-    }
-#undef SA
+    constexpr u32 cap = MAD ? 7 : 8;
+    auto uniform = [&](u32 first, u32 nb, u32 bpt) {   // layers [first, first + nb), nb a multiple of bpt
+        const size_t LN = (size_t)L * N;
+        const u64 *dbf = db + (size_t)first * E * LN;
+        u64 *accf = acc + (size_t)first * nq * K * 2 * LN;
+        const dim3 grid((N / (MAD ? 1 : 2) + TPB - 1) / TPB, L, hn * (nb / bpt));
+        with_u32<1, cap>(bpt, [&](auto B_) {
+            if constexpr (MAD) {
+                StageAXOut xf = xo;
+                if (xf.out) xf.out += (size_t)first * nq * 4 * xf.M * N;
+                hipLaunchKernelGGL(stage_a_mad_kernel<(int)B_()>, grid, dim3(TPB), 0, st, dc, N, L, K, nb, E, idx, minus, dbf, accf, bstride, h0, nq, q, xf);
+            } else {
+                hipLaunchKernelGGL(stage_a_kernel<(int)B_()>, grid, dim3(TPB), 0, st, dc, N, L, K, nb, E, idx, minus, dbf, accf, bstride, h0, nq, q);
+            }
+        });
+    };
+    u32 bpt = b <= cap ? b : 0;
+    for (u32 c = cap; c >= 4 && !bpt; c--)
+        if (b % c == 0) bpt = c;
+    if (bpt) return uniform(0, b, bpt);
+    uniform(0, b / cap * cap, cap);
+    uniform(b / cap * cap, b % cap, b % cap);
 }
 
-void launch_stage_a(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const u64 *idx, const u64 *minus,
-                    const u64 *db, u64 *acc, hipStream_t st, bool small_moduli, u32 bstride, u32 h0, u32 hn, u32 nq, u32 q,
-                    const StageAXOut *xop)
+// Stage A of nq >= 1 queries on one handle: acc[b][nq][K][2][L][N].  Groups of two to four queries, ONE launch per group whatever
+// the layer count (a layer count that is no multiple of the per-thread layer count leaves a ragged last group), each reading the
+// database once.  Query groups, layers per thread and terms in flight by the rules of stage_a_common.h (stage_a_for_groups); a group
+// of three on a ring that fills the chip keeps its index words resident instead (stage_a_resident_lpp said so: one partition of
+// `lpp` layers per block), and a single query goes to the one-query kernels.
+template <bool MAD>
+static void launch_stage_a_groups(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const StageAQueries &qs, u32 nq, const u64 *db,
+                                  u64 *acc, hipStream_t st, u32 bstride, u32 h0, u32 hn, StageAXOut xo)
 {
-    StageAXOut xo;
-    if (xop && small_moduli) xo = *xop;  // (the 128-bit kernel keeps writing acc: callers check small_moduli before they rely on xo)
-    if (!bstride) bstride = b;
-    if (!hn) hn = K - h0;
-    if (!nq) nq = 1;
-    const bool mad = small_moduli;
-    const u32 cap = mad ? 7 : 8;
-    // Bin layers per thread: a thread re-reads the two index-ciphertext limbs once per group of layers, so groups should be
-    // as large as the accumulators allow.  A divisor of b in [4, cap] gives one uniform launch; otherwise (b = 17, 23, ...:
-    // one queue's share of an odd split) groups of `cap` layers plus one launch for the remainder -- never one layer per
-    // thread, which read the index matrix b times.
-    u32 bpt = 0;
-    for (u32 c = cap; c >= 4; c--)
-        if (b % c == 0) {
-            bpt = c;
-            break;
+    const u32 nx = (N + TPB - 1) / TPB, tiles = nx * L * hn;
+    stage_a_for_groups<MAD>(qs, nq, b, [&](auto Q_, auto B_, auto D_, const StageAQueries &sub, u32 q0) {
+        if constexpr (Q_() == 1) {   // (BPT and DEPTH are the tiled kernel's)
+            launch_stage_a_one<MAD>(dc, N, L, K, b, E, sub.idx[0], sub.minus[0], db, acc, st, bstride, h0, hn, nq, q0, xo);
+        } else {
+            if constexpr (MAD && Q_() == 3) {
+                const u32 lpp = stage_a_resident_lpp(3, E, b, (u64)N * L * hn);
+                auto resident = [&](auto E_) {
+                    hipLaunchKernelGGL((stage_a_resident_kernel<3, E_(), stage_a_resident_ring(E_())>), stage_a_grid(nx, L, hn, (b + lpp - 1) / lpp),
+                                       dim3(TPB), 0, st, dc, N, L, K, b, lpp, sub, db, acc, bstride, h0, nq, q0, tiles, xo);
+                };
+                if (lpp && E == 14) return resident(std::integral_constant<int, 14>{});
+                if (lpp && E == 12) return resident(std::integral_constant<int, 12>{});
+            }
+            hipLaunchKernelGGL((stage_a_tiled_kernel<(int)B_(), (int)Q_(), (int)D_(), MAD>), stage_a_grid(nx, L, hn, (b + B_() - 1) / B_()), dim3(TPB),
+                               0, st, dc, N, L, K, b, E, sub, db, acc, bstride, h0, nq, q0, tiles, xo);
         }
-    if (b <= cap) bpt = b;
-    const size_t LN = (size_t)L * N;
-    if (bpt) {
-        launch_stage_a_uniform(dc, N, L, K, b, E, idx, minus, db, acc, st, mad, bstride, h0, hn, (int)bpt, nq, q, xo);
-        return;
-    }
-    const u32 full = (b / cap) * cap, rest = b - full;
-    launch_stage_a_uniform(dc, N, L, K, full, E, idx, minus, db, acc, st, mad, bstride, h0, hn, (int)cap, nq, q, xo);
-    StageAXOut xr = xo;
-    if (xr.out) xr.out += (size_t)full * nq * 4 * xr.M * N;
-    launch_stage_a_uniform(dc, N, L, K, rest, E, idx, minus, db + (size_t)full * E * LN, acc + (size_t)full * nq * K * 2 * LN, st, mad,
-                           bstride, h0, hn, (int)rest, nq, q, xr);
-}
-
-// Stage A of a query batch: acc[b][nq][K][2][L][N].  Column-accumulator kernel (every modulus < 2^60): groups of two to four
-// queries per launch, ONE launch per group whatever the layer count (a layer count that is no multiple of the per-thread layer
-// count leaves a ragged last group), each reading the database once; otherwise one launch_stage_a series per query.  Query groups,
-// layers per thread and terms in flight by the rules of stage_a_common.h.
-template <int Q, int BPT>
-static void launch_stage_a_batch_qb(const DevConsts *dc, u32 N, u32 L, u32 K, u32 nb, u32 E, const StageAQueries &qs, const u64 *db,
-                                    u64 *acc, hipStream_t st, u32 bstride, u32 h0, u32 hn, u32 nq, u32 q0, StageAXOut xo)
-{
-    const u32 nx = (N + TPB - 1) / TPB;
-    constexpr int DEPTH = stage_a_depth(Q, BPT);
-    hipLaunchKernelGGL((stage_a_mad_batch_kernel<BPT, Q, DEPTH>), stage_a_grid(nx, L, hn, (nb + BPT - 1) / BPT), dim3(TPB), 0, st, dc, N, L, K,
-                       nb, E, qs, db, acc, bstride, h0, nq, q0, nx * L * hn, xo);
-}
-template <int Q>
-static void launch_stage_a_batch_q(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const StageAQueries &qs, const u64 *db,
-                                   u64 *acc, hipStream_t st, u32 bstride, u32 h0, u32 hn, u32 nq, u32 q0, StageAXOut xo)
-{
-    constexpr u32 cap = stage_a_layer_cap(Q, true);
-    const u32 bpt = stage_a_layers(Q, b, cap);
-    if constexpr (cap >= 4)
-        if (bpt == 4) return launch_stage_a_batch_qb<Q, 4>(dc, N, L, K, b, E, qs, db, acc, st, bstride, h0, hn, nq, q0, xo);
-    if constexpr (cap >= 3)
-        if (bpt == 3) return launch_stage_a_batch_qb<Q, 3>(dc, N, L, K, b, E, qs, db, acc, st, bstride, h0, hn, nq, q0, xo);
-    if (bpt == 2) return launch_stage_a_batch_qb<Q, 2>(dc, N, L, K, b, E, qs, db, acc, st, bstride, h0, hn, nq, q0, xo);
-    return launch_stage_a_batch_qb<Q, 1>(dc, N, L, K, b, E, qs, db, acc, st, bstride, h0, hn, nq, q0, xo);
-}
-// three queries, resident index words (stage_a_resident_lpp said so): `lpp` layers per partition
-template <int E>
-static void launch_stage_a_resident(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 lpp, const StageAQueries &qs, const u64 *db,
-                                    u64 *acc, hipStream_t st, u32 bstride, u32 h0, u32 hn, u32 nq, u32 q0, StageAXOut xo)
-{
-    const u32 nx = (N + TPB - 1) / TPB;
-    hipLaunchKernelGGL((stage_a_resident_kernel<3, E, stage_a_resident_ring(E)>), stage_a_grid(nx, L, hn, (b + lpp - 1) / lpp), dim3(TPB), 0, st,
-                       dc, N, L, K, b, lpp, qs, db, acc, bstride, h0, nq, q0, nx * L * hn, xo);
+    });
 }
 void launch_stage_a_batch(const DevConsts *dc, u32 N, u32 L, u32 K, u32 b, u32 E, const StageAQueries &qs, u32 nq, const u64 *db,
                           u64 *acc, hipStream_t st, bool small_moduli, u32 bstride, u32 h0, u32 hn, const StageAXOut *xop)
 {
     StageAXOut xo;
-    if (xop && small_moduli) xo = *xop;
+    if (xop && small_moduli) xo = *xop;   // (the 128-bit arithmetic keeps writing acc: callers check small_moduli before they rely on xo)
     if (!bstride) bstride = b;
     if (!hn) hn = K - h0;
-    u32 q0 = 0;
-    while (small_moduli && nq - q0 >= 2) {
-        const u32 g = stage_a_query_group(nq - q0);
-        StageAQueries sub = {};
-        for (u32 q = 0; q < g; q++) sub.idx[q] = qs.idx[q0 + q], sub.minus[q] = qs.minus[q0 + q];
-        if (g == 2) launch_stage_a_batch_q<2>(dc, N, L, K, b, E, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
-        else if (g == 3) {
-            const u32 lpp = stage_a_resident_lpp(3, E, b, (u64)N * L * hn);
-            if (lpp && E == 14) launch_stage_a_resident<14>(dc, N, L, K, b, lpp, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
-            else if (lpp && E == 12) launch_stage_a_resident<12>(dc, N, L, K, b, lpp, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
-            else launch_stage_a_batch_q<3>(dc, N, L, K, b, E, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
-        }
-        else launch_stage_a_batch_q<4>(dc, N, L, K, b, E, sub, db, acc, st, bstride, h0, hn, nq, q0, xo);
-        q0 += g;
-    }
-    for (; q0 < nq; q0++)
-        launch_stage_a(dc, N, L, K, b, E, qs.idx[q0], qs.minus[q0], db, acc, st, small_moduli, bstride, h0, hn, nq, q0, xop);
+    if (small_moduli) launch_stage_a_groups<true>(dc, N, L, K, b, E, qs, nq, db, acc, st, bstride, h0, hn, xo);
+    else launch_stage_a_groups<false>(dc, N, L, K, b, E, qs, nq, db, acc, st, bstride, h0, hn, xo);
 }
 
 // ---------------------------------------------------------------------------------------------

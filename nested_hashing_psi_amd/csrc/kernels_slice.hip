@@ -55,55 +55,22 @@ __global__ void __launch_bounds__(TPB) stage_a_slice_kernel(const DevConsts *__r
     }
 }
 
-template <int Q, int BPT, bool MAD>
-static void launch_slice_qb(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, u32 b, u32 E, const StageAQueries &qs, const u64 *db,
-                            u64 *acc, hipStream_t st, u32 nq, u32 q0)
+template <bool MAD>
+static void launch_slice_groups(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, u32 b, u32 E, const StageAQueries &qs, u32 nq,
+                                const u64 *db, u64 *acc, hipStream_t st)
 {
     const u32 nx = (N + TPB - 1) / TPB;
-    constexpr int DEPTH = stage_a_depth(Q, BPT);
-    hipLaunchKernelGGL((stage_a_slice_kernel<BPT, Q, DEPTH, MAD>), stage_a_grid(nx, un, 1, (b + BPT - 1) / BPT), dim3(TPB), 0, st, dc, N, L,
-                       u_lo, un, b, E, qs, db, acc, nq, q0, nx * un);
-}
-template <int Q, bool MAD>
-static void launch_slice_q(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, u32 b, u32 E, const StageAQueries &qs, const u64 *db, u64 *acc,
-                           hipStream_t st, u32 nq, u32 q0)
-{
-    constexpr u32 cap = stage_a_layer_cap(Q, MAD);
-    const u32 bpt = stage_a_layers(Q, b, cap);
-#define SL_(B_)                                                                                                  \
-    if constexpr (cap >= B_)                                                                                     \
-        if (bpt == B_) return launch_slice_qb<Q, B_, MAD>(dc, N, L, u_lo, un, b, E, qs, db, acc, st, nq, q0)
-    SL_(7);
-    SL_(6);
-    SL_(5);
-    SL_(4);
-    SL_(3);
-    SL_(2);
-#undef SL_
-    launch_slice_qb<Q, 1, MAD>(dc, N, L, u_lo, un, b, E, qs, db, acc, st, nq, q0);
-}
-template <bool MAD>
-static void launch_slice_m(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, u32 b, u32 E, const StageAQueries &qs, u32 nq, const u64 *db,
-                           u64 *acc, hipStream_t st)
-{
-    u32 q0 = 0;
-    while (q0 < nq) {
-        const u32 g = stage_a_query_group(nq - q0);
-        StageAQueries sub = {};
-        for (u32 q = 0; q < g; q++) sub.idx[q] = qs.idx[q0 + q], sub.minus[q] = qs.minus[q0 + q];
-        if (g == 1) launch_slice_q<1, MAD>(dc, N, L, u_lo, un, b, E, sub, db, acc, st, nq, q0);
-        else if (g == 2) launch_slice_q<2, MAD>(dc, N, L, u_lo, un, b, E, sub, db, acc, st, nq, q0);
-        else if (g == 3) launch_slice_q<3, MAD>(dc, N, L, u_lo, un, b, E, sub, db, acc, st, nq, q0);
-        else launch_slice_q<4, MAD>(dc, N, L, u_lo, un, b, E, sub, db, acc, st, nq, q0);
-        q0 += g;
-    }
+    stage_a_for_groups<MAD>(qs, nq, b, [&](auto Q_, auto B_, auto D_, const StageAQueries &sub, u32 q0) {
+        hipLaunchKernelGGL((stage_a_slice_kernel<(int)B_(), (int)Q_(), (int)D_(), MAD>), stage_a_grid(nx, un, 1, (b + B_() - 1) / B_()), dim3(TPB), 0,
+                           st, dc, N, L, u_lo, un, b, E, sub, db, acc, nq, q0, nx * un);
+    });
 }
 void launch_stage_a_slice(const DevConsts *dc, u32 N, u32 L, u32 u_lo, u32 un, u32 b, u32 E, const StageAQueries &qs, u32 nq, const u64 *db,
                           u64 *acc, hipStream_t st, bool small_moduli)
 {
     if (!un || !b || !nq) return;
-    if (small_moduli) launch_slice_m<true>(dc, N, L, u_lo, un, b, E, qs, nq, db, acc, st);
-    else launch_slice_m<false>(dc, N, L, u_lo, un, b, E, qs, nq, db, acc, st);
+    if (small_moduli) launch_slice_groups<true>(dc, N, L, u_lo, un, b, E, qs, nq, db, acc, st);
+    else launch_slice_groups<false>(dc, N, L, u_lo, un, b, E, qs, nq, db, acc, st);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -302,12 +302,7 @@ static void enqueue_run_bins_full(Sched &s, u32 b0, u32 nb, u64 *results, bool c
         const u64 *db = h->d_db + (size_t)b0 * E * LN;
         StageAXOut xo;
         if (x_direct) xo.out = h->ws.eqp + r0 * 4 * M * N, xo.M = M, xo.logns = h->plan.lane_logn;
-        if (nq > 1) {
-            launch_stage_a_batch(h->d_dc, N, L, K, layers, E, qs, nq, db, acc, s.stream, h->plan.small_moduli, b, 0, 0, x_direct ? &xo : nullptr);
-        } else {
-            launch_stage_a(h->d_dc, N, L, K, nb, E, qs.idx[0], qs.minus[0], db, acc, s.stream, h->plan.small_moduli, b, 0, 0, 1, 0,
-                           x_direct ? &xo : nullptr);
-        }
+        launch_stage_a_batch(h->d_dc, N, L, K, layers, E, qs, nq, db, acc, s.stream, h->plan.small_moduli, b, 0, 0, x_direct ? &xo : nullptr);
     }
     enqueue_chain_bins(s, b0, layers, results);
 }

@@ -1,10 +1,13 @@
 // stage_a_common.h -- what the stage A kernels of kernels_pie.hip (the whole query on one handle) and kernels_slice.hip (one handle's
 // (inner hash function, limb) units) share: the block -> tile map, the lane-ordered home of a coefficient, the instruction blocks of
 // the epilogue (column accumulator -> residue, the sum with the minus word), the term loop of the tiled kernels (stage_a_terms:
-// stage_a_mad_batch_kernel and stage_a_slice_kernel are a prologue and an epilogue around it), the multiply-add block of the
+// stage_a_tiled_kernel and stage_a_slice_kernel are a prologue and an epilogue around it), the multiply-add block of the
 // resident kernel (colacc_mac2_cut) and, for the launchers, the rules that pick query groups, bin layers per thread, terms in flight
-// and the resident or the tiled kernel (stage_a_query_group, stage_a_layers, stage_a_depth, stage_a_resident_lpp).
+// and the resident or the tiled kernel (stage_a_query_group, stage_a_layers, stage_a_depth, stage_a_resident_lpp) and the one
+// dispatch that turns them into template arguments (stage_a_for_groups).
 #pragma once
+#include <type_traits>
+
 #include "kernels.hpp"
 #include "madasm.h"
 
@@ -395,6 +398,19 @@ __device__ __forceinline__ void colacc_mac2_cut(ColAcc &a, ColAcc &b, Split30 x0
 // ---------------------------------------------------------------------------------------------
 // Launch rules of the tiled kernels (launch_stage_a_batch, launch_stage_a_slice).
 // ---------------------------------------------------------------------------------------------
+// A run-time value as a template argument: with_u32<LO, HI>(v, f) calls f(std::integral_constant<u32, v>) for v in [LO, HI] and says
+// whether it did.  The callers' generic lambdas read the argument as a constant (L_()).
+template <u32 LO, u32 HI, class F>
+static bool with_u32(u32 v, F &&f)
+{
+    if constexpr (LO <= HI) {
+        if (v != LO) return with_u32<LO + 1, HI>(v, f);
+        f(std::integral_constant<u32, LO>{});
+        return true;
+    }
+    return false;
+}
+
 // Queries of the next launch, given the queries left: groups of four, three or two (five: 3 + 2; six: 3 + 3; seven: 4 + 3); a single
 // one alone.
 constexpr u32 stage_a_query_group(u32 left) { return left == 5 || left == 6 ? 3 : left < 4 ? left : 4; }
@@ -428,6 +444,24 @@ static_assert(stage_a_layers(3, 12, stage_a_layer_cap(3, true)) == 3, "twelve la
 // query: stage_a_mad_kernel's four, and three with seven layers (176 registers with four, 168 are the most that leave three waves
 // per SIMD).
 constexpr int stage_a_depth(int Q, int BPT) { return Q == 1 ? (BPT == 7 ? 3 : 4) : (Q == 4 || Q * BPT >= 9) ? 2 : 3; }
+
+// The rules as ONE dispatch: walks the query groups of a batch and calls f(Q, BPT, DEPTH, sub, q0) per group -- queries per thread,
+// layers per thread and terms in flight as std::integral_constant<u32, ...>, the group's queries and the index of its first one.
+template <bool MAD, class F>
+static void stage_a_for_groups(const StageAQueries &qs, u32 nq, u32 b, F &&f)
+{
+    for (u32 q0 = 0, g; q0 < nq; q0 += g) {
+        g = stage_a_query_group(nq - q0);
+        StageAQueries sub = {};
+        for (u32 q = 0; q < g; q++) sub.idx[q] = qs.idx[q0 + q], sub.minus[q] = qs.minus[q0 + q];
+        with_u32<1, 4>(g, [&](auto Q_) {
+            constexpr u32 Q = Q_(), cap = stage_a_layer_cap(Q, MAD);
+            with_u32<1, cap>(stage_a_layers(Q, b, cap), [&](auto B_) {
+                f(Q_, B_, std::integral_constant<u32, (u32)stage_a_depth((int)Q, (int)B_())>{}, sub, q0);
+            });
+        });
+    }
+}
 
 // The resident kernel (stage_a_resident_kernel) or the tiled one, for a launch of Q queries over b layers with `threads` = N L hn
 // coefficients.  -DPIEHIP_STAGE_A_RESIDENT=0 keeps every launch on the tiled kernel (A/B builds).

@@ -125,7 +125,7 @@ def test_c3_serial_queue_all_layers(ob, pie_mod):
 
 @pytest.mark.parametrize("streams", [0, 1])
 def test_c3_headline_batch_of_three(ob, pie_mod, streams):
-    """bench.py's default timed region itself: C3 with setQueryBatch(3) on ONE handle (b = 14, E = 14 -> stage_a_mad_batch_kernel<2,3>
+    """bench.py's default timed region itself: C3 with setQueryBatch(3) on ONE handle (b = 14, E = 14 -> the Q = 3 stage A launch
     over seven layer pairs; transform launches of 1 344 / 2 352 / 2 268 / 2 016 slices), three different real queries, on two queues
     (8 + 6 bin layers, the default) and on one (bench.py --streams 1, the per-kernel profile passes): every query's 14 result
     ciphertexts equal the oracle's run() of that query alone, and each decrypts to its own client's intersection."""

@@ -2,7 +2,7 @@
 
 launch_stage_a_batch sends a group of three queries to that kernel where stage_a_resident_lpp (stage_a_common.h) says so: E = 14 or
 E = 12 (the two instantiations), more layers than one tiled group holds (b > 3), and at least STAGE_A_RESIDENT_MIN_THREADS = 65 536
-coefficients N L K in the launch.  Every other launch stays on the tiled kernel (stage_a_mad_batch_kernel), so the cases sit on both
+coefficients N L K in the launch.  Every other launch stays on the tiled kernel (stage_a_tiled_kernel), so the cases sit on both
 sides of each condition and mix the two kernels in one run():
   E       1, 7, 8, 9 and 15 are tiled (no instantiation; 15 is past what a thread's registers hold), 12 and 14 resident -- both
           cross the kernel's one carry sweep (after term 8), and every word q - 1 overflows column 1 at once if the sweep is lost

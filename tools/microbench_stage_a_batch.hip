@@ -30,7 +30,7 @@ static void run(bool same_idx, u32 Bl = B)   // Bl: bin layers of this launch (<
     for (int rep = 0; rep < NREP; rep++) {
         const u64 *db = g_db + (size_t)(rep % NBUF) * DBW;
         CK(hipEventRecord(e0, 0));
-        hipLaunchKernelGGL((stage_a_mad_batch_kernel<BPT, Q, DEPTH>), grid, dim3(TPB), 0, 0, g_dc, N, L, K, Bl, E, qs, db, g_acc, B, 0u, (u32)Q, 0u, tiles, StageAXOut{});
+        hipLaunchKernelGGL((stage_a_tiled_kernel<BPT, Q, DEPTH, true>), grid, dim3(TPB), 0, 0, g_dc, N, L, K, Bl, E, qs, db, g_acc, B, 0u, (u32)Q, 0u, tiles, StageAXOut{});
         CK(hipEventRecord(e1, 0));
         CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));

@@ -11,7 +11,7 @@ rows = [r for r in csv.DictReader(open(sys.argv[1])) if r["Kind"] == "KERNEL_DIS
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 short = lambda n: re.sub(r"\(.*", "", re.sub(r"^void ", "", n)).replace("piehip::", "").replace("ntt16::", "")
 # the step's launch sequence: everything between two launches of the stage A kernel
-marks = [i for i, r in enumerate(rows) if "stage_a_mad" in r["Kernel_Name"]]
+marks = [i for i, r in enumerate(rows) if "stage_a" in r["Kernel_Name"]]
 steps = [rows[a:b] for a, b in zip(marks, marks[1:])]
 length = statistics.mode(len(s) for s in steps)
 steps = [s for s in steps if len(s) == length]
