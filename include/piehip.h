@@ -279,7 +279,11 @@ int piehip_copy_results_device(piehip_handle h, void *d_dst);
  *   piehip_gather_results        out: the only exchange of the evaluation itself.  After piehip_run on every rank, each rank's
  *                                result rows travel to `root` (the rank that answers the client: sendResult, .cpp:143-152) --
  *                                exact sizes, one transfer per rank, each over its own xGMI link.  d_out on the root:
- *                                [b_total][nq][2][L][N] in bin order, caller-owned HBM; ignored elsewhere.
+ *                                [b_total][nq][ncomp][rl][N] in bin order, caller-owned HBM; ignored elsewhere.  ncomp and rl are
+ *                                the handle's piehip_get_result_components and min(piehip_get_result_limbs, piehip_get_chain_limbs)
+ *                                (the former alone for K = 1): 2 and L unless a setting says otherwise.  b_total counts what the
+ *                                ranks share out: TILED layers on a tiled database (piehip_set_layer_tiling).  Rows of any other
+ *                                shape than [2][L][N] travel only after piehip_rccl_agree_rows (below): PIEHIP_ESTATE otherwise.
  * RCCL is bound at run time (the copy already in the process, else /opt/rocm's): a one-GPU deployment never loads it.
  *   piehip_rccl_unique_id   ncclGetUniqueId: 128 bytes made on one rank and handed to the others by the caller's own means
  *   piehip_rccl_init        ncclCommInitRank on the handle's device (collective over the nranks processes); the handle owns it
@@ -296,7 +300,7 @@ int piehip_rccl_broadcast(piehip_handle h, int root, void *d_buf, size_t bytes);
 int piehip_rccl_broadcast_query(piehip_handle h, int root);
 int piehip_gather_results(piehip_handle h, uint32_t b_total, int root, void *d_out);
 /* the same, with the gathered list brought down to host memory on the root: *results (root only; NULL elsewhere) is a page-locked
- * array [b_total][nq][2][L][N] owned by the handle, complete after piehip_sync -- what sendResult (.cpp:143-152) reads */
+ * array [b_total][nq][ncomp][rl][N] owned by the handle, complete after piehip_sync -- what sendResult (.cpp:143-152) reads */
 int piehip_gather_results_host(piehip_handle h, uint32_t b_total, int root, uint64_t **results);
 /* Nobody waits for the other ranks without a bound.  A collective completes when EVERY rank has queued its side; a rank that
  * never does (it died; it returned an error from one of the calls above before anything was queued) would leave its peers'
@@ -309,7 +313,16 @@ int piehip_gather_results_host(piehip_handle h, uint32_t b_total, int root, uint
  *   piehip_rccl_abort   the same on purpose: a rank on its way out tears its side down, its peers' waits end at once
  *   piehip_rccl_agree   *all_ok = (every rank passed ok != 0): one all-reduced word + piehip_rccl_wait; called at the end of a phase
  *                       (database built, key loaded) so that a failure on one rank ends the session on all of them BEFORE anybody
- *                       enters a collective the failed rank will not join.  Not part of the per-query path. */
+ *                       enters a collective the failed rank will not join.  Not part of the per-query path.
+ *   piehip_rccl_agree_rows   the same mechanism for the shape of a result row.  Collective: every rank contributes (ncomp, rl, nq)
+ *                       as its handle stands; *same = 1 on every rank if and only if all ranks gave equal triples (one min-reduction
+ *                       over the values and their negations + piehip_rccl_wait).  On same = 1 the handle remembers the triple, and
+ *                       piehip_gather_results(_host) moves rows of that shape.  Every call that can change the triple forgets it:
+ *                       piehip_set_result_limbs, _set_result_relin, _set_chain_limbs, _set_chain_schedule, _set_query_batch, every
+ *                       database load or build, piehip_rccl_init / _attach / _abort.  A gather on a handle whose rows are not
+ *                       [2][L][N] and whose triple is not the remembered one returns PIEHIP_ESTATE before anything is queued: a rank
+ *                       that forgot to agree fails on its own and never posts a transfer of the wrong size.  Handles at the default
+ *                       shape need no agreement.  Not part of the per-query path. */
 /* Query slices across the ranks ("Query slices" below; the plan of both calls and of the gather: csrc/exchange_plan.h).  Rank r of G is a query-sliced
  * handle with the units of piehip_query_slice(K, L, G, r) and the bin layers of piehip_rccl_bin_slice(b, G, r); no rank needs the
  * whole query, and no rank but the root ever holds it.  Per batch of queries, every rank calls, in this order: piehip_rccl_scatter_query,
@@ -338,6 +351,7 @@ int piehip_rccl_exchange_accumulators(piehip_handle h);
 int piehip_rccl_wait(piehip_handle h, uint32_t timeout_ms);
 int piehip_rccl_abort(piehip_handle h);
 int piehip_rccl_agree(piehip_handle h, int ok, int *all_ok, uint32_t timeout_ms);
+int piehip_rccl_agree_rows(piehip_handle h, uint32_t timeout_ms, int *same);
 
 /* ---- the OpenFHE primitives under run(), exposed one by one for kernel-level parity tests ------
  * (host buffers in, host buffers out; synchronous) */
@@ -387,9 +401,9 @@ int piehip_base_convert(piehip_handle h, int which, const uint64_t *in, uint32_t
  *                            has that kernel and the forward transform of the kept limbs left.
  *   piehip_get_result_limbs  the setting.
  * PIEHIP_EINVAL: keep == 0 or keep > L.  PIEHIP_ESTATE: keep < L on a handle with piehip_set_graph(1), and piehip_set_graph(1) on a
- * handle with keep < L (the captured graph stays one plain query per run()).  piehip_gather_results(_host) REFUSES (PIEHIP_ESTATE) a
- * handle with keep < L: the ranks' row sizes would have to agree and nothing checks that across ranks.  piehip_fhepie_* ignores the
- * setting. */
+ * handle with keep < L (the captured graph stays one plain query per run()).  piehip_gather_results(_host) gathers the rows of a
+ * handle with keep < L once the ranks have compared their row shapes (piehip_rccl_agree_rows, after the setting; PIEHIP_ESTATE
+ * until then): both ends of a transfer then name one size.  piehip_fhepie_* ignores the setting. */
 int piehip_mod_reduce(piehip_handle h, const uint64_t *in /*[nct][2][L][N]*/, uint32_t nct, uint32_t keep,
                       uint64_t *out /*[nct][2][keep][N]*/);
 int piehip_set_result_limbs(piehip_handle h, uint32_t keep);
@@ -432,8 +446,8 @@ int piehip_get_result_limbs(piehip_handle h, uint32_t *keep);
  * piehip_client_decrypt_budget with ncomp = 3 measures what a three-component row has left.
  * PIEHIP_ESTATE: on = 0 on a handle with piehip_set_graph(1), and piehip_set_graph(1) on a handle with on = 0 (the captured graph
  * stays the reference's run()); on = 0 on a query-sliced handle (piehip_load_db*_sliced), and a sliced load on a handle with on = 0.
- * piehip_gather_results(_host) REFUSES (PIEHIP_ESTATE) a handle with on = 0, for the reason it refuses keep < L.  piehip_fhepie_*
- * ignores the setting.
+ * piehip_gather_results(_host) gathers three-component rows under the condition of keep < L: after piehip_rccl_agree_rows, and
+ * PIEHIP_ESTATE until then.  piehip_fhepie_* ignores the setting.
  *   piehip_client_decrypt_deg2  Decrypt + GetPackedValue of three-component rows ct[nct][3][L][N] -> slots[nct][B] (centred):
  *                            c0 + c1 s + c2 s^2 on the handle's chain (rows reduced to keep < L limbs decrypt on a context of the
  *                            chain q[:keep] with the first keep limbs of the key, as two-component ones do). */
@@ -480,7 +494,8 @@ int piehip_client_decrypt_deg2(piehip_handle h, const uint64_t *sk, const uint64
  * The L-2 column and the third row do NOT decrypt: the setting is the caller's responsibility.
  * PIEHIP_EINVAL: Lc = 0 or Lc > L.  PIEHIP_ESTATE (the handle stays usable): Lc < L on a handle with piehip_set_graph(1), and
  * piehip_set_graph(1) on a handle with Lc < L; Lc < L on a query-sliced handle, and a sliced load on a handle with Lc < L;
- * piehip_gather_results(_host) on a handle with Lc < L.  piehip_fhepie_* ignores the setting.  Added without a new version number:
+ * piehip_gather_results(_host) on a handle whose rows have fewer than L limbs by this setting, until the ranks have agreed on the
+ * row shape (piehip_rccl_agree_rows).  piehip_fhepie_* ignores the setting.  Added without a new version number:
  * look the symbols up; nothing of 102 changed. */
 int piehip_set_chain_limbs(piehip_handle h, uint32_t Lc);
 int piehip_get_chain_limbs(piehip_handle h, uint32_t *Lc);

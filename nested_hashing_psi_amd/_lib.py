@@ -111,6 +111,7 @@ SYMBOLS = {
     "piehip_rccl_wait": (C.c_int, [C.c_void_p, C.c_uint32]),
     "piehip_rccl_abort": (C.c_int, [C.c_void_p]),
     "piehip_rccl_agree": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_uint32]),
+    "piehip_rccl_agree_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]),
     "piehip_expand_uniform": (C.c_int, [C.c_void_p, u8p, C.c_uint32, u64p]),
     "piehip_expand_uniform_device": (C.c_int, [C.c_void_p, u8p, C.c_uint32, C.c_void_p]),
     "piehip_stage_minus_seeded_q": (C.c_int, [C.c_void_p, C.c_uint32, u64p, u8p]),

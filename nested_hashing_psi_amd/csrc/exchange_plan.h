@@ -17,9 +17,11 @@
 //             of everybody's.  b is outermost, so that is one contiguous block per (s, d).  d receives it into a staging buffer
 //             at offset bin_n_d nq 2N u_lo_s: block after block in unit order, each [bin_n_d][nq][u_n_s][2][N].  Its own rows never
 //             leave acc_slice.  A transfer with u_n_s = 0 or bin_n_d = 0 does not exist, on either side.
-//   gather    rank r has the result rows [bin_n_r][nq][2][L][N] of its bin layers.  The root posts one receive per peer with layers, in
-//             ascending rank, straight into the rows at bin_lo_r of its list [b][nq][2][L][N]; such a peer posts one send of its result
-//             buffer.  A rank without layers posts nothing; the root's own rows are a device copy outside the plan.
+//   gather    rank r has the result rows [bin_n_r][nq][ncomp][rl][N] of its bin layers: ncomp components on rl limbs each, 2 and L
+//             unless a setting of the handles says otherwise (plan_row_words; the ranks have agreed on it: piehip_rccl_agree_rows).
+//             The root posts one receive per peer with layers, in ascending rank, straight into the rows at bin_lo_r of its list
+//             [b][nq][ncomp][rl][N]; such a peer posts one send of its result buffer.  A rank without layers posts nothing; the root's
+//             own rows are a device copy outside the plan.
 //
 // Posting order.  A rank walks its peers in ascending rank; towards a higher-ranked peer it posts its send first and then its
 // receive, towards a lower-ranked peer its receive first and then its send.  RCCL does not care about the order inside a group; a
@@ -40,6 +42,8 @@ namespace piehip {
 
 struct ExchangeShape {
     uint32_t K, L, b, nq, N, E;   // (E: ciphertexts per unit of the index matrix; the scatter's sizes only)
+    // a result ciphertext as the gather moves it: components, and limbs per component (0: all L)
+    uint32_t ncomp = 2, row_limbs = 0;
 };
 
 // [lo, hi) of `total` things for rank r of G: contiguous, sizes differ by at most one (piehip_query_slice, piehip_rccl_bin_slice)
@@ -59,8 +63,8 @@ enum PlanBuffer {
     PLAN_OWN_MINUS,     // ... minus slice [u_n][2][N]
     PLAN_ACC_SLICE,     // the rank's acc_slice[b][nq][u_n][2][N]
     PLAN_ACC_STAGE,     // the rank's staging buffer of received blocks, bin_n nq 2N K L words
-    PLAN_RESULT_ROWS,   // the result rows of this rank, [bin_n][nq][2][L][N]
-    PLAN_GATHERED       // the gathered list at the root, [b][nq][2][L][N]
+    PLAN_RESULT_ROWS,   // the result rows of this rank, [bin_n][nq][ncomp][rl][N]
+    PLAN_GATHERED       // the gathered list at the root, [b][nq][ncomp][rl][N]
 };
 
 // one transfer as one of its two ranks sees it; offsets and sizes in words
@@ -121,11 +125,14 @@ inline std::vector<PlanTransfer> exchange_plan(const ExchangeShape &s, int G, in
     return out;
 }
 
+// words of one bin layer's result rows: its nq result ciphertexts of ncomp components on rl limbs
+static inline size_t plan_row_words(const ExchangeShape &s) { return (size_t)s.nq * s.ncomp * (s.row_limbs ? s.row_limbs : s.L) * s.N; }
+
 // the transfers rank r posts in piehip_gather_results, in posting order (static: the library's dynamic symbol table stays as it was)
 static inline std::vector<PlanTransfer> gather_plan(const ExchangeShape &s, int G, int r, int root)
 {
     std::vector<PlanTransfer> out;
-    const size_t row = (size_t)s.nq * 2 * s.L * s.N;   // words per bin layer: its nq result ciphertexts
+    const size_t row = plan_row_words(s);
     for (int p = 0; p < G; p++) {
         if (p == root || (r != root && p != r)) continue;
         uint32_t lo, hi;

@@ -495,6 +495,7 @@ static int alloc_workspace(piehip_ctx *h, u32 K, u32 b)
 extern "C++" int piehip::alloc_run_buffers(piehip_ctx *h, u32 K, u32 b, u32 E, bool with_db)
 {
     drop_graph(h);  // the captured launches hold the addresses and shapes of the buffers below
+    h->forget_rows();  // K decides the components and limbs of a result row
     if (with_db) slice_free(h);  // a whole database from here on: no longer a query-sliced handle
     if (h->db_borrowed && with_db) {  // a database of its own from here on; the key goes back too (load it again)
         detach_database(h);
@@ -983,6 +984,7 @@ int piehip_set_query_batch(piehip_handle h, uint32_t nq)
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     drop_graph(h);
+    h->forget_rows();
     h->stage_open = false;
     // caller-owned device pointers of queries outside the new batch are forgotten (they may be freed by now); a later, larger
     // batch must set them again.  Per-query keys are sized by the batch: load them again after a change.
@@ -1116,6 +1118,7 @@ int piehip_set_result_limbs(piehip_handle h, uint32_t keep)
     if (keep < h->hp.L && h->use_graph)
         return fail(PIEHIP_ESTATE, "set_result_limbs: a handle that replays a captured graph (piehip_set_graph) hands out full results");
     HIPCHK(hipSetDevice(h->device));
+    h->forget_rows();
     const u32 before = h->res_limbs;
     h->res_limbs = keep;
     const int rc = ensure_full_rows(h, h->K);
@@ -1139,6 +1142,7 @@ int piehip_set_result_relin(piehip_handle h, int on)
         return fail(PIEHIP_ESTATE, "set_result_relin: a handle that replays a captured graph (piehip_set_graph) relinearises its results");
     if (!on && h->slice.on) return fail(PIEHIP_ESTATE, "set_result_relin: a query-sliced handle relinearises its results");
     HIPCHK(hipSetDevice(h->device));
+    h->forget_rows();
     const bool before = h->res_relin;
     h->res_relin = on != 0;
     const int rc = ensure_full_rows(h, h->K);
@@ -1260,6 +1264,7 @@ int piehip_set_chain_schedule(piehip_handle h, const uint32_t *Lc, uint32_t n)
         lv->cx.N = h->hp.N, lv->cx.L = Lc[i], lv->cx.M = lv->hp.M;
         h->levels.emplace(Lc[i], std::move(lv));
     }
+    h->forget_rows();
     u32 before[MAX_CHAIN_SCHED];
     const u32 n_before = h->chain_n;
     std::copy(h->chain_sched, h->chain_sched + MAX_CHAIN_SCHED, before);

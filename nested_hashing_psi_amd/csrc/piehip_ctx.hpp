@@ -264,8 +264,13 @@ struct piehip_ctx {
     void *comm = nullptr;
     bool comm_owned = false;
     int comm_ranks = 0, comm_rank = 0;
-    u64 *d_gather = nullptr, *pin_gather = nullptr;   // the root's gathered result list [b_total][nq][2][L][N]: HBM, page-locked host
+    u64 *d_gather = nullptr, *pin_gather = nullptr;   // the root's gathered result list [b_total][nq][ncomp][rl][N]: HBM, page-locked host
     size_t gather_words = 0;
+    // piehip_rccl_agree_rows: the row shape (components, limbs, queries) every rank of the communicator had when they last compared;
+    // forgotten (forget_rows) by every call that can change this handle's.  The gather moves rows of another shape than the default
+    // [2][L][N] only while the handle's shape is the agreed one
+    bool rows_agreed = false;
+    u32 rows_ncomp = 0, rows_limbs = 0, rows_nq = 0;
     piehip::SliceState slice;
     // rotation-based PIE (FHEHIPPIE): rotation keys by index, EVALUATION index maps, packed sub-tables
     std::map<int32_t, u64 *> rotkeys;   // [L][2][L][N] each
@@ -296,6 +301,7 @@ struct piehip_ctx {
     // limbs of a result row: the minimum of the two settings (chain limbs change nothing where there is no product: K = 1)
     u32 out_limbs() const { return K >= 2 ? std::min(res_limbs, chain_last()) : res_limbs; }
     size_t res_ct_words() const { return res_comps() * (size_t)out_limbs() * hp.N; }   // one result ciphertext as it leaves the handle
+    void forget_rows() { rows_agreed = false; }
 };
 
 namespace piehip {

@@ -145,6 +145,7 @@ void set_comm(piehip_ctx *h, void *comm, bool owned, int nranks, int rank)
     h->comm_owned = owned;
     h->comm_ranks = nranks;
     h->comm_rank = rank;
+    h->forget_rows();   // what was agreed was agreed with the ranks of another communicator
 }
 void forget_comm(piehip_ctx *h) { set_comm(h, nullptr, false, 0, 0); }
 
@@ -311,15 +312,57 @@ int piehip_rccl_bin_slice(uint32_t b_total, int nranks, int rank, uint32_t *bin_
     return PIEHIP_OK;
 }
 
+// Rows of another shape than two components on L limbs (piehip_set_result_limbs, piehip_set_result_relin, piehip_set_chain_limbs /
+// _schedule).  Both ends of a transfer must name one size, and a setting is a rank's own: so the ranks compare (components, limbs,
+// queries) once, after the settings and before the first gather, and every handle remembers what all of them had.  Mechanism of
+// piehip_rccl_agree: one min-reduction over the three values and their negations -- min(v) = -min(-v) exactly where all ranks gave one v.
+int piehip_rccl_agree_rows(piehip_handle h, uint32_t timeout_ms, int *same)
+{
+    NEED(h);
+    if (!same) return fail(PIEHIP_EINVAL, "null result");
+    if (!h->comm) return fail(PIEHIP_ESTATE, "rccl_agree_rows: no communicator");
+    NEED_RCCL(R);
+    if (!R->AllReduce) return fail(PIEHIP_EHIP, "rccl_agree_rows: this RCCL has no ncclAllReduce");
+    HIPCHK(hipSetDevice(h->device));
+    h->forget_rows();
+    const u32 mine[3] = {h->res_comps(), h->out_limbs(), h->nq};
+    Tmp tmp(h);
+    TMPGET(d_words, 3);   // (six int32)
+    int32_t *pin = nullptr;
+    HIPCHK(hipHostMalloc((void **)&pin, 64, hipHostMallocPortable));
+    for (int i = 0; i < 3; i++) pin[i] = (int32_t)mine[i], pin[3 + i] = -(int32_t)mine[i];
+    int rc = PIEHIP_OK;
+    do {
+        if (hipMemcpyAsync(d_words, pin, 24, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(PIEHIP_EHIP, "rccl_agree_rows: upload"); break; }
+        const ncclResult_t r = R->AllReduce(d_words, d_words, 6, ncclInt32, ncclMin, (ncclComm_t)h->comm, h->stream);
+        if (r != ncclSuccess) { rc = fail(PIEHIP_EHIP, std::string("rccl_agree_rows: ") + R->GetErrorString(r)); break; }
+        if (hipMemcpyAsync(pin, d_words, 24, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { rc = fail(PIEHIP_EHIP, "rccl_agree_rows: download"); break; }
+        rc = piehip_rccl_wait(h, timeout_ms);
+    } while (0);
+    if (rc == PIEHIP_OK) {
+        bool all = true;
+        for (int i = 0; i < 3; i++) all = all && pin[i] == -pin[3 + i];
+        *same = all ? 1 : 0;
+        if (all) h->rows_agreed = true, h->rows_ncomp = mine[0], h->rows_limbs = mine[1], h->rows_nq = mine[2];
+    }
+    (void)hipHostFree(pin);
+    return rc;
+}
+
 // what both gather calls refuse first
 static int gather_check(const piehip_ctx *h, int root, bool has_dest)
 {
-    if (!h->res_relin)   // (the same reason)
-        return fail(PIEHIP_ESTATE, "gather_results: unrelinearised results (piehip_set_result_relin) are not gathered");
-    if (h->res_limbs != h->hp.L)   // the ranks' row sizes would have to agree, and nothing checks a setting across ranks
-        return fail(PIEHIP_ESTATE, "gather_results: results reduced to fewer limbs (piehip_set_result_limbs) are not gathered");
-    if (h->chain_floor() != h->hp.L)   // (likewise)
-        return fail(PIEHIP_ESTATE, "gather_results: results of a chain on fewer limbs (piehip_set_chain_limbs) are not gathered");
+    // the default row needs no agreement (every rank that has it posts the sizes it always posted); any other travels only as agreed.
+    // First of all, as the settings' refusals it replaces: a handle without a communicator has agreed on nothing
+    const u32 ncomp = h->res_comps(), rl = h->out_limbs(), L = h->hp.L;
+    if ((ncomp != 2 || rl != L) && !(h->rows_agreed && h->rows_ncomp == ncomp && h->rows_limbs == rl && h->rows_nq == h->nq)) {
+        std::string by;   // the settings that shaped the row
+        if (ncomp != 2) by += " piehip_set_result_relin";
+        if (h->res_limbs != L) by += " piehip_set_result_limbs";
+        if (h->K >= 2 && h->chain_last() != L) by += " piehip_set_chain_limbs";
+        return fail(PIEHIP_ESTATE, "gather_results: result rows of " + std::to_string(ncomp) + " components on " + std::to_string(rl) + " limbs (" +
+                                       by.substr(1) + "): the ranks have not agreed on this shape since it was set (piehip_rccl_agree_rows)");
+    }
     if (!h->comm) return fail(PIEHIP_ESTATE, "gather_results: no communicator (piehip_rccl_init / piehip_rccl_attach)");
     if (root < 0 || root >= h->comm_ranks) return fail(PIEHIP_EINVAL, "gather_results: root outside the communicator");
     if (h->comm_rank == root && !has_dest) return fail(PIEHIP_EINVAL, "gather_results: the root needs a destination");
@@ -339,10 +382,10 @@ int piehip_gather_results(piehip_handle h, uint32_t b_total, int root, void *d_o
     NEED_RCCL(R);
     HIPCHK(hipSetDevice(h->device));
     // exact sizes, no padding: each slice crosses its own xGMI link once, straight into its rows of d_out; the root's own rows are a device copy
-    const ExchangeShape shape = {h->K, h->hp.L, b_total, h->nq, h->hp.N, h->E};
+    const ExchangeShape shape = {h->K, h->hp.L, b_total, h->nq, h->hp.N, h->E, h->res_comps(), h->out_limbs()};
     auto base = [&](const PlanTransfer &t) -> u64 * { return t.buf == PLAN_GATHERED ? (u64 *)d_out : h->d_out; };
     if ((rc = post_transfers(h, R, gather_plan(shape, G, me, root), base, "gather_results"))) return rc;
-    const size_t row = (size_t)h->nq * 2 * h->LN();   // words per bin layer: its nq result ciphertexts
+    const size_t row = plan_row_words(shape);   // words per bin layer: its nq result ciphertexts
     if (me == root && hi > lo)
         HIPCHK(hipMemcpyAsync((u64 *)d_out + (size_t)lo * row, h->d_out, (size_t)(hi - lo) * row * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
     return PIEHIP_OK;
@@ -356,7 +399,7 @@ int piehip_gather_results_host(piehip_handle h, uint32_t b_total, int root, uint
     const bool is_root = h->comm_rank == root;
     if (is_root) {   // the device half is a kept buffer; the page-locked half goes when that is replaced
         HIPCHK(hipSetDevice(h->device));
-        const size_t words = (size_t)b_total * h->nq * 2 * h->LN();
+        const size_t words = (size_t)b_total * h->nq * h->res_ct_words();
         const bool same = h->gather_words == words;
         if ((rc = keep_buffer(h, &h->d_gather, &h->gather_words, words))) return rc;   // (drains the stream before it replaces)
         if (!same && h->pin_gather) (void)hipHostFree(h->pin_gather), h->pin_gather = nullptr;

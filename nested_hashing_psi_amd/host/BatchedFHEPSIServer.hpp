@@ -50,11 +50,17 @@ inline ContextMessage readContextMessage(int fd)
 }
 
 // The EvalMult key message as words [L][2][L][N], the modulus index being the innermost L.  moduli (q_0..q_{L-1}) given: the key-switch
-// accumulators take canonical residues only; null where the sender has checked what it forwards.
-inline std::vector<uint64_t> readEvalMultKey(int fd, const ContextMessage &c, const uint64_t *moduli)
+// accumulators take canonical residues only; null where the sender has checked what it forwards.  An EMPTY message is a client that
+// sends no key: with mayBeEmpty the result is empty and the caller decides (a K = 2 database whose results are not relinearised needs
+// no key: include/piehip.h "Result relinearisation"), otherwise std::invalid_argument.
+inline std::vector<uint64_t> readEvalMultKey(int fd, const ContextMessage &c, const uint64_t *moduli, bool mayBeEmpty = false)
 {
     std::vector<uint8_t> m;
     wire::readWithSizeIntoVector(fd, m);
+    if (m.empty()) {
+        if (!mayBeEmpty) throw std::invalid_argument("empty EvalMult key message: this server relinearises and needs every client's key");
+        return {};
+    }
     const size_t words = (size_t)c.L * 2 * c.L * c.N;
     if (m.size() != words * sizeof(uint64_t)) throw std::runtime_error("EvalMult key message size");
     std::vector<uint64_t> evk(words);
@@ -92,11 +98,12 @@ inline OnPiece stagePieces(piehip_handle h, uint32_t q)
     };
 }
 
-// sendResult, .cpp:143-152: b ciphertexts of `keep` limbs, one message each, rowStride words apart
-inline void sendResults(int fd, const uint64_t *results, uint32_t b, size_t rowStride, uint32_t keep, uint32_t N)
+// sendResult, .cpp:143-152: b ciphertexts of ncomp components on `keep` limbs, one message each, rowStride words apart (two
+// components: the message packCiphertexts makes, byte for byte)
+inline void sendResults(int fd, const uint64_t *results, uint32_t b, size_t rowStride, uint32_t keep, uint32_t N, uint32_t ncomp = 2)
 {
     for (uint32_t i = 0; i < b; i++) {
-        const auto out = wire::packCiphertexts(results + (size_t)i * rowStride, 1, keep, N);
+        const auto out = wire::packRows(results + (size_t)i * rowStride, 1, ncomp, keep, N);
         wire::writeWithSize(fd, out.data(), out.size());
     }
 }
@@ -163,6 +170,13 @@ public:
     // change: the clients make the same choice from the same numbers, repeat the slots of every query vector R times, and read block r of
     // result g as bin layer g R + r.  Call before run().
     void setLayerTiling(bool on) { layerTiling = on; }
+
+    // Result relinearisation (include/piehip.h "Result relinearisation"; on = the reference's behaviour): off, the last product of the
+    // chain is not relinearised and every result message carries THREE components (WireFraming.hpp, packRows), which the clients decrypt
+    // as d0 + d1 s + d2 s^2.  With two Cuckoo hash functions the chain then uses no EvalMult key at all: a client may send an EMPTY key
+    // message, recognised by its place in the set-up phase, and no key is loaded for it; a key that does arrive is loaded as ever.  In
+    // every other case an empty key message is std::invalid_argument.  Call before run().
+    void setResultRelin(bool on) { resultRelin = on; }
     uint32_t tiledLayers() const { return tiled ? tiled : ht.maxItemsPerPosition; }   // known once the set-up phase has the context
 
     long long offlineComputation = 0, onlineComputation = 0;  // microseconds, PSIServer.hpp:89-103
@@ -184,6 +198,7 @@ public:
                 PieContext::check(piehip_set_query_batch(cc->handle(), nq));
                 if (resultLimbs) PieContext::check(piehip_set_result_limbs(cc->handle(), resultLimbs));
                 if (chainLimbs) PieContext::check(piehip_set_chain_limbs(cc->handle(), chainLimbs));
+                if (!resultRelin) PieContext::check(piehip_set_result_relin(cc->handle(), 0));
                 if (layerTiling) {
                     uint32_t R = 1;
                     PieContext::check(piehip_layer_tiling(c.N, ht.numberOfSimpleHashFunctions, ht.eachSimpleTableSize, ht.maxItemsPerPosition,
@@ -197,7 +212,8 @@ public:
                 throw std::invalid_argument("the clients of one batch must use the same crypto context parameters");
             }
             wire::readWithSizeIntoVector(fd, m);  // public key: stored by the reference, never used by the operator
-            const std::vector<uint64_t> evk = readEvalMultKey(fd, c, qMod.data());
+            const std::vector<uint64_t> evk = readEvalMultKey(fd, c, qMod.data(), !resultRelin && ht.numberOfCuckooHashFunctions == 2);
+            if (evk.empty()) continue;   // (allowed above: the chain of this server uses no key)
             if (nq == 1) cc->setEvalMultKey(evk.data());
             else PieContext::check(piehip_load_relin_key_q(cc->handle(), q, evk.data()));  // every client's own key
         }
@@ -255,10 +271,14 @@ public:
         PieContext::check(piehip_run_staged(cc->handle(), pinRes));
         PieContext::check(piehip_run_host_wait(cc->handle()));
         onlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
-        uint32_t keep = resultLimbs ? resultLimbs : L;   // limbs per result ciphertext as it leaves the device and the server
-        if (chainLimbs && chainLimbs < keep) keep = chainLimbs;   // (K >= 2 here: a Cuckoo table has more than one hash function)
-        const size_t rct = 2 * (size_t)keep * N;
-        for (uint32_t q = 0; q < nq; q++) sendResults(fds[q], pinRes + q * rct, b, nq * rct, keep, N);   // rows are [bin layer][query]
+        // components and limbs of a result ciphertext as it leaves the device and the server: what the handle says they are
+        uint32_t ncomp = 0, keep = 0, lc = 0;
+        PieContext::check(piehip_get_result_components(cc->handle(), &ncomp));
+        PieContext::check(piehip_get_result_limbs(cc->handle(), &keep));
+        PieContext::check(piehip_get_chain_limbs(cc->handle(), &lc));
+        if (K >= 2 && lc < keep) keep = lc;
+        const size_t rct = (size_t)ncomp * keep * N;
+        for (uint32_t q = 0; q < nq; q++) sendResults(fds[q], pinRes + q * rct, b, nq * rct, keep, N, ncomp);   // rows are [bin layer][query]
     }
 
 private:
@@ -270,6 +290,7 @@ private:
     uint32_t resultLimbs = 0;   // setResultLimbs: 0 = every limb
     uint32_t chainLimbs = 0;    // the constructor's option: 0 = every limb
     bool layerTiling = false;   // setLayerTiling
+    bool resultRelin = true;    // setResultRelin
     uint32_t tiled = 0;         // result messages per client with a layer tiling (0: no tiling)
     std::vector<uint64_t> qMod;
     std::unique_ptr<PieContext> cc;

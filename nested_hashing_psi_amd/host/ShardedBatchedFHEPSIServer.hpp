@@ -62,6 +62,8 @@ public:
 
     void run()  // PSIServer.hpp:66-87
     {
+        if (querySlices && rowSettings())   // (a sliced handle refuses them one by one; here before the first message is read)
+            throw std::invalid_argument("resultLimbs, chainLimbs, chainSchedule and resultRelin = false apply in bin-layer mode only, not with querySlices");
         try {
             runSetUpPhase();
             if (rank == 0) wire::signalPhaseOver(fd);
@@ -75,6 +77,16 @@ public:
     }
 
     bool querySlices = false;               // stage A sharded by (inner hash function, limb) unit: see above
+    // The shape of a result row (include/piehip.h "Result limbs", "Chain limbs", "Result relinearisation"), bin-layer mode only, set
+    // before run() and THE SAME ON EVERY RANK: every rank applies them in the set-up phase and the ranks then compare their row shapes
+    // (piehip_rccl_agree_rows); ranks started with different values all end the session there with std::invalid_argument.  The result
+    // messages carry piehip_get_result_components components of min(resultLimbs, chain limbs) limbs.  With resultRelin = false and two
+    // Cuckoo hash functions the client may send an empty EvalMult key message (BatchedFHEPSIServer::setResultRelin); rank 0 forwards it
+    // like any other.  The noise budget of a setting is the operator's business.
+    uint32_t resultLimbs = 0;               // 0 = every limb
+    uint32_t chainLimbs = 0;                // 0 = every limb; ignored where chainSchedule is set
+    std::vector<uint32_t> chainSchedule;    // piehip_set_chain_schedule: a limb count per product
+    bool resultRelin = true;
     bool failOfflineForTesting = false;     // this rank's database build "fails": the group must end the session, not hang
     uint32_t collectiveTimeoutMs = 30000;   // bound on every wait for the other ranks (piehip_rccl_wait / piehip_rccl_agree)
 
@@ -95,7 +107,8 @@ public:
         const ContextMessage c = readContextMessage(from);
         if (rank > 0) readExactly(seeds, sizeof(seeds), "seed message size");
         else wire::readWithSizeIntoVector(from, m);  // public key: unused by the operator
-        const std::vector<uint64_t> evk = readEvalMultKey(from, c, rank == 0 ? c.moduli : nullptr);   // rank 0 has checked what it forwards
+        // (rank 0 has checked what it forwards; an empty key message is forwarded like any other and judged on every rank alike, below)
+        const std::vector<uint64_t> evk = readEvalMultKey(from, c, rank == 0 ? c.moduli : nullptr, true);
         if (rank == 0) {
             PieContext::check(piehip_rccl_unique_id(id));
             for (int s : side) {  // session set-up for the workers
@@ -107,8 +120,17 @@ public:
         }
         cc.reset(new PieContext(c.N, c.L, c.t, c.moduli, c.moduli + c.L, device));
         qMod.assign(c.moduli, c.moduli + c.L);
-        cc->setEvalMultKey(evk.data());
+        if (evk.empty() && !(ht.numberOfCuckooHashFunctions == 2 && !resultRelin))
+            throw std::invalid_argument("empty EvalMult key message: only a server with two Cuckoo hash functions and resultRelin = false runs without a key");
+        if (!evk.empty()) cc->setEvalMultKey(evk.data());
         PieContext::check(piehip_rccl_init(cc->handle(), id, G, rank));
+        if (rowSettings()) {
+            // a setter that refuses throws here and run() aborts this rank's side: the peers' agreement ends at once, not at its bound
+            if (resultLimbs) PieContext::check(piehip_set_result_limbs(cc->handle(), resultLimbs));
+            if (!chainSchedule.empty()) PieContext::check(piehip_set_chain_schedule(cc->handle(), chainSchedule.data(), (uint32_t)chainSchedule.size()));
+            else if (chainLimbs) PieContext::check(piehip_set_chain_limbs(cc->handle(), chainLimbs));
+            if (!resultRelin) PieContext::check(piehip_set_result_relin(cc->handle(), 0));
+        }
         PieContext::check(piehip_rccl_bin_slice(ht.maxItemsPerPosition, G, rank, &lo, &hi));
         if (hi > lo)
             PieContext::check(piehip_reserve(cc->handle(), serverSet.size(), ht.numberOfSimpleHashFunctions, ht.eachSimpleTableSize,
@@ -135,6 +157,15 @@ public:
             }
             PieContext::check(piehip_sync(cc->handle()));
         });
+        // The database is in place (its K decides the components and limbs of a row, and loading it forgets an agreement): the ranks
+        // compare what their settings made of a result row, once per session, before the first gather
+        if (rowSettings()) {
+            int same = 0;
+            PieContext::check(piehip_rccl_agree_rows(cc->handle(), collectiveTimeoutMs, &same));
+            if (!same)
+                throw std::invalid_argument("the ranks of the server group were started with different resultLimbs, chainLimbs, chainSchedule or "
+                                            "resultRelin: their result rows differ in shape");
+        }
         // one evaluation of an all-zero query through the whole online path (code objects, queues, the communicator's first
         // collective) while nobody waits for it.  Only rank 0 ever holds a whole query in host memory: the workers of the broadcast mode
         // get their device-side input buffers and run queues, no page-locked index matrix (29 MiB at C3 that nothing would ever write)
@@ -173,11 +204,25 @@ public:
         const auto begin = std::chrono::steady_clock::now();
         const uint64_t *results = evaluateQuery();  // .cpp:101-103 across the ranks
         onlineComputation = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
-        if (rank == 0) sendResults(fd, results, ht.maxItemsPerPosition, ctWords(), L, N);
+        if (rank == 0) {   // framed with the shape the ranks agreed on: this handle's
+            uint32_t ncomp = 0, rl = 0;
+            rowShape(&ncomp, &rl);
+            sendResults(fd, results, ht.maxItemsPerPosition, (size_t)ncomp * rl * N, rl, N, ncomp);
+        }
     }
 
 private:
-    size_t ctWords() const { return 2 * (size_t)cc->towers() * cc->ringDimension(); }
+    size_t ctWords() const { return 2 * (size_t)cc->towers() * cc->ringDimension(); }   // a query ciphertext
+    bool rowSettings() const { return resultLimbs || chainLimbs || !chainSchedule.empty() || !resultRelin; }
+    // components and limbs of a result ciphertext as the handle stands
+    void rowShape(uint32_t *ncomp, uint32_t *rl) const
+    {
+        uint32_t keep = 0, lc = 0;
+        PieContext::check(piehip_get_result_components(cc->handle(), ncomp));
+        PieContext::check(piehip_get_result_limbs(cc->handle(), &keep));
+        PieContext::check(piehip_get_chain_limbs(cc->handle(), &lc));
+        *rl = ht.numberOfCuckooHashFunctions >= 2 && lc < keep ? lc : keep;
+    }
 
     // rank 0's page-locked whole-query arrays
     void hostArrays(uint64_t **pinIdx, uint64_t **pinMinus)
@@ -222,7 +267,7 @@ private:
         PieContext::check(piehip_run(cc->handle()));
         return gatherToRoot();
     }
-    // results -> rank 0's host memory: page-locked, owned by the library, [b][2][L][N] in bin order
+    // results -> rank 0's host memory: page-locked, owned by the library, [b][ncomp][rl][N] in bin order (rowShape)
     const uint64_t *gatherToRoot()
     {
         uint64_t *gathered = nullptr;

@@ -137,5 +137,54 @@ inline uint32_t unpackCiphertexts(const std::vector<uint8_t> &msg, uint32_t L, u
     return h.count;
 }
 
+// ---- rows of two or three components ---------------------------------------------------------------------------------------------
+// A result ciphertext whose last product was not relinearised (include/piehip.h "Result relinearisation") has three components.  The
+// component count travels in the low 32 bits of LimbHeader::reserved, 0 meaning 2: a message of two-component rows is byte for byte
+// what packCiphertexts makes, and a receiver that knows only the functions above refuses a three-component message by its length.
+inline uint32_t rowComponents(const LimbHeader &h)
+{
+    const uint64_t c = h.reserved;
+    if (c != 0 && c != 2 && c != 3) throw std::invalid_argument("ciphertext message names a component count other than 2 or 3");
+    return c == 0 ? 2u : (uint32_t)c;
+}
+inline std::vector<uint8_t> packRows(const uint64_t *limbs, uint32_t count, uint32_t ncomp, uint32_t L, uint32_t N)
+{
+    if (ncomp != 2 && ncomp != 3) throw std::invalid_argument("a ciphertext row has two or three components");
+    const size_t words = (size_t)count * ncomp * L * N;
+    const LimbHeader h = {0x48454950u, count, L, N, ncomp == 2 ? 0u : (uint64_t)ncomp};
+    const uint8_t *hp = reinterpret_cast<const uint8_t *>(&h), *lp = reinterpret_cast<const uint8_t *>(limbs);
+    std::vector<uint8_t> msg;
+    msg.reserve(sizeof(h) + words * sizeof(uint64_t));
+    msg.insert(msg.end(), hp, hp + sizeof(h));
+    msg.insert(msg.end(), lp, lp + words * sizeof(uint64_t));
+    return msg;
+}
+// header of a message of rows, validated against the context and -- with the component count it names -- against the message length
+// BEFORE anything is sized by it; *ncomp: that count
+inline LimbHeader checkedRowsHeader(const std::vector<uint8_t> &msg, uint32_t L, uint32_t N, uint32_t *ncomp)
+{
+    if (msg.size() < sizeof(LimbHeader)) throw std::invalid_argument("short ciphertext message");
+    LimbHeader h;
+    std::memcpy(&h, msg.data(), sizeof(h));
+    if (h.magic != 0x48454950u || h.L != L || h.N != N) throw std::invalid_argument("ciphertext message does not match the context");
+    const uint32_t nc = rowComponents(h);
+    const size_t per_ct = (size_t)nc * L * N * sizeof(uint64_t), body = msg.size() - sizeof(LimbHeader);
+    if (per_ct == 0 || body % per_ct != 0 || body / per_ct != h.count) throw std::invalid_argument("ciphertext message length mismatch");
+    *ncomp = nc;
+    return h;
+}
+// returns the row count, *ncomp the components of each; throws if the message does not describe [count][ncomp][L][N] or (moduli !=
+// null: q_0..q_{L-1}) a residue is not canonical
+inline uint32_t unpackRows(const std::vector<uint8_t> &msg, uint32_t L, uint32_t N, std::vector<uint64_t> &limbs, uint32_t *ncomp,
+                           const uint64_t *moduli = nullptr)
+{
+    const LimbHeader h = checkedRowsHeader(msg, L, N, ncomp);   // the count is bounded by the message that actually arrived
+    const size_t words = (size_t)h.count * *ncomp * L * N;
+    limbs.resize(words);
+    std::memcpy(limbs.data(), msg.data() + sizeof(h), words * sizeof(uint64_t));
+    if (moduli) checkCanonical(limbs.data(), (size_t)h.count * *ncomp * L, L, N, moduli, "ciphertext");
+    return h.count;
+}
+
 }  // namespace wire
 }  // namespace piehip

@@ -737,9 +737,15 @@ class BatchedFHEHIPPIE:
         _check(lib().piehip_gather_results_host(self.cc._h, int(b_total), int(root), C.byref(p)))
         if not p:
             return None
-        nq = self.nq
-        shape = (b_total, 2, self.cc.L, self.cc.N) if nq == 1 else (b_total, nq, 2, self.cc.L, self.cc.N)
-        return np.ctypeslib.as_array(p, shape=shape)
+        return np.ctypeslib.as_array(p, shape=(b_total,) + self._res_shape()[1:])
+
+    def agreeRows(self, timeout_ms=30000):
+        """True when every rank's result rows have this rank's shape -- components, limbs, queries per run() (piehip_rccl_agree_rows).
+        Collective.  After setResultLimbs / setResultRelin(False) / setChainLimbs / setChainSchedule the gather moves rows only once
+        this has returned True, and every later change of a setting, the batch or the database asks for it again."""
+        out = C.c_int()
+        _check(lib().piehip_rccl_agree_rows(self.cc._h, int(timeout_ms), C.byref(out)))
+        return bool(out.value)
 
     def copyResultsToDevice(self, ptr):
         _check(lib().piehip_copy_results_device(self.cc._h, ptr))
