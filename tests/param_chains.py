@@ -83,7 +83,15 @@ def chain_by_name(N, L, name):
         return barrett_60(N, L)
     if name in ("last_q_over", "last_p_over", "q4_over"):
         return over_at(N, L, name)
+    if name == "barrett_one_p_61":
+        return barrett_one_p_61(N, L)
     return named_chain(N, L, name)
+
+
+def barrett_one_p_61(N, L):
+    """(q, p): barrett_60 with its last P modulus replaced by a 61-bit prime, as one_p_61 is to the default chain: the parent has no
+    lazy transforms and does not fold, every level below L drops that prime, folds (N = 16384, 32768) and is of the Barrett kind"""
+    return split(uniform(N, 2 * L, FOLD_BOUND) + uniform(N, 1, 1 << 61), L)
 
 
 def uniform(N, count, below=1 << 60):

@@ -92,80 +92,85 @@ def waves(v):
     return min(8, 512 // ((v + 7) // 8 * 8))
 
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--removed", default=None)
-ap.add_argument("--renamed", default=None)
-ap.add_argument("--neutral-ordinals", action="store_true")
-ap.add_argument("before")
-ap.add_argument("after")
-args = ap.parse_args()
-pa, pt = kernels(args.before, args.neutral_ordinals)
-he, ht = kernels(args.after, args.neutral_ordinals)
-renamed = []
-if args.renamed:
-    for ln in open(args.renamed):
-        if ln.strip():
-            old, new = ln.rstrip('\n').split('\t')
-            renamed.append((find(pa, old.strip(), "first"), find(he, new.strip(), "second")))
-    assert len(set(o for o, n in renamed)) == len(renamed) == len(set(n for o, n in renamed)), "--renamed: a name occurs twice"
-    # from here on a pair is one kernel under its old name
-    moved = {o: unnamed(he[n], n) for o, n in renamed}
-    for o, n in renamed:
-        del he[n]
-    clash = [short(o) for o in moved if o in he]
-    assert not clash, "--renamed: old names the second listing still has: %s" % clash
-    for o, n in renamed:
-        pa[o] = unnamed(pa[o], o)
-    he.update(moved)
-removed = set(ln.strip() for ln in open(args.removed) if ln.strip()) if args.removed else set()
-gone = [k for k in pa if k not in he]
-new = [k for k in he if k not in pa]
-named = [k for k in pa if k in removed or short(k) in removed]
-unexpected = [short(k) for k in gone if k not in named]
-assert not unexpected, "kernels of the first listing missing from the second: %s" % unexpected
-assert not [k for k in named if k in he], "kernels named as removed that the second listing still has: %s" % [short(k) for k in named if k in he]
-assert len(named) == len(removed), "names in --removed that the first listing does not have"
-if gone:
-    print("%d kernels removed on purpose (--removed), missing from the second listing:" % len(gone))
-    for k in gone:
-        print("  " + short(k))
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--removed", default=None)
+    ap.add_argument("--renamed", default=None)
+    ap.add_argument("--neutral-ordinals", action="store_true")
+    ap.add_argument("before")
+    ap.add_argument("after")
+    args = ap.parse_args()
+    pa, pt = kernels(args.before, args.neutral_ordinals)
+    he, ht = kernels(args.after, args.neutral_ordinals)
+    renamed = []
+    if args.renamed:
+        for ln in open(args.renamed):
+            if ln.strip():
+                old, new = ln.rstrip('\n').split('\t')
+                renamed.append((find(pa, old.strip(), "first"), find(he, new.strip(), "second")))
+        assert len(set(o for o, n in renamed)) == len(renamed) == len(set(n for o, n in renamed)), "--renamed: a name occurs twice"
+        # from here on a pair is one kernel under its old name
+        moved = {o: unnamed(he[n], n) for o, n in renamed}
+        for o, n in renamed:
+            del he[n]
+        clash = [short(o) for o in moved if o in he]
+        assert not clash, "--renamed: old names the second listing still has: %s" % clash
+        for o, n in renamed:
+            pa[o] = unnamed(pa[o], o)
+        he.update(moved)
+    removed = set(ln.strip() for ln in open(args.removed) if ln.strip()) if args.removed else set()
+    gone = [k for k in pa if k not in he]
+    new = [k for k in he if k not in pa]
+    named = [k for k in pa if k in removed or short(k) in removed]
+    unexpected = [short(k) for k in gone if k not in named]
+    assert not unexpected, "kernels of the first listing missing from the second: %s" % unexpected
+    assert not [k for k in named if k in he], "kernels named as removed that the second listing still has: %s" % [short(k) for k in named if k in he]
+    assert len(named) == len(removed), "names in --removed that the first listing does not have"
+    if gone:
+        print("%d kernels removed on purpose (--removed), missing from the second listing:" % len(gone))
+        for k in gone:
+            print("  " + short(k))
+        print()
+        for k in gone:
+            del pa[k]
+    if renamed:
+        print("%d kernels renamed (--renamed), each pair compared as one kernel, its own name neutralised:" % len(renamed))
+        for o, n in renamed:
+            print("  %s -> %s%s" % (short(o), short(n), "" if pa[o] == he[o] else "   DIFFERS"))
+        print()
+    if args.neutral_ordinals:
+        print("(function ordinals in local labels neutralised)")
+    same = [k for k in pa if pa[k] == he[k]]
+    diff = [k for k in pa if pa[k] != he[k]]
+    print("%d kernels, %d with identical listing (instructions, kernel descriptor, metadata), %d differ" % (len(pa), len(same), len(diff)))
+    print("whole listing identical" if pt == ht else "whole listing differs")
+    if new:   # kernels only the second listing has: their register figures and instruction totals
+        print()
+        print("%d kernels only in the second listing:" % len(new))
+        for k in new:
+            r, c = he[k]['regs'], mix(he[k]['body'])
+            print("  %-52s vgpr %3d spill %d sgpr %3d scratch %3d waves %d instructions %5d  v_cndmask_b32 %d" % (
+                short(k), r[0], r[1], r[2], r[3], waves(r[0]), sum(c.values()), c['v_cndmask_b32']))
     print()
-    for k in gone:
-        del pa[k]
-if renamed:
-    print("%d kernels renamed (--renamed), each pair compared as one kernel, its own name neutralised:" % len(renamed))
-    for o, n in renamed:
-        print("  %s -> %s%s" % (short(o), short(n), "" if pa[o] == he[o] else "   DIFFERS"))
+    print("identical, by kernel template: " + ", ".join("%s x %d" % kv for kv in collections.Counter(re.sub(r'<.*', '', short(k)) for k in same).items()))
     print()
-if args.neutral_ordinals:
-    print("(function ordinals in local labels neutralised)")
-same = [k for k in pa if pa[k] == he[k]]
-diff = [k for k in pa if pa[k] != he[k]]
-print("%d kernels, %d with identical listing (instructions, kernel descriptor, metadata), %d differ" % (len(pa), len(same), len(diff)))
-print("whole listing identical" if pt == ht else "whole listing differs")
-if new:   # kernels only the second listing has: their register figures and instruction totals
-    print()
-    print("%d kernels only in the second listing:" % len(new))
-    for k in new:
-        r, c = he[k]['regs'], mix(he[k]['body'])
-        print("  %-52s vgpr %3d spill %d sgpr %3d scratch %3d waves %d instructions %5d  v_cndmask_b32 %d" % (
-            short(k), r[0], r[1], r[2], r[3], waves(r[0]), sum(c.values()), c['v_cndmask_b32']))
-print()
-print("identical, by kernel template: " + ", ".join("%s x %d" % kv for kv in collections.Counter(re.sub(r'<.*', '', short(k)) for k in same).items()))
-print()
-print("kernels whose listing differs (parent -> this tree):")
-print("%-46s %-11s %-5s %-9s %-7s %-5s %-15s %-9s %-9s %-11s %-9s %-9s %-9s %s" % (
-    "kernel", "vgpr", "spill", "sgpr", "scratch", "waves", "instructions", "g_load", "g_store", "mad_u64_u32", "mul_hi", "mul_lo", "lshl_add", "other mnemonics that differ"))
-ok = True
-for k in diff:
-    a, b = pa[k], he[k]
-    ca, cb = mix(a['body']), mix(b['body'])
-    ta, tb = sum(ca.values()), sum(cb.values())
-    cols = ["%d->%d" % (fam(ca, f), fam(cb, f)) if fam(ca, f) != fam(cb, f) else "%d" % fam(ca, f) for f in FAMS]
-    others = sorted(m for m in set(ca) | set(cb) if ca[m] != cb[m] and not m.startswith(FAMS))
-    ra, rb = a['regs'], b['regs']
-    pr = lambda i: ("%d->%d" % (ra[i], rb[i])) if ra[i] != rb[i] else "%d" % ra[i]
-    wa, wb = waves(ra[0]), waves(rb[0])
+    print("kernels whose listing differs (parent -> this tree):")
     print("%-46s %-11s %-5s %-9s %-7s %-5s %-15s %-9s %-9s %-11s %-9s %-9s %-9s %s" % (
-        short(k), pr(0), pr(1), pr(2), pr(3), ("%d->%d" % (wa, wb)) if wa != wb else "%d" % wa,
-        "%d->%d (%+.2f%%)" % (ta, tb, 100.0 * (tb - ta) / ta), *cols, " ".join("%s %+d" % (m, cb[m] - ca[m]) for m in others)))
+        "kernel", "vgpr", "spill", "sgpr", "scratch", "waves", "instructions", "g_load", "g_store", "mad_u64_u32", "mul_hi", "mul_lo", "lshl_add", "other mnemonics that differ"))
+    ok = True
+    for k in diff:
+        a, b = pa[k], he[k]
+        ca, cb = mix(a['body']), mix(b['body'])
+        ta, tb = sum(ca.values()), sum(cb.values())
+        cols = ["%d->%d" % (fam(ca, f), fam(cb, f)) if fam(ca, f) != fam(cb, f) else "%d" % fam(ca, f) for f in FAMS]
+        others = sorted(m for m in set(ca) | set(cb) if ca[m] != cb[m] and not m.startswith(FAMS))
+        ra, rb = a['regs'], b['regs']
+        pr = lambda i: ("%d->%d" % (ra[i], rb[i])) if ra[i] != rb[i] else "%d" % ra[i]
+        wa, wb = waves(ra[0]), waves(rb[0])
+        print("%-46s %-11s %-5s %-9s %-7s %-5s %-15s %-9s %-9s %-11s %-9s %-9s %-9s %s" % (
+            short(k), pr(0), pr(1), pr(2), pr(3), ("%d->%d" % (wa, wb)) if wa != wb else "%d" % wa,
+            "%d->%d (%+.2f%%)" % (ta, tb, 100.0 * (tb - ta) / ta), *cols, " ".join("%s %+d" % (m, cb[m] - ca[m]) for m in others)))
+
+
+if __name__ == "__main__":
+    main()
