@@ -219,7 +219,8 @@ int piehip_get_transform_slots(piehip_handle h, uint32_t *n /* the cap, 0 = none
  *   0  128-bit accumulators, two-word Barrett (some modulus outside (2^59, 2^60))
  *   1  30-bit column accumulators, one-word Barrett (every Q and P modulus in (2^59, 2^60))
  *   2  column accumulators folded with d (every Q and P modulus is 2^60 - d with d < 2^27: the default chains) in the base
- *      conversions, scale-and-round and the fused tensor product; results are the same residues either way */
+ *      conversions, scale-and-round and the fused tensor product, and butterflies that reduce by the same fold in the
+ *      16-coefficient transforms of Q and P limbs; results are the same residues either way */
 int piehip_get_reduction(piehip_handle h, uint32_t *kind);
 /* The same for the level context of Lc limbs (Chain limbs: a level has a plan of its own, decided from the moduli it keeps, so a
  * level of a Barrett parent folds where the parent's only wide-d moduli are among those it drops).  Lc = L is the handle's own

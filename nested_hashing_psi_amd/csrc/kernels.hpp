@@ -56,6 +56,8 @@ struct NttPlan {
     bool small_moduli = false;   // every Q and P modulus lies in (2^59, 2^60): v_mad_u64_u32 column accumulators, one-word Barrett
     bool fold_moduli = false;    // ... and is 2^60 - d with d < COLACC_FOLD_MAX_D (the default chains): the base conversions, scale-and-
                                  // round and the tensor load phase reduce their column sums by folding with d (stage_a_common.h)
+    u32 fold_mod_count = 0;      // ... the moduli [0, fold_mod_count) that says it of (Q and P, not the plaintext modulus behind them): a
+                                 // launch of the 16-coefficient transform on moduli inside takes the folding butterflies (ntt16_kernel.h)
     // schedule switches derived from the above (piehip_run.cpp)
     bool xq_reuse = false;         // the inverse transform of operand X drops a lane-ordered copy into the QP array, the forward skips it
     bool x_direct = false;         // stage A of a query batch may write X there in the first place (StageAXOut)

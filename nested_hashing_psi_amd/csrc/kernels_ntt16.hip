@@ -36,18 +36,32 @@ static void launch_ntt16_k(const ntt16::Args &a, u32 num_cus, hipStream_t st)
     const u32 grid = a.nitems < slots ? a.nitems : slots;
     hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(G::T), lds, st, a);
 }
-// the five instantiations of a slice length: forward, forward with the digit lift, inverse, and the inverse with the tensor load phase at
-// the two column-accumulator kinds (fd: ArithKind::fold, NttPlan::fold_moduli)
+// the four launch kinds of a slice length at one arithmetic kind: forward, forward with the digit lift, inverse, and the inverse with the
+// tensor load phase
+template <u32 LOGNS, ArithKind KIND>
+static void launch_ntt16_kind(const ntt16::Args &a, bool inverse, bool lift, u32 num_cus, hipStream_t st, bool tensor)
+{
+    using ntt16::ntt16_kernel_t;
+    if (tensor) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, true, false, true, KIND>>(a, num_cus, st);
+    else if (inverse) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, true, false, false, KIND>>(a, num_cus, st);
+    else if (lift) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, false, true, false, KIND>>(a, num_cus, st);
+    else launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, false, false, false, KIND>>(a, num_cus, st);
+}
+// fd: every modulus of the launch is 2^60 - d with d < COLACC_FOLD_MAX_D -- ArithKind::fold (the butterflies, the canonical forward store, the
+// column sums of the tensor load phase)
 template <u32 LOGNS>
 static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 num_cus, hipStream_t st, bool tensor = false, bool fd = false)
 {
-    using ntt16::ntt16_kernel_t;
-    if (tensor && fd) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, true, false, true, ArithKind::fold>>(a, num_cus, st);
-    else if (tensor) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, true, false, true>>(a, num_cus, st);
-    else if (inverse) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, true>>(a, num_cus, st);
-    else if (lift) launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, false, true>>(a, num_cus, st);
-    else launch_ntt16_k<LOGNS, ntt16_kernel_t<LOGNS, false>>(a, num_cus, st);
+#if NTT16_FOLD_BFLY
+    if (fd) return launch_ntt16_kind<LOGNS, ArithKind::fold>(a, inverse, lift, num_cus, st, tensor);
+#else  // (the butterflies are Barrett-kind blocks everywhere: only the tensor load phase has a folded form)
+    if (fd && tensor) return launch_ntt16_k<LOGNS, ntt16::ntt16_kernel_t<LOGNS, true, false, true, ArithKind::fold>>(a, num_cus, st);
+#endif
+    launch_ntt16_kind<LOGNS, ArithKind::barrett>(a, inverse, lift, num_cus, st, tensor);
 }
+// A plan with fold_moduli speaks of its Q and P moduli [0, fold_mod_count); the plaintext modulus behind them (the client's transforms
+// mod t) is of another shape and keeps the Barrett kind.
+static bool launch_folds(const NttPlan &pl, u32 mod_base, u32 mod_count) { return pl.fold_moduli && mod_base + mod_count <= pl.fold_mod_count; }
 
 void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_count, bool inverse, bool sigma, hipStream_t st,
                   const NttExtra *ex, const Ntt16Digits *dg)
@@ -93,10 +107,11 @@ void launch_ntt16(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mo
         a.lift_L = dg->L;
     }
     const bool lift = a.lift_first != ~0u;
+    const bool fd = launch_folds(pl, mod_base, mod_count) && (!dg || dg->L <= pl.fold_mod_count);
     if (pl.lane_logn == 14)
-        launch_ntt16_t<14>(a, inverse, lift, pl.transform_cus(), st);
+        launch_ntt16_t<14>(a, inverse, lift, pl.transform_cus(), st, false, fd);
     else
-        launch_ntt16_t<13>(a, inverse, lift, pl.transform_cus(), st);
+        launch_ntt16_t<13>(a, inverse, lift, pl.transform_cus(), st, false, fd);
 }
 
 void launch_ntt16_tensor(const NttPlan &pl, const u64 *e, u64 *d, u32 nb, u32 M, hipStream_t st, u32 eval_q_L, bool eval_q_d2)

@@ -111,15 +111,67 @@ struct ModC {
 // SC: the twiddles are wave-uniform (SGPR operands).  H2: the block takes 2 sh as an operand (t.sh2) instead of doubling the
 // high word of the multiplicand itself -- one instruction fewer; worth it where a twiddle serves several butterflies (every
 // wave-uniform one: the doubling is a scalar instruction; per-lane ones of the stages with fewer twiddles than butterflies).
+//
+// KIND = ArithKind::fold: every modulus is q = 2^60 - d with d < 2^27 (NttPlan::fold_moduli; d = m.nql, m.nq4 is not read).  For any 64-bit x
+//   fold(x) = (x mod 2^60) + (x >> 60) d  is congruent to x and below T = 2^60 + 2^31 < 2q
+// in three instructions (v_lshrrev_b32, v_and_b32, one v_mad_u64_u32 onto the masked pair) where the select takes four:
+//   forward   u = fold(a) < T:  a' = u + v < 6q, b' = u + 4q - v in (0, 6q)  -- NTT16_CTF1 / NTT16_CTF1H, 18 / 17 instructions, the seeded
+//             block with the fold in a's own registers (the mask is written through ah: the same contract, the same listing check)
+//   inverse   a' = fold(a + b) < T                                           -- NTT16_GSF1 / NTT16_GSF1H, 19 / 18
+//             below_T (a and b are both known to be below T): a' = a + b < 2T = 2^61 + 2^32 < 4q, no reduction at all
+//                                                                            -- NTT16_GSN1 / NTT16_GSN1H, 16 / 15
+// Which inverse butterflies may pass below_T is static (GsRanges below).  The forward transform has no such case: its outputs
+// u + v and u + 4q - v are never below 4q, let alone T.
 #ifndef NTT16_INV_H2
 #define NTT16_INV_H2 1
 #endif
-template <bool INV, bool SC, bool H2 = SC && (!INV || NTT16_INV_H2)>
-__device__ __forceinline__ void bfly(u64 &x0, u64 &y0, const Tw &t0, const ModC &m)
+// -DNTT16_FOLD_BFLY=0: the Barrett-kind blocks everywhere, and no fold-kind instantiation beside the tensor launch's
+#ifndef NTT16_FOLD_BFLY
+#define NTT16_FOLD_BFLY 1
+#endif
+template <bool INV, bool SC, bool H2 = SC && (!INV || NTT16_INV_H2), ArithKind KIND = ArithKind::barrett>
+__device__ __forceinline__ void bfly(u64 &x0, u64 &y0, const Tw &t0, const ModC &m, bool below_T = false)
 {
     u64 a0 = x0;  // forward, seeded: the tied operand -- a on entry, a' on exit
     const u64 b0 = y0;
-    if (INV) {
+    if (INV && KIND == ArithKind::fold && NTT16_FOLD_BFLY) {
+        u64 ao0, bo0;
+        if (below_T) {  // (a compile-time constant at every call site once the stage loops are unrolled)
+            u64 cs;
+            if (SC && H2)
+                NTT16_GSN1H(NTT16_S);
+            else if (SC)
+                NTT16_GSN1(NTT16_S);
+            else if (H2)
+                NTT16_GSN1H(NTT16_V);
+            else
+                NTT16_GSN1(NTT16_V);
+            (void)cs;
+        } else {
+            if (SC && H2)
+                NTT16_GSF1H(NTT16_S);
+            else if (SC)
+                NTT16_GSF1(NTT16_S);
+            else if (H2)
+                NTT16_GSF1H(NTT16_V);
+            else
+                NTT16_GSF1(NTT16_V);
+        }
+        x0 = ao0, y0 = bo0;
+    } else if (!INV && KIND == ArithKind::fold && NTT16_FOLD_BFLY) {
+        u32 bol0, boh0;
+        u64 cs;
+        if (SC && H2)
+            NTT16_CTF1H(NTT16_S);
+        else if (SC)
+            NTT16_CTF1(NTT16_S);
+        else if (H2)
+            NTT16_CTF1H(NTT16_V);
+        else
+            NTT16_CTF1(NTT16_V);
+        (void)cs;
+        x0 = a0, y0 = ((u64)boh0 << 32) | bol0;
+    } else if (INV) {
         u32 aol0, aoh0;
         u64 bo0;
         if (SC && H2)
@@ -160,12 +212,32 @@ __device__ __forceinline__ void bfly(u64 &x0, u64 &y0, const Tw &t0, const ModC 
     }
 }
 // two butterflies (call sites pair them; one block each: see tools/gen_ntt16_bfly.py on why they are not interleaved)
-template <bool INV, bool SC, bool H2 = SC && !INV>
-__device__ __forceinline__ void bfly2(u64 &x0, u64 &y0, const Tw &t0, u64 &x1, u64 &y1, const Tw &t1, const ModC &m)
+template <bool INV, bool SC, bool H2 = SC && !INV, ArithKind KIND = ArithKind::barrett>
+__device__ __forceinline__ void bfly2(u64 &x0, u64 &y0, const Tw &t0, u64 &x1, u64 &y1, const Tw &t1, const ModC &m, bool below_T0 = false,
+                                      bool below_T1 = false)
 {
-    bfly<INV, SC, H2>(x0, y0, t0, m);
-    bfly<INV, SC, H2>(x1, y1, t1, m);
+    bfly<INV, SC, H2, KIND>(x0, y0, t0, m, below_T0);
+    bfly<INV, SC, H2, KIND>(x1, y1, t1, m, below_T1);
 }
+// The range state of the sixteen registers of an inverse pass at ArithKind::fold: bit k set = x[k] is known to be below T.  In the
+// Gentleman-Sande network a butterfly of one stage pairs two sum legs or two product legs of the stage before.  A sum leg is below T
+// after a fold and only below 2T < 4q without one; a product leg is below 4q (the 63-bit Shoup estimate is up to 3 short).  Every
+// pass starts from "below 4q" on all registers -- the contract of the loads and of the LDS hand-offs, which carry no state --, so a
+// pass of 2, 3, 4 stages has 4, 6, 9 non-folding butterflies of 16, 24, 32 (tools/gen_ntt16_bfly.py prints the table, tests/test_fold_bfly.py
+// restates it).  The stage loops are fully unrolled, so the state is a constant wherever it is read.
+struct GsRanges {
+    u32 below_T = 0;
+    // may the butterfly on (x[k], x[k + d]) skip the fold?
+    __device__ __forceinline__ constexpr bool nofold(int k, int d) const { return ((below_T >> k) & (below_T >> (k + d)) & 1u) != 0; }
+    // the stage that pairs registers d apart is done
+    __device__ __forceinline__ constexpr void stage(int d)
+    {
+        u32 n = 0;
+        for (int k = 0; k < 16; k++)
+            if (!(k & d) && !nofold(k, d)) n |= 1u << k;
+        below_T = n;
+    }
+};
 // m-th index in [0, 16) whose bit `d` (a power of two) is clear
 __device__ __forceinline__ constexpr int bfly_lo(int m, int d) { return ((m & ~(d - 1)) << 1) | (m & (d - 1)); }
 
@@ -197,6 +269,29 @@ __device__ __forceinline__ u64 csub_neg(u64 x, u64 negm)
         : [lo] "=&v"(lo), [hi] "=&v"(hi)
         : [x] "v"(x), [xl] "v"((u32)x), [xh] "v"((u32)(x >> 32)), [nm] "s"(negm)
         : "v125", "v126", "v127");
+    return ((u64)hi << 32) | lo;
+}
+
+// x < 2^64 -> [0, q) for q = 2^60 - d, d < 2^27 (d is the low word of negq = 2^64 - q): fold(x) = x + (x >> 60) d - ((x >> 60) << 60) < 2q
+// (bfly above), then one conditional subtraction of q: 8 instructions where three conditional subtractions (x in [0, 8q)) take 12.
+// The fold subtracts the top four bits from the high word after the multiply-add instead of masking them before it: the addend
+// would have to be the pair {low word of x, masked high word}, and an asm operand cannot name the halves of x.  (Masking in place
+// through a tied operand, as the forward block does with a, is one instruction fewer and one more register contract to check in
+// every listing; not taken for a store phase of sixteen coefficients per slice.)
+__device__ __forceinline__ u64 fold_csub_neg(u64 x, u64 negq)
+{
+    u32 lo, hi;
+    asm("v_lshrrev_b32 v125, 28, %[xh]\n\t"
+        "v_and_b32 v124, 0xf0000000, %[xh]\n\t"
+        "v_mad_u64_u32 v[126:127], vcc, v125, %[d], %[x]\n\t"
+        "v_sub_u32 v127, v127, v124\n\t"
+        "v_lshl_add_u64 v[124:125], v[126:127], 0, %[nq]\n\t"
+        "v_ashrrev_i32 v123, 31, v125\n\t"
+        "v_bfi_b32 %[lo], v123, v126, v124\n\t"
+        "v_bfi_b32 %[hi], v123, v127, v125"
+        : [lo] "=&v"(lo), [hi] "=&v"(hi)
+        : [x] "v"(x), [xh] "v"((u32)(x >> 32)), [nq] "s"(negq), [d] "s"((u32)negq)
+        : "vcc", "v123", "v124", "v125", "v126", "v127");
     return ((u64)hi << 32) | lo;
 }
 
@@ -524,13 +619,15 @@ __device__ __forceinline__ void tensor_load(u64 (&x)[16], const u64 *pa, const u
 // LIFT (forward only): the launch may carry key-switch digit items (Args::lift_first); a separate instantiation, so that the
 // plain forward transform does not pay for the lift's registers
 // TENSOR (inverse only, lane order in): every item forms its input from the QP operands (Args::tsrc); likewise its own instantiation
-// KIND (TENSOR only; the transforms run on column-accumulator contexts): how the tensor load phase reduces its column sums -- the one-word
-// Barrett block, or at ArithKind::fold the folded block (NttPlan::fold_moduli).  Every other instantiation is built at the default.
+// KIND: ArithKind::fold where every modulus of the launch is 2^60 - d, d < 2^27 (NttPlan::fold_moduli) -- the butterflies and the canonical
+// forward store reduce by folding with d (bfly above), and so does the tensor load phase its column sums; ArithKind::barrett: the select
+// blocks and the one-word Barrett block.  (The transforms run on 60-bit moduli only: there is no ArithKind::wide instantiation.)
 template <u32 LOGNS, bool INV, bool LIFT = false, bool TENSOR = false, ArithKind KIND = ArithKind::barrett>
 __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 {
-    static_assert(KIND == ArithKind::barrett || (TENSOR && KIND == ArithKind::fold), "the kind: of the tensor load phase, column accumulators");
+    static_assert(KIND == ArithKind::barrett || (KIND == ArithKind::fold && (TENSOR || NTT16_FOLD_BFLY)), "the kinds of 60-bit moduli");
     constexpr bool FD = KIND == ArithKind::fold;
+    constexpr ArithKind BK = NTT16_FOLD_BFLY ? KIND : ArithKind::barrett;  // the butterflies' kind
     typedef Geo<LOGNS> G;
     constexpr u32 NS = G::NS, T = G::T, R = G::R, LOGR = G::LOGR, CPT = G::CPT, TWK_PER_SLICE = G::TWK_PER_SLICE;
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
@@ -679,7 +776,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 #pragma unroll
                     for (int k = 0; k < 16; k++) {
                         u64 u0 = lift1(x[k]), v0 = lift1(y[k]);
-                        bfly<false, true>(u0, v0, t, mc);
+                        bfly<false, true, true, BK>(u0, v0, t, mc);
                         x[k] = blk ? v0 : u0;
                     }
                 } else {
@@ -701,7 +798,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                     if (r & d) continue;
                     const Tw t = make_tw(NTT16_TWL(1u << s, (u32)r >> (LOGR - s)));
 #pragma unroll
-                    for (int c = 0; c < (int)CPT; c++) bfly<false, true>(x[CPT * r + c], x[CPT * (r + d) + c], t, mc);
+                    for (int c = 0; c < (int)CPT; c++) bfly<false, true, true, BK>(x[CPT * r + c], x[CPT * (r + d) + c], t, mc);
                 }
             }
             NTT16_STAMP(1);
@@ -724,7 +821,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                     const int k0 = bfly_lo(mm, d), k1 = bfly_lo(mm + 1, d);
                     const Tw t0 = make_tw(NTT16_TWL(G::W << sb, (w << sb) + ((u32)k0 >> (4 - sb))));
                     const Tw t1 = make_tw(NTT16_TWL(G::W << sb, (w << sb) + ((u32)k1 >> (4 - sb))));
-                    bfly2<false, true>(x[k0], x[k0 + d], t0, x[k1], x[k1 + d], t1, mc);
+                    bfly2<false, true, true, BK>(x[k0], x[k0 + d], t0, x[k1], x[k1 + d], t1, mc);
                 }
             }
             // per-lane twiddles from here on, each stage's loaded one stage ahead (the last stages' eight in two halves: with the
@@ -744,27 +841,27 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             {
                 const Tw t = make_tw(t7[0]);
 #pragma unroll
-                for (int k = 0; k < 8; k += 2) bfly2<false, false, true>(x[k], x[k + 8], t, x[k + 1], x[k + 9], t, mc);
+                for (int k = 0; k < 8; k += 2) bfly2<false, false, true, BK>(x[k], x[k + 8], t, x[k + 1], x[k + 9], t, mc);
             }
             NTT16_LOAD3H(t10, 3, 0);
             NTT16_FENCE();
 #pragma unroll
             for (int mm = 0; mm < 8; mm += 2) {
                 const int k0 = bfly_lo(mm, 4), k1 = bfly_lo(mm + 1, 4);
-                bfly2<false, false, true>(x[k0], x[k0 + 4], make_tw(t8[k0 >> 3]), x[k1], x[k1 + 4], make_tw(t8[k1 >> 3]), mc);
+                bfly2<false, false, true, BK>(x[k0], x[k0 + 4], make_tw(t8[k0 >> 3]), x[k1], x[k1 + 4], make_tw(t8[k1 >> 3]), mc);
             }
             NTT16_LOAD3H(t10, 3, 4);
             NTT16_FENCE();
 #pragma unroll
             for (int mm = 0; mm < 8; mm += 2) {
                 const int k0 = bfly_lo(mm, 2), k1 = bfly_lo(mm + 1, 2);
-                bfly2<false, false>(x[k0], x[k0 + 2], make_tw(t9[k0 >> 2]), x[k1], x[k1 + 2], make_tw(t9[k1 >> 2]), mc);
+                bfly2<false, false, false, BK>(x[k0], x[k0 + 2], make_tw(t9[k0 >> 2]), x[k1], x[k1 + 2], make_tw(t9[k1 >> 2]), mc);
             }
             NTT16_LOAD4(t11, 0, 4);
             NTT16_FENCE();
 #pragma unroll
             for (int k = 0; k < 16; k += 4)
-                bfly2<false, false>(x[k], x[k + 1], make_tw(t10[k >> 1]), x[k + 2], x[k + 3], make_tw(t10[(k >> 1) + 1]), mc);
+                bfly2<false, false, false, BK>(x[k], x[k + 1], make_tw(t10[k >> 1]), x[k + 2], x[k + 3], make_tw(t10[(k >> 1) + 1]), mc);
 #pragma unroll
             for (int k = 0; k < 16; k++) p3[4 * k + 2 * (k >> 3)] = x[k];
             NTT16_STAMP(6);
@@ -782,7 +879,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 #pragma unroll
             for (int g4 = 0; g4 < 4; g4++) {  // stage 11: both butterflies of a group of four share its twiddle
                 const Tw t = make_tw(t11[g4]);
-                bfly2<false, false>(x[4 * g4], x[4 * g4 + 2], t, x[4 * g4 + 1], x[4 * g4 + 3], t, mc);
+                bfly2<false, false, false, BK>(x[4 * g4], x[4 * g4 + 2], t, x[4 * g4 + 1], x[4 * g4 + 3], t, mc);
                 if (g4 == 1) {
                     NTT16_FENCE();
                     _Pragma("unroll") for (int j_ = 4; j_ < 8; j_++) t12[j_] = *at_bytes(tw4 + 64 * (4 + j_), lb);
@@ -792,13 +889,14 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             NTT16_FENCE();
 #pragma unroll
             for (int k = 0; k < 16; k += 4)  // stage 12
-                bfly2<false, false>(x[k], x[k + 1], make_tw(t12[k >> 1]), x[k + 2], x[k + 3], make_tw(t12[(k >> 1) + 1]), mc);
+                bfly2<false, false, false, BK>(x[k], x[k + 1], make_tw(t12[k >> 1]), x[k + 2], x[k + 3], make_tw(t12[(k >> 1) + 1]), mc);
             NTT16_STAMP(7);
             // ---- lane-ordered store -------------------------------------------------------------------------------------------
             const bool lazy = (a.flags & F_LAZY_OUT) != 0 && !lift;  // the key-switch MAC splits canonical digits into 30-bit halves
             if (!lazy) {
 #pragma unroll
-                for (int k = 0; k < 16; k++) x[k] = csub_neg(csub_neg(csub_neg(x[k], 0 - q4), 0 - q2), 0 - q);
+                for (int k = 0; k < 16; k++)
+                    x[k] = BK == ArithKind::fold ? fold_csub_neg(x[k], 0 - q) : csub_neg(csub_neg(csub_neg(x[k], 0 - q4), 0 - q2), 0 - q);
             }
 #pragma unroll
             for (int j = 0; j < 8; j++) {
@@ -885,9 +983,11 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             NTT16_FENCE();
             NTT16_PRIO_I(1);
             // ---- pass 4': stages 12, 11 ----------------------------------------------------------------------------------------
+            GsRanges rs;  // (read at ArithKind::fold only; reset at every pass entry)
 #pragma unroll
             for (int k = 0; k < 16; k += 4) {  // stage 12
-                bfly2<true, false>(x[k], x[k + 1], make_tw(t12[k >> 1]), x[k + 2], x[k + 3], make_tw(t12[(k >> 1) + 1]), mc);
+                bfly2<true, false, false, BK>(x[k], x[k + 1], make_tw(t12[k >> 1]), x[k + 2], x[k + 3], make_tw(t12[(k >> 1) + 1]), mc,
+                                              rs.nofold(k, 1), rs.nofold(k + 2, 1));
                 if (k == 4) {   // the first half of this stage's twiddles is dead: the next stage's take their registers
                     NTT16_FENCE();
                     NTT16_LOAD4(t11, 0, 4);
@@ -896,10 +996,12 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             }
             NTT16_LOAD3(t10, 3);
             NTT16_FENCE();
+            rs.stage(1);
 #pragma unroll
             for (int g4 = 0; g4 < 4; g4++) {  // stage 11
                 const Tw t = make_tw(t11[g4]);
-                bfly2<true, false>(x[4 * g4], x[4 * g4 + 2], t, x[4 * g4 + 1], x[4 * g4 + 3], t, mc);
+                bfly2<true, false, false, BK>(x[4 * g4], x[4 * g4 + 2], t, x[4 * g4 + 1], x[4 * g4 + 3], t, mc, rs.nofold(4 * g4, 2),
+                                              rs.nofold(4 * g4 + 1, 2));
             }
             NTT16_STAMP(1);
             // (the stores below overwrite the image the other waves read in pass 1' of the previous slice: they are behind the
@@ -920,27 +1022,35 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             for (int k = 0; k < 16; k++) x[k] = p3[4 * k + 2 * (k >> 3)];
             NTT16_LOAD3(t9, 2);
             NTT16_FENCE();
+            rs = GsRanges();
 #pragma unroll
             for (int k = 0; k < 16; k += 4)
-                bfly2<true, false>(x[k], x[k + 1], make_tw(t10[k >> 1]), x[k + 2], x[k + 3], make_tw(t10[(k >> 1) + 1]), mc);
+                bfly2<true, false, false, BK>(x[k], x[k + 1], make_tw(t10[k >> 1]), x[k + 2], x[k + 3], make_tw(t10[(k >> 1) + 1]), mc,
+                                              rs.nofold(k, 1), rs.nofold(k + 2, 1));
             NTT16_LOAD3(t8, 1);
             NTT16_LOAD3(t7, 0);
             NTT16_FENCE();
+            rs.stage(1);
 #pragma unroll
             for (int mm = 0; mm < 8; mm += 2) {
                 const int k0 = bfly_lo(mm, 2), k1 = bfly_lo(mm + 1, 2);
-                bfly2<true, false>(x[k0], x[k0 + 2], make_tw(t9[k0 >> 2]), x[k1], x[k1 + 2], make_tw(t9[k1 >> 2]), mc);
+                bfly2<true, false, false, BK>(x[k0], x[k0 + 2], make_tw(t9[k0 >> 2]), x[k1], x[k1 + 2], make_tw(t9[k1 >> 2]), mc, rs.nofold(k0, 2),
+                                              rs.nofold(k1, 2));
             }
             NTT16_FENCE();
+            rs.stage(2);
 #pragma unroll
             for (int mm = 0; mm < 8; mm += 2) {
                 const int k0 = bfly_lo(mm, 4), k1 = bfly_lo(mm + 1, 4);
-                bfly2<true, false>(x[k0], x[k0 + 4], make_tw(t8[k0 >> 3]), x[k1], x[k1 + 4], make_tw(t8[k1 >> 3]), mc);
+                bfly2<true, false, false, BK>(x[k0], x[k0 + 4], make_tw(t8[k0 >> 3]), x[k1], x[k1 + 4], make_tw(t8[k1 >> 3]), mc, rs.nofold(k0, 4),
+                                              rs.nofold(k1, 4));
             }
+            rs.stage(4);
             {
                 const Tw t = make_tw(t7[0]);
 #pragma unroll
-                for (int k = 0; k < 8; k += 2) bfly2<true, false>(x[k], x[k + 8], t, x[k + 1], x[k + 9], t, mc);
+                for (int k = 0; k < 8; k += 2)
+                    bfly2<true, false, false, BK>(x[k], x[k + 8], t, x[k + 1], x[k + 9], t, mc, rs.nofold(k, 8), rs.nofold(k + 1, 8));
             }
 #pragma unroll
             for (int k = 0; k < 16; k++) p3[4 * k + 2 * (k >> 3)] = x[k];
@@ -950,6 +1060,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             NTT16_PRIO_I(3);
 #pragma unroll
             for (int k = 0; k < 16; k++) x[k] = p2[68 * k];
+            rs = GsRanges();
 #pragma unroll
             for (int sb = 3; sb >= 0; sb--) {
                 const int d = 8 >> sb;
@@ -958,8 +1069,9 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                     const int k0 = bfly_lo(mm, d), k1 = bfly_lo(mm + 1, d);
                     const Tw t0 = make_tw(NTT16_TWL(G::W << sb, (w << sb) + ((u32)k0 >> (4 - sb))));
                     const Tw t1 = make_tw(NTT16_TWL(G::W << sb, (w << sb) + ((u32)k1 >> (4 - sb))));
-                    bfly2<true, true>(x[k0], x[k0 + d], t0, x[k1], x[k1 + d], t1, mc);
+                    bfly2<true, true, false, BK>(x[k0], x[k0 + d], t0, x[k1], x[k1 + d], t1, mc, rs.nofold(k0, d), rs.nofold(k1, d));
                 }
+                rs.stage(d);
             }
 #pragma unroll
             for (int k = 0; k < 16; k++) p2[68 * k] = x[k];
@@ -976,6 +1088,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             // waiting for the younger half (equal priorities: the arbiter serves the oldest wave first;
             // profiles/r04/ntt16_lab_cycle_stamps_inverse.txt).
             __syncthreads();
+            rs = GsRanges();
 #pragma unroll
             for (int s = (int)LOGR - 1; s >= 0; s--) {
                 const int d = (int)(R >> 1) >> s;
@@ -984,8 +1097,10 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                     if (r & d) continue;
                     const Tw t = make_tw(NTT16_TWL(1u << s, (u32)r >> (LOGR - s)));
 #pragma unroll
-                    for (int c = 0; c < (int)CPT; c++) bfly<true, true>(x[CPT * r + c], x[CPT * (r + d) + c], t, mc);
+                    for (int c = 0; c < (int)CPT; c++)
+                        bfly<true, true, NTT16_INV_H2 != 0, BK>(x[CPT * r + c], x[CPT * (r + d) + c], t, mc, rs.nofold(CPT * r + c, CPT * d));
                 }
+                rs.stage(CPT * d);
             }
             NTT16_STAMP(7);
             const u64 n_inv = dcs->mod[mod].n_inv, n_inv_sh = dcs->mod[mod].n_inv_sh;

@@ -176,6 +176,7 @@ static std::string context_tables(piehip_ctx *h, const HostParams &hp, NttPlan &
             if (a < M && (1ull << 60) - hp.moduli[a] >= COLACC_FOLD_MAX_D) fold_moduli = false;  // q = 2^60 - d, d below the proven bound
         }
         ntt_plan_decide(pl, lazy_ok, small_moduli, fold_moduli);
+        pl.fold_mod_count = pl.fold_moduli ? M : 0;
         hipDeviceProp_t prop;
         pl.num_cus = (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) ? (u32)prop.multiProcessorCount : 256u;
     }
