@@ -48,7 +48,7 @@ struct NttPlan {
     bool lane_order = false;     // the register-blocked kernels apply: arrays that stay inside the library keep their EVALUATION side as
                                  // the threads of lane_kernel hold it (sigma), keys and masks have lane-ordered copies
     bool fold = false;           // lane-ordered transforms run as two half-size slices per limb; the neighbouring coefficient-wise
-                                 // kernels apply the outermost stage (kernels_pie.hip "Outer-stage folding")
+                                 // kernels apply the outermost stage (pie_kernel_common.h "Outer-stage folding")
     NttKernel lane_kernel = NttKernel::radix2;  // the kernel that defines the lane order
     u32 lane_logn = 0;           // log2 of its slice length,
     u32 lane_T = 0;              // its threads per slice
@@ -83,7 +83,7 @@ void ntt_plan_decide(NttPlan &pl, bool lazy_ok, bool small_moduli, bool fold_mod
 // q = 2^60 - d takes the folded block for d below this: the largest d its bound proof supports at z < 2^124 (2^28 at z < 2^123)
 static const u64 COLACC_FOLD_MAX_D = 1ull << 27;
 // The arithmetic kind (ArithKind, modarith.h) a launcher runs its kernel at: every kernel that reduces variable x variable column sums
-// takes the kind as one template argument, and the launchers turn this run-time value into it (with_arith, kernels_pie.hip).  The
+// takes the kind as one template argument, and the launchers turn this run-time value into it (with_arith, pie_kernel_common.h).  The
 // library passes its plans; tests/lazy_inputs builds an Arith from the plan or, explicitly, from its option fd=, and prints the kind
 // that ran (DESIGN.md section 5a lists who holds which kind).
 // mad, fold: the kind read as the two questions a caller may ask of it -- column accumulators at all? the folded block? --, fixed with
@@ -201,7 +201,7 @@ void launch_scale_pq_expand(const DevConsts *dc, u32 N, u32 L, const u64 *in, si
                             Arith ar);
 // Both conversions of a ciphertext multiplication in one launch, on the context (dc, L limbs, M = 2 L + 1; small_moduli and fold: its
 // plan's): X centred-lifted into slots 0, 1 of out[n_outer][4][M][N], Y scaled by P/Q into slots 2, 3.  fold: the outermost stage of
-// the forward transform that follows is applied on the store side (kernels_pie.hip, "Outer-stage folding").
+// the forward transform that follows is applied on the store side (pie_kernel_common.h, "Outer-stage folding").
 // An operand: polynomial c of row o at p + o*row + c*poly, COEFFICIENT format, and how it arrives --
 //   neither of the below   as the context's inverse transform left it: [L][N] limbs; with fold the outer stage is pending, [0, 4q) residues
 //   plain                  [L][N] limbs, canonical, nothing pending even where the context folds (launch_chain_drop, an unfolded inverse
@@ -237,7 +237,7 @@ bool expand_drop_built(u32 Ly, u32 Lx, u32 Lc);
 // e[nb][4][M][N] (a0 a1 b0 b1, EVALUATION) -> d[nb][3][M][N]
 void launch_tensor(const DevConsts *dc, u32 N, u32 M, const u64 *e, u64 *d, u32 nb, hipStream_t st, bool small_moduli);
 // d[nb][3][M][N] (COEFFICIENT) -> components 0,1 to out01 + bin*stride01 + c*L*N, component 2 to out2 + bin*stride2
-// fold: the outermost NTT stage of the neighbouring transforms is applied here (see kernels_pie.hip, "Outer-stage
+// fold: the outermost NTT stage of the neighbouring transforms is applied here (see pie_kernel_common.h, "Outer-stage
 // folding"); fold_comp2: component 2 also feeds a forward transform directly (3-component output)
 // p_only2 (pl.result_eval_q, with p_only01 and fold_comp2): component 2 likewise -- the product is not relinearised, launch_deg2_finish
 // adds all three terms
@@ -284,7 +284,7 @@ void launch_ct_mul_plain(const DevConsts *dc, u32 N, u32 L, const u64 *x, const 
 // limb drop of npoly polynomials in COEFFICIENT format: in[npoly][L][N] -> out[npoly][keep][N], the limbs L - 1 .. keep dropped one
 // after the other with centred rounding (include/piehip.h "Result limbs").  1 <= keep < L <= MAX_L; false (nothing launched) otherwise
 bool launch_limb_drop(const DevConsts *dc, u32 N, u32 L, u32 keep, const u64 *in, u64 *out, u32 npoly, hipStream_t st);
-// ---- chain limbs (include/piehip.h "Chain limbs"; kernels_pie.hip) -----------------------------------------------------------
+// ---- chain limbs (include/piehip.h "Chain limbs"; kernels_chain_drop.hip) -----------------------------------------------------------
 // The limb drop in front of the product chain, on npoly polynomials data[npoly][L][N] in COEFFICIENT format as the parent's inverse
 // transform left them (fold: outer stage pending): IN PLACE, the first `keep` limbs of every polynomial become the dropped
 // polynomial's, canonical, nothing pending; the limbs behind them are left alone.  1 <= keep < L <= MAX_L; false otherwise

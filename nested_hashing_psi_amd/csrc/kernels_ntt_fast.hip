@@ -401,7 +401,7 @@ ntt_fast_kernel(u64 *__restrict__ gdata, const u64x2 *__restrict__ gtw, const u6
                     v.x = mul_shoup(x[2 * k], m.n_inv, m.n_inv_sh, q);
                     v.y = mul_shoup(x[2 * k + 1], m.n_inv, m.n_inv_sh, q);
                 } else if (a.folded) {  // the consumer applies the outermost stage and N^-1 with a Shoup product, which
-                                        // takes the unnormalised [0, 4q) residues as they are (kernels_pie.hip fold_load)
+                                        // takes the unnormalised [0, 4q) residues as they are (pie_kernel_common.h fold_load)
                     v.x = x[2 * k];
                     v.y = x[2 * k + 1];
                 } else {  // split transform of a ring above 2^14: the global-memory stages expect canonical residues

@@ -1,7 +1,7 @@
 // kernels_slice.hip -- query-sliced stage A for gfx950 (include/piehip.h "Query slices"; DESIGN.md section 6 "Query slices"): the inner products of
 // BatchedFHEHIPPIE.cpp:96-116 for one handle's (inner hash function, limb) units, over one-limb arrays, and the placement of
 // accumulator limbs that arrive from the handles that computed them into the arrays the product chain reads (.cpp:117-126).
-// The term loop, the launch rules and the instruction blocks are those of kernels_pie.hip's tiled stage A (stage_a_common.h, madasm.h).
+// The term loop, the launch rules and the instruction blocks are those of kernels_stage_a.hip's tiled stage A (stage_a_common.h, madasm.h).
 #include "kernels.hpp"
 #include "madasm.h"
 #include "stage_a_common.h"

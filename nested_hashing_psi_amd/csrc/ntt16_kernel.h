@@ -483,13 +483,13 @@ inline u32 lane_to_std(u32 p) { return lane_to_std_t(p, T); }
 #define NTT16_LIFT_XCD 1
 #endif
 // ---- the tensor product in the inverse transform's load phase (TENSOR instantiation) ----------------------------------------
-// What tensor_kernel<true> (kernels_pie.hip) computes, for the one result polynomial d of the item, straight into x[16]: the
+// What tensor_kernel<true> (kernels_keyswitch.hip) computes, for the one result polynomial d of the item, straight into x[16]: the
 // result never goes to memory.  The operands arrive in [0, 8q) from the lazy forward transform; sign-mask subtractions bring
 // them below 2q (the second factor of a single product: below 4q is enough), the products go through the carry-free 30-bit
 // column sums (madasm.h) and one Barrett block that leaves [0, 4q) -- what the inverse butterflies take.  Bounds, q < 2^60:
 //   one product   a < 2q, b < 4q:  30-bit low halves, high halves < 2^31 and < 2^32; columns < 2^60, < 2^63, < 2^63; z < 8 q^2 < 2^123
 //   two products  all < 2q:        high halves < 2^31; columns < 2^61, < 2^63, < 2^63;                           z < 8 q^2 < 2^123
-// The block is kernels_pie.hip's PIE_COLACC123_TO_4Q (one-word Barrett with mu = floor(2^123 / q): z >> 59 from the
+// The block is stage_a_common.h's PIE_COLACC123_TO_4Q (one-word Barrett with mu = floor(2^123 / q): z >> 59 from the
 // carry-normalised columns, quotient estimate at most 2 short: modarith.h) on ten of the butterfly blocks' fixed registers.
 #ifndef NTT16_TENSOR_XCD
 #define NTT16_TENSOR_XCD 1
@@ -762,7 +762,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                 };
                 if (a.s0 == 1) {
                     // two folded slices per limb: the outermost stage (u, v) -> (u + v psi^{N/2}, u - v psi^{N/2}) is one more
-                    // butterfly, and this slice keeps its half (kernels_pie.hip fold_store does the same for the other kernels)
+                    // butterfly, and this slice keeps its half (pie_kernel_common.h fold_store does the same for the other kernels)
                     u64x2 fw;
                     fw.x = dcs->fold_w[lj];
                     fw.y = dcs->fold_w_sh[lj] >> 1;

@@ -41,7 +41,7 @@ struct DevConsts {
     u64 tQ_modp_sh[8];
     u64 tQF_modq[8][8];       // [j][k]  [floor(tQ/p_j)]_{q_k}
     u64 qi_modqj[8][8];       // [i][j]  q_i mod q_j  (centred digit lift of the BV key switch)
-    // outermost NTT stage folded into the neighbouring coefficient-wise kernels (kernels_pie.hip):
+    // outermost NTT stage folded into the neighbouring coefficient-wise kernels (pie_kernel_common.h):
     u64 fold_w[MAX_M + 1], fold_w_sh[MAX_M + 1];    // forward: psi^{N/2} (twiddle of the stage with one group)
     u64 fold_ia[MAX_M + 1], fold_ia_sh[MAX_M + 1];  // inverse: N^-1            (sum branch)
     u64 fold_ib[MAX_M + 1], fold_ib_sh[MAX_M + 1];  // inverse: psi^{-N/2} N^-1 (difference branch)
@@ -55,7 +55,7 @@ struct DevConsts {
     u64 t_inv_modq[8];
     u64 t_modq_sh[8];
     u64 Q_modt;
-    // limb drop of a result ciphertext (kernels_pie.hip "Limb drop"): dropping q_l turns the residue mod q_i, i < l, into
+    // limb drop of a result ciphertext (kernels_chain_drop.hip "Limb drop"): dropping q_l turns the residue mod q_i, i < l, into
     // (c_i - r) q_l^-1 with r the centred residue mod q_l
     u64 drop_inv[8][8], drop_inv_sh[8][8];  // [l][i]  [q_l^-1]_{q_i} and its Shoup companion
     u64 drop_off[8][8];                     // [l][i]  the smallest multiple of q_i that is >= (q_l - 1) / 2

@@ -1,6 +1,6 @@
-// pie_arith.h -- the arithmetic helpers of the base conversions of kernels_pie.hip (sign-mask conditional subtraction, the
+// pie_arith.h -- the arithmetic helpers of the base conversions of pie_convert.h (sign-mask conditional subtraction, the
 // constant-operand modular products as instruction blocks, the exact high product, the CRT lift), in a header so that
-// tests/arith_check compiles these definitions themselves.  Moved here word for word: kernels_pie.hip compiles to the same
+// tests/arith_check compiles these definitions themselves.  Moved here word for word: the kernels compile to the same
 // instructions as before (profiles/arith_blocks/).
 #pragma once
 #include "kernels.hpp"

@@ -1,4 +1,4 @@
-// stage_a_common.h -- what the stage A kernels of kernels_pie.hip (the whole query on one handle) and kernels_slice.hip (one handle's
+// stage_a_common.h -- what the stage A kernels of kernels_stage_a.hip (the whole query on one handle) and kernels_slice.hip (one handle's
 // (inner hash function, limb) units) share: the block -> tile map, the lane-ordered home of a coefficient, the instruction blocks of
 // the epilogue (column accumulator -> residue, the sum with the minus word), the term loop of the tiled kernels (stage_a_terms:
 // stage_a_tiled_kernel and stage_a_slice_kernel are a prologue and an epilogue around it), the multiply-add block of the
@@ -13,7 +13,7 @@
 
 namespace piehip {
 
-// fixed scratch registers of the instruction blocks here and in kernels_pie.hip ("constant-operand modular products")
+// fixed scratch registers of the instruction blocks here and in pie_arith.h ("constant-operand modular products")
 #define PIE_ASM_CLOB "vcc", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71"
 
 // Block -> (coefficient block, limb, inner hash function, group of bin layers).  The `groups` blocks of one tile read the same
@@ -357,7 +357,7 @@ __device__ __forceinline__ void stage_a_terms(const StageAQueries &qs, size_t io
 }
 
 // ---------------------------------------------------------------------------------------------
-// Pieces of the resident kernel (stage_a_resident_kernel of kernels_pie.hip): the other loop order.  The thread keeps the index
+// Pieces of the resident kernel (stage_a_resident_kernel of kernels_stage_a.hip): the other loop order.  The thread keeps the index
 // words of its coefficient in registers, already cut into 30-bit halves, and the database words of the launch's layers stream
 // past them -- so a database word arrives once for the Q queries and is cut once, not once per query as in colacc_mac2.
 // ---------------------------------------------------------------------------------------------

@@ -169,7 +169,7 @@ def mac_columns(d01, dig, key, j, c, v=0, whole=False):
 # ---- lane order ----------------------------------------------------------------------------------------------------------------
 def lane_map(N, slice_len, T, kp):
     """lane-order position -> standard position for slices of slice_len coefficients, T threads per slice, kp coefficient pairs per
-    thread: pair k of thread tau sits at k T + tau and belongs at kp tau + k (kernels_pie.hip, relin_mac_kernel)"""
+    thread: pair k of thread tau sits at k T + tau and belongs at kp tau + k (kernels_keyswitch.hip, relin_mac_kernel)"""
     assert 2 * kp * T == slice_len and N % slice_len == 0
     p = np.arange(N)
     pp = (p % slice_len) >> 1

@@ -3,7 +3,7 @@ that the kernels' one-word operand stays inside its contract on them, and that t
 
 The drop of limb l takes r = c mod q_l centred and leaves c_i <- (c_i - r) q_l^-1 mod q_i (tests/test_result_limbs.py pins this
 residue form on whole integers).  The device forms -- limb_drop_kernel, chain_drop_kernel and drop_limbs inside
-expand_both_drop_kernel (kernels_pie.hip) -- branch on the sign mask s = [c_l > (q_l - 1)/2] and hand the Shoup product the word
+expand_both_drop_kernel (kernels_chain_drop.hip) -- branch on the sign mask s = [c_l > (q_l - 1)/2] and hand the Shoup product the word
 x = c_i - c_l + off + (s & (q_l - off)), off the smallest multiple of q_i that is >= (q_l - 1)/2 (params.cpp).  A drop of several
 limbs meets DERIVED residues from its second step on, so planting edges in the residues as given reaches the first step only: the
 families here are built backwards (undrop) from the residue every step is to meet.

@@ -36,7 +36,7 @@ KIND_CHAIN = (1 << 50, "barrett_60", None)         # a chain of each kind (chain
 # (parent, level) kinds of the chains the chain-limbs rows use
 CHAIN_KINDS = {None: ("fold", "fold"), "barrett_60": ("barrett", "barrett"), 1 << 50: ("wide", "wide"),
                "one_p_61": ("wide", "fold"), "barrett_one_p_61": ("wide", "barrett")}
-FUSED_PAIRS = {(2, 1), (3, 2), (4, 3), (5, 4), (6, 5), (7, 6), (4, 2), (6, 4)}   # PIE_CHAIN_DROP_PAIRS (kernels_pie.hip)
+FUSED_PAIRS = {(2, 1), (3, 2), (4, 3), (5, 4), (6, 5), (7, 6), (4, 2), (6, 4)}   # PIE_CHAIN_DROP_PAIRS (kernels_chain_drop.hip)
 
 
 def b_(v):

@@ -1,6 +1,6 @@
 """Stage A over long index sums (reference BatchedFHEHIPPIE.cpp:101-116): sum_j idx[h][j] * db[h][bin][j] + minus.
 
-Stage A of a whole query on one handle (kernels_pie.hip): a batch goes through stage_a_tiled_kernel<BPT, Q, DEPTH, MAD> in groups of
+Stage A of a whole query on one handle (kernels_stage_a.hip): a batch goes through stage_a_tiled_kernel<BPT, Q, DEPTH, MAD> in groups of
 Q = 2..4 queries (BPT bin layers per thread, DEPTH terms in flight; three queries on a ring that fills the chip through the resident
 kernel: tests/test_gpu_stage_a_resident.py), one query through stage_a_mad_kernel<BPT> (four terms in flight) or, on the wide
 arithmetic, stage_a_kernel<BPT> (none), with a divisor of b layers per thread or groups of seven / eight and a remainder launch
@@ -16,7 +16,7 @@ proof allows still does not wrap), so the index and database words here are ever
 [q - 2^24, q): the columns as full as the moduli allow, data that still tells lanes, layers and queries apart.  E runs
 across the periods (31..33, 63..65, 119..121 where both MAD periods line up and E = 120 hands the epilogue 8 uncarried and
 15 unreduced terms at once, 148, 240, 581; 1 and 2, sums shorter than the ring of terms in flight) and b / nq pick every template
-instantiation (the `kernels` column, from the launcher rules: launch_stage_a_one in kernels_pie.hip; for batches, stage_a_query_group / stage_a_layers / stage_a_depth in
+instantiation (the `kernels` column, from the launcher rules: launch_stage_a_one in kernels_stage_a.hip; for batches, stage_a_query_group / stage_a_layers / stage_a_depth in
 stage_a_common.h).  Every result is compared bit for bit with the oracle's run() (oracle/pie_oracle.c: one mulmod + addmod per
 term, independent of the GPU's lazy scheme); K = 2, so stage A feeds the whole product chain.
 

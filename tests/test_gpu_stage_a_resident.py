@@ -1,4 +1,4 @@
-"""Stage A of a query batch with the index words resident in registers (stage_a_resident_kernel of kernels_pie.hip).
+"""Stage A of a query batch with the index words resident in registers (stage_a_resident_kernel of kernels_stage_a.hip).
 
 launch_stage_a_batch sends a group of three queries to that kernel where stage_a_resident_lpp (stage_a_common.h) says so: E = 14 or
 E = 12 (the two instantiations), more layers than one tiled group holds (b > 3), and at least STAGE_A_RESIDENT_MIN_THREADS = 65 536

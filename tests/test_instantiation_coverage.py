@@ -90,7 +90,8 @@ def test_nothing_launched(built):
 
 def test_makefile_files():
     files = ic.makefile_hip_files()
-    assert {"kernels_pie", "kernels_slice", "kernels_ntt16", "kernels_ntt_fast"} <= set(files)
+    assert {"kernels_pie", "kernels_stage_a", "kernels_convert", "kernels_chain_drop", "kernels_keyswitch", "kernels_slice", "kernels_ntt16",
+            "kernels_ntt_fast"} <= set(files)
     assert all(os.path.exists(os.path.join(ic.CSRC, f + ".hip")) for f in files)
 
 

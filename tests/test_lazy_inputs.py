@@ -92,7 +92,7 @@ def _mac_case(uniform, L=7, N=4096):
 
 
 def test_mac_columns_reach_the_claimed_bounds_and_stop_there():
-    """relin_mac_kernel at L = 7 (kernels_pie.hip): column 0 < (L + 8) 2^60 + 2^30 < 2^64, column 1 < 2 L 2^60 + 2^32"""
+    """relin_mac_kernel at L = 7 (kernels_keyswitch.hip): column 0 < (L + 8) 2^60 + 2^30 < 2^64, column 1 < 2 L 2^60 + 2^32"""
     L = 7
     qs, ops = _mac_case(False)
     bound0, bound1 = (L + 8) * P60 + (1 << 30), 2 * L * P60 + (1 << 32)

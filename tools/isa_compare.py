@@ -1,5 +1,6 @@
 """per-kernel comparison of two hipcc -S listings of one file (before and after a change):
-    python tools/isa_compare.py [--removed FILE] [--renamed FILE] [--neutral-ordinals] before.s after.s
+    python tools/isa_compare.py [--removed FILE] [--renamed FILE] [--neutral-ordinals] before.s after.s [after2.s ...]
+Several "after" listings: the file was cut into these (each kernel in exactly one of them); they are read as one listing.
 Kernels that only the second listing has are listed with their figures; one that only the first has is an error.  A kernel counts as
 identical when its instructions, its kernel descriptor and its metadata entry are (the compilation-unit id, __hip_cuid_<hash>,
 neutralised); for the others: tools/isa_regs.py's columns, waves per SIMD, instruction totals and the counts of the memory and
@@ -98,10 +99,18 @@ def main():
     ap.add_argument("--renamed", default=None)
     ap.add_argument("--neutral-ordinals", action="store_true")
     ap.add_argument("before")
-    ap.add_argument("after")
+    ap.add_argument("after", nargs="+")
     args = ap.parse_args()
     pa, pt = kernels(args.before, args.neutral_ordinals)
-    he, ht = kernels(args.after, args.neutral_ordinals)
+    he, ht = collections.OrderedDict(), ""
+    for path in args.after:
+        part, txt = kernels(path, args.neutral_ordinals)
+        twice = [short(k) for k in part if k in he]
+        assert not twice, "kernels that more than one of the second listings has: %s" % twice
+        he.update(part)
+        ht += txt
+        if len(args.after) > 1:
+            print("second listing, part: %s (%d kernels)" % (path, len(part)))
     renamed = []
     if args.renamed:
         for ln in open(args.renamed):

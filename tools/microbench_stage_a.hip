@@ -1,7 +1,7 @@
 // Stage A's kernel in isolation (tools/, not shipped): the shipped kernel source, launched over a rotation of databases
 // so that every launch streams from HBM, per (layers per thread, coefficients per thread, terms in flight).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Inested_hashing_psi_amd/csrc tools/microbench_stage_a.hip -o /tmp/mbsa
-#include "../nested_hashing_psi_amd/csrc/kernels_pie.hip"
+#include "../nested_hashing_psi_amd/csrc/kernels_stage_a.hip"
 #include <cstdio>
 #include <cstdlib>
 using namespace piehip;

@@ -3,7 +3,7 @@
 // queries' index matrices distinct or all the same array (how much of the time is index-matrix traffic); and the resident kernel
 // (stage_a_resident_kernel: index words in registers, layers streaming past) beside the shipped tilings, at the C3 and the C2 ring.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Inested_hashing_psi_amd/csrc tools/microbench_stage_a_batch.hip -o build_lab/mbsab
-#include "../nested_hashing_psi_amd/csrc/kernels_pie.hip"
+#include "../nested_hashing_psi_amd/csrc/kernels_stage_a.hip"
 #include <cstdio>
 #include <cstdlib>
 using namespace piehip;
