@@ -117,7 +117,6 @@ struct NttExtra {
     u32 copy_K = 1, copy_L = 1, copy_M = 1;
     u32 skip_L = 0, skip_M = 0;
     bool lazy_out = false;  // forward, lane order: leave the residues in [0, 8q) (the consumer reduces anyway)
-    bool folded = false;    // set by launch_ntt(.., folded): inverse transforms then hand over unnormalised [0, 4q) residues
     bool x_lane_in = false; // 16-coefficient kernel, inverse, standard order in: the operand-0 polynomials are READ, lane-ordered, from
                             // where copy_out would have put them (stage A wrote them there: StageAXOut) and nothing is copied
 };
@@ -210,8 +209,9 @@ void launch_scale_pq_expand(const DevConsts *dc, u32 N, u32 L, const u64 *in, si
 //                          (src_dc: that level's constants); dropped to L limbs in the load phase.  Folded rings with every modulus in
 //                          (2^59, 2^60), and (Y's, X's, L) a combination expand_drop_built knows
 //   q_ready (X only)       the Q limbs of X in `out` already hold its EVALUATION form (NttExtra, StageAXOut) and are left alone
-// Built: both pending on one polynomial distance, L <= MAX_L; both plain; Y dropped with X dropped from Y's level (under Y's
-// constants) or another, or with X pending and q_ready.  false, nothing launched, for anything else.
+// Built: both pending on one polynomial distance, L <= MAX_L, with fold only where X is q_ready (a folding plan has xq_reuse); both
+// plain; Y dropped with X dropped from Y's level (under Y's constants) or another, or with X pending and q_ready.  false, nothing
+// launched, for anything else.
 struct ExpandOperand {
     const u64 *p = nullptr;
     size_t row = 0, poly = 0;

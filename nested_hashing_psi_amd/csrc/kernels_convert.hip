@@ -59,11 +59,14 @@ bool launch_expand_pair(const DevConsts *dc, u32 N, u32 L, const ExpandOperand &
     if (ydrop) return launch_expand_pair_drop(dc, N, L, x, y, n_outer, out, st, ar, fold);   // (kernels_chain_drop.hip)
     if (xdrop || x.plain != y.plain) return false;
     if (x.plain) return launch_expand_pair_plain(dc, N, L, x, y, n_outer, out, st, ar, fold);   // (kernels_chain_drop.hip)
+    if (fold && !x.q_ready) return false;   // (a folded context has plan.xq_reuse: its X always arrives with the Q limbs in place)
     return x.poly == y.poly && with_u32<1, 7>(L, [&](auto L_) {
         with_arith(ar, [&](auto K_) {
-            with_bools([&](auto F_, auto Q_) {
+            auto launch = [&](auto F_, auto Q_) {
                 hipLaunchKernelGGL((expand_both_kernel<F_(), L_(), K_(), Q_()>), grid, block, 0, st, dc, N, x.p, x.row, y.p, y.row, y.poly, out, n_outer);
-            }, fold, x.q_ready);
+            };
+            if (fold) launch(std::true_type{}, std::true_type{});
+            else with_bools([&](auto Q_) { launch(std::false_type{}, Q_); }, x.q_ready);
         });
     });
 }

@@ -196,11 +196,8 @@ void launch_ntt(const NttPlan &pl, u64 *data, u32 nlimbs, u32 mod_base, u32 mod_
         launch_ntt16(pl, data, nlimbs, mod_base, mod_count, inverse, sigma, st, ex);
         return;
     }
-    if (folded) {  // two half-size slices per limb, outer stage done by the neighbouring kernels
-        NttExtra exf;
-        if (ex) exf = *ex;
-        exf.folded = true;
-        launch_ntt_fast(pl, pl.twc_fold, 1, data, nlimbs, mod_base, mod_count, inverse, sigma, st, nullptr, 0, &exf);
+    if (folded) {  // two half-size slices per limb, outer stage done by the neighbouring kernels (forward, standard order: see ntt_route)
+        launch_ntt_fast(pl, pl.twc_fold, 1, data, nlimbs, mod_base, mod_count, inverse, sigma, st, nullptr, 0, ex);
         return;
     }
     NttArgs a;

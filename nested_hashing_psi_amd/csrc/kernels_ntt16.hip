@@ -52,11 +52,7 @@ static void launch_ntt16_kind(const ntt16::Args &a, bool inverse, bool lift, u32
 template <u32 LOGNS>
 static void launch_ntt16_t(const ntt16::Args &a, bool inverse, bool lift, u32 num_cus, hipStream_t st, bool tensor = false, bool fd = false)
 {
-#if NTT16_FOLD_BFLY
     if (fd) return launch_ntt16_kind<LOGNS, ArithKind::fold>(a, inverse, lift, num_cus, st, tensor);
-#else  // (the butterflies are Barrett-kind blocks everywhere: only the tensor load phase has a folded form)
-    if (fd && tensor) return launch_ntt16_k<LOGNS, ntt16::ntt16_kernel_t<LOGNS, true, false, true, ArithKind::fold>>(a, num_cus, st);
-#endif
     launch_ntt16_kind<LOGNS, ArithKind::barrett>(a, inverse, lift, num_cus, st, tensor);
 }
 // A plan with fold_moduli speaks of its Q and P moduli [0, fold_mod_count); the plaintext modulus behind them (the client's transforms

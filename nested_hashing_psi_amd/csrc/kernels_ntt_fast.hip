@@ -49,7 +49,6 @@ struct NttFastArgs {
     // transforms it; lift_L = 0 disables.
     const u64 *lift_src;
     u32 lift_L;
-    u32 sigma_split;  // forward, lane order: store as if the limb were 2^sigma_split slices (the folded layout)
     u32 mod_base, mod_count;
     // inverse, standard order in: also write the lane-ordered EVALUATION input of operand polynomials to the Q limbs of
     // the QP operand array (the tensor product then needs no forward transform for them).  Limb li of the input
@@ -58,7 +57,6 @@ struct NttFastArgs {
     u32 copy_K, copy_L, copy_M;
     // forward: the transformed limbs are a compact enumeration of [nb][4][skip_M] without limbs < skip_L of slots 0, 1
     u32 skip_L, skip_M;
-    u32 folded;  // s0 != 0 because the caller's neighbouring kernels apply the outermost stage (not the global-memory stages)
 };
 
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
@@ -267,9 +265,7 @@ ntt_fast_kernel(u64 *__restrict__ gdata, const u64x2 *__restrict__ gtw, const u6
                     }
                     v.x = r0;
                     v.y = r1;
-                    // lane order of a limb transformed as 2^sigma_split slices: slice tau / Ts, thread tau % Ts
-                    const u32 Ts = T >> a.sigma_split;
-                    *reinterpret_cast<u64x2 *>(g + (size_t)(tau / Ts) * (n >> a.sigma_split) + 2 * (k * Ts + tau % Ts)) = v;
+                    *reinterpret_cast<u64x2 *>(g + 2 * (k * T + tau)) = v;
                 }
                 continue;
             }
@@ -400,10 +396,6 @@ ntt_fast_kernel(u64 *__restrict__ gdata, const u64x2 *__restrict__ gtw, const u6
                 if (a.s0 == 0) {
                     v.x = mul_shoup(x[2 * k], m.n_inv, m.n_inv_sh, q);
                     v.y = mul_shoup(x[2 * k + 1], m.n_inv, m.n_inv_sh, q);
-                } else if (a.folded) {  // the consumer applies the outermost stage and N^-1 with a Shoup product, which
-                                        // takes the unnormalised [0, 4q) residues as they are (pie_kernel_common.h fold_load)
-                    v.x = x[2 * k];
-                    v.y = x[2 * k + 1];
                 } else {  // split transform of a ring above 2^14: the global-memory stages expect canonical residues
                     u64 r0 = x[2 * k], r1 = x[2 * k + 1];
                     r0 = r0 >= q2 ? r0 - q2 : r0;
@@ -486,7 +478,6 @@ void launch_ntt_fast(const NttPlan &pl, const u64 *twc, u32 s0, u64 *data, u32 n
     a.sigma = sigma ? 1u : 0u;
     a.lift_src = lift_src;
     a.lift_L = (lift_src && !inverse && s0 == 0) ? lift_L : 0;
-    a.sigma_split = 0;  // (the lifted digits in the lane order of two folded slices: those contexts' lane order is the other kernel's now)
     a.mod_base = mod_base;
     a.mod_count = mod_count;
     a.copy_out = (ex && inverse && !sigma) ? ex->copy_out : nullptr;
@@ -495,7 +486,6 @@ void launch_ntt_fast(const NttPlan &pl, const u64 *twc, u32 s0, u64 *data, u32 n
     a.copy_M = ex ? ex->copy_M : 1;
     a.skip_L = (ex && !inverse) ? ex->skip_L : 0;
     a.skip_M = ex ? ex->skip_M : 0;
-    a.folded = (ex && ex->folded) ? 1u : 0u;
     const bool lazy = ex && ex->lazy_out && !inverse && sigma && !a.lift_L;
     // resident workgroups per CU by LDS: 136 KiB -> 1, 68 KiB -> 2, 34 KiB -> 4
     const u32 per_cu = logn == 14 ? 1 : (logn == 13 ? 2 : 4);
@@ -512,8 +502,10 @@ void launch_ntt_fast(const NttPlan &pl, const u64 *twc, u32 s0, u64 *data, u32 n
         }                                                                         \
     } while (0)
     if (logn == 14) NTT_DISPATCH(14);
-    else if (logn == 13) NTT_DISPATCH(13);
-    else NTT_DISPATCH(12);
+    else if (logn == 13) {  // ntt_route gives every inverse and every lane-order call on 2^13 slices to the 16-coefficient kernel
+        assert(!inverse && !sigma);
+        launch_one<13, false, false>(a, maxg, st);
+    } else NTT_DISPATCH(12);
 #undef NTT_DISPATCH
 }
 

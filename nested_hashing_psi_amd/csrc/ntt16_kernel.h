@@ -122,19 +122,12 @@ struct ModC {
 //                                                                            -- NTT16_GSN1 / NTT16_GSN1H, 16 / 15
 // Which inverse butterflies may pass below_T is static (GsRanges below).  The forward transform has no such case: its outputs
 // u + v and u + 4q - v are never below 4q, let alone T.
-#ifndef NTT16_INV_H2
-#define NTT16_INV_H2 1
-#endif
-// -DNTT16_FOLD_BFLY=0: the Barrett-kind blocks everywhere, and no fold-kind instantiation beside the tensor launch's
-#ifndef NTT16_FOLD_BFLY
-#define NTT16_FOLD_BFLY 1
-#endif
-template <bool INV, bool SC, bool H2 = SC && (!INV || NTT16_INV_H2), ArithKind KIND = ArithKind::barrett>
+template <bool INV, bool SC, bool H2 = SC, ArithKind KIND = ArithKind::barrett>
 __device__ __forceinline__ void bfly(u64 &x0, u64 &y0, const Tw &t0, const ModC &m, bool below_T = false)
 {
     u64 a0 = x0;  // forward, seeded: the tied operand -- a on entry, a' on exit
     const u64 b0 = y0;
-    if (INV && KIND == ArithKind::fold && NTT16_FOLD_BFLY) {
+    if (INV && KIND == ArithKind::fold) {
         u64 ao0, bo0;
         if (below_T) {  // (a compile-time constant at every call site once the stage loops are unrolled)
             u64 cs;
@@ -158,7 +151,7 @@ __device__ __forceinline__ void bfly(u64 &x0, u64 &y0, const Tw &t0, const ModC 
                 NTT16_GSF1(NTT16_V);
         }
         x0 = ao0, y0 = bo0;
-    } else if (!INV && KIND == ArithKind::fold && NTT16_FOLD_BFLY) {
+    } else if (!INV && KIND == ArithKind::fold) {
         u32 bol0, boh0;
         u64 cs;
         if (SC && H2)
@@ -479,9 +472,6 @@ inline u32 lane_to_std(u32 p) { return lane_to_std_t(p, T); }
 #define NTT16_PRIO_F(i) NTT16_PASS_PRIO(NTT16_PRIO_PICK(i, NTT16_PF))
 #define NTT16_PRIO_I(i) NTT16_PASS_PRIO(NTT16_PRIO_PICK(i, NTT16_PI))
 
-#ifndef NTT16_LIFT_XCD
-#define NTT16_LIFT_XCD 1
-#endif
 // ---- the tensor product in the inverse transform's load phase (TENSOR instantiation) ----------------------------------------
 // What tensor_kernel<true> (kernels_keyswitch.hip) computes, for the one result polynomial d of the item, straight into x[16]: the
 // result never goes to memory.  The operands arrive in [0, 8q) from the lazy forward transform; sign-mask subtractions bring
@@ -491,9 +481,6 @@ inline u32 lane_to_std(u32 p) { return lane_to_std_t(p, T); }
 //   two products  all < 2q:        high halves < 2^31; columns < 2^61, < 2^63, < 2^63;                           z < 8 q^2 < 2^123
 // The block is stage_a_common.h's PIE_COLACC123_TO_4Q (one-word Barrett with mu = floor(2^123 / q): z >> 59 from the
 // carry-normalised columns, quotient estimate at most 2 short: modarith.h) on ten of the butterfly blocks' fixed registers.
-#ifndef NTT16_TENSOR_XCD
-#define NTT16_TENSOR_XCD 1
-#endif
 // x in [0, 8q) -> [0, 2q): csub_neg by 4q, then by 2q, as one statement
 __device__ __forceinline__ u64 csub2_neg(u64 x, u64 negm4, u64 negm2)
 {
@@ -567,17 +554,14 @@ __device__ __forceinline__ u64 colacc123_to_4q(u64 c0, u64 c1, u64 c2, u64 mu, u
     return r;
 }
 // x[16] <- a b (TWO: a b + c d) of the lane-ordered slices at pa, pb (pc, pd).  Four operands of 16 coefficients do not fit
-// beside x[16]: the 16-byte lanes come in as a window of NTT16_TENSOR_DEPTH pairs per operand, the next one requested as a pair's
+// beside x[16]: the 16-byte lanes come in as a window of DEPTH pairs per operand, the next one requested as a pair's
 // products are done (its registers are the ones just freed).
-#ifndef NTT16_TENSOR_DEPTH
-#define NTT16_TENSOR_DEPTH 3
-#endif
 // FD (NttPlan::fold_moduli): the folded block reduces the column sums, mu is not used
 template <u32 T, bool TWO, bool FD>
 __device__ __forceinline__ void tensor_load(u64 (&x)[16], const u64 *pa, const u64 *pb, const u64 *pc, const u64 *pd, u32 voffb, u64 q,
                                             u64 mu)
 {
-    constexpr int DEPTH = NTT16_TENSOR_DEPTH;
+    constexpr int DEPTH = 3;
     const u64 nq = 0 - q, nq2 = 0 - 2 * q, nq4 = 0 - 4 * q;
     u64x2 va[8], vb[8], vc[8], vd[8];
 #define NTT16_TLOAD(j)                                                           \
@@ -625,9 +609,8 @@ __device__ __forceinline__ void tensor_load(u64 (&x)[16], const u64 *pa, const u
 template <u32 LOGNS, bool INV, bool LIFT = false, bool TENSOR = false, ArithKind KIND = ArithKind::barrett>
 __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 {
-    static_assert(KIND == ArithKind::barrett || (KIND == ArithKind::fold && (TENSOR || NTT16_FOLD_BFLY)), "the kinds of 60-bit moduli");
+    static_assert(KIND == ArithKind::barrett || KIND == ArithKind::fold, "the kinds of 60-bit moduli");
     constexpr bool FD = KIND == ArithKind::fold;
-    constexpr ArithKind BK = NTT16_FOLD_BFLY ? KIND : ArithKind::barrett;  // the butterflies' kind
     typedef Geo<LOGNS> G;
     constexpr u32 NS = G::NS, T = G::T, R = G::R, LOGR = G::LOGR, CPT = G::CPT, TWK_PER_SLICE = G::TWK_PER_SLICE;
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
@@ -671,10 +654,8 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
         u32 item_l = item;
         if (lift) {
             item_l = item - a.lift_first;
-#if NTT16_LIFT_XCD
             const u32 G = a.lift_L << a.s0, blk8 = 8 * G, within = item_l % blk8;
             if (item_l - within + blk8 <= a.nitems - a.lift_first) item_l = item_l - within + (within & 7) * G + (within >> 3);
-#endif
         }
         // TENSOR: the three items d = 0, 1, 2 of one (row, limb, slice) read the same four operand slices (a0 b0 | a0 b1 a1 b0 | a1 b1).
         // Enumerated with d innermost and dealt like the digit items above (blocks of 8 x 3), they run in workgroups 8 apart in the
@@ -686,19 +667,12 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
         if (TENSOR) {
             const u32 M_ = a.mod_count, TL = a.tq_L, TM = M_ - TL;  // TM: limbs with triples
             if (item < a.tq_first) {
-#if NTT16_TENSOR_XCD
                 u32 il = item;
                 const u32 within = il % 24;
                 if (il - within + 24 <= a.tq_first) il = il - within + (within & 7) * 3 + (within >> 3);
                 const u32 u = il / 3, lm = u >> a.s0;
                 t_d = il % 3, t_blk = u & ((1u << a.s0) - 1), t_row = lm / TM;
                 t_limb = (t_row * 3 + t_d) * M_ + TL + lm % TM;
-#else
-                const u32 lm = item >> a.s0;
-                t_blk = item & ((1u << a.s0) - 1);
-                t_row = lm / (3 * TM), t_d = (lm / TM) % 3;
-                t_limb = (t_row * 3 + t_d) * M_ + TL + lm % TM;
-#endif
             } else {
                 const u32 v = item - a.tq_first, lm = v >> a.s0;
                 t_d = 2, t_blk = v & ((1u << a.s0) - 1), t_row = lm / TL;
@@ -776,7 +750,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 #pragma unroll
                     for (int k = 0; k < 16; k++) {
                         u64 u0 = lift1(x[k]), v0 = lift1(y[k]);
-                        bfly<false, true, true, BK>(u0, v0, t, mc);
+                        bfly<false, true, true, KIND>(u0, v0, t, mc);
                         x[k] = blk ? v0 : u0;
                     }
                 } else {
@@ -798,7 +772,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                     if (r & d) continue;
                     const Tw t = make_tw(NTT16_TWL(1u << s, (u32)r >> (LOGR - s)));
 #pragma unroll
-                    for (int c = 0; c < (int)CPT; c++) bfly<false, true, true, BK>(x[CPT * r + c], x[CPT * (r + d) + c], t, mc);
+                    for (int c = 0; c < (int)CPT; c++) bfly<false, true, true, KIND>(x[CPT * r + c], x[CPT * (r + d) + c], t, mc);
                 }
             }
             NTT16_STAMP(1);
@@ -821,7 +795,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                     const int k0 = bfly_lo(mm, d), k1 = bfly_lo(mm + 1, d);
                     const Tw t0 = make_tw(NTT16_TWL(G::W << sb, (w << sb) + ((u32)k0 >> (4 - sb))));
                     const Tw t1 = make_tw(NTT16_TWL(G::W << sb, (w << sb) + ((u32)k1 >> (4 - sb))));
-                    bfly2<false, true, true, BK>(x[k0], x[k0 + d], t0, x[k1], x[k1 + d], t1, mc);
+                    bfly2<false, true, true, KIND>(x[k0], x[k0 + d], t0, x[k1], x[k1 + d], t1, mc);
                 }
             }
             // per-lane twiddles from here on, each stage's loaded one stage ahead (the last stages' eight in two halves: with the
@@ -841,27 +815,27 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             {
                 const Tw t = make_tw(t7[0]);
 #pragma unroll
-                for (int k = 0; k < 8; k += 2) bfly2<false, false, true, BK>(x[k], x[k + 8], t, x[k + 1], x[k + 9], t, mc);
+                for (int k = 0; k < 8; k += 2) bfly2<false, false, true, KIND>(x[k], x[k + 8], t, x[k + 1], x[k + 9], t, mc);
             }
             NTT16_LOAD3H(t10, 3, 0);
             NTT16_FENCE();
 #pragma unroll
             for (int mm = 0; mm < 8; mm += 2) {
                 const int k0 = bfly_lo(mm, 4), k1 = bfly_lo(mm + 1, 4);
-                bfly2<false, false, true, BK>(x[k0], x[k0 + 4], make_tw(t8[k0 >> 3]), x[k1], x[k1 + 4], make_tw(t8[k1 >> 3]), mc);
+                bfly2<false, false, true, KIND>(x[k0], x[k0 + 4], make_tw(t8[k0 >> 3]), x[k1], x[k1 + 4], make_tw(t8[k1 >> 3]), mc);
             }
             NTT16_LOAD3H(t10, 3, 4);
             NTT16_FENCE();
 #pragma unroll
             for (int mm = 0; mm < 8; mm += 2) {
                 const int k0 = bfly_lo(mm, 2), k1 = bfly_lo(mm + 1, 2);
-                bfly2<false, false, false, BK>(x[k0], x[k0 + 2], make_tw(t9[k0 >> 2]), x[k1], x[k1 + 2], make_tw(t9[k1 >> 2]), mc);
+                bfly2<false, false, false, KIND>(x[k0], x[k0 + 2], make_tw(t9[k0 >> 2]), x[k1], x[k1 + 2], make_tw(t9[k1 >> 2]), mc);
             }
             NTT16_LOAD4(t11, 0, 4);
             NTT16_FENCE();
 #pragma unroll
             for (int k = 0; k < 16; k += 4)
-                bfly2<false, false, false, BK>(x[k], x[k + 1], make_tw(t10[k >> 1]), x[k + 2], x[k + 3], make_tw(t10[(k >> 1) + 1]), mc);
+                bfly2<false, false, false, KIND>(x[k], x[k + 1], make_tw(t10[k >> 1]), x[k + 2], x[k + 3], make_tw(t10[(k >> 1) + 1]), mc);
 #pragma unroll
             for (int k = 0; k < 16; k++) p3[4 * k + 2 * (k >> 3)] = x[k];
             NTT16_STAMP(6);
@@ -879,7 +853,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 #pragma unroll
             for (int g4 = 0; g4 < 4; g4++) {  // stage 11: both butterflies of a group of four share its twiddle
                 const Tw t = make_tw(t11[g4]);
-                bfly2<false, false, false, BK>(x[4 * g4], x[4 * g4 + 2], t, x[4 * g4 + 1], x[4 * g4 + 3], t, mc);
+                bfly2<false, false, false, KIND>(x[4 * g4], x[4 * g4 + 2], t, x[4 * g4 + 1], x[4 * g4 + 3], t, mc);
                 if (g4 == 1) {
                     NTT16_FENCE();
                     _Pragma("unroll") for (int j_ = 4; j_ < 8; j_++) t12[j_] = *at_bytes(tw4 + 64 * (4 + j_), lb);
@@ -889,14 +863,14 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             NTT16_FENCE();
 #pragma unroll
             for (int k = 0; k < 16; k += 4)  // stage 12
-                bfly2<false, false, false, BK>(x[k], x[k + 1], make_tw(t12[k >> 1]), x[k + 2], x[k + 3], make_tw(t12[(k >> 1) + 1]), mc);
+                bfly2<false, false, false, KIND>(x[k], x[k + 1], make_tw(t12[k >> 1]), x[k + 2], x[k + 3], make_tw(t12[(k >> 1) + 1]), mc);
             NTT16_STAMP(7);
             // ---- lane-ordered store -------------------------------------------------------------------------------------------
             const bool lazy = (a.flags & F_LAZY_OUT) != 0 && !lift;  // the key-switch MAC splits canonical digits into 30-bit halves
             if (!lazy) {
 #pragma unroll
                 for (int k = 0; k < 16; k++)
-                    x[k] = BK == ArithKind::fold ? fold_csub_neg(x[k], 0 - q) : csub_neg(csub_neg(csub_neg(x[k], 0 - q4), 0 - q2), 0 - q);
+                    x[k] = FD ? fold_csub_neg(x[k], 0 - q) : csub_neg(csub_neg(csub_neg(x[k], 0 - q4), 0 - q2), 0 - q);
             }
 #pragma unroll
             for (int j = 0; j < 8; j++) {
@@ -986,7 +960,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             GsRanges rs;  // (read at ArithKind::fold only; reset at every pass entry)
 #pragma unroll
             for (int k = 0; k < 16; k += 4) {  // stage 12
-                bfly2<true, false, false, BK>(x[k], x[k + 1], make_tw(t12[k >> 1]), x[k + 2], x[k + 3], make_tw(t12[(k >> 1) + 1]), mc,
+                bfly2<true, false, false, KIND>(x[k], x[k + 1], make_tw(t12[k >> 1]), x[k + 2], x[k + 3], make_tw(t12[(k >> 1) + 1]), mc,
                                               rs.nofold(k, 1), rs.nofold(k + 2, 1));
                 if (k == 4) {   // the first half of this stage's twiddles is dead: the next stage's take their registers
                     NTT16_FENCE();
@@ -1000,7 +974,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 #pragma unroll
             for (int g4 = 0; g4 < 4; g4++) {  // stage 11
                 const Tw t = make_tw(t11[g4]);
-                bfly2<true, false, false, BK>(x[4 * g4], x[4 * g4 + 2], t, x[4 * g4 + 1], x[4 * g4 + 3], t, mc, rs.nofold(4 * g4, 2),
+                bfly2<true, false, false, KIND>(x[4 * g4], x[4 * g4 + 2], t, x[4 * g4 + 1], x[4 * g4 + 3], t, mc, rs.nofold(4 * g4, 2),
                                               rs.nofold(4 * g4 + 1, 2));
             }
             NTT16_STAMP(1);
@@ -1025,7 +999,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
             rs = GsRanges();
 #pragma unroll
             for (int k = 0; k < 16; k += 4)
-                bfly2<true, false, false, BK>(x[k], x[k + 1], make_tw(t10[k >> 1]), x[k + 2], x[k + 3], make_tw(t10[(k >> 1) + 1]), mc,
+                bfly2<true, false, false, KIND>(x[k], x[k + 1], make_tw(t10[k >> 1]), x[k + 2], x[k + 3], make_tw(t10[(k >> 1) + 1]), mc,
                                               rs.nofold(k, 1), rs.nofold(k + 2, 1));
             NTT16_LOAD3(t8, 1);
             NTT16_LOAD3(t7, 0);
@@ -1034,7 +1008,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 #pragma unroll
             for (int mm = 0; mm < 8; mm += 2) {
                 const int k0 = bfly_lo(mm, 2), k1 = bfly_lo(mm + 1, 2);
-                bfly2<true, false, false, BK>(x[k0], x[k0 + 2], make_tw(t9[k0 >> 2]), x[k1], x[k1 + 2], make_tw(t9[k1 >> 2]), mc, rs.nofold(k0, 2),
+                bfly2<true, false, false, KIND>(x[k0], x[k0 + 2], make_tw(t9[k0 >> 2]), x[k1], x[k1 + 2], make_tw(t9[k1 >> 2]), mc, rs.nofold(k0, 2),
                                               rs.nofold(k1, 2));
             }
             NTT16_FENCE();
@@ -1042,7 +1016,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
 #pragma unroll
             for (int mm = 0; mm < 8; mm += 2) {
                 const int k0 = bfly_lo(mm, 4), k1 = bfly_lo(mm + 1, 4);
-                bfly2<true, false, false, BK>(x[k0], x[k0 + 4], make_tw(t8[k0 >> 3]), x[k1], x[k1 + 4], make_tw(t8[k1 >> 3]), mc, rs.nofold(k0, 4),
+                bfly2<true, false, false, KIND>(x[k0], x[k0 + 4], make_tw(t8[k0 >> 3]), x[k1], x[k1 + 4], make_tw(t8[k1 >> 3]), mc, rs.nofold(k0, 4),
                                               rs.nofold(k1, 4));
             }
             rs.stage(4);
@@ -1050,7 +1024,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                 const Tw t = make_tw(t7[0]);
 #pragma unroll
                 for (int k = 0; k < 8; k += 2)
-                    bfly2<true, false, false, BK>(x[k], x[k + 8], t, x[k + 1], x[k + 9], t, mc, rs.nofold(k, 8), rs.nofold(k + 1, 8));
+                    bfly2<true, false, false, KIND>(x[k], x[k + 8], t, x[k + 1], x[k + 9], t, mc, rs.nofold(k, 8), rs.nofold(k + 1, 8));
             }
 #pragma unroll
             for (int k = 0; k < 16; k++) p3[4 * k + 2 * (k >> 3)] = x[k];
@@ -1069,7 +1043,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                     const int k0 = bfly_lo(mm, d), k1 = bfly_lo(mm + 1, d);
                     const Tw t0 = make_tw(NTT16_TWL(G::W << sb, (w << sb) + ((u32)k0 >> (4 - sb))));
                     const Tw t1 = make_tw(NTT16_TWL(G::W << sb, (w << sb) + ((u32)k1 >> (4 - sb))));
-                    bfly2<true, true, false, BK>(x[k0], x[k0 + d], t0, x[k1], x[k1 + d], t1, mc, rs.nofold(k0, d), rs.nofold(k1, d));
+                    bfly2<true, true, false, KIND>(x[k0], x[k0 + d], t0, x[k1], x[k1 + d], t1, mc, rs.nofold(k0, d), rs.nofold(k1, d));
                 }
                 rs.stage(d);
             }
@@ -1098,7 +1072,7 @@ __global__ void __launch_bounds__(Geo<LOGNS>::T, 4) ntt16_kernel_t(Args a)
                     const Tw t = make_tw(NTT16_TWL(1u << s, (u32)r >> (LOGR - s)));
 #pragma unroll
                     for (int c = 0; c < (int)CPT; c++)
-                        bfly<true, true, NTT16_INV_H2 != 0, BK>(x[CPT * r + c], x[CPT * (r + d) + c], t, mc, rs.nofold(CPT * r + c, CPT * d));
+                        bfly<true, true, true, KIND>(x[CPT * r + c], x[CPT * (r + d) + c], t, mc, rs.nofold(CPT * r + c, CPT * d));
                 }
                 rs.stage(CPT * d);
             }

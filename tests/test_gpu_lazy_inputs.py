@@ -426,7 +426,7 @@ EB_CASES = [("default", kind, L) for kind in ("barrett", "fold") for L in (2, 6,
 @functools.lru_cache(maxsize=None)
 def _expand_both_case(chain, L):
     """(o, x, y, wx, wy): X and Y [1][2][L][N] over [0, 4q) with the outer stage pending and their conversions by the oracle,
-    shared by the kinds and by both skip_q"""
+    shared by the kinds"""
     N = 16384
     o = _oracle(chain, N, L)
     qs, ps = _mods(o)
@@ -439,10 +439,10 @@ def _expand_both_case(chain, L):
     return o, x, y, wx, wy
 
 
-@pytest.mark.parametrize("skip_q", [0, 1])
+@pytest.mark.parametrize("skip_q", [1])   # (a folded context's X always has its Q limbs in place: the only folded form built)
 @pytest.mark.parametrize("chain,kind,L", EB_CASES, ids=[_kind_id(c, k, "%d" % L) for c, k, L in EB_CASES])
 def test_expand_both_folded(chain, kind, L, skip_q):
-    """expand_both_kernel<true, L, kind, SKIPQ> at kind barrett and at kind fold.  X and Y over [0, 4q)
+    """expand_both_kernel<true, L, kind, true> at kind barrett and at kind fold.  X and Y over [0, 4q)
     with the outer stage pending; every output limb leaves through fold_store; skip_q: the Q limbs of X's slots keep the fill
     pattern"""
     N = 16384
@@ -455,6 +455,17 @@ def test_expand_both_folded(chain, kind, L, skip_q):
         assert (got["out"][0, c, :first] == FILL).all(), "X%d: a Q limb was written" % c
         _check_fold_store(o, got["out"][0, c, first:], wx[c][first:], first, "X%d" % c, canonical_u=False)
         _check_fold_store(o, got["out"][0, 2 + c], wy[c], 0, "Y%d" % c, canonical_u=False)
+
+
+def test_expand_both_folded_without_skip_q_is_refused():
+    """fold = 1 with skip_q = 0 is no combination of the library's (plan.fold implies plan.xq_reuse, and every caller passes
+    x.q_ready = plan.xq_reuse): launch_expand_pair returns false and launches nothing, and the program reports that with status 2"""
+    N, L = 16384, 1
+    o = _oracle("default", N, L)
+    z = np.zeros((1, 2, L, N), dtype=np.uint64)
+    with pytest.raises(AssertionError, match=r"(?s)status 2\b.*refused: expand_both: a combination the launcher is not built for"):
+        _run("expand_both", o, {"x": z, "y": z}, {"out": (1, 4, o.M, N)}, n_outer=1, fold=1, skip_q=0)
+    assert not _stopped
 
 
 # every (chain, N, L) of the cases above that name a kind, with the kind its plan selects (tests/test_reduction_kinds.py)

@@ -117,6 +117,22 @@ def test_what_is_still_unlaunched_is_listed_as_unreachable_with_a_reason():
     assert not missing, "unlaunched and not listed as unreachable: %s" % missing
 
 
+def test_the_unreachable_kernels_are_not_built():
+    """removed.txt: the 19 kernels of unreachable.txt and the six expand_both_kernel<true, L, K, false> that only tests/lazy_inputs
+    selected.  The device listings of this checkout (no GPU: hipcc cross-compiles) hold none of them, and exactly the rest of the
+    two families"""
+    import subprocess
+    import isa_compare
+    removed = set(_lines("removed.txt"))
+    assert len(removed) == 25 and set(_reasons()) <= removed
+    subprocess.check_call(["make", "-j2", "-C", ic.CSRC, "build/kernels_convert.s", "build/kernels_ntt_fast.s"], stdout=subprocess.DEVNULL,
+                          stderr=subprocess.DEVNULL)
+    names = [isa_compare.short(k) for f in ("kernels_convert", "kernels_ntt_fast") for k in ic.built_kernels(os.path.join(ic.CSRC, "build", f + ".s"))]
+    assert not removed & set(names)
+    count = lambda fam: sum(n.startswith(fam + "<") for n in names)
+    assert count("expand_both_kernel") == 63 and count("ntt_fast_kernel") == 11
+
+
 def test_every_kernel_the_suite_did_not_launch_has_a_case_or_a_reason():
     """tests/test_gpu_instantiations.py names one instantiation per case: together with unreachable.txt its rows are exactly the
     kernels of before_unlaunched.txt, none twice, and each row says which dispatcher selects it"""

@@ -19,7 +19,7 @@ table counts the blocks per form -- select (NTT16_GS1 / GS1H, 20 / 19), folding 
 (NTT16_GSN1 / GSN1H, 16 / 15) -- with their sizes; a fold-kind kernel must hold the non-folding blocks of the static range table
 (28 of 104 in a 2^13 slice, 31 of 112 in a 2^14 slice: tools/gen_ntt16_bfly.py) and no select block, a Barrett-kind kernel select
 blocks only.  The rows of the fold-kind transforms (not the tensor launch's, which was a fold-kind kernel before its butterflies
-were) are printed under the heading "fold" and begin with "fold:".  A listing built with -DNTT16_FOLD_BFLY=0 has none of this."""
+were) are printed under the heading "fold" and begin with "fold:"."""
 import re
 import subprocess
 import sys
@@ -177,7 +177,6 @@ def main():
         transform = 'ntt16_kernel_t' in name   # (a harness kernel holds one block of whatever kind it was written for)
         if transform and is_fold and 'ArithKindE2' not in name:
             complaints.append((0, "folding blocks in a Barrett-kind kernel"))
-        # (-DNTT16_FOLD_BFLY=0 leaves the tensor launch's fold-kind kernels on select blocks: they count as Barrett-kind here)
         inv = [(b, inverse_form(b)) for b in blocks if inverse_form(b)]
         inv_bad = [c for b, f in inv for c in check_inverse(b, f)]
         if inv:
